@@ -29,6 +29,12 @@ Set-up before the W warm-up steps includes `--prewarm-steps` (64) untimed steps:
 construction needs milliseconds of work to reach its sustained clock -- at a 0.27 ms step (one rank's shard of 8) W = 2 /
 K = 20 measured 0.311 ms per step without it and 0.266 with it (K = 200: 0.265 / 0.257).  The timed region is unchanged:
 exactly K steps between two synchronisations (+ barriers), max over ranks.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps and a short line (`metric`, `value`, `unit`,
+`ms_per_step`, `higher_is_better`, `dtype`, `config`, ...).  Everything else above -- result digests and shard checksums,
+`roofline`, `cpu_baseline`, recall, the host-transfer figure, the exchange's own cost and every extra leg -- runs only with
+`--full`.  `--dump-outputs DIR` writes what the last timed step handed its caller (the [B, k] distances and ids) as .npy files;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -70,9 +76,14 @@ def parse():
     p.add_argument('--data', choices=['lowrank', 'uniform'], default='lowrank',
                    help='database / query distribution (SURVEY.md section 8d): lowrank = rank-16 (rank-64 above 128-d) latent Gaussian '
                         '+ noise; uniform = U[0,1)^D, the reference\'s own test distribution (tests/test_pq_bind.py:19)')
+    p.add_argument('--full', action='store_true',
+                   help='besides the headline: result digests, roofline, CPU baseline, recall, host-transfer and exchange figures and the '
+                        'extra legs (--legs); a plain run only sets up, warms up, times the steps and prints the line')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write the last timed step\'s result (distances float32, ids float64, [batch, k]) to DIR/<name>.npy')
     p.add_argument('--legs', default='auto',
-                   help='comma list of extra legs (rank 0, N=1, never `value`): rerank, graph, ivf, facade, uniform, c2, c4, c5, m32, k50; "none"; "auto" = all '
-                        'of them for the default workload, rerank + ivf otherwise')
+                   help='with --full: comma list of extra legs (rank 0, N=1, never `value`): rerank, graph, ivf, facade, uniform, c2, c4, c5, m32, k50; '
+                        '"none"; "auto" = all of them for the default workload, rerank + ivf otherwise')
     p.add_argument('--metric', choices=['euclidean', 'cosine', 'inner_product'], default='euclidean',
                    help="BASELINE config 2/3: euclidean; config 4 (10M x 768, m=64, batch 256): cosine")
     p.add_argument('--streams', type=int, choices=list(range(0, 9)), default=0,
@@ -135,6 +146,26 @@ def sub_run(cmd, timeout_s):
         return {'error': f'timeout after {timeout_s} s'}
 
 
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: at most this much in all (.npy headers included)
+
+
+def dump_outputs(dirname: str, result) -> None:
+    """``--dump-outputs``: what a caller of the timed path receives from its last step -- ``(dists [B, k], ids [B, k])`` -- as
+    ``distances.npy`` (float32) and ``ids.npy`` (float64: exact below 2^53).  Above the size limit a fixed, seeded sample of the
+    query rows is written instead, its row numbers beside it (``query_rows.npy``)."""
+    os.makedirs(dirname, exist_ok=True)
+    d = result[0].to(torch.float32).cpu().numpy()
+    i = result[1].to(torch.float64).cpu().numpy()
+    row_bytes = d.shape[1] * (4 + 8)
+    if d.shape[0] * row_bytes > DUMP_LIMIT_BYTES - 4096:  # (4 KB for the files' headers)
+        n = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)
+        rows = np.sort(np.random.RandomState(0).choice(d.shape[0], n, replace=False))
+        d, i = d[rows], i[rows]
+        np.save(os.path.join(dirname, 'query_rows.npy'), rows.astype(np.float64))
+    np.save(os.path.join(dirname, 'distances.npy'), d)
+    np.save(os.path.join(dirname, 'ids.npy'), i)
+
+
 def free_port() -> int:
     import socket
 
@@ -175,15 +206,15 @@ def main():
         legs.remove('rerank')
     if args.ivf_cells <= 1 and 'ivf' in legs:
         legs.remove('ivf')
-    if world > 1:
-        legs = []  # (the extra legs are single-GPU figures)
+    if world > 1 or not args.full:
+        legs = []  # (the extra legs are single-GPU figures, and --full ones)
     # ---- the other BASELINE configurations and the reference's own test distribution, as sub-runs (rank 0, N=1), run BEFORE this
     # process creates its own GPU context (a second resident process costs the sub-run's kernels 25-40 %) ------------
     sub = {}
     if rank == 0 and world == 1:
         me = os.path.join(ROOT, 'bench.py')
         # (the legs' batches alternate between two streams, as the multi-GPU runs do; each leg's own config says so)
-        common = ['--legs', 'none', '--gpus', '1', '--streams', '2', '--query-batches', '2']
+        common = ['--full', '--legs', 'none', '--gpus', '1', '--streams', '2', '--query-batches', '2']
         if 'c2' in legs:  # config 2: 1M x 128, m=16, L2, batch 1024
             sub['c2'] = sub_run([me, '--rows', '1000000', '--steps', '40', '--warmup', '10'] + common, 240)
         if 'c4' in legs:  # config 4: 10M x 768, m=64, cosine, batch 256
@@ -267,7 +298,7 @@ def main():
     # ---- build this rank's shard --------------------------------------------------------------------
     lo, hi = shard_range(N, world, rank)
     n_local = hi - lo
-    keep_vectors = 'rerank' in legs or world > 1 and not args.no_rerank
+    keep_vectors = 'rerank' in legs or world > 1 and args.full and not args.no_rerank
     index = PQFlatGpuIndex(dim=D, metric=metric, pq_codec=codec, initial_size=max(n_local, 64),
                            rerank=keep_vectors, skewed=(args.layout == 'skewed'))
     t0 = time.time()
@@ -385,6 +416,41 @@ def main():
         elapsed = coll_max(elapsed)
     ms_per_step = elapsed / args.steps * 1e3
     qps = B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[(args.steps - 1) % NB])  # (the merged result the last timed step handed over)
+
+    gathering_cfg = use_dist and (world > 1 or bool(os.environ.get('ANNLITE_FORCE_GATHER')))
+    head = {
+        'metric': 'queries/sec', 'value': qps, 'unit': 'queries/s', 'n_gpus': world, 'gpus_arg': args.gpus, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'strong',
+        'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic' if args.data == 'lowrank' else 'synthetic (uniform)',
+        'config': {
+            'workload': f'{N} x {D}-dim float32, PQ m={M} ks={Ks}, {args.metric}, batch {B}, k={k}, exhaustive ADC scan + exact top-k',
+            'rows_total': N, 'rows_per_gpu': n_local, 'batch': B, 'k': k, 'parallelism': f'row-shard x{world}',
+            'codes_layout': args.layout,
+            # what torch.distributed itself reports (one process per GPU over RCCL); 1 / None without a process group
+            'n_ranks': dist.get_world_size() if use_dist else 1,
+            'backend': (dist.get_backend() + (' (RCCL)' if dist.get_backend() == 'nccl' else ' (collectives through host memory; ranks may share a device)')) if use_dist else None,
+            # independent batches alternate between this many HIP streams (each batch's kernels in order on its own)
+            'streams': n_streams,
+            'query_batches': NB,  # distinct batches the timed steps rotate through
+            'prewarm_steps': args.prewarm_steps,  # untimed set-up steps BEFORE the W warm-up steps (clock ramp)
+            # N > 1: every rank seeds from 1 / N of the single-GPU seed rows and the ranks all-gather their seeds' k smallest
+            # bounds before the scan (sharded.py); seed_peers_emulated: --emulate-seed-peers (one rank standing for P)
+            'seed_exchange': bool(gathering_cfg and sharded.seed_exchange and index.split_supported(queries, k)),
+            'seed_rows': sharded.seed_rows() if gathering_cfg else None,
+            'seed_peers_emulated': n_emulated,
+        },
+    }
+    if not args.full:  # a plain run: the headline and nothing else
+        if rank == 0:
+            rec = dict(head, host_enqueue_ms_per_step=host_enqueue_ms, setup={'train_s': train_s, 'index_s': index_s},
+                       summary={'main': {'qps': round(qps), 'ms': round(ms_per_step, 4), 'n': world}})
+            print(json.dumps(rec))
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
     for j in range(NB):  # (fewer timed steps than batches: the rest untimed, so that every batch has a result to check)
         if outs[j] is None:
             outs[j] = sharded.search_batch(q_sets[j], limit=k)
@@ -882,7 +948,6 @@ def main():
             'batches_checked': NB, 'batches_differing': bad_batches,
         }
 
-    gathering_cfg = use_dist and (world > 1 or bool(os.environ.get('ANNLITE_FORCE_GATHER')))
     if rank == 0:
         # The scan does not stream its algorithmic bytes from HBM (every code row is shared by the 16 / 32 queries of a
         # tile and stays in L2): its roof is the LDS look-up rate.  One ds_read_b128 (4 LDS cycles per wave64) serves
@@ -935,26 +1000,7 @@ def main():
             'hbm': None if traffic is None else {'bytes_per_launch': traffic, 'frac': traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
         }
         rec = {
-            'metric': 'queries/sec', 'value': qps, 'unit': 'queries/s', 'n_gpus': world, 'gpus_arg': args.gpus, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True, 'scaling': 'strong',
-            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic' if args.data == 'lowrank' else 'synthetic (uniform)',
-            'config': {
-                'workload': f'{N} x {D}-dim float32, PQ m={M} ks={Ks}, {args.metric}, batch {B}, k={k}, exhaustive ADC scan + exact top-k',
-                'rows_total': N, 'rows_per_gpu': n_local, 'batch': B, 'k': k, 'parallelism': f'row-shard x{world}',
-                'codes_layout': args.layout,
-                # what torch.distributed itself reports (one process per GPU over RCCL); 1 / None without a process group
-                'n_ranks': dist.get_world_size() if use_dist else 1,
-                'backend': (dist.get_backend() + (' (RCCL)' if dist.get_backend() == 'nccl' else ' (collectives through host memory; ranks may share a device)')) if use_dist else None,
-                # independent batches alternate between this many HIP streams (each batch's kernels in order on its own)
-                'streams': n_streams,
-                'query_batches': NB,  # distinct batches the timed steps rotate through
-                'prewarm_steps': args.prewarm_steps,  # untimed set-up steps BEFORE the W warm-up steps (clock ramp)
-                # N > 1: every rank seeds from 1 / N of the single-GPU seed rows and the ranks all-gather their seeds' k smallest
-                # bounds before the scan (sharded.py); seed_peers_emulated: --emulate-seed-peers (one rank standing for P)
-                'seed_exchange': bool(gathering_cfg and sharded.seed_exchange and index.split_supported(queries, k)),
-                'seed_rows': sharded.seed_rows() if gathering_cfg else None,
-                'seed_peers_emulated': n_emulated,
-            },
+            **head,
             # N > 1: every rank's own clock over the K steps, its scan kernel (HIP events) and the exchange alone (one packed
             # all-gather + merge, 20 back to back) -- a first multi-GPU run says where its time went
             'per_rank': per_rank,

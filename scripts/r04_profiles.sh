@@ -7,12 +7,12 @@ cd "$(dirname "$0")/.."; ROOT=$PWD; OUT=gpurun_out/r04p; mkdir -p $OUT; export T
 PARTS=${@:-bench stats pmc10m pmcshard pmcc4 small shards}
 for part in $PARTS; do case $part in
 bench)
-  timeout 900 python bench.py > $OUT/bench_10m_n1.json 2>$OUT/bench_10m_n1.err;;
+  timeout 900 python bench.py --full > $OUT/bench_10m_n1.json 2>$OUT/bench_10m_n1.err;;
 stats)
-  rocprofv3 --kernel-trace --stats -f csv -d $ROOT/$OUT/bench_trace -- python bench.py --legs none --cpu-queries 0 --recall-queries 0 > $OUT/bench_10m_n1_under_rocprof.json 2>$OUT/bench_trace.log
+  rocprofv3 --kernel-trace --stats -f csv -d $ROOT/$OUT/bench_trace -- python bench.py --full --legs none --cpu-queries 0 --recall-queries 0 > $OUT/bench_10m_n1_under_rocprof.json 2>$OUT/bench_trace.log
   python - <<PY > $OUT/bench_10m_n1_rocprof_kernel_stats.txt
 import csv,glob
-print('command: rocprofv3 --kernel-trace --stats -- python bench.py --legs none --cpu-queries 0 --recall-queries 0   (the default workload: 64 set-up + 20 warm-up + 200 timed steps + the host-transfer and roofline legs)')
+print('command: rocprofv3 --kernel-trace --stats -- python bench.py --full --legs none --cpu-queries 0 --recall-queries 0   (the default workload: 64 set-up + 20 warm-up + 200 timed steps + the host-transfer and roofline legs)')
 print([l for l in open('$OUT/bench_10m_n1_under_rocprof.json') if l.startswith('{')][-1].strip()[:600])
 for f in glob.glob('$OUT/bench_trace/**/*kernel_stats.csv', recursive=True):
     for r in csv.DictReader(open(f)):
@@ -49,8 +49,8 @@ PY
 shards)
   for rows in 10000000 5000000 2500000 1250000; do
     A="--rows $rows --legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 200 --warmup 20"
-    for s in 1 2; do timeout 300 python bench.py $A --streams $s > $OUT/bench_shard_${rows}_s${s}_200steps.json 2>/dev/null; done
-    ANNLITE_FORCE_GATHER=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 $A --streams 2 > $OUT/bench_shard_${rows}_forced_gather_200steps.json 2>/dev/null
+    for s in 1 2; do timeout 300 python bench.py --full $A --streams $s > $OUT/bench_shard_${rows}_s${s}_200steps.json 2>/dev/null; done
+    ANNLITE_FORCE_GATHER=1 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 $A --streams 2 > $OUT/bench_shard_${rows}_forced_gather_200steps.json 2>/dev/null
   done
   python - <<'PY' | tee gpurun_out/r04p/shard_table.txt
 import json,glob

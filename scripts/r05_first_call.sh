@@ -5,16 +5,16 @@
 set -u
 cd "$(dirname "$0")/.."; OUT=gpurun_out/r05first; mkdir -p $OUT
 timeout 260 python -m pytest tests -x -q -m gpu > $OUT/pytest_gpu.txt 2>&1; echo "suite rc=$?"; tail -3 $OUT/pytest_gpu.txt
-timeout 240 python bench.py > $OUT/bench_10m_n1.json 2>$OUT/bench_10m_n1.err; echo "bench rc=$?"
+timeout 240 python bench.py --full > $OUT/bench_10m_n1.json 2>$OUT/bench_10m_n1.err; echo "bench rc=$?"
 for rows in 10000000 1250000; do
   A="--rows $rows --legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 200 --warmup 20"
-  timeout 120 python bench.py $A --streams 2 > $OUT/bench_shard_${rows}_s2.json 2>/dev/null
-  ANNLITE_FORCE_GATHER=1 timeout 120 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 $A --streams 2 > $OUT/bench_shard_${rows}_forced_gather.json 2>/dev/null
+  timeout 120 python bench.py --full $A --streams 2 > $OUT/bench_shard_${rows}_s2.json 2>/dev/null
+  ANNLITE_FORCE_GATHER=1 timeout 120 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 $A --streams 2 > $OUT/bench_shard_${rows}_forced_gather.json 2>/dev/null
 done
 # slice-per-XCD map for M = 16 (what M = 64 got in round 4): A/B on this box, 10M and 1.25M rows, one stream
 for rows in 10000000 1250000; do
   for map in 0 1; do
-    ANNLITE_Q8_MAP=$map timeout 120 python bench.py --rows $rows --legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 100 --warmup 20 > $OUT/bench_map${map}_${rows}.json 2>/dev/null
+    ANNLITE_Q8_MAP=$map timeout 120 python bench.py --full --rows $rows --legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 100 --warmup 20 > $OUT/bench_map${map}_${rows}.json 2>/dev/null
   done
 done
 P="--rows 10000000 --data lowrank --fused --valid --iters 8"

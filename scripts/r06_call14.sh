@@ -16,7 +16,7 @@ for k in d:
     if k.startswith('hnsw_') or k.startswith('exhaustive'):
         print(' ', k, d[k])
 PY
-timeout 600 python bench.py --legs rerank --cpu-queries 0 --steps 40 --warmup 5 2>/dev/null | python -c "
+timeout 600 python bench.py --full --legs rerank --cpu-queries 0 --steps 40 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); r = d['rerank']
 print('main %.0f q/s; rerank leg: %9.0f q/s at recall@10 %.4f' % (d['value'], r['value'], r['recall_at_10']))" | tee $OUT/rerank_leg.txt

@@ -2,7 +2,7 @@
 # Round 6, call 17: bench.py's new `graph` leg (HNSW-over-PQ over the headline's 10M rows, built on the GPU) beside the re-rank leg.
 set -u
 cd "$(dirname "$0")/.."; OUT=gpurun_out/r06c17; mkdir -p $OUT
-timeout 900 python bench.py --legs rerank,graph,ivf --cpu-queries 0 --steps 40 --warmup 5 > $OUT/bench_graph_leg.json 2> $OUT/bench_graph_leg.err
+timeout 900 python bench.py --full --legs rerank,graph,ivf --cpu-queries 0 --steps 40 --warmup 5 > $OUT/bench_graph_leg.json 2> $OUT/bench_graph_leg.err
 tail -3 $OUT/bench_graph_leg.err
 python - <<'PY'
 import json

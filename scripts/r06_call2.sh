@@ -8,12 +8,12 @@ timeout 900 python -m pytest tests -q -m gpu --maxfail=8 --deselect tests/test_s
 A="--legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 200 --warmup 20"
 for mode in mfma exact; do
   E=""; [ $mode = exact ] && E="ANNLITE_NO_MFMA_SEED=1"
-  env $E timeout 120 python bench.py --rows 1250000 $A --streams 2 > $OUT/bench_shard_1250000_s2_$mode.json 2>/dev/null
-  env $E ANNLITE_FORCE_GATHER=1 timeout 120 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --rows 1250000 $A --streams 2 > $OUT/bench_shard_1250000_forced_gather_$mode.json 2>/dev/null
-  env $E timeout 120 python bench.py --rows 1000000 $A --streams 2 > $OUT/bench_c2_s2_$mode.json 2>/dev/null
-  env $E timeout 120 python bench.py --rows 1000000 $A --streams 1 > $OUT/bench_c2_s1_$mode.json 2>/dev/null
-  env $E timeout 200 python bench.py --legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 100 --warmup 10 > $OUT/bench_10m_$mode.json 2>/dev/null
-  env $E timeout 200 python bench.py --k 50 --legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 50 --warmup 10 --streams 2 > $OUT/bench_10m_k50_$mode.json 2>/dev/null
+  env $E timeout 120 python bench.py --full --rows 1250000 $A --streams 2 > $OUT/bench_shard_1250000_s2_$mode.json 2>/dev/null
+  env $E ANNLITE_FORCE_GATHER=1 timeout 120 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --rows 1250000 $A --streams 2 > $OUT/bench_shard_1250000_forced_gather_$mode.json 2>/dev/null
+  env $E timeout 120 python bench.py --full --rows 1000000 $A --streams 2 > $OUT/bench_c2_s2_$mode.json 2>/dev/null
+  env $E timeout 120 python bench.py --full --rows 1000000 $A --streams 1 > $OUT/bench_c2_s1_$mode.json 2>/dev/null
+  env $E timeout 200 python bench.py --full --legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 100 --warmup 10 > $OUT/bench_10m_$mode.json 2>/dev/null
+  env $E timeout 200 python bench.py --full --k 50 --legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 50 --warmup 10 --streams 2 > $OUT/bench_10m_k50_$mode.json 2>/dev/null
 done
 python - <<'PY'
 import json, glob

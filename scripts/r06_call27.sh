@@ -11,7 +11,7 @@ for k in d:
     if k.startswith('hnsw_') or k.startswith('exhaustive'):
         print(' ', k, d[k])
 PY
-timeout 600 python bench.py --legs graph --cpu-queries 0 --steps 40 --warmup 5 2>/dev/null | python -c "
+timeout 600 python bench.py --full --legs graph --cpu-queries 0 --steps 40 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('graph leg', d['graph'])"

@@ -11,6 +11,6 @@ for shape in "--m 128 --dsub 1" "--m 64 --dsub 2"; do
   echo "== $shape"; cat $OUT/scan_1m_${tag}_plain.txt
 done
 A="--legs none --cpu-queries 0 --recall-queries 0 --no-rerank --steps 200 --warmup 20"
-ANNLITE_FORCE_GATHER=1 timeout 120 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --rows 1250000 $A --streams 2 2>/dev/null | python -c "
+ANNLITE_FORCE_GATHER=1 timeout 120 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --rows 1250000 $A --streams 2 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('shard forced gather: ms/step %.4f host_enqueue %.4f exchange_ms %s sha %s' % (d['ms_per_step'], d['host_enqueue_ms_per_step'], d.get('exchange_ms'), d['result_sha256'][:8]))" | tee $OUT/shard_forced_gather.txt

@@ -21,4 +21,4 @@ print('ANNLITE_Q8_MAP=$v', {c: round(sum(v)/len(v), 1) for c, v in acc.items()},
 PY
   rm -rf $OUT/pmc_$v
 done
-timeout 600 python bench.py --legs ivf --cpu-queries 0 2>/dev/null | tail -c 400 | tee $OUT/bench_ivf_leg_tail.txt
+timeout 600 python bench.py --full --legs ivf --cpu-queries 0 2>/dev/null | tail -c 400 | tee $OUT/bench_ivf_leg_tail.txt

@@ -7,4 +7,4 @@ timeout 600 python scripts/bench_ivf_bytes.py --probes 8,16,32 --reps 30 2>&1 | 
 import sys, json
 for l in sys.stdin:
     r = json.loads(l); print(r['n_probe'], r['bytes'], r['paths_bit_equal'], r['stages'])" | tee $OUT/ivf_dpp_select.txt
-timeout 600 python bench.py --legs ivf --cpu-queries 0 2>/dev/null | tail -c 500 | tee $OUT/bench_ivf_leg_tail.txt
+timeout 600 python bench.py --full --legs ivf --cpu-queries 0 2>/dev/null | tail -c 500 | tee $OUT/bench_ivf_leg_tail.txt

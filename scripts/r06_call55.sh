@@ -5,7 +5,7 @@ set -u
 cd "$(dirname "$0")/.."; OUT=gpurun_out/r06c55; mkdir -p $OUT
 for f in 4 2 1; do
   echo "ANNLITE_IVF_CAND_RANK=$f" | tee -a $OUT/ivf_cand_rank.txt
-  ANNLITE_IVF_CAND_RANK=$f timeout 600 python bench.py --legs rerank,ivf --cpu-queries 0 2>/dev/null | tail -1 | python -c "
+  ANNLITE_IVF_CAND_RANK=$f timeout 600 python bench.py --full --legs rerank,ivf --cpu-queries 0 2>/dev/null | tail -1 | python -c "
 import sys, json
 r = json.loads(sys.stdin.read()); print(json.dumps(r['ivf'].get('rerank16'))); print(json.dumps(r['ivf'].get('rerank')))" | tee -a $OUT/ivf_cand_rank.txt
 done

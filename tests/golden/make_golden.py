@@ -19,6 +19,9 @@ Each case stores, for a (M, dsub, Ks) shape of SURVEY.md section 8c:
   PQIndex  pqindex_d / pqindex_i  (limit=10, scans all capacity rows) (pq_index.py:29-56)
   Hnsw     hnsw_{metric}_d / _i   HnswIndex(pq_codec).search          (hnsw/index.py:139-167)
   math     l2norm_q, topk_d (math.top_k values of adist[0])           (math.py:6-18, 94-120)
+
+`reference/answers.npz` holds the reference's answers behind tests/test_oracle_vs_reference.py and the reference's HNSW recall
+in tests/test_graph_host.py, so that those tests also run where the reference cannot (`make_golden.py reference` rewrites it).
 """
 import os
 import sys
@@ -187,6 +190,36 @@ def make_cells_case(ref, name='cells_m16_d64', M=16, dsub=4, Ks=256, N=4000, B=8
     print('%-16s -> %s  (%.1f KB)' % (name, os.path.relpath(path, ROOT), os.path.getsize(path) / 1024))
 
 
+def make_reference_answers(ref):
+    """tests/golden/reference/answers.npz: the reference's answers behind tests/test_oracle_vs_reference.py (large arrays as
+    digests, codes / cell ids as their differences from the oracle's) and the reference's recall in tests/test_graph_host.py --
+    what those tests check against where the reference cannot run."""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import pq_oracle
+    import test_graph_host as th
+    import test_oracle_vs_reference as tr
+
+    pq_oracle.build()
+    out = {}
+
+    def put(prefix, answers, own=None):
+        for key, val in answers.items():
+            out.update(tr.to_stored(prefix + '/' + key, val, None if own is None else own.get(key)))
+
+    for case in tr.LUT_CASES:
+        cb, q, x = tr.lut_inputs(*case)
+        put('luts_%d_%d_%d_%d_%d' % case, tr.lut_answers(ref, *case), {'codes': pq_oracle.encode_c(x, cb)})
+    cent, x, q, cb, k = tr.cells_inputs()
+    put('cells', tr.cells_answers(ref, pq_oracle), {'vq_cells': pq_oracle.assign_cells(x, cent)})
+    put('filter', tr.filter_answers(ref))
+    put('filter_fuzz', tr.fuzz_answers(ref))
+    put('hnsw', {'recall': np.array(th.reference_recall(ref))})
+    path = os.path.join(HERE, 'reference', 'answers.npz')
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.savez_compressed(path, **out)
+    print('%-16s -> %s  (%.1f KB)' % ('reference', os.path.relpath(path, ROOT), os.path.getsize(path) / 1024))
+
+
 def main():
     ref = ref_import.load()
     only = set(sys.argv[1:])  # (no arguments: every fixture; names: only those -- e.g. a case added later)
@@ -195,6 +228,8 @@ def main():
             make_case(ref, name, *spec)
     if not only or 'cells' in only:
         make_cells_case(ref)
+    if not only or 'reference' in only:
+        make_reference_answers(ref)
 
 
 if __name__ == '__main__':

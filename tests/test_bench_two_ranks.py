@@ -18,7 +18,7 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-WORKLOAD = ['--rows', '300000', '--steps', '6', '--warmup', '2', '--prewarm-steps', '4', '--recall-queries', '32',
+WORKLOAD = ['--full', '--rows', '300000', '--steps', '6', '--warmup', '2', '--prewarm-steps', '4', '--recall-queries', '32',
             '--cpu-queries', '0', '--legs', 'none']
 
 
@@ -74,12 +74,38 @@ def test_single_gpu_line_ends_with_the_summary(single):
     assert s['main']['n'] == 1 and s['main']['sha'] == single['result_sha256'][:8] and s['main']['qps'] > 0
 
 
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path, single):
+    """Without --full the line is the headline alone (same contract fields, none of the --full figures), and --dump-outputs writes
+    what the last timed step handed its caller: the very result the --full line digests for that step's batch."""
+    import hashlib
+
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    out = tmp_path / 'out'
+    plain = [a for a in WORKLOAD if a != '--full']
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--dump-outputs', str(out)] + plain,
+                       capture_output=True, text=True, env=env, timeout=900, cwd=str(tmp_path))
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    rec = _line(r.stdout)
+    for key in ('metric', 'unit', 'higher_is_better', 'dtype', 'steps', 'warmup', 'n_gpus'):
+        assert rec[key] == single[key], key
+    assert rec['value'] > 0 and rec['ms_per_step'] > 0 and rec['config'] == single['config']
+    for key in ('roofline', 'cpu_baseline', 'recall_at_10', 'rerank', 'result_sha256', 'with_host_transfer'):
+        assert key not in rec, key
+    d, i = np.load(out / 'distances.npy'), np.load(out / 'ids.npy')
+    assert d.dtype == np.float32 and i.dtype == np.float64 and d.shape == i.shape == (rec['config']['batch'], rec['config']['k'])
+    last_batch = (rec['steps'] - 1) % rec['config']['query_batches']
+    blob = i.astype(np.int64).tobytes() + d.view(np.uint32).tobytes()
+    assert hashlib.sha256(blob).hexdigest()[:16] == single['result_sha256_per_batch'][last_batch]
+
+
 def test_bench_graph_leg(tmp_path):
     """The `graph` leg (round 6): HNSW-over-PQ over the bench's own rows -- level 0 built on the GPU, pair walk, fused exact re-rank --
     next to the exhaustive scan's line: present, timed, recall measured against the same brute-force truth, and in the summary."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
-    args = ['--rows', '300000', '--steps', '6', '--warmup', '2', '--prewarm-steps', '4', '--recall-queries', '64', '--cpu-queries', '0',
-            '--legs', 'graph']
+    args = ['--full', '--rows', '300000', '--steps', '6', '--warmup', '2', '--prewarm-steps', '4', '--recall-queries', '64',
+            '--cpu-queries', '0', '--legs', 'graph']
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + args, capture_output=True, text=True, env=env,
                        timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

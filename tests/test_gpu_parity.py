@@ -1195,7 +1195,7 @@ def test_bench_under_torchrun_rccl_gather_path(tmp_path):
 
     env = dict(os.environ, ANNLITE_FORCE_GATHER='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
-           '--master-port', '29533', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--rows', '300000', '--steps', '3',
+           '--master-port', '29533', os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '1', '--rows', '300000', '--steps', '3',
            '--warmup', '1', '--recall-queries', '32', '--cpu-queries', '2']
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

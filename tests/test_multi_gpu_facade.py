@@ -77,7 +77,9 @@ class FakeShard:
 
 
 @pytest.fixture()
-def world():
+def world(monkeypatch):
+    # the fake devices are numpy shards: no HIP device is made current for them, on a machine with GPUs as on one without
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
     import pq_oracle
     from annlite_amd import Metric, PQCodec
     from annlite_amd.core.index.multi_gpu import MultiGpuPQIndex

@@ -356,7 +356,7 @@ def test_bench_seed_exchange_under_torchrun_one_rank(tmp_path):
 
     env = dict(os.environ, ANNLITE_FORCE_GATHER='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
-           '--master-port', '29537', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--rows', '400000', '--steps', '12',
+           '--master-port', '29537', os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '1', '--rows', '400000', '--steps', '12',
            '--warmup', '2', '--recall-queries', '0', '--cpu-queries', '2', '--no-rerank', '--legs', 'none', '--seed-exchange',
            '--emulate-seed-peers', '8']
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=str(tmp_path))

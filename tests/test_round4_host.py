@@ -73,6 +73,30 @@ def test_bench_does_not_reexec_under_a_launcher(monkeypatch):
         bench.main()
 
 
+def test_bench_dump_outputs_files_and_sample(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: the step's [B, k] result as distances.npy (float32) and ids.npy (float64, exact); above the size limit
+    a fixed sample of the query rows (the same on every call), their row numbers beside them, within the limit."""
+    bench = _bench_module()
+    rs = np.random.RandomState(1)
+    d = torch.from_numpy(rs.rand(300, 10).astype(np.float32))
+    i = torch.from_numpy(rs.randint(0, 10_000_000, size=(300, 10)).astype(np.int64))
+    bench.dump_outputs(str(tmp_path / 'all'), (d, i))
+    gd, gi = np.load(tmp_path / 'all' / 'distances.npy'), np.load(tmp_path / 'all' / 'ids.npy')
+    assert gd.dtype == np.float32 and gi.dtype == np.float64 and gd.shape == gi.shape == (300, 10)
+    assert np.array_equal(gd, d.numpy()) and np.array_equal(gi.astype(np.int64), i.numpy())
+    assert not (tmp_path / 'all' / 'query_rows.npy').exists()
+
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 4096 + 100 * (10 * 12 + 8))
+    rows = []
+    for name in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / name), (d, i))
+        rows.append(np.load(tmp_path / name / 'query_rows.npy').astype(np.int64))
+        assert sum(os.path.getsize(tmp_path / name / f) for f in os.listdir(tmp_path / name)) <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(rows[0], rows[1]) and len(rows[0]) == 100 and np.all(np.diff(rows[0]) > 0)
+    sd, si = np.load(tmp_path / 'a' / 'distances.npy'), np.load(tmp_path / 'a' / 'ids.npy')
+    assert np.array_equal(sd, d.numpy()[rows[0]]) and np.array_equal(si.astype(np.int64), i.numpy()[rows[0]])
+
+
 # ------------------------------------------------------------------ lazy match lists
 def _resolver(calls):
     from annlite_amd.docarray_compat import Document
