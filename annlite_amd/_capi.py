@@ -91,6 +91,7 @@ SYMBOLS = (
     'annlite_profile_last_scan_clock_mhz',
     'annlite_kernel_rev',
     'annlite_debug_counters',
+    'annlite_debug_split_counters',
     'annlite_debug_timeline',
     'annlite_debug_items',
     'annlite_debug_prep_timeline',
@@ -199,6 +200,7 @@ def lib() -> ctypes.CDLL:
     L.annlite_profile_last_scan_clock_mhz.argtypes = [ctypes.POINTER(ctypes.c_float)]
     L.annlite_kernel_rev.argtypes = [ctypes.c_char_p]
     L.annlite_debug_counters.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    L.annlite_debug_split_counters.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_debug_timeline.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_debug_items.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_debug_prep_timeline.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
@@ -405,4 +407,12 @@ def debug_items():
 def debug_counters():
     out = (ctypes.c_uint64 * 8)()
     check(lib().annlite_debug_counters(out), 'debug_counters')
+    return [int(v) for v in out]
+
+
+def debug_split_counters():
+    """The byte-table kernel's split step (see ``annlite_debug_split_counters``): rows through its first phase, survivors,
+    second-phase wave-steps, wave-steps finished in place."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().annlite_debug_split_counters(out), 'debug_split_counters')
     return [int(v) for v in out]

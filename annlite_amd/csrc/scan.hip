@@ -644,6 +644,7 @@ extern "C" int annlite_scan_plan_tiles(int64_t N, int64_t M, int64_t Ks, int cod
 }
 
 static unsigned long long *g_dbg = nullptr;  // debug only (ANNLITE_DEBUG_COUNTERS): leaked device buffer: 16 counters + 4096 per-item records of 8
+                                             // + the split step's 4 counters (kDbgSplit)
 static unsigned long long *g_dbg_prep = nullptr;  // ... and the preparation launch's 8 phase stamps (annlite_debug_prep_timeline)
 static thread_local int g_prof_on = 0;
 static thread_local hipEvent_t g_ev0 = nullptr, g_ev1 = nullptr;
@@ -766,12 +767,13 @@ static int scan_partial(const void *codes_dev, int code_bytes, int codes_layout,
     const Knobs &kn = knobs();  // (one block for the whole call)
     a.dbg_skip = kn.debug_skip;
     if (kn.debug_counters && !(gopt && gopt->gate)) {  // (the gated pass leaves the first launch's counters alone)
-        if (!g_dbg) ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg, 128 + 4096 * 64));
+        if (!g_dbg) ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg, 8 * (kDbgSplit + 4)));
         if (!g_dbg_prep) {
             ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg_prep, 64));
             ANNLITE_HIP_TRY(hipMemset(g_dbg_prep, 0, 64));
         }
         ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg, 0, 128, st));
+        ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg + kDbgSplit, 0, 32, st));
         a.dbg = g_dbg;
         if (kn.debug_counters == 2) a.dbg_skip |= 8;  // phase stamps only (annlite_debug_timeline): the
                                                                            // per-wave event counters cost tens of microseconds
@@ -1128,6 +1130,17 @@ extern "C" int annlite_debug_counters(uint64_t *out8) {
     }
     ANNLITE_HIP_TRY(hipDeviceSynchronize());
     ANNLITE_HIP_TRY(hipMemcpy(out8, g_dbg, 64, hipMemcpyDeviceToHost));
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_debug_split_counters(uint64_t *out4) {
+    ANNLITE_REQUIRE(out4 != nullptr, "out4 is NULL");
+    if (!g_dbg) {
+        set_error("no counters recorded (set ANNLITE_DEBUG_COUNTERS=1 before the scan)");
+        return ANNLITE_ERR_INVALID;
+    }
+    ANNLITE_HIP_TRY(hipDeviceSynchronize());
+    ANNLITE_HIP_TRY(hipMemcpy(out4, g_dbg + kDbgSplit, 32, hipMemcpyDeviceToHost));
     return ANNLITE_OK;
 }
 
@@ -1784,8 +1797,9 @@ static int ivf_search_impl(int lut_kind, const float *queries_dev, int64_t B, in
     a.flush_mask = 63;
     a.dbg_skip = kn.debug_skip;
     if (kn.debug_counters) {  // (ANNLITE_DEBUG_COUNTERS: the scan's event counters / per-item stamps, as scan_partial wires them)
-        if (!g_dbg) ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg, 128 + 4096 * 64));
+        if (!g_dbg) ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg, 8 * (kDbgSplit + 4)));
         ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg, 0, 128, st));
+        ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg + kDbgSplit, 0, 32, st));
         a.dbg = g_dbg;
         if (kn.debug_counters == 2) a.dbg_skip |= 8;
     }

@@ -289,6 +289,9 @@ struct Q8Cfg {
 // entry spills into the next code's row: 257 rows): the 16 lanes of a ds_read_b128 -- 16 different sub-spaces, the skew -- then hit
 // 16 different 16-byte bank groups in both reads.  scripts/ubench/step_loop.hip ADDR=3: 0.883 -> 0.923 of the look-up roof.
 constexpr int kQ8Image16 = 131072 + 256;
+// ANNLITE_DEBUG_COUNTERS: where the byte-table kernel's split-step counters sit in the debug buffer (behind the 16 counters and the
+// 4096 per-item records of 8): rows through the first phase, survivors queued, second-phase wave-steps, wave-steps finished in place
+constexpr int kDbgSplit = 16 + 4096 * 8;
 __host__ __device__ constexpr uint32_t q8_entry16(uint32_t code, uint32_t m, uint32_t g) {
     return ((m & 1u) << 16) + (code << 8) + ((2u * (m >> 1) + g + (m & 1u)) << 4);
 }

@@ -75,6 +75,9 @@ namespace annlite {
 #ifndef ANNLITE_Q8_DEPTH
 #define ANNLITE_Q8_DEPTH 8  // look-ups in flight per lane
 #endif
+#ifndef ANNLITE_Q8_SPLIT_DEPTH
+#define ANNLITE_Q8_SPLIT_DEPTH 4  // ... in the split step's second phase and where a step finishes in place (rarer: its registers matter more)
+#endif
 
 // Q8Cfg: entries are clipped at QMAX (M * QMAX <= 240: a byte sum never carries); a slot without a bound yet
 // ("open": nothing seeded it) clips at QOPEN, M * QOPEN <= 112, so that T = 127 passes every row.
@@ -1118,9 +1121,19 @@ __device__ __attribute__((noinline)) void q8_finish_item(q8_kernarg_ptr ka, int 
 // scanning that cell's rows (ScanArgs::tile_rows); slot q scans with the tables of query vmap[tile * 32 + q] (Q8Lds::qmap), the image is
 // assembled from the queries' own byte tables (q8_gather_table), gkey is indexed by QUERY -- the tiles of a query's other cells import
 // its bound --, no epoch ends (a cell is a few dozen steps), every slot's list goes to `partial` by slot (annlite_ivf_merge).
-template <int M, int NW, bool SKEWED, int NQ, int CB, bool RQ, int LK = 16, bool TL = false>
+// HS > 0 (the SPLIT STEP, M = 16 row queue with SKEWED rows): a step first adds the look-ups of HS sub-spaces only and tests those
+// partial byte sums against T -- entries are >= 0, so S_HS <= S and a row that fails there fails the full test too.  The few rows
+// that pass (the survivors) go to a per-wave ring of row ids in LDS (q8_split_ring); once it holds 64, a step runs over them with
+// all 16 sub-spaces (code rows re-fetched from L2 and rotated to the lane's skew).  A step where more than q8_split_fallback<HS>()
+// rows survive finishes in place instead.  The ring is emptied before every epoch end.  HS = 0: the one-phase step.
+template <int HS>
+constexpr int q8_split_fallback() { return (64 * (16 - HS)) / 20; }  // (finishing in place costs 2 (16 - HS) look-ups per row, a survivor ~32 / 64 of a step)
+constexpr int kSplitRing = 128;  // survivor ring entries per scanning wave (u32 row ids): < 64 waiting + at most 64 pushed
+
+template <int M, int NW, bool SKEWED, int NQ, int CB, bool RQ, int LK = 16, bool TL = false, int HS = 0>
 __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const ScanArgs a) {
     static_assert(!TL || (M == 16 && NQ == 2 && CB == 1 && RQ && LK == 16), "cell tiles: the M = 16 row-queue kernel with 16-key lists");
+    static_assert(HS == 0 || (M == 16 && NQ == 2 && CB == 1 && RQ && SKEWED && HS > 0 && HS < 16), "the split step: M = 16, row queue, SKEWED rows");
     static_assert(LK == 16 || (LK == 64 && (RQ || M != 16) && M != 64), "64-key lists: M = 16 with the row queue (4-byte ring entries), M = 8 / 32");
     constexpr uint32_t RE = (uint32_t)q8_ring_entry_bytes<M, LK>();  // bytes of a ring entry
     constexpr bool WIDE = Q8Cfg<M>::WIDE;
@@ -1813,6 +1826,81 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                 if constexpr (WIDE) return (th - sm) & 0x80008000u;
                 else return (th - (sm & 0x7f7f7f7fu)) & ~sm & 0x80808080u;
             };
+            // ---- split step (HS > 0) ----
+            // look-ups of sub-spaces t in [T0, T1), both entry groups, through a ring of DEPTH landing registers, added into acc (T0 = 0:
+            // set).  The address of look-up (t, group 0) is made when it is issued (no 16 address registers live across the phases), group 1
+            // reads 16 bytes behind it right after.
+            // Phase one reads mbase[0 .. HS - 1]; the rarer parts (ONFLY) make mbase[t] from an opaque copy sp of the lane's skew as they go,
+            // so that mbase[HS ..] is dead in the step loop (kept live across it, the allocator spilled it).
+            auto split_sums = [&](const uint32_t (&cc)[CW], auto T0c, auto T1c, auto DEPTHc, auto ONFLY, uint32_t sp, u32x4 (&acc)[2]) {
+                constexpr int T0 = decltype(T0c)::value, TOT = 2 * (decltype(T1c)::value - T0);
+                constexpr int DEPTH = decltype(DEPTHc)::value < TOT ? decltype(DEPTHc)::value : TOT;
+                if constexpr (P16) {
+                    if constexpr (decltype(ONFLY)::value) asm volatile("" : "+v"(sp));  // (made here: not hoisted out of the loop)
+                    u32x4 v[DEPTH];
+                    uint32_t ad = 0;
+                    auto fetch = [&](u32x4 &dst, auto I) {
+                        constexpr int i = decltype(I)::value, t = T0 + i / 2;
+                        if constexpr (i % 2 == 0) {
+                            uint32_t mb;
+                            if constexpr (decltype(ONFLY)::value) {  // (q8_entry16(0, m, 0) = (m & 1) << 16 | m << 4)
+                                const uint32_t m = (sp + (uint32_t)t) & 15u;
+                                mb = ((m & 1u) << 16) | (m << 4);
+                            } else mb = mbase[t];
+                            ad = __builtin_amdgcn_perm(cc[t / 4], mb, 0x0c020000u | ((4u + (uint32_t)(t % 4)) << 8));
+                        }
+                        dst = *(lds_entry_ptr)(uintptr_t)(ad + (uint32_t)((i % 2) * 16));
+                    };
+                    static_for<0, DEPTH>([&](auto I) { fetch(v[decltype(I)::value], I); });
+                    static_for<0, TOT>([&](auto I) {
+                        constexpr int i = decltype(I)::value;
+                        asm volatile("" ::: "memory");
+                        if constexpr (T0 == 0 && i < 2) acc[i] = v[i % DEPTH];
+                        else acc[i % 2] += v[i % DEPTH];
+                        // (the rarer parts: the add is pinned here -- left free, the scheduler sank the adds below the next look-ups and
+                        // held 16 of them in flight, and the allocator spilled loop invariants around the second phase)
+                        if constexpr (decltype(ONFLY)::value) asm volatile("" : "+v"(acc[i % 2]));
+                        if constexpr (i + DEPTH < TOT) fetch(v[i % DEPTH], std::integral_constant<int, i + DEPTH>{});
+                    });
+                }
+            };
+            auto split_pass = [&](const u32x4 (&acc)[2]) -> bool {  // any query of this lane's row with S <= T
+                uint32_t anyv = 0;
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) anyv |= (thw[4 * h + e] - (acc[h][e] & 0x7f7f7f7fu)) & ~acc[h][e];
+                return (anyv & 0x80808080u) != 0u;
+            };
+            // the survivor ring of this wave: entries [sv_h, sv_h + sv_c) mod kSplitRing (sv_h is 0 or 64: the ring is taken 64 at a time)
+            const uint32_t sv_ad = lds.qmap + 128u + (uint32_t)wave * (uint32_t)(kSplitRing * 4);
+            constexpr int HS1 = HS > 0 ? HS : 1;  // (the lambdas below are compiled for HS = 0 too, and never called there)
+            uint32_t sv_h = 0, sv_c = 0;
+            uint32_t n_rows_a = 0, n_surv = 0, n_tail = 0, n_fb = 0;  // (ANNLITE_DEBUG_COUNTERS)
+            // first phase of a step: the rows of the block whose full test must still run -- the rows passing the full test when more than
+            // q8_split_fallback rows survive HS sub-spaces (finished in place), else none (the survivors are queued)
+            auto split_head = [&](auto vmask, uint32_t row0) -> unsigned long long {  // (generic: instantiated by HS > 0 only)
+                u32x4 acc[2];
+                split_sums(ccur, std::integral_constant<int, 0>{}, std::integral_constant<int, HS1>{}, std::integral_constant<int, ANNLITE_Q8_DEPTH>{}, std::false_type{}, 0u, acc);
+                const unsigned long long alive = __ballot(split_pass(acc)) & vmask;
+                const uint32_t n = (uint32_t)__popcll(alive);
+                if (a.dbg) n_rows_a += (uint32_t)__popcll(vmask);
+                if (n > (uint32_t)q8_split_fallback<HS1>()) {
+                    uint32_t sp = (uint32_t)s;
+                    asm volatile("" : "+v"(sp));
+                    split_sums(ccur, std::integral_constant<int, HS1>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, ANNLITE_Q8_SPLIT_DEPTH>{}, std::true_type{}, sp, acc);
+                    ++n_fb;
+                    return __ballot(split_pass(acc)) & vmask;
+                }
+                if (n) {
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(alive >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)alive, 0u));
+                    if (__builtin_amdgcn_inverse_ballot_w64(alive))
+                        ldsv_st<uint32_t>(sv_ad + 4u * ((sv_h + sv_c + rank) & (uint32_t)(kSplitRing - 1)), row0 + (uint32_t)lane);
+                    sv_c += n;
+                    n_surv += n;
+                }
+                return 0ull;
+            };
             uint32_t vcur = ~0u, vnext = ~0u;
             const uint32_t *valid = a.valid;
             auto load_valid = [&](uint32_t row) -> uint32_t {
@@ -1825,6 +1913,58 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
             // the next block, picked up at the top of that one; the number of the block after that is drawn in between.
             // (Fetching two steps ahead and rotating the registers at the end of the step made the compiler wait for the
             // load it had just issued: s_waitcnt vmcnt(0) every step.)
+            uint32_t rs = 0;  // (pushed entries) | (consumed entries, as last read) << 16 of this wave's ring, both mod 2^16
+            uint32_t n_slow = 0, n_push = 0;
+            // (row queue) push the ROW ids of the lanes in rem (the consumer finds the queries: q8_row_pass_mask) -- one ring
+            // reservation, lane-parallel stores
+            auto push_rows = [&](unsigned long long rem, uint32_t rid) {
+                ++n_slow;
+                const uint32_t n = (uint32_t)__popcll(rem);
+                uint32_t tl = rs & 0xffffu, hd = rs >> 16;
+                while (((tl + n - hd) & 0xffffu) > (uint32_t)kWaveRing) {  // the consumer is behind
+                    hd = ldsv<uint32_t>(lds.heads() + 4u * (uint32_t)wave) & 0xffffu;
+                    if (((tl + n - hd) & 0xffffu) <= (uint32_t)kWaveRing) break;
+                    __builtin_amdgcn_s_sleep(8);
+                }
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rem >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rem, 0u));
+                if (__builtin_amdgcn_inverse_ballot_w64(rem))  // (the hit lanes: exec <- rem)
+                    ldsv_st<uint32_t>(lds.ring + RE * ((uint32_t)wave * kWaveRing + ((tl + rank) & (kWaveRing - 1))),
+                                      rid);  // (the low word of the entry; the consumer reads nothing else of it)
+                tl = (tl + n) & 0xffffu;
+                if (lane == 0) ldsv_st<uint32_t>(lds.tails() + 4u * (uint32_t)wave, tl);
+                rs = tl | (hd << 16);
+                n_push += n;
+            };
+            // second phase of the split step: the full test of the first nb (1..64) entries of the survivor ring, one row per lane.  A
+            // survivor's row n sits in a lane l with l != n (mod 16) as a rule: its SKEWED code bytes are rotated by (l - n) mod 16 so that
+            // look-up t still reads sub-space (l + t) mod 16 -- the lane's own column, conflict-free.  (The code rows came through L2
+            // a few steps ago.)
+            auto split_tail = [&](auto nb) {  // (generic: instantiated by HS > 0 only)
+                const bool on = (uint32_t)lane < nb;
+                const uint32_t rid = ldsv<uint32_t>(sv_ad + 4u * ((sv_h + (on ? (uint32_t)lane : 0u)) & (uint32_t)(kSplitRing - 1)));
+                uint32_t cb[CW];
+                load_row(rid, cb);
+                uint32_t sp = (uint32_t)s;
+                asm volatile("" : "+v"(sp));
+                const uint32_t r = (sp - rid) & 15u;
+                {  // cb[t] <- byte (t + r) mod 16: dwords by r / 4 (two select stages), then bytes by r % 4
+                    const bool q1 = (r & 4u) != 0u, q2 = (r & 8u) != 0u;
+                    uint32_t d[CW];
+#pragma unroll
+                    for (int i = 0; i < CW; ++i) d[i] = q1 ? cb[(i + 1) % CW] : cb[i];
+#pragma unroll
+                    for (int i = 0; i < CW; ++i) cb[i] = q2 ? d[(i + 2) % CW] : d[i];
+#pragma unroll
+                    for (int i = 0; i < CW; ++i) d[i] = __builtin_amdgcn_alignbyte(cb[(i + 1) % CW], cb[i], r & 3u);
+#pragma unroll
+                    for (int i = 0; i < CW; ++i) cb[i] = d[i];
+                }
+                u32x4 acc[2];
+                split_sums(cb, std::integral_constant<int, 0>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, ANNLITE_Q8_SPLIT_DEPTH>{}, std::true_type{}, sp, acc);
+                const unsigned long long rem = __ballot(on && split_pass(acc));
+                if (rem && !(a.dbg_skip & 4)) push_rows(rem, rid);
+                ++n_tail;
+            };
             uint32_t b_cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)draw());
             uint32_t pend = draw();
             load_row(blk_row(b_cur) + lane, cnext);
@@ -1835,8 +1975,6 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
             // registers stay put.
             uint32_t it_no = 0;
             const uint32_t thw_mask = (uint32_t)a.q8_thw_mask;
-            uint32_t rs = 0;  // (pushed entries) | (consumed entries, as last read) << 16 of this wave's ring, both mod 2^16
-            uint32_t n_slow = 0, n_push = 0;
             unsigned long long t_wait = 0;
             for (int epoch_step = a.q8_epoch0;; epoch_step = a.q8_epoch_mul * epoch_step + (a.q8_epoch_mul - 1)) {
                 const bool final = TL || epoch_step >= n_steps - 1;
@@ -1878,42 +2016,34 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     if (s_end - row0 < 64u) vmask = (1ull << (s_end - row0)) - 1ull;
                     // validity word of this lane's row, fetched one step ahead with the code bytes
                     if (valid) vmask &= __ballot((vcur >> (lane & 31)) & 1u);
-                    make_addr(ccur);
                     uint32_t sums[NF];
-                    row_sums(ccur, sums);
-                    // any (query, lane) with S <= T ?
-                    uint32_t anyv = 0;
-                    if constexpr (WIDE) {
+                    unsigned long long rem;
+                    if constexpr (HS > 0) rem = split_head(vmask, row0);
+                    else {
+                        make_addr(ccur);
+                        row_sums(ccur, sums);
+                        // any (query, lane) with S <= T ?
+                        uint32_t anyv = 0;
+                        if constexpr (WIDE) {
 #pragma unroll
-                        for (int w = 0; w < NF; ++w) anyv |= thw[w] - sums[w];
-                        anyv &= 0x80008000u;
-                    } else {
-                        // S < 128 and (0x80 | T) - (S & 0x7f) has bit 7 set (T <= 127: no borrow)
+                            for (int w = 0; w < NF; ++w) anyv |= thw[w] - sums[w];
+                            anyv &= 0x80008000u;
+                        } else {
+                            // S < 128 and (0x80 | T) - (S & 0x7f) has bit 7 set (T <= 127: no borrow)
 #pragma unroll
-                        for (int w = 0; w < NF; ++w) anyv |= (thw[w] - (sums[w] & 0x7f7f7f7fu)) & ~sums[w];
-                        anyv &= 0x80808080u;
+                            for (int w = 0; w < NF; ++w) anyv |= (thw[w] - (sums[w] & 0x7f7f7f7fu)) & ~sums[w];
+                            anyv &= 0x80808080u;
+                        }
+                        rem = __ballot(anyv != 0) & vmask;
                     }
-                    unsigned long long rem = __ballot(anyv != 0) & vmask;
                     if constexpr (ROWQ) {
-                        if (rem && !(a.dbg_skip & 4)) {
-                            // push the ROW ids of the hit lanes (the consumer finds the queries: q8_row_pass_mask) -- one ring
-                            // reservation, lane-parallel stores
-                            ++n_slow;
-                            const uint32_t n = (uint32_t)__popcll(rem);
-                            uint32_t tl = rs & 0xffffu, hd = rs >> 16;
-                            while (((tl + n - hd) & 0xffffu) > (uint32_t)kWaveRing) {  // the consumer is behind
-                                hd = ldsv<uint32_t>(lds.heads() + 4u * (uint32_t)wave) & 0xffffu;
-                                if (((tl + n - hd) & 0xffffu) <= (uint32_t)kWaveRing) break;
-                                __builtin_amdgcn_s_sleep(8);
+                        if (rem && !(a.dbg_skip & 4)) push_rows(rem, row0 + (uint32_t)lane);
+                        if constexpr (HS > 0) {
+                            if (sv_c >= 64u) {
+                                split_tail(64u);
+                                sv_h ^= 64u;
+                                sv_c -= 64u;
                             }
-                            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(rem >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rem, 0u));
-                            if (__builtin_amdgcn_inverse_ballot_w64(rem))  // (the hit lanes: exec <- rem)
-                                ldsv_st<uint32_t>(lds.ring + RE * ((uint32_t)wave * kWaveRing + ((tl + rank) & (kWaveRing - 1))),
-                                                  row0 + (uint32_t)lane);  // (the low word of the entry; the consumer reads nothing else of it)
-                            tl = (tl + n) & 0xffffu;
-                            if (lane == 0) ldsv_st<uint32_t>(lds.tails() + 4u * (uint32_t)wave, tl);
-                            rs = tl | (hd << 16);
-                            n_push += n;
                         }
                     } else
                     if (rem && !(a.dbg_skip & 4)) {
@@ -1996,6 +2126,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     b_cur = b_nxt;
                     b_nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)pend);
                 }
+                if constexpr (HS > 0) {  // (nothing may wait in the survivor ring when the lists are published or the table rebuilt)
+                    if (sv_c) split_tail(sv_c);
+                    sv_h = sv_c = 0u;
+                }
                 if (lane == 0) lds_add_u32(lds.arrived(), 1u);
                 const unsigned long long tw = a.dbg ? __builtin_readcyclecounter() : 0ull;
                 if (final) stamp(2);
@@ -2009,6 +2143,12 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                 atomicAdd(a.dbg + 0, (unsigned long long)n_slow);
                 atomicAdd(a.dbg + 1, (unsigned long long)n_push);
                 if (wave == 0) atomicAdd(a.dbg + 7, t_wait);
+                if constexpr (HS > 0) {  // split step: rows through its first phase, survivors queued, second-phase wave-steps, waves finished in place
+                    atomicAdd(a.dbg + kDbgSplit + 0, (unsigned long long)n_rows_a);
+                    atomicAdd(a.dbg + kDbgSplit + 1, (unsigned long long)n_surv);
+                    atomicAdd(a.dbg + kDbgSplit + 2, (unsigned long long)n_tail);
+                    atomicAdd(a.dbg + kDbgSplit + 3, (unsigned long long)n_fb);
+                }
             }
         }
 
@@ -2074,16 +2214,17 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
 
 using namespace annlite;
 
-template <int M, int NW, bool SKEWED, int NQ, int CB, bool RQ = false, int LK = 16, bool TL = false>
+template <int M, int NW, bool SKEWED, int NQ, int CB, bool RQ = false, int LK = 16, bool TL = false, int HS = 0>
 static int launch_q8(const ScanArgs &a, int grid, hipStream_t st) {
     constexpr int QT = 32;  // (the control block is laid out for 32 slots whatever the kernel uses)
     // (the row queue's parking area, 3072 B behind everything else, exists only for the kernels that run it: the 128 KB tables of
     // M = 32 / M = 8 with uint16 codes + 16 KB of 64-key lists + the 8 KB ring fit the 160 KB without it)
     const size_t need = (size_t)(M == 64 ? (a.Ks + 1) * 512 : M == 32 ? 131072 : (M == 16 && NQ == 2) ? kQ8Image16 : a.Ks * NQ * M * 16) + 1664 +
                         (size_t)QT * LK * 8 + QT * 8 +
-                        (size_t)kRingSize * q8_ring_entry_bytes<M, LK>() + 4 * 128 * 9 + 32 + 32 + 16 + ((RQ || LK == 16) ? 3072 : 0) + (TL ? 128 : 0);
+                        (size_t)kRingSize * q8_ring_entry_bytes<M, LK>() + 4 * 128 * 9 + 32 + 32 + 16 + ((RQ || LK == 16) ? 3072 : 0) + (TL ? 128 : 0) +
+                        (HS ? 128 + (NW - 1) * kSplitRing * 4 : 0);  // (the survivor rings sit behind the cell tiles' query map, present or not)
     ANNLITE_REQUIRE(need <= 160 * 1024, "byte-table kernel: %zu B of LDS", need);
-    auto fn = adc_scan_q8_kernel<M, NW, SKEWED, NQ, CB, RQ, LK, TL>;
+    auto fn = adc_scan_q8_kernel<M, NW, SKEWED, NQ, CB, RQ, LK, TL, HS>;
     ANNLITE_HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
     hipLaunchKernelGGL(fn, dim3(grid), dim3(NW * 64), need, st, a);
     return launch_status("adc_scan_q8_kernel");
@@ -2095,7 +2236,13 @@ int annlite::launch_q8_scan(int id, bool sk, const ScanArgs &a, int grid, hipStr
             // shared bounds (the plain search): the row queue.  Unshared slices (the candidate generator of the re-rank stage: every
             // slice keeps 16 keys, the consumer is the bottleneck) keep the enumeration in the scanning waves -- with the row queue the
             // re-rank leg ran at 513 k q/s instead of 554 k
-            if (a.gkey) return sk ? launch_q8<16, 16, true, 2, 1, true>(a, grid, st) : launch_q8<16, 16, false, 2, 1, true>(a, grid, st);
+            // SKEWED rows take the split step with 12 sub-spaces first (ANNLITE_Q8_SPLIT=0: the one-phase step).  10M rows, the bench, alternating:
+            // one-phase 766 / 767 k q/s, HS = 8 719 / 721 (survivors 4.9 %, 7 % of the wave-steps finished in place), 10 818 / 819, 12 821 / 820
+            if (a.gkey) {
+                if (!sk) return launch_q8<16, 16, false, 2, 1, true>(a, grid, st);
+                if (knobs().q8_split == 0) return launch_q8<16, 16, true, 2, 1, true>(a, grid, st);
+                return launch_q8<16, 16, true, 2, 1, true, 16, false, 12>(a, grid, st);
+            }
             return sk ? launch_q8<16, 16, true, 2, 1>(a, grid, st) : launch_q8<16, 16, false, 2, 1>(a, grid, st);
         case 1651:  // M = 16, k <= 16, cell tiles (annlite_ivf_search_topk): one work item per tile of (query, cell) pairs
             if (!a.gkey || !a.tile_rows || !a.vmap || !a.btab || !a.gseed0 || a.tile_done || a.gk2 || a.guard) {

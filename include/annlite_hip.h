@@ -354,6 +354,9 @@ ANNLITE_API int annlite_scan_state_info(annlite_scan_state *state, int32_t *kern
  * candidate [1] candidates pushed [2] exact sums [3] candidates queued for a list [4] consumer-wave cycles inside
  * batches [5] table rebuilds [6] consumer batches [7] cycles of wave 0 at epoch ends. */
 ANNLITE_API int annlite_debug_counters(uint64_t *out8);
+/* Debug aid, same switch: the byte-table kernel's split step (M = 16, ANNLITE_Q8_SPLIT): [0] rows through its first phase
+ * [1] rows that survived it (queued for the second) [2] second-phase wave-steps [3] wave-steps finished in place. */
+ANNLITE_API int annlite_debug_split_counters(uint64_t *out4);
 /* Debug aid, same switch: phase stamps of the byte-table kernel's workgroups (thread 0, 100 MHz wall clock): [0] 2^62 -
  * earliest start, [1] latest end; sums over the work items of [2] start stamp, [3] initialisation + first table build,
  * [4] step loop, [5] wait at the last barrier, [6] list store + merge; [7] work items. */
