@@ -63,7 +63,7 @@ struct Knobs {
     int seed_chunk_log;         // ANNLITE_SEED_CHUNK_LOG (clamped to [0, 6]; default 3)
     bool no_fused_seed;         // ANNLITE_NO_FUSED_SEED
     bool no_prebuilt_tables;    // ANNLITE_NO_PREBUILT_TABLES
-    int q8_split;               // ANNLITE_Q8_SPLIT=0: the byte-table kernel's one-phase step instead of the split step (M = 16, A/B switch)
+    int q8_split;               // ANNLITE_Q8_SPLIT=0: the byte-table kernel's one-phase step instead of the split step (M = 16, A/B switch; 12: the split step with 12 sub-spaces first)
     bool no_early_merge;        // ANNLITE_NO_EARLY_MERGE
     int64_t early_merge_patience;  // ANNLITE_EARLY_MERGE_PATIENCE
     bool no_inkernel_merge;     // ANNLITE_NO_INKERNEL_MERGE

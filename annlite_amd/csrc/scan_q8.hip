@@ -78,6 +78,9 @@ namespace annlite {
 #ifndef ANNLITE_Q8_SPLIT_DEPTH
 #define ANNLITE_Q8_SPLIT_DEPTH 4  // ... in the split step's second phase and where a step finishes in place (rarer: its registers matter more)
 #endif
+#ifndef ANNLITE_Q8_SPLIT_H
+#define ANNLITE_Q8_SPLIT_H 11  // sub-spaces in the split step's first phase (id 1650 with shared bounds and SKEWED rows; ANNLITE_Q8_SPLIT=12: 12)
+#endif
 
 // Q8Cfg: entries are clipped at QMAX (M * QMAX <= 240: a byte sum never carries); a slot without a bound yet
 // ("open": nothing seeded it) clips at QOPEN, M * QOPEN <= 112, so that T = 127 passes every row.
@@ -1877,21 +1880,50 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
             constexpr int HS1 = HS > 0 ? HS : 1;  // (the lambdas below are compiled for HS = 0 too, and never called there)
             uint32_t sv_h = 0, sv_c = 0;
             uint32_t n_rows_a = 0, n_surv = 0, n_tail = 0, n_fb = 0;  // (ANNLITE_DEBUG_COUNTERS)
-            // first phase of a step: the rows of the block whose full test must still run -- the rows passing the full test when more than
-            // q8_split_fallback rows survive HS sub-spaces (finished in place), else none (the survivors are queued)
-            auto split_head = [&](auto vmask, uint32_t row0) -> unsigned long long {  // (generic: instantiated by HS > 0 only)
-                u32x4 acc[2];
-                split_sums(ccur, std::integral_constant<int, 0>{}, std::integral_constant<int, HS1>{}, std::integral_constant<int, ANNLITE_Q8_DEPTH>{}, std::false_type{}, 0u, acc);
+            // The first phase's look-up stream runs ACROSS the step boundary: its landing ring `ring` enters a step holding the step's
+            // first PD look-ups in flight, and the slots its last look-ups free take the NEXT block's first PD (from cnext, fetched a
+            // step ahead).  The drain, the pass test, the vote, the survivor store and the loop top then run with look-ups in flight
+            // instead of an empty LDS queue.  The rare parts (finish in place, second phase) let the prefix die and issue it again.
+            constexpr int PD = HS > 0 ? (ANNLITE_Q8_DEPTH < 2 * HS1 ? ANNLITE_Q8_DEPTH : 2 * HS1) : 1;
+            u32x4 ring[PD];
+            // look-up i of a first phase: sub-space i / 2, entry group i % 2 (the pair's address is made with its group-0 look-up, in ad)
+            auto split_fetch = [&](u32x4 &dst, const uint32_t (&cc)[CW], uint32_t &ad, auto I) {
+                constexpr int i = decltype(I)::value, t = i / 2;
+                if constexpr (i % 2 == 0) ad = __builtin_amdgcn_perm(cc[t / 4], mbase[t], 0x0c020000u | ((4u + (uint32_t)(t % 4)) << 8));
+                dst = *(lds_entry_ptr)(uintptr_t)(ad + (uint32_t)((i % 2) * 16));
+            };
+            auto split_prefix = [&](const auto &cc) {  // the first PD look-ups of the block in cc (generic: instantiated by HS > 0 only)
+                uint32_t ad = 0;
+                static_for<0, PD>([&](auto I) { split_fetch(ring[decltype(I)::value], cc, ad, I); });
+            };
+            // the first phase of the block in ccur (its first PD look-ups already in the ring), the next block's first PD issued behind it
+            auto split_first = [&](auto &acc) {  // (generic: instantiated by HS > 0 only)
+                constexpr int TOT = 2 * HS1;
+                u32x4 nr[PD];
+                uint32_t ad = 0, an = 0;
+                static_for<0, TOT>([&](auto I) {
+                    constexpr int i = decltype(I)::value, j = i + PD;
+                    // (where the next block's look-ups are issued, the adds are held behind the barrier every second sub-space: left
+                    // free, the scheduler hoisted the drain and the pass test above them and issued the next look-ups only after
+                    // lgkmcnt(0))
+                    if constexpr (j >= TOT && i % 4 == 0) asm volatile("" : "+v"(acc[0]), "+v"(acc[1])::"memory");
+                    else asm volatile("" ::: "memory");
+                    if constexpr (i < 2) acc[i] = ring[i % PD];
+                    else acc[i % 2] += ring[i % PD];
+                    if constexpr (j < TOT) split_fetch(ring[j % PD], ccur, ad, std::integral_constant<int, j>{});
+                    else split_fetch(nr[j - TOT], cnext, an, std::integral_constant<int, j - TOT>{});
+                });
+#pragma unroll
+                for (int i = 0; i < PD; ++i) ring[i] = nr[i];
+            };
+            // first phase of a step (acc: the byte sums of HS sub-spaces): true when more than q8_split_fallback rows survive it (the step
+            // finishes in place: split_finish), else the survivors are queued
+            auto split_head = [&](auto vmask, uint32_t row0, u32x4 (&acc)[2]) -> bool {  // (generic: instantiated by HS > 0 only)
+                split_first(acc);
                 const unsigned long long alive = __ballot(split_pass(acc)) & vmask;
                 const uint32_t n = (uint32_t)__popcll(alive);
                 if (a.dbg) n_rows_a += (uint32_t)__popcll(vmask);
-                if (n > (uint32_t)q8_split_fallback<HS1>()) {
-                    uint32_t sp = (uint32_t)s;
-                    asm volatile("" : "+v"(sp));
-                    split_sums(ccur, std::integral_constant<int, HS1>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, ANNLITE_Q8_SPLIT_DEPTH>{}, std::true_type{}, sp, acc);
-                    ++n_fb;
-                    return __ballot(split_pass(acc)) & vmask;
-                }
+                if (n > (uint32_t)q8_split_fallback<HS1>()) return true;
                 if (n) {
                     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(alive >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)alive, 0u));
                     if (__builtin_amdgcn_inverse_ballot_w64(alive))
@@ -1899,7 +1931,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     sv_c += n;
                     n_surv += n;
                 }
-                return 0ull;
+                return false;
+            };
+            // the rows of the block in ccur passing the full test (sub-spaces HS .. 15 added to acc)
+            auto split_finish = [&](auto vmask, u32x4 (&acc)[2]) -> unsigned long long {  // (generic: instantiated by HS > 0 only)
+                uint32_t sp = (uint32_t)s;
+                asm volatile("" : "+v"(sp));
+                split_sums(ccur, std::integral_constant<int, HS1>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, ANNLITE_Q8_SPLIT_DEPTH>{}, std::true_type{}, sp, acc);
+                ++n_fb;
+                return __ballot(split_pass(acc)) & vmask;
             };
             uint32_t vcur = ~0u, vnext = ~0u;
             const uint32_t *valid = a.valid;
@@ -1983,7 +2023,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                 // waited for HERE.  Left pending into the loop, they merged into the loop header's wait state, and every step then
                 // waited with vmcnt(1) for the code row it had just issued for the NEXT step when the table has a validity bitmap --
                 // the fetch latency exposed once per step.  10M rows, the bench: 1.236 -> 1.187 ms per launch, 819 -> 859 k q/s)
-                if constexpr (HS > 0) asm volatile("" ::"v"(cnext[0]), "v"(cnext[1]), "v"(cnext[2]), "v"(cnext[3]), "v"(vnext));
+                if constexpr (HS > 0) {
+                    asm volatile("" ::"v"(cnext[0]), "v"(cnext[1]), "v"(cnext[2]), "v"(cnext[3]), "v"(vnext));
+                    split_prefix(cnext);  // (the epoch's first block; across an epoch end the table may have been rebuilt)
+                }
                 for (; b_cur < end_blk; ++it_no) {
                     const uint32_t row0 = blk_row(b_cur);  // (< s_end: b_cur < n_blocks)
                     pend = draw();
@@ -2023,8 +2066,23 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     if (valid) vmask &= __ballot((vcur >> (lane & 31)) & 1u);
                     uint32_t sums[NF];
                     unsigned long long rem;
-                    if constexpr (HS > 0) rem = split_head(vmask, row0);
-                    else {
+                    if constexpr (HS > 0) {
+                        u32x4 acc[2];
+                        const bool fb = split_head(vmask, row0, acc);
+                        if (fb || sv_c >= 64u) {  // (rare: the next block's first look-ups are dropped here and issued again below)
+                            if (fb) {
+                                rem = split_finish(vmask, acc);
+                                if (rem && !(a.dbg_skip & 4)) push_rows(rem, row0 + (uint32_t)lane);
+                            }
+                            if (sv_c >= 64u) {
+                                split_tail(64u);
+                                sv_h ^= 64u;
+                                sv_c -= 64u;
+                            }
+                            asm volatile("" ::: "memory");
+                            split_prefix(cnext);
+                        }
+                    } else {
                         make_addr(ccur);
                         row_sums(ccur, sums);
                         // any (query, lane) with S <= T ?
@@ -2042,14 +2100,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                         rem = __ballot(anyv != 0) & vmask;
                     }
                     if constexpr (ROWQ) {
-                        if (rem && !(a.dbg_skip & 4)) push_rows(rem, row0 + (uint32_t)lane);
-                        if constexpr (HS > 0) {
-                            if (sv_c >= 64u) {
-                                split_tail(64u);
-                                sv_h ^= 64u;
-                                sv_c -= 64u;
-                            }
-                        }
+                        if constexpr (HS == 0)  // (the split step pushes its rows above)
+                            if (rem && !(a.dbg_skip & 4)) push_rows(rem, row0 + (uint32_t)lane);
                     } else
                     if (rem && !(a.dbg_skip & 4)) {
                         ++n_slow;
@@ -2245,8 +2297,11 @@ int annlite::launch_q8_scan(int id, bool sk, const ScanArgs &a, int grid, hipStr
             // one-phase 766 / 767 k q/s, HS = 8 719 / 721 (survivors 4.9 %, 7 % of the wave-steps finished in place), 10 818 / 819, 12 821 / 820
             if (a.gkey) {
                 if (!sk) return launch_q8<16, 16, false, 2, 1, true>(a, grid, st);
+                // (round 8: the next block's first look-ups issued across the step boundary; 10M rows, the bench, alternating: HS = 12 892-895 k,
+                // 11 906-910, 10 906-911, HEAD's 12 857-861.  ANNLITE_Q8_SPLIT=12 keeps the HS = 12 step as an in-process A/B)
                 if (knobs().q8_split == 0) return launch_q8<16, 16, true, 2, 1, true>(a, grid, st);
-                return launch_q8<16, 16, true, 2, 1, true, 16, false, 12>(a, grid, st);
+                if (knobs().q8_split == 12 && ANNLITE_Q8_SPLIT_H != 12) return launch_q8<16, 16, true, 2, 1, true, 16, false, 12>(a, grid, st);
+                return launch_q8<16, 16, true, 2, 1, true, 16, false, ANNLITE_Q8_SPLIT_H>(a, grid, st);
             }
             return sk ? launch_q8<16, 16, true, 2, 1>(a, grid, st) : launch_q8<16, 16, false, 2, 1>(a, grid, st);
         case 1651:  // M = 16, k <= 16, cell tiles (annlite_ivf_search_topk): one work item per tile of (query, cell) pairs
