@@ -17,15 +17,16 @@ namespace annlite {
 // ---- cell selection ------------------------------------------------------------------------------
 // One 256-thread workgroup per QB = 4 queries: the query vectors sit in LDS (read by broadcast), thread t owns the
 // centroids t, t + 256, ... and keeps QB running sums while it streams a centroid row ONCE; the QB x C distances
-// go to LDS, where one wave per query picks the P nearest under the fixed order (distance asc, cell asc).
+// go to LDS as ordered keys (f32_to_key: -0 as +0, every NaN one key behind +inf), where one wave per query picks
+// the P nearest under the fixed order (distance asc, cell asc): numpy's order, NaN last, as oracle.select_cells.
 constexpr int kSelQB = 4;
 template <int KIND>  // 0: squared L2, 1: negative inner product
 __global__ __launch_bounds__(256) void ivf_select_cells_kernel(const float *__restrict__ q, int B, int D,
                                                               const float *__restrict__ cent, int C, int P,
                                                               int32_t *__restrict__ cells) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float *qs = (float *)smem;               // [QB][D]
-    float *ds = qs + (size_t)kSelQB * D;     // [QB][C]
+    float *qs = (float *)smem;                             // [QB][D]
+    uint32_t *ks = (uint32_t *)(qs + (size_t)kSelQB * D);  // [QB][C] keys of the distances
     const int tid = threadIdx.x;
     const int b0 = blockIdx.x * kSelQB;
     for (int i = tid; i < kSelQB * D; i += 256) {
@@ -62,30 +63,27 @@ __global__ __launch_bounds__(256) void ivf_select_cells_kernel(const float *__re
             for (int j = 0; j < D; ++j) step(cr[j], j);
         }
 #pragma unroll
-        for (int u = 0; u < kSelQB; ++u) ds[u * C + c] = KIND == 0 ? acc[u] : -acc[u];
+        for (int u = 0; u < kSelQB; ++u) ks[u * C + c] = f32_to_key((KIND == 0 ? acc[u] : -acc[u]) + 0.f);
     }
     __syncthreads();
     // the P nearest, one wave per query: P rounds of "lane-local minimum over its cells -> wave argmin -> mark taken"
-    // under the fixed order (distance asc, cell asc).  (Rank counting every cell against every other was C^2 per
-    // query: 0.88 ms for 1024 queries x 1024 cells.)
+    // under the fixed order (key asc, cell asc).  (Rank counting every cell against every other was C^2 per
+    // query: 0.88 ms for 1024 queries x 1024 cells.)  A taken cell's key becomes kKeyInfHi, above every distance's key
+    // (NaN included), which the strict lane scan never accepts: with P <= C every round finds an untaken cell.
     const int lane = tid & 63, wave = tid >> 6;
     for (int u = wave; u < kSelQB; u += 4) {
         if (b0 + u >= B) continue;
-        float *row = ds + u * C;
+        uint32_t *row = ks + u * C;
         for (int p = 0; p < P; ++p) {
-            float best = __builtin_inff();
-            int bi = 0x7fffffff;
-            for (int c = lane; c < C; c += 64) {
-                const float v = row[c];
-                if (v < best || (v == best && c < bi)) best = v, bi = c;
+            uint32_t khi = kKeyInfHi, klo = 0xffffffffu;
+            for (int c = lane; c < C; c += 64) {  // (ascending c: the strict '<' keeps the lowest cell of equal keys)
+                const uint32_t v = row[c];
+                if (v < khi) khi = v, klo = (uint32_t)c;
             }
             // wave argmin by DPP (round 6): row_shr 1 / 2 / 4 / 8 inside the 16-lane rows, row_bcast 15 / 31 across them -- lane 63 ends
-            // up with the minimum of all 64 (the order (distance, cell) as a 64-bit key: ordered float bits, then the cell), read back
-            // through an SGPR.  (Six __shfl_xor steps of two values each went through ds_bpermute: ~1 us per round, 16 of the
-            // kernel's 26 us at 16 probes.)
+            // up with the minimum of all 64 (the order (key, cell) as a 64-bit key), read back through an SGPR.  (Six __shfl_xor
+            // steps of two values each went through ds_bpermute: ~1 us per round, 16 of the kernel's 26 us at 16 probes.)
             {
-                uint32_t khi = f32_to_ordered(best + 0.f);  // (never NaN: the lane's minimum starts at +inf; -0 as +0: the float order's tie)
-                uint32_t klo = (uint32_t)bi;
                 auto step = [&](int ctrl_id) {
                     uint32_t ohi, olo;
                     // (old = all-ones: a lane without a source in this step keeps the key that loses every comparison)
@@ -100,14 +98,10 @@ __global__ __launch_bounds__(256) void ivf_select_cells_kernel(const float *__re
                     if (ohi < khi || (ohi == khi && olo < klo)) khi = ohi, klo = olo;
                 };
                 step(0), step(1), step(2), step(3), step(4), step(5);
-                const uint32_t whi = (uint32_t)__builtin_amdgcn_readlane((int)khi, 63);
-                bi = __builtin_amdgcn_readlane((int)klo, 63);
-                best = ordered_to_f32(whi);
             }
-            // (a query with NaN / inf components finds no minimum: fall back to cell p so that the plan never sees an
-            // out-of-range cell -- the results of such a query are meaningless either way)
-            if (lane == 0) cells[(int64_t)(b0 + u) * P + p] = bi < C ? bi : p;
-            if (bi < C && lane == (bi & 63)) row[bi] = __builtin_inff();  // taken (LDS ops of a wave execute in order)
+            const int bi = __builtin_amdgcn_readlane((int)klo, 63);  // < C: an untaken cell's key is below kKeyInfHi
+            if (lane == 0) cells[(int64_t)(b0 + u) * P + p] = bi;
+            if (lane == (bi & 63)) row[bi] = kKeyInfHi;  // taken (LDS ops of a wave execute in order)
         }
     }
 }

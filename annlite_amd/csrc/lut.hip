@@ -134,6 +134,18 @@ __global__ __launch_bounds__(256) void lut_ip_mfma_kernel(const float *__restric
         // reference order is fma(codeword, query, acc); the product commutes exactly
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
     }
+    // An exact zero may carry the other sign than the fmaf chain's: a product that underflows rounds the chain to -0, the MFMA
+    // returns +0.  Such entries (rare: exact zeros) take the chain itself.
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int b = bt * 16 + kk * 4 + r;
+        if (acc[r] == 0.f && b < B && ki < Ks) {
+            const float *qb = q + (int64_t)b * D + m * dsub;
+            float s = 0.f;
+            for (int j = 0; j < dsub; ++j) s = __builtin_fmaf(cw[j], qb[j], s);
+            acc[r] = s;
+        }
+    }
     if (ipdist) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] = inv_ks - acc[r];

@@ -47,7 +47,9 @@ def code_bytes_of(t: torch.Tensor) -> int:
 
 def codes_to_numpy(t: torch.Tensor) -> np.ndarray:
     a = t.cpu().numpy()
-    return {1: a, 2: a.view(np.uint16), 4: a.view(np.uint32)}[a.dtype.itemsize] if a.dtype.kind == 'i' else a
+    if a.dtype.kind != 'i' or a.dtype.itemsize == 1:
+        return a
+    return a.view({2: np.uint16, 4: np.uint32}[a.dtype.itemsize])  # (same width: any row length)
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:

@@ -230,3 +230,18 @@ def test_graph_index_build_side_is_resolved_without_a_gpu():
         mk(build='cpu')
     with pytest.raises(AssertionError):
         mk(expand_width=3)
+
+
+def test_codes_to_numpy_keeps_any_row_length():
+    """uint16 / uint32 codes travel as int16 / int32 tensors; the host view must work for an odd number of sub-spaces too (it used
+    to build every view of the array, and an int16 row of 3 codes has no uint32 view)"""
+    import torch
+
+    from annlite_amd import ops
+
+    for dt, want in ((torch.uint8, np.uint8), (torch.int16, np.uint16), (torch.int32, np.uint32)):
+        for M in (1, 3, 4):
+            t = torch.arange(2 * M, dtype=dt).reshape(2, M) - (1 if dt != torch.uint8 else 0)
+            a = ops.codes_to_numpy(t)
+            assert a.dtype == want and a.shape == (2, M)
+            assert np.array_equal(a.astype(np.int64) & (np.iinfo(want).max), t.numpy().astype(np.int64) & np.iinfo(want).max)

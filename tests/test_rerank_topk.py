@@ -68,3 +68,51 @@ def test_fused_rerank_equals_gather_topk_gather(ops, metric, D, R, k):
         ok = fi[b] >= 0
         ref = ((x[fi[b][ok]] - q[b]) ** 2).sum(1) if metric == 1 else 1.0 - x[fi[b][ok]] @ q[b]
         assert np.allclose(fd[b][ok], ref, rtol=1e-4, atol=1e-4)
+
+
+def _pairs_rerank():
+    Ds, Rs, ks = [1, 63, 64, 65, 768], [1, 63, 64, 65, 200], [1, 10, 64]
+    return [(D, R, ks[(i + j) % len(ks)]) for i, D in enumerate(Ds) for j, R in enumerate(Rs)]
+
+
+@pytest.mark.parametrize('metric', [1, 2, 3])
+def test_fused_rerank_returns_the_float64_nearest(ops, metric):
+    """Against float64: the returned ids are the k nearest valid candidates, ranks may differ from float64's only between
+    candidates whose float64 distances lie within the fp32 summation bound of each other, and every distance lies within that
+    bound of float64.  Bound per (query, candidate), terms t_j = (x_j - q_j)^2 (EUCLIDEAN) or x_j q_j: the kernel sums
+    ceil(D / 64) terms per lane with fma, then a 6-level butterfly, so |error| <= (2 D + 4) u sum|t_j| + u |d| (u = 2^-24; the
+    2 D covers the chains and the rounding of x_j - q_j, the last term 1 - s)."""
+    u = 2.0 ** -24
+    for D, R, k in _pairs_rerank():
+        rs = np.random.RandomState(1000 * metric + 10 * D + R)
+        N, B = 3000, 6
+        x = rs.randn(N, D).astype(np.float32)
+        q = rs.randn(B, D).astype(np.float32)
+        if metric == 3:
+            x = (x / np.linalg.norm(x.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+            q = (q / np.linalg.norm(q.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+        cand = np.stack([rs.choice(N, R, replace=False) for _ in range(B)]).astype(np.int64)
+        cand[rs.rand(B, R) < 0.15] = -1
+        cand[0, :] = -1                      # no valid candidate
+        if R > 1:
+            cand[1, R - 1] = N + 5           # beyond the table: not a candidate
+        fd, fi = ops.rerank_topk(metric, ops.to_dev(q), ops.to_dev(x), ops.to_dev(cand), k)
+        fd, fi = fd.cpu().numpy(), fi.cpu().numpy()
+        for b in range(B):
+            ids = cand[b][(cand[b] >= 0) & (cand[b] < N)]
+            x64, q64 = x[ids].astype(np.float64), q[b].astype(np.float64)
+            terms = (x64 - q64) ** 2 if metric == 1 else x64 * q64
+            d64 = terms.sum(1) if metric == 1 else 1.0 - terms.sum(1)
+            tol = (2 * D + 4) * u * np.abs(terms).sum(1) + u * np.abs(d64)
+            kk = min(k, ids.size)
+            order = np.argsort(d64, kind='stable')
+            pos = {int(r): j for j, r in enumerate(ids)}
+            got = fi[b, :kk]
+            assert (fi[b, kk:] == -1).all() and np.isinf(fd[b, kk:]).all(), (metric, D, R, k, b)
+            assert len(set(got.tolist())) == kk and all(int(r) in pos for r in got), (metric, D, R, k, b)
+            j_got = np.array([pos[int(r)] for r in got], dtype=np.int64)
+            j_true = order[:kk]
+            # the candidate returned at rank r is as near as float64's rank-r candidate, up to both bounds
+            assert (np.abs(d64[j_got] - d64[j_true]) <= tol[j_got] + tol[j_true]).all(), (metric, D, R, k, b)
+            assert (np.abs(fd[b, :kk].astype(np.float64) - d64[j_got]) <= tol[j_got]).all(), (metric, D, R, k, b)
+            assert (np.diff(fd[b, :kk]) >= 0).all()
