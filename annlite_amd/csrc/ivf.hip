@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256) void ivf_rescore_kernel(const float *__restric
                 d += t[2 * Ks + ((word >> 16) & 0xffu)];
                 d += t[3 * Ks + (word >> 24)];
             }
-            const uint32_t hi = f32_to_ordered(d);
+            const uint32_t hi = f32_to_key(d);  // (every NaN sum one key behind +inf, whatever its sign and payload: ties go by id)
             const uint32_t lo = act ? (uint32_t)(row_ids ? row_ids[row] : row) : kIdNone;
             const unsigned long long pm = __ballot(act && key_less(hi, lo, thr_hi, thr_lo));
             if (pm) wavelist_offer(L, pm, hi, lo, km1, thr_hi, thr_lo, lane);
@@ -480,6 +480,7 @@ extern "C" int annlite_ivf_plan_first(const int32_t *cells_dev, int64_t B, int64
     ANNLITE_REQUIRE(cells_dev && cell_rows_dev && cell_order_dev && vmap_dev && slot_of_dev && tile_rows_dev,
                     "null device pointer");
     const size_t lds = (size_t)(2 * (n_first > 0 ? 2 * C : C) + 16) * 4;
+    ANNLITE_REQUIRE(lds <= 160 * 1024, "n_cells=%lld with two classes of cells does not fit the plan kernel's LDS (%zu B)", (long long)C, lds);
     ANNLITE_HIP_TRY(hipFuncSetAttribute((const void *)ivf_plan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(ivf_plan_kernel, dim3(1), dim3(1024), lds, (hipStream_t)stream, cells_dev, (int)(B * P), (int)P, (int)C,
                        (int)qt, cell_rows_dev, cell_order_dev, (int)n_tiles_max, vmap_dev, slot_of_dev, tile_rows_dev,

@@ -249,7 +249,8 @@ __global__ __launch_bounds__(256) void merge_lists_kernel(const float *dist, con
     const int km1 = k - 1;
     // ids are 64-bit here (global row ids of different shards), so the list is kept directly as
     // (float dist, int64 id) per lane; candidates are offered one by one (G*k is small).
-    // (compared through the order-preserving keys, the scan kernels' own order: NaN sums behind +inf, numpy's rule)
+    // (compared through the order-preserving keys, the scan kernels' own order: NaN sums behind +inf, numpy's rule; the lists
+    // may hold any float, so -0.0 is folded into +0.0 first -- key(-0.0) < key(+0.0), numpy ties them)
     const int total = G * k;
     uint32_t lk = kKeyInfHi;
     int64_t li = INT64_MAX;
@@ -259,7 +260,7 @@ __global__ __launch_bounds__(256) void merge_lists_kernel(const float *dist, con
         const float cd = packed ? __uint_as_float((uint32_t)packed[e * 2 + 1]) : dist[e];
         const int64_t ci = packed ? packed[e * 2] : id[e];
         if (ci < 0) continue;  // padding entry of a short shard
-        const uint32_t ck = f32_to_key(cd);
+        const uint32_t ck = f32_to_key(cd + 0.f);  // (-0.0 as +0.0: the two zeros tie, the id decides -- numpy's order)
         const bool less = (lk < ck) || (lk == ck && li < ci);
         const int pos = __popcll(__ballot(less));
         if (pos > km1) continue;
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float *values, int
     float tf = __builtin_inff();
     for (int64_t base = 0; base < N; base += 64) {
         const int64_t i = base + lane;
-        const float d = (i < N) ? src[i] : __builtin_inff();
+        const float d = (i < N) ? src[i] + 0.f : __builtin_inff();  // (-0.0 as +0.0: the two zeros tie, the index decides)
         const unsigned long long pm = __ballot(i < N && !(d > tf));  // (NaN values: candidates that sort behind +inf, numpy's order)
         if (pm) {
             wavelist_offer(L, pm, f32_to_key(d), (uint32_t)i, km1, th, tl, lane);
@@ -1734,6 +1735,7 @@ static int ivf_search_impl(int lut_kind, const float *queries_dev, int64_t B, in
     // (measured, profiles/r06/ivf_first_tiles_ab.txt: slower at 1 / 2 / 4 -- the first class adds a scan of every cell for a few slots each
     // and the candidates do not shrink in proportion: off by default)
     int64_t n_first = kn.ivf_first >= 0 ? kn.ivf_first : 0;
+    if ((4 * C + 16) * 4 > 160 * 1024) n_first = 0;  // (two classes of so many cells do not fit the plan kernel's LDS: one class)
     if (n_first >= P) n_first = 0;
     // (the plan as an extra workgroup of the preparation launch was measured too: that launch fills every CU with one workgroup each, the
     // extra one ran behind them -- 93.7 us against 69 + 24)

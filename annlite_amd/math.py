@@ -44,7 +44,9 @@ def l2_normalize(x, eps: float = np.finfo(np.float32).eps):
 def top_k(values, k: int, descending: bool = False) -> Tuple:
     """annlite/math.py:94-120 -- k smallest per row, ascending; ties broken by index ascending
     (the reference leaves tie order to numpy's introselect).  k <= 64 runs on the wave-list kernel;
-    larger k falls to a full device sort (torch.sort is stable => same tie rule)."""
+    larger k falls to a full device sort (torch.sort is stable => same tie rule).  numpy's order: -0.0 == +0.0, every NaN
+    behind +inf and tied with every other NaN; a zero comes back as +0.0 and a NaN as the canonical quiet NaN; with ``descending``
+    the values are negated on the way out, so a caller sees -0.0 for either zero and a NaN with its sign bit set."""
     t, is_np = _wrap(values)
     assert t.ndim == 2
     if descending:
@@ -54,6 +56,9 @@ def top_k(values, k: int, descending: bool = False) -> Tuple:
     if 1 <= kk <= 64:
         d, i = ops.topk_rows(t.float().contiguous(), kk)
     else:
+        # (the device sort orders bit patterns: NaNs of different sign / payload and the two zeros would not tie)
+        if t.is_floating_point():
+            t = torch.where(torch.isnan(t), torch.full_like(t, float('nan')), t + 0.0)
         d, i = torch.sort(t, dim=1, stable=True)
         d, i = d[:, :kk], i[:, :kk]
     if descending:

@@ -379,6 +379,39 @@ def ivf_plan(cells: torch.Tensor, n_cells: int, qt: int, cell_rows: torch.Tensor
     return vmap, slot_of, tile_rows, used
 
 
+def ivf_max_tiles_first(B: int, P: int, C: int, qt: int) -> int:
+    return int(lib().annlite_ivf_max_tiles_first(B, P, C, qt))
+
+
+def ivf_plan_first(cells: torch.Tensor, n_cells: int, qt: int, cell_rows: torch.Tensor, cell_order: torch.Tensor, n_first: int):
+    """``ivf_plan`` with the pairs of every query's ``n_first`` nearest cells in tiles of their own, which come first
+    (``annlite_ivf_plan_first``; ``n_first`` 0 or >= P: one class of cells, ``ivf_plan``'s tiles)."""
+    B, P = cells.shape
+    T = ivf_max_tiles_first(B, P, n_cells, qt) if 0 < n_first < P else ivf_max_tiles(B, P, n_cells, qt)
+    dev = cells.device
+    vmap = torch.empty((T * qt,), dtype=torch.int32, device=dev)
+    slot_of = torch.empty((B, P), dtype=torch.int32, device=dev)
+    tile_rows = torch.empty((T, 2), dtype=torch.int64, device=dev)
+    used = torch.empty((1,), dtype=torch.int32, device=dev)
+    check(lib().annlite_ivf_plan_first(cells.data_ptr(), B, P, n_cells, qt, cell_rows.data_ptr(), cell_order.data_ptr(), T,
+                                       vmap.data_ptr(), slot_of.data_ptr(), tile_rows.data_ptr(), used.data_ptr(), int(n_first),
+                                       stream_ptr()), 'ivf_plan_first')
+    return vmap, slot_of, tile_rows, used
+
+
+def ivf_merge_lists(lists: torch.Tensor, slot_of: torch.Tensor, k: int, row_ids: Optional[torch.Tensor] = None,
+                    id_base: int = 0, sqrt: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_ivf_merge_lists``: the per-slot lists ``lists`` i64 [V, k] of keys ``(ordered(sum) << 32) | table row``
+    (ascending, all-ones = none) of every query's P slots -> ([B,k] f32, [B,k] i64) under (distance, external id)."""
+    B, P = slot_of.shape
+    assert lists.dtype == torch.int64 and lists.is_contiguous() and lists.shape[1] == k
+    od = torch.empty((B, k), dtype=torch.float32, device=lists.device)
+    oi = torch.empty((B, k), dtype=torch.int64, device=lists.device)
+    check(lib().annlite_ivf_merge_lists(lists.data_ptr(), k, slot_of.data_ptr(), B, P, _ptr(row_ids), id_base, od.data_ptr(),
+                                        oi.data_ptr(), 1 if sqrt else 0, stream_ptr()), 'ivf_merge_lists')
+    return od, oi
+
+
 def pq_search_tiles(lut_kind: int, queries: torch.Tensor, codebooks: torch.Tensor, codes: torch.Tensor, k: int,
                     M: int, Ks: int, tile_rows: torch.Tensor, vmap: torch.Tensor,
                     valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,

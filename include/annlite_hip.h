@@ -442,7 +442,9 @@ ANNLITE_API int annlite_exact_gather_dist(int metric, const float *queries_dev, 
 /* The same distances FUSED with the top-k (round 6): out[b][0..k) = the k smallest exact distances among cand[b][0..R) in
  * (distance, position in the list) order -- what annlite_exact_gather_dist + annlite_topk_rows + a gather of the ids give, bit for
  * bit -- as (distance, cand id); candidates < 0, >= N or cleared in valid_bits_dev (may be NULL) are skipped, missing places hold
- * (+inf, -1).  k <= 64.  flags: ANNLITE_FLAG_SQRT (EUCLIDEAN results, hnsw/index.py:164-165).  One wave per query. */
+ * (+inf, -1).  A valid candidate whose exact distance is +inf is indistinguishable from a missing place and comes back as
+ * (+inf, -1) too; NaN distances sort behind every +inf (numpy's order) and keep their id.
+ * k <= 64.  flags: ANNLITE_FLAG_SQRT (EUCLIDEAN results, hnsw/index.py:164-165).  One wave per query. */
 ANNLITE_API int annlite_rerank_topk(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
                         const int64_t *cand_dev, int64_t R, const uint32_t *valid_bits_dev, int64_t k, int flags,
                         float *out_dist_dev, int64_t *out_id_dev, void *stream);
@@ -481,7 +483,8 @@ ANNLITE_API int annlite_ivf_plan(const int32_t *cells_dev, int64_t B, int64_t P,
 /* ... with two classes of tiles: the pairs of every query's n_first nearest cells (probe ranks < n_first) in tiles of their own that
  * come FIRST, the other pairs behind them (annlite_ivf_search_topk: the scan shares a query's bound between its tiles; the k best
  * rows of the nearest cells then bound the candidates of the others from the start).  n_tiles_max >= annlite_ivf_max_tiles_first.
- * n_first = 0 or >= P: annlite_ivf_plan. */
+ * n_first = 0 or >= P: annlite_ivf_plan.  Two classes double the kernel's per-cell counters: (4 C + 16) * 4 bytes of LDS, so
+ * C <= 10236 with 0 < n_first < P (ANNLITE_ERR_INVALID above, nothing launched); one class serves C up to 16384. */
 ANNLITE_API int64_t annlite_ivf_max_tiles_first(int64_t B, int64_t P, int64_t C, int64_t qt);
 ANNLITE_API int annlite_ivf_plan_first(const int32_t *cells_dev, int64_t B, int64_t P, int64_t C, int64_t qt,
                            const int64_t *cell_rows_dev, const int32_t *cell_order_dev, int64_t n_tiles_max,

@@ -4,6 +4,7 @@ annlite_exact_gather_dist -> masking -> annlite_topk_rows -> gather of the ids -
 import numpy as np
 import pytest
 
+from _refs import bitmap as _bitmap
 from conftest import has_gpu
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason='needs a GPU')]
@@ -116,3 +117,90 @@ def test_fused_rerank_returns_the_float64_nearest(ops, metric):
             assert (np.abs(d64[j_got] - d64[j_true]) <= tol[j_got] + tol[j_true]).all(), (metric, D, R, k, b)
             assert (np.abs(fd[b, :kk].astype(np.float64) - d64[j_got]) <= tol[j_got]).all(), (metric, D, R, k, b)
             assert (np.diff(fd[b, :kk]) >= 0).all()
+
+
+@pytest.mark.parametrize('metric', [1, 2, 3])
+@pytest.mark.parametrize('D', [20, 130])
+def test_fused_rerank_padding_zero_distances_duplicates_and_non_finite_vectors(ops, metric, D):
+    """The inputs the random cases lack: lists of -1 (some, all), k above the number of valid candidates, a bitmap that deletes
+    the nearest row, vectors EQUAL to the query (distance exactly 0 under every metric: the query is a unit basis vector),
+    the same vector under several ids (the earlier list position wins: the documented order of the fused kernel, which for an
+    ascending list is the lower id), one NaN and one inf coordinate.  WHICH rows may come back: float64 distances, within the
+    fp32 summation bound of the test above.  Their VALUES and order: annlite_exact_gather_dist's bits (the five-launch
+    path), selected here in numpy -- NaN last (behind the +inf of a -1 entry too), ties by position, a +inf distance is reported as
+    (+inf, -1)."""
+    u = 2.0 ** -24
+    rs = np.random.RandomState(10 * D + metric)
+    N, B, R = 60, 7, 70
+    x = rs.randn(N, D).astype(np.float32)
+    q = rs.randn(B, D).astype(np.float32)
+    if metric == 3:
+        x = (x / np.linalg.norm(x.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+        q = (q / np.linalg.norm(q.astype(np.float64), axis=1, keepdims=True)).astype(np.float32)
+    q[0] = 0
+    q[0, 3] = 1.0
+    q[1] = q[0]
+    x[10] = x[11] = x[40] = q[0]          # distance 0 to query 0, three ids
+    x[5] = x[6] = x[7] = x[30]            # one vector, four ids
+    x[20, D - 1] = np.nan
+    x[21, 0] = np.inf
+    x[22, 3] = -np.inf
+    cand = np.stack([rs.permutation(N) for _ in range(B)]).astype(np.int64)
+    cand = np.concatenate([cand, cand[:, :R - N]], axis=1)   # R > N: every row at least once, ten of them twice
+    cand[0] = np.concatenate([np.arange(N), np.arange(R - N)])  # ascending ids: position order is id order
+    cand[1] = cand[0][::-1]                                     # descending: the HIGHER id stands first and wins
+    cand[2, :] = -1                                             # nothing
+    cand[3, 1:] = -1                                            # one candidate
+    cand[3, 0] = 20                                             # ... the NaN vector
+    cand[4, rs.rand(R) < 0.8] = -1
+    cand[5, 5:] = -1
+    valid = np.ones(N, bool)
+    valid[[10, 30, 44]] = False                                 # the nearest row of query 0 and one of the duplicates
+    xd, qd, cd = ops.to_dev(x), ops.to_dev(q), ops.to_dev(cand)
+    for use_valid in (False, True):
+        c2 = cand.copy()
+        if use_valid:
+            c2[(c2 >= 0) & ~valid[np.clip(c2, 0, N - 1)]] = -1
+        exact = ops.exact_gather_dist(metric, qd, xd, ops.to_dev(c2)).cpu().numpy()
+        for k in (1, 10, 64):
+            fd, fi = ops.rerank_topk(metric, qd, xd, cd, k, valid_bits=ops.to_dev(_bitmap(valid)) if use_valid else None)
+            fd, fi = fd.cpu().numpy(), fi.cpu().numpy()
+            for b in range(B):
+                nan = np.isnan(exact[b])
+                o = np.lexsort((np.arange(R), np.where(nan, np.float32(0), exact[b]), nan))[:k]
+                wd = exact[b][o]
+                wi = np.where(wd == np.inf, -1, c2[b][o])
+                assert np.array_equal(fi[b], wi), (metric, D, use_valid, k, b, fi[b][:8], wi[:8])
+                assert np.array_equal(fd[b], wd, equal_nan=True), (metric, D, use_valid, k, b)
+                fin = ~np.isnan(wd)
+                assert np.array_equal(fd[b][fin].view(np.uint32), wd[fin].view(np.uint32))
+                # float64: the rows returned are the nearest valid candidates
+                pos = np.nonzero(c2[b] >= 0)[0]
+                with np.errstate(all='ignore'):
+                    x64, q64 = x[c2[b][pos]].astype(np.float64), q[b].astype(np.float64)
+                    terms = (x64 - q64) ** 2 if metric == 1 else x64 * q64
+                    d64 = terms.sum(1) if metric == 1 else 1.0 - terms.sum(1)
+                    tol = (2 * D + 4) * u * np.abs(terms).sum(1) + u * np.abs(d64)
+                # numbers below +inf first; then everything at +inf -- such candidates and every -1 / deleted position alike,
+                # reported as (+inf, -1) --; NaN distances behind those (numpy's order)
+                n_nan = int(np.isnan(d64).sum())
+                n_num = int((d64 < np.inf).sum())
+                n_inf = R - n_num - n_nan
+                assert (fi[b] >= 0).sum() == min(k, n_num) + min(max(k - n_num - n_inf, 0), n_nan), (metric, D, use_valid, k, b)
+                kk = min(k, n_num)
+                if kk == 0:
+                    continue
+                n64 = np.isnan(d64)
+                o64 = np.lexsort((np.where(n64, 0.0, d64), n64))
+                last = o64[kk - 1]
+                if not np.isfinite(d64[last]):
+                    continue  # (the last number is -inf: only exact ties qualify, checked above)
+                got = {int(r) for r in fi[b] if r >= 0}
+                for j, p in enumerate(pos):
+                    if int(c2[b][p]) in got and np.isfinite(d64[j]):
+                        assert d64[j] <= d64[last] + tol[j] + tol[last], (metric, D, use_valid, k, b, int(c2[b][p]))
+            if k == 64:  # the vectors equal to the query: distance exactly 0, in list order (query 1: the list reversed)
+                want0 = ([11, 40], [40, 11]) if use_valid else ([10, 11, 40], [40, 11, 10])
+                for b in (0, 1):
+                    zero = [int(r) for r in fi[b][fd[b] == 0]]
+                    assert [r for r in zero if r in (10, 11, 40)][:len(want0[b])] == want0[b], (metric, D, use_valid, b, zero)
