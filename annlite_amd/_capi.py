@@ -96,6 +96,13 @@ SYMBOLS = (
     'annlite_debug_items',
     'annlite_debug_prep_timeline',
     'annlite_debug_seed_candidates',
+    'annlite_flat_row_norms',
+    'annlite_flat_list_capacity',
+    'annlite_flat_slack',
+    'annlite_flat_filter',
+    'annlite_flat_search_workspace_bytes',
+    'annlite_flat_search_topk',
+    'annlite_flat_overflow_count',
 )
 
 
@@ -205,6 +212,13 @@ def lib() -> ctypes.CDLL:
     L.annlite_debug_items.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_debug_prep_timeline.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_debug_seed_candidates.argtypes = [vp, i64, i64, vp, vp, i32, i64, i64, i64, vp, i64, vp, vp]
+    L.annlite_flat_row_norms.argtypes = [vp, i64, i64, vp, i64, i64, vp, vp]
+    L.annlite_flat_list_capacity.argtypes = []
+    L.annlite_flat_slack.argtypes = [i32, i64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.annlite_flat_filter.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp]
+    L.annlite_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, i64, i32, vp, vp, vp, sz, vp]
+    L.annlite_flat_overflow_count.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_graph_search_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_graph_search_stats_ex.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     for name in SYMBOLS:

@@ -1,0 +1,402 @@
+// flat.hip -- exact float32 search over un-quantised vectors.
+//
+// The reference's default index (AnnLite without n_subvectors) holds float vectors: HnswIndex.search
+// (annlite/core/index/hnsw/index.py:139-167) or, as brute force, FlatIndex.search (annlite/core/index/flat_index.py:15-39:
+// cdist + top_k).  Here: a dense f32 MFMA contraction FILTERS the table against a per-query bound with a proven slack, the
+// rows that pass are appended to per-query candidate lists, and a wave per query re-scores its list in the arithmetic of
+// rerank_topk_kernel (codec.hip) -- so the answer is exact in that arithmetic whatever the filter's rounding was.
+#include <math.h>
+
+#include "common.h"
+
+namespace annlite {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kFlatTile = 128;            // rows x queries of a workgroup tile (4 waves, 64 x 64 each: 2 x 2 MFMA tiles of 32 x 32)
+constexpr int kFlatDepth = 32;            // coordinates per LDS stage
+constexpr int kFlatLd = kFlatDepth + 1;   // LDS row pitch in floats: 33 keeps the 32 rows of one MFMA operand on 32 banks
+constexpr int kFlatCap = 4096;            // candidates per query list (32 k + 8 sigma at k = 64 is 4096)
+constexpr int64_t kFlatSample = 4096;     // rows of the first (exact) sample; tables up to this size skip the filter
+constexpr double kFlatGrowth = 32.0;      // a stage's row set is at most this many times the previous one
+
+// ---- |x|^2 per row: the lane-strided fmaf chain + butterfly of the exact kernels (relative error <= gamma(ceil(D/64) + 6)) ----
+__global__ __launch_bounds__(256) void flat_norms_kernel(const float *__restrict__ x, int D, const int64_t *__restrict__ ids, int64_t n,
+                                                        int64_t id_base, int64_t capacity, float *__restrict__ norms) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int64_t row = ids ? ids[i] : id_base + i;
+    if (row < 0 || row >= capacity) return;
+    const float *xr = x + row * D;
+    float s = 0.f;
+    for (int j = lane; j < D; j += 64) s = __builtin_fmaf(xr[j], xr[j], s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) norms[row] = s;
+}
+
+// ---- the filter: scores of a tile of rows x a tile of queries on v_mfma_f32_32x32x2_f32 ------------------------------------------
+// Row r of the stage's row set is table row r * stride (r < S).  A workgroup keeps ONE row tile and walks the query tiles
+// blockIdx.y, blockIdx.y + gridDim.y, ...: the table streams from HBM once, the queries (B x D floats) stay in L2.
+// Operands: A = rows (lane l: row l & 31, coordinate l >> 5), B = queries (lane l: coordinate l >> 5, query l & 31); C/D: query =
+// lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  A lane therefore owns ONE query per tile: bound and |q|^2 sit in registers.
+//
+// A row passes when   !(v > thr + (c_rel * a + c_abs))   with a = fl(|x|^2 + |q|^2), v = fl(a - 2 dot) (EUCLIDEAN) or fl(1 - dot):
+// every exact distance <= thr passes (proof: DESIGN.md section 3.6), and a NaN or infinite thr, a, dot or slack passes EVERYTHING
+// (the comparison is written negated for that: section 4's convention).
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+                                                         const float *__restrict__ norms, int64_t S, int64_t stride,
+                                                         const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
+                                                         const float *__restrict__ thr, float c_rel, float c_abs,
+                                                         int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles) {
+    __shared__ float As[kFlatTile * kFlatLd];
+    __shared__ float Bs[kFlatTile * kFlatLd];
+    __shared__ float nxs[kFlatTile];
+    __shared__ int oks[kFlatTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
+    if (tid < kFlatTile) {
+        const int64_t r = r0 + tid;
+        bool ok = r < S;
+        const int64_t row = ok ? r * stride : 0;
+        if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
+        oks[tid] = ok ? 1 : 0;
+        nxs[tid] = ok ? norms[row] : 0.f;
+    }
+    const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
+    const int l31 = lane & 31, lh = lane >> 5;
+    for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
+        const int q0 = qt * kFlatTile;
+        f32x16 acc00, acc01, acc10, acc11;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        for (int k0 = 0; k0 < D; k0 += kFlatDepth) {
+            __syncthreads();  // the previous stage is consumed (first pass: the row tile's norms and flags are written)
+            if constexpr (VEC) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int e = tid + i * 256;  // 1024 slots of 4 floats
+                    const int r = e >> 3, c = (e & 7) * 4;
+                    f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
+                    const int64_t rr = r0 + r;
+                    const int qq = q0 + r;
+                    if (rr < S && k0 + c < D) va = *(const f32x4 *)(x + rr * stride * D + k0 + c);
+                    if (qq < B && k0 + c < D) vb = *(const f32x4 *)(q + (int64_t)qq * D + k0 + c);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        As[r * kFlatLd + c + t] = va[t];
+                        Bs[r * kFlatLd + c + t] = vb[t];
+                    }
+                }
+            } else {
+#pragma unroll 4
+                for (int i = 0; i < 16; ++i) {
+                    const int e = tid + i * 256;  // 4096 floats
+                    const int r = e >> 5, c = e & 31;
+                    const int64_t rr = r0 + r;
+                    const int qq = q0 + r;
+                    As[r * kFlatLd + c] = (rr < S && k0 + c < D) ? x[rr * stride * D + k0 + c] : 0.f;
+                    Bs[r * kFlatLd + c] = (qq < B && k0 + c < D) ? q[(int64_t)qq * D + k0 + c] : 0.f;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < kFlatDepth; kk += 2) {
+                const int kc = kk + lh;
+                const float a0 = As[(wr + l31) * kFlatLd + kc], a1 = As[(wr + 32 + l31) * kFlatLd + kc];
+                const float b0 = Bs[(wq + l31) * kFlatLd + kc], b1 = Bs[(wq + 32 + l31) * kFlatLd + kc];
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11, 0, 0, 0);
+            }
+        }
+        // epilogue: score, compare, append
+#pragma unroll
+        for (int qj = 0; qj < 2; ++qj) {
+            const int qi = q0 + wq + qj * 32 + l31;
+            if (qi >= B) continue;
+            const float qn = qnorm[qi], t = thr[qi];
+            int32_t *my_cnt = cnt + qi;
+            int32_t *my_list = cand + (int64_t)qi * cap;
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri) {
+                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                    if (!oks[rl]) continue;
+                    const float a = nxs[rl] + qn;
+                    const float dot = acc[reg];
+                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
+                    const float bound = t + (c_rel * a + c_abs);
+                    if (!(v > bound)) {
+                        // (a list that has already overflowed takes the slower route whatever else arrives: stop counting)
+                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
+                            const int pos = atomicAdd(my_cnt, 1);
+                            if (pos < cap) my_list[pos] = (int32_t)((r0 + rl) * stride);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---- exact distances + top-k, a wave per query, ties by ROW ID ---------------------------------------------------------------------
+// The per-lane partial sums, the butterfly and the epilogue are rerank_topk_kernel's (codec.hip), operation for operation: the
+// distances are bit-equal to annlite_rerank_topk's.  What differs is the order among equal distances -- the row id instead of the
+// position in the list, so the result does not depend on the order in which the filter's atomics filled the list -- and where the
+// candidates come from:
+//   list != NULL : the query's candidate list (min(cnt[b], cap) entries)
+//   list == NULL : the rows c * stride, c < S (the first sample; a small table; the route of an overflowed query)
+// Only rows valid in the bitmap are offered.  thr_out != NULL: the k-th smallest distance (raw, no sqrt; +inf with fewer than k
+// rows) goes there -- a bound for the next filter stage -- instead of the result arrays.
+__global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+                                                        int64_t N, const int32_t *__restrict__ list, const int32_t *__restrict__ cnt, int cap,
+                                                        int64_t S, int64_t stride, const uint32_t *__restrict__ valid, int k, int do_sqrt,
+                                                        int final_list, int only_overflowed, float *__restrict__ thr_out,
+                                                        float *__restrict__ out_d, int64_t *__restrict__ out_i, int32_t *__restrict__ ovf,
+                                                        uint32_t *__restrict__ ovf_total) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    int64_t n;
+    if (list) {
+        const int c = cnt[b];
+        if (final_list) {
+            const bool over = c > cap;
+            if (lane == 0) {
+                ovf[b] = over ? 1 : 0;
+                if (over) atomicAdd(ovf_total, 1u);
+            }
+            if (over) return;  // (answered by the launch that follows, over all rows)
+        }
+        n = c < cap ? c : cap;
+    } else {
+        if (only_overflowed && !ovf[b]) return;
+        n = S;
+    }
+    constexpr int U = 8;
+    const float *qr = q + (int64_t)b * D;
+    const int32_t *lr = list ? list + (int64_t)b * cap : nullptr;
+    const int km1 = k - 1;
+    WaveList L;
+    L.reset();
+    uint32_t th = kKeyInfHi, tl = kIdNone;
+    for (int64_t c0 = 0; c0 < n; c0 += 64) {
+        const int64_t ci = c0 + lane;
+        int64_t row = -1;
+        if (ci < n) row = lr ? (int64_t)lr[ci] : ci * stride;
+        if (row >= N) row = -1;
+        if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
+        if (__ballot(row >= 0) == 0ull) continue;
+        float mine = __builtin_inff();
+        const int n_here = n - c0 < 64 ? (int)(n - c0) : 64;
+        for (int u0 = 0; u0 < n_here; u0 += U) {
+            float s[U];
+            int64_t rw[U];
+            bool any = false;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                rw[u] = __shfl(row, u0 + u);  // (wave-uniform)
+                s[u] = 0.f;
+                any |= rw[u] >= 0;
+            }
+            if (!any) continue;
+            for (int j = lane; j < D; j += 64) {
+                const float qj = qr[j];
+                float xv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) xv[u] = rw[u] >= 0 ? x[rw[u] * D + j] : 0.f;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (metric == ANNLITE_METRIC_EUCLIDEAN) {
+                        const float d = xv[u] - qj;
+                        s[u] = __builtin_fmaf(d, d, s[u]);
+                    } else {
+                        s[u] = __builtin_fmaf(xv[u], qj, s[u]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) s[u] += __shfl_xor(s[u], o);
+                const float dist = (metric == ANNLITE_METRIC_EUCLIDEAN) ? s[u] : 1.f - s[u];
+                if (lane == u0 + u) mine = dist;
+            }
+        }
+        const float tf = (th == kKeyInfHi) ? __builtin_inff() : ordered_to_f32(th);
+        const unsigned long long pm = __ballot(row >= 0 && !(mine > tf));  // (NaN: behind +inf, numpy's order)
+        if (pm) wavelist_offer(L, pm, f32_to_key(mine), (uint32_t)row, km1, th, tl, lane);
+    }
+    const bool none = (L.hi == kKeyInfHi && L.lo == kIdNone);
+    float d = none ? __builtin_inff() : ordered_to_f32(L.hi);
+    if (thr_out) {
+        if (lane == km1) thr_out[b] = d;
+        return;
+    }
+    if (lane <= km1) {
+        const int64_t id = (none || d == __builtin_inff()) ? (int64_t)-1 : (int64_t)L.lo;
+        if (do_sqrt) d = __builtin_sqrtf(d);
+        out_d[(int64_t)b * k + lane] = d;
+        out_i[(int64_t)b * k + lane] = id;
+    }
+}
+
+// ---- workspace of annlite_flat_search_topk -------------------------------------------------------------------------------------------
+struct FlatWs {
+    uint32_t *ovf_total;  // queries of the last call whose final list overflowed
+    float *thr, *qnorm;
+    int32_t *cnt, *ovf, *cand;
+    size_t bytes;
+};
+static FlatWs flat_carve(void *ws, int64_t B) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    FlatWs w;
+    char *p = (char *)ws;
+    size_t o = 0;
+    w.ovf_total = (uint32_t *)(p + o), o += 256;
+    w.thr = (float *)(p + o), o += up((size_t)B * 4);
+    w.qnorm = (float *)(p + o), o += up((size_t)B * 4);
+    w.cnt = (int32_t *)(p + o), o += up((size_t)B * 4);
+    w.ovf = (int32_t *)(p + o), o += up((size_t)B * 4);
+    w.cand = (int32_t *)(p + o), o += up((size_t)B * kFlatCap * 4);
+    w.bytes = o;
+    return w;
+}
+
+// The slack's two constants.  u = 2^-24.
+static void flat_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
+    const double u = 5.9604644775390625e-08;
+    const double nl = (double)((D + 63) / 64);
+    *c_rel = (float)(1.05 * u * ((double)D + 3.0 * nl + 40.0));
+    *c_abs = metric == ANNLITE_METRIC_EUCLIDEAN ? 1e-30f : (float)(8.0 * u);
+}
+
+static int flat_launch_filter(int metric, const float *q, int64_t B, int64_t D, const float *x, const float *norms, int64_t S, int64_t stride,
+                              const uint32_t *valid, const float *qnorm, const float *thr, int32_t *cand, int32_t *cnt, hipStream_t st) {
+    float c_rel, c_abs;
+    flat_slack(metric, D, &c_rel, &c_abs);
+    const int64_t n_rt = (S + kFlatTile - 1) / kFlatTile;
+    const int n_qt = (int)((B + kFlatTile - 1) / kFlatTile);
+    int64_t ny = (4 * (int64_t)device_cu_count() + n_rt - 1) / n_rt;  // few row tiles: spread the query tiles too
+    ny = ny < 1 ? 1 : ny > n_qt ? n_qt : ny;
+    const dim3 grid((unsigned)n_rt, (unsigned)ny);
+    const bool vec = D % 4 == 0 && ((uintptr_t)q % 16 == 0) && ((uintptr_t)x % 16 == 0);
+    if (vec)
+        hipLaunchKernelGGL(flat_filter_kernel<true>, grid, dim3(256), 0, st, metric, q, (int)B, (int)D, x, norms, S, stride, valid, qnorm, thr,
+                           c_rel, c_abs, cand, cnt, kFlatCap, n_qt);
+    else
+        hipLaunchKernelGGL(flat_filter_kernel<false>, grid, dim3(256), 0, st, metric, q, (int)B, (int)D, x, norms, S, stride, valid, qnorm, thr,
+                           c_rel, c_abs, cand, cnt, kFlatCap, n_qt);
+    return launch_status("flat_filter_kernel");
+}
+
+}  // namespace annlite
+
+using namespace annlite;
+
+extern "C" int annlite_flat_row_norms(const float *vectors_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n, int64_t id_base,
+                                      float *norms_dev, void *stream) {
+    ANNLITE_REQUIRE(capacity >= 0 && D >= 1 && n >= 0 && D <= INT32_MAX, "bad shape");
+    if (n == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(vectors_dev && norms_dev, "null device pointer");
+    hipLaunchKernelGGL(flat_norms_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, vectors_dev, (int)D, ids_dev, n,
+                       id_base, capacity, norms_dev);
+    return launch_status("flat_norms_kernel");
+}
+
+extern "C" int annlite_flat_list_capacity(void) { return kFlatCap; }
+
+extern "C" int annlite_flat_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3 && D >= 1 && c_rel && c_abs, "bad argument");
+    flat_slack(metric, D, c_rel, c_abs);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_filter(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, const float *norms_dev,
+                                   int64_t N, int64_t stride, const uint32_t *valid_bits_dev, const float *query_norms_dev,
+                                   const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev, void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= INT32_MAX, "bad shape");
+    if (B == 0 || N == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && query_norms_dev && bounds_dev && cand_dev && count_dev, "null device pointer");
+    return flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev,
+                              query_norms_dev, bounds_dev, cand_dev, count_dev, (hipStream_t)stream);
+}
+
+extern "C" int annlite_flat_search_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    ANNLITE_REQUIRE(N >= 0 && D >= 1 && B >= 0 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64)");
+    *bytes = (int64_t)flat_carve(nullptr, B).bytes;
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_search_topk(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                        const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
+                                        float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= INT32_MAX,
+                    "bad shape (1 <= k <= 64)");
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_dev && norms_dev)), "null device pointer");
+    const FlatWs w = flat_carve(workspace_dev, B);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
+    const dim3 qgrid((unsigned)((B + 3) / 4));
+    ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
+    if (N <= kFlatSample) {  // the first sample would be the whole table: exact sums over all rows
+        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
+                           kFlatCap, N, (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 0, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
+        return launch_status("flat_exact_kernel");
+    }
+    int rc = annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream);
+    if (rc != ANNLITE_OK) return rc;
+    // stage 0: the k-th smallest exact distance among kFlatSample rows spread over the table
+    hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap,
+                       kFlatSample, N / kFlatSample, valid_bits_dev, (int)k, 0, 0, 0, w.thr, nullptr, nullptr, w.ovf, w.ovf_total);
+    if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
+    // stages 1 .. n: row sets growing by the same factor (<= kFlatGrowth) up to the whole table; each takes the bound of the one before
+    const double ratio = (double)N / (double)kFlatSample;
+    int n_stages = (int)ceil(log(ratio) / log(kFlatGrowth) - 1e-9);
+    if (n_stages < 1) n_stages = 1;
+    for (int s = 1; s <= n_stages; ++s) {
+        int64_t stride = 1;
+        if (s < n_stages) {
+            const double want = (double)kFlatSample * pow(ratio, (double)s / n_stages);
+            stride = (int64_t)((double)N / want);
+            if (stride <= 1) continue;  // (as large as the table already: leave it to the last stage)
+        }
+        const bool last = s == n_stages;
+        ANNLITE_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)B * 4, st));
+        rc = flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev, w.qnorm,
+                                w.thr, w.cand, w.cnt, st);
+        if (rc != ANNLITE_OK) return rc;
+        // (a list that overflowed before the last stage still holds `cap` valid rows: the k-th of ANY k valid rows is a bound)
+        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt, kFlatCap,
+                           (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr,
+                           out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
+        if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
+    }
+    // queries whose last list overflowed: exact sums over all rows (the other waves leave at once)
+    hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap, N,
+                       (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 1, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
+    return launch_status("flat_exact_kernel");
+}
+
+extern "C" int annlite_flat_overflow_count(const void *workspace_dev, void *stream, int64_t *count) {
+    ANNLITE_REQUIRE(workspace_dev && count, "null pointer");
+    uint32_t v = 0;
+    ANNLITE_HIP_TRY(hipMemcpyAsync(&v, workspace_dev, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    ANNLITE_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    *count = (int64_t)v;
+    return ANNLITE_OK;
+}

@@ -14,6 +14,9 @@ Changed on purpose: the vector index per cell 
 GPU scan ``PQFlatGpuIndex`` instead of an HNSW graph walked one query at a time
 (container.py:48-59, 214); ALL queries of a ``search`` call go through one batched launch.
 
+Without ``n_subvectors`` (the reference's default: an un-quantised float ``HnswIndex``) the index is ``FlatGpuIndex``: exact
+float32 search -- an f32 MFMA filter with a proven slack, then exact sums.  No codec, nothing to train.
+
 ``n_cells > 1`` (index.py:125-133, 458-483): a ``VQCodec`` coarse quantiser assigns every vector to a cell and ONE
 ``IvfPQGpuIndex`` holds all cells.  Like the reference (``n_probe = max(n_probe, n_cells)``, index.py:94) a search
 visits every cell, so results equal the single-cell index; ``ivf_prune=True`` (kwarg) makes the search honour
@@ -56,12 +59,12 @@ MAX_TRAINING_DATA_SIZE = 10240  # index.py:23
 
 
 class AnnLite:
-    """MI355X-native drop-in for :class:`annlite.AnnLite` on the PQ search path.
+    """MI355X-native drop-in for :class:`annlite.AnnLite`: the PQ search path, and exact search over float vectors.
 
     :param n_dim: dimensionality of input vectors (divisible by ``n_subvectors``)
     :param metric: 'euclidean', 'inner_product' or 'cosine'
-    :param n_subvectors: number of PQ sub-quantisers = bytes per stored vector (required here: the
-        GPU index is PQ-encoded; the reference's un-quantised float-HNSW path is out of scope)
+    :param n_subvectors: number of PQ sub-quantisers = bytes per stored vector; ``None`` (the default, as in the reference)
+        keeps the float vectors themselves and searches them exactly (``FlatGpuIndex``; ``n_cells`` must be 1, no ``graph``)
     :param n_clusters: codewords per sub-quantiser (default 256)
     :param rerank: keep the float vectors in HBM and re-score ADC candidates exactly (kwarg, rides
         the reference's ``**kwargs`` channel to the index, container.py:56).  With ``n_cells > 1`` and ``ivf_prune=True`` the same channel
@@ -97,7 +100,13 @@ class AnnLite:
         if n_components:
             raise NotImplementedError('n_components (PCA projector) is outside the accelerated hot path (SURVEY.md section 2 row 15)')
         if not n_subvectors:
-            raise NotImplementedError('annlite_amd accelerates the PQ path: pass n_subvectors (the un-quantised float-HNSW index is out of scope)')
+            # the reference's default configuration: an un-quantised float index (FlatGpuIndex: exact search)
+            if n_cells > 1:
+                raise NotImplementedError('n_cells > 1 without n_subvectors (cells over float vectors) is not implemented: pass n_subvectors, '
+                                          'or n_cells=1 for the exact float32 index')
+            if kwargs.get('graph'):
+                raise NotImplementedError('graph=True without n_subvectors (a float HNSW graph) is not implemented: the float index '
+                                          'searches exhaustively and exactly; pass n_subvectors for the graph over PQ codes')
         self.n_dim = n_dim
         self.n_components = n_components
         self.n_subvectors = n_subvectors
@@ -121,7 +130,9 @@ class AnnLite:
         self.data_path = data_path
 
         self._pq_codec = None
-        if self._pq_codec_path.exists():
+        if not n_subvectors:
+            pass  # (no codec: nothing to train)
+        elif self._pq_codec_path.exists():
             logger.info(f'Load trained PQ codec (n_subvectors={self.n_subvectors}) from {self.model_path}')
             self._pq_codec = PQCodec.load(self._pq_codec_path)
         else:
@@ -158,6 +169,15 @@ class AnnLite:
         GPU scan; ``AnnLite(..., graph=True, ef_search=..., max_connection=..., ef_construction=...)`` selects the
         HNSW-over-PQ index with the reference's knobs (graph walked on the GPU, BASELINE config 5)."""
         kw = dict(self._index_kwargs)
+        if self._pq_codec is None:
+            from .core.index.flat_gpu import FlatGpuIndex
+
+            if self._devices is not None and len(self._devices) > 1:
+                warnings.warn('devices= is ignored for the float index (it lives on the current device)')
+            kw.pop('graph', None)
+            for name in ('rerank', 'rerank_pool', 'skewed'):  # (PQ index options: the float index is exact already)
+                kw.pop(name, None)
+            return FlatGpuIndex(dim=self.n_dim, metric=self.metric, **kw)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')
         if self._vq_codec is not None:
@@ -200,6 +220,8 @@ class AnnLite:
     def is_trained(self) -> bool:
         if self._vq_codec is not None and not self._vq_codec.is_trained:  # index.py:929-930
             return False
+        if not self.n_subvectors:  # the float index has nothing to train (index.py:925-932: no codec -> trained)
+            return True
         return bool(self._pq_codec is not None and self._pq_codec.is_trained)
 
     @property
@@ -237,6 +259,8 @@ class AnnLite:
         if self._vq_codec is not None:  # index.py:218-222
             logger.info(f'Start training VQ codec (K={self.n_cells}) with {x.shape[0]} data...')
             self._vq_codec.fit(x)
+        if self._pq_codec is None:  # (force_train on the float index: still nothing to train)
+            return
         self._pq_codec.fit(x)
         if auto_save:
             self.dump_model()
@@ -249,6 +273,8 @@ class AnnLite:
         if self._vq_codec is not None:  # index.py:259-263
             self._vq_codec.partial_fit(x)
             self._vq_codec.build_codebook()
+        if self._pq_codec is None:
+            return
         self._pq_codec.partial_fit(x)
         self._pq_codec.build_codebook()
         if auto_save:
@@ -256,7 +282,8 @@ class AnnLite:
 
     def dump_model(self):
         self.model_path.mkdir(parents=True, exist_ok=True)
-        self._pq_codec.dump(self._pq_codec_path)
+        if self._pq_codec is not None:
+            self._pq_codec.dump(self._pq_codec_path)
         if self._vq_codec is not None:
             self._vq_codec.dump(self._vq_codec_path)  # index.py:684-685
 
@@ -561,9 +588,13 @@ class AnnLite:
     # ------------------------------------------------------------------ codec passthrough (index.py:552-572)
     def encode(self, x):
         self._sanity_check(x)
+        if self._pq_codec is None:
+            raise RuntimeError('this index holds un-quantised float vectors: there is no PQ codec to encode with')
         return self._pq_codec.encode(x)
 
     def decode(self, x):
         assert len(x.shape) == 2
+        if self._pq_codec is None:
+            raise RuntimeError('this index holds un-quantised float vectors: there is no PQ codec to decode with')
         assert x.shape[1] == self.n_subvectors
         return self._pq_codec.decode(x)

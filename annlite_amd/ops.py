@@ -669,3 +669,72 @@ def rerank_topk(metric: int, queries: torch.Tensor, vectors: torch.Tensor, cand:
                                     _ptr(valid_bits), int(k), 1 if sqrt else 0, out_d.data_ptr(), out_i.data_ptr(),
                                     stream_ptr()), 'rerank_topk')
     return out_d, out_i
+
+
+# ---------------------------------------------------------------------------------------------- exact float32 search
+def flat_row_norms(vectors: torch.Tensor, ids: Optional[torch.Tensor] = None, n: Optional[int] = None, id_base: int = 0,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``annlite_flat_row_norms``: ``out[row] = |vectors[row]|^2`` for the rows ``ids`` (i64) or ``id_base .. id_base + n``."""
+    cap, D = vectors.shape
+    if out is None:
+        out = torch.zeros((cap,), dtype=torch.float32, device=vectors.device)
+    cnt = ids.numel() if ids is not None else (cap - id_base if n is None else n)
+    check(lib().annlite_flat_row_norms(vectors.data_ptr(), cap, D, _ptr(ids), cnt, id_base, out.data_ptr(), stream_ptr()), 'flat_row_norms')
+    return out
+
+
+def flat_list_capacity() -> int:
+    return int(lib().annlite_flat_list_capacity())
+
+
+def flat_slack(metric: int, dim: int) -> Tuple[np.float32, np.float32]:
+    """``annlite_flat_slack``: the ``(c_rel, c_abs)`` the filter kernel is launched with (host only, needs no GPU)."""
+    c_rel, c_abs = ctypes.c_float(0), ctypes.c_float(0)
+    check(lib().annlite_flat_slack(int(metric), int(dim), ctypes.byref(c_rel), ctypes.byref(c_abs)), 'flat_slack')
+    return np.float32(c_rel.value), np.float32(c_abs.value)
+
+
+def flat_filter(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
+                valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, stride: int = 1,
+                query_norms: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_flat_filter``: ``(cand i32 [B, cap], count i32 [B])`` -- the rows (in no particular order) that may lie within
+    ``bounds`` f32 [B] of each query; ``count > cap`` marks an overflowed list."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    cap = flat_list_capacity()
+    if query_norms is None:
+        query_norms = flat_row_norms(queries)
+    cand = torch.empty((B, cap), dtype=torch.int32, device=queries.device)
+    count = torch.zeros((B,), dtype=torch.int32, device=queries.device)
+    check(lib().annlite_flat_filter(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, stride, _ptr(valid_bits),
+                                    query_norms.data_ptr(), bounds.data_ptr(), cand.data_ptr(), count.data_ptr(), stream_ptr()), 'flat_filter')
+    return cand, count
+
+
+def flat_search_topk(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, k: int,
+                     valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, sqrt: bool = False,
+                     workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_flat_search_topk``: exact k nearest rows (k <= 64), ``(dist f32 [B, k], ids i64 [B, k])`` ascending by
+    (distance, id), (+inf, -1) padded.  ``flat_overflow_count(workspace)`` reads the call's overflow counter afterwards."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    need = ctypes.c_int64(0)
+    check(lib().annlite_flat_search_workspace_bytes(N, D, B, k, ctypes.byref(need)), 'flat_search_workspace_bytes')
+    dev = queries.device
+    ws = (workspace or ScanWorkspace()).get(int(need.value), dev)
+    od = torch.empty((B, k), dtype=torch.float32, device=dev)
+    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
+    check(lib().annlite_flat_search_topk(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
+                                         int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()),
+          'flat_search_topk')
+    return od, oi
+
+
+def flat_overflow_count(workspace: ScanWorkspace) -> int:
+    """Queries of the last ``flat_search_topk`` on this stream's workspace buffer that took the all-rows route."""
+    buf = workspace.bufs.get(stream_ptr())
+    if buf is None:
+        return 0
+    n = ctypes.c_int64(0)
+    check(lib().annlite_flat_overflow_count(buf.data_ptr(), stream_ptr(), ctypes.byref(n)), 'flat_overflow_count')
+    return int(n.value)

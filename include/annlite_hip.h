@@ -450,6 +450,41 @@ ANNLITE_API int annlite_rerank_topk(int metric, const float *queries_dev, int64_
                         float *out_dist_dev, int64_t *out_id_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Exact float32 search over un-quantised vectors.
+ * replaces: the reference's default index, AnnLite without n_subvectors -- HnswIndex.search on float vectors
+ * (annlite/core/index/hnsw/index.py:139-167) and its brute-force form FlatIndex.search (annlite/core/index/flat_index.py:15-39:
+ * cdist + top_k).  The distances are annlite_rerank_topk's, bit for bit (a document searched with its own vector comes back at
+ * exactly 0); results ascend by (distance, row id), NaN distances behind +inf; rows cleared in valid_bits_dev never appear.
+ * ---------------------------------------------------------------------------------------------- */
+/* norms[row] = |vectors[row]|^2 for row = ids_dev[i] (ids_dev != NULL) or id_base + i, i < n: what add / update call for the rows
+ * they wrote (flat_index.py:41-50 `_data[ids] = x` has no such array: cdist recomputes the norms in every search). */
+ANNLITE_API int annlite_flat_row_norms(const float *vectors_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n,
+                           int64_t id_base, float *norms_dev, void *stream);
+/* Entries a query's candidate list holds (count_dev above it: the list overflowed). */
+ANNLITE_API int annlite_flat_list_capacity(void);
+/* The two constants of the filter's slack, c_rel * fl(|x|^2 + |q|^2) + c_abs, as the filter kernel is handed them (host only; DESIGN.md
+ * section 3.6 derives them).  No reference counterpart. */
+ANNLITE_API int annlite_flat_slack(int metric, int64_t D, float *c_rel, float *c_abs);
+/* The filter stage alone (f32 MFMA contraction; flat_index.py:29 `cdist`): over the rows 0, stride, 2 stride, ... < N that are set in
+ * valid_bits_dev (may be NULL), every row whose exact distance to queries[b] (raw: squared L2, or 1 - <q, x>) is <= bounds_dev[b]
+ * is appended to cand_dev i32 [B][annlite_flat_list_capacity()], in no particular order, together with the few rows the proven
+ * slack lets through; count_dev i32 [B] (zeroed by the caller) counts them.  A NaN or infinite bound passes every row.
+ * query_norms_dev f32 [B] = annlite_flat_row_norms of the queries. */
+ANNLITE_API int annlite_flat_filter(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                        const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
+                        const float *query_norms_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev, void *stream);
+ANNLITE_API int annlite_flat_search_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes);
+/* The search (flat_index.py:15-39, hnsw/index.py:139-167): out [B][k] = the k nearest valid rows of vectors_dev f32 [N][D], (+inf, -1)
+ * where the table has fewer.  norms_dev f32 [N] from annlite_flat_row_norms.  1 <= k <= 64, N < 2^31.  flags: ANNLITE_FLAG_SQRT
+ * (EUCLIDEAN results, hnsw/index.py:164-165).  COSINE expects normalised rows and queries. */
+ANNLITE_API int annlite_flat_search_topk(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                             const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
+                             float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* Queries of the last annlite_flat_search_topk on this workspace whose final candidate list overflowed (they were answered by exact
+ * sums over all rows).  Synchronises the stream.  No reference counterpart. */
+ANNLITE_API int annlite_flat_overflow_count(const void *workspace_dev, void *stream, int64_t *count);
+
+/* ------------------------------------------------------------------------------------------------
  * Pruned (IVF) search over cells (follow-on of rank 4).
  * Reference structure: AnnLite(n_cells > 1): VQCodec coarse quantiser (annlite/core/codec/vq.py),
  * AnnLite._cell_selection (annlite/index.py:458-466: cdist(query, vq codebook) -> top_k(n_probe)),
