@@ -81,6 +81,10 @@ namespace annlite {
 #ifndef ANNLITE_Q8_SPLIT_H
 #define ANNLITE_Q8_SPLIT_H 11  // sub-spaces in the split step's first phase (id 1650 with shared bounds and SKEWED rows; ANNLITE_Q8_SPLIT=12: 12)
 #endif
+#ifndef ANNLITE_Q8_SPLIT_BIAS
+#define ANNLITE_Q8_SPLIT_BIAS 1  // the split step's first phase starts its byte sums from the slots' BIAS bytes and tests bit 7 (q8_st_bound;
+                                 // 0: filter words and the round-8 test -- the A/B build of scripts/build_variant.sh)
+#endif
 
 // Q8Cfg: entries are clipped at QMAX (M * QMAX <= 240: a byte sum never carries); a slot without a bound yet
 // ("open": nothing seeded it) clips at QOPEN, M * QOPEN <= 112, so that T = 127 passes every row.
@@ -378,10 +382,25 @@ __device__ __forceinline__ uint32_t q8_ld_bound(const Q8Lds &o, int q) {
     if constexpr (Q8Cfg<M>::WIDE) return ldsv<unsigned short>(q8_bound_ad<M>(o, q));
     else return ldsv<unsigned char>(q8_bound_ad<M>(o, q));
 }
-template <int M>
+// Split step (HS > 0, ANNLITE_Q8_SPLIT_BIAS): every slot also keeps a BIAS byte, min(255 - b, 255 - 15 HS) for its bound byte b (= 0x80 | T:
+// min(127 - T, ...)), in the 32 bytes at Q8Lds::qmap -- the split step is no cell-tile kernel.  A first-phase byte sum S_H <= 15 HS
+// that starts from the bias never carries, and its bit 7 is clear exactly when S_H <= max(T, 15 HS - 128): the first phase's test is
+// ONE bit per byte (see split_pass1).  A pad slot (b = 0x7f, no flag bit: it never passes) keeps bias 0x80: its table is all zero, and
+// whatever a build leaves there is clipped at QOPEN = 7 (q8_slot_params), so its byte stays within [0x80, 0x80 + 7 HS] -- bit 7 set, no
+// carry.  The two bytes are stored one after the other: a scanning wave may see one a publication older than the other -- an older
+// bound only passes more.
+template <int HS>
+constexpr uint32_t q8_bias_clamp() { return 255u - 15u * (uint32_t)HS; }
+template <int M, int HS = 0>
 __device__ __forceinline__ void q8_st_bound(const Q8Lds &o, int q, uint32_t v) {
     if constexpr (Q8Cfg<M>::WIDE) ldsv_st<unsigned short>(q8_bound_ad<M>(o, q), (unsigned short)v);
     else ldsv_st<unsigned char>(q8_bound_ad<M>(o, q), (unsigned char)v);
+    if constexpr (HS > 0 && ANNLITE_Q8_SPLIT_BIAS != 0) {
+        static_assert(0x80 + Q8Cfg<M>::QOPEN * HS <= 255, "a pad slot's byte never carries");
+        const uint32_t nb = 255u - (v & 0xffu);
+        const uint32_t bias = (v & Q8Cfg<M>::TFLAG) ? (nb < q8_bias_clamp<HS>() ? nb : q8_bias_clamp<HS>()) : 0x80u;
+        ldsv_st<unsigned char>(o.qmap + (uint32_t)q, (unsigned char)bias);
+    }
 }
 template <int M>
 __device__ __forceinline__ uint32_t q8_ld_built(const Q8Lds &o, int q) {  // T the slot's table was built for
@@ -436,7 +455,7 @@ __device__ __forceinline__ void q8_publish_global(const FlushCtx &c, const Q8Lds
     pend_j = ~0ull;
 }
 
-template <int M, bool SKEWED, int QT, int CB, bool ROWS_IN_LDS = false, int LK = 16, bool TL = false>
+template <int M, bool SKEWED, int QT, int CB, bool ROWS_IN_LDS = false, int LK = 16, bool TL = false, int HS = 0>
 __device__ __forceinline__ void q8_consume(const FlushCtx &c, const Q8Lds &o, const unsigned long long (&e)[2], bool (&act)[2],
                                            int lane, uint32_t &n_kept, uint32_t &n_offered, unsigned long long &pend_o,
                                            unsigned long long &pend_j) {
@@ -617,7 +636,7 @@ __device__ __forceinline__ void q8_consume(const FlushCtx &c, const Q8Lds &o, co
                 pend_o = okey;  // (keys only fall)
                 ldsv_st<unsigned long long>(gkl_ad, okey);
                 const uint32_t nb = q8_bound<M>(okey, ldsv<double>(o.c0 + 8u * (uint32_t)lane), ldsv<double>(o.c1 + 8u * (uint32_t)lane));
-                if (nb < q8_ld_bound<M>(o, lane)) q8_st_bound<M>(o, lane, nb);
+                if (nb < q8_ld_bound<M>(o, lane)) q8_st_bound<M, HS>(o, lane, nb);
             }
         }
         if constexpr (LK == 64) {
@@ -636,7 +655,7 @@ __device__ __forceinline__ void q8_consume(const FlushCtx &c, const Q8Lds &o, co
 // (Re)build of a workgroup's table: slot parameters (one thread per slot) from the best bound known for the query, then
 // the byte table.  Out of line on purpose: it runs a dozen times per work item, and inlined into the step loop its 40
 // live registers made the compiler spill the loop-invariant LDS base registers of the look-ups into the hot path.
-template <int M, int NW, int NQ, int LK = 16, bool TL = false>
+template <int M, int NW, int NQ, int LK = 16, bool TL = false, int HS = 0>
 __device__ __attribute__((noinline)) void q8_rebuild(q8_kernarg_ptr ka, int tile, int first, int slice) {
     constexpr int QT = q8_qt<M, NQ>();
     static_assert(!TL || (M == 16 && NQ == 2 && LK == 16), "cell tiles: the M = 16 kernel with 16-key lists");
@@ -694,7 +713,7 @@ __device__ __attribute__((noinline)) void q8_rebuild(q8_kernarg_ptr ka, int tile
                 const uint32_t t2 = q8_bound_from_key<M>(key_now, a.smax[b], step, a.qlo[b]);
                 tnow = t2 < tb ? t2 : tb;
             }
-            q8_st_bound<M>(o, tid, tnow);
+            q8_st_bound<M, HS>(o, tid, tnow);
             if constexpr (Q8Cfg<M>::WIDE) ldsv_st<unsigned short>(o.tb + 2u * (uint32_t)tid, (unsigned short)tb);
             else ldsv_st<unsigned char>(o.tb + (uint32_t)tid, (unsigned char)tb);
         }
@@ -1129,6 +1148,8 @@ __device__ __attribute__((noinline)) void q8_finish_item(q8_kernarg_ptr ka, int 
 // that pass (the survivors) go to a per-wave ring of row ids in LDS (q8_split_ring); once it holds 64, a step runs over them with
 // all 16 sub-spaces (code rows re-fetched from L2 and rotated to the lane's skew).  A step where more than q8_split_fallback<HS>()
 // rows survive finishes in place instead.  The ring is emptied before every epoch end.  HS = 0: the one-phase step.
+// (Round 9, ANNLITE_Q8_SPLIT_BIAS: the first phase's sums start from the slots' bias bytes and its test is bit 7 of every byte --
+// S_HS <= max(T, 15 HS - 128), see q8_st_bound; the full tests are the unchanged ones.)
 template <int HS>
 constexpr int q8_split_fallback() { return (64 * (16 - HS)) / 20; }  // (finishing in place costs 2 (16 - HS) look-ups per row, a survivor ~32 / 64 of a step)
 constexpr int kSplitRing = 128;  // survivor ring entries per scanning wave (u32 row ids): < 64 waiting + at most 64 pushed
@@ -1136,7 +1157,7 @@ constexpr int kSplitRing = 128;  // survivor ring entries per scanning wave (u32
 template <int M, int NW, bool SKEWED, int NQ, int CB, bool RQ, int LK = 16, bool TL = false, int HS = 0>
 __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const ScanArgs a) {
     static_assert(!TL || (M == 16 && NQ == 2 && CB == 1 && RQ && LK == 16), "cell tiles: the M = 16 row-queue kernel with 16-key lists");
-    static_assert(HS == 0 || (M == 16 && NQ == 2 && CB == 1 && RQ && SKEWED && HS > 0 && HS < 16), "the split step: M = 16, row queue, SKEWED rows");
+    static_assert(HS == 0 || (M == 16 && NQ == 2 && CB == 1 && RQ && SKEWED && !TL && HS > 0 && HS < 16), "the split step: M = 16, row queue, SKEWED rows, no cell tiles");
     static_assert(LK == 16 || (LK == 64 && (RQ || M != 16) && M != 64), "64-key lists: M = 16 with the row queue (4-byte ring entries), M = 8 / 32");
     constexpr uint32_t RE = (uint32_t)q8_ring_entry_bytes<M, LK>();  // bytes of a ring entry
     constexpr bool WIDE = Q8Cfg<M>::WIDE;
@@ -1229,7 +1250,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
             }
             __syncthreads();
             if (ldsv<uint32_t>(lds.ctl)) {
-                q8_rebuild<M, NW, NQ, LK, TL>(ka, tile, 0, slice);
+                q8_rebuild<M, NW, NQ, LK, TL, HS>(ka, tile, 0, slice);
                 if (a.dbg && tid == 0) atomicAdd(a.dbg + 5, 1ull);
             }
         };
@@ -1242,7 +1263,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
             ldsv_st<uint32_t>(lds.arrived(), 0);
             ldsv_st<uint32_t>(lds.blk_ctr(), 0);  // the block counter the scanning waves draw from
         }
-        q8_rebuild<M, NW, NQ, LK, TL>(ka, tile, 1, slice);  // (its barriers cover the initialisation above)
+        q8_rebuild<M, NW, NQ, LK, TL, HS>(ka, tile, 1, slice);  // (its barriers cover the initialisation above)
         stamp(1);
 
         // epochs end after steps q8_epoch0, q8_epoch0 * mul + (mul - 1), ... and after the last step
@@ -1342,7 +1363,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                 if (real && part == 0 && bound < ldsv<unsigned long long>(gkl_ad)) {
                     ldsv_st<unsigned long long>(gkl_ad, bound);
                     const uint32_t nb = q8_bound<M>(bound, ldsv<double>(lds.c0 + 8u * (uint32_t)q), ldsv<double>(lds.c1 + 8u * (uint32_t)q));
-                    if (nb < q8_ld_bound<M>(lds, q)) q8_st_bound<M>(lds, q, nb);
+                    if (nb < q8_ld_bound<M>(lds, q)) q8_st_bound<M, HS>(lds, q, nb);
                 }
             };
             // Every scanning wave pushes into its OWN ring of kWaveRing entries (it alone writes the ring and its tail, the
@@ -1489,7 +1510,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                             ldsv_st<u32x2>(park, (u32x2){pmr[0], pmr[1]});
                             rowq_more = __ballot((pmr[0] | pmr[1]) != 0u) != 0;
                         }
-                        q8_consume<M, SKEWED, QT, CB, ROWQ, LK, TL>(fc, lds, e, act, lane, n_kept, n_offered, pend_o, pend_j);
+                        q8_consume<M, SKEWED, QT, CB, ROWQ, LK, TL, HS>(fc, lds, e, act, lane, n_kept, n_offered, pend_o, pend_j);
                         __builtin_amdgcn_s_setprio(0);
                         ++n_batches;
                         if (a.dbg) t_busy += __builtin_readcyclecounter() - t0;
@@ -1698,8 +1719,21 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     }
                 }
             };
+            // Split step with bias words (ANNLITE_Q8_SPLIT_BIAS): what the step loop keeps in thw[] are the slots' BIAS bytes (q8_st_bound), the
+            // start values of the first phase's byte sums.  The rare parts, which test full sums, load the filter words over them for as long
+            // as they run: the loop never holds both sets.
+            constexpr bool BIAS = HS > 0 && ANNLITE_Q8_SPLIT_BIAS != 0;
+            auto load_stepw = [&](uint32_t (&t)[NF]) {
+                if constexpr (BIAS) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const u32x4 v = *(volatile ANNLITE_LDS u32x4 *)(uintptr_t)(lds.qmap + 16u * (uint32_t)h);
+                        t[4 * h + 0] = v.x, t[4 * h + 1] = v.y, t[4 * h + 2] = v.z, t[4 * h + 3] = v.w;
+                    }
+                } else load_thw(t);
+            };
             uint32_t thw[NF];
-            load_thw(thw);
+            load_stepw(thw);
             // byte sums of the row for both entry groups (4 dwords x 4 x u8 each): the 2 M look-ups run through a ring of
             // DEPTH landing registers -- look-up i + DEPTH is issued as soon as look-up i has been added (all M look-ups
             // of a group in flight, as the u16 kernel has them, takes 64 landing VGPRs: with them the allocator spilled
@@ -1875,6 +1909,16 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     for (int e = 0; e < 4; ++e) anyv |= (thw[4 * h + e] - (acc[h][e] & 0x7f7f7f7fu)) & ~acc[h][e];
                 return (anyv & 0x80808080u) != 0u;
             };
+            // ... of the first phase with bias words: the byte of query q holds S_H + bias_q <= 255, bit 7 clear <=> S_H <= max(T_q, 15 HS - 128)
+            // -- S_H <= T_q bit for bit down to T_q = 15 HS - 128, looser below (the full test of a survivor is the unchanged one)
+            auto split_pass1 = [&](const u32x4 (&acc)[2]) -> bool {
+                uint32_t allv = ~0u;
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) allv &= acc[h][e];
+                return (~allv & 0x80808080u) != 0u;
+            };
             // the survivor ring of this wave: entries [sv_h, sv_h + sv_c) mod kSplitRing (sv_h is 0 or 64: the ring is taken 64 at a time)
             const uint32_t sv_ad = lds.qmap + 128u + (uint32_t)wave * (uint32_t)(kSplitRing * 4);
             constexpr int HS1 = HS > 0 ? HS : 1;  // (the lambdas below are compiled for HS = 0 too, and never called there)
@@ -1905,11 +1949,15 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     constexpr int i = decltype(I)::value, j = i + PD;
                     // (where the next block's look-ups are issued, the adds are held behind the barrier every second sub-space: left
                     // free, the scheduler hoisted the drain and the pass test above them and issued the next look-ups only after
-                    // lgkmcnt(0))
-                    if constexpr (j >= TOT && i % 4 == 0) asm volatile("" : "+v"(acc[0]), "+v"(acc[1])::"memory");
+                    // lgkmcnt(0).  With bias words they are held there through the whole phase: with the bias as a twelfth addend the
+                    // scheduler otherwise sank the adds below the look-ups, kept two dozen landing registers live and the allocator
+                    // reloaded the lane constants mbase[] from scratch in every step.  Pairs of sub-spaces still add as v_add3_u32)
+                    if constexpr ((BIAS || j >= TOT) && i % 4 == 0 && i > 0) asm volatile("" : "+v"(acc[0]), "+v"(acc[1])::"memory");
                     else asm volatile("" ::: "memory");
-                    if constexpr (i < 2) acc[i] = ring[i % PD];
-                    else acc[i % 2] += ring[i % PD];
+                    if constexpr (i < 2) {
+                        if constexpr (BIAS) acc[i] = ring[i % PD] + (u32x4){thw[4 * i], thw[4 * i + 1], thw[4 * i + 2], thw[4 * i + 3]};
+                        else acc[i] = ring[i % PD];
+                    } else acc[i % 2] += ring[i % PD];
                     if constexpr (j < TOT) split_fetch(ring[j % PD], ccur, ad, std::integral_constant<int, j>{});
                     else split_fetch(nr[j - TOT], cnext, an, std::integral_constant<int, j - TOT>{});
                 });
@@ -1920,7 +1968,10 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
             // finishes in place: split_finish), else the survivors are queued
             auto split_head = [&](auto vmask, uint32_t row0, u32x4 (&acc)[2]) -> bool {  // (generic: instantiated by HS > 0 only)
                 split_first(acc);
-                const unsigned long long alive = __ballot(split_pass(acc)) & vmask;
+                bool pass;
+                if constexpr (BIAS) pass = split_pass1(acc);
+                else pass = split_pass(acc);
+                const unsigned long long alive = __ballot(pass) & vmask;
                 const uint32_t n = (uint32_t)__popcll(alive);
                 if (a.dbg) n_rows_a += (uint32_t)__popcll(vmask);
                 if (n > (uint32_t)q8_split_fallback<HS1>()) return true;
@@ -2070,6 +2121,16 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                         u32x4 acc[2];
                         const bool fb = split_head(vmask, row0, acc);
                         if (fb || sv_c >= 64u) {  // (rare: the next block's first look-ups are dropped here and issued again below)
+                            if constexpr (BIAS) {
+                                if (fb) {  // finishing in place: the bias out of the first-phase sums (no borrow: every byte holds S_H + bias)
+#pragma unroll
+                                    for (int h = 0; h < 2; ++h)
+#pragma unroll
+                                        for (int e = 0; e < 4; ++e) acc[h][e] -= thw[4 * h + e];
+                                }
+                                asm volatile("" ::: "memory");
+                                load_thw(thw);  // (full sums reach 240: the filter words and their test)
+                            }
                             if (fb) {
                                 rem = split_finish(vmask, acc);
                                 if (rem && !(a.dbg_skip & 4)) push_rows(rem, row0 + (uint32_t)lane);
@@ -2081,6 +2142,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                             }
                             asm volatile("" ::: "memory");
                             split_prefix(cnext);
+                            if constexpr (BIAS) load_stepw(thw);
                         }
                     } else {
                         make_addr(ccur);
@@ -2178,13 +2240,16 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     // pick up the workgroup's bounds every 2nd step (every 8th where a work item scans >= 500k rows: ScanArgs::q8_thw_mask)
                     if ((it_no & thw_mask) == thw_mask) {
                         asm volatile("" ::: "memory");
-                        load_thw(thw);
+                        load_stepw(thw);
                     }
                     b_cur = b_nxt;
                     b_nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)pend);
                 }
                 if constexpr (HS > 0) {  // (nothing may wait in the survivor ring when the lists are published or the table rebuilt)
-                    if (sv_c) split_tail(sv_c);
+                    if (sv_c) {
+                        if constexpr (BIAS) load_thw(thw);  // (the second phase tests full sums)
+                        split_tail(sv_c);
+                    }
                     sv_h = sv_c = 0u;
                 }
                 if (lane == 0) lds_add_u32(lds.arrived(), 1u);
@@ -2194,7 +2259,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                 if (a.dbg) t_wait += __builtin_readcyclecounter() - tw;
                 if (final) stamp(3);
                 if (final) break;
-                load_thw(thw);
+                load_stepw(thw);
             }
             if (a.dbg && lane == 0 && !(a.dbg_skip & 8)) {  // [0] wave-steps with a candidate, [1] entries pushed, [7] wave 0's cycles at epoch ends
                 atomicAdd(a.dbg + 0, (unsigned long long)n_slow);
