@@ -1,7 +1,8 @@
 """The plugin contract ``CellContainer`` programs against (annlite/core/index/base.py): construction from
 ``dim / dtype / metric / initial_size / expand_step_size / expand_mode``, ``capacity`` and ``size``, the three
 mutators every index implements, ``reset``.  Growth policy: capacity starts at ``initial_size`` (or one expansion
-step) and the concrete index enlarges it in multiples of ``expand_step_size``."""
+step) and the concrete index enlarges it in multiples of ``expand_step_size`` (the single-device indexes: through
+``row_store.RowStoreIndex``)."""
 import abc
 from typing import List, Optional, Union
 
@@ -19,6 +20,12 @@ def str2dtype(dtype_str: str):
         return _DTYPES[dtype_str]
     except KeyError:
         raise TypeError(f'Unrecognized dtype string: {dtype_str}') from None
+
+
+def drop_hnsw_kwargs(kwargs: dict):
+    """HNSW-only kwargs the reference forwards to every index are accepted and ignored by the exhaustive ones."""
+    for name in ('ef_construction', 'ef_search', 'max_connection'):
+        kwargs.pop(name, None)
 
 
 class BaseIndex(abc.ABC):

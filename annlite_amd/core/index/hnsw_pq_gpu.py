@@ -29,6 +29,7 @@ from ... import _graph_capi as gc
 from ... import ops
 from ...enums import Metric
 from .pq_flat_gpu import PQFlatGpuIndex
+from .row_store import empty_answer, like_input, ranked_answer
 
 
 class HnswPQGpuIndex(PQFlatGpuIndex):
@@ -247,8 +248,7 @@ class HnswPQGpuIndex(PQFlatGpuIndex):
         B, k = q.shape[0], int(limit)
         N = self._n_rows
         if N == 0 or B == 0 or (self._graph is None and (self._gg is None or self._gg.n == 0)):
-            d = torch.full((B, k), float('inf'), dtype=torch.float32, device=q.device)
-            i = torch.full((B, k), -1, dtype=torch.int64, device=q.device)
+            d, i = empty_answer(B, k, q.device)
         else:
             ef = max(int(ef_search or self.ef_search), k)
             cand, cand_d = self.candidates(q, ef)
@@ -258,21 +258,15 @@ class HnswPQGpuIndex(PQFlatGpuIndex):
                 # L2 tables: same table, same ascending-m fp32 chain as annlite_adc_gather, bit for bit) and its list is ascending
                 # with the deleted rows blanked (-1, +inf) -- the result is the list's first k real entries: no table build, no
                 # gather.  (cosine / inner product: the metric's tables differ from the walk's -- the gather below.)
-                kk = min(k, ef)
-                d, pos = ops.topk_rows(cand_d, kk)
-                i = torch.gather(cand, 1, pos.clamp(min=0))
-                i = torch.where((pos < 0) | torch.isinf(d), torch.full_like(i, -1), i)
-                d = torch.sqrt(d)  # hnsw/index.py:164-165
-                if kk < k:
-                    d = torch.cat([d, torch.full((B, k - kk), float('inf'), device=d.device)], dim=1)
-                    i = torch.cat([i, torch.full((B, k - kk), -1, dtype=torch.int64, device=i.device)], dim=1)
-                return (d.cpu().numpy(), i.cpu().numpy()) if is_np else (d, i)
+                # (an early return of its own: the steps below would build the metric's tables and gather for nothing)
+                d, pos = ops.topk_rows(cand_d, min(k, ef))
+                return like_input(is_np, *ranked_answer(cand, d, pos, k, sqrt=True))
             if self.rerank and self._vectors is not None and k <= 64:
                 # (round 6) exact distances of the candidates + validity screen + top-k + sqrt in ONE launch, one wave per query:
                 # the same numbers as the steps below, bit for bit (annlite_rerank_topk)
                 d, i = ops.rerank_topk(int(self.metric), q, self._vectors, cand, k, valid_bits=self._valid,
                                        sqrt=self.metric == Metric.EUCLIDEAN)
-                return (d.cpu().numpy(), i.cpu().numpy()) if is_np else (d, i)
+                return like_input(is_np, d, i)  # (the kernel's answer is final: nothing of the epilogue below applies)
             # rows deleted after the walk started / never written are masked here as well
             ok = (cand >= 0) & self._valid_bool[cand.clamp(min=0)]
             cand = torch.where(ok, cand, torch.full_like(cand, -1))
@@ -284,18 +278,9 @@ class HnswPQGpuIndex(PQFlatGpuIndex):
                 kind, xq = self._scan_inputs(x, q)  # (host buffers: normalised like the flat index's queries, bit for bit)
                 lut = ops.lut_build(xq, self.pq_codec.codebooks_dev, kind, LAYOUT_BMK)  # [B, M, Ks] on the device
                 dist = ops.adc_gather(lut, self._plain_table(N), cand)
-            kk = min(k, ef)
-            d, pos = self._topk_rows_any(dist, kk)
-            i = torch.gather(cand, 1, pos.clamp(min=0))
-            i = torch.where((pos < 0) | torch.isinf(d), torch.full_like(i, -1), i)
-            if self.metric == Metric.EUCLIDEAN:
-                d = torch.sqrt(d)  # hnsw/index.py:164-165
-            if kk < k:
-                d = torch.cat([d, torch.full((B, k - kk), float('inf'), device=d.device)], dim=1)
-                i = torch.cat([i, torch.full((B, k - kk), -1, dtype=torch.int64, device=i.device)], dim=1)
-        if is_np:
-            return d.cpu().numpy(), i.cpu().numpy()
-        return d, i
+            d, pos = self._topk_rows_any(dist, min(k, ef))
+            d, i = ranked_answer(cand, d, pos, k, sqrt=self.metric == Metric.EUCLIDEAN)
+        return like_input(is_np, d, i)
 
     def _plain_table(self, N: int) -> torch.Tensor:
         """Code rows in sub-space order for the gather kernel (cached; rebuilt after inserts)."""

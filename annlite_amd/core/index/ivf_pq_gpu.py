@@ -11,7 +11,8 @@ Semantics:
     nearest cells; the result is the exact top-k of those rows under the fixed order (distance asc, id asc).
 
 Layout in HBM on top of the flat index's storage (codes by offset, validity, optional float vectors):
-  * ``_cell_of``  i32 [capacity]        cell of every offset (nearest centroid in squared L2, vq.py:81-90)
+  * ``_cell_of``  i32 [capacity]        cell of every offset (nearest centroid in squared L2, vq.py:81-90): one more column
+                                        of the row store (row_store.py), grown with the others
   * sealed view, rebuilt lazily after a mutation (one sort + one gather over the live rows):
       ``_table``     u8 [Nt, M] SKEWED by table row: the live rows grouped by cell, every cell starts at a
                      multiple of 64 rows, ascending offset inside a cell
@@ -36,6 +37,7 @@ from ...enums import Metric
 from ..codec.pq import PQCodec
 from ..codec.vq import VQCodec
 from .pq_flat_gpu import PQFlatGpuIndex
+from .row_store import empty_answer, like_input, ranked_answer
 
 
 class IvfPQGpuIndex(PQFlatGpuIndex):
@@ -47,7 +49,6 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
         assert vq_codec is not None, 'IvfPQGpuIndex needs a VQCodec'
         self.vq_codec = vq_codec
         self.n_probe = n_probe  # None: every cell (the reference's behaviour)
-        self._cell_of = None
         self._sealed = False
         self._table = self._table_plain = self._row_ids = self._cell_rows = self._cell_order = self._pos_of = None
         self.cand_cap = 256  # emitted candidates per (query, cell) list; an overflowing list falls back to the whole cell
@@ -71,17 +72,15 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
         return self.vq_codec.n_clusters
 
     # ------------------------------------------------------------------ storage
+    def _columns(self):
+        return {**super()._columns(), '_cell_of': ((), torch.int32)}  # (a column: a growth carries the cells along)
+
     def _alloc(self, capacity: int):
-        old = self._cell_of
         super()._alloc(capacity)
-        self._cell_of = torch.zeros((capacity,), dtype=torch.int32, device=self._codes.device)
-        if old is not None:
-            n = min(old.numel(), capacity)
-            self._cell_of[:n] = old[:n]
-        self._sealed = False
+        self._sealed = False  # (new storage, whoever asked for it: the sealed view is of the old one)
 
     def add_with_ids(self, x, ids, **kwargs):
-        ids_t = ops.to_dev(np.asarray(ids, dtype=np.int64) if not isinstance(ids, torch.Tensor) else ids, torch.int64)
+        ids_t = self._ids_to_dev(ids)
         if ids_t.numel() == 0:
             return
         super().add_with_ids(x, ids_t)  # codes / validity / float vectors exactly as the flat index stores them
@@ -97,7 +96,6 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
 
     def reset(self, capacity: Optional[int] = None):
         super().reset(capacity=capacity)
-        self._cell_of = None
         self._sealed = False
 
     # ------------------------------------------------------------------ sealed (cell-sorted) view
@@ -175,16 +173,13 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
             'pruned search needs the quantised-filter scan plan (M in {8,16,32,64}, Ks <= 256)'
         dev = q.device
         if self._n_rows == 0 or B == 0:
-            d = torch.full((B, k), float('inf'), dtype=torch.float32, device=dev)
-            i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+            d, i = empty_answer(B, k, dev)
         else:
             self._seal()
             d, i = self._search_pruned(q, k, max(1, int(P)), indices, rerank_k)
             if row_base:
                 i = torch.where(i >= 0, i + row_base, i)
-        if is_np:
-            return d.cpu().numpy(), i.cpu().numpy()
-        return d, i
+        return like_input(is_np, d, i)
 
     def search_batch_packed(self, x, limit: int, row_base: int = 0):
         """(row-sharded search, sharded.py) the packed fast path is the exhaustive scan's: with pruning active the
@@ -201,7 +196,7 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
         """``indices`` filter (offsets) as a bitmap over TABLE rows; None = every stored row."""
         if indices is None:
             return None  # the cell ranges hold live rows only; padding lies outside every range
-        idx = ops.to_dev(np.asarray(indices, dtype=np.int64) if not isinstance(indices, torch.Tensor) else indices, torch.int64)
+        idx = self._ids_to_dev(indices)
         idx = idx[(idx >= 0) & (idx < self._pos_of.numel())]
         pos = self._pos_of[idx]
         pos = pos[pos >= 0]
@@ -317,14 +312,7 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
             return ops.rerank_topk(int(self.metric), q, self._vectors, ids.contiguous(), k_out, sqrt=self.metric == Metric.EUCLIDEAN)
         exact = ops.exact_gather_dist(int(self.metric), q, self._vectors, ids)
         d, pos = self._topk_rows_any(exact, min(k_out, ids.shape[1]))  # (k_out > 64: a stable device sort, never cut silently)
-        i = torch.gather(ids, 1, pos.clamp(min=0))
-        i = torch.where((pos < 0) | torch.isinf(d), torch.full_like(i, -1), i)
-        if self.metric == Metric.EUCLIDEAN:
-            d = torch.sqrt(d)
-        if d.shape[1] < k_out:
-            d = torch.cat([d, torch.full((d.shape[0], k_out - d.shape[1]), float('inf'), device=d.device)], dim=1)
-            i = torch.cat([i, torch.full((i.shape[0], k_out - i.shape[1]), -1, dtype=torch.int64, device=i.device)], dim=1)
-        return d, i
+        return ranked_answer(ids, d, pos, k_out, sqrt=self.metric == Metric.EUCLIDEAN)
 
     # ------------------------------------------------------------------ persistence
     def dump(self, index_file):

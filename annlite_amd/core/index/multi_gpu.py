@@ -22,7 +22,8 @@ import numpy as np
 import torch
 
 from ...enums import Metric
-from .base import BaseIndex
+from .base import BaseIndex, drop_hnsw_kwargs
+from .row_store import pad_to_k
 
 
 class _OnDevice:
@@ -59,18 +60,13 @@ def merge_lists_sorted(d: torch.Tensor, i: torch.Tensor, k: int) -> Tuple[torch.
     by_d = torch.argsort(torch.where(nan, torch.full_like(dd, float('inf')), dd), dim=1, stable=True)
     cls = torch.gather(nan.to(torch.int8) + 2 * pad.to(torch.int8), 1, by_d)
     by_d = torch.gather(by_d, 1, torch.argsort(cls, dim=1, stable=True))[:, :k]
-    od, oi = torch.gather(dd, 1, by_d), torch.gather(ii, 1, by_d)
-    if od.shape[1] < k:
-        od = torch.cat([od, torch.full((B, k - od.shape[1]), float('inf'), dtype=od.dtype, device=od.device)], dim=1)
-        oi = torch.cat([oi, torch.full((B, k - oi.shape[1]), -1, dtype=oi.dtype, device=oi.device)], dim=1)
-    return od, oi
+    return pad_to_k(torch.gather(dd, 1, by_d), torch.gather(ii, 1, by_d), k)
 
 
 class MultiGpuPQIndex(BaseIndex):
     def __init__(self, dim: int, pq_codec=None, metric: Metric = Metric.COSINE, devices: Sequence[int] = (0,), block: int = 65536,
                  shard_factory: Optional[Callable] = None, merge_packed: Optional[Callable] = None, **kwargs):
-        for kk in ('ef_construction', 'ef_search', 'max_connection'):
-            kwargs.pop(kk, None)
+        drop_hnsw_kwargs(kwargs)
         super().__init__(dim, metric=metric, **{k: v for k, v in kwargs.items() if k in ('dtype', 'initial_size', 'expand_step_size', 'expand_mode')})
         assert pq_codec is not None, 'MultiGpuPQIndex needs a PQCodec'
         assert len(devices) >= 1 and block >= 64 and block % 64 == 0

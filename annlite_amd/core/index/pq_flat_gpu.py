@@ -16,14 +16,16 @@ metric-aware and batched, with ``HnswIndex``'s pre/post-processing so it is a dr
 plus ``search_batch(X[B,D], limit)`` so that a whole ``AnnLite.search(docs)`` call is one launch
 instead of the reference's per-query python loop (annlite/container.py:214).
 
+Storage, validity, the mutation protocol, ``search`` and the file envelope are ``RowStoreIndex``'s (row_store.py), shared with
+``FlatGpuIndex``; this module declares the columns, writes them (SKEWED where the fast scan plan applies) and searches them.
+
 Data layout in HBM: one ``uint8 [capacity, M]`` code table, stored pre-SKEWED (row n
 rotated left by n mod M bytes) when the fast scan plan applies; a ``uint32`` validity bitmap (delete
 marks / never-written rows); optionally the raw ``float32 [capacity, D]`` vectors for the exact
 re-rank stage (``rerank=True``; 10M x 128 fp32 = 5.1 GB of the 288 GB).
 """
-import math
 from pathlib import Path
-from typing import List, Optional, Tuple, Union
+from typing import Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -33,7 +35,7 @@ from ..._capi import CODES_PLAIN, CODES_SKEWED, ScanState, scan_plan
 from ...enums import ExpandMode, Metric
 from ...math import l2_normalize_host
 from ..codec.pq import PQCodec
-from .base import BaseIndex
+from .row_store import RowStoreIndex, empty_answer, float_from_key, float_order_key, like_input, pad_to_k, ranked_answer
 
 
 class SplitBatch:
@@ -44,7 +46,10 @@ class SplitBatch:
         self.union, self.scan, self.plain, self._keep = union, scan, plain, keep
 
 
-class PQFlatGpuIndex(BaseIndex):
+class PQFlatGpuIndex(RowStoreIndex):
+    FORMAT = 'annlite_amd.PQFlatGpuIndex/1'
+    STATE_KEYS = ('dim', 'M', 'Ks')
+
     def __init__(
         self,
         dim: int,
@@ -57,26 +62,16 @@ class PQFlatGpuIndex(BaseIndex):
         rerank_pool: str = 'slices',
         **kwargs,
     ):
-        # HNSW-only kwargs the reference forwards (ef_construction, ef_search, max_connection) are accepted and ignored
-        for k in ('ef_construction', 'ef_search', 'max_connection'):
-            kwargs.pop(k, None)
-        super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
         assert pq_codec is not None, 'PQFlatGpuIndex needs a PQCodec'
-        self.pq_codec = pq_codec
+        self.pq_codec = pq_codec  # (before the base class asks for the columns: they follow the codec)
         self.rerank = bool(rerank)
+        super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
         # candidates of the exact re-rank stage: 'slices' = the union of the row slices' own ADC top-rerank_k lists (n_slices x
         # rerank_k rows); 'global' = the global ADC top-rerank_k (<= 64, default 50) of the shared-bound search
         assert rerank_pool in ('slices', 'global')
         self.rerank_pool = rerank_pool
         self._want_skew = bool(skewed)
         self._ws = ops.ScanWorkspace()
-        # device storage is allocated on first use so that constructing an index (and the host-side
-        # error paths, e.g. "not trained") does not need a GPU
-        self._codes = None
-        self._valid_bool = None
-        self._valid_bits_cache = None
-        self._vectors = None
-        self._n_rows = 0
         self._scan_state = None  # the library's per-table kernel choice (created with the device storage)
         if index_file:
             self.load(index_file)
@@ -98,51 +93,14 @@ class PQFlatGpuIndex(BaseIndex):
         fast = self.code_bytes == 1 and self.M in (8, 16, 32, 64) and self.Ks <= 256
         return CODES_SKEWED if (fast and self._want_skew) else CODES_PLAIN
 
-    def _alloc(self, capacity: int):
-        dev = ops.device()
+    def _columns(self):
+        """``uint8 [capacity, M]`` codes (wider for Ks > 256); the raw vectors only for the exact re-rank stage"""
         tdt = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[self.code_bytes]
-        self._codes = torch.zeros((capacity, self.M), dtype=tdt, device=dev)
-        # validity: bool per row is the source of truth, the uint32 bitmap the kernels read is packed lazily
-        self._valid_bool = torch.zeros((((capacity + 31) // 32 + 2) * 32,), dtype=torch.bool, device=dev)
-        self._valid_bits_cache: Optional[torch.Tensor] = None
-        self._vectors = torch.zeros((capacity, self.dim), dtype=torch.float32, device=dev) if self.rerank else None
-        self._capacity = capacity
-        self._n_rows = 0  # scan range = highest written row id + 1
-        self._size = 0
+        return {'_codes': ((self.M,), tdt), '_vectors': ((self.dim,), torch.float32) if self.rerank else None}
 
-    def _ensure_alloc(self):
-        if self._codes is None:
-            self._alloc(self._capacity)
-
-    def _expand_capacity(self, new_capacity: int):
-        self._ensure_alloc()
-        old_codes, old_valid, old_vec, n_rows, size = self._codes, self._valid_bool, self._vectors, self._n_rows, self._size
-        self._alloc(new_capacity)
-        self._codes[: old_codes.shape[0]] = old_codes
-        self._valid_bool[: old_codes.shape[0]] = old_valid[: old_codes.shape[0]]
-        if old_vec is not None:
-            self._vectors[: old_vec.shape[0]] = old_vec
-        self._n_rows, self._size = n_rows, size
-
-    # ------------------------------------------------------------------ pre-processing (hnsw/index.py:20-48)
-    def _pre(self, x) -> torch.Tensor:
+    def _check_ready(self):
         if not self.pq_codec.is_trained:
             raise RuntimeError('Please train the PQ before using HNSW quantization backend')
-        if isinstance(x, np.ndarray) and self.metric == Metric.COSINE:
-            # host buffers are normalised with the reference's own numpy expression before the upload (bit-equal
-            # vectors => bit-equal codes / tables / ids); device tensors by the kernel
-            xh = np.ascontiguousarray(x.reshape(1, -1) if x.ndim == 1 else x, dtype=np.float32)
-            assert xh.shape[-1] == self.dim, (
-                f'the query embedding dimension does not match with index dimension: {xh.shape[-1]} vs {self.dim}')
-            return ops.to_dev(l2_normalize_host(xh), torch.float32)
-        x = ops.to_dev(x, torch.float32)
-        if x.ndim == 1:
-            x = x.reshape(1, -1)
-        assert x.shape[-1] == self.dim, (
-            f'the query embedding dimension does not match with index dimension: {x.shape[-1]} vs {self.dim}')
-        if self.metric == Metric.COSINE:
-            x = ops.l2_normalize(x)
-        return x
 
     def _scan_inputs(self, x, q: torch.Tensor):
         """(LUT kind, queries as the table build sees them): ``PQCodec.get_dist_mat`` normalises cosine queries a second
@@ -154,83 +112,20 @@ class PQFlatGpuIndex(BaseIndex):
                 np.ascontiguousarray(x.reshape(1, -1) if x.ndim == 1 else x, dtype=np.float32))), torch.float32)
         return self.pq_codec.scan_inputs(q)
 
-    @staticmethod
-    def _pack_bits(flags: torch.Tensor) -> torch.Tensor:
-        """bool [32*W] -> int32 [W] bitmap words (bit i of word w = flags[32*w + i]); plumbing only."""
-        shifts = torch.arange(32, device=flags.device, dtype=torch.int64)
-        packed = (flags.reshape(-1, 32).to(torch.int64) << shifts[None, :]).sum(dim=1)
-        return torch.where(packed >= 2 ** 31, packed - 2 ** 32, packed).to(torch.int32)
-
-    @property
-    def _valid(self) -> torch.Tensor:
-        if self._valid_bits_cache is None:
-            self._valid_bits_cache = self._pack_bits(self._valid_bool)
-        return self._valid_bits_cache
-
-    def _set_bits(self, ids: torch.Tensor, value: bool):
-        self._valid_bool[ids] = value
-        self._valid_bits_cache = None
-
-    def _get_bits(self, ids: torch.Tensor) -> torch.Tensor:
-        return self._valid_bool[ids]
-
-    # ------------------------------------------------------------------ mutation
-    def add_with_ids(self, x, ids: List[int], **kwargs):
-        x = self._pre(x)
-        self._ensure_alloc()
-        ids_t = ops.to_dev(np.asarray(ids, dtype=np.int64) if not isinstance(ids, torch.Tensor) else ids, torch.int64)
-        assert ids_t.numel() == x.shape[0]
-        if ids_t.numel() == 0:
-            return
-        max_id = int(ids_t.max().item()) + 1
-        if max_id > self.capacity:
-            steps = math.ceil(max_id / self.expand_step_size)  # hnsw/index.py:132-135
-            self._expand_capacity(steps * self.expand_step_size)
+    # ------------------------------------------------------------------ mutation (protocol: row_store.py)
+    def _write_rows(self, x, ids):
         codes = ops.pq_encode(x, self.pq_codec.codebooks_dev)
         if self._layout() == CODES_SKEWED:
-            ops.codes_skew(codes, ids_t, out=self._codes)
+            ops.codes_skew(codes, ids, out=self._codes)
         else:
-            self._codes[ids_t] = codes
+            self._codes[ids] = codes
         if self._vectors is not None:
-            self._vectors[ids_t] = x
-        was_valid = self._get_bits(ids_t)
-        self._set_bits(ids_t, True)
-        self._size += int((~was_valid).sum().item())
-        self._n_rows = max(self._n_rows, max_id)
-
-    def update_with_ids(self, x, ids: List[int], **kwargs):
-        """flat_index.py:70-71 semantics (overwrite rows); HnswIndex refuses updates, PQIndex allows."""
-        self.add_with_ids(x, ids)
-
-    def delete(self, ids: List[int]):
-        if self._codes is None or len(ids) == 0:
-            return
-        ids_t = ops.to_dev(np.asarray(list(ids), dtype=np.int64), torch.int64)
-        was_valid = self._get_bits(ids_t)
-        self._set_bits(ids_t, False)
-        self._size -= int(was_valid.sum().item())
+            self._vectors[ids] = x
 
     def reset(self, capacity: Optional[int] = None):
         super().reset(capacity=capacity)
-        self._codes = None
-        self._valid_bool = None
-        self._valid_bits_cache = None
-        self._vectors = None
-        self._n_rows = 0
         if self._scan_state is not None:
             self._scan_state.reset()
-
-    @property
-    def size(self):
-        return self._size
-
-    # ------------------------------------------------------------------ search
-    def _filter_bits(self, indices) -> torch.Tensor:
-        """`indices` argument of search (pq_index.py:42-44, container.py:107-120): restrict to a subset."""
-        idx = ops.to_dev(np.asarray(indices, dtype=np.int64) if not isinstance(indices, torch.Tensor) else indices, torch.int64)
-        sel = torch.zeros_like(self._valid_bool)
-        sel[idx] = True
-        return self._pack_bits(sel & self._valid_bool)
 
     # ------------------------------------------------------------------ kernel choice
     # Which M = 16 scan kernel serves this table -- byte filter tables (data with structure: what PQ is for) or u16 filter
@@ -266,8 +161,7 @@ class PQFlatGpuIndex(BaseIndex):
             valid = self._valid if indices is None else self._filter_bits(indices)
         dev = q.device
         if N == 0 or B == 0:
-            d = torch.full((B, k), float('inf'), dtype=torch.float32, device=dev)
-            i = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+            d, i = empty_answer(B, k, dev)
         elif self.rerank and self._vectors is not None:
             d, i = self._search_rerank(q, k, valid, N, rerank_k, self._scan_inputs(x, q), filtered=indices is not None)
         elif k <= 64:
@@ -284,9 +178,7 @@ class PQFlatGpuIndex(BaseIndex):
             d, i = self._search_large_k(q, k, valid, N, self._scan_inputs(x, q))
         if row_base:
             i = torch.where(i >= 0, i + row_base, i)  # (paths that do not take row_base natively)
-        if is_np:
-            return d.cpu().numpy(), i.cpu().numpy()
-        return d, i
+        return like_input(is_np, d, i)
 
     def search_batch_packed(self, x, limit: int, row_base: int = 0) -> Optional[torch.Tensor]:
         """Plain ADC top-k of a device batch as ONE i64 tensor [B, k, 2] = (row_base + id or -1, bits of the RAW
@@ -363,14 +255,12 @@ class PQFlatGpuIndex(BaseIndex):
         lut = ops.lut_build(xq, self.pq_codec.codebooks_dev, kind, LAYOUT_BMK)
         codes = self._plain_codes(N)
         dev = q.device
-        shifts = torch.arange(32, device=dev, dtype=torch.int64)
-        vb = (((valid.to(torch.int64) & 0xFFFFFFFF)[:, None] >> shifts[None, :]) & 1).bool().reshape(-1)[:N]  # unpack
+        vb = self._unpack_bits(valid, N)
         kk = min(k, N)
         B = q.shape[0]
-        chunk = max(1, min(B, (1 << 26) // max(N, 1)))  # <= 64M keys (512 MB) + their f32 sums per chunk
+        chunk = max(1, min(B, (1 << 26) // max(N, 1)))  # <= 64M keys (512 MB) + their f32 sums per chunk (the flat index: half)
         rows = torch.arange(N, device=dev, dtype=torch.int64)
         inf = torch.tensor(float('inf'), device=dev)
-        nan = torch.tensor(float('nan'), device=dev)
         key_none = torch.tensor(torch.iinfo(torch.int64).max, dtype=torch.int64, device=dev)
         ds, is_ = [], []
         for b0 in range(0, B, chunk):
@@ -378,23 +268,16 @@ class PQFlatGpuIndex(BaseIndex):
             dist = torch.empty((nb, N), dtype=torch.float32, device=dev)
             for j in range(nb):
                 ops.adc_dist(lut[b0 + j], codes, out=dist[j])
-            dist = dist + 0.0  # (-0.0 -> +0.0: equal VALUES tie-break by id)
-            dist = torch.where(torch.isnan(dist), nan, dist)  # one NaN, sign bit clear: it sorts behind +inf (numpy's order)
-            bits = dist.view(torch.int32)
-            bits = bits ^ ((bits >> 31) & 0x7FFFFFFF)  # signed-comparable image of the float order
-            keys = (bits.to(torch.int64) << 32) | rows[None, :]
+            # -0.0 -> +0.0 before keying: equal VALUES tie-break by id, what the scan kernels' lists do with ADC sums (the flat
+            # index's exact distances keep key(-0.0) < key(+0.0): FlatGpuIndex._keyed_topk)
+            keys = (float_order_key(dist + 0.0) << 32) | rows[None, :]
             keys = torch.where(vb[None, :], keys, key_none)  # deleted / never-written rows: behind every real row, NaN ones included
             top = torch.topk(keys, kk, dim=1, largest=False, sorted=True).values
             none = top == key_none
-            si = torch.where(none, torch.zeros_like(top), top & 0xFFFFFFFF)
-            sd = torch.where(none, inf, torch.gather(dist, 1, si))
-            si = torch.where(none, torch.full_like(si, -1), si)
-            ds.append(sd)
-            is_.append(si)
-        d, i = torch.cat(ds), torch.cat(is_)
-        if kk < k:
-            d = torch.cat([d, torch.full((d.shape[0], k - kk), float('inf'), device=d.device)], dim=1)
-            i = torch.cat([i, torch.full((i.shape[0], k - kk), -1, dtype=torch.int64, device=i.device)], dim=1)
+            # (a real row at +inf keeps its id here; the flat index blanks it, as its k <= 64 kernel does)
+            ds.append(torch.where(none, inf, float_from_key(top >> 32)))
+            is_.append(torch.where(none, torch.full_like(top, -1), top & 0xFFFFFFFF))
+        d, i = pad_to_k(torch.cat(ds), torch.cat(is_), k)
         if self.metric == Metric.EUCLIDEAN:
             d = torch.sqrt(d)
         return d, i
@@ -451,64 +334,23 @@ class PQFlatGpuIndex(BaseIndex):
         exact = ops.exact_gather_dist(int(self.metric), q, self._vectors, cand)  # [B, R]
         kk = min(k, cand.shape[1])
         d, pos = self._topk_rows_any(exact, kk)
-        i = torch.gather(cand, 1, pos.clamp(min=0))
-        i = torch.where(pos < 0, torch.full_like(i, -1), i)
-        i = torch.where(torch.isinf(d), torch.full_like(i, -1), i)
-        if self.metric == Metric.EUCLIDEAN:
-            d = torch.sqrt(d)
-        if kk < k:
-            d = torch.cat([d, torch.full((B, k - kk), float('inf'), device=d.device)], dim=1)
-            i = torch.cat([i, torch.full((B, k - kk), -1, dtype=torch.int64, device=i.device)], dim=1)
-        return d, i
+        return ranked_answer(cand, d, pos, k, sqrt=self.metric == Metric.EUCLIDEAN)
 
-    def search(self, x, limit: int = 10, indices=None):
-        """ONE query, reference signature (hnsw/index.py:139-167): ``(dists[k'], ids[k'])`` numpy,
-        ``k' <= limit`` valid entries only."""
-        if indices is not None and len(indices) < limit:
-            limit = len(indices)  # hnsw/index.py:153-154
-        if limit <= 0:
-            return np.empty((0,), np.float32), np.empty((0,), np.int64)
-        d, i = self.search_batch(x, limit=limit, indices=indices)
-        if isinstance(d, torch.Tensor):
-            d, i = d.cpu().numpy(), i.cpu().numpy()
-        d, i = d[0], i[0]
-        keep = i >= 0
-        return d[keep], i[keep]
+    # ------------------------------------------------------------------ persistence (envelope: row_store.py)
+    def _dump_state(self, N):
+        """Codes are saved in the PLAIN (reference) layout."""
+        return {'metric': int(self.metric),
+                'codes': ops.codes_to_numpy(self._plain_codes(N)) if N else np.zeros((0, self.M), self.pq_codec.code_dtype),
+                'vectors': self._vectors[:N].cpu().numpy() if self._vectors is not None else None}
 
-    # ------------------------------------------------------------------ persistence (own format)
-    def dump(self, index_file: Union[str, Path]):
-        """hnsw/index.py:121-122 analogue.  Codes are saved in the PLAIN (reference) layout."""
-        self._ensure_alloc()
-        N = self._n_rows
-        state = {
-            'format': 'annlite_amd.PQFlatGpuIndex/1',
-            'dim': self.dim, 'M': self.M, 'Ks': self.Ks, 'metric': int(self.metric),
-            'n_rows': N, 'size': self._size, 'capacity': self._capacity,
-            'codes': ops.codes_to_numpy(self._plain_codes(N)) if N else np.zeros((0, self.M), self.pq_codec.code_dtype),
-            'valid': self._valid_bool[:N].cpu().numpy(),
-            'vectors': self._vectors[:N].cpu().numpy() if self._vectors is not None else None,
-        }
-        with open(str(index_file), 'wb') as f:
-            np.save(f, np.array([state], dtype=object), allow_pickle=True)
-
-    def load(self, index_file: Union[str, Path]):
-        with open(str(index_file), 'rb') as f:
-            state = np.load(f, allow_pickle=True)[0]
-        assert state['format'] == 'annlite_amd.PQFlatGpuIndex/1'
-        assert state['dim'] == self.dim and state['M'] == self.M and state['Ks'] == self.Ks
-        self._alloc(max(int(state['capacity']), self._capacity))
-        N = int(state['n_rows'])
+    def _load_state(self, state, N):
         if N:
-            codes = ops.to_dev(state['codes'])
+            codes = self._to_dev(state['codes'])
             if self._layout() == CODES_SKEWED:
                 ops.codes_skew(codes, ids=None, id_base=0, out=self._codes)
             else:
                 self._codes[:N] = codes
             if self._vectors is not None and state['vectors'] is not None:
-                self._vectors[:N] = ops.to_dev(state['vectors'])
-        v = ops.to_dev(state['valid'])
-        self._valid_bool[: v.numel()] = v
-        self._valid_bits_cache = None
-        self._n_rows, self._size = N, int(state['size'])
+                self._vectors[:N] = self._to_dev(state['vectors'])
         if self._scan_state is not None:
             self._scan_state.reset()  # (another table: what was measured no longer applies)

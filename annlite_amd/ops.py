@@ -23,9 +23,10 @@ def device() -> torch.device:
     return torch.device('cuda', torch.cuda.current_device())
 
 
-def to_dev(a, dtype=None) -> torch.Tensor:
-    """numpy / torch (any device) -> contiguous tensor on the current HIP device."""
-    dev = device()
+def to_dev(a, dtype=None, dev=None) -> torch.Tensor:
+    """numpy / torch (any device) -> contiguous tensor on the current HIP device (or on ``dev``)."""
+    if dev is None:
+        dev = device()
     if isinstance(a, np.ndarray):
         if a.dtype == np.uint16:
             a = a.view(np.int16)
