@@ -103,6 +103,10 @@ SYMBOLS = (
     'annlite_flat_search_workspace_bytes',
     'annlite_flat_search_topk',
     'annlite_flat_overflow_count',
+    'annlite_flat_list_counts',
+    'annlite_ivf_flat_stages',
+    'annlite_ivf_flat_search_workspace_bytes',
+    'annlite_ivf_flat_search_topk',
 )
 
 
@@ -219,6 +223,11 @@ def lib() -> ctypes.CDLL:
     L.annlite_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, i64, i32, vp, vp, vp, sz, vp]
     L.annlite_flat_overflow_count.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_flat_list_counts.argtypes = [vp, i64, vp, vp]
+    L.annlite_ivf_flat_stages.argtypes = [i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32)]
+    L.annlite_ivf_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_ivf_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, vp,
+                                               vp, sz, vp]
     L.annlite_graph_search_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_graph_search_stats_ex.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     for name in SYMBOLS:

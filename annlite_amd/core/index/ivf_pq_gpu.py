@@ -12,7 +12,8 @@ Semantics:
 
 Layout in HBM on top of the flat index's storage (codes by offset, validity, optional float vectors):
   * ``_cell_of``  i32 [capacity]        cell of every offset (nearest centroid in squared L2, vq.py:81-90): one more column
-                                        of the row store (row_store.py), grown with the others
+                                        of the row store (row_store.py), grown with the others (cells.py: shared with
+                                        ``IvfFlatGpuIndex``, like the cell selection and the ``.cells.npy`` side file)
   * sealed view, rebuilt lazily after a mutation (one sort + one gather over the live rows):
       ``_table``     u8 [Nt, M] SKEWED by table row: the live rows grouped by cell, every cell starts at a
                      multiple of 64 rows, ascending offset inside a cell
@@ -28,7 +29,6 @@ each) -> ``annlite_pq_search_tiles`` (quantised tables of the queries + integer 
 """
 from typing import Optional, Tuple
 
-import numpy as np
 import torch
 
 from ... import ops
@@ -36,20 +36,21 @@ from ..._capi import CODES_SKEWED, LUT_IPDIST, LUT_L2, scan_plan, scan_plan_tile
 from ...enums import Metric
 from ..codec.pq import PQCodec
 from ..codec.vq import VQCodec
+from .cells import CellColumnMixin
 from .pq_flat_gpu import PQFlatGpuIndex
 from .row_store import empty_answer, like_input, ranked_answer
 
 
-class IvfPQGpuIndex(PQFlatGpuIndex):
+class IvfPQGpuIndex(CellColumnMixin, PQFlatGpuIndex):
     R_CAP = 4096  # rows a query re-ranks at most (float re-rank of a pruned search); grows with k * n_probe: see _search_pruned
     rerank_truncated = 0  # queries (so far) whose candidate set exceeded the cap and lost the later cells' lists
     def __init__(self, dim: int, pq_codec: Optional[PQCodec] = None, vq_codec: Optional[VQCodec] = None,
                  n_probe: Optional[int] = None, rerank_bound_rank: int = 1, rerank_split: Tuple[int, int] = (2, 4), **kwargs):
-        super().__init__(dim, pq_codec=pq_codec, **kwargs)
         assert vq_codec is not None, 'IvfPQGpuIndex needs a VQCodec'
         self.vq_codec = vq_codec
-        self.n_probe = n_probe  # None: every cell (the reference's behaviour)
         self._sealed = False
+        super().__init__(dim, pq_codec=pq_codec, **kwargs)
+        self.n_probe = n_probe  # None: every cell (the reference's behaviour)
         self._table = self._table_plain = self._row_ids = self._cell_rows = self._cell_order = self._pos_of = None
         self.cand_cap = 256  # emitted candidates per (query, cell) list; an overflowing list falls back to the whole cell
         self.byte_tiles = True  # M = 16, k <= 16: annlite_ivf_search_topk / _candidates (False: the u16 tile scan + re-score)
@@ -66,37 +67,6 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
         self._split_cache = None
         self._tws = ops.ScanWorkspace()
         self.last_pruned_path = None  # which kernels served the last pruned search (measurement scripts)
-
-    @property
-    def n_cells(self) -> int:
-        return self.vq_codec.n_clusters
-
-    # ------------------------------------------------------------------ storage
-    def _columns(self):
-        return {**super()._columns(), '_cell_of': ((), torch.int32)}  # (a column: a growth carries the cells along)
-
-    def _alloc(self, capacity: int):
-        super()._alloc(capacity)
-        self._sealed = False  # (new storage, whoever asked for it: the sealed view is of the old one)
-
-    def add_with_ids(self, x, ids, **kwargs):
-        ids_t = self._ids_to_dev(ids)
-        if ids_t.numel() == 0:
-            return
-        super().add_with_ids(x, ids_t)  # codes / validity / float vectors exactly as the flat index stores them
-        # the reference assigns cells on the vectors as given (index.py:291-292, vq.py:81-90)
-        raw = ops.to_dev(x, torch.float32)
-        raw = raw.reshape(1, -1) if raw.ndim == 1 else raw
-        self._cell_of[ids_t] = self.vq_codec.encode(raw).to(torch.int32)
-        self._sealed = False
-
-    def delete(self, ids):
-        super().delete(ids)
-        self._sealed = False
-
-    def reset(self, capacity: Optional[int] = None):
-        super().reset(capacity=capacity)
-        self._sealed = False
 
     # ------------------------------------------------------------------ sealed (cell-sorted) view
     def _seal(self):
@@ -149,15 +119,6 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
             self._split_cache = (S, rows, order)
         return self._split_cache[1], self._split_cache[2]
 
-    def _select_kind_and_centroids(self) -> Tuple[int, torch.Tensor]:
-        """cdist(query, vq codebook, metric) of ``_cell_selection`` (index.py:462-464) as a ranking."""
-        cb = self.vq_codec.codebook_dev
-        if self.metric == Metric.EUCLIDEAN:
-            return 0, cb
-        if self.metric == Metric.COSINE:
-            return 1, ops.l2_normalize(cb)  # queries are normalised by _pre: 1 - cos ranks like -<q, c/|c|>
-        return 1, cb
-
     # ------------------------------------------------------------------ search
     def search_batch(self, x, limit: int = 10, indices=None, rerank_k: Optional[int] = None, row_base: int = 0,
                      n_probe: Optional[int] = None):
@@ -187,10 +148,6 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
         if self.n_probe is not None and self.n_probe < self.n_cells:
             return None
         return super().search_batch_packed(x, limit, row_base=row_base)
-
-    def probe_cells(self, q: torch.Tensor, n_probe: int) -> torch.Tensor:
-        kind, cent = self._select_kind_and_centroids()
-        return ops.ivf_select_cells(kind, q, cent, n_probe)
 
     def _table_bits(self, indices) -> Optional[torch.Tensor]:
         """``indices`` filter (offsets) as a bitmap over TABLE rows; None = every stored row."""
@@ -313,14 +270,3 @@ class IvfPQGpuIndex(PQFlatGpuIndex):
         exact = ops.exact_gather_dist(int(self.metric), q, self._vectors, ids)
         d, pos = self._topk_rows_any(exact, min(k_out, ids.shape[1]))  # (k_out > 64: a stable device sort, never cut silently)
         return ranked_answer(ids, d, pos, k_out, sqrt=self.metric == Metric.EUCLIDEAN)
-
-    # ------------------------------------------------------------------ persistence
-    def dump(self, index_file):
-        super().dump(index_file)
-        np.save(str(index_file) + '.cells.npy', self._cell_of[: self._n_rows].cpu().numpy())
-
-    def load(self, index_file):
-        super().load(index_file)
-        cells = np.load(str(index_file) + '.cells.npy')
-        self._cell_of[: cells.shape[0]] = ops.to_dev(cells)
-        self._sealed = False

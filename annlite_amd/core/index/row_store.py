@@ -1,7 +1,8 @@
 """``RowStoreIndex`` -- what every single-device index here shares: rows addressed by offset in lazily allocated device columns,
 a validity flag per row, the mutation protocol of ``add_with_ids`` / ``delete``, the reference's one-query ``search`` and the
-``np.save`` envelope of ``dump`` / ``load``.  ``FlatGpuIndex`` (vectors + norms) and ``PQFlatGpuIndex`` (codes, optional vectors;
-through it ``IvfPQGpuIndex`` and ``HnswPQGpuIndex``) declare their columns and write them; how they search is their own.
+``np.save`` envelope of ``dump`` / ``load``.  ``FlatGpuIndex`` (vectors + norms; through it ``IvfFlatGpuIndex``) and ``PQFlatGpuIndex``
+(codes, optional vectors; through it ``IvfPQGpuIndex`` and ``HnswPQGpuIndex``) declare their columns and write them; how they search
+is their own.
 
 Above the class: the pure-torch pieces of a search result that the indexes (and ``multi_gpu.merge_lists_sorted``) put together the
 same way -- the empty answer, padding to ``k``, ids taken by position, and the integer key that orders floats like numpy's sort.

@@ -5,6 +5,10 @@
 // cdist + top_k).  Here: a dense f32 MFMA contraction FILTERS the table against a per-query bound with a proven slack, the
 // rows that pass are appended to per-query candidate lists, and a wave per query re-scores its list in the arithmetic of
 // rerank_topk_kernel (codec.hip) -- so the answer is exact in that arithmetic whatever the filter's rounding was.
+//
+// Second half of the file: the same search over the rows of each query's probed CELLS (the reference's n_cells > 1 structure over that
+// index, container.py:88-144) -- the filter over (cell, queries that probe it) tiles, the cells a permutation
+// of the row offsets.
 #include <math.h>
 
 #include "common.h"
@@ -154,6 +158,73 @@ __global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const floa
 //   list == NULL : the rows c * stride, c < S (the first sample; a small table; the route of an overflowed query)
 // Only rows valid in the bitmap are offered.  thr_out != NULL: the k-th smallest distance (raw, no sqrt; +inf with fewer than k
 // rows) goes there -- a bound for the next filter stage -- instead of the result arrays.
+// The chain itself, shared by every exact kernel of this file: up to 64 rows (one per lane, -1: none; n_here = lanes that were
+// offered one) are scored against the wave's query and offered to its list.
+__device__ __forceinline__ void flat_exact_chunk(int metric, const float *__restrict__ qr, int D, const float *__restrict__ x, int64_t N,
+                                                 const uint32_t *__restrict__ valid, int64_t row, int n_here, int km1, int lane, WaveList &L,
+                                                 uint32_t &th, uint32_t &tl) {
+    constexpr int U = 8;
+    if (row >= N) row = -1;
+    if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
+    if (__ballot(row >= 0) == 0ull) return;
+    float mine = __builtin_inff();
+    for (int u0 = 0; u0 < n_here; u0 += U) {
+        float s[U];
+        int64_t rw[U];
+        bool any = false;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            rw[u] = __shfl(row, u0 + u);  // (wave-uniform)
+            s[u] = 0.f;
+            any |= rw[u] >= 0;
+        }
+        if (!any) continue;
+        for (int j = lane; j < D; j += 64) {
+            const float qj = qr[j];
+            float xv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) xv[u] = rw[u] >= 0 ? x[rw[u] * D + j] : 0.f;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (metric == ANNLITE_METRIC_EUCLIDEAN) {
+                    const float d = xv[u] - qj;
+                    s[u] = __builtin_fmaf(d, d, s[u]);
+                } else {
+                    s[u] = __builtin_fmaf(xv[u], qj, s[u]);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s[u] += __shfl_xor(s[u], o);
+            const float dist = (metric == ANNLITE_METRIC_EUCLIDEAN) ? s[u] : 1.f - s[u];
+            if (lane == u0 + u) mine = dist;
+        }
+    }
+    const float tf = (th == kKeyInfHi) ? __builtin_inff() : ordered_to_f32(th);
+    const unsigned long long pm = __ballot(row >= 0 && !(mine > tf));  // (NaN: behind +inf, numpy's order)
+    if (pm) wavelist_offer(L, pm, f32_to_key(mine), (uint32_t)row, km1, th, tl, lane);
+}
+
+// ... and what becomes of the wave's list: the next stage's bound (thr_out != NULL) or the query's result row.
+__device__ __forceinline__ void flat_exact_finish(const WaveList &L, int b, int k, int lane, int do_sqrt, float *__restrict__ thr_out,
+                                                  float *__restrict__ out_d, int64_t *__restrict__ out_i) {
+    const int km1 = k - 1;
+    const bool none = (L.hi == kKeyInfHi && L.lo == kIdNone);
+    float d = none ? __builtin_inff() : ordered_to_f32(L.hi);
+    if (thr_out) {
+        if (lane == km1) thr_out[b] = d;
+        return;
+    }
+    if (lane <= km1) {
+        const int64_t id = (none || d == __builtin_inff()) ? (int64_t)-1 : (int64_t)L.lo;
+        if (do_sqrt) d = __builtin_sqrtf(d);
+        out_d[(int64_t)b * k + lane] = d;
+        out_i[(int64_t)b * k + lane] = id;
+    }
+}
+
 __global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
                                                         int64_t N, const int32_t *__restrict__ list, const int32_t *__restrict__ cnt, int cap,
                                                         int64_t S, int64_t stride, const uint32_t *__restrict__ valid, int k, int do_sqrt,
@@ -179,10 +250,8 @@ __global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float
         if (only_overflowed && !ovf[b]) return;
         n = S;
     }
-    constexpr int U = 8;
     const float *qr = q + (int64_t)b * D;
     const int32_t *lr = list ? list + (int64_t)b * cap : nullptr;
-    const int km1 = k - 1;
     WaveList L;
     L.reset();
     uint32_t th = kKeyInfHi, tl = kIdNone;
@@ -190,60 +259,164 @@ __global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float
         const int64_t ci = c0 + lane;
         int64_t row = -1;
         if (ci < n) row = lr ? (int64_t)lr[ci] : ci * stride;
-        if (row >= N) row = -1;
-        if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
-        if (__ballot(row >= 0) == 0ull) continue;
-        float mine = __builtin_inff();
-        const int n_here = n - c0 < 64 ? (int)(n - c0) : 64;
-        for (int u0 = 0; u0 < n_here; u0 += U) {
-            float s[U];
-            int64_t rw[U];
-            bool any = false;
+        flat_exact_chunk(metric, qr, D, x, N, valid, row, n - c0 < 64 ? (int)(n - c0) : 64, k - 1, lane, L, th, tl);
+    }
+    flat_exact_finish(L, b, k, lane, do_sqrt, thr_out, out_d, out_i);
+}
+
+// ---- cells over float vectors ---------------------------------------------------------------------------------
+// The live rows grouped by cell: perm i32 [n_perm] holds their offsets, cell c = perm[cell_rows[c][0] .. cell_rows[c][1]), ascending
+// inside a cell.  A query's row set is the ranges of its P probed cells; "stride s" means the entries 0, s, 2 s, ... of EACH range.
+// The lists, the norms, the bitmap and the exact chain above all speak offsets, so nothing else changes.
+__device__ __forceinline__ void ivf_flat_cell_range(int32_t cell, int C, const int64_t *__restrict__ cell_rows, int64_t n_perm, int64_t &begin,
+                                                    int64_t &end) {
+    const int c = (unsigned)cell < (unsigned)C ? cell : 0;  // (an id out of range: cell 0, as ivf_plan_kernel reads it)
+    begin = cell_rows[2 * c], end = cell_rows[2 * c + 1];
+    if (begin < 0) begin = 0;
+    if (end > n_perm) end = n_perm;
+}
+
+// flat_exact_kernel's `list == NULL` mode over the probed cells: exact sums of every stride-th entry of each of the query's P cells
+// (the first sample; all probed rows where they are few; the route of an overflowed query).
+__global__ __launch_bounds__(256) void ivf_flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+                                                            int64_t N, const int32_t *__restrict__ cells, int P, int C,
+                                                            const int64_t *__restrict__ cell_rows, const int32_t *__restrict__ perm,
+                                                            int64_t n_perm, int64_t stride, const uint32_t *__restrict__ valid, int k,
+                                                            int do_sqrt, int only_overflowed, float *__restrict__ thr_out,
+                                                            float *__restrict__ out_d, int64_t *__restrict__ out_i,
+                                                            const int32_t *__restrict__ ovf) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    if (only_overflowed && !ovf[b]) return;
+    const float *qr = q + (int64_t)b * D;
+    WaveList L;
+    L.reset();
+    uint32_t th = kKeyInfHi, tl = kIdNone;
+    for (int p = 0; p < P; ++p) {
+        int64_t begin, end;
+        ivf_flat_cell_range(cells[(int64_t)b * P + p], C, cell_rows, n_perm, begin, end);
+        const int64_t n = (end - begin + stride - 1) / stride;
+        for (int64_t c0 = 0; c0 < n; c0 += 64) {
+            const int64_t ci = c0 + lane;
+            const int64_t row = ci < n ? (int64_t)perm[begin + ci * stride] : -1;
+            flat_exact_chunk(metric, qr, D, x, N, valid, row, n - c0 < 64 ? (int)(n - c0) : 64, k - 1, lane, L, th, tl);
+        }
+    }
+    flat_exact_finish(L, b, k, lane, do_sqrt, thr_out, out_d, out_i);
+}
+
+// flat_filter_kernel over (plan tile t, row tile of t's cell): tile t = the 128 slots vmap[128 t ..] of queries that probe ONE cell
+// (annlite_ivf_plan; -1: a padding slot), whose range of perm is tile_rows[t] (begin -1: an unused tile).  blockIdx.x = the row tile
+// inside the cell at this stride, blockIdx.y (+ gridDim.y, ...) = t.  A operand: rows gathered through perm, B operand: queries
+// gathered through vmap; the contraction, the score, the comparison and the append are flat_filter_kernel's, and what is appended is
+// the row's OFFSET.  A query sits in at most one slot per cell and a row in one cell, so a list takes no pair twice.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ivf_flat_filter_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+                                                             const float *__restrict__ norms, int64_t N, const int32_t *__restrict__ perm,
+                                                             int64_t n_perm, const int64_t *__restrict__ tile_rows,
+                                                             const int32_t *__restrict__ vmap, int n_tiles, int64_t stride,
+                                                             const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
+                                                             const float *__restrict__ thr, float c_rel, float c_abs,
+                                                             int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap) {
+    __shared__ float As[kFlatTile * kFlatLd];
+    __shared__ float Bs[kFlatTile * kFlatLd];
+    __shared__ float nxs[kFlatTile];
+    __shared__ int rws[kFlatTile];  // offset of the tile's row, -1: none (past the cell's end, not valid)
+    __shared__ int qss[kFlatTile];  // query of the tile's slot, -1: padding
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
+    const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
+    const int l31 = lane & 31, lh = lane >> 5;
+    for (int t = blockIdx.y; t < n_tiles; t += gridDim.y) {
+        int64_t begin = tile_rows[2 * (int64_t)t], end = tile_rows[2 * (int64_t)t + 1];
+        if (begin < 0) continue;
+        if (end > n_perm) end = n_perm;
+        const int64_t S = (end - begin + stride - 1) / stride;
+        if (r0 >= S) continue;  // (both tests are the workgroup's: no barrier is left behind)
+        __syncthreads();        // the previous tile's epilogue has read rws / nxs / qss
+        if (tid < kFlatTile) {
+            const int64_t r = r0 + tid;
+            int64_t row = r < S ? (int64_t)perm[begin + r * stride] : -1;
+            if (row >= N) row = -1;
+            if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
+            rws[tid] = (int)row;
+            nxs[tid] = row >= 0 ? norms[row] : 0.f;
+        } else {
+            const int qi = vmap[(int64_t)t * kFlatTile + tid - kFlatTile];
+            qss[tid - kFlatTile] = (unsigned)qi < (unsigned)B ? qi : -1;
+        }
+        f32x16 acc00, acc01, acc10, acc11;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                rw[u] = __shfl(row, u0 + u);  // (wave-uniform)
-                s[u] = 0.f;
-                any |= rw[u] >= 0;
+        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        for (int k0 = 0; k0 < D; k0 += kFlatDepth) {
+            __syncthreads();  // the previous stage is consumed (first pass: the tile's rows and queries are written)
+            if constexpr (VEC) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int e = tid + i * 256;  // 1024 slots of 4 floats
+                    const int r = e >> 3, c = (e & 7) * 4;
+                    f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
+                    const int rr = rws[r], qq = qss[r];
+                    if (rr >= 0 && k0 + c < D) va = *(const f32x4 *)(x + (int64_t)rr * D + k0 + c);
+                    if (qq >= 0 && k0 + c < D) vb = *(const f32x4 *)(q + (int64_t)qq * D + k0 + c);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        As[r * kFlatLd + c + u] = va[u];
+                        Bs[r * kFlatLd + c + u] = vb[u];
+                    }
+                }
+            } else {
+#pragma unroll 4
+                for (int i = 0; i < 16; ++i) {
+                    const int e = tid + i * 256;  // 4096 floats
+                    const int r = e >> 5, c = e & 31;
+                    const int rr = rws[r], qq = qss[r];
+                    As[r * kFlatLd + c] = (rr >= 0 && k0 + c < D) ? x[(int64_t)rr * D + k0 + c] : 0.f;
+                    Bs[r * kFlatLd + c] = (qq >= 0 && k0 + c < D) ? q[(int64_t)qq * D + k0 + c] : 0.f;
+                }
             }
-            if (!any) continue;
-            for (int j = lane; j < D; j += 64) {
-                const float qj = qr[j];
-                float xv[U];
+            __syncthreads();
 #pragma unroll
-                for (int u = 0; u < U; ++u) xv[u] = rw[u] >= 0 ? x[rw[u] * D + j] : 0.f;
+            for (int kk = 0; kk < kFlatDepth; kk += 2) {
+                const int kc = kk + lh;
+                const float a0 = As[(wr + l31) * kFlatLd + kc], a1 = As[(wr + 32 + l31) * kFlatLd + kc];
+                const float b0 = Bs[(wq + l31) * kFlatLd + kc], b1 = Bs[(wq + 32 + l31) * kFlatLd + kc];
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11, 0, 0, 0);
+            }
+        }
+        // epilogue: score, compare, append (flat_filter_kernel's)
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (metric == ANNLITE_METRIC_EUCLIDEAN) {
-                        const float d = xv[u] - qj;
-                        s[u] = __builtin_fmaf(d, d, s[u]);
-                    } else {
-                        s[u] = __builtin_fmaf(xv[u], qj, s[u]);
+        for (int qj = 0; qj < 2; ++qj) {
+            const int qi = qss[wq + qj * 32 + l31];
+            if (qi < 0) continue;
+            const float qn = qnorm[qi], tq = thr[qi];
+            int32_t *my_cnt = cnt + qi;
+            int32_t *my_list = cand + (int64_t)qi * cap;
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri) {
+                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                    const int off = rws[rl];
+                    if (off < 0) continue;
+                    const float a = nxs[rl] + qn;
+                    const float dot = acc[reg];
+                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
+                    const float bound = tq + (c_rel * a + c_abs);
+                    if (!(v > bound)) {
+                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
+                            const int pos = atomicAdd(my_cnt, 1);
+                            if (pos < cap) my_list[pos] = off;
+                        }
                     }
                 }
             }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) s[u] += __shfl_xor(s[u], o);
-                const float dist = (metric == ANNLITE_METRIC_EUCLIDEAN) ? s[u] : 1.f - s[u];
-                if (lane == u0 + u) mine = dist;
-            }
         }
-        const float tf = (th == kKeyInfHi) ? __builtin_inff() : ordered_to_f32(th);
-        const unsigned long long pm = __ballot(row >= 0 && !(mine > tf));  // (NaN: behind +inf, numpy's order)
-        if (pm) wavelist_offer(L, pm, f32_to_key(mine), (uint32_t)row, km1, th, tl, lane);
-    }
-    const bool none = (L.hi == kKeyInfHi && L.lo == kIdNone);
-    float d = none ? __builtin_inff() : ordered_to_f32(L.hi);
-    if (thr_out) {
-        if (lane == km1) thr_out[b] = d;
-        return;
-    }
-    if (lane <= km1) {
-        const int64_t id = (none || d == __builtin_inff()) ? (int64_t)-1 : (int64_t)L.lo;
-        if (do_sqrt) d = __builtin_sqrtf(d);
-        out_d[(int64_t)b * k + lane] = d;
-        out_i[(int64_t)b * k + lane] = id;
     }
 }
 
@@ -294,6 +467,72 @@ static int flat_launch_filter(int metric, const float *q, int64_t B, int64_t D, 
         hipLaunchKernelGGL(flat_filter_kernel<false>, grid, dim3(256), 0, st, metric, q, (int)B, (int)D, x, norms, S, stride, valid, qnorm, thr,
                            c_rel, c_abs, cand, cnt, kFlatCap, n_qt);
     return launch_status("flat_filter_kernel");
+}
+
+
+// ---- cells: workspace, stages, launchers ---------------------------------------------------------------------------------------------
+constexpr int kIvfFlatMaxStages = 16;  // strides annlite_ivf_flat_stages can return (2^31 rows: 19 bits of stride, 5 at a time, + the first)
+
+struct IvfFlatWs {
+    FlatWs f;  // (first: annlite_flat_overflow_count reads the same counter)
+    int64_t n_tiles;
+    int32_t *vmap, *slot_of, *n_used;
+    int64_t *tile_rows;
+    size_t bytes;
+};
+static IvfFlatWs ivf_flat_carve(void *ws, int64_t B, int64_t P, int64_t C) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    IvfFlatWs w;
+    w.f = flat_carve(ws, B);
+    w.n_tiles = annlite_ivf_max_tiles(B, P, C, kFlatTile);
+    char *p = (char *)ws;
+    size_t o = w.f.bytes;
+    w.tile_rows = (int64_t *)(p + o), o += up((size_t)w.n_tiles * 16);
+    w.vmap = (int32_t *)(p + o), o += up((size_t)w.n_tiles * kFlatTile * 4);
+    w.slot_of = (int32_t *)(p + o), o += up((size_t)B * P * 4);
+    w.n_used = (int32_t *)(p + o), o += 256;
+    w.bytes = o;
+    return w;
+}
+
+// The strides of a search over at most M probed rows per query: strides[0] = the first (exact) sample's, the smallest that keeps
+// M / stride at or below kFlatSample; then the filter stages', each row set at most kFlatGrowth times the one before, down to 1.
+// None for M <= kFlatSample (exact sums over all probed rows).
+static int ivf_flat_strides(int64_t M, int64_t *strides) {
+    if (M <= kFlatSample) return 0;
+    int64_t s = (M + kFlatSample - 1) / kFlatSample;  // >= 2
+    int n = 0;
+    strides[n++] = s;
+    int rem = (int)ceil(log((double)s) / log(kFlatGrowth) - 1e-9);
+    if (rem < 1) rem = 1;
+    while (s > 1 && n < kIvfFlatMaxStages) {
+        int64_t nx = 1;
+        if (rem > 1) nx = (int64_t)ceil((double)s / pow((double)s, 1.0 / rem) - 1e-9);
+        if (nx * (int64_t)kFlatGrowth < s) nx = (s + (int64_t)kFlatGrowth - 1) / (int64_t)kFlatGrowth;
+        if (nx >= s) nx = s - 1;
+        if (nx < 1) nx = 1;
+        strides[n++] = s = nx;
+        if (rem > 1) --rem;
+    }
+    return n;
+}
+
+static int ivf_flat_launch_filter(int metric, const float *q, int64_t B, int64_t D, const float *x, const float *norms, int64_t N,
+                                  const int32_t *perm, int64_t n_perm, const IvfFlatWs &w, int64_t max_cell_rows, int64_t stride,
+                                  const uint32_t *valid, hipStream_t st) {
+    float c_rel, c_abs;
+    flat_slack(metric, D, &c_rel, &c_abs);
+    const int64_t n_rt = ((max_cell_rows + stride - 1) / stride + kFlatTile - 1) / kFlatTile;
+    if (n_rt <= 0 || w.n_tiles <= 0) return ANNLITE_OK;
+    const dim3 grid((unsigned)n_rt, (unsigned)(w.n_tiles < 65535 ? w.n_tiles : 65535));
+    const bool vec = D % 4 == 0 && ((uintptr_t)q % 16 == 0) && ((uintptr_t)x % 16 == 0);
+    if (vec)
+        hipLaunchKernelGGL(ivf_flat_filter_kernel<true>, grid, dim3(256), 0, st, metric, q, (int)B, (int)D, x, norms, N, perm, n_perm, w.tile_rows,
+                           w.vmap, (int)w.n_tiles, stride, valid, w.f.qnorm, w.f.thr, c_rel, c_abs, w.f.cand, w.f.cnt, kFlatCap);
+    else
+        hipLaunchKernelGGL(ivf_flat_filter_kernel<false>, grid, dim3(256), 0, st, metric, q, (int)B, (int)D, x, norms, N, perm, n_perm, w.tile_rows,
+                           w.vmap, (int)w.n_tiles, stride, valid, w.f.qnorm, w.f.thr, c_rel, c_abs, w.f.cand, w.f.cnt, kFlatCap);
+    return launch_status("ivf_flat_filter_kernel");
 }
 
 }  // namespace annlite
@@ -399,4 +638,84 @@ extern "C" int annlite_flat_overflow_count(const void *workspace_dev, void *stre
     ANNLITE_HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     *count = (int64_t)v;
     return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_list_counts(const void *workspace_dev, int64_t B, int32_t *count_dev, void *stream) {
+    ANNLITE_REQUIRE(workspace_dev && count_dev && B >= 0, "bad argument");
+    if (B == 0) return ANNLITE_OK;
+    const FlatWs w = flat_carve(const_cast<void *>(workspace_dev), B);
+    ANNLITE_HIP_TRY(hipMemcpyAsync(count_dev, w.cnt, (size_t)B * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_ivf_flat_stages(int64_t max_probed_rows, int64_t *strides_out, int *n_out) {
+    ANNLITE_REQUIRE(max_probed_rows >= 0 && strides_out && n_out, "bad argument");
+    *n_out = ivf_flat_strides(max_probed_rows, strides_out);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_ivf_flat_search_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    ANNLITE_REQUIRE(B >= 0 && P >= 1 && C >= 1 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64)");
+    *bytes = (int64_t)ivf_flat_carve(nullptr, B, P, C).bytes;
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_ivf_flat_search_topk(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                            const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev,
+                                            int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                            const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t max_probed_rows, int64_t k,
+                                            int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
+                                            size_t workspace_bytes, void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= INT32_MAX,
+                    "bad shape (1 <= k <= 64)");
+    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
+                        max_cell_rows <= n_perm && max_probed_rows >= 0,
+                    "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld max_probed_rows=%lld", (long long)P, (long long)C,
+                    (long long)n_perm, (long long)max_cell_rows, (long long)max_probed_rows);
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && cells_dev && cell_rows_dev && cell_order_dev &&
+                        (n_perm == 0 || (vectors_dev && norms_dev && perm_dev)),
+                    "null device pointer");
+    const IvfFlatWs w = ivf_flat_carve(workspace_dev, B, P, C);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
+    const dim3 qgrid((unsigned)((B + 3) / 4));
+    ANNLITE_HIP_TRY(hipMemsetAsync(w.f.ovf_total, 0, 256, st));
+    auto exact_cells = [&](int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
+        hipLaunchKernelGGL(ivf_flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, cells_dev, (int)P,
+                           (int)C, cell_rows_dev, perm_dev, n_perm, stride, valid_bits_dev, (int)k, sqrt_out, only_overflowed, thr_out,
+                           out_dist_dev, out_id_dev, w.f.ovf);
+        return launch_status("ivf_flat_exact_kernel");
+    };
+    int64_t strides[kIvfFlatMaxStages];
+    const int n_strides = ivf_flat_strides(max_probed_rows, strides);
+    if (n_strides == 0) return exact_cells(1, do_sqrt, 0, nullptr);  // few probed rows: exact sums over all of them
+    int rc = annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.f.qnorm, stream);
+    if (rc != ANNLITE_OK) return rc;
+    // the (cell, queries that probe it) tiles of the filter stages
+    rc = annlite_ivf_plan(cells_dev, B, P, C, kFlatTile, cell_rows_dev, cell_order_dev, w.n_tiles, w.vmap, w.slot_of, w.tile_rows, w.n_used,
+                          stream);
+    if (rc != ANNLITE_OK) return rc;
+    // stage 0: the k-th smallest exact distance among every strides[0]-th entry of the query's cells
+    if ((rc = exact_cells(strides[0], 0, 0, w.f.thr)) != ANNLITE_OK) return rc;
+    for (int s = 1; s < n_strides; ++s) {
+        const bool last = s == n_strides - 1;  // (strides[n_strides - 1] == 1)
+        ANNLITE_HIP_TRY(hipMemsetAsync(w.f.cnt, 0, (size_t)B * 4, st));
+        rc = ivf_flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, N, perm_dev, n_perm, w, max_cell_rows, strides[s],
+                                    valid_bits_dev, st);
+        if (rc != ANNLITE_OK) return rc;
+        // the list re-rank of annlite_flat_search_topk, unchanged: the lists hold offsets
+        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.f.cand, w.f.cnt,
+                           kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0,
+                           last ? nullptr : w.f.thr, out_dist_dev, out_id_dev, w.f.ovf, w.f.ovf_total);
+        if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
+    }
+    // queries whose last list overflowed: exact sums over all their probed rows (the other waves leave at once)
+    return exact_cells(1, do_sqrt, 1, nullptr);
 }

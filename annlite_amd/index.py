@@ -16,6 +16,8 @@ GPU scan ``PQFlatGpuIndex`` instead of an HNSW graph walked one query at a time
 
 Without ``n_subvectors`` (the reference's default: an un-quantised float ``HnswIndex``) the index is ``FlatGpuIndex``: exact
 float32 search -- an f32 MFMA filter with a proven slack, then exact sums.  No codec, nothing to train.
+With ``n_cells > 1`` and ``ivf_prune=True`` it is ``IvfFlatGpuIndex``: cells over the float vectors -- a ``VQCodec`` to train, and
+a search that scans each query's ``n_probe`` nearest cells and answers those rows exactly.
 
 ``n_cells > 1`` (index.py:125-133, 458-483): a ``VQCodec`` coarse quantiser assigns every vector to a cell and ONE
 ``IvfPQGpuIndex`` holds all cells.  Like the reference (``n_probe = max(n_probe, n_cells)``, index.py:94) a search
@@ -64,7 +66,8 @@ class AnnLite:
     :param n_dim: dimensionality of input vectors (divisible by ``n_subvectors``)
     :param metric: 'euclidean', 'inner_product' or 'cosine'
     :param n_subvectors: number of PQ sub-quantisers = bytes per stored vector; ``None`` (the default, as in the reference)
-        keeps the float vectors themselves and searches them exactly (``FlatGpuIndex``; ``n_cells`` must be 1, no ``graph``)
+        keeps the float vectors themselves and searches them exactly (``FlatGpuIndex``; ``n_cells > 1`` needs ``ivf_prune=True``:
+        ``IvfFlatGpuIndex``; no ``graph``)
     :param n_clusters: codewords per sub-quantiser (default 256)
     :param rerank: keep the float vectors in HBM and re-score ADC candidates exactly (kwarg, rides
         the reference's ``**kwargs`` channel to the index, container.py:56).  With ``n_cells > 1`` and ``ivf_prune=True`` the same channel
@@ -101,9 +104,11 @@ class AnnLite:
             raise NotImplementedError('n_components (PCA projector) is outside the accelerated hot path (SURVEY.md section 2 row 15)')
         if not n_subvectors:
             # the reference's default configuration: an un-quantised float index (FlatGpuIndex: exact search)
-            if n_cells > 1:
-                raise NotImplementedError('n_cells > 1 without n_subvectors (cells over float vectors) is not implemented: pass n_subvectors, '
-                                          'or n_cells=1 for the exact float32 index')
+            if n_cells > 1 and not kwargs.get('ivf_prune'):
+                # (every cell visited -- all the reference does with its cells -- is the exact index with n_cells=1)
+                raise NotImplementedError('n_cells > 1 without n_subvectors (cells over float vectors) is the pruned exact search: pass '
+                                          'ivf_prune=True (a query then scans its n_probe nearest cells), or n_cells=1 for the exhaustive '
+                                          'exact float32 index, or n_subvectors')
             if kwargs.get('graph'):
                 raise NotImplementedError('graph=True without n_subvectors (a float HNSW graph) is not implemented: the float index '
                                           'searches exhaustively and exactly; pass n_subvectors for the graph over PQ codes')
@@ -177,6 +182,10 @@ class AnnLite:
             kw.pop('graph', None)
             for name in ('rerank', 'rerank_pool', 'skewed'):  # (PQ index options: the float index is exact already)
                 kw.pop(name, None)
+            if self._vq_codec is not None:  # (ivf_prune=True: the constructor refuses cells over floats without it)
+                from .core.index.ivf_flat_gpu import IvfFlatGpuIndex
+
+                return IvfFlatGpuIndex(dim=self.n_dim, metric=self.metric, vq_codec=self._vq_codec, n_probe=self._n_probe_arg, **kw)
             return FlatGpuIndex(dim=self.n_dim, metric=self.metric, **kw)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')
@@ -259,10 +268,9 @@ class AnnLite:
         if self._vq_codec is not None:  # index.py:218-222
             logger.info(f'Start training VQ codec (K={self.n_cells}) with {x.shape[0]} data...')
             self._vq_codec.fit(x)
-        if self._pq_codec is None:  # (force_train on the float index: still nothing to train)
-            return
-        self._pq_codec.fit(x)
-        if auto_save:
+        if self._pq_codec is not None:  # (the float index has no PQ codec: with cells only the VQ codec is trained)
+            self._pq_codec.fit(x)
+        if auto_save and (self._pq_codec is not None or self._vq_codec is not None):
             self.dump_model()
 
     def partial_train(self, x, auto_save: bool = True, force_train: bool = False):
@@ -273,11 +281,10 @@ class AnnLite:
         if self._vq_codec is not None:  # index.py:259-263
             self._vq_codec.partial_fit(x)
             self._vq_codec.build_codebook()
-        if self._pq_codec is None:
-            return
-        self._pq_codec.partial_fit(x)
-        self._pq_codec.build_codebook()
-        if auto_save:
+        if self._pq_codec is not None:
+            self._pq_codec.partial_fit(x)
+            self._pq_codec.build_codebook()
+        if auto_save and (self._pq_codec is not None or self._vq_codec is not None):
             self.dump_model()
 
     def dump_model(self):

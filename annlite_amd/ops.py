@@ -4,7 +4,7 @@ Every function takes/returns ``torch`` tensors living on the current HIP device 
 hand-written gfx950 kernels of ``libannlite_hip.so`` on torch's current stream.  No function here
 computes anything on the CPU; without a GPU they raise ``RuntimeError`` (``_capi.require_gpu``).
 """
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import ctypes
@@ -739,3 +739,46 @@ def flat_overflow_count(workspace: ScanWorkspace) -> int:
     n = ctypes.c_int64(0)
     check(lib().annlite_flat_overflow_count(buf.data_ptr(), stream_ptr(), ctypes.byref(n)), 'flat_overflow_count')
     return int(n.value)
+
+
+def flat_list_counts(workspace: ScanWorkspace, B: int) -> torch.Tensor:
+    """``annlite_flat_list_counts``: i32 [B], the rows the last filter stage of the last ``flat_search_topk`` /
+    ``ivf_flat_search_topk`` of ``B`` queries on this stream's workspace buffer offered each list (measurement scripts)."""
+    buf = workspace.bufs[stream_ptr()]
+    out = torch.empty((B,), dtype=torch.int32, device=buf.device)
+    check(lib().annlite_flat_list_counts(buf.data_ptr(), B, out.data_ptr(), stream_ptr()), 'flat_list_counts')
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- cells over float vectors
+def ivf_flat_stages(max_probed_rows: int) -> List[int]:
+    """``annlite_ivf_flat_stages``: the strides ``ivf_flat_search_topk`` uses for queries that probe at most ``max_probed_rows``
+    rows -- the first exact sample's, then the filter stages' down to 1; empty: exact sums over all probed rows (host only,
+    needs no GPU)."""
+    strides, n = (ctypes.c_int64 * 16)(), ctypes.c_int(0)
+    check(lib().annlite_ivf_flat_stages(int(max_probed_rows), strides, ctypes.byref(n)), 'ivf_flat_stages')
+    return [int(strides[i]) for i in range(n.value)]
+
+
+def ivf_flat_search_topk(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, cells: torch.Tensor,
+                         n_cells: int, perm: torch.Tensor, cell_rows: torch.Tensor, cell_order: torch.Tensor, max_cell_rows: int,
+                         max_probed_rows: int, k: int, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+                         sqrt: bool = False, workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_ivf_flat_search_topk``: exact k nearest (k <= 64) among the rows of each query's probed ``cells`` i32 [B, P] --
+    ``perm`` i32 = the live offsets grouped by cell, ``cell_rows`` i64 [C, 2] their ranges, ``cell_order`` i32 [C] cells by
+    descending size.  ``(dist f32 [B, k], ids i64 [B, k])`` ascending by (distance, id), (+inf, -1) padded;
+    ``flat_overflow_count(workspace)`` reads the call's overflow counter afterwards."""
+    B, D = queries.shape
+    P = cells.shape[1]
+    N = vectors.shape[0] if n_rows is None else n_rows
+    need = ctypes.c_int64(0)
+    check(lib().annlite_ivf_flat_search_workspace_bytes(B, P, n_cells, k, ctypes.byref(need)), 'ivf_flat_search_workspace_bytes')
+    dev = queries.device
+    ws = (workspace or ScanWorkspace()).get(int(need.value), dev)
+    od = torch.empty((B, k), dtype=torch.float32, device=dev)
+    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
+    check(lib().annlite_ivf_flat_search_topk(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
+                                             cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
+                                             cell_order.data_ptr(), int(max_cell_rows), int(max_probed_rows), int(k), 1 if sqrt else 0,
+                                             od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), 'ivf_flat_search_topk')
+    return od, oi

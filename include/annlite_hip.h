@@ -483,6 +483,39 @@ ANNLITE_API int annlite_flat_search_topk(int metric, const float *queries_dev, i
 /* Queries of the last annlite_flat_search_topk on this workspace whose final candidate list overflowed (they were answered by exact
  * sums over all rows).  Synchronises the stream.  No reference counterpart. */
 ANNLITE_API int annlite_flat_overflow_count(const void *workspace_dev, void *stream, int64_t *count);
+/* count_dev i32 [B] = how many rows the LAST filter stage of the last search on this workspace (annlite_flat_search_topk or
+ * annlite_ivf_flat_search_topk with the same B) offered each query's list; above annlite_flat_list_capacity(): overflowed.
+ * Undefined after a search that ran no filter.  For measurements; no reference counterpart. */
+ANNLITE_API int annlite_flat_list_counts(const void *workspace_dev, int64_t B, int32_t *count_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Cells over float vectors: the exact search above restricted to the rows of each query's P probed cells.
+ * replaces: the reference's n_cells > 1 structure over its default float index -- AnnLite._cell_selection's consumers, one float
+ * index per cell and the hstack / argsort merge of CellContainer.ivf_search (annlite/container.py:88-144) -- with n_probe < n_cells
+ * (the reference itself always visits every cell, index.py:94: that is annlite_flat_search_topk).
+ * The vectors stay where they are; the cells are a permutation:
+ *   perm_dev       i32 [n_perm]  offsets of the live rows grouped by cell, ascending inside a cell
+ *   cell_rows_dev  i64 [C][2]    (begin, end) of every cell in perm_dev
+ *   cell_order_dev i32 [C]       cells by descending size
+ *   cells_dev      i32 [B][P]    the probed cells of every query (annlite_ivf_select_cells; distinct per query; an id outside
+ *                                [0, C) is read as cell 0, as annlite_ivf_plan reads it)
+ * Result: per query the k nearest of the rows of its cells that are set in valid_bits_dev (may be NULL) -- distances, order and
+ * padding exactly as annlite_flat_search_topk, i.e. annlite_rerank_topk's arithmetic over those rows.
+ * ---------------------------------------------------------------------------------------------- */
+/* The strides the search uses for a query that probes at most max_probed_rows rows (host only; no reference counterpart):
+ * strides_out[0] = the first exact sample takes every strides_out[0]-th entry of each probed cell, strides_out[1 ..] = the filter
+ * stages', descending to 1.  *n_out = how many (at most 16; 0: exact sums over all probed rows, no filter). */
+ANNLITE_API int annlite_ivf_flat_stages(int64_t max_probed_rows, int64_t *strides_out, int *n_out);
+ANNLITE_API int annlite_ivf_flat_search_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t k, int64_t *bytes);
+/* max_cell_rows = the largest cell's length (bounds the filter's grid: rows of a longer cell would not be seen), max_probed_rows =
+ * the sum of the P largest lengths (chooses the stages; any value is correct).  C <= 16384, 1 <= k <= 64, N < 2^31.  All launches
+ * on `stream`, no host round trip; annlite_flat_overflow_count(workspace) counts the queries that took the slower route. */
+ANNLITE_API int annlite_ivf_flat_search_topk(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                 const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev,
+                                 int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                 const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t max_probed_rows, int64_t k,
+                                 int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
+                                 void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pruned (IVF) search over cells (follow-on of rank 4).
