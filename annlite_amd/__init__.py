@@ -2,7 +2,7 @@
 
 Public surface (mirrors the reference's names, see DESIGN.md / INTEGRATION.md):
 
-    from annlite_amd import AnnLite, PQCodec, PQFlatGpuIndex, HnswPQGpuIndex, Metric, pq_bind
+    from annlite_amd import AnnLite, PQCodec, PQFlatGpuIndex, HnswPQGpuIndex, FlatGpuIndex, HnswFlatGpuIndex, Metric, pq_bind
 
 The compute path is the hand-written HIP library ``annlite_amd/libannlite_hip.so`` (C ABI in
 ``include/annlite_hip.h``), loaded through ctypes; there is no CPU fallback.
@@ -27,6 +27,12 @@ def __getattr__(name):
     if name == 'HnswPQGpuIndex':
         from .core.index.hnsw_pq_gpu import HnswPQGpuIndex
         return HnswPQGpuIndex
+    if name == 'FlatGpuIndex':
+        from .core.index.flat_gpu import FlatGpuIndex
+        return FlatGpuIndex
+    if name == 'HnswFlatGpuIndex':
+        from .core.index.hnsw_flat_gpu import HnswFlatGpuIndex
+        return HnswFlatGpuIndex
     if name in ('pq_bind', 'ops', 'math', 'sharded'):
         import importlib
         return importlib.import_module('.' + name, __name__)

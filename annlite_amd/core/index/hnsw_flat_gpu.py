@@ -1,0 +1,153 @@
+"""``HnswFlatGpuIndex`` -- a level-0 HNSW graph over the un-quantised float vectors, built and walked on the GPU: the sub-linear form of
+the reference's default configuration (``AnnLite(n_dim)`` without ``n_subvectors`` is ``HnswIndex`` on float vectors,
+annlite/core/index/hnsw/index.py:52-191; same knobs: ``max_connection`` 16, ``ef_construction`` 200, ``ef_search`` 50).
+
+It IS a ``FlatGpuIndex`` -- same rows, norms, validity bitmap, exact ``search_exhaustive`` -- with link lists beside the rows:
+
+  * built in batches by ``graph_gpu_build.GpuLevel0GraphF32`` (``graph_f32.hip``), which reads this index's own
+    ``_vectors`` column: no second copy of the vectors;
+  * walked by ``annlite_graph_f32_search``, one wave per query.  Every distance of build and walk carries
+    ``annlite_exact_gather_dist``'s bits for the metric -- the numbers ``FlatGpuIndex`` returns -- so the walk's list is final: no
+    re-rank, a stored vector found by its own query comes back at exactly 0.0, and an id both indexes return carries the same bits.
+    As in hnswlib's spaces the graph is built and walked with the metric's own distance (COSINE rows are stored normalised: the L2
+    order; INNER_PRODUCT walks ``1 - <q, x>``).
+
+A search the graph does not serve -- a filter (``indices=``), k or ef beyond 256, no graph yet -- is answered by the exact search of
+the parent: never worse.  Ids must be dense in insertion order (0, 1, 2, ...: what AnnLite's offsets are); rows are not updated in
+place (delete + add a new offset, hnsw/index.py:173-177); a delete clears the validity bit only -- the row keeps routing the walk.
+"""
+from pathlib import Path
+from typing import List, Optional, Tuple, Union
+
+import numpy as np
+import torch
+
+from ... import ops
+from ...enums import Metric
+from .flat_gpu import FlatGpuIndex
+from .row_store import empty_answer, like_input, ranked_answer
+
+
+class HnswFlatGpuIndex(FlatGpuIndex):
+    FORMAT = 'annlite_amd.HnswFlatGpuIndex/1'
+    ALSO_LOADS = (FlatGpuIndex.FORMAT,)  # (rows without links: the graph is rebuilt from them)
+    MAX_EF = 256                         # the walk's list: four registers per lane
+    MAX_DIM = 2048
+
+    def __init__(self, dim: int, dtype: np.dtype = np.float32, metric: Metric = Metric.COSINE, ef_construction: int = 200,
+                 ef_search: int = 50, max_connection: int = 16, seed: int = 100, build: Optional[str] = 'gpu',
+                 index_file: Optional[Union[str, Path]] = None, **kwargs):
+        # (named here: RowStoreIndex drops the HNSW kwargs the reference forwards to every index)
+        if build not in (None, 'gpu'):
+            raise NotImplementedError(f"build={build!r}: only the GPU-built level-0 graph exists over float vectors (build='gpu')")
+        if not 2 <= int(max_connection) <= 16:
+            raise ValueError(f'max_connection={max_connection}: the GPU graph holds 2 * max_connection <= 32 links per node (2 ... 16)')
+        if not 1 <= int(dim) <= self.MAX_DIM:
+            raise ValueError(f'dim={dim}: the float graph takes 1 <= dim <= {self.MAX_DIM}')
+        super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
+        self.ef_construction = int(ef_construction)  # hnsw/index.py:66-69
+        self.ef_search = int(ef_search)
+        self.max_connection = int(max_connection)
+        self.seed = int(seed)  # (kept for the reference's signature: level 0 only -- no random level is drawn)
+        self.build = 'gpu'
+        self._gg = None  # GpuLevel0GraphF32
+        if index_file:
+            self.load(index_file)
+
+    # ------------------------------------------------------------------ graph handle
+    def _ensure_graph(self):
+        if self._gg is None:
+            from .graph_gpu_build import GpuLevel0GraphF32
+
+            self._gg = GpuLevel0GraphF32(self._device(), int(self.metric), self.max_connection, self.ef_construction)
+        return self._gg
+
+    def _rebuild_graph(self, N: int):
+        """Link rows 0 .. N of the vector column from nothing."""
+        self._gg = None
+        if N:
+            gg = self._ensure_graph()
+            gg.reserve(int(self.capacity))
+            gg.add(self._vectors, N)
+
+    # ------------------------------------------------------------------ build
+    def add_with_ids(self, x, ids: List[int], **kwargs):
+        ids_np = np.ascontiguousarray(np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids, dtype=np.int64)).reshape(-1)
+        if ids_np.size == 0:
+            return
+        n = self._n_rows
+        if not (ids_np[0] == n and (np.diff(ids_np) == 1).all()):
+            raise RuntimeError(f'the GPU-built graph takes ids in insertion order (next: {n}, got {ids_np[:3]}...)')
+        super().add_with_ids(x, ids_np)  # rows, norms, validity (the parent pre-processes; it may re-allocate the columns)
+        gg = self._ensure_graph()
+        if gg.n != n:  # (rows without links -- a graph dropped behind the rows' back: link them all)
+            self._rebuild_graph(self._n_rows)
+            return
+        gg.reserve(int(self.capacity))
+        gg.add(self._vectors, ids_np.size)
+
+    def update_with_ids(self, x, ids: List[int], **kwargs):
+        raise RuntimeError('the HNSW graph does not support in-place updates (delete + add a new offset): '
+                           'hnsw/index.py:173-177')
+
+    def reset(self, capacity: Optional[int] = None):
+        super().reset(capacity=capacity)
+        self._gg = None
+
+    # ------------------------------------------------------------------ search
+    def candidates(self, q_dev: torch.Tensor, ef: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Graph walk for pre-processed queries ``q_dev`` f32 [B, D]: ``(ids i64 [B, ef], distance f32 [B, ef])`` on the device,
+        ascending by (distance, id); deleted rows blanked in place to (-1, +inf).  The distances are the metric's own, final (squared
+        for EUCLIDEAN)."""
+        ef = int(ef or self.ef_search)
+        gg = self._gg
+        if gg is None or gg.n == 0 or gg.n != self._n_rows:
+            raise RuntimeError('no graph to walk (the index is empty)')
+        if ef > self.MAX_EF:
+            raise RuntimeError(f'the GPU walk keeps ef <= {self.MAX_EF} candidates (ef = {ef})')
+        return ops.graph_f32_search(int(self.metric), q_dev.contiguous(), self._vectors, gg.links, gg.seeds(), ef,
+                                    valid_bits=self._valid, n_rows=gg.n)
+
+    def search_exhaustive(self, x, limit: int = 10, **kw):
+        return super().search_batch(x, limit=limit, **kw)
+
+    def search_batch(self, x, limit: int = 10, indices=None, ef_search: Optional[int] = None, **kwargs):
+        """``(dists [B, k], ids [B, k])``: the first k real entries of the walk's list of ``max(ef_search, k)`` candidates.  A filter
+        (``indices``), an index without a graph and k or ef beyond 256 are answered by the parent's exact search."""
+        k = int(limit)
+        ef = max(int(ef_search or self.ef_search), k)
+        gg = self._gg
+        if indices is not None or gg is None or gg.n == 0 or gg.n != self._n_rows or k > self.MAX_EF or ef > self.MAX_EF:
+            return super().search_batch(x, limit=limit, indices=indices)
+        is_np = not isinstance(x, torch.Tensor)
+        q = self._pre(x)
+        B = q.shape[0]
+        self._overflowed = 0
+        if B == 0:
+            return like_input(is_np, *empty_answer(B, k, q.device))
+        cand, cand_d = self.candidates(q, ef)
+        if k <= 64:
+            d, pos = ops.topk_rows(cand_d, min(k, ef))
+        else:  # (beyond the wave kernel's k: a stable sort keeps the (value, position) order)
+            sd, si = torch.sort(cand_d, dim=1, stable=True)
+            d, pos = sd[:, :k], torch.where(torch.isinf(sd[:, :k]), torch.full_like(si[:, :k], -1), si[:, :k])
+        return like_input(is_np, *ranked_answer(cand, d, pos, k, sqrt=self.metric == Metric.EUCLIDEAN))
+
+    # ------------------------------------------------------------------ persistence: the links ride in the row store's one envelope
+    def _dump_state(self, N):
+        st = super()._dump_state(N)
+        gg = self._gg
+        if gg is not None and gg.n == N and N:
+            st['links'] = gg.links[:N].cpu().numpy()
+            st['max_connection'] = self.max_connection
+        return st
+
+    def _load_state(self, state, N):
+        super()._load_state(state, N)
+        self._gg = None
+        links = state.get('links')
+        if N and links is not None and links.shape == (N, 2 * self.max_connection + 1):
+            self._ensure_graph().load_state({'n': N, 'links': links})
+        elif N:
+            # rows without (usable) links -- the flat index's file, or lists of another max_connection: rebuilt from the stored rows
+            self._rebuild_graph(N)

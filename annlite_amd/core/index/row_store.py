@@ -75,6 +75,7 @@ def like_input(is_np: bool, d: torch.Tensor, i: torch.Tensor):
 class RowStoreIndex(BaseIndex):
     FORMAT: str = ''                  # the `format` string of the index's files
     STATE_KEYS: Tuple[str, ...] = ()  # attributes written as integers by `dump` that `load` requires to be the index's own
+    ALSO_LOADS: Tuple[str, ...] = ()  # formats of other indexes whose files `load` takes as well (same keys, a subset of the state)
 
     def __init__(self, dim: int, dtype: np.dtype = np.float32, metric: Metric = Metric.COSINE, **kwargs):
         # HNSW-only kwargs the reference forwards are accepted and ignored
@@ -266,7 +267,7 @@ class RowStoreIndex(BaseIndex):
     def load(self, index_file: Union[str, Path]):
         with open(str(index_file), 'rb') as f:
             state = np.load(f, allow_pickle=True)[0]
-        assert state['format'] == self.FORMAT
+        assert state['format'] == self.FORMAT or state['format'] in self.ALSO_LOADS
         assert all(state[key] == getattr(self, key) for key in self.STATE_KEYS)
         self._alloc(max(int(state['capacity']), self._capacity))
         N = int(state['n_rows'])

@@ -67,7 +67,7 @@ class AnnLite:
     :param metric: 'euclidean', 'inner_product' or 'cosine'
     :param n_subvectors: number of PQ sub-quantisers = bytes per stored vector; ``None`` (the default, as in the reference)
         keeps the float vectors themselves and searches them exactly (``FlatGpuIndex``; ``n_cells > 1`` needs ``ivf_prune=True``:
-        ``IvfFlatGpuIndex``; no ``graph``)
+        ``IvfFlatGpuIndex``) or, with ``graph=True, build='gpu'``, through a level-0 HNSW graph over them (``HnswFlatGpuIndex``)
     :param n_clusters: codewords per sub-quantiser (default 256)
     :param rerank: keep the float vectors in HBM and re-score ADC candidates exactly (kwarg, rides
         the reference's ``**kwargs`` channel to the index, container.py:56).  With ``n_cells > 1`` and ``ivf_prune=True`` the same channel
@@ -110,8 +110,13 @@ class AnnLite:
                                           'ivf_prune=True (a query then scans its n_probe nearest cells), or n_cells=1 for the exhaustive '
                                           'exact float32 index, or n_subvectors')
             if kwargs.get('graph'):
-                raise NotImplementedError('graph=True without n_subvectors (a float HNSW graph) is not implemented: the float index '
-                                          'searches exhaustively and exactly; pass n_subvectors for the graph over PQ codes')
+                # the float HNSW graph (HnswFlatGpuIndex): only the GPU-built level-0 graph exists over floats
+                # -- there is no host library for it -- so it is opted into with the PQ graph's `build` vocabulary
+                if n_cells > 1:
+                    raise NotImplementedError('graph=True and n_cells > 1 cannot be combined (the float graph is one index over all rows)')
+                if kwargs.get('build') != 'gpu':
+                    raise NotImplementedError("graph=True without n_subvectors (a float HNSW graph) exists as the GPU-built level-0 graph "
+                                              "only: pass build='gpu' (build='host' needs n_subvectors: the graph over PQ codes)")
         self.n_dim = n_dim
         self.n_components = n_components
         self.n_subvectors = n_subvectors
@@ -179,9 +184,14 @@ class AnnLite:
 
             if self._devices is not None and len(self._devices) > 1:
                 warnings.warn('devices= is ignored for the float index (it lives on the current device)')
-            kw.pop('graph', None)
+            graph = kw.pop('graph', False)
             for name in ('rerank', 'rerank_pool', 'skewed'):  # (PQ index options: the float index is exact already)
                 kw.pop(name, None)
+            if graph:  # (build='gpu', n_cells == 1: the constructor refuses the rest)
+                from .core.index.hnsw_flat_gpu import HnswFlatGpuIndex
+
+                return HnswFlatGpuIndex(dim=self.n_dim, metric=self.metric, **kw)
+            kw.pop('build', None)
             if self._vq_codec is not None:  # (ivf_prune=True: the constructor refuses cells over floats without it)
                 from .core.index.ivf_flat_gpu import IvfFlatGpuIndex
 

@@ -201,6 +201,59 @@ def graph_pack_nodes(links: torch.Tensor, codes: torch.Tensor, nodes: torch.Tens
                                          nodes.data_ptr(), nodes.numel(), packed.data_ptr(), stream_ptr()), 'graph_pack_nodes')
 
 
+# ---------------------------------------------------------------------------------------------- float graph (graph_f32.hip)
+def graph_f32_search(metric: int, queries: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor, seeds: torch.Tensor, ef: int,
+                     valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_graph_f32_search``: the beam walk over the level-0 lists ``links`` i32 [N, L+1] (count, ids) with exact distances on
+    the float rows ``vectors`` f32 [N, D] (``exact_gather_dist``'s bits).  Returns (ids i64 [B, ef] ascending by (distance, id), rows
+    cleared in ``valid_bits`` blanked in place to -1; dist f32 [B, ef], +inf there)."""
+    assert queries.dtype == torch.float32 and vectors.dtype == torch.float32 and queries.is_contiguous() and vectors.is_contiguous()
+    assert links.is_contiguous() and seeds.is_contiguous() and links.element_size() == 4 and seeds.element_size() == 4
+    B, D = queries.shape
+    assert vectors.shape[1] == D
+    N = vectors.shape[0] if n_rows is None else int(n_rows)
+    assert N <= vectors.shape[0] and N <= links.shape[0]
+    out_i = torch.empty((B, ef), dtype=torch.int64, device=vectors.device)
+    out_d = torch.empty((B, ef), dtype=torch.float32, device=vectors.device)
+    check(lib().annlite_graph_f32_search(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, links.data_ptr(), links.shape[1] - 1,
+                                         seeds.data_ptr(), seeds.numel(), _ptr(valid_bits), int(ef), out_i.data_ptr(), out_d.data_ptr(),
+                                         stream_ptr()), 'graph_f32_search')
+    return out_i, out_d
+
+
+def graph_f32_search_stats() -> Tuple[int, int]:
+    """(expansions, rows evaluated) of the last float graph walk (ANNLITE_DEBUG_COUNTERS=1)."""
+    out = (ctypes.c_uint64 * 2)()
+    check(lib().annlite_graph_f32_search_stats(out), 'graph_f32_search_stats')
+    return int(out[0]), int(out[1])
+
+
+def graph_f32_build_select(metric: int, cand: torch.Tensor, base0: int, vectors: torch.Tensor, max_keep: int, links: torch.Tensor,
+                           n_rows: Optional[int] = None) -> torch.Tensor:
+    """``annlite_graph_f32_build_select``: ``graph_build_select`` with the float distance between the rows of ``vectors``."""
+    assert cand.dtype == torch.int64 and cand.is_contiguous() and vectors.dtype == torch.float32 and vectors.is_contiguous()
+    b, ef = cand.shape
+    N = vectors.shape[0] if n_rows is None else int(n_rows)
+    assert N <= vectors.shape[0] and N <= links.shape[0] and links.is_contiguous() and links.element_size() == 4
+    pairs = torch.empty((b, int(max_keep)), dtype=torch.int64, device=vectors.device)
+    check(lib().annlite_graph_f32_build_select(int(metric), cand.data_ptr(), int(ef), b, int(base0), vectors.data_ptr(), N, vectors.shape[1],
+                                               int(max_keep), links.data_ptr(), links.shape[1] - 1, pairs.data_ptr(), stream_ptr()),
+          'graph_f32_build_select')
+    return pairs
+
+
+def graph_f32_build_reverse(metric: int, keys_sorted: torch.Tensor, seg: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor,
+                            n_rows: Optional[int] = None):
+    """``annlite_graph_f32_build_reverse``: ``graph_build_reverse`` with the float distance between the rows of ``vectors``."""
+    assert keys_sorted.dtype == torch.int64 and seg.dtype == torch.int64 and keys_sorted.is_contiguous() and seg.is_contiguous()
+    assert vectors.dtype == torch.float32 and vectors.is_contiguous() and links.is_contiguous() and links.element_size() == 4
+    N = vectors.shape[0] if n_rows is None else int(n_rows)
+    assert N <= vectors.shape[0] and N <= links.shape[0]
+    check(lib().annlite_graph_f32_build_reverse(int(metric), keys_sorted.data_ptr(), seg.data_ptr(), seg.numel() - 1, vectors.data_ptr(), N,
+                                                vectors.shape[1], links.data_ptr(), links.shape[1] - 1, stream_ptr()),
+          'graph_f32_build_reverse')
+
+
 class ScanWorkspace:
     """Re-usable device scratch for the scan (avoids an allocation per search call).  One buffer PER STREAM:
     batches issued on different streams run concurrently (the next batch's kernels fill the CUs the previous

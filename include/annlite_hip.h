@@ -215,6 +215,27 @@ ANNLITE_API int annlite_graph_search_stats(uint64_t *out2);
 /* ... EIGHT counters: [2] the expansions whose record had been prefetched (packed walk); shader cycles summed over the queries'
  * waves: [3] seed phase, [4] pick + wait for the record, [5] visited table, [6] PQLookup sums, [7] list merge. */
 ANNLITE_API int annlite_graph_search_stats_ex(uint64_t *out8);
+/* ---- the level-0 graph over FLOAT vectors (graph_f32.hip): the walk and the two build kernels above with ONE float distance ------
+ * Every distance compared -- query to row in the walk, row to row in the build -- carries annlite_exact_gather_dist's bits for the
+ * metric (64 lane-strided fmaf chains, the xor butterfly 32..1; EUCLIDEAN: sum of (x[j] - q[j])^2, else 1 - sum of x[j] q[j]): the
+ * walk's list holds final distances, a stored vector finds itself at exactly 0.0.  1 <= D <= 2048.
+ *   annlite_graph_f32_search         one wave per query over links_dev u32 [N][links_per_node + 1] (count, ids; links_per_node <= 64),
+ *                                    seeds_dev u32 [n_seeds] DISTINCT, vectors_dev f32 [N][D], queries_dev f32 [B][D]; ef <= 256.  The
+ *                                    order of annlite_graph_search; the list is ordered by (distance, node id), NaN behind +inf.
+ *                                    out_ids_dev i64 [B][ef] / out_dist_dev f32 [B][ef]: ascending, rows cleared in valid_bits_dev
+ *                                    (may be NULL) blanked IN PLACE to (-1, +inf) -- they still route the walk.
+ *   annlite_graph_f32_build_select   annlite_graph_build_select; the batch's points are rows base0 .. base0 + b of vectors_dev [N][D]
+ *   annlite_graph_f32_build_reverse  annlite_graph_build_reverse; a shrinking pool is ordered by (distance to the target, id)
+ *   annlite_graph_f32_search_stats   debug aid (ANNLITE_DEBUG_COUNTERS=1): [0] expansions, [1] rows evaluated of the last float walk */
+ANNLITE_API int annlite_graph_f32_search(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
+                         const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
+                         const uint32_t *valid_bits_dev, int ef, int64_t *out_ids_dev, float *out_dist_dev, void *stream);
+ANNLITE_API int annlite_graph_f32_build_select(int metric, const int64_t *cand_dev, int ef, int64_t b, int64_t base0,
+                         const float *vectors_dev, int64_t N, int64_t D, int max_keep, uint32_t *links_dev, int links_per_node,
+                         int64_t *pairs_dev, void *stream);
+ANNLITE_API int annlite_graph_f32_build_reverse(int metric, const int64_t *keys_dev, const int64_t *seg_dev, int64_t n_segments,
+                         const float *vectors_dev, int64_t N, int64_t D, uint32_t *links_dev, int links_per_node, void *stream);
+ANNLITE_API int annlite_graph_f32_search_stats(uint64_t *out2);
 
 /* ------------------------------------------------------------------------------------------------
  * Batched flat ADC scan + top-k: the hot path.
