@@ -388,7 +388,7 @@ __global__ __launch_bounds__(kSeedWaves * 64) void seed_bound_kernel(const uint8
             ((double *)(s_par + 8))[tid] = Lsum;
             ((unsigned long long *)(s_par + 16))[tid] = ~0ull;
             gkey[b] = ~0ull;  // (the fill leaves the bounds to this kernel; the selection below overwrites it)
-            if (sb.seedk)
+            if (sb.seedk && b < B)  // (seedk is the caller's [B][kSeedKeys], not padded to the group of 16 like the workspace arrays)
                 for (int j = 0; j < kSeedKeys; ++j) sb.seedk[(int64_t)b * kSeedKeys + j] = ~0ull;
             if constexpr (CELLS) {  // the query's nearest cell: [begin, end) and its blocks of 64 rows (behind the kept parameters)
                 int32_t *s_cell = (int32_t *)(s_par + 96);  // [4] begin, [4] end, [4] blocks

@@ -1,14 +1,19 @@
 """The float graph walk (annlite_graph_f32_search, graph_f32.hip) pinned BIT FOR BIT against a plain restatement of its order.
 
-The order is that of the PQ walk one node at a time (tests/test_graph_pair.py ``walk_restated`` with width 1, restated here): seeds
-scanned flat in rounds of 64, the best unexpanded entry expanded, a step's unseen neighbours (ids < N) tested against the list's
-worst entry BEFORE any of them is inserted, the walk over when the first min(ef, 64 E) entries hold no unexpanded node.  What
-differs is the distance: ``ops.exact_gather_dist`` over all rows is the oracle -- the kernel's distances carry its bits -- and the
-list is ordered by (``f32_key(distance)``, node id): negative distances (INNER_PRODUCT) ascend, NaN sorts behind +inf."""
+The order is that of the PQ walk one node at a time (tests/test_graph_pair.py ``walk_restated`` with width 1, restated in
+tests/_refs.py): seeds scanned flat in rounds of 64, the best unexpanded entry expanded, a step's unseen neighbours (ids < N) tested
+against the list's worst entry BEFORE any of them is inserted, the walk over when the first min(ef, 64 E) entries hold no unexpanded
+node.  What differs is the distance: ``ops.exact_gather_dist`` over all rows is the oracle -- the kernel's distances carry its bits --
+and the list is ordered by (``f32_key(distance)``, node id): negative distances (INNER_PRODUCT) ascend, NaN sorts behind +inf.
+
+Beyond the comfortable shapes: a visited table of 16 or 64 entries (every node evaluated again and again, the merge's duplicate
+check alone keeps the list right: tests/test_graph_f32_restated.py is the argument, without a GPU), D = 1 and D = 2048 (three waves
+per workgroup), ef = 1, L = 1, B = 1, one seed, 64 and 65 seeds, seeds beyond the table, a table of one row -- and the returned
+distances against float64 within the fp32 summation bound of tests/test_rerank_topk.py."""
 import numpy as np
 import pytest
 
-from _refs import bitmap, f32_key
+from _refs import bitmap, f32_key, fp32_chain_bound, random_links as _random_graph, walk_restated
 from conftest import has_gpu
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason='needs a GPU')]
@@ -24,71 +29,6 @@ def ops():
 
     torch.cuda.set_device(0)
     return _ops
-
-
-def _random_graph(rs, n, L, full_frac=0.6):
-    links = np.zeros((n, L + 1), np.uint32)
-    cnt = np.where(rs.rand(n) < full_frac, L, rs.randint(0, L + 1, n)).astype(np.uint32)  # ragged and empty lists
-    links[:, 0] = cnt
-    nb = rs.randint(0, n, size=(n, L)).astype(np.uint32)
-    near = (np.arange(n)[:, None] + rs.randint(1, 50, size=(n, L))) % n
-    nb = np.where(rs.rand(n, L) < 0.7, near, nb).astype(np.uint32)
-    nb[rs.rand(n, L) < 0.002] = n + 5  # beyond the table: never followed
-    nb[:, 1] = np.where(rs.rand(n) < 0.05, nb[:, 0], nb[:, 1])  # a neighbour listed twice
-    links[:, 1:] = nb
-    return links.view(np.int32)
-
-
-def _key_to_bits(k):
-    """inverse of the list's key: the float's own bits (the canonical NaN for the NaN key)"""
-    k = int(k)
-    return k ^ 0x80000000 if k & 0x80000000 else k ^ 0xffffffff
-
-
-def walk_restated(links, seeds, keys, ef, valid=None):
-    """One query.  ``links`` u32 [N, L+1] (count, ids), ``keys`` u64 [N]: f32_key of the query's distance to every row.
-    Returns (ids i64 [ef], distance bits u32 [ef])."""
-    n = keys.shape[0]
-    E = 1 if ef <= 64 else 2 if ef <= 128 else 4  # registers per lane of the kernel's list
-    slots, cap = 64 * E, min(ef, 64 * E)
-    lst = []  # sorted [(key, node, expanded)]: the kernel's list of 64 E entries, `cap` of them live
-    seen = set()
-
-    def offer(nodes):
-        if not len(nodes):
-            return
-        worst = (lst[cap - 1][0], lst[cap - 1][1]) if len(lst) >= cap else (1 << 40, 1 << 40)
-        new = [(int(keys[v]), int(v), False) for v in nodes if (int(keys[v]), int(v)) < worst]
-        lst.extend(new)
-        lst.sort(key=lambda t: (t[0], t[1]))
-        del lst[slots:]
-
-    seeds = [int(s) for s in seeds]
-    for s0 in range(0, len(seeds), 64):
-        offer([s for s in seeds[s0:s0 + 64] if s < n])
-    for t in lst:
-        seen.add(t[1])
-    while True:
-        pick = [i for i, t in enumerate(lst[:cap]) if not t[2]][:1]
-        if not pick:
-            break
-        i = pick[0]
-        lst[i] = (lst[i][0], lst[i][1], True)
-        fresh = []
-        row = links[lst[i][1]]
-        for nb in row[1:1 + int(row[0])]:
-            nb = int(nb)
-            if nb < n and nb not in seen:
-                seen.add(nb)
-                fresh.append(nb)
-        offer(fresh)
-    ids = np.full(ef, -1, np.int64)
-    bits = np.full(ef, np.float32(np.inf).view(np.uint32), np.uint32)
-    for i, t in enumerate(lst[:cap]):
-        if valid is None or valid[t[1]]:
-            ids[i] = t[1]
-            bits[i] = _key_to_bits(t[0])
-    return ids, bits
 
 
 SHAPES = [(128, 32, 128), (64, 32, 64), (3, 5, 10), (200, 17, 33), (128, 32, 129), (128, 32, 200), (768, 24, 256), (128, 64, 100)]
@@ -145,3 +85,207 @@ def test_float_walk_refuses_what_it_cannot_hold(ops):
     x = torch.zeros((100, 8), dtype=torch.float32, device='cuda')
     with pytest.raises(Exception, match='ef'):
         ops.graph_f32_search(EUCLIDEAN, x[:2].contiguous(), x, links, seeds, 257)
+
+
+# ---- the same data at any size, made once per shape and shared: the tests below leave it unchanged ------------------------------
+class _Case:
+    pass
+
+
+_cases = {}
+
+
+def _case(ops, metric, D, L, n=N, b=B, seeds='150'):
+    """The data of the test above for a table of ``n`` rows and ``b`` queries: tie block, a stored row as its own query, a NaN and an
+    inf query (where the batch has them), a neighbour listed twice, ids beyond the table; the distance matrix of
+    ``exact_gather_dist`` and its keys.  ``seeds``: '150' distinct ids, '1' / '64' / '65' of them, or 'beyond': every fifth id >= n."""
+    import torch
+
+    key = (metric, D, L, n, b, seeds)
+    if key in _cases:
+        return _cases[key]
+    rs = np.random.RandomState(metric * 100003 + D * 1000 + L * 7 + n + 31 * b)
+    c = _Case()
+    c.metric, c.D, c.L, c.n, c.b = metric, D, L, n, b
+    c.links = _random_graph(rs, n, L)
+    c.x = rs.randn(n, D).astype(np.float32)
+    t0 = n // 3
+    c.x[t0:t0 + 40] = c.x[t0]
+    c.q = rs.randn(b, D).astype(np.float32)
+    c.self_q, c.self_row = min(2, b - 1), 77
+    c.q[c.self_q] = c.x[c.self_row]
+    if metric == COSINE:
+        c.x /= np.linalg.norm(c.x, axis=1, keepdims=True)
+        c.q /= np.linalg.norm(c.q, axis=1, keepdims=True)
+    if b > 7:
+        c.q[4, D // 2] = np.nan
+        c.q[7, 0] = np.inf
+    full = np.nonzero(c.links.view(np.uint32)[:, 0] == L)[0]  # (seeds with a full list: a walk from one seed goes somewhere)
+    n_seeds = N_SEEDS if seeds in ('150', 'beyond') else int(seeds)
+    c.seeds = rs.choice(full, n_seeds, replace=False).astype(np.int64)
+    if n_seeds >= 64 and c.self_row not in c.seeds:
+        c.seeds[1] = c.self_row  # (the links are random, not a proximity graph: the row that is its own query is a seed)
+    if seeds == 'beyond':
+        c.seeds[::5] = n + np.arange(c.seeds[::5].size) * 7  # skipped: neither evaluated nor recorded
+        c.seeds[5] = 0xfffffffe  # (the largest id the format has)
+    c.seeds = c.seeds.astype(np.uint32)
+    c.valid = rs.rand(n) < 0.9
+    c.x_d, c.q_d, c.links_d, c.seeds_d = ops.to_dev(c.x), ops.to_dev(c.q), ops.to_dev(c.links), ops.to_dev(c.seeds)
+    c.vb = ops.to_dev(bitmap(c.valid))
+    all_rows = torch.arange(n, device='cuda', dtype=torch.int64)[None, :].expand(b, n).contiguous()
+    c.dist = ops.exact_gather_dist(metric, c.q_d, c.x_d, all_rows).cpu().numpy()
+    if b > 7:
+        assert np.isnan(c.dist[4]).all() and not np.isfinite(c.dist[7]).any()
+    c.keys = f32_key(c.dist)
+    c.restated = {}
+    _cases[key] = c
+    return c
+
+
+def _restated(c, ef):
+    """{masked: ([ids per query], [bits per query])} and the walk's counters summed over the batch, computed once per (case, ef)"""
+    if ef not in c.restated:
+        lk = c.links.view(np.uint32)
+        out = {}
+        tot = dict(expansions=0, evals=0)
+        for masked in (False, True):
+            rows = []
+            for b in range(c.b):
+                st = {}
+                rows.append(walk_restated(lk, c.seeds, c.keys[b], ef, c.valid if masked else None, stats=st))
+                if not masked:
+                    tot = {k: tot[k] + st[k] for k in tot}
+            out[masked] = (np.stack([r[0] for r in rows]), np.stack([r[1] for r in rows]))
+        c.restated[ef] = (out, tot)
+    return c.restated[ef]
+
+
+def _run(ops, c, ef, masked):
+    import torch
+
+    gi, gd = ops.graph_f32_search(c.metric, c.q_d, c.x_d, c.links_d, c.seeds_d, ef, valid_bits=c.vb if masked else None)
+    torch.cuda.synchronize()
+    return gi.cpu().numpy(), gd.cpu().numpy().view(np.uint32)
+
+
+def _assert_equals_restated(ops, c, ef):
+    want, _ = _restated(c, ef)
+    for masked in (False, True):
+        gi, gbits = _run(ops, c, ef, masked)
+        for b in range(c.b):
+            assert np.array_equal(gi[b], want[masked][0][b]), (masked, b)
+            assert np.array_equal(gbits[b], want[masked][1][b]), (masked, b)
+
+
+FULL_TABLE = [(EUCLIDEAN, 128, 32, 64), (EUCLIDEAN, 128, 32, 128), (EUCLIDEAN, 128, 32, 256), (EUCLIDEAN, 128, 64, 100),
+              (INNER_PRODUCT, 64, 32, 200), (COSINE, 64, 32, 64)]
+
+
+@pytest.mark.parametrize('hash_bits', [4, 6])
+@pytest.mark.parametrize('metric,D,L,ef', FULL_TABLE)
+def test_a_full_visited_table_changes_nothing_but_the_rows_evaluated(ops, monkeypatch, metric, D, L, ef, hash_bits):
+    """ANNLITE_GRAPH_HASH_BITS = 4 / 6: 16 / 64 visited entries against lists of 64 .. 256 -- Beam::visit gives up from the seeds
+    on (16 probes: four times round the four buckets of the 16-entry table), every neighbour is reported as new and evaluated again,
+    and the merge's ``tbl_full`` branch has to see the duplicate and take the careful path (E = 1, 2 and 4).  The list is the
+    restatement's and the default table's, bit for bit; the counters show that the path ran: as many expansions, more rows."""
+    c = _case(ops, metric, D, L)
+    want, tot = _restated(c, ef)
+    default = {masked: _run(ops, c, ef, masked) for masked in (False, True)}
+    monkeypatch.setenv('ANNLITE_GRAPH_HASH_BITS', str(hash_bits))
+    for masked in (False, True):
+        gi, gbits = _run(ops, c, ef, masked)
+        for b in range(c.b):
+            assert np.array_equal(gi[b], want[masked][0][b]), (masked, b)
+            assert np.array_equal(gbits[b], want[masked][1][b]), (masked, b)
+            real = gi[b][gi[b] >= 0]
+            assert np.unique(real).size == real.size  # no node twice in a list
+        assert np.array_equal(gi, default[masked][0]) and np.array_equal(gbits, default[masked][1]), masked
+    monkeypatch.setenv('ANNLITE_DEBUG_COUNTERS', '1')
+    _run(ops, c, ef, False)
+    small = ops.graph_f32_search_stats()
+    monkeypatch.delenv('ANNLITE_GRAPH_HASH_BITS')
+    _run(ops, c, ef, False)
+    large = ops.graph_f32_search_stats()
+    print(f'hash_bits={hash_bits} (expansions, rows): small table {small}, default table {large}, restated {tot}')
+    assert small[0] == large[0] == tot['expansions']
+    assert large[1] == tot['evals']  # (the default table held every node: each row once)
+    assert small[1] > large[1]
+
+
+def _extreme(ops, metric, D, L, ef, **kw):
+    _assert_equals_restated(ops, _case(ops, metric, D, L, **kw), ef)
+
+
+@pytest.mark.parametrize('D,L,ef', [(1, 8, 16), (16, 8, 1), (16, 1, 10)])
+def test_float_walk_at_one_dimension_one_entry_one_link(ops, D, L, ef):
+    _extreme(ops, EUCLIDEAN, D, L, ef)
+
+
+@pytest.mark.parametrize('metric', [EUCLIDEAN, INNER_PRODUCT])
+@pytest.mark.parametrize('ef', [64, 256])
+def test_float_walk_at_2048_dimensions(ops, metric, ef):
+    """8 KB of query per wave: workgroups of three waves (192 threads), ten queries leave the last one wave."""
+    _extreme(ops, metric, 2048, 16, ef, n=600)
+
+
+@pytest.mark.parametrize('b', [1, 5])
+def test_float_walk_with_few_queries(ops, b):
+    _extreme(ops, EUCLIDEAN, 128, 32, 128, b=b)
+
+
+@pytest.mark.parametrize('seeds', ['1', '64', '65', 'beyond'])
+def test_float_walk_seed_sets(ops, seeds):
+    """One seed, exactly one round, one round and one id, and a set in which every fifth id is not a row (skipped)."""
+    c = _case(ops, EUCLIDEAN, 128, 32, seeds=seeds)
+    if seeds == 'beyond':
+        assert (c.seeds.astype(np.int64) >= c.n).sum() == N_SEEDS // 5
+    _assert_equals_restated(ops, c, 128)
+    gi, _ = _run(ops, c, 128, False)
+    assert (gi >= 0).sum(1).min() > 64  # (the walk went somewhere: more entries than one round of seeds)
+
+
+def test_float_walk_over_one_row(ops):
+    """N = 1: one node without links, seeds [0]: one real entry, then (-1, +inf)."""
+    import torch
+
+    x = np.array([[1.0, 2.0, 3.0]], np.float32)
+    q = np.array([[1.0, 2.0, 3.0], [0.0, 0.0, 1.0]], np.float32)
+    links = np.zeros((1, 9), np.int32)
+    links[0, 1:] = 0  # (slots beyond the count: never read as neighbours)
+    seeds = np.zeros(1, np.int32)
+    gi, gd = ops.graph_f32_search(EUCLIDEAN, ops.to_dev(q), ops.to_dev(x), ops.to_dev(links), ops.to_dev(seeds), 10)
+    torch.cuda.synchronize()
+    gi, gd = gi.cpu().numpy(), gd.cpu().numpy()
+    assert np.array_equal(gi, np.array([[0] + [-1] * 9] * 2))
+    assert np.array_equal(gd, np.array([[0.0] + [np.inf] * 9, [9.0] + [np.inf] * 9], np.float32))
+    keys = f32_key(np.array([[0.0], [9.0]], np.float32))
+    for b in range(2):
+        ri, rbits = walk_restated(links.view(np.uint32), seeds, keys[b], 10)
+        assert np.array_equal(gi[b], ri) and np.array_equal(gd[b].view(np.uint32), rbits)
+
+
+@pytest.mark.parametrize('metric', [EUCLIDEAN, INNER_PRODUCT, COSINE])
+@pytest.mark.parametrize('D', [1, 768, 2048])
+def test_float_walk_distances_against_float64(ops, metric, D):
+    """Every finite (id, distance) the walk returns lies within the fp32 summation bound of the float64 distance of that row
+    (``_refs.fp32_chain_bound``: the chain of annlite_exact_gather_dist, which the tests above take as the oracle); a stored row
+    asked for itself is found at exactly 0.0 (EUCLIDEAN)."""
+    c = _case(ops, metric, D, 16, n=600 if D == 2048 else N)
+    ef = 64
+    _assert_equals_restated(ops, c, ef)
+    gi, gbits = _run(ops, c, ef, False)
+    gd = gbits.view(np.float32)
+    checked = 0
+    for b in range(c.b):
+        ok = (gi[b] >= 0) & np.isfinite(gd[b])
+        ids = gi[b][ok]
+        x64, q64 = c.x[ids].astype(np.float64), c.q[b].astype(np.float64)
+        terms = (x64 - q64) ** 2 if metric == EUCLIDEAN else x64 * q64
+        d64 = terms.sum(1) if metric == EUCLIDEAN else 1.0 - terms.sum(1)
+        tol = fp32_chain_bound(terms, d64, D)
+        err = np.abs(gd[b][ok].astype(np.float64) - d64)
+        assert (err <= tol).all(), (b, float((err / np.maximum(tol, 1e-300)).max()))
+        checked += ids.size
+    assert checked >= (c.b - 2) * ef  # (all but the NaN and the inf query returned finite distances)
+    if metric == EUCLIDEAN:
+        assert gi[c.self_q, 0] == c.self_row and gbits[c.self_q, 0] == 0  # +0.0

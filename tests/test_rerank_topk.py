@@ -4,7 +4,7 @@ annlite_exact_gather_dist -> masking -> annlite_topk_rows -> gather of the ids -
 import numpy as np
 import pytest
 
-from _refs import bitmap as _bitmap
+from _refs import bitmap as _bitmap, fp32_chain_bound
 from conftest import has_gpu
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not has_gpu(), reason='needs a GPU')]
@@ -82,8 +82,7 @@ def test_fused_rerank_returns_the_float64_nearest(ops, metric):
     candidates whose float64 distances lie within the fp32 summation bound of each other, and every distance lies within that
     bound of float64.  Bound per (query, candidate), terms t_j = (x_j - q_j)^2 (EUCLIDEAN) or x_j q_j: the kernel sums
     ceil(D / 64) terms per lane with fma, then a 6-level butterfly, so |error| <= (2 D + 4) u sum|t_j| + u |d| (u = 2^-24; the
-    2 D covers the chains and the rounding of x_j - q_j, the last term 1 - s)."""
-    u = 2.0 ** -24
+    2 D covers the chains and the rounding of x_j - q_j, the last term 1 - s): ``_refs.fp32_chain_bound``."""
     for D, R, k in _pairs_rerank():
         rs = np.random.RandomState(1000 * metric + 10 * D + R)
         N, B = 3000, 6
@@ -104,7 +103,7 @@ def test_fused_rerank_returns_the_float64_nearest(ops, metric):
             x64, q64 = x[ids].astype(np.float64), q[b].astype(np.float64)
             terms = (x64 - q64) ** 2 if metric == 1 else x64 * q64
             d64 = terms.sum(1) if metric == 1 else 1.0 - terms.sum(1)
-            tol = (2 * D + 4) * u * np.abs(terms).sum(1) + u * np.abs(d64)
+            tol = fp32_chain_bound(terms, d64, D)
             kk = min(k, ids.size)
             order = np.argsort(d64, kind='stable')
             pos = {int(r): j for j, r in enumerate(ids)}
@@ -129,7 +128,6 @@ def test_fused_rerank_padding_zero_distances_duplicates_and_non_finite_vectors(o
     fp32 summation bound of the test above.  Their VALUES and order: annlite_exact_gather_dist's bits (the five-launch
     path), selected here in numpy -- NaN last (behind the +inf of a -1 entry too), ties by position, a +inf distance is reported as
     (+inf, -1)."""
-    u = 2.0 ** -24
     rs = np.random.RandomState(10 * D + metric)
     N, B, R = 60, 7, 70
     x = rs.randn(N, D).astype(np.float32)
@@ -180,7 +178,7 @@ def test_fused_rerank_padding_zero_distances_duplicates_and_non_finite_vectors(o
                     x64, q64 = x[c2[b][pos]].astype(np.float64), q[b].astype(np.float64)
                     terms = (x64 - q64) ** 2 if metric == 1 else x64 * q64
                     d64 = terms.sum(1) if metric == 1 else 1.0 - terms.sum(1)
-                    tol = (2 * D + 4) * u * np.abs(terms).sum(1) + u * np.abs(d64)
+                    tol = fp32_chain_bound(terms, d64, D)
                 # numbers below +inf first; then everything at +inf -- such candidates and every -1 / deleted position alike,
                 # reported as (+inf, -1) --; NaN distances behind those (numpy's order)
                 n_nan = int(np.isnan(d64).sum())

@@ -278,6 +278,44 @@ def test_early_merger_and_its_give_up_path(ops, oracle, monkeypatch, patience, M
 
 
 # ------------------------------------------------------------------------------------ the search in two halves with a seed exchange
+def test_split_prepare_writes_the_seed_keys_of_its_queries_only(ops):
+    """``seed_keys_dev`` is the caller's u64 [B][SEED_KEYS]; the preparation launch works on groups of 16 queries.  B = 70: the
+    last group holds ten queries that do not exist -- their rows of the key array are not the caller's (here: rows of a larger
+    buffer, which must keep what they held).  The kernel used to reset them: 1280 bytes written behind the array."""
+    import torch
+    from annlite_amd import _capi
+    from annlite_amd._capi import LUT_L2, PHASE_PREPARE, SEED_KEYS
+
+    rs = np.random.RandomState(5)  # (the table of the test below: structured data, on which the state settles on the byte-table kernel)
+    N, M, dsub, Ks, B, k = 600_000, 16, 8, 256, 70, 10
+    D = M * dsub
+    A = rs.randn(8, D).astype(np.float32)
+    cb_d = ops.to_dev(rs.randn(M, Ks, dsub).astype(np.float32))
+    codes_d = torch.empty((N, M), dtype=torch.uint8, device='cuda')
+    for c0 in range(0, N, 100_000):
+        x = (rs.randn(100_000, 8).astype(np.float32) @ A + 0.05 * rs.randn(100_000, D).astype(np.float32)).astype(np.float32)
+        codes_d[c0:c0 + 100_000] = ops.pq_encode(ops.to_dev(x), cb_d)
+    q_d = ops.to_dev((rs.randn(B, 8).astype(np.float32) @ A + 0.05 * rs.randn(B, D).astype(np.float32)).astype(np.float32))
+    cd = ops.codes_skew(codes_d)
+    ws, state = ops.ScanWorkspace(), _capi.ScanState()
+    mark = 0x0123456789abcdef
+    buf = torch.full((B + 32, SEED_KEYS), mark, dtype=torch.int64, device='cuda')
+    keys = None
+    for _ in range(12):  # (a few plain calls settle the kernel choice, as below)
+        ops.pq_search_topk(LUT_L2, q_d, cb_d, cd, k, M, Ks, codes_layout=1, workspace=ws, state=state)
+        torch.cuda.synchronize()
+        keys = ops.pq_search_split(PHASE_PREPARE, LUT_L2, q_d, cb_d, cd, k, M, Ks, state, ws, codes_layout=1, seed_rows=4096,
+                                   seed_keys=buf[:B])
+        if keys is not None:
+            break
+    assert keys is not None, 'the state never settled on the byte-table kernel'
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy()
+    assert (got[B:] == mark).all()
+    kh = got[:B].view(np.uint64)
+    assert (kh[:, :k] != np.uint64(2 ** 64 - 1)).all() and (kh[:, k:] == np.uint64(2 ** 64 - 1)).all()
+
+
 def test_split_search_with_seed_union_equals_the_plain_search(ops, oracle):
     """annlite_pq_search_split (PREPARE -> annlite_pq_search_seed_union -> SCAN): a rank that seeds from few rows and tightens
     its bound with the union of "peer" key sets (here: the seeds of other row ranges of the same table -- valid bounds for it)
