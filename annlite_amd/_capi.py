@@ -111,6 +111,9 @@ SYMBOLS = (
     'annlite_ivf_flat_stages',
     'annlite_ivf_flat_search_workspace_bytes',
     'annlite_ivf_flat_search_topk',
+    'annlite_affine_rows',
+    'annlite_pca_accumulate_workspace_bytes',
+    'annlite_pca_accumulate',
 )
 
 
@@ -236,6 +239,9 @@ def lib() -> ctypes.CDLL:
     L.annlite_ivf_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_ivf_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, vp,
                                                vp, sz, vp]
+    L.annlite_affine_rows.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, vp, i64, vp]
+    L.annlite_pca_accumulate_workspace_bytes.argtypes = [i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_pca_accumulate.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]
     L.annlite_graph_search_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_graph_search_stats_ex.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     for name in SYMBOLS:

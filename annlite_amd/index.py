@@ -24,7 +24,15 @@ a search that scans each query's ``n_probe`` nearest cells and answers those row
 visits every cell, so results equal the single-cell index; ``ivf_prune=True`` (kwarg) makes the search honour
 ``n_probe`` -- the pruned scan of SURVEY.md section 8f's follow-on.
 
-Out of scope of this tier: PCA projection (``n_components``), RocksDB/SQLite
+``n_components=K, projector='gpu'`` (index.py:111-123): a ``ProjectorCodec`` in front of every index above -- a
+PCA fitted on the GPU (covariance accumulated exactly, eigen-decomposition on the host: the subspace sklearn's PCA finds, by another
+route -- hence the explicit opt-in; ``n_components`` alone still raises).  ``index`` / ``update`` / ``search`` upload the rows once and project
+them on the device; the index and the PQ codec have dimension K; stored documents keep their original embeddings.
+Changed on purpose: ``train`` fits the projector first and trains the VQ / PQ codecs on the PROJECTED training rows (the reference hands
+them the raw ``x``, index.py:212-228, which cannot train a PQ codec of dimension K); ``partial_train`` shows the other codecs each batch
+through the projector's state after that batch -- a caller who wants them trained against one fixed projection trains the projector first.
+
+Out of scope of this tier: RocksDB/SQLite
 persistence of documents, remote backup.  Documents and tags live in memory; the Mongo-style ``filter`` dict is
 evaluated on the host and handed to the GPU scan as a row bitmap (section 8f-3).
 """
@@ -69,6 +77,9 @@ class AnnLite:
         keeps the float vectors themselves and searches them exactly (``FlatGpuIndex``; ``n_cells > 1`` needs ``ivf_prune=True``:
         ``IvfFlatGpuIndex``) or, with ``graph=True, build='gpu'``, through a level-0 HNSW graph over them (``HnswFlatGpuIndex``)
     :param n_clusters: codewords per sub-quantiser (default 256)
+    :param n_components: with ``projector='gpu'`` (kwarg): project the vectors to this many PCA components on the GPU in front of
+        whichever index the other arguments select (``ProjectorCodec``; trained by ``train`` / ``partial_train``); ``n_components``
+        without ``projector='gpu'`` raises ``NotImplementedError`` (the fit is not sklearn's: an explicit opt-in)
     :param rerank: keep the float vectors in HBM and re-score ADC candidates exactly (kwarg, rides
         the reference's ``**kwargs`` channel to the index, container.py:56).  With ``n_cells > 1`` and ``ivf_prune=True`` the same channel
         takes ``rerank_bound_rank`` / ``rerank_split`` (the candidate pool of the pruned search's re-rank: ``IvfPQGpuIndex``)
@@ -97,11 +108,21 @@ class AnnLite:
         if 'dim' in kwargs:
             warnings.warn('The argument `dim` will be deprecated, please use `n_dim` instead.')
             n_dim = kwargs.pop('dim')
-        if n_subvectors:
+        projector = kwargs.pop('projector', None)
+        if projector is not None and projector != 'gpu':
+            raise NotImplementedError(f"projector={projector!r}: the PCA projector exists on the GPU only, pass projector='gpu'")
+        use_projector = bool(n_components) and projector == 'gpu'
+        if n_subvectors and use_projector:  # index.py:143-146: the PQ codec sees the projected vectors
+            assert n_components % n_subvectors == 0, '"n_components" needs to be divisible by "n_subvectors"'
+        elif n_subvectors:
             assert n_dim % n_subvectors == 0, '"n_dim" needs to be divisible by "n_subvectors"'
         assert n_cells >= 1
-        if n_components:
-            raise NotImplementedError('n_components (PCA projector) is outside the accelerated hot path (SURVEY.md section 2 row 15)')
+        if n_components and not use_projector:
+            # the reference fits sklearn's PCA / IncrementalPCA; the projector here is an eigen-decomposition of an exactly accumulated
+            # covariance (the same subspace by another route) and is therefore opted into by name
+            raise NotImplementedError("n_components (PCA projector) is served by the GPU projector only: pass projector='gpu' "
+                                      "(a fit by covariance eigen-decomposition, not sklearn's SVD / IncrementalPCA)")
+        assert not (projector and not n_components), "projector='gpu' needs n_components"
         if not n_subvectors:
             # the reference's default configuration: an un-quantised float index (FlatGpuIndex: exact search)
             if n_cells > 1 and not kwargs.get('ivf_prune'):
@@ -139,6 +160,17 @@ class AnnLite:
             data_path.mkdir(parents=True, exist_ok=True)
         self.data_path = data_path
 
+        self._projector_codec = None
+        if use_projector:  # index.py:111-123
+            from .core.codec.projector import ProjectorCodec
+
+            if self._projector_codec_path.exists():
+                logger.info(f'Load pre-trained projector codec (n_components={self.n_components}) from {self.model_path}')
+                self._projector_codec = ProjectorCodec.load(self._projector_codec_path)
+            else:
+                self._projector_codec = ProjectorCodec(n_dim, n_components=n_components)
+        self._index_dim = n_components if use_projector else n_dim  # what the indexes and the PQ codec see
+
         self._pq_codec = None
         if not n_subvectors:
             pass  # (no codec: nothing to train)
@@ -146,7 +178,7 @@ class AnnLite:
             logger.info(f'Load trained PQ codec (n_subvectors={self.n_subvectors}) from {self.model_path}')
             self._pq_codec = PQCodec.load(self._pq_codec_path)
         else:
-            self._pq_codec = PQCodec(dim=n_dim, n_subvectors=n_subvectors, n_clusters=n_clusters, metric=metric)
+            self._pq_codec = PQCodec(dim=self._index_dim, n_subvectors=n_subvectors, n_clusters=n_clusters, metric=metric)
 
         self._vq_codec = None
         if n_cells > 1:  # index.py:125-133
@@ -190,31 +222,31 @@ class AnnLite:
             if graph:  # (build='gpu', n_cells == 1: the constructor refuses the rest)
                 from .core.index.hnsw_flat_gpu import HnswFlatGpuIndex
 
-                return HnswFlatGpuIndex(dim=self.n_dim, metric=self.metric, **kw)
+                return HnswFlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
             kw.pop('build', None)
             if self._vq_codec is not None:  # (ivf_prune=True: the constructor refuses cells over floats without it)
                 from .core.index.ivf_flat_gpu import IvfFlatGpuIndex
 
-                return IvfFlatGpuIndex(dim=self.n_dim, metric=self.metric, vq_codec=self._vq_codec, n_probe=self._n_probe_arg, **kw)
-            return FlatGpuIndex(dim=self.n_dim, metric=self.metric, **kw)
+                return IvfFlatGpuIndex(dim=self._index_dim, metric=self.metric, vq_codec=self._vq_codec, n_probe=self._n_probe_arg, **kw)
+            return FlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')
         if self._vq_codec is not None:
             from .core.index.ivf_pq_gpu import IvfPQGpuIndex
 
             assert not kw.pop('graph', False), 'graph=True and n_cells > 1 cannot be combined'
-            return IvfPQGpuIndex(dim=self.n_dim, metric=self.metric, pq_codec=self._pq_codec, vq_codec=self._vq_codec,
+            return IvfPQGpuIndex(dim=self._index_dim, metric=self.metric, pq_codec=self._pq_codec, vq_codec=self._vq_codec,
                                  n_probe=self._n_probe_arg if self._ivf_prune else None, **kw)
         if kw.pop('graph', False):
             from .core.index.hnsw_pq_gpu import HnswPQGpuIndex
 
-            return HnswPQGpuIndex(dim=self.n_dim, metric=self.metric, pq_codec=self._pq_codec, **kw)
+            return HnswPQGpuIndex(dim=self._index_dim, metric=self.metric, pq_codec=self._pq_codec, **kw)
         if self._devices is not None and len(self._devices) > 1:
             from .core.index.multi_gpu import MultiGpuPQIndex
 
-            return MultiGpuPQIndex(dim=self.n_dim, metric=self.metric, pq_codec=self._pq_codec, devices=self._devices,
+            return MultiGpuPQIndex(dim=self._index_dim, metric=self.metric, pq_codec=self._pq_codec, devices=self._devices,
                                    block=self._shard_block, **kw)
-        return PQFlatGpuIndex(dim=self.n_dim, metric=self.metric, pq_codec=self._pq_codec, **kw)
+        return PQFlatGpuIndex(dim=self._index_dim, metric=self.metric, pq_codec=self._pq_codec, **kw)
 
     # ------------------------------------------------------------------ bookkeeping (index.py:574-599, 952-963)
     @property
@@ -236,7 +268,13 @@ class AnnLite:
         return self.model_path / 'vq_codec.params'  # index.py:589-591
 
     @property
+    def _projector_codec_path(self):
+        return self.model_path / 'projector_codec.params'  # index.py:597-599
+
+    @property
     def is_trained(self) -> bool:
+        if self._projector_codec is not None and not self._projector_codec.is_trained:  # index.py:927
+            return False
         if self._vq_codec is not None and not self._vq_codec.is_trained:  # index.py:929-930
             return False
         if not self.n_subvectors:  # the float index has nothing to train (index.py:925-932: no codec -> trained)
@@ -262,6 +300,13 @@ class AnnLite:
     def vec_index(self, cell_id: int = 0) -> PQFlatGpuIndex:
         return self._vec_indexes[cell_id]
 
+    def _project(self, x):
+        """container.py:210, 245, 271: what the vector index is given.  With a projector the rows go up once and are projected there
+        (``annlite_affine_rows``); the index receives the device tensor.  Stored documents keep their original embeddings."""
+        if self._projector_codec is None:
+            return x
+        return self._projector_codec.encode(ops.to_dev(x, torch.float32))
+
     def _sanity_check(self, x):
         assert x.ndim == 2, 'inputs must be a 2D array'
         assert x.shape[1] == self.n_dim, (
@@ -275,12 +320,17 @@ class AnnLite:
             logger.warning('The indexer has been trained or is not trainable. Please use ``force_train=True`` to retrain.')
             return
         x = x if isinstance(x, torch.Tensor) else np.ascontiguousarray(x, dtype=np.float32)
+        if self._projector_codec is not None:  # index.py:212-216
+            logger.info(f'Start training Projector codec (n_components={self.n_components}) with {x.shape[0]} data...')
+            x = ops.to_dev(x, torch.float32)
+            self._projector_codec.fit(x)
+            x = self._projector_codec.encode(x)  # (changed on purpose: the other codecs are trained on what they will be given)
         if self._vq_codec is not None:  # index.py:218-222
             logger.info(f'Start training VQ codec (K={self.n_cells}) with {x.shape[0]} data...')
             self._vq_codec.fit(x)
         if self._pq_codec is not None:  # (the float index has no PQ codec: with cells only the VQ codec is trained)
             self._pq_codec.fit(x)
-        if auto_save and (self._pq_codec is not None or self._vq_codec is not None):
+        if auto_save and (self._pq_codec is not None or self._vq_codec is not None or self._projector_codec is not None):
             self.dump_model()
 
     def partial_train(self, x, auto_save: bool = True, force_train: bool = False):
@@ -288,17 +338,25 @@ class AnnLite:
         if self.is_trained and not force_train:
             logger.warning('The annlite has been trained or is not trainable. Please use ``force_train=True`` to retrain.')
             return
+        if self._projector_codec is not None:  # index.py:253-257
+            # the other codecs see this batch through the projector's state after it: a caller who wants them trained against ONE
+            # projection trains the projector first (all batches, or `train`), then the rest
+            x = ops.to_dev(x, torch.float32)
+            self._projector_codec.partial_fit(x)
+            x = self._projector_codec.encode(x)
         if self._vq_codec is not None:  # index.py:259-263
             self._vq_codec.partial_fit(x)
             self._vq_codec.build_codebook()
         if self._pq_codec is not None:
             self._pq_codec.partial_fit(x)
             self._pq_codec.build_codebook()
-        if auto_save and (self._pq_codec is not None or self._vq_codec is not None):
+        if auto_save and (self._pq_codec is not None or self._vq_codec is not None or self._projector_codec is not None):
             self.dump_model()
 
     def dump_model(self):
         self.model_path.mkdir(parents=True, exist_ok=True)
+        if self._projector_codec is not None:
+            self._projector_codec.dump(self._projector_codec_path)  # index.py:682-683
         if self._pq_codec is not None:
             self._pq_codec.dump(self._pq_codec_path)
         if self._vq_codec is not None:
@@ -396,7 +454,7 @@ class AnnLite:
         first = len(self._offset2id)
         offsets = np.arange(first, first + len(docs), dtype=np.int64)
         # vectors first: if the device call fails no offset exists without codes
-        self.vec_index(0).add_with_ids(np.ascontiguousarray(x, dtype=np.float32), offsets)
+        self.vec_index(0).add_with_ids(self._project(np.ascontiguousarray(x, dtype=np.float32)), offsets)
         self._offset2int = None
         for d in docs:
             self._id2offset[d.id] = len(self._offset2id)
@@ -475,7 +533,9 @@ class AnnLite:
         if k <= 0:
             B = query_np.shape[0]
             return np.full((B, 0), np.inf, np.float32), np.full((B, 0), -1, np.int64)
-        d, i = self.vec_index(0).search_batch(np.ascontiguousarray(query_np, dtype=np.float32), limit=k, indices=indices)
+        d, i = self.vec_index(0).search_batch(self._project(np.ascontiguousarray(query_np, dtype=np.float32)), limit=k, indices=indices)
+        if isinstance(d, torch.Tensor):  # (projected queries are device tensors, and so is their answer)
+            d, i = d.cpu().numpy(), i.cpu().numpy()
         return d, i
 
     def search(self, docs, filter: Optional[dict] = None, limit: int = 10, include_metadata: bool = True, **kwargs):
@@ -607,6 +667,8 @@ class AnnLite:
         self._sanity_check(x)
         if self._pq_codec is None:
             raise RuntimeError('this index holds un-quantised float vectors: there is no PQ codec to encode with')
+        if self._projector_codec is not None:  # index.py:554
+            x = self._projector_codec.encode(x)
         return self._pq_codec.encode(x)
 
     def decode(self, x):
@@ -614,4 +676,7 @@ class AnnLite:
         if self._pq_codec is None:
             raise RuntimeError('this index holds un-quantised float vectors: there is no PQ codec to decode with')
         assert x.shape[1] == self.n_subvectors
-        return self._pq_codec.decode(x)
+        x = self._pq_codec.decode(x)
+        if self._projector_codec is not None:  # index.py:569
+            x = self._projector_codec.decode(x)
+        return x

@@ -835,3 +835,50 @@ def ivf_flat_search_topk(metric: int, queries: torch.Tensor, vectors: torch.Tens
                                              cell_order.data_ptr(), int(max_cell_rows), int(max_probed_rows), int(k), 1 if sqrt else 0,
                                              od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), 'ivf_flat_search_topk')
     return od, oi
+
+
+# ---------------------------------------------------------------------------------------------- PCA projector
+def _row_stride(t: torch.Tensor, what: str) -> int:
+    assert t.dim() == 2 and t.dtype == torch.float32, f'{what} must be a 2-D float32 tensor'
+    assert t.shape[1] == 1 or t.stride(1) == 1, f'{what}: the rows must be contiguous'
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    assert ld >= t.shape[1], f'{what}: overlapping rows'
+    return int(ld)
+
+
+def affine_rows(x: torch.Tensor, M: torch.Tensor, sub: Optional[torch.Tensor] = None, add: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``annlite_affine_rows``: ``out[r] = (x[r] - sub) @ M.T + add`` on f32 MFMA -- ``x`` f32 [n, Din] and ``out`` f32 [n, Dout] may be
+    row-strided views (contiguous rows), ``M`` f32 [Dout, Din] contiguous, ``sub`` [Din] / ``add`` [Dout] optional."""
+    n, Din = x.shape
+    Dout, Dm = M.shape
+    assert Dm == Din, 'M must be [Dout, Din]'
+    assert M.is_contiguous() and M.dtype == torch.float32
+    assert sub is None or (sub.numel() == Din and sub.is_contiguous() and sub.dtype == torch.float32)
+    assert add is None or (add.numel() == Dout and add.is_contiguous() and add.dtype == torch.float32)
+    if out is None:
+        out = torch.empty((n, Dout), dtype=torch.float32, device=x.device)
+    assert out.shape == (n, Dout)
+    check(lib().annlite_affine_rows(x.data_ptr(), n, Din, _row_stride(x, 'x'), M.data_ptr(), Dout, _ptr(sub), _ptr(add), out.data_ptr(),
+                                    _row_stride(out, 'out'), stream_ptr()), 'affine_rows')
+    return out
+
+
+def pca_accumulate(x: torch.Tensor, shift: torch.Tensor, sum64: torch.Tensor, gram64: torch.Tensor,
+                   workspace: Optional[ScanWorkspace] = None) -> None:
+    """``annlite_pca_accumulate``: ``sum64 (f64 [D]) += sum (x - shift)`` and ``gram64 (f64 [D, D]) += sum (x - shift)(x - shift)^T`` over
+    the rows of ``x`` f32 [n, D], in place; chunked f32 MFMA products folded in f64 in a fixed order (the same bits on every run)."""
+    n, D = x.shape
+    assert shift.numel() == D and shift.dtype == torch.float32 and shift.is_contiguous()
+    assert sum64.dtype == torch.float64 and sum64.numel() == D and sum64.is_contiguous()
+    assert gram64.dtype == torch.float64 and gram64.shape == (D, D) and gram64.is_contiguous()
+    need = ctypes.c_int64(0)
+    check(lib().annlite_pca_accumulate_workspace_bytes(n, D, ctypes.byref(need)), 'pca_accumulate_workspace_bytes')
+    ws = (workspace or ScanWorkspace()).get(int(need.value), x.device)
+    check(lib().annlite_pca_accumulate(x.data_ptr(), n, D, _row_stride(x, 'x'), shift.data_ptr(), sum64.data_ptr(), gram64.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), stream_ptr()), 'pca_accumulate')
+
+
+def pca_chunk_rows() -> int:
+    """Rows of one partial product of ``pca_accumulate`` (a compile-time constant of the library)."""
+    return 512

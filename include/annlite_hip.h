@@ -676,6 +676,30 @@ ANNLITE_API int annlite_ivf_merge_lists(const uint64_t *lists_dev, int64_t k, co
                             const int64_t *row_ids_dev, int64_t id_base, float *out_dist_dev, int64_t *out_id_dev, int flags,
                             void *stream);
 
+/* The PCA projector.
+ * out[r][o] = sum_k (x[r][k] - sub[k]) M[o][k] + add[o] on f32 MFMA: x_dev f32 [n][Din] with row stride ldx (floats), M_dev f32
+ * [Dout][Din] contiguous, sub_dev f32 [Din] and add_dev f32 [Dout] (either may be NULL), out_dev f32 [n][Dout] with row stride ldo;
+ * columns of out beyond Dout are not written.  `sub` is subtracted from every element BEFORE the products (one rounding), so a
+ * common offset of the rows does not cancel inside the sums.  Every output element is one fma chain over k ascending: the result
+ * is the same bits on every run.  n == 0 returns without a launch.
+ * replaces: ProjectorCodec.encode / decode = sklearn PCA.transform / inverse_transform (annlite/core/codec/projector.py:109-130):
+ * encode with M = components (scaled by 1 / sqrt(explained variance) with whiten), sub = mean; decode with M = the transpose
+ * ([D][K] contiguous, scaled by sqrt(explained variance) with whiten), add = mean. */
+ANNLITE_API int annlite_affine_rows(const float *x_dev, int64_t n, int64_t Din, int64_t ldx, const float *M_dev, int64_t Dout,
+                        const float *sub_dev, const float *add_dev, float *out_dev, int64_t ldo, void *stream);
+
+/* The data pass of a PCA fit: sum_dev f64 [D] += sum_r (x[r] - shift), gram_dev f64 [D][D] += sum_r (x[r] - shift)(x[r] - shift)^T
+ * over the n rows of x_dev (f32, row stride ldx); shift_dev f32 [D] is the caller's guess of the mean (any vector is correct, one
+ * near the mean keeps the f32 products small).  The rows are cut into chunks of 512 (a constant); per chunk and 128 x 128 tile with
+ * tj >= ti the products run as f32 MFMA fma chains over the chunk's rows in order, and a second kernel adds the chunks' partials to
+ * the f64 accumulators in chunk order, mirroring the tiles below the diagonal: no atomics, the same bits on every run and every
+ * device, gram exactly symmetric (if it was on entry).  1 <= D <= 2048.  Workspace: annlite_pca_accumulate_workspace_bytes.
+ * replaces: the data pass of ProjectorCodec.fit / partial_fit = sklearn PCA.fit / IncrementalPCA.partial_fit
+ * (annlite/core/codec/projector.py:60-107); the eigen-decomposition of the D x D matrix stays on the host. */
+ANNLITE_API int annlite_pca_accumulate_workspace_bytes(int64_t n, int64_t D, int64_t *bytes);
+ANNLITE_API int annlite_pca_accumulate(const float *x_dev, int64_t n, int64_t D, int64_t ldx, const float *shift_dev, double *sum_dev,
+                           double *gram_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
