@@ -55,6 +55,7 @@ SYMBOLS = (
     'annlite_graph_build_reverse',
     'annlite_graph_pack_nodes',
     'annlite_graph_f32_search',
+    'annlite_graph_f32_search_admit',
     'annlite_graph_f32_search_stats',
     'annlite_graph_f32_build_select',
     'annlite_graph_f32_build_reverse',
@@ -172,6 +173,7 @@ def lib() -> ctypes.CDLL:
     L.annlite_graph_pack_nodes.argtypes = [vp, i32, vp, i64, i64, vp, i64, vp, vp]
     L.annlite_graph_record_bytes.argtypes = [i32, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_graph_f32_search.argtypes = [i32, vp, i64, i64, vp, i64, vp, i32, vp, i64, vp, i32, vp, vp, vp]
+    L.annlite_graph_f32_search_admit.argtypes = [i32, vp, i64, i64, vp, i64, vp, i32, vp, i64, vp, i32, i32, vp, vp, vp, vp]
     L.annlite_graph_f32_build_select.argtypes = [i32, vp, i32, i64, i64, vp, i64, i64, i32, vp, i32, vp, vp]
     L.annlite_graph_f32_build_reverse.argtypes = [i32, vp, vp, i64, vp, i64, i64, vp, i32, vp]
     L.annlite_graph_f32_search_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]

@@ -19,6 +19,11 @@ float32 search -- an f32 MFMA filter with a proven slack, then exact sums (DESIG
 With ``n_cells > 1`` and ``ivf_prune=True`` it is ``IvfFlatGpuIndex``: cells over the float vectors -- a ``VQCodec`` to train, and
 a search that scans each query's ``n_probe`` nearest cells and answers those rows exactly.
 
+With ``graph=True, build='gpu'`` it is ``HnswFlatGpuIndex``, a level-0 HNSW graph over the float vectors.  A
+search with a ``filter`` is answered exactly by default; ``filter_search='graph'`` answers it on the graph as hnswlib's filtered search
+does (the walk routes through every row, only rows that pass the filter are listed), except for filters that keep too few rows for the
+walk to pay (``HnswFlatGpuIndex.FILTER_WALK_MIN_FRACTION``), which stay exact.
+
 ``n_cells > 1`` (index.py:125-133, 458-483): a ``VQCodec`` coarse quantiser assigns every vector to a cell and ONE
 ``IvfPQGpuIndex`` holds all cells.  Like the reference (``n_probe = max(n_probe, n_cells)``, index.py:94) a search
 visits every cell, so results equal the single-cell index; ``ivf_prune=True`` (kwarg) makes the search honour
@@ -83,6 +88,9 @@ class AnnLite:
     :param rerank: keep the float vectors in HBM and re-score ADC candidates exactly (kwarg, rides
         the reference's ``**kwargs`` channel to the index, container.py:56).  With ``n_cells > 1`` and ``ivf_prune=True`` the same channel
         takes ``rerank_bound_rank`` / ``rerank_split`` (the candidate pool of the pruned search's re-rank: ``IvfPQGpuIndex``)
+    :param filter_search: ``'exact'`` (default) or ``'graph'`` (kwarg, same channel; the float HNSW graph only, ignored by the other
+        indexes): how a search that carries a ``filter`` is answered -- by the exact filtered search, or by the graph walk that lists
+        only the rows the filter admits (``HnswFlatGpuIndex.search_batch``)
     """
 
     def __init__(
@@ -224,11 +232,13 @@ class AnnLite:
 
                 return HnswFlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
             kw.pop('build', None)
+            kw.pop('filter_search', None)  # (the float graph's option: these indexes answer a filter exactly)
             if self._vq_codec is not None:  # (ivf_prune=True: the constructor refuses cells over floats without it)
                 from .core.index.ivf_flat_gpu import IvfFlatGpuIndex
 
                 return IvfFlatGpuIndex(dim=self._index_dim, metric=self.metric, vq_codec=self._vq_codec, n_probe=self._n_probe_arg, **kw)
             return FlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
+        kw.pop('filter_search', None)  # (the float graph's option: the indexes over PQ codes are unchanged)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')
         if self._vq_codec is not None:

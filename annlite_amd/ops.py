@@ -221,8 +221,35 @@ def graph_f32_search(metric: int, queries: torch.Tensor, vectors: torch.Tensor, 
     return out_i, out_d
 
 
+def graph_f32_search_admit(metric: int, queries: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor, seeds: torch.Tensor,
+                           ef_route: int, ef: int, admit_bits: torch.Tensor, n_rows: Optional[int] = None,
+                           route_worst: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_graph_f32_search_admit``: ``graph_f32_search`` at ``ef = ef_route`` -- same expansions, same rows evaluated -- that
+    keeps, beside the routing list, the ``ef <= ef_route`` best rows set in the bitmap ``admit_bits`` (i32 words over the rows; required)
+    among everything it evaluates.  Returns (ids i64 [B, ef] ascending by (distance, id), admitted rows only, -1 at the tail; dist f32
+    [B, ef], +inf there).  ``route_worst`` f32 [B], when given, receives the distance of the routing list's last place (+inf while that
+    list is not full): how far the walk reached."""
+    assert queries.dtype == torch.float32 and vectors.dtype == torch.float32 and queries.is_contiguous() and vectors.is_contiguous()
+    assert links.is_contiguous() and seeds.is_contiguous() and links.element_size() == 4 and seeds.element_size() == 4
+    B, D = queries.shape
+    assert vectors.shape[1] == D
+    N = vectors.shape[0] if n_rows is None else int(n_rows)
+    assert N <= vectors.shape[0] and N <= links.shape[0]
+    assert route_worst is None or (route_worst.dtype == torch.float32 and route_worst.is_contiguous() and route_worst.numel() == B
+                                   and route_worst.device == vectors.device)
+    # (None goes to the library, which refuses it)
+    assert admit_bits is None or (admit_bits.is_contiguous() and admit_bits.element_size() == 4 and admit_bits.numel() * 32 >= N)
+    out_i = torch.empty((B, ef), dtype=torch.int64, device=vectors.device)
+    out_d = torch.empty((B, ef), dtype=torch.float32, device=vectors.device)
+    check(lib().annlite_graph_f32_search_admit(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, links.data_ptr(),
+                                               links.shape[1] - 1, seeds.data_ptr(), seeds.numel(), _ptr(admit_bits), int(ef_route),
+                                               int(ef), out_i.data_ptr(), out_d.data_ptr(), _ptr(route_worst), stream_ptr()),
+          'graph_f32_search_admit')
+    return out_i, out_d
+
+
 def graph_f32_search_stats() -> Tuple[int, int]:
-    """(expansions, rows evaluated) of the last float graph walk (ANNLITE_DEBUG_COUNTERS=1)."""
+    """(expansions, rows evaluated) of the last float graph walk, with or without an admit list (ANNLITE_DEBUG_COUNTERS=1)."""
     out = (ctypes.c_uint64 * 2)()
     check(lib().annlite_graph_f32_search_stats(out), 'graph_f32_search_stats')
     return int(out[0]), int(out[1])

@@ -224,12 +224,25 @@ ANNLITE_API int annlite_graph_search_stats_ex(uint64_t *out8);
  *                                    order of annlite_graph_search; the list is ordered by (distance, node id), NaN behind +inf.
  *                                    out_ids_dev i64 [B][ef] / out_dist_dev f32 [B][ef]: ascending, rows cleared in valid_bits_dev
  *                                    (may be NULL) blanked IN PLACE to (-1, +inf) -- they still route the walk.
+ *   annlite_graph_f32_search_admit   the same walk at ef = ef_route (same expansions, same rows evaluated: admit_bits_dev never
+ *                                    touches the routing list) with a SECOND sorted list of ef <= ef_route <= 256 places that is
+ *                                    offered every batch the routing list is offered -- a seed round, an expansion's unseen
+ *                                    neighbours -- restricted to the rows set in admit_bits_dev (u32 bitmap over the N rows,
+ *                                    required; valid & filter), under the same test-against-the-worst-entry-then-merge rule.  It
+ *                                    ends as the ef smallest (distance, id) among the admitted rows the walk evaluated: out_ids_dev
+ *                                    i64 [B][ef] / out_dist_dev f32 [B][ef] ascending, missing places (-1, +inf) at the tail.
+ *                                    out_route_worst_dev f32 [B] (may be NULL): the distance of the routing list's last place, +inf
+ *                                    while that list is not full -- how far the walk reached; a result beyond it was only met on the way.
  *   annlite_graph_f32_build_select   annlite_graph_build_select; the batch's points are rows base0 .. base0 + b of vectors_dev [N][D]
  *   annlite_graph_f32_build_reverse  annlite_graph_build_reverse; a shrinking pool is ordered by (distance to the target, id)
  *   annlite_graph_f32_search_stats   debug aid (ANNLITE_DEBUG_COUNTERS=1): [0] expansions, [1] rows evaluated of the last float walk */
 ANNLITE_API int annlite_graph_f32_search(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
                          const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
                          const uint32_t *valid_bits_dev, int ef, int64_t *out_ids_dev, float *out_dist_dev, void *stream);
+ANNLITE_API int annlite_graph_f32_search_admit(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
+                         const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
+                         const uint32_t *admit_bits_dev, int ef_route, int ef, int64_t *out_ids_dev, float *out_dist_dev,
+                         float *out_route_worst_dev, void *stream);
 ANNLITE_API int annlite_graph_f32_build_select(int metric, const int64_t *cand_dev, int ef, int64_t b, int64_t base0,
                          const float *vectors_dev, int64_t N, int64_t D, int max_keep, uint32_t *links_dev, int links_per_node,
                          int64_t *pairs_dev, void *stream);
