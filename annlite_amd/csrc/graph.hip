@@ -23,8 +23,7 @@
 // still-unexpanded node is PREFETCHED into registers while the current node's neighbours are evaluated: if the next pick is
 // that node -- it is, once the walk has reached its plateau -- no round trip is exposed at all.  The order of the walk and
 // the arithmetic are unchanged: candidate lists are bit-equal to the plain kernel's (tests/test_graph_packed.py).
-#include "scan_common.h"
-#include "graph_beam.h"
+#include "graph_pq_walk.h"
 
 namespace annlite {
 
@@ -51,254 +50,22 @@ __global__ __launch_bounds__(256) void graph_beam_search_kernel(const uint32_t *
                                                                int hash_bits, int64_t *__restrict__ out_ids,
                                                                float *__restrict__ out_dist,
                                                                unsigned long long *__restrict__ stats) {
-    constexpr int CW = M / 4;
-    unsigned int n_expand = 0, n_eval = 0, n_hit = 0;  // (ANNLITE_DEBUG_COUNTERS: link lists read, rows evaluated, prefetched records used)
-    unsigned long long t_seed = 0, t_rec = 0, t_visit = 0, t_sum = 0, t_offer = 0;  // ... and shader cycles by phase (packed walk)
-    auto now = [&]() -> unsigned long long { return stats ? __builtin_readcyclecounter() : 0ull; };
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int b = blockIdx.x * (blockDim.x >> 6) + wave;  // 1..4 waves per workgroup, as many as the LDS holds
     if (b >= B) return;  // (whole waves leave; no block-wide barrier below)
-    const uint32_t hash_n = 1u << hash_bits;
-    const size_t per_wave = (size_t)M * Ks * 4 + (size_t)hash_n * 4 + (BATCH ? (size_t)E * 64 * 12 + 1024 : 0);  // (same formula as launch_beam)
-    float *s_lut = (float *)(smem + wave * per_wave);
-    uint32_t *s_hash = (uint32_t *)(smem + wave * per_wave + (size_t)M * Ks * 4);
-    uint32_t *s_mrg = s_hash + hash_n;  // BATCH: the merge's scratch, u32 [3][64 E]: keys hi, ids, expanded flags; then u32 [4][64]: the
-                                        // candidates compacted (hi, id) and by rank (hi, id)
-    {
-        const f32x4 *src = (const f32x4 *)(lut_bmk + (int64_t)b * M * Ks);
-        for (int i = lane; i < M * Ks / 4; i += 64) ((f32x4 *)s_lut)[i] = src[i];
-        for (uint32_t i = lane; i < hash_n / 4; i += 64) ((u32x4 *)s_hash)[i] = (u32x4){kEmpty, kEmpty, kEmpty, kEmpty};
-    }
-    // (one wave: its LDS writes are visible to its own later reads in program order)
-
-    // the list, its insertion and the visited table: graph_beam.h
-    // (by LDS byte address in the LDS address space: through a generic volatile pointer the bucket read was a FLAT load, and a flat
-    // load counts on the vector-memory counter too -- every probe then waited for the prefetched record)
-    typedef __attribute__((address_space(3))) unsigned char *lds_bytes;
-    const uint32_t hash_ad = (uint32_t)(uintptr_t)(lds_bytes)smem + (uint32_t)(wave * per_wave) + (uint32_t)(M * Ks * 4);
+    // the walk itself -- seeds, visited table, records, PQLookup sums, merge -- is graph_pq_walk.h's, shared with graph_admit.hip
+    PQWalkCounters ct;
     Beam<E, BATCH> bm;
-    bm.init(lane, ef, s_mrg, hash_ad, hash_bits);
+    float *s_lut;
+    pq_walk_setup<M, E, BATCH>(smem, wave, lane, lut_bmk, b, Ks, ef, hash_bits, bm, s_lut);
     BeamList<E> &L = bm.L;
     const int cap = bm.cap;
-    auto visit = [&](uint32_t node) -> bool { return bm.visit(node); };
     auto offer = [&](bool mine, uint32_t node, float d) { bm.offer(mine, node, f32_to_ordered(d)); };
-    auto pick_next = [&](uint32_t &node, uint32_t &second) -> bool { return bm.pick_next(node, second); };
-    auto load_row = [&](uint32_t node, uint32_t (&c)[CW]) {
-        const uint32_t *p = (const uint32_t *)(codes + (int64_t)node * M);
-#pragma unroll
-        for (int i = 0; i < CW; ++i) c[i] = p[i];
-    };
-    auto pq_sum = [&](const uint32_t (&c)[CW]) -> float {  // hnswlib::PQLookup: ascending-m fp32 adds
-        float d = 0.f;
-#pragma unroll
-        for (int m = 0; m < M; ++m) d += s_lut[m * Ks + ((c[m / 4] >> (8 * (m % 4))) & 0xffu)];
-        return d;
-    };
-    auto pq_lookup = [&](uint32_t node) -> float {
-        uint32_t c[CW];
-        load_row(node, c);
-        return pq_sum(c);
-    };
     auto is_valid = [&](uint32_t node) -> bool { return !valid || ((valid[node >> 5] >> (node & 31)) & 1u); };
-
-
-    // ---- seeds: the top of the hierarchy, scanned flat -------------------------------------------------
-    // (seeds are distinct: no visited check while scanning them; only the ones that made the list are recorded --
-    // recording all of them would fill the hash table before the walk starts)
-    // (the round's code rows are requested one round ahead, its seed ids two: the rounds' two dependent round trips overlap
-    // the previous rounds' insertions; the ORDER of the offers is unchanged)
-    {
-        const unsigned long long t_s0 = now();
-        auto seed_at = [&](int s0) -> uint32_t { return s0 + lane < n_seeds ? seeds[s0 + lane] : 0xffffffffu; };
-        uint32_t node_cur = seed_at(0), node_nxt = seed_at(64);
-        uint32_t c_cur[CW];
-        load_row(((int64_t)node_cur < N) ? node_cur : 0u, c_cur);
-        for (int s0 = 0; s0 < n_seeds; s0 += 64) {
-            const uint32_t node = node_cur;
-            const bool mine = s0 + lane < n_seeds && (int64_t)node < N;
-            uint32_t c[CW];
-#pragma unroll
-            for (int i = 0; i < CW; ++i) c[i] = c_cur[i];
-            node_cur = node_nxt;
-            if (s0 + 64 < n_seeds) load_row(((int64_t)node_cur < N) ? node_cur : 0u, c_cur);
-            node_nxt = seed_at(s0 + 128);
-            const float d = mine ? pq_sum(c) : 0.f;
-            n_eval += (unsigned int)__popcll(__ballot(mine));
-            offer(mine, node, d);
-        }
-        t_seed = now() - t_s0;
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-        if (L.lo[e] != kIdNone) visit(L.lo[e]);
-
-    // ---- walk ------------------------------------------------------------------------------------------
-    if constexpr (PACKED && W == 2) {
-        const int Lc = links_per_node;  // (<= 32: one HALF wave per record)
-        const int half = lane >> 5, hj = lane & 31;
-        // the record of `node` as seen by this lane's half: neighbour hj's code row and id (slots beyond the count hold 0xffffffff)
-        auto load_rec = [&](uint32_t node, uint32_t (&c)[CW], uint32_t &nb) {
-            const uint8_t *r = packed + (int64_t)node * rec_stride;
-            const int j = hj < Lc ? hj : 0;
-            const uint32_t *pc = (const uint32_t *)(r + (int64_t)j * M);
-#pragma unroll
-            for (int i = 0; i < CW; ++i) c[i] = pc[i];
-            nb = ((const uint32_t *)(r + (int64_t)Lc * M))[j];
-        };
-        // the two best unexpanded entries (marked expanded) and the two after them (the halves' prefetch targets)
-        auto pick_pair = [&](uint32_t (&nd)[4]) -> bool {
-            int p[4] = {-1, -1, -1, -1};
-            int found = 0;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                if (found < 4) {
-                    unsigned long long m = __ballot(!L.exp[e] && (e * 64 + lane) < cap);
-                    while (m && found < 4) {
-                        p[found++] = e * 64 + __builtin_ctzll(m);
-                        m &= m - 1;
-                    }
-                }
-            }
-            if (found == 0) return false;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) nd[i] = kEmpty;
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (p[i] >= 0 && p[i] / 64 == e) nd[i] = __builtin_amdgcn_readlane(L.lo[e], p[i] % 64);
-                if ((p[0] >= 0 && p[0] / 64 == e && lane == p[0] % 64) || (p[1] >= 0 && p[1] / 64 == e && lane == p[1] % 64)) L.exp[e] = true;
-            }
-            return true;
-        };
-        uint32_t pf_c[CW], pf_nb = kEmpty, pf_node = kEmpty;  // this HALF's prefetched record (pf_node == kEmpty: none)
-#pragma unroll
-        for (int i = 0; i < CW; ++i) pf_c[i] = 0;
-        for (;;) {
-            uint32_t nd[4];
-            const unsigned long long t0 = now();
-            if (!pick_pair(nd)) break;
-            // a prefetched record stays in the half that holds it: the halves swap nodes when that keeps more of them (the
-            // candidates of a step are merged as a SET -- which half evaluated a neighbour does not matter)
-            const uint32_t pf0 = __builtin_amdgcn_readlane(pf_node, 0), pf1 = __builtin_amdgcn_readlane(pf_node, 32);
-            const bool two = nd[1] != kEmpty;
-            const int keep_straight = (pf0 == nd[0] ? 1 : 0) + (two && pf1 == nd[1] ? 1 : 0);
-            const int keep_swapped = (two && pf0 == nd[1] ? 1 : 0) + (pf1 == nd[0] ? 1 : 0);
-            const bool swapped = keep_swapped > keep_straight;
-            const uint32_t node = ((half != 0) != swapped) ? nd[1] : nd[0];
-            const bool have = node != kEmpty;
-            uint32_t c[CW], nb = kEmpty;
-#pragma unroll
-            for (int i = 0; i < CW; ++i) c[i] = 0;
-            if (have && pf_node == node) {
-#pragma unroll
-                for (int i = 0; i < CW; ++i) c[i] = pf_c[i];
-                nb = pf_nb;
-            } else if (have) {
-                load_rec(node, c, nb);
-            }
-            n_hit += (unsigned int)__popcll(__ballot(have && pf_node == node && hj == 0));
-            // (the current records must have ARRIVED before the prefetches are issued: see the one-at-a-time loop below)
-            asm volatile("" : "+v"(nb));
-#pragma unroll
-            for (int i = 0; i < CW; ++i) asm volatile("" : "+v"(c[i]));
-            // half 0 requests the best node that is unexpanded NOW, half 1 the one after it: the next pair unless this step's
-            // neighbours turn out better
-            pf_node = half ? nd[3] : nd[2];
-            if (pf_node != kEmpty) load_rec(pf_node, pf_c, pf_nb);
-            n_expand += two ? 2u : 1u;
-            const unsigned long long t1 = now();
-            // (a neighbour of BOTH nodes is probed by two lanes at once: the table's compare-and-swap lets exactly one of them through)
-            bool mine = have && hj < Lc;
-            mine = mine && (int64_t)nb < N && visit(nb);
-            n_eval += (unsigned int)__popcll(__ballot(mine));
-            const unsigned long long t2 = now();
-            float d = mine ? pq_sum(c) : 0.f;
-            if (stats) asm volatile("" : "+v"(d));
-            const unsigned long long t3 = now();
-            offer(mine, nb, d);
-            if (stats) {
-                const unsigned long long t4 = now();
-                t_rec += t1 - t0, t_visit += t2 - t1, t_sum += t3 - t2, t_offer += t4 - t3;
-            }
-        }
-    } else if constexpr (PACKED) {
-        // record of a node: lane j < L holds neighbour j's code row and id; the count is a wave-uniform load
-        const int Lc = links_per_node;  // (<= 64: one lane per neighbour)
-        // (slots beyond the node's count hold the id 0xffffffff, which fails the `nb < N` test like any id beyond the table:
-        // the walk never reads the count -- a wave-uniform, i.e. SCALAR load would share its counter with the LDS traffic of
-        // visit() and stall it for a full memory round trip whenever a prefetch is in flight)
-        auto load_rec = [&](uint32_t node, uint32_t (&c)[CW], uint32_t &nb) {
-            const uint8_t *r = packed + (int64_t)node * rec_stride;
-            const int j = lane < Lc ? lane : 0;
-            const uint32_t *pc = (const uint32_t *)(r + (int64_t)j * M);
-#pragma unroll
-            for (int i = 0; i < CW; ++i) c[i] = pc[i];
-            nb = ((const uint32_t *)(r + (int64_t)Lc * M))[j];
-        };
-        uint32_t pf_c[CW], pf_nb = 0, pf_node = kEmpty;  // the prefetched record (pf_node == kEmpty: none)
-#pragma unroll
-        for (int i = 0; i < CW; ++i) pf_c[i] = 0;
-        for (;;) {
-            uint32_t node = 0, second = kEmpty;
-            const unsigned long long t0 = now();
-            if (!pick_next(node, second)) break;
-            uint32_t c[CW], nb;
-            if (pf_node == node) {
-                ++n_hit;
-#pragma unroll
-                for (int i = 0; i < CW; ++i) c[i] = pf_c[i];
-                nb = pf_nb;
-            } else {
-                load_rec(node, c, nb);
-            }
-            // The current record must have ARRIVED before the prefetch below is issued: the memory counter is in order and the
-            // compiler, merging the paths with and without a prefetch, otherwise waits for everything outstanding -- the
-            // prefetch included -- at the first use of the current record.  (An empty asm that reads the registers.)
-            asm volatile("" : "+v"(nb));
-#pragma unroll
-            for (int i = 0; i < CW; ++i) asm volatile("" : "+v"(c[i]));
-            // request the record of the best node that is unexpanded NOW: the next pick unless one of this node's neighbours
-            // turns out better
-            pf_node = second;
-            if (second != kEmpty) load_rec(second, pf_c, pf_nb);
-            ++n_expand;
-            const unsigned long long t1 = now();
-            bool mine = lane < Lc;
-            mine = mine && (int64_t)nb < N && visit(nb);
-            n_eval += (unsigned int)__popcll(__ballot(mine));
-            const unsigned long long t2 = now();
-            float d = mine ? pq_sum(c) : 0.f;
-            if (stats) asm volatile("" : "+v"(d));
-            const unsigned long long t3 = now();
-            offer(mine, nb, d);
-            if (stats) {
-                const unsigned long long t4 = now();
-                t_rec += t1 - t0, t_visit += t2 - t1, t_sum += t3 - t2, t_offer += t4 - t3;
-            }
-        }
-    } else {
-        for (;;) {
-            uint32_t node = 0, second = kEmpty;
-            if (!pick_next(node, second)) break;
-            const uint32_t *ll = links + (int64_t)node * (links_per_node + 1);
-            const uint32_t cnt = ll[0];
-            ++n_expand;
-            bool mine = false;
-            uint32_t nb = 0;
-            float d = 0.f;
-            for (uint32_t base = 0; base < cnt; base += 64) {  // (links_per_node <= 64 in practice: one round)
-                mine = base + lane < cnt;
-                nb = mine ? ll[1 + base + lane] : 0u;
-                mine = mine && (int64_t)nb < N && visit(nb);
-                n_eval += (unsigned int)__popcll(__ballot(mine));
-                d = mine ? pq_lookup(nb) : 0.f;
-                offer(mine, nb, d);
-            }
-        }
-    }
+    pq_beam_walk<M, E, PACKED, BATCH, W>(bm, s_lut, lane, links, links_per_node, packed, rec_stride, seeds, n_seeds, codes, N, Ks, stats,
+                                         offer, ct);
 
     // ---- result: the list, ascending; deleted rows dropped here (they still route the walk, like hnswlib) ---
     // compacting is left to the host-side top-k (ids of dropped rows become -1 / +inf)
@@ -311,12 +78,7 @@ __global__ __launch_bounds__(256) void graph_beam_search_kernel(const uint32_t *
             out_dist[(int64_t)b * ef + i] = none ? __builtin_inff() : ordered_to_f32(L.hi[e]);
         }
     }
-    if (stats && lane == 0) {
-        atomicAdd(stats + 0, (unsigned long long)n_expand);
-        atomicAdd(stats + 1, (unsigned long long)n_eval);
-        atomicAdd(stats + 2, (unsigned long long)n_hit);
-        atomicAdd(stats + 3, t_seed), atomicAdd(stats + 4, t_rec), atomicAdd(stats + 5, t_visit), atomicAdd(stats + 6, t_sum), atomicAdd(stats + 7, t_offer);
-    }
+    if (stats && lane == 0) pq_walk_add_stats(stats, ct);
 }
 
 }  // namespace annlite
@@ -347,15 +109,12 @@ __global__ __launch_bounds__(256) void graph_pack_kernel(const uint32_t *__restr
     }
 }
 
-static int64_t graph_record_stride(int64_t L, int64_t M) { return ((L * M + 4 * L + 4 + 15) / 16) * 16; }
-
 template <int M, int E, bool PACKED, bool BATCH, int W = 1>
 static int launch_beam(const uint32_t *links, int lpn, const uint8_t *packed, const uint32_t *seeds, int n_seeds, const uint8_t *codes,
                        int64_t N, const uint32_t *valid, const float *lut, int64_t B, int64_t Ks, int ef, int hash_bits,
                        int64_t *out_ids, float *out_dist, unsigned long long *stats, hipStream_t st) {
-    const size_t per_wave = (size_t)M * Ks * 4 + ((size_t)4 << hash_bits) + (BATCH ? (size_t)E * 64 * 12 + 1024 : 0);
-    int wpb = (int)((size_t)160 * 1024 / per_wave);
-    if (wpb > 4) wpb = 4;
+    const size_t per_wave = pq_walk_lds_per_wave<E, BATCH>(M, Ks, hash_bits);
+    const int wpb = pq_walk_waves_per_block(per_wave);
     ANNLITE_REQUIRE(wpb >= 1, "M * Ks tables do not fit the LDS");
     const size_t lds = wpb * per_wave;
     auto fn = graph_beam_search_kernel<M, E, PACKED, BATCH, W>;
@@ -379,20 +138,18 @@ extern "C" int annlite_graph_search_stats(uint64_t *out2) {
     return ANNLITE_OK;
 }
 
-static int graph_search_impl(const uint32_t *links_dev, const uint8_t *packed_dev, int links_per_node, const uint32_t *seeds_dev,
-                             int64_t n_seeds, const void *codes_dev, int64_t N, int64_t M, int64_t Ks, const uint32_t *valid_bits_dev,
-                             const float *lut_bmk_dev, int64_t B, int ef, int64_t *out_ids_dev, float *out_dist_dev, void *stream,
-                             int width = 1) {
-    ANNLITE_REQUIRE(B >= 0 && N >= 0 && ef >= 1 && ef <= 256, "bad B=%lld N=%lld ef=%d (ef <= 256)", (long long)B,
-                    (long long)N, ef);
-    ANNLITE_REQUIRE(width == 1 || (width == 2 && packed_dev && links_per_node <= 32),
+// the walks' checks on graph, tables and expansion width (graph_search_impl, annlite_graph_search_packed_admit)
+int annlite::graph_walk_check(bool packed, int links_per_node, int64_t n_seeds, int64_t N, int64_t M, int64_t Ks, int64_t B, int width) {
+    ANNLITE_REQUIRE(width == 1 || (width == 2 && packed && links_per_node <= 32),
                     "expansion width %d: 1, or 2 over packed records of at most 32 neighbours (links_per_node = %d)", width, links_per_node);
     ANNLITE_REQUIRE(Ks >= 1 && Ks <= 256 && (M == 8 || M == 16 || M == 32 || M == 64), "graph search supports M in {8,16,32,64}, Ks <= 256");
     ANNLITE_REQUIRE(links_per_node >= 1 && n_seeds >= 1 && N < (1ll << 32) - 1, "bad graph");
-    ANNLITE_REQUIRE(!packed_dev || links_per_node <= 64, "packed records hold at most 64 neighbours (links_per_node = %d)", links_per_node);
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE((links_dev || packed_dev) && seeds_dev && codes_dev && lut_bmk_dev && out_ids_dev && out_dist_dev, "null device pointer");
-    hipStream_t st = (hipStream_t)stream;
+    ANNLITE_REQUIRE(!packed || links_per_node <= 64, "packed records hold at most 64 neighbours (links_per_node = %d)", links_per_node);
+    return ANNLITE_OK;
+}
+
+// entries of the visited table (log2) beside a routing list of `ef` places
+int annlite::graph_walk_hash_bits(int ef) {
     // 4096 entries up to ef = 128 (a walk records 2-3k nodes: 5M rows, ef 128 gave the same recall as 8192 entries at
     // 1.5x the speed -- 5 instead of 3 waves per CU), 8192 beyond; a full table only costs re-evaluations (see visit)
     // round 6: 4096 entries up to ef = 208 as well -- with 8192 entries beside a list of more than 128 entries only three waves fit a CU
@@ -404,13 +161,34 @@ static int graph_search_impl(const uint32_t *links_dev, const uint8_t *packed_de
     if (knobs().graph_hash_bits >= 0) hash_bits = knobs().graph_hash_bits;  // (ANNLITE_GRAPH_HASH_BITS: tests force a tiny table)
     if (hash_bits < 4) hash_bits = 4;    // (buckets of four entries, 16-byte initialisation)
     if (hash_bits > 15) hash_bits = 15;  // (128 KB: what is left of the LDS beside the smallest table)
-    const uint8_t *codes = (const uint8_t *)codes_dev;
-    unsigned long long *stats = nullptr;
+    return hash_bits;
+}
+
+// *stats: the debug counters' buffer, zeroed on `st` (NULL unless ANNLITE_DEBUG_COUNTERS)
+int annlite::graph_walk_stats(hipStream_t st, unsigned long long **stats) {
+    *stats = nullptr;
     if (knobs().debug_counters) {
         if (!g_graph_stats) ANNLITE_HIP_TRY(hipMalloc((void **)&g_graph_stats, 64));
         ANNLITE_HIP_TRY(hipMemsetAsync(g_graph_stats, 0, 64, st));
-        stats = g_graph_stats;
+        *stats = g_graph_stats;
     }
+    return ANNLITE_OK;
+}
+
+static int graph_search_impl(const uint32_t *links_dev, const uint8_t *packed_dev, int links_per_node, const uint32_t *seeds_dev,
+                             int64_t n_seeds, const void *codes_dev, int64_t N, int64_t M, int64_t Ks, const uint32_t *valid_bits_dev,
+                             const float *lut_bmk_dev, int64_t B, int ef, int64_t *out_ids_dev, float *out_dist_dev, void *stream,
+                             int width = 1) {
+    ANNLITE_REQUIRE(B >= 0 && N >= 0 && ef >= 1 && ef <= 256, "bad B=%lld N=%lld ef=%d (ef <= 256)", (long long)B,
+                    (long long)N, ef);
+    if (int rc = graph_walk_check(packed_dev != nullptr, links_per_node, n_seeds, N, M, Ks, B, width)) return rc;
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE((links_dev || packed_dev) && seeds_dev && codes_dev && lut_bmk_dev && out_ids_dev && out_dist_dev, "null device pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int hash_bits = graph_walk_hash_bits(ef);
+    const uint8_t *codes = (const uint8_t *)codes_dev;
+    unsigned long long *stats = nullptr;
+    if (int rc = graph_walk_stats(st, &stats)) return rc;
 #define ANNLITE_BEAM_ARGS links_dev, links_per_node, packed_dev, seeds_dev, (int)n_seeds, codes, N, valid_bits_dev, lut_bmk_dev, B, Ks, ef, \
                           hash_bits, out_ids_dev, out_dist_dev, stats, st
 #define ANNLITE_BEAM(MM, PK, BT) \

@@ -22,7 +22,8 @@ a search that scans each query's ``n_probe`` nearest cells and answers those row
 With ``graph=True, build='gpu'`` it is ``HnswFlatGpuIndex``, a level-0 HNSW graph over the float vectors.  A
 search with a ``filter`` is answered exactly by default; ``filter_search='graph'`` answers it on the graph as hnswlib's filtered search
 does (the walk routes through every row, only rows that pass the filter are listed), except for filters that keep too few rows for the
-walk to pay (``HnswFlatGpuIndex.FILTER_WALK_MIN_FRACTION``), which stay exact.
+walk to pay (``HnswFlatGpuIndex.FILTER_WALK_MIN_FRACTION``), which stay exact.  The graph over PQ codes (``n_subvectors=M, graph=True``:
+``HnswPQGpuIndex``) takes the same option with a floor of its own (``HnswPQGpuIndex.FILTER_WALK_MIN_FRACTION``).
 
 ``n_cells > 1`` (index.py:125-133, 458-483): a ``VQCodec`` coarse quantiser assigns every vector to a cell and ONE
 ``IvfPQGpuIndex`` holds all cells.  Like the reference (``n_probe = max(n_probe, n_cells)``, index.py:94) a search
@@ -88,9 +89,10 @@ class AnnLite:
     :param rerank: keep the float vectors in HBM and re-score ADC candidates exactly (kwarg, rides
         the reference's ``**kwargs`` channel to the index, container.py:56).  With ``n_cells > 1`` and ``ivf_prune=True`` the same channel
         takes ``rerank_bound_rank`` / ``rerank_split`` (the candidate pool of the pruned search's re-rank: ``IvfPQGpuIndex``)
-    :param filter_search: ``'exact'`` (default) or ``'graph'`` (kwarg, same channel; the float HNSW graph only, ignored by the other
-        indexes): how a search that carries a ``filter`` is answered -- by the exact filtered search, or by the graph walk that lists
-        only the rows the filter admits (``HnswFlatGpuIndex.search_batch``)
+    :param filter_search: ``'exact'`` (default) or ``'graph'`` (kwarg, same channel; the two graph indexes -- ``graph=True`` with or
+        without ``n_subvectors`` --, ignored by the other indexes): how a search that carries a ``filter`` is answered -- by the exact
+        filtered search, or by the graph walk that lists only the rows the filter admits (``HnswFlatGpuIndex.search_batch``,
+        ``HnswPQGpuIndex.search_batch``)
     """
 
     def __init__(
@@ -238,7 +240,8 @@ class AnnLite:
 
                 return IvfFlatGpuIndex(dim=self._index_dim, metric=self.metric, vq_codec=self._vq_codec, n_probe=self._n_probe_arg, **kw)
             return FlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
-        kw.pop('filter_search', None)  # (the float graph's option: the indexes over PQ codes are unchanged)
+        if not (self._vq_codec is None and kw.get('graph')):
+            kw.pop('filter_search', None)  # (the graph indexes' option: the other indexes over PQ codes answer a filter exactly)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')
         if self._vq_codec is not None:

@@ -159,6 +159,33 @@ def graph_search_packed(packed: torch.Tensor, links_per_node: int, seeds: torch.
     return out_i, out_d
 
 
+def graph_search_packed_admit(packed: torch.Tensor, links_per_node: int, seeds: torch.Tensor, codes: torch.Tensor, lut_bmk: torch.Tensor,
+                              ef_route: int, ef: int, admit_bits: torch.Tensor, n_rows: Optional[int] = None, expand_width: int = 1,
+                              route_worst: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_graph_search_packed_admit``: ``graph_search_packed`` at ``ef = ef_route`` -- same expansions, same rows evaluated --
+    that keeps, beside the routing list, the ``ef <= ef_route`` best rows set in the bitmap ``admit_bits`` (i32 words over the rows;
+    required) among everything it evaluates.  Returns (ids i64 [B, ef] ascending by (PQLookup sum, id), admitted rows only, -1 at the
+    tail; dist f32 [B, ef], +inf there).  ``route_worst`` f32 [B], when given, receives the sum at the routing list's last place (+inf
+    while that list is not full): how far the walk reached."""
+    assert codes.dtype == torch.uint8 and codes.is_contiguous() and packed.is_contiguous() and lut_bmk.is_contiguous()
+    assert lut_bmk.dtype == torch.float32 and seeds.is_contiguous() and seeds.element_size() == 4
+    B, M, Ks = lut_bmk.shape
+    assert codes.shape[1] == M
+    N = codes.shape[0] if n_rows is None else int(n_rows)
+    assert N <= codes.shape[0] and N <= packed.shape[0]
+    assert route_worst is None or (route_worst.dtype == torch.float32 and route_worst.is_contiguous() and route_worst.numel() == B
+                                   and route_worst.device == codes.device)
+    # (None goes to the library, which refuses it)
+    assert admit_bits is None or (admit_bits.is_contiguous() and admit_bits.element_size() == 4 and admit_bits.numel() * 32 >= N)
+    out_i = torch.empty((B, ef), dtype=torch.int64, device=codes.device)
+    out_d = torch.empty((B, ef), dtype=torch.float32, device=codes.device)
+    check(lib().annlite_graph_search_packed_admit(packed.data_ptr(), int(links_per_node), seeds.data_ptr(), seeds.numel(),
+                                                  codes.data_ptr(), N, M, Ks, _ptr(admit_bits), lut_bmk.data_ptr(), B, int(ef_route),
+                                                  int(ef), int(expand_width), out_i.data_ptr(), out_d.data_ptr(), _ptr(route_worst),
+                                                  stream_ptr()), 'graph_search_packed_admit')
+    return out_i, out_d
+
+
 def graph_record_bytes(links_per_node: int, M: int) -> int:
     import ctypes
 

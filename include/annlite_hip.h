@@ -183,6 +183,19 @@ ANNLITE_API int annlite_graph_search_packed_ex(const void *packed_dev, int links
                          int64_t n_seeds, const void *codes_dev, int64_t N, int64_t M, int64_t Ks,
                          const uint32_t *valid_bits_dev, const float *lut_bmk_dev, int64_t B, int ef, int expand_width,
                          int64_t *out_ids_dev, float *out_dist_dev, void *stream);
+/* ... for a FILTERED search (graph_admit.hip): annlite_graph_search_packed_ex's walk at ef = ef_route -- same expansions, same rows
+ * evaluated, same prefetched records: admit_bits_dev never touches the routing list -- with a SECOND sorted list of
+ * ef <= ef_route <= 256 places that is offered every batch the routing list is offered (a seed round, a step's unseen neighbours),
+ * restricted to the rows set in admit_bits_dev (u32 bitmap over the N rows, REQUIRED: valid & filter; a walk without a filter is the
+ * entry point above), under the same test-against-the-worst-entry-then-merge rule, ordered by (PQLookup sum, id).  It ends as the ef
+ * smallest (sum, id) among the admitted rows the walk evaluated: out_ids_dev i64 [B][ef] / out_dist_dev f32 [B][ef] ascending, the
+ * missing places (-1, +inf) at the tail.  out_route_worst_dev f32 [B] (may be NULL): the sum at the routing list's last place, +inf
+ * while that list is not full -- how far the walk reached; a result beyond it was only met on the way.  expand_width as above.
+ * ANNLITE_DEBUG_COUNTERS fills the counters of annlite_graph_search_stats_ex. */
+ANNLITE_API int annlite_graph_search_packed_admit(const void *packed_dev, int links_per_node, const uint32_t *seeds_dev,
+                         int64_t n_seeds, const void *codes_dev, int64_t N, int64_t M, int64_t Ks,
+                         const uint32_t *admit_bits_dev, const float *lut_bmk_dev, int64_t B, int ef_route, int ef,
+                         int expand_width, int64_t *out_ids_dev, float *out_dist_dev, float *out_route_worst_dev, void *stream);
 /* ---- the level-0 graph BUILT ON THE GPU, in batches (round 6; graph_build.hip) -------------------------------------------------
  * replaces, for a batch of points: hnswlib addPoint (include/hnswlib/hnswalg.h:1108-1235) = searchBaseLayer with ef_construction
  * (the walk above over the graph as it is, the points' own L2 tables as queries), getNeighborsByHeuristic2 (378-429) and
