@@ -110,6 +110,11 @@ SYMBOLS = (
     'annlite_flat_search_topk',
     'annlite_flat_overflow_count',
     'annlite_flat_list_counts',
+    'annlite_flat_split_slack',
+    'annlite_flat_centred_norms',
+    'annlite_flat_search_split_workspace_bytes',
+    'annlite_flat_filter_split',
+    'annlite_flat_search_topk_split',
     'annlite_ivf_flat_stages',
     'annlite_ivf_flat_search_workspace_bytes',
     'annlite_ivf_flat_search_topk',
@@ -239,6 +244,11 @@ def lib() -> ctypes.CDLL:
     L.annlite_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, i64, i32, vp, vp, vp, sz, vp]
     L.annlite_flat_overflow_count.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_flat_list_counts.argtypes = [vp, i64, vp, vp]
+    L.annlite_flat_split_slack.argtypes = [i32, i64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.annlite_flat_centred_norms.argtypes = [vp, i64, i64, vp, i64, i64, vp, vp, vp]
+    L.annlite_flat_search_split_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_flat_filter_split.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.annlite_flat_search_topk_split.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp, sz, vp]
     L.annlite_ivf_flat_stages.argtypes = [i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32)]
     L.annlite_ivf_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_ivf_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, vp,

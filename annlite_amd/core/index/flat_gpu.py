@@ -12,8 +12,11 @@ arithmetic.  The answer is exact in that arithmetic: a stored vector searched wi
 
 Where it is slow (and still exact): the filter's slack is relative to ``|x|^2 + |q|^2``, not to the distance.  Data with a large
 common offset (every coordinate near 1000) makes it exceed every distance: all rows pass, the lists overflow and each query is
-answered by one wave over ALL rows (``last_overflowed`` counts them) -- centre such data before indexing it.  The same route serves
-NaN / infinite queries and searches restricted (``indices=``, deletes) to fewer than about k rows in 4096.
+answered by one wave over ALL rows (``last_overflowed`` counts them).  ``flat_filter='bf16x3'`` is the filter for such data: it
+contracts the rows minus a fixed centre (``centre='mean'``: the mean of the first batch added), carried as two bf16 numbers each, on
+three bf16 MFMAs, and its slack is relative to ``|x - centre|^2 + |q - centre|^2``; the answer keeps its bits (DESIGN.md section 3.6,
+"split filter").  The all-rows route also serves NaN / infinite queries and searches restricted (``indices=``, deletes) to fewer
+than about k rows in 4096, under either filter.
 """
 from pathlib import Path
 from typing import Optional, Tuple, Union
@@ -32,34 +35,102 @@ def flat_slack_constants(metric: Metric, dim: int) -> Tuple[np.float32, np.float
     return ops.flat_slack(int(Metric(metric)), dim)
 
 
+def flat_split_slack_constants(metric: Metric, dim: int) -> Tuple[np.float32, np.float32]:
+    """``(c_rel, c_abs)`` of the split filter (``flat_filter='bf16x3'``), where the norms are those of the centred values
+    (``annlite_flat_split_slack``; derivation: DESIGN.md section 3.6, "split filter")."""
+    return ops.flat_split_slack(int(Metric(metric)), dim)
+
+
 class FlatGpuIndex(RowStoreIndex):
+    """
+    :param flat_filter: ``'f32'`` (default): the f32 MFMA filter.  ``'bf16x3'``: the split-bf16 filter over centred rows -- the same
+        answer bit for bit, a slack that does not grow with a common offset of the data, ``dim <= 32768``.  Searches with
+        ``limit > 64`` keep the f32 filter under either value: offset data stays slow there.
+    :param centre: what ``'bf16x3'`` subtracts from rows and queries before it splits them, EUCLIDEAN only -- INNER_PRODUCT and COSINE
+        are not invariant under a shift and run the split filter on the values themselves.  ``'mean'`` (default): the f32 mean of the
+        first ``add_with_ids`` batch, frozen until ``reset()``; an array ``[dim]``: that point; ``None``: no centring.  Any centre gives
+        the exact answer; it only moves the slack (a NaN or infinite one -- the mean of a first batch that holds such a value --
+        lets every row pass: every query then takes the all-rows route).  ``centre_`` reads the one in use.
+    """
     FORMAT = 'annlite_amd.FlatGpuIndex/1'
     STATE_KEYS = ('dim', 'metric')
+    FLAT_FILTERS = ('f32', 'bf16x3')
+    SPLIT_MAX_DIM = 32768    # (annlite_flat_split_slack: the range of the slack's derivation)
+    FILTER_MIN_ROWS = 4097   # (kFlatSample + 1 in flat.hip: smaller tables are answered by exact sums, no filter runs)
 
     def __init__(self, dim: int, dtype: np.dtype = np.float32, metric: Metric = Metric.COSINE,
-                 index_file: Optional[Union[str, Path]] = None, **kwargs):
+                 index_file: Optional[Union[str, Path]] = None, flat_filter: str = 'f32', centre='mean', **kwargs):
+        if flat_filter not in self.FLAT_FILTERS:
+            raise ValueError(f"flat_filter={flat_filter!r}: 'f32' (the f32 MFMA filter) or 'bf16x3' (the split-bf16 filter over centred rows)")
+        if isinstance(centre, str) and centre != 'mean':
+            raise ValueError(f"centre={centre!r}: 'mean', None or an array of {dim} coordinates")
+        if centre is not None and not isinstance(centre, str):
+            centre = np.array(centre.cpu() if isinstance(centre, torch.Tensor) else centre, dtype=np.float32)
+            if centre.shape != (dim,):
+                raise ValueError(f'centre has shape {centre.shape}: ({dim},) expected')
+        if flat_filter == 'bf16x3' and dim > self.SPLIT_MAX_DIM:
+            raise ValueError(f"flat_filter='bf16x3' takes dim <= {self.SPLIT_MAX_DIM}")
+        self.flat_filter = flat_filter
+        self.centre = centre
+        self.last_flat_filter = None  # 'f32' / 'bf16x3': the filter of the last search_batch; None: it ran none
+        self._centre_dev = None
+        self._centred = flat_filter == 'bf16x3' and Metric(metric) == Metric.EUCLIDEAN and centre is not None
         super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
         self._ws = ops.ScanWorkspace()
         self._overflowed = 0  # (of the last search_batch; None: ask the library's workspace)
         if index_file:
             self.load(index_file)
 
+    # ------------------------------------------------------------------ the split filter's centre
+    @property
+    def centre_(self) -> Optional[np.ndarray]:
+        """The centre the split filter subtracts, f32 ``[dim]``; None: none (the f32 filter, another metric, ``centre=None``, or
+        ``'mean'`` before the first rows arrived)."""
+        return None if self._centre_dev is None else self._centre_dev.cpu().numpy()
+
+    def _fix_centre(self, rows: torch.Tensor, stored=None):
+        """Settle the centre once: the constructor's array, else the one an index file carried, else the f32 mean of ``rows``."""
+        if not self._centred or self._centre_dev is not None:
+            return
+        if not isinstance(self.centre, str):
+            self._centre_dev = self._to_dev(self.centre, torch.float32).contiguous()
+        elif stored is not None:
+            self._centre_dev = self._to_dev(np.asarray(stored, dtype=np.float32).reshape(self.dim), torch.float32).contiguous()
+        else:
+            self._centre_dev = rows.to(torch.float32).mean(dim=0).contiguous()
+
+    def reset(self, capacity: Optional[int] = None):
+        super().reset(capacity=capacity)
+        self._centre_dev = None
+
     # ------------------------------------------------------------------ storage (row_store.py)
     def _columns(self):
-        return {'_vectors': ((self.dim,), torch.float32), '_norms': ((), torch.float32)}
+        """``_cnorms``: the norms of the centred rows, kept only where the split filter has a centre (it reads ``_norms`` otherwise)"""
+        return {'_vectors': ((self.dim,), torch.float32), '_norms': ((), torch.float32),
+                '_cnorms': ((), torch.float32) if self._centred else None}
 
     def _write_rows(self, x, ids):
         self._vectors[ids] = x  # flat_index.py:41-50 `_data[ids] = x`
         ops.flat_row_norms(self._vectors, ids=ids, out=self._norms)
+        if self._centred:
+            self._fix_centre(x)
+            ops.flat_centred_norms(self._vectors, self._centre_dev, ids=ids, out=self._cnorms)
 
     def _dump_state(self, N):
-        """vectors as stored (normalised for COSINE); norms are recomputed on load"""
-        return {'vectors': self._vectors[:N].cpu().numpy()}
+        """vectors as stored (normalised for COSINE); norms are recomputed on load.  ``centre`` (optional key): the split filter's"""
+        state = {'vectors': self._vectors[:N].cpu().numpy()}
+        if self._centre_dev is not None:
+            state['centre'] = self.centre_
+        return state
 
     def _load_state(self, state, N):
+        self._centre_dev = None
         if N:
             self._vectors[:N] = self._to_dev(state['vectors'])
             ops.flat_row_norms(self._vectors, n=N, out=self._norms)
+            if self._centred:  # (a file without the key -- an older one, an f32 index's: the mean of the rows it holds)
+                self._fix_centre(self._vectors[:N], stored=state.get('centre'))
+                ops.flat_centred_norms(self._vectors, self._centre_dev, n=N, out=self._cnorms)
 
     # ------------------------------------------------------------------ search
     @property
@@ -81,14 +152,22 @@ class FlatGpuIndex(RowStoreIndex):
         N = self._n_rows
         dev = q.device
         self._overflowed = 0
+        self.last_flat_filter = None
         if N == 0 or B == 0:
             d, i = empty_answer(B, k, dev)
         else:
             valid = self._valid if indices is None else self._filter_bits(indices)
-            if k <= 64:
+            if k <= 64 and self.flat_filter == 'bf16x3':
+                d, i = ops.flat_search_topk_split(int(self.metric), q, self._vectors, self._cnorms if self._centred else self._norms, k,
+                                                  centre=self._centre_dev if self._centred else None, valid_bits=valid, n_rows=N,
+                                                  sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
+                self._overflowed = None
+                self.last_flat_filter = 'bf16x3' if N >= self.FILTER_MIN_ROWS else None
+            elif k <= 64:
                 d, i = ops.flat_search_topk(int(self.metric), q, self._vectors, self._norms, k, valid_bits=valid, n_rows=N,
                                             sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)  # hnsw/index.py:164-165
                 self._overflowed = None  # (read from the workspace when asked for: it costs a synchronisation)
+                self.last_flat_filter = 'f32' if N >= self.FILTER_MIN_ROWS else None
             else:
                 d, i = self._search_large_k(q, k, valid, N)
         return like_input(is_np, d, i)
@@ -147,6 +226,7 @@ class FlatGpuIndex(RowStoreIndex):
                               else torch.full((nb,), float('inf'), device=dev))
             bound = torch.cat(bounds).contiguous()  # (+inf -- fewer than k valid sampled rows, NaN distances -- passes everything)
             cand32, count = ops.flat_filter(int(self.metric), q, self._vectors, self._norms, bound, valid_bits=valid, n_rows=N)
+            self.last_flat_filter = 'f32'  # (whatever `flat_filter` says: offset data stays slow for limit > 64)
             over = count > cap
             ok = torch.arange(cap, device=dev)[None, :] < count[:, None]
             cand = torch.where(ok, cand32.to(torch.int64), torch.full((1, 1), -1, dtype=torch.int64, device=dev))

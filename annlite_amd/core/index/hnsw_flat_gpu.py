@@ -17,7 +17,8 @@ exact search of the parent: never worse.  ``filter_search='graph'`` (constructor
 instead, as hnswlib's ``searchBaseLayerSTWithFilter`` does: ``annlite_graph_f32_search_admit`` walks through every node and keeps the
 best admitted rows among everything it evaluates ("filtered walk").  Ids must be dense in insertion order
 (0, 1, 2, ...: what AnnLite's offsets are); rows are not updated in place (delete + add a new offset, hnsw/index.py:173-177); a delete
-clears the validity bit only -- the row keeps routing the walk.
+clears the validity bit only -- the row keeps routing the walk.  ``flat_filter`` / ``centre`` are the parent's keywords and reach it
+unchanged: they choose the filter of those exact searches (``search_exhaustive`` included), never the walk.
 """
 from pathlib import Path
 from typing import List, Optional, Tuple, Union
@@ -137,6 +138,7 @@ class HnswFlatGpuIndex(FlatGpuIndex):
         q = self._pre(x)
         B = q.shape[0]
         self._overflowed = 0
+        self.last_flat_filter = None
         self.last_filter_path = 'graph'
         if B == 0:
             return like_input(is_np, *empty_answer(B, k, q.device))
@@ -194,6 +196,7 @@ class HnswFlatGpuIndex(FlatGpuIndex):
         q = self._pre(x)
         B = q.shape[0]
         self._overflowed = 0
+        self.last_flat_filter = None  # (a walk: no filter ran)
         if B == 0:
             return like_input(is_np, *empty_answer(B, k, q.device))
         cand, cand_d = self.candidates(q, ef)

@@ -42,6 +42,10 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         self.n_probe = n_probe  # None: every cell (the reference's behaviour)
         self._sealed = False
         self._perm = self._cell_rows = self._cell_order = self._sizes_cum = None
+        # (accepted and ignored: the cell-tile filter is the f32 one, and so is this index's every-cell search -- the split filter
+        # over cell tiles is not built)
+        kwargs.pop('flat_filter', None)
+        kwargs.pop('centre', None)
         super().__init__(dim, metric=metric, **kwargs)
 
     # ------------------------------------------------------------------ sealed (cell-grouped) view

@@ -25,8 +25,11 @@ constexpr int64_t kFlatSample = 4096;     // rows of the first (exact) sample; t
 constexpr double kFlatGrowth = 32.0;      // a stage's row set is at most this many times the previous one
 
 // ---- |x|^2 per row: the lane-strided fmaf chain + butterfly of the exact kernels (relative error <= gamma(ceil(D/64) + 6)) ----
+// CENTRED: the same chain over c_j = fl(x_j - mu_j), the values the split filter contracts (second half of the filter section).
+template <bool CENTRED>
 __global__ __launch_bounds__(256) void flat_norms_kernel(const float *__restrict__ x, int D, const int64_t *__restrict__ ids, int64_t n,
-                                                        int64_t id_base, int64_t capacity, float *__restrict__ norms) {
+                                                        int64_t id_base, int64_t capacity, const float *__restrict__ mu,
+                                                        float *__restrict__ norms) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
@@ -34,7 +37,10 @@ __global__ __launch_bounds__(256) void flat_norms_kernel(const float *__restrict
     if (row < 0 || row >= capacity) return;
     const float *xr = x + row * D;
     float s = 0.f;
-    for (int j = lane; j < D; j += 64) s = __builtin_fmaf(xr[j], xr[j], s);
+    for (int j = lane; j < D; j += 64) {
+        const float c = CENTRED ? xr[j] - mu[j] : xr[j];
+        s = __builtin_fmaf(c, c, s);
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) norms[row] = s;
@@ -138,6 +144,195 @@ __global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const floa
                     const float bound = t + (c_rel * a + c_abs);
                     if (!(v > bound)) {
                         // (a list that has already overflowed takes the slower route whatever else arrives: stop counting)
+                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
+                            const int pos = atomicAdd(my_cnt, 1);
+                            if (pos < cap) my_list[pos] = (int32_t)((r0 + rl) * stride);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ---- the split filter: the same scores from three bf16 MFMAs over CENTRED rows ("split filter") -----------
+// Each f32 value c = fl(x_j - mu_j) (mu = 0 without a centre) is carried as c_h + c_l, c_h = bf16(c), c_l = bf16(fl(c - c_h)), both by
+// the hardware's round-to-nearest-even conversion, and  q.x ~ q_h.x_h + q_h.x_l + q_l.x_h  on v_mfma_f32_32x32x16_bf16 (three MFMAs of
+// K = 16 where the f32 form issues eight of K = 2).  The rows are split while they are staged into LDS -- the table in HBM is the f32
+// one --, the queries once per call (flat_split_queries_kernel).  norms / qnorm are the norms of the CENTRED values.
+// LDS: two bf16 planes per operand, 32 coordinates (two K steps) per stage, row pitch 40 bf16 = 80 bytes = 5 slots of 16 bytes.  A lane
+// reads the 8 coordinates 8 (lane >> 5) .. of row lane & 31 as one ds_read_b128; the 16 lanes that instruction serves together hold
+// rows that are distinct mod 16, and 5 r mod 16 is a permutation: every lane group covers the 64 banks once.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kSplitDepth = 32;             // coordinates per LDS stage
+constexpr int kSplitLd = kSplitDepth + 8;   // LDS row pitch in bf16
+constexpr int64_t kSplitMaxDim = 32768;     // the slack's derivation holds up to here
+
+__device__ __forceinline__ void split_bf16(float c, __bf16 &h, __bf16 &l) {
+    h = (__bf16)c;
+    l = (__bf16)(c - (float)h);  // (the difference is exact; an infinite c gives (inf, NaN): the score is NaN and the row passes)
+}
+
+// qh / ql bf16 [B][Dp] (Dp = D rounded up to 16, the padding zero) and qnorm[b] = |fl(q - mu)|^2 in flat_norms_kernel's chain.
+__global__ __launch_bounds__(256) void flat_split_queries_kernel(const float *__restrict__ q, int B, int D, int Dp, const float *__restrict__ mu,
+                                                                __bf16 *__restrict__ qh, __bf16 *__restrict__ ql, float *__restrict__ qnorm) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float *qr = q + (int64_t)b * D;
+    float s = 0.f;
+    for (int j = lane; j < Dp; j += 64) {
+        float c = 0.f;
+        if (j < D) {
+            c = mu ? qr[j] - mu[j] : qr[j];
+            s = __builtin_fmaf(c, c, s);
+        }
+        __bf16 h, l;
+        split_bf16(c, h, l);
+        qh[(int64_t)b * Dp + j] = h;
+        ql[(int64_t)b * Dp + j] = l;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) qnorm[b] = s;
+}
+
+// flat_filter_kernel's job, grid, tile and epilogue.  scores != NULL (tests, measurements): v of every (query, stage row) pair goes to
+// scores f32 [B][S] as well.
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, const __bf16 *__restrict__ qh, const __bf16 *__restrict__ ql, int B,
+                                                               int D, int Dp, const float *__restrict__ x, const float *__restrict__ mu,
+                                                               const float *__restrict__ norms, int64_t S, int64_t stride,
+                                                               const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
+                                                               const float *__restrict__ thr, float c_rel, float c_abs,
+                                                               int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles,
+                                                               float *__restrict__ scores) {
+    __shared__ __attribute__((aligned(16))) __bf16 Ah[kFlatTile * kSplitLd];
+    __shared__ __attribute__((aligned(16))) __bf16 Al[kFlatTile * kSplitLd];
+    __shared__ __attribute__((aligned(16))) __bf16 Bh[kFlatTile * kSplitLd];
+    __shared__ __attribute__((aligned(16))) __bf16 Bl[kFlatTile * kSplitLd];
+    __shared__ float nxs[kFlatTile];
+    __shared__ int oks[kFlatTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
+    if (tid < kFlatTile) {
+        const int64_t r = r0 + tid;
+        bool ok = r < S;
+        const int64_t row = ok ? r * stride : 0;
+        if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
+        oks[tid] = ok ? 1 : 0;
+        nxs[tid] = ok ? norms[row] : 0.f;
+    }
+    const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
+    const int l31 = lane & 31, lh = lane >> 5;
+    for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
+        const int q0 = qt * kFlatTile;
+        f32x16 acc00, acc01, acc10, acc11;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        for (int k0 = 0; k0 < D; k0 += kSplitDepth) {
+            __syncthreads();  // the previous stage is consumed (first pass: the row tile's norms and flags are written)
+            // rows: f32 from HBM, centred, split, two planes
+            if constexpr (VEC) {
+#pragma unroll
+                for (int i = 0; i < kSplitDepth / 8; ++i) {
+                    const int e = tid + i * 256;  // slots of 4 floats
+                    const int r = e / (kSplitDepth / 4), c = (e % (kSplitDepth / 4)) * 4;
+                    f32x4 cv = {0.f, 0.f, 0.f, 0.f};
+                    const int64_t rr = r0 + r;
+                    if (rr < S && k0 + c < D) {
+                        cv = *(const f32x4 *)(x + rr * stride * D + k0 + c);
+                        if (mu) cv = cv - *(const f32x4 *)(mu + k0 + c);
+                    }
+                    bf16x4 h4, l4;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        __bf16 h, l;
+                        split_bf16(cv[t], h, l);
+                        h4[t] = h, l4[t] = l;
+                    }
+                    *(bf16x4 *)(Ah + r * kSplitLd + c) = h4;
+                    *(bf16x4 *)(Al + r * kSplitLd + c) = l4;
+                }
+            } else {
+#pragma unroll 4
+                for (int i = 0; i < kSplitDepth / 2; ++i) {
+                    const int e = tid + i * 256;  // single floats
+                    const int r = e / kSplitDepth, c = e % kSplitDepth;
+                    const int64_t rr = r0 + r;
+                    float cv = 0.f;
+                    if (rr < S && k0 + c < D) {
+                        cv = x[rr * stride * D + k0 + c];
+                        if (mu) cv = cv - mu[k0 + c];
+                    }
+                    __bf16 h, l;
+                    split_bf16(cv, h, l);
+                    Ah[r * kSplitLd + c] = h;
+                    Al[r * kSplitLd + c] = l;
+                }
+            }
+            // queries: the planes of flat_split_queries_kernel, 16 bytes at a time (Dp is a multiple of 8 coordinates)
+#pragma unroll
+            for (int i = 0; i < kSplitDepth / 16; ++i) {
+                const int e = tid + i * 256;  // slots of 8 bf16 per plane
+                const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
+                const int qq = q0 + r;
+                bf16x8 vh, vl;
+#pragma unroll
+                for (int t = 0; t < 8; ++t) vh[t] = vl[t] = (__bf16)0.f;
+                if (qq < B && k0 + c < Dp) {
+                    vh = *(const bf16x8 *)(qh + (int64_t)qq * Dp + k0 + c);
+                    vl = *(const bf16x8 *)(ql + (int64_t)qq * Dp + k0 + c);
+                }
+                *(bf16x8 *)(Bh + r * kSplitLd + c) = vh;
+                *(bf16x8 *)(Bl + r * kSplitLd + c) = vl;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < kSplitDepth; kk += 16) {
+                if (k0 + kk >= D) break;  // (a K step of padding only)
+                const int kc = kk + 8 * lh;
+                const bf16x8 a0h = *(const bf16x8 *)(Ah + (wr + l31) * kSplitLd + kc), a0l = *(const bf16x8 *)(Al + (wr + l31) * kSplitLd + kc);
+                const bf16x8 a1h = *(const bf16x8 *)(Ah + (wr + 32 + l31) * kSplitLd + kc), a1l = *(const bf16x8 *)(Al + (wr + 32 + l31) * kSplitLd + kc);
+                const bf16x8 b0h = *(const bf16x8 *)(Bh + (wq + l31) * kSplitLd + kc), b0l = *(const bf16x8 *)(Bl + (wq + l31) * kSplitLd + kc);
+                const bf16x8 b1h = *(const bf16x8 *)(Bh + (wq + 32 + l31) * kSplitLd + kc), b1l = *(const bf16x8 *)(Bl + (wq + 32 + l31) * kSplitLd + kc);
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0h, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1h, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0h, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1h, acc11, 0, 0, 0);
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0l, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1l, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0l, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1l, acc11, 0, 0, 0);
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b0h, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b1h, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b0h, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b1h, acc11, 0, 0, 0);
+            }
+        }
+        // epilogue: score, compare, append (flat_filter_kernel's, on the centred norms)
+#pragma unroll
+        for (int qj = 0; qj < 2; ++qj) {
+            const int qi = q0 + wq + qj * 32 + l31;
+            if (qi >= B) continue;
+            const float qn = qnorm[qi], t = thr[qi];
+            int32_t *my_cnt = cnt + qi;
+            int32_t *my_list = cand + (int64_t)qi * cap;
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri) {
+                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                    const float a = nxs[rl] + qn;
+                    const float dot = acc[reg];
+                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
+                    if (scores && r0 + rl < S) scores[(int64_t)qi * S + r0 + rl] = v;
+                    if (!oks[rl]) continue;
+                    const float bound = t + (c_rel * a + c_abs);
+                    if (!(v > bound)) {
                         if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
                             const int pos = atomicAdd(my_cnt, 1);
                             if (pos < cap) my_list[pos] = (int32_t)((r0 + rl) * stride);
@@ -469,6 +664,109 @@ static int flat_launch_filter(int metric, const float *q, int64_t B, int64_t D, 
     return launch_status("flat_filter_kernel");
 }
 
+// ---- the split filter's share of a workspace: the query planes, behind the FlatWs of the same B (so that the overflow counter and the
+// list counters sit where annlite_flat_overflow_count / annlite_flat_list_counts read them) ----
+struct FlatSplitWs {
+    FlatWs f;
+    int64_t Dp;  // D rounded up to the MFMA's K step
+    __bf16 *qh, *ql;
+    size_t bytes;
+};
+static FlatSplitWs flat_split_carve(void *ws, int64_t B, int64_t D) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    FlatSplitWs w;
+    w.f = flat_carve(ws, B);
+    w.Dp = (D + 15) / 16 * 16;
+    char *p = (char *)ws;
+    size_t o = w.f.bytes;
+    w.qh = (__bf16 *)(p + o), o += up((size_t)B * w.Dp * 2);
+    w.ql = (__bf16 *)(p + o), o += up((size_t)B * w.Dp * 2);
+    w.bytes = o;
+    return w;
+}
+
+// The split filter's two constants ("split filter").  u = 2^-24, Dp = 16 ceil(D / 16).
+static void flat_split_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
+    const double u = 5.9604644775390625e-08;
+    const double nl = (double)((D + 63) / 64), dp = (double)((D + 15) / 16 * 16);
+    *c_rel = (float)(1.05 * u * (6.6 * dp + 780.0 + 3.0 * nl + 44.0));
+    *c_abs = metric == ANNLITE_METRIC_EUCLIDEAN ? 2e-30f : (float)(9.0 * u);
+}
+
+// Per call: centre and split the queries into the workspace planes, |fl(q - mu)|^2 into w.f.qnorm.
+static int flat_split_prepare(const float *q, int64_t B, int64_t D, const float *mu, const FlatSplitWs &w, hipStream_t st) {
+    hipLaunchKernelGGL(flat_split_queries_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, q, (int)B, (int)D, (int)w.Dp, mu, w.qh, w.ql,
+                       w.f.qnorm);
+    return launch_status("flat_split_queries_kernel");
+}
+
+static int flat_split_launch_filter(int metric, int64_t B, int64_t D, const float *x, const float *mu, const float *norms, int64_t S,
+                                    int64_t stride, const uint32_t *valid, const FlatSplitWs &w, const float *thr, int32_t *cand,
+                                    int32_t *cnt, float *scores, hipStream_t st) {
+    float c_rel, c_abs;
+    flat_split_slack(metric, D, &c_rel, &c_abs);
+    const int64_t n_rt = (S + kFlatTile - 1) / kFlatTile;
+    const int n_qt = (int)((B + kFlatTile - 1) / kFlatTile);
+    int64_t ny = (4 * (int64_t)device_cu_count() + n_rt - 1) / n_rt;  // (flat_launch_filter's grid)
+    ny = ny < 1 ? 1 : ny > n_qt ? n_qt : ny;
+    const dim3 grid((unsigned)n_rt, (unsigned)ny);
+    const bool vec = D % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)mu % 16 == 0);
+    if (vec)
+        hipLaunchKernelGGL(flat_split_filter_kernel<true>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, mu, norms, S,
+                           stride, valid, w.f.qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
+    else
+        hipLaunchKernelGGL(flat_split_filter_kernel<false>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, mu, norms, S,
+                           stride, valid, w.f.qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
+    return launch_status("flat_split_filter_kernel");
+}
+
+// ---- the stages of a search, shared by annlite_flat_search_topk and annlite_flat_search_topk_split: the small-
+// table shortcut, the first exact sample, filter stages over growing row sets, the re-rank of the lists and the route of an overflowed
+// list.  prepare(): what the filter needs from the queries, once per call; filter(S, stride): one filter launch into w.cand / w.cnt
+// against the bounds w.thr. ----
+template <class Prepare, class Filter>
+static int flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
+                              const uint32_t *valid_bits_dev, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, const FlatWs &w,
+                              hipStream_t st, Prepare &&prepare, Filter &&filter) {
+    const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
+    const dim3 qgrid((unsigned)((B + 3) / 4));
+    ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
+    if (N <= kFlatSample) {  // the first sample would be the whole table: exact sums over all rows
+        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
+                           kFlatCap, N, (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 0, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
+        return launch_status("flat_exact_kernel");
+    }
+    int rc = prepare();
+    if (rc != ANNLITE_OK) return rc;
+    // stage 0: the k-th smallest exact distance among kFlatSample rows spread over the table
+    hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap,
+                       kFlatSample, N / kFlatSample, valid_bits_dev, (int)k, 0, 0, 0, w.thr, nullptr, nullptr, w.ovf, w.ovf_total);
+    if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
+    // stages 1 .. n: row sets growing by the same factor (<= kFlatGrowth) up to the whole table; each takes the bound of the one before
+    const double ratio = (double)N / (double)kFlatSample;
+    int n_stages = (int)ceil(log(ratio) / log(kFlatGrowth) - 1e-9);
+    if (n_stages < 1) n_stages = 1;
+    for (int s = 1; s <= n_stages; ++s) {
+        int64_t stride = 1;
+        if (s < n_stages) {
+            const double want = (double)kFlatSample * pow(ratio, (double)s / n_stages);
+            stride = (int64_t)((double)N / want);
+            if (stride <= 1) continue;  // (as large as the table already: leave it to the last stage)
+        }
+        const bool last = s == n_stages;
+        ANNLITE_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)B * 4, st));
+        if ((rc = filter((N + stride - 1) / stride, stride)) != ANNLITE_OK) return rc;
+        // (a list that overflowed before the last stage still holds `cap` valid rows: the k-th of ANY k valid rows is a bound)
+        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt, kFlatCap,
+                           (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr,
+                           out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
+        if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
+    }
+    // queries whose last list overflowed: exact sums over all rows (the other waves leave at once)
+    hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap, N,
+                       (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 1, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
+    return launch_status("flat_exact_kernel");
+}
 
 // ---- cells: workspace, stages, launchers ---------------------------------------------------------------------------------------------
 constexpr int kIvfFlatMaxStages = 16;  // strides annlite_ivf_flat_stages can return (2^31 rows: 19 bits of stride, 5 at a time, + the first)
@@ -544,8 +842,8 @@ extern "C" int annlite_flat_row_norms(const float *vectors_dev, int64_t capacity
     ANNLITE_REQUIRE(capacity >= 0 && D >= 1 && n >= 0 && D <= INT32_MAX, "bad shape");
     if (n == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(vectors_dev && norms_dev, "null device pointer");
-    hipLaunchKernelGGL(flat_norms_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, vectors_dev, (int)D, ids_dev, n,
-                       id_base, capacity, norms_dev);
+    hipLaunchKernelGGL(flat_norms_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, vectors_dev, (int)D, ids_dev,
+                       n, id_base, capacity, (const float *)nullptr, norms_dev);
     return launch_status("flat_norms_kernel");
 }
 
@@ -589,46 +887,88 @@ extern "C" int annlite_flat_search_topk(int metric, const float *queries_dev, in
         return ANNLITE_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
-    const dim3 qgrid((unsigned)((B + 3) / 4));
-    ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
-    if (N <= kFlatSample) {  // the first sample would be the whole table: exact sums over all rows
-        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
-                           kFlatCap, N, (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 0, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
-        return launch_status("flat_exact_kernel");
+    return flat_search_staged(
+        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w, st,
+        [&]() { return annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream); },
+        [&](int64_t S, int64_t stride) {
+            return flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, S, stride, valid_bits_dev, w.qnorm, w.thr, w.cand, w.cnt,
+                                      st);
+        });
+}
+
+extern "C" int annlite_flat_split_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3 && D >= 1 && D <= kSplitMaxDim && c_rel && c_abs, "bad argument (1 <= D <= %lld)",
+                    (long long)kSplitMaxDim);
+    flat_split_slack(metric, D, c_rel, c_abs);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_centred_norms(const float *vectors_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n,
+                                          int64_t id_base, const float *centre_dev, float *norms_dev, void *stream) {
+    ANNLITE_REQUIRE(capacity >= 0 && D >= 1 && n >= 0 && D <= INT32_MAX, "bad shape");
+    if (n == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(vectors_dev && norms_dev && centre_dev, "null device pointer");
+    hipLaunchKernelGGL(flat_norms_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, vectors_dev, (int)D, ids_dev, n,
+                       id_base, capacity, centre_dev, norms_dev);
+    return launch_status("flat_norms_kernel");
+}
+
+extern "C" int annlite_flat_search_split_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    ANNLITE_REQUIRE(N >= 0 && D >= 1 && D <= kSplitMaxDim && B >= 0 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
+                    (long long)kSplitMaxDim);
+    *bytes = (int64_t)flat_split_carve(nullptr, B, D).bytes;
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_filter_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                         const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
+                                         float *query_norms_out_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
+                                         const float *centre_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes,
+                                         void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
+                    "bad shape (D <= %lld)", (long long)kSplitMaxDim);
+    ANNLITE_REQUIRE(!centre_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "a centre is for EUCLIDEAN only");
+    if (B == 0 || N == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
+    const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
     }
-    int rc = annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = flat_split_prepare(queries_dev, B, D, centre_dev, w, st);
     if (rc != ANNLITE_OK) return rc;
-    // stage 0: the k-th smallest exact distance among kFlatSample rows spread over the table
-    hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap,
-                       kFlatSample, N / kFlatSample, valid_bits_dev, (int)k, 0, 0, 0, w.thr, nullptr, nullptr, w.ovf, w.ovf_total);
-    if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
-    // stages 1 .. n: row sets growing by the same factor (<= kFlatGrowth) up to the whole table; each takes the bound of the one before
-    const double ratio = (double)N / (double)kFlatSample;
-    int n_stages = (int)ceil(log(ratio) / log(kFlatGrowth) - 1e-9);
-    if (n_stages < 1) n_stages = 1;
-    for (int s = 1; s <= n_stages; ++s) {
-        int64_t stride = 1;
-        if (s < n_stages) {
-            const double want = (double)kFlatSample * pow(ratio, (double)s / n_stages);
-            stride = (int64_t)((double)N / want);
-            if (stride <= 1) continue;  // (as large as the table already: leave it to the last stage)
-        }
-        const bool last = s == n_stages;
-        ANNLITE_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)B * 4, st));
-        rc = flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev, w.qnorm,
-                                w.thr, w.cand, w.cnt, st);
-        if (rc != ANNLITE_OK) return rc;
-        // (a list that overflowed before the last stage still holds `cap` valid rows: the k-th of ANY k valid rows is a bound)
-        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt, kFlatCap,
-                           (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr,
-                           out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
-        if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
+    if (query_norms_out_dev)
+        ANNLITE_HIP_TRY(hipMemcpyAsync(query_norms_out_dev, w.f.qnorm, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    return flat_split_launch_filter(metric, B, D, vectors_dev, centre_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev, w,
+                                    bounds_dev, cand_dev, count_dev, scores_dev, st);
+}
+
+extern "C" int annlite_flat_search_topk_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                              const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const float *centre_dev,
+                                              int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
+                                              size_t workspace_bytes, void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
+                    "bad shape (1 <= k <= 64, D <= %lld)", (long long)kSplitMaxDim);
+    ANNLITE_REQUIRE(!centre_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "a centre is for EUCLIDEAN only");
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_dev && norms_dev)), "null device pointer");
+    const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
     }
-    // queries whose last list overflowed: exact sums over all rows (the other waves leave at once)
-    hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap, N,
-                       (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 1, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
-    return launch_status("flat_exact_kernel");
+    hipStream_t st = (hipStream_t)stream;
+    return flat_search_staged(
+        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st,
+        [&]() { return flat_split_prepare(queries_dev, B, D, centre_dev, w, st); },
+        [&](int64_t S, int64_t stride) {
+            return flat_split_launch_filter(metric, B, D, vectors_dev, centre_dev, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand,
+                                            w.f.cnt, nullptr, st);
+        });
 }
 
 extern "C" int annlite_flat_overflow_count(const void *workspace_dev, void *stream, int64_t *count) {

@@ -93,6 +93,9 @@ class AnnLite:
         without ``n_subvectors`` --, ignored by the other indexes): how a search that carries a ``filter`` is answered -- by the exact
         filtered search, or by the graph walk that lists only the rows the filter admits (``HnswFlatGpuIndex.search_batch``,
         ``HnswPQGpuIndex.search_batch``)
+    :param flat_filter: ``'f32'`` (default) or ``'bf16x3'``, with ``centre`` (``'mean'``, ``None`` or an array) (kwargs, same channel;
+        the float indexes -- no ``n_subvectors`` --, dropped for the indexes over PQ codes, ignored with ``n_cells > 1``): the filter
+        of the exact float search; ``'bf16x3'`` is the one for data with a large common offset (``FlatGpuIndex``)
     """
 
     def __init__(
@@ -242,6 +245,8 @@ class AnnLite:
             return FlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
         if not (self._vq_codec is None and kw.get('graph')):
             kw.pop('filter_search', None)  # (the graph indexes' option: the other indexes over PQ codes answer a filter exactly)
+        for name in ('flat_filter', 'centre'):  # (the float indexes' options: nothing over PQ codes runs that filter)
+            kw.pop(name, None)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')
         if self._vq_codec is not None:

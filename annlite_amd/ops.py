@@ -857,6 +857,73 @@ def flat_list_counts(workspace: ScanWorkspace, B: int) -> torch.Tensor:
     return out
 
 
+def flat_split_slack(metric: int, dim: int) -> Tuple[np.float32, np.float32]:
+    """``annlite_flat_split_slack``: the ``(c_rel, c_abs)`` the split filter kernel is launched with (host only, needs no GPU)."""
+    c_rel, c_abs = ctypes.c_float(0), ctypes.c_float(0)
+    check(lib().annlite_flat_split_slack(int(metric), int(dim), ctypes.byref(c_rel), ctypes.byref(c_abs)), 'flat_split_slack')
+    return np.float32(c_rel.value), np.float32(c_abs.value)
+
+
+def flat_centred_norms(vectors: torch.Tensor, centre: torch.Tensor, ids: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                       id_base: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``annlite_flat_centred_norms``: ``out[row] = |fl(vectors[row] - centre)|^2`` for the rows ``ids`` (i64) or
+    ``id_base .. id_base + n``."""
+    cap, D = vectors.shape
+    assert centre.dtype == torch.float32 and centre.numel() == D and centre.is_contiguous()
+    if out is None:
+        out = torch.zeros((cap,), dtype=torch.float32, device=vectors.device)
+    cnt = ids.numel() if ids is not None else (cap - id_base if n is None else n)
+    check(lib().annlite_flat_centred_norms(vectors.data_ptr(), cap, D, _ptr(ids), cnt, id_base, centre.data_ptr(), out.data_ptr(),
+                                           stream_ptr()), 'flat_centred_norms')
+    return out
+
+
+def _flat_split_workspace(N: int, D: int, B: int, k: int, dev, workspace: Optional[ScanWorkspace]) -> torch.Tensor:
+    need = ctypes.c_int64(0)
+    check(lib().annlite_flat_search_split_workspace_bytes(N, D, B, k, ctypes.byref(need)), 'flat_search_split_workspace_bytes')
+    return (workspace or ScanWorkspace()).get(int(need.value), dev)
+
+
+def flat_filter_split(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
+                      centre: Optional[torch.Tensor] = None, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+                      stride: int = 1, scores: bool = False, workspace: Optional[ScanWorkspace] = None):
+    """``annlite_flat_filter_split``: ``flat_filter`` with the split-bf16 filter over ``fl(x - centre)``; ``norms`` are
+    ``flat_centred_norms`` with the same centre (``flat_row_norms`` without one).  ``(cand i32 [B, cap], count i32 [B],
+    query_norms f32 [B])`` -- the last as the filter used them -- and, with ``scores=True``, the filter's score of every
+    (query, stage row) pair, f32 [B, ceil(N / stride)]."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    cap = flat_list_capacity()
+    dev = queries.device
+    ws = _flat_split_workspace(N, D, B, 1, dev, workspace)
+    cand = torch.empty((B, cap), dtype=torch.int32, device=dev)
+    count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    qn = torch.empty((B,), dtype=torch.float32, device=dev)
+    sc = torch.full((B, (N + stride - 1) // stride), float('nan'), dtype=torch.float32, device=dev) if scores else None
+    check(lib().annlite_flat_filter_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, stride,
+                                          _ptr(valid_bits), qn.data_ptr(), bounds.data_ptr(), cand.data_ptr(), count.data_ptr(),
+                                          _ptr(centre), _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_filter_split')
+    return (cand, count, qn, sc) if scores else (cand, count, qn)
+
+
+def flat_search_topk_split(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, k: int,
+                           centre: Optional[torch.Tensor] = None, valid_bits: Optional[torch.Tensor] = None,
+                           n_rows: Optional[int] = None, sqrt: bool = False,
+                           workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_flat_search_topk_split``: ``flat_search_topk`` with the split-bf16 filter (``norms``: see ``flat_filter_split``);
+    the same answer, bit for bit.  ``flat_overflow_count`` / ``flat_list_counts`` read this workspace too."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    ws = _flat_split_workspace(N, D, B, k, dev, workspace)
+    od = torch.empty((B, k), dtype=torch.float32, device=dev)
+    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
+    check(lib().annlite_flat_search_topk_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N,
+                                               _ptr(valid_bits), _ptr(centre), int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
+                                               ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_search_topk_split')
+    return od, oi
+
+
 # ---------------------------------------------------------------------------------------------- cells over float vectors
 def ivf_flat_stages(max_probed_rows: int) -> List[int]:
     """``annlite_ivf_flat_stages``: the strides ``ivf_flat_search_topk`` uses for queries that probe at most ``max_probed_rows``

@@ -535,6 +535,31 @@ ANNLITE_API int annlite_flat_overflow_count(const void *workspace_dev, void *str
  * Undefined after a search that ran no filter.  For measurements; no reference counterpart. */
 ANNLITE_API int annlite_flat_list_counts(const void *workspace_dev, int64_t B, int32_t *count_dev, void *stream);
 
+/* The same search with the SPLIT filter ("split filter"): the filter contracts c = fl(x - centre) (centre f32 [D];
+ * NULL: c = x) carried as two bf16 numbers, c_h + c_l, on three bf16 MFMAs; its slack is relative to |x - centre|^2 + |q - centre|^2, so
+ * data with a large common offset no longer passes every row.  The exact stage and therefore the answer are annlite_flat_search_topk's,
+ * bit for bit.  1 <= D <= 32768.  A centre is taken for EUCLIDEAN only (another metric with one: an error).  No reference counterpart. */
+/* The split filter's (c_rel, c_abs) (host only). */
+ANNLITE_API int annlite_flat_split_slack(int metric, int64_t D, float *c_rel, float *c_abs);
+/* annlite_flat_row_norms over fl(vectors[row] - centre): the norms column the split filter reads when it has a centre. */
+ANNLITE_API int annlite_flat_centred_norms(const float *vectors_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n,
+                               int64_t id_base, const float *centre_dev, float *norms_dev, void *stream);
+ANNLITE_API int annlite_flat_search_split_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes);
+/* annlite_flat_filter with the split filter.  norms_dev: annlite_flat_centred_norms with the same centre (annlite_flat_row_norms without
+ * one).  The queries are centred and split into the workspace (annlite_flat_search_split_workspace_bytes of the same B, D) by this call;
+ * query_norms_out_dev (may be NULL) f32 [B] receives |fl(q - centre)|^2 as the filter used it.  scores_dev (may be NULL; tests and
+ * measurements) f32 [B][ceil(N / stride)] receives the filter's score v of every (query, stage row) pair, valid or not. */
+ANNLITE_API int annlite_flat_filter_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                              const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
+                              float *query_norms_out_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
+                              const float *centre_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* annlite_flat_search_topk with the split filter: the same stages, lists, capacity and overflow route (annlite_flat_overflow_count and
+ * annlite_flat_list_counts read this workspace too).  norms_dev as for annlite_flat_filter_split. */
+ANNLITE_API int annlite_flat_search_topk_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                   const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const float *centre_dev, int64_t k,
+                                   int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
+                                   void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Cells over float vectors: the exact search above restricted to the rows of each query's P probed cells.
  * replaces: the reference's n_cells > 1 structure over its default float index -- AnnLite._cell_selection's consumers, one float

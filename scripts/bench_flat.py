@@ -4,10 +4,13 @@
 
     python scripts/bench_flat.py                       # 1M x 128, 1024 queries, k = 10, euclidean
     python scripts/bench_flat.py --rows 10000000
+    python scripts/bench_flat.py --filter both         # the f32 and the split-bf16 filter, round by round: one JSON line each
+    python scripts/bench_flat.py --filter both --offset 1000   # ... on data with a large common offset
 
 Baseline: |x|^2 - 2 q x^T by torch.addmm over row chunks (no B x N matrix exists), torch.topk per chunk, one merge.
-Filter time: the full-table filter launch (annlite_flat_filter with the bounds the search would hand it) between HIP events;
-its work is 2 B N D FLOP against the 157.3 TFLOP/s fp32 matrix roof.
+Filter time: the full-table filter launch (annlite_flat_filter with the bounds the search would hand it; for bf16x3
+annlite_flat_filter_split, which also centres and splits the queries) between HIP events; its work is 2 B N D FLOP against the
+157.3 TFLOP/s fp32 matrix roof -- the yardstick of both filters, whatever instruction they issue.
 """
 import argparse
 import json
@@ -33,6 +36,8 @@ def main():
     ap.add_argument('--steps', type=int, default=10, help='batches per round and path')
     ap.add_argument('--truth-queries', type=int, default=32)
     ap.add_argument('--chunk', type=int, default=65536, help='rows per chunk of the torch baseline')
+    ap.add_argument('--filter', default='f32', choices=['f32', 'bf16x3', 'both'], help="FlatGpuIndex(flat_filter=...); 'both': alternating")
+    ap.add_argument('--offset', type=float, default=0.0, help='added to every coordinate of rows and queries')
     args = ap.parse_args()
 
     import torch
@@ -45,17 +50,23 @@ def main():
     N, D, B, k = args.rows, args.dim, args.batch, args.k
     metric = Metric.from_string(args.metric)
     gen = torch.Generator(device=dev).manual_seed(0)
-    idx = FlatGpuIndex(D, metric=metric, initial_size=N)
+    modes = ['f32', 'bf16x3'] if args.filter == 'both' else [args.filter]
+    # ONE index for both filters: built with the split filter's columns when that mode runs (centre = the first batch's mean), and
+    # `flat_filter` switched between rounds -- the f32 path reads nothing the other mode added
+    idx = FlatGpuIndex(D, metric=metric, initial_size=N, flat_filter=modes[-1])
     step = 1 << 20
     for r0 in range(0, N, step):  # (generated on the device: no 5 GB host array)
         n = min(step, N - r0)
-        idx.add_with_ids(torch.randn((n, D), generator=gen, device=dev), torch.arange(r0, r0 + n, device=dev))
-    q = torch.randn((B, D), generator=gen, device=dev)
+        idx.add_with_ids(torch.randn((n, D), generator=gen, device=dev) + args.offset, torch.arange(r0, r0 + n, device=dev))
+    q = torch.randn((B, D), generator=gen, device=dev) + args.offset
     x = idx._vectors[:N]
     l2 = metric == Metric.EUCLIDEAN
 
-    def ours():
-        return idx.search_batch(q, limit=k)
+    def ours(mode):
+        def run():
+            idx.flat_filter = mode
+            return idx.search_batch(q, limit=k)
+        return run
 
     xn = (x * x).sum(1) if l2 else None
 
@@ -92,13 +103,18 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / args.steps, out
 
-    ms_ours, ms_base = [], []
+    ms_ours, ms_base, answers, overflowed = {m: [] for m in modes}, [], {}, {}
     for _ in range(args.rounds):
-        t, (d, i) = timed(ours)
-        ms_ours.append(t)
+        for m in modes:
+            t, answers[m] = timed(ours(m))
+            ms_ours[m].append(t)
+            assert idx.last_flat_filter == m
+            overflowed[m] = idx.last_overflowed
         t, (bd, bi) = timed(baseline)
         ms_base.append(t)
-    overflowed = idx.last_overflowed
+    for m in modes[1:]:  # the filters differ, the answer does not
+        assert torch.equal(answers[m][0], answers[modes[0]][0]) and torch.equal(answers[m][1], answers[modes[0]][1])
+    i = answers[modes[0]][1]
 
     # the full-table filter alone, with the bound the last stage works with: the k-th exact distance of the result itself is the
     # tightest the search can reach; the bound it really has (from 1/13 .. 1/32 of the table) lets a few hundred rows through
@@ -106,23 +122,34 @@ def main():
     ratio = N / 4096.0
     n_stages = max(1, int(np.ceil(np.log(max(ratio, 1.0001)) / np.log(32.0) - 1e-9)))
     stride = max(1, int(ratio ** (1.0 / n_stages)))  # the last stage's bound comes from every stride-th row
-    sub = FlatGpuIndex(D, metric=metric, initial_size=(N + stride - 1) // stride)
+    sub = FlatGpuIndex(D, metric=metric, initial_size=(N + stride - 1) // stride, flat_filter=modes[-1])
     sub.add_with_ids(x[::stride].contiguous(), torch.arange((N + stride - 1) // stride, device=dev))
     sd = sub.search_batch(q, limit=k)[0][:, k - 1]
     bound = ((sd * sd) if l2 else sd).contiguous()
     del sub
     qn = ops.flat_row_norms(qq)
-    f_ms = []
-    for _ in range(args.rounds):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        cand, count = ops.flat_filter(int(metric), qq, idx._vectors, idx._norms, bound, valid_bits=idx._valid, n_rows=N, query_norms=qn)
-        e1.record()
-        torch.cuda.synchronize()
-        f_ms.append(e0.elapsed_time(e1))
-    filter_ms = statistics.median(f_ms)
-    count = count.cpu().numpy()
+    centred = idx._centre_dev is not None
+
+    def filter_once(mode):
+        if mode == 'f32':
+            return ops.flat_filter(int(metric), qq, idx._vectors, idx._norms, bound, valid_bits=idx._valid, n_rows=N, query_norms=qn)[:2]
+        return ops.flat_filter_split(int(metric), qq, idx._vectors, idx._cnorms if centred else idx._norms, bound,
+                                     centre=idx._centre_dev, valid_bits=idx._valid, n_rows=N, workspace=idx._ws)[:2]
+
+    filter_ms, counts = {}, {}
+    for m in modes:
+        filter_once(m)
+        f_ms = []
+        for _ in range(args.rounds):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            cand, count = filter_once(m)
+            e1.record()
+            torch.cuda.synchronize()
+            f_ms.append(e0.elapsed_time(e1))
+        filter_ms[m] = statistics.median(f_ms)
+        counts[m] = count.cpu().numpy()
 
     # recall@k against float64 on a subset of the queries
     nt = min(args.truth_queries, B)
@@ -143,19 +170,23 @@ def main():
     recall = float(np.mean([len(set(got[b]) & set(truth[b])) / k for b in range(nt)]))
     recall_base = float(np.mean([len(set(base_ids[b]) & set(truth[b])) / k for b in range(nt)]))
 
-    med, med_b = statistics.median(ms_ours), statistics.median(ms_base)
+    med_b = statistics.median(ms_base)
     flop = 2.0 * B * N * D
-    print(json.dumps({
-        'bench': 'flat_f32', 'rows': N, 'dim': D, 'batch': B, 'k': k, 'metric': args.metric, 'rounds': args.rounds, 'steps': args.steps,
-        'ms_per_batch': round(med, 4), 'qps': round(B / med * 1e3, 1), 'ms_rounds': [round(v, 4) for v in ms_ours],
-        'baseline_torch_ms_per_batch': round(med_b, 4), 'baseline_torch_qps': round(B / med_b * 1e3, 1),
-        'baseline_ms_rounds': [round(v, 4) for v in ms_base], 'speedup_vs_torch': round(med_b / med, 3),
-        'filter_ms': round(filter_ms, 4), 'filter_tflops': round(flop / filter_ms / 1e9, 2),
-        'filter_fraction_of_fp32_roof': round(flop / filter_ms / 1e9 / ROOF_TFLOPS, 4), 'roof_ms': round(flop / ROOF_TFLOPS / 1e9, 4),
-        'filter_bound_rows_stride': stride, 'candidates_mean': round(float(count.mean()), 1), 'candidates_max': int(count.max()),
-        'overflowed_queries': int(overflowed), 'recall_at_k_vs_float64': recall, 'baseline_recall_at_k_vs_float64': recall_base,
-        'truth_queries': nt, 'device': torch.cuda.get_device_name(0),
-    }))
+    for m in modes:
+        med, f, count = statistics.median(ms_ours[m]), filter_ms[m], counts[m]
+        print(json.dumps({
+            'bench': 'flat_f32', 'flat_filter': m, 'filters_in_this_run': modes, 'offset': args.offset,
+            'centred': bool(centred and m == 'bf16x3'), 'rows': N, 'dim': D, 'batch': B, 'k': k, 'metric': args.metric,
+            'rounds': args.rounds, 'steps': args.steps,
+            'ms_per_batch': round(med, 4), 'qps': round(B / med * 1e3, 1), 'ms_rounds': [round(v, 4) for v in ms_ours[m]],
+            'baseline_torch_ms_per_batch': round(med_b, 4), 'baseline_torch_qps': round(B / med_b * 1e3, 1),
+            'baseline_ms_rounds': [round(v, 4) for v in ms_base], 'speedup_vs_torch': round(med_b / med, 3),
+            'filter_ms': round(f, 4), 'filter_tflops': round(flop / f / 1e9, 2),
+            'filter_fraction_of_fp32_roof': round(flop / f / 1e9 / ROOF_TFLOPS, 4), 'roof_ms': round(flop / ROOF_TFLOPS / 1e9, 4),
+            'filter_bound_rows_stride': stride, 'candidates_mean': round(float(count.mean()), 1), 'candidates_max': int(count.max()),
+            'overflowed_queries': int(overflowed[m]), 'recall_at_k_vs_float64': recall, 'baseline_recall_at_k_vs_float64': recall_base,
+            'truth_queries': nt, 'device': torch.cuda.get_device_name(0),
+        }), flush=True)
 
 
 if __name__ == '__main__':
