@@ -85,6 +85,10 @@ namespace annlite {
 #define ANNLITE_Q8_SPLIT_BIAS 1  // the split step's first phase starts its byte sums from the slots' BIAS bytes and tests bit 7 (q8_st_bound;
                                  // 0: filter words and the round-8 test -- the A/B build of scripts/build_variant.sh)
 #endif
+#ifndef ANNLITE_Q8_SPLIT_UNROLL
+#define ANNLITE_Q8_SPLIT_UNROLL 1  // the split step's loop runs two blocks per trip, the row registers in swapped roles (0: one block per trip
+                                   // and a copy of the next rows over the current ones in every step -- the A/B build)
+#endif
 
 // Q8Cfg: entries are clipped at QMAX (M * QMAX <= 240: a byte sum never carries); a slot without a bound yet
 // ("open": nothing seeded it) clips at QOPEN, M * QOPEN <= 112, so that T = 127 passes every row.
@@ -1723,11 +1727,17 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
             // start values of the first phase's byte sums.  The rare parts, which test full sums, load the filter words over them for as long
             // as they run: the loop never holds both sets.
             constexpr bool BIAS = HS > 0 && ANNLITE_Q8_SPLIT_BIAS != 0;
+            // Split step: what its common trip reads or writes in LDS beside the table -- the block counter, the bias words, the wave's
+            // survivor ring -- is addressed from ONE VGPR holding lds.shq, with the area's offset as the instruction's immediate.  (Every
+            // address is lds.shq plus a compile-time constant.  As separate loop invariants they took an SGPR each, and at the kernel's
+            // 100 SGPRs the allocator kept them in VGPR lanes: a v_readlane and a v_mov in front of each use, every step.)
+            uint32_t shq_v = lds.shq;
+            if constexpr (HS > 0) asm volatile("" : "+v"(shq_v));
             auto load_stepw = [&](uint32_t (&t)[NF]) {
                 if constexpr (BIAS) {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const u32x4 v = *(volatile ANNLITE_LDS u32x4 *)(uintptr_t)(lds.qmap + 16u * (uint32_t)h);
+                        const u32x4 v = *(volatile ANNLITE_LDS u32x4 *)(uintptr_t)(shq_v + (lds.qmap - lds.shq) + 16u * (uint32_t)h);
                         t[4 * h + 0] = v.x, t[4 * h + 1] = v.y, t[4 * h + 2] = v.z, t[4 * h + 3] = v.w;
                     }
                 } else load_thw(t);
@@ -1921,9 +1931,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
             };
             // the survivor ring of this wave: entries [sv_h, sv_h + sv_c) mod kSplitRing (sv_h is 0 or 64: the ring is taken 64 at a time)
             const uint32_t sv_ad = lds.qmap + 128u + (uint32_t)wave * (uint32_t)(kSplitRing * 4);
+            const uint32_t sv_wave = (uint32_t)wave * (uint32_t)(kSplitRing * 4);  // (the step's store: shq_v + sv_wave + the ring's constant offset)
             constexpr int HS1 = HS > 0 ? HS : 1;  // (the lambdas below are compiled for HS = 0 too, and never called there)
             uint32_t sv_h = 0, sv_c = 0;
             uint32_t n_rows_a = 0, n_surv = 0, n_tail = 0, n_fb = 0;  // (ANNLITE_DEBUG_COUNTERS)
+            // (non-zero with the counters on; a 32-bit scalar for s_cmp: as a bool it went through a VGPR and a v_cmp per step)
+            uint32_t dbg_on = (uint32_t)(uintptr_t)a.dbg | (uint32_t)((unsigned long long)(uintptr_t)a.dbg >> 32);
+            if constexpr (HS > 0) asm volatile("" : "+s"(dbg_on));
             // The first phase's look-up stream runs ACROSS the step boundary: its landing ring `ring` enters a step holding the step's
             // first PD look-ups in flight, and the slots its last look-ups free take the NEXT block's first PD (from cnext, fetched a
             // step ahead).  The drain, the pass test, the vote, the survivor store and the loop top then run with look-ups in flight
@@ -1940,8 +1954,8 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                 uint32_t ad = 0;
                 static_for<0, PD>([&](auto I) { split_fetch(ring[decltype(I)::value], cc, ad, I); });
             };
-            // the first phase of the block in ccur (its first PD look-ups already in the ring), the next block's first PD issued behind it
-            auto split_first = [&](auto &acc) {  // (generic: instantiated by HS > 0 only)
+            // the first phase of the block in cc (its first PD look-ups already in the ring), the next block's (cn) first PD issued behind it
+            auto split_first = [&](auto &acc, const auto &cc, const auto &cn) {  // (generic: instantiated by HS > 0 only)
                 constexpr int TOT = 2 * HS1;
                 u32x4 nr[PD];
                 uint32_t ad = 0, an = 0;
@@ -1958,37 +1972,43 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                         if constexpr (BIAS) acc[i] = ring[i % PD] + (u32x4){thw[4 * i], thw[4 * i + 1], thw[4 * i + 2], thw[4 * i + 3]};
                         else acc[i] = ring[i % PD];
                     } else acc[i % 2] += ring[i % PD];
-                    if constexpr (j < TOT) split_fetch(ring[j % PD], ccur, ad, std::integral_constant<int, j>{});
-                    else split_fetch(nr[j - TOT], cnext, an, std::integral_constant<int, j - TOT>{});
+                    if constexpr (j < TOT) split_fetch(ring[j % PD], cc, ad, std::integral_constant<int, j>{});
+                    else split_fetch(nr[j - TOT], cn, an, std::integral_constant<int, j - TOT>{});
                 });
 #pragma unroll
                 for (int i = 0; i < PD; ++i) ring[i] = nr[i];
             };
             // first phase of a step (acc: the byte sums of HS sub-spaces): true when more than q8_split_fallback rows survive it (the step
             // finishes in place: split_finish), else the survivors are queued
-            auto split_head = [&](auto vmask, uint32_t row0, u32x4 (&acc)[2]) -> bool {  // (generic: instantiated by HS > 0 only)
-                split_first(acc);
+            auto split_head = [&](auto vmask, uint32_t row0, u32x4 (&acc)[2], const auto &cc, const auto &cn) -> bool {  // (generic: instantiated by HS > 0 only)
+                split_first(acc, cc, cn);
                 bool pass;
                 if constexpr (BIAS) pass = split_pass1(acc);
                 else pass = split_pass(acc);
                 const unsigned long long alive = __ballot(pass) & vmask;
-                const uint32_t n = (uint32_t)__popcll(alive);
-                if (a.dbg) n_rows_a += (uint32_t)__popcll(vmask);
+                uint32_t n = (uint32_t)__popcll(alive);
+                asm("" : "+s"(n));  // (a 32-bit scalar: left to the optimizer, the compares below were made on the 64-bit count, in VALU)
+                uint32_t dbg_now = dbg_on;
+                asm volatile("" : "+s"(dbg_now));  // (compared here: hoisted, the condition came back per step through a v_cndmask and a v_cmp)
+                if (dbg_now != 0u) {  // (a branch, not a select: off, the counter costs the step a scalar compare)
+                    asm volatile("");
+                    n_rows_a += (uint32_t)__popcll(vmask);
+                }
                 if (n > (uint32_t)q8_split_fallback<HS1>()) return true;
                 if (n) {
                     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(alive >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)alive, 0u));
                     if (__builtin_amdgcn_inverse_ballot_w64(alive))
-                        ldsv_st<uint32_t>(sv_ad + 4u * ((sv_h + sv_c + rank) & (uint32_t)(kSplitRing - 1)), row0 + (uint32_t)lane);
+                        ldsv_st<uint32_t>(shq_v + sv_wave + 4u * ((sv_h + sv_c + rank) & (uint32_t)(kSplitRing - 1)) + (lds.qmap + 128u - lds.shq), row0 + (uint32_t)lane);
                     sv_c += n;
                     n_surv += n;
                 }
                 return false;
             };
-            // the rows of the block in ccur passing the full test (sub-spaces HS .. 15 added to acc)
-            auto split_finish = [&](auto vmask, u32x4 (&acc)[2]) -> unsigned long long {  // (generic: instantiated by HS > 0 only)
+            // the rows of the block in cc passing the full test (sub-spaces HS .. 15 added to acc)
+            auto split_finish = [&](auto vmask, u32x4 (&acc)[2], const auto &cc) -> unsigned long long {  // (generic: instantiated by HS > 0 only)
                 uint32_t sp = (uint32_t)s;
                 asm volatile("" : "+v"(sp));
-                split_sums(ccur, std::integral_constant<int, HS1>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, ANNLITE_Q8_SPLIT_DEPTH>{}, std::true_type{}, sp, acc);
+                split_sums(cc, std::integral_constant<int, HS1>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, ANNLITE_Q8_SPLIT_DEPTH>{}, std::true_type{}, sp, acc);
                 ++n_fb;
                 return __ballot(split_pass(acc)) & vmask;
             };
@@ -1999,6 +2019,34 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                 if (row >= n_rows) row = n_rows - 1;
                 if constexpr (WIDE) return ((const uint32_t __attribute__((address_space(1))) *)valid_v)[row >> 5];
                 else return valid[row >> 5];
+            };
+            // Split step: a block's 64 rows are consecutive, so the step fetches them from a SCALAR base (codes + 16 rb, made next to blk_row
+            // in SALU for every block: interleaved slices are not contiguous) plus a lane offset, and the validity word from valid + rb / 8
+            // plus (lane >> 5) * 4 -- both still vector-memory loads (vmcnt; a scalar load returns out of order in lgkmcnt, among the
+            // look-ups).  load_row's clamp to the table's last row is one v_min_u32 of the lane constant with a scalar per load: rb =
+            // min(r, n_rows - 1), a lane reads row rb + min(lane, n_rows - 1 - rb) and the validity word of row rb + min(lane & 32,
+            // (n_rows - 1 - rb) & ~31) -- the word of a row < n_rows; the lanes that differ from the clamped row's word are past the table
+            // and masked by vmask.  (The min also puts the offset's zero-extension into the step's own basic block: as loop invariants
+            // the compiler kept the offsets as 64-bit pairs and added the base per lane, v_lshl_add_u64 instead of an SGPR-base load;
+            // taking the clamp on a uniform branch was tried and costs a v_mov per offset on the common side for the same reason.)
+            uint32_t lane16 = (uint32_t)lane_pin * 16u, lane_w4 = ((uint32_t)lane_pin >> 5) * 4u, lane_bit = 1u << (lane_pin & 31);
+            if constexpr (HS > 0) asm volatile("" : "+v"(lane16), "+v"(lane_w4), "+v"(lane_bit));  // (kept in registers, not made again per step)
+            auto load_block = [&](uint32_t r, uint32_t (&c)[CW], uint32_t &v) {  // r: a block's first row (a multiple of 64, or past the table)
+                if constexpr (CW != 4 || ANNLITE_Q8_EXP == 3) {
+                    load_row(r + (uint32_t)lane, c);
+                    v = load_valid(r + (uint32_t)lane);
+                } else {
+                    const uint32_t last = n_rows - 1u;
+                    const uint32_t rb = r < last ? r : last, room = last - rb;
+                    const uint32_t lim16 = room < 64u ? room * 16u : 63u * 16u, limw = (room >> 5) != 0u ? 4u : 0u;
+                    unsigned long long cb = (unsigned long long)(uintptr_t)codes32 + (unsigned long long)rb * 16u;
+                    unsigned long long vb = (unsigned long long)(uintptr_t)valid + (unsigned long long)(rb >> 5) * 4u;
+                    asm("" : "+s"(cb), "+s"(vb));
+                    const uint32_t o16 = lane16 < lim16 ? lane16 : lim16, ow4 = lane_w4 < limw ? lane_w4 : limw;
+                    const u32x4 w = *(const u32x4 __attribute__((address_space(1))) *)(cb + o16);
+                    if (valid) v = *(const uint32_t __attribute__((address_space(1))) *)(vb + ow4);
+                    c[0] = w.x, c[1] = w.y, c[2] = w.z, c[3] = w.w;
+                }
             };
             // The code bytes (and validity word) of a lane's row are fetched ONE STEP AHEAD: issued at the top of a step for
             // the next block, picked up at the top of that one; the number of the block after that is drawn in between.
@@ -2034,7 +2082,13 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                 const bool on = (uint32_t)lane < nb;
                 const uint32_t rid = ldsv<uint32_t>(sv_ad + 4u * ((sv_h + (on ? (uint32_t)lane : 0u)) & (uint32_t)(kSplitRing - 1)));
                 uint32_t cb[CW];
-                load_row(rid, cb);
+                if constexpr (CW != 4 || ANNLITE_Q8_EXP == 3) load_row(rid, cb);
+                else {  // (load_row, clamped to the item's rows instead of the table's: a survivor's row is < s_end <= n_rows, and s_end sits in an SGPR
+                        // for every step's vmask -- n_rows does not any more, and load_row's compare read it from the kernarg segment here)
+                    const uint32_t rr = rid < s_end - 1u ? rid : s_end - 1u;
+                    const u32x4 w = *(const u32x4 __attribute__((address_space(1))) *)((const uint32_t __attribute__((address_space(1))) *)(uintptr_t)codes32 + (int64_t)rr * CW);
+                    cb[0] = w.x, cb[1] = w.y, cb[2] = w.z, cb[3] = w.w;
+                }
                 uint32_t sp = (uint32_t)s;
                 asm volatile("" : "+v"(sp));
                 const uint32_t r = (sp - rid) & 15u;
@@ -2078,6 +2132,72 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     asm volatile("" ::"v"(cnext[0]), "v"(cnext[1]), "v"(cnext[2]), "v"(cnext[3]), "v"(vnext));
                     split_prefix(cnext);  // (the epoch's first block; across an epoch end the table may have been rebuilt)
                 }
+                // Split step: one block per call -- the block's rows in (cc, vc), fetched a step ahead; the next block's land in (cn, vn).
+                // The loop runs TWO blocks per trip with the two register sets in swapped roles, so that no step copies the next rows
+                // over the current ones; every block still has its own draw and epoch-end test, and an epoch that ends after the
+                // first half of a trip moves the rows fetched ahead to where the next epoch expects them (once per epoch).
+                auto split_step = [&](auto &cc, auto &cn, uint32_t &vc, uint32_t &vn) {  // (generic: instantiated by HS > 0 only)
+                    const uint32_t row0 = blk_row(b_cur);  // (< s_end: b_cur < n_blocks)
+                    asm volatile("" : "=v"(pend));  // (lane 0 draws; the other lanes' value is never read: no v_mov 0 per step)
+                    if (lane == 0) pend = lds_add_u32(shq_v + (lds.blk_ctr() - lds.shq), lane_bit);  // (lane 0's lane_bit = 1: no v_mov of the addend)
+                    load_block(blk_row(b_nxt), cn, vn);  // (past the slice at its end: clamped, unused)
+                    unsigned long long vmask = ~0ull;
+                    if (s_end - row0 < 64u) vmask = (1ull << (s_end - row0)) - 1ull;
+                    if (valid) vmask &= __ballot((vc & lane_bit) != 0u);
+                    u32x4 acc[2];
+                    const bool fb = split_head(vmask, row0, acc, cc, cn);
+                    if (fb || sv_c >= 64u) {  // (rare: the next block's first look-ups are dropped here and issued again below)
+                        if constexpr (BIAS) {
+                            if (fb) {  // finishing in place: the bias out of the first-phase sums (no borrow: every byte holds S_H + bias)
+#pragma unroll
+                                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                                    for (int e = 0; e < 4; ++e) acc[h][e] -= thw[4 * h + e];
+                            }
+                            asm volatile("" ::: "memory");
+                            load_thw(thw);  // (full sums reach 240: the filter words and their test)
+                        }
+                        if (fb) {
+                            const unsigned long long rem = split_finish(vmask, acc, cc);
+                            if (rem && !(a.dbg_skip & 4)) push_rows(rem, row0 + (uint32_t)lane);
+                        }
+                        if (sv_c >= 64u) {
+                            split_tail(64u);
+                            sv_h ^= 64u;
+                            sv_c -= 64u;
+                        }
+                        asm volatile("" ::: "memory");
+                        split_prefix(cn);
+                        if constexpr (BIAS) load_stepw(thw);
+                    }
+                    // pick up the workgroup's bounds every 2nd step (every 8th where a work item scans >= 500k rows: ScanArgs::q8_thw_mask)
+                    if ((it_no & thw_mask) == thw_mask) {
+                        asm volatile("" ::: "memory");
+                        load_stepw(thw);
+                    }
+                    b_cur = b_nxt;
+                    b_nxt = (uint32_t)__builtin_amdgcn_readfirstlane((int)pend);
+                    ++it_no;
+                };
+                if constexpr (HS > 0 && ANNLITE_Q8_SPLIT_UNROLL != 0) {
+                    while (b_cur < end_blk) {
+                        split_step(cnext, ccur, vnext, vcur);
+                        if (b_cur >= end_blk) {
+#pragma unroll
+                            for (int i = 0; i < CW; ++i) cnext[i] = ccur[i];
+                            vnext = vcur;
+                            break;
+                        }
+                        split_step(ccur, cnext, vcur, vnext);
+                    }
+                } else if constexpr (HS > 0) {
+                    while (b_cur < end_blk) {
+#pragma unroll
+                        for (int i = 0; i < CW; ++i) ccur[i] = cnext[i];
+                        vcur = vnext;
+                        split_step(ccur, cnext, vcur, vnext);
+                    }
+                } else
                 for (; b_cur < end_blk; ++it_no) {
                     const uint32_t row0 = blk_row(b_cur);  // (< s_end: b_cur < n_blocks)
                     pend = draw();
@@ -2117,34 +2237,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                     if (valid) vmask &= __ballot((vcur >> (lane & 31)) & 1u);
                     uint32_t sums[NF];
                     unsigned long long rem;
-                    if constexpr (HS > 0) {
-                        u32x4 acc[2];
-                        const bool fb = split_head(vmask, row0, acc);
-                        if (fb || sv_c >= 64u) {  // (rare: the next block's first look-ups are dropped here and issued again below)
-                            if constexpr (BIAS) {
-                                if (fb) {  // finishing in place: the bias out of the first-phase sums (no borrow: every byte holds S_H + bias)
-#pragma unroll
-                                    for (int h = 0; h < 2; ++h)
-#pragma unroll
-                                        for (int e = 0; e < 4; ++e) acc[h][e] -= thw[4 * h + e];
-                                }
-                                asm volatile("" ::: "memory");
-                                load_thw(thw);  // (full sums reach 240: the filter words and their test)
-                            }
-                            if (fb) {
-                                rem = split_finish(vmask, acc);
-                                if (rem && !(a.dbg_skip & 4)) push_rows(rem, row0 + (uint32_t)lane);
-                            }
-                            if (sv_c >= 64u) {
-                                split_tail(64u);
-                                sv_h ^= 64u;
-                                sv_c -= 64u;
-                            }
-                            asm volatile("" ::: "memory");
-                            split_prefix(cnext);
-                            if constexpr (BIAS) load_stepw(thw);
-                        }
-                    } else {
+                    {
                         make_addr(ccur);
                         row_sums(ccur, sums);
                         // any (query, lane) with S <= T ?
@@ -2162,8 +2255,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void adc_scan_q8_kernel(const Scan
                         rem = __ballot(anyv != 0) & vmask;
                     }
                     if constexpr (ROWQ) {
-                        if constexpr (HS == 0)  // (the split step pushes its rows above)
-                            if (rem && !(a.dbg_skip & 4)) push_rows(rem, row0 + (uint32_t)lane);
+                        if (rem && !(a.dbg_skip & 4)) push_rows(rem, row0 + (uint32_t)lane);
                     } else
                     if (rem && !(a.dbg_skip & 4)) {
                         ++n_slow;
