@@ -28,16 +28,16 @@ import torch
 
 from ... import ops
 from ...enums import Metric
+from .filter_walk import FilterWalkMixin
 from .flat_gpu import FlatGpuIndex
 from .row_store import empty_answer, like_input, ranked_answer
 
 
-class HnswFlatGpuIndex(FlatGpuIndex):
+class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
     FORMAT = 'annlite_amd.HnswFlatGpuIndex/1'
     ALSO_LOADS = (FlatGpuIndex.FORMAT,)  # (rows without links: the graph is rebuilt from them)
     MAX_EF = 256                         # the walk's list: four registers per lane
     MAX_DIM = 2048
-    FILTER_SEARCH = ('exact', 'graph')
     # DESIGN.md section 3.8, table "filtered walk" (1M x 128): the smallest measured share of admitted rows at which the filtered walk
     # is faster than the exact filtered search AND within 0.03 of the unfiltered walk's recall@10 (at 0.05 a sixth of the queries is
     # answered again exactly and the two paths are level: 211 k against 220 k q/s)
@@ -53,17 +53,14 @@ class HnswFlatGpuIndex(FlatGpuIndex):
             raise ValueError(f'max_connection={max_connection}: the GPU graph holds 2 * max_connection <= 32 links per node (2 ... 16)')
         if not 1 <= int(dim) <= self.MAX_DIM:
             raise ValueError(f'dim={dim}: the float graph takes 1 <= dim <= {self.MAX_DIM}')
-        if filter_search not in self.FILTER_SEARCH:
-            raise ValueError(f"filter_search={filter_search!r}: 'exact' (the parent's exact filtered search) or 'graph' (the filtered walk)")
+        self._check_filter_search(filter_search, "the parent's exact filtered search")
         super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
         self.ef_construction = int(ef_construction)  # hnsw/index.py:66-69
         self.ef_search = int(ef_search)
         self.max_connection = int(max_connection)
         self.seed = int(seed)  # (kept for the reference's signature: level 0 only -- no random level is drawn)
         self.build = 'gpu'
-        self.filter_search = filter_search
-        self.last_filter_path = None     # 'graph' / 'exact': how the last search that carried `indices` was answered
-        self.last_filter_reanswered = 0  # ... and how many of its queries the exact search answered again (see search_batch)
+        self._init_filter_search(filter_search)
         self._gg = None  # GpuLevel0GraphF32
         if index_file:
             self.load(index_file)
@@ -125,44 +122,16 @@ class HnswFlatGpuIndex(FlatGpuIndex):
     def search_exhaustive(self, x, limit: int = 10, **kw):
         return super().search_batch(x, limit=limit, **kw)
 
-    def _search_filtered_on_graph(self, x, k: int, ef: int, indices, forced: bool):
-        """The filtered walk, or None where the exact search is to answer (no admitted row; the auto rule's selectivity floor).
-        ``admit = valid & filter``; with ``s`` the admitted share of the rows the routing list gets ``ef / s`` places (at most 256), so
-        that about ``ef`` of the rows it keeps are admitted ones, and the result list ``ef``."""
-        admit = self._filter_bits(indices)
-        n_rows = self._n_rows
-        n_adm = int(self._unpack_bits(admit, n_rows).sum().item())
-        if n_adm == 0 or (not forced and n_adm < self.FILTER_WALK_MIN_FRACTION * n_rows):
-            return None
-        is_np = not isinstance(x, torch.Tensor)
-        q = self._pre(x)
-        B = q.shape[0]
-        self._overflowed = 0
-        self.last_flat_filter = None
-        self.last_filter_path = 'graph'
-        if B == 0:
-            return like_input(is_np, *empty_answer(B, k, q.device))
-        ef_route = min(self.MAX_EF, max(ef, -(-ef * n_rows // n_adm)))
+    # the filtered walk's two hooks (filter_walk.FilterWalkMixin)
+    def _filter_walk(self, q, ef_route: int, ef: int, admit, reach):
         gg = self._gg
-        reach = torch.empty((B,), dtype=torch.float32, device=q.device)
-        cand, cand_d = ops.graph_f32_search_admit(int(self.metric), q.contiguous(), self._vectors, gg.links, gg.seeds(), ef_route, ef,
-                                                  admit, n_rows=gg.n, route_worst=reach)
+        return ops.graph_f32_search_admit(int(self.metric), q.contiguous(), self._vectors, gg.links, gg.seeds(), ef_route, ef, admit,
+                                          n_rows=gg.n, route_worst=reach)
+
+    def _filter_rank(self, x, q, cand, cand_d, k: int, ef: int, admit):
         # (the list is ascending with its missing places at the tail: the first k columns are the answer, by position)
-        pos = torch.arange(k, device=q.device, dtype=torch.int64)[None, :].expand(B, k)
-        d, i = ranked_answer(cand, cand_d[:, :k], pos, k, sqrt=self.metric == Metric.EUCLIDEAN)
-        # completeness: a list with fewer than min(k, n_adm) rows is answered again by the exact filtered search.  Convergence: so is
-        # a query whose k-th row lies beyond the routing list's last place -- inside that distance the walk looked as closely as the
-        # plain walk at ef_route does, beyond it the list only holds the admitted rows met on the way (a filter that admits nothing
-        # near the query: hnswlib walks on there, bounded by its admitted results; this walk is bounded by ef_route)
-        kk = min(k, n_adm)
-        short = torch.nonzero((cand[:, kk - 1] < 0) | (cand_d[:, kk - 1] > reach)).reshape(-1)
-        self.last_filter_reanswered = int(short.numel())  # (the one host look)
-        if self.last_filter_reanswered:  # (from the caller's own rows: pre-processing them twice would not be the exact search's bits)
-            xs = x.reshape(1, -1) if x.ndim == 1 else x
-            ed, ei = super().search_batch(xs[short.to(xs.device) if isinstance(xs, torch.Tensor) else short.cpu().numpy()], limit=k,
-                                          indices=indices)
-            d[short], i[short] = self._to_dev(ed), self._to_dev(ei)
-        return like_input(is_np, d, i)
+        pos = torch.arange(k, device=q.device, dtype=torch.int64)[None, :].expand(q.shape[0], k)
+        return (*ranked_answer(cand, cand_d[:, :k], pos, k, sqrt=self.metric == Metric.EUCLIDEAN), k)
 
     def search_batch(self, x, limit: int = 10, indices=None, ef_search: Optional[int] = None, filter_search: Optional[str] = None,
                      **kwargs):
@@ -178,18 +147,16 @@ class HnswFlatGpuIndex(FlatGpuIndex):
         list's last place -- the walk did not reach that far, it only met such rows on the way (a filter that admits nothing near
         the query).  Finding those queries costs one host look at a column of the walk's result.
         ``last_filter_path`` ('graph' / 'exact') and ``last_filter_reanswered`` say what the last filtered search did."""
-        if filter_search is not None and filter_search not in self.FILTER_SEARCH:
-            raise ValueError(f"filter_search={filter_search!r}: 'exact' or 'graph'")
+        self._check_filter_search(filter_search)
         k = int(limit)
         ef = max(int(ef_search or self.ef_search), k)
         gg = self._gg
         no_walk = gg is None or gg.n == 0 or gg.n != self._n_rows or k > self.MAX_EF or ef > self.MAX_EF
         if indices is not None:
-            self.last_filter_path, self.last_filter_reanswered = 'exact', 0
-            if not no_walk and (filter_search or self.filter_search) == 'graph':
-                answer = self._search_filtered_on_graph(x, k, ef, indices, forced=filter_search == 'graph')
-                if answer is not None:
-                    return answer
+            self._overflowed, self.last_flat_filter = 0, None  # (a walk runs no filter; the parent's search sets its own)
+            answer = self._filtered_answer(x, k, ef, indices, filter_search, not no_walk)
+            if answer is not None:
+                return answer
         if indices is not None or no_walk:
             return super().search_batch(x, limit=limit, indices=indices)
         is_np = not isinstance(x, torch.Tensor)

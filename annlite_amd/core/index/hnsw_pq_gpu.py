@@ -33,13 +33,13 @@ import torch
 from ... import _graph_capi as gc
 from ... import ops
 from ...enums import Metric
+from .filter_walk import FilterWalkMixin
 from .pq_flat_gpu import PQFlatGpuIndex
 from .row_store import empty_answer, like_input, ranked_answer
 
 
-class HnswPQGpuIndex(PQFlatGpuIndex):
+class HnswPQGpuIndex(FilterWalkMixin, PQFlatGpuIndex):
     MAX_EF = 256  # the GPU walk's list: four registers per lane
-    FILTER_SEARCH = ('exact', 'graph')
     # The smallest measured share of admitted rows at which the filtered walk is faster than the exhaustive masked scan AND within the
     # test margin of the unfiltered walk's recall@10.  DESIGN.md section 8b, item 8 (5M x 128, M = 16, ef_search 128): NO measured share
     # qualifies -- the scan answers 1.0-1.4 M q/s under any filter, the filtered walk 0.40-0.70 M -- so as a constructor rule only a
@@ -50,12 +50,9 @@ class HnswPQGpuIndex(PQFlatGpuIndex):
                  ef_search: int = 50, max_connection: int = 16, n_threads: int = 0, seed: int = 100,
                  walk: str = 'gpu', packed_graph: bool = True, expand_width: int = 2, build: Optional[str] = None,
                  filter_search: str = 'exact', **kwargs):
-        if filter_search not in self.FILTER_SEARCH:
-            raise ValueError(f"filter_search={filter_search!r}: 'exact' (the parent's exhaustive masked scan) or 'graph' (the filtered walk)")
+        self._check_filter_search(filter_search, "the parent's exhaustive masked scan")
         super().__init__(dim, pq_codec=pq_codec, metric=metric, **kwargs)
-        self.filter_search = filter_search
-        self.last_filter_path = None     # 'graph' / 'exact': how the last search that carried `indices` was answered
-        self.last_filter_reanswered = 0  # ... and how many of its queries the exact search answered again (see search_batch)
+        self._init_filter_search(filter_search)
         self.ef_construction = int(ef_construction)  # hnsw/index.py:66-69
         self.ef_search = int(ef_search)
         self.max_connection = int(max_connection)
@@ -266,70 +263,44 @@ class HnswPQGpuIndex(PQFlatGpuIndex):
             return self._gg is not None and self._gg.n == self._n_rows
         return self._graph is not None
 
-    def _search_filtered_on_graph(self, x, k: int, ef: int, indices, forced: bool):
-        """The filtered walk, or None where the exact search is to answer (no admitted row; the constructor rule's selectivity floor).
-        ``admit = valid & filter``; with ``s`` the admitted share of the rows the routing list gets ``ef / s`` places (at most 256), so
-        that about ``ef`` of the rows it keeps are admitted ones, and the result list ``ef``.  The result list is then ranked as the
-        unfiltered search ranks its candidates."""
+    # the filtered walk's two hooks (filter_walk.FilterWalkMixin)
+    def _filter_walk(self, q, ef_route: int, ef: int, admit, reach):
         from ..._capi import LAYOUT_BMK, LUT_L2
 
-        admit = self._filter_bits(indices)
-        n_rows = self._n_rows
-        n_adm = int(self._unpack_bits(admit, n_rows).sum().item())
-        if n_adm == 0 or (not forced and n_adm < self.FILTER_WALK_MIN_FRACTION * n_rows):
-            return None
-        is_np = not isinstance(x, torch.Tensor)
-        q = self._pre(x)
-        B = q.shape[0]
-        self.last_filter_path = 'graph'
-        if B == 0:
-            return like_input(is_np, *empty_answer(B, k, q.device))
-        ef_route = min(self.MAX_EF, max(ef, -(-ef * n_rows // n_adm)))
         # tables and graph: what `candidates` walks with
+        n_rows = self._n_rows
         _, xg = self.pq_codec.scan_inputs(q)
         links, seeds = self._export_graph()
         lut = ops.lut_build(xg, self.pq_codec.codebooks_dev, LUT_L2, LAYOUT_BMK)
         plain = self._plain_table(n_rows)
         lpn = links.shape[1] - 1
-        reach = torch.empty((B,), dtype=torch.float32, device=q.device)
-        cand, cand_d = ops.graph_search_packed_admit(self._packed_records(links, plain), lpn, seeds, plain, lut, ef_route, ef, admit,
-                                                     n_rows=n_rows, expand_width=self.expand_width if lpn <= 32 else 1, route_worst=reach)
+        return ops.graph_search_packed_admit(self._packed_records(links, plain), lpn, seeds, plain, lut, ef_route, ef, admit, n_rows=n_rows,
+                                             expand_width=self.expand_width if lpn <= 32 else 1, route_worst=reach)
+
+    def _filter_rank(self, x, q, cand, cand_d, k: int, ef: int, admit):
+        """The result list ranked as the unfiltered search ranks its candidates.  ``depth`` is how far into the list the answer reaches:
+        ranked by ADC sums it is the list's first k entries; a re-rank (exact distances, or another metric's tables) draws on ALL of the
+        list, as the unfiltered search's re-rank draws on all ef candidates of a list that lies within the walk's reach by construction
+        -- an entry only met on the way stands where a nearer admitted row, never evaluated, belongs."""
+        from ..._capi import LAYOUT_BMK
+
         euclid = self.metric == Metric.EUCLIDEAN
         if self.rerank and self._vectors is not None:
             if k <= 64:
-                d, i = ops.rerank_topk(int(self.metric), q, self._vectors, cand, k, valid_bits=admit, sqrt=euclid)
-            else:
-                dist = ops.exact_gather_dist(int(self.metric), q, self._vectors, cand)
-                d, pos = self._topk_rows_any(dist, min(k, ef))
-                d, i = ranked_answer(cand, d, pos, k, sqrt=euclid)
-        elif euclid:
+                return (*ops.rerank_topk(int(self.metric), q, self._vectors, cand, k, valid_bits=admit, sqrt=euclid), ef)
+            dist = ops.exact_gather_dist(int(self.metric), q, self._vectors, cand)
+            d, pos = self._topk_rows_any(dist, min(k, ef))
+            return (*ranked_answer(cand, d, pos, k, sqrt=euclid), ef)
+        if euclid:
             # the walk's own sums ARE the metric's (same table, same ascending-m fp32 chain as annlite_adc_gather) and the list is
             # ascending with its missing places at the tail: the first k columns are the answer, by position
-            pos = torch.arange(k, device=q.device, dtype=torch.int64)[None, :].expand(B, k)
-            d, i = ranked_answer(cand, cand_d[:, :k], pos, k, sqrt=True)
-        else:
-            kind, xq = self._scan_inputs(x, q)  # (host buffers: normalised like the flat index's queries, bit for bit)
-            mlut = ops.lut_build(xq, self.pq_codec.codebooks_dev, kind, LAYOUT_BMK)
-            dist = ops.adc_gather(mlut, plain, cand)
-            d, pos = self._topk_rows_any(dist, min(k, ef))
-            d, i = ranked_answer(cand, d, pos, k, sqrt=False)
-        # completeness: a list with fewer than `depth` rows is answered again by the exact filtered search.  Convergence: so is a query
-        # whose depth-th sum lies beyond the routing list's last place -- inside that sum the walk looked as closely as the plain walk
-        # at ef_route does, beyond it the list only holds the admitted rows met on the way (a filter that admits nothing near the
-        # query).  Both on the walk's own L2 sums, whatever the ranking.  `depth` is how far into the list the answer reaches: ranked
-        # by ADC sums it is the list's first k entries; a re-rank (exact distances, or another metric's tables) draws on ALL of the
-        # list, as the unfiltered search's re-rank draws on all ef candidates of a list that lies within the walk's reach by
-        # construction -- an entry only met on the way stands where a nearer admitted row, never evaluated, belongs.
-        reranked = (self.rerank and self._vectors is not None) or not euclid
-        depth = min(ef if reranked else k, n_adm)
-        short = torch.nonzero((cand[:, depth - 1] < 0) | (cand_d[:, depth - 1] > reach)).reshape(-1)
-        self.last_filter_reanswered = int(short.numel())  # (the one host look)
-        if self.last_filter_reanswered:  # (from the caller's own rows: pre-processing them twice would not be the exact search's bits)
-            xs = x.reshape(1, -1) if x.ndim == 1 else x
-            ed, ei = super().search_batch(xs[short.to(xs.device) if isinstance(xs, torch.Tensor) else short.cpu().numpy()], limit=k,
-                                          indices=indices)
-            d[short], i[short] = self._to_dev(ed), self._to_dev(ei)
-        return like_input(is_np, d, i)
+            pos = torch.arange(k, device=q.device, dtype=torch.int64)[None, :].expand(q.shape[0], k)
+            return (*ranked_answer(cand, cand_d[:, :k], pos, k, sqrt=True), k)
+        kind, xq = self._scan_inputs(x, q)  # (host buffers: normalised like the flat index's queries, bit for bit)
+        mlut = ops.lut_build(xq, self.pq_codec.codebooks_dev, kind, LAYOUT_BMK)
+        dist = ops.adc_gather(mlut, self._plain_table(self._n_rows), cand)
+        d, pos = self._topk_rows_any(dist, min(k, ef))
+        return (*ranked_answer(cand, d, pos, k, sqrt=False), ef)
 
     def search_batch(self, x, limit: int = 10, indices=None, ef_search: Optional[int] = None, filter_search: Optional[str] = None,
                      **kwargs):
@@ -347,16 +318,13 @@ class HnswPQGpuIndex(PQFlatGpuIndex):
         list is ranked by its own ADC sums, and the whole list (``ef``) where it is re-ranked (``rerank=True``, cosine / inner product:
         a re-rank draws on every entry).  Finding those queries costs one host look.
         ``last_filter_path`` ('graph' / 'exact') and ``last_filter_reanswered`` say what the last filtered search did."""
-        if filter_search is not None and filter_search not in self.FILTER_SEARCH:
-            raise ValueError(f"filter_search={filter_search!r}: 'exact' or 'graph'")
+        self._check_filter_search(filter_search)
         if indices is not None:
-            self.last_filter_path, self.last_filter_reanswered = 'exact', 0
             k = int(limit)
             ef = max(int(ef_search or self.ef_search), k)
-            if (filter_search or self.filter_search) == 'graph' and self._filter_walk_ok(k, ef):
-                answer = self._search_filtered_on_graph(x, k, ef, indices, forced=filter_search == 'graph')
-                if answer is not None:
-                    return answer
+            answer = self._filtered_answer(x, k, ef, indices, filter_search, self._filter_walk_ok(k, ef))
+            if answer is not None:
+                return answer
             return super().search_batch(x, limit=limit, indices=indices)
         is_np = not isinstance(x, torch.Tensor)
         q = self._pre(x)

@@ -60,24 +60,10 @@ __global__ __launch_bounds__(256) void graph_beam_search_kernel(const uint32_t *
     Beam<E, BATCH> bm;
     float *s_lut;
     pq_walk_setup<M, E, BATCH>(smem, wave, lane, lut_bmk, b, Ks, ef, hash_bits, bm, s_lut);
-    BeamList<E> &L = bm.L;
-    const int cap = bm.cap;
     auto offer = [&](bool mine, uint32_t node, float d) { bm.offer(mine, node, f32_to_ordered(d)); };
-    auto is_valid = [&](uint32_t node) -> bool { return !valid || ((valid[node >> 5] >> (node & 31)) & 1u); };
     pq_beam_walk<M, E, PACKED, BATCH, W>(bm, s_lut, lane, links, links_per_node, packed, rec_stride, seeds, n_seeds, codes, N, Ks, stats,
                                          offer, ct);
-
-    // ---- result: the list, ascending; deleted rows dropped here (they still route the walk, like hnswlib) ---
-    // compacting is left to the host-side top-k (ids of dropped rows become -1 / +inf)
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = e * 64 + lane;
-        if (i < ef) {
-            const bool none = (L.hi[e] == kKeyInfHi && L.lo[e] == kIdNone) || i >= cap || !is_valid(L.lo[e]);
-            out_ids[(int64_t)b * ef + i] = none ? (int64_t)-1 : (int64_t)L.lo[e];
-            out_dist[(int64_t)b * ef + i] = none ? __builtin_inff() : ordered_to_f32(L.hi[e]);
-        }
-    }
+    beam_write(bm, b, ef, valid, out_ids, out_dist);
     if (stats && lane == 0) pq_walk_add_stats(stats, ct);
 }
 

@@ -2,23 +2,13 @@
 // filtered search on the graph instead of by the exhaustive masked scan (the reference: knn_query_with_filter,
 // hnsw_bindings.cpp:392-516 -> hnswlib searchBaseLayerST with a filter functor).
 //
-// The walk is graph_pq_walk.h's, the one graph.hip's graph_beam_search_kernel<M, E, PACKED = true, BATCH = true, W> runs, with TWO
-// sorted lists.  C (Beam<E>, cap = ef_route) is that kernel's list and is handled exactly as there: the bitmap `admit` (valid & filter,
-// one bit per row) never touches it, so the expansions, the rows evaluated and the prefetched records used are
-// annlite_graph_search_packed_ex's at ef = ef_route.  R (Beam<ER>, cap = ef <= ef_route; its expanded flags and visited table are
-// never used) is offered every batch C is offered -- a seed round, a step's unseen neighbours: up to 64 lanes in the pair walk --
-// restricted to the lanes whose node is set in `admit`, under the same rule: tested against R's worst entry as it is now, whatever
-// C's worst entry is, then merged.  Order: (f32_to_ordered(sum), id), C's own.
-// INVARIANT: R's live entries are the ef smallest (key, id) among the admitted rows the walk evaluated.
-// A row can be offered to R twice, and R's merge then has to drop the copy (`tbl_full`: the merge's equality tests).  Two ways:
-//   * the visited table overflowed (Beam::visit): C's overflow state is carried into R before every offer -- R never calls visit;
-//   * a seed that missed C's list is not recorded as visited (only C's entries are) and may stand in R: it comes back as somebody's
-//     neighbour.  That takes more seeds than C has places -- a host-built graph exports up to 4096 -- so R checks from the start
-//     iff n_seeds > min(ef_route, 64 E).
-// A re-offered row that is NOT in R lost against R's worst entry before, or was pushed out, and the worst entry only falls: it loses
-// again (tests/test_graph_pq_admit_restated.py).  In the pair walk a neighbour of both nodes passes the visited table's
-// compare-and-swap once: R sees the `mine` lanes C sees.  R shares C's merge scratch: ER <= E, and the two offers of a wave are
-// sequential.  LDS per wave and the workgroup are the plain walk's (one wave per SIMD at M = 16: registers are not the limit).
+// The walk is graph_pq_walk.h's, the one graph.hip's graph_beam_search_kernel<M, E, PACKED = true, BATCH = true, W> runs; the routing
+// list C and the result list R, what each is offered and the invariant that holds between them are graph_beam.h's AdmitList.  C's
+// expansions, rows evaluated and prefetched records used are annlite_graph_search_packed_ex's at ef = ef_route.  What is this file's:
+//   * the key: (f32_to_ordered(sum), id), the PQ walk's own;
+//   * the pair walk offers up to 64 lanes per step, and a neighbour of both nodes passes the visited table's compare-and-swap once: R
+//     sees the `mine` lanes C sees;
+//   * LDS per wave and the workgroup are the plain walk's (one wave per SIMD at M = 16: registers are not the limit).
 #include "graph_pq_walk.h"
 
 namespace annlite {
@@ -31,7 +21,6 @@ __global__ __launch_bounds__(256) void graph_pq_admit_kernel(int links_per_node,
                                                             int Ks, int ef_route, int ef, int hash_bits, int64_t *__restrict__ out_ids,
                                                             float *__restrict__ out_dist, float *__restrict__ out_route_worst,
                                                             unsigned long long *__restrict__ stats) {
-    static_assert(ER <= E, "R's merge layout has to fit the scratch sized for C");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -41,40 +30,13 @@ __global__ __launch_bounds__(256) void graph_pq_admit_kernel(int links_per_node,
     Beam<E, true> bm;
     float *s_lut;
     pq_walk_setup<M, E, true>(smem, wave, lane, lut_bmk, b, Ks, ef_route, hash_bits, bm, s_lut);
-    Beam<ER, true> rs;
-    rs.init(lane, ef, bm.s_mrg, bm.hash_ad, hash_bits);
-    rs.tbl_full = n_seeds > bm.cap;
-    // both lists are offered one batch; `mine` lanes hold a node < N
-    auto offer_both = [&](bool mine, uint32_t node, float d) {
-        const uint32_t word = mine ? admit[node >> 5] : 0u;  // (only a row's own word is read)
-        const bool adm = ((word >> (node & 31)) & 1u) != 0u;
-        const uint32_t key = f32_to_ordered(d);
-        bm.offer(mine, node, key);
-        asm volatile("" ::: "memory");  // (C's last reads of the scratch stay ahead of R's first writes)
-        rs.tbl_ovf = bm.tbl_ovf;
-        rs.offer(adm, node, key);
-        asm volatile("" ::: "memory");
-    };
+    AdmitList<E, ER> rl;
+    rl.init(bm, ef, n_seeds, admit);
+    auto offer_both = [&](bool mine, uint32_t node, float d) __attribute__((always_inline)) { rl.offer_both(bm, mine, node, f32_to_ordered(d)); };
     pq_beam_walk<M, E, true, true, W>(bm, s_lut, lane, nullptr, links_per_node, packed, rec_stride, seeds, n_seeds, codes, N, Ks, stats,
                                       offer_both, ct);
-
-    // ---- result: R, ascending; it holds admitted rows only, so the missing places are all at the tail ----
-#pragma unroll
-    for (int e = 0; e < ER; ++e) {
-        const int i = e * 64 + lane;
-        if (i < ef) {
-            const bool none = (rs.L.hi[e] == kKeyInfHi && rs.L.lo[e] == kIdNone) || i >= rs.cap;
-            out_ids[(int64_t)b * ef + i] = none ? (int64_t)-1 : (int64_t)rs.L.lo[e];
-            out_dist[(int64_t)b * ef + i] = none ? __builtin_inff() : ordered_to_f32(rs.L.hi[e]);
-        }
-    }
-    // how far the walk reached: the sum at C's last place (+inf while C is not full).  An entry of R at or below it lies where the
-    // walk looked as closely as the plain walk at ef_route does; one beyond it was only met on the way (the caller's convergence test).
-    if (out_route_worst) {
-        uint32_t whi, wlo;
-        bm.worst(whi, wlo);
-        if (lane == 0) out_route_worst[b] = whi == kKeyInfHi && wlo == kIdNone ? __builtin_inff() : ordered_to_f32(whi);
-    }
+    rl.write(b, ef, out_ids, out_dist);
+    rl.write_route_worst(bm, b, out_route_worst);
     if (stats && lane == 0) pq_walk_add_stats(stats, ct);
 }
 

@@ -316,4 +316,82 @@ struct Beam {
     }
 };
 
+// row `b` of a walk's result: the list's first `ef` places, ascending; the places beyond `cap`, the empty ones and the rows cleared
+// in `valid` (NULL: none is) blanked in place to (-1, +inf) -- such rows still route the walk, like hnswlib's; compacting is left to
+// the host-side top-k
+template <int E, bool BATCH>
+__device__ __forceinline__ void beam_write(const Beam<E, BATCH> &bm, int b, int ef, const uint32_t *__restrict__ valid,
+                                           int64_t *__restrict__ out_ids, float *__restrict__ out_dist) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = e * 64 + bm.lane;
+        if (i < ef) {
+            bool none = (bm.L.hi[e] == kKeyInfHi && bm.L.lo[e] == kIdNone) || i >= bm.cap;
+            if (!none && valid) none = !((valid[bm.L.lo[e] >> 5] >> (bm.L.lo[e] & 31)) & 1u);
+            out_ids[(int64_t)b * ef + i] = none ? (int64_t)-1 : (int64_t)bm.L.lo[e];
+            out_dist[(int64_t)b * ef + i] = none ? __builtin_inff() : ordered_to_f32(bm.L.hi[e]);
+        }
+    }
+}
+
+// The ADMITTED-RESULT list of a filtered walk (graph_admit.hip over PQ codes, graph_f32.hip over float rows).  Such a walk keeps TWO
+// sorted lists.  C (Beam<E>, cap = ef_route) is the plain walk's list and is handled exactly as there: the bitmap `admit` (valid &
+// filter, one bit per row) never touches it, so the expansions and the rows evaluated are the plain walk's at ef = ef_route.  R (this
+// struct: Beam<ER>, cap = ef <= ef_route; its expanded flags and visited table are never used) is offered every batch C is offered --
+// a seed round, a step's unseen neighbours -- restricted to the lanes whose node is set in `admit`, under the same rule: tested
+// against R's worst entry as it is now, whatever C's worst entry is, then merged.  Order: (key, id), C's own key.
+// INVARIANT: R's live entries are the ef smallest (key, id) among the admitted rows the walk evaluated.
+// A row can be offered to R twice, and R's merge then has to drop the copy (`tbl_full`: the merge's equality tests).  Two ways:
+//   * the visited table overflowed (Beam::visit): C's overflow state is carried into R before every offer -- R never calls visit;
+//   * a seed that missed C's list is not recorded as visited (only C's entries are) and may stand in R: it comes back as somebody's
+//     neighbour.  That takes more seeds than C has places -- a host-built graph exports up to 4096 -- so R checks from the start
+//     iff n_seeds > min(ef_route, 64 E).
+// A re-offered row that is NOT in R lost against R's worst entry before, or was pushed out, and the worst entry only falls: it loses
+// again (tests/test_graph_pq_admit_restated.py, tests/test_graph_f32_admit_restated.py).  R shares C's merge scratch: ER <= E, and
+// the two offers of a wave are sequential.
+template <int E, int ER>
+struct AdmitList {
+    static_assert(ER <= E, "R's merge layout has to fit the scratch sized for C");
+    Beam<ER, true> rs;
+    const uint32_t *admit;
+
+    // after C's own init
+    __device__ __forceinline__ void init(const Beam<E, true> &bm, int ef, int n_seeds, const uint32_t *admit_) {
+        admit = admit_;
+        rs.init(bm.lane, ef, bm.s_mrg, bm.hash_ad, bm.hash_bits);
+        rs.tbl_full = n_seeds > bm.cap;
+    }
+
+    // both lists are offered one batch; `mine` lanes hold a node < N.  (The lambda a kernel wraps this in is marked always_inline: left
+    // to the inliner's size estimate it stays a call once a list has three or four registers per lane, and both lists then live in
+    // scratch memory.)
+    __device__ __forceinline__ void offer_both(Beam<E, true> &bm, bool mine, uint32_t node, uint32_t key) {
+        const uint32_t word = mine ? admit[node >> 5] : 0u;  // (only a row's own word is read)
+        const bool adm = ((word >> (node & 31)) & 1u) != 0u;
+        bm.offer(mine, node, key);
+        asm volatile("" ::: "memory");  // (C's last reads of the scratch stay ahead of R's first writes)
+        rs.tbl_ovf = bm.tbl_ovf;
+        rs.offer(adm, node, key);
+        asm volatile("" ::: "memory");
+    }
+
+    // R, ascending; it holds admitted rows only, so the missing places are all at the tail
+    __device__ __forceinline__ void write(int b, int ef, int64_t *__restrict__ out_ids, float *__restrict__ out_dist) const {
+        beam_write(rs, b, ef, nullptr, out_ids, out_dist);
+    }
+
+    // how far the walk reached: the key's value at C's last place (+inf while C is not full).  An entry of R at or below it lies where
+    // the walk looked as closely as the plain walk at ef_route does; one beyond it was only met on the way (the caller's convergence
+    // test).  `out` may be NULL.
+    __device__ __forceinline__ void write_route_worst(const Beam<E, true> &bm, int b, float *__restrict__ out) const {
+        if (!out) return;
+        uint32_t whi, wlo;
+        bm.worst(whi, wlo);
+        if (bm.lane == 0) out[b] = whi == kKeyInfHi && wlo == kIdNone ? __builtin_inff() : ordered_to_f32(whi);
+    }
+};
+
+// host side, graph.hip: entries of the visited table (log2) beside a routing list of `ef` places, whatever the walk's distance
+int graph_walk_hash_bits(int ef);
+
 }  // namespace annlite

@@ -70,37 +70,43 @@ __device__ __forceinline__ float rows_dist(unsigned long long pm, uint32_t node,
 }
 
 // ---- walk ---------------------------------------------------------------------------------------------------------------------
+// ONE COPY for the two kernels below, in the shape of graph_pq_walk.h's: a kernel sets its wave up with f32_walk_setup, then calls
+// f32_beam_walk with what is to happen to every batch of evaluated rows as `offer(mine, node, key)`.
 // The order of graph_beam_search_kernel<.., PACKED = false, BATCH = true> (tests/test_graph_pair.py walk_restated, width 1): seeds
 // scanned flat in rounds of 64, the best unexpanded entry expanded, a step's unseen neighbours (ids < N) tested against the list's
 // worst entry before any is inserted, the list ordered by (f32_to_key(distance), node id) -- NaN behind +inf --, the walk over when
-// the first min(ef, 64 E) entries hold no unexpanded node; rows cleared in `valid` route the walk and are blanked on output.
-template <int E, bool L2>
-__global__ __launch_bounds__(256) void graph_f32_search_kernel(const float *__restrict__ q, int B, int D, const float *__restrict__ x,
-                                                              int64_t N, const uint32_t *__restrict__ links, int lpn,
-                                                              const uint32_t *__restrict__ seeds, int n_seeds,
-                                                              const uint32_t *__restrict__ valid, int ef, int hash_bits,
-                                                              int64_t *__restrict__ out_ids, float *__restrict__ out_dist,
-                                                              unsigned long long *__restrict__ stats) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int b = blockIdx.x * (blockDim.x >> 6) + wave;
-    if (b >= B) return;  // (whole waves leave; no block-wide barrier below)
-    unsigned int n_expand = 0, n_eval = 0;  // (ANNLITE_DEBUG_COUNTERS: link lists read, rows evaluated)
+// the first min(ef, 64 E) entries hold no unexpanded node.
+
+// LDS of one walking wave: the query (padded to 16 B), the visited table, the merge's scratch of a list of E registers per lane
+__host__ __device__ inline size_t f32_walk_lds_per_wave(int E, int D, int hash_bits) {
+    return (((size_t)D * 4 + 15) & ~(size_t)15) + ((size_t)4 << hash_bits) + (size_t)E * 64 * 12 + 1024;
+}
+
+// The wave's query and visited table filled, its list `bm` (cap = ef) empty; `s_q`: the query.
+template <int E>
+__device__ __forceinline__ void f32_walk_setup(unsigned char *smem, int wave, int lane, const float *__restrict__ q, int b, int D, int ef,
+                                               int hash_bits, Beam<E, true> &bm, const float *&s_q) {
     const uint32_t hash_n = 1u << hash_bits;
     const size_t q_bytes = ((size_t)D * 4 + 15) & ~(size_t)15;
-    const size_t per_wave = q_bytes + (size_t)hash_n * 4 + (size_t)E * 64 * 12 + 1024;  // (same formula as launch_walk)
-    float *s_q = (float *)(smem + wave * per_wave);
+    const size_t per_wave = f32_walk_lds_per_wave(E, D, hash_bits);
+    float *s_qw = (float *)(smem + wave * per_wave);
     uint32_t *s_hash = (uint32_t *)(smem + wave * per_wave + q_bytes);
     uint32_t *s_mrg = s_hash + hash_n;
-    for (int j = lane; j < D; j += 64) s_q[j] = q[(int64_t)b * D + j];
+    for (int j = lane; j < D; j += 64) s_qw[j] = q[(int64_t)b * D + j];
     for (uint32_t i = lane; i < hash_n / 4; i += 64) ((u32x4 *)s_hash)[i] = (u32x4){kEmpty, kEmpty, kEmpty, kEmpty};
     asm volatile("" ::: "memory");  // (one wave: its LDS writes are visible to its own later reads in program order)
     typedef __attribute__((address_space(3))) unsigned char *lds_bytes;
     const uint32_t hash_ad = (uint32_t)(uintptr_t)(lds_bytes)smem + (uint32_t)(wave * per_wave) + (uint32_t)q_bytes;
-    Beam<E, true> bm;
     bm.init(lane, ef, s_mrg, hash_ad, hash_bits);
+    s_q = s_qw;
+}
 
+// Seeds, then the walk, until `bm`'s list holds no unexpanded node.  ANNLITE_DEBUG_COUNTERS: `n_expand` link lists read, `n_eval`
+// rows evaluated.
+template <int E, bool L2, class Offer>
+__device__ __forceinline__ void f32_beam_walk(Beam<E, true> &bm, const float *s_q, int lane, const float *__restrict__ x, int D, int64_t N,
+                                              const uint32_t *__restrict__ links, int lpn, const uint32_t *__restrict__ seeds, int n_seeds,
+                                              Offer &&offer, unsigned int &n_expand, unsigned int &n_eval) {
     // ---- seeds, scanned flat (distinct: no visited check; only the ones that made the list are recorded) ----
     for (int s0 = 0; s0 < n_seeds; s0 += 64) {
         const uint32_t node = s0 + lane < n_seeds ? seeds[s0 + lane] : kEmpty;
@@ -108,7 +114,7 @@ __global__ __launch_bounds__(256) void graph_f32_search_kernel(const float *__re
         const unsigned long long pm = __ballot(mine);
         const float d = rows_dist<L2>(pm, node, x, D, s_q, lane);
         n_eval += (unsigned int)__popcll(pm);
-        bm.offer(mine, node, f32_to_key(d));
+        offer(mine, node, f32_to_key(d));
     }
 #pragma unroll
     for (int e = 0; e < E; ++e)
@@ -139,39 +145,42 @@ __global__ __launch_bounds__(256) void graph_f32_search_kernel(const float *__re
         const unsigned long long pm = __ballot(mine);
         const float d = rows_dist<L2>(pm, nb, x, D, s_q, lane);
         n_eval += (unsigned int)__popcll(pm);
-        bm.offer(mine, nb, f32_to_key(d));
+        offer(mine, nb, f32_to_key(d));
     }
+}
 
-    // ---- result: the list, ascending; deleted rows blanked in place (compacting is left to the host-side top-k) ----
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = e * 64 + lane;
-        if (i < ef) {
-            bool none = (bm.L.hi[e] == kKeyInfHi && bm.L.lo[e] == kIdNone) || i >= bm.cap;
-            if (!none && valid) none = !((valid[bm.L.lo[e] >> 5] >> (bm.L.lo[e] & 31)) & 1u);
-            out_ids[(int64_t)b * ef + i] = none ? (int64_t)-1 : (int64_t)bm.L.lo[e];
-            out_dist[(int64_t)b * ef + i] = none ? __builtin_inff() : ordered_to_f32(bm.L.hi[e]);
-        }
-    }
+__device__ __forceinline__ void f32_walk_add_stats(unsigned long long *stats, int lane, unsigned int n_expand, unsigned int n_eval) {
     if (stats && lane == 0) {
         atomicAdd(stats + 0, (unsigned long long)n_expand);
         atomicAdd(stats + 1, (unsigned long long)n_eval);
     }
 }
 
-// ---- walk with an admitted-result list (annlite_graph_f32_search_admit) ---------------------------------------------------------
-// The walk above with TWO sorted lists.  C (Beam<E>, cap = ef_route) is the kernel above's list and is handled exactly as there: the
-// bitmap `admit` never touches it, so the expansions and the rows evaluated are annlite_graph_f32_search's at ef = ef_route.  R
-// (Beam<ER>, cap = ef <= ef_route; its expanded flags and visited table are never used) is offered every batch C is offered -- a seed
-// round, an expansion's unseen neighbours -- restricted to the lanes whose node is set in `admit`, under the same rule: tested
-// against R's worst entry as it is now, whatever C's worst entry is, then merged.
-// INVARIANT: R's live entries are the ef smallest (f32_to_key(distance), id) among the admitted rows the walk evaluated.
-// A row can be offered to R twice, and R's merge then has to drop the copy (`tbl_full`: the merge's equality tests).  Two ways:
-//   * the visited table overflowed (Beam::visit): C's overflow state is carried into R before every offer -- R never calls visit;
-//   * a seed that missed C's list is not recorded as visited (only C's entries are) and may stand in R: it comes back as somebody's
-//     neighbour.  That takes more seeds than C has places, so R checks from the start iff n_seeds > min(ef_route, 64 E).
-// A re-offered row that is NOT in R lost against R's worst entry before, or was pushed out, and the worst entry only falls: it loses
-// again (tests/test_graph_f32_admit_restated.py).  R shares C's merge scratch: ER <= E, and the two offers of a wave are sequential.
+// annlite_graph_f32_search: one list; rows cleared in `valid` route the walk and are blanked on output
+template <int E, bool L2>
+__global__ __launch_bounds__(256) void graph_f32_search_kernel(const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+                                                              int64_t N, const uint32_t *__restrict__ links, int lpn,
+                                                              const uint32_t *__restrict__ seeds, int n_seeds,
+                                                              const uint32_t *__restrict__ valid, int ef, int hash_bits,
+                                                              int64_t *__restrict__ out_ids, float *__restrict__ out_dist,
+                                                              unsigned long long *__restrict__ stats) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int b = blockIdx.x * (blockDim.x >> 6) + wave;
+    if (b >= B) return;  // (whole waves leave; no block-wide barrier below)
+    unsigned int n_expand = 0, n_eval = 0;
+    Beam<E, true> bm;
+    const float *s_q;
+    f32_walk_setup<E>(smem, wave, lane, q, b, D, ef, hash_bits, bm, s_q);
+    auto offer = [&](bool mine, uint32_t node, uint32_t key) __attribute__((always_inline)) { bm.offer(mine, node, key); };
+    f32_beam_walk<E, L2>(bm, s_q, lane, x, D, N, links, lpn, seeds, n_seeds, offer, n_expand, n_eval);
+    beam_write(bm, b, ef, valid, out_ids, out_dist);
+    f32_walk_add_stats(stats, lane, n_expand, n_eval);
+}
+
+// annlite_graph_f32_search_admit: the walk above at ef = ef_route -- same expansions, same rows evaluated -- with graph_beam.h's
+// admitted-result list beside it.  Key: (f32_to_key(distance), id), the float walk's own.
 template <int E, int ER, bool L2>
 __global__ __launch_bounds__(256) void graph_f32_admit_kernel(const float *__restrict__ q, int B, int D, const float *__restrict__ x,
                                                              int64_t N, const uint32_t *__restrict__ links, int lpn,
@@ -180,100 +189,22 @@ __global__ __launch_bounds__(256) void graph_f32_admit_kernel(const float *__res
                                                              int64_t *__restrict__ out_ids, float *__restrict__ out_dist,
                                                              float *__restrict__ out_route_worst,
                                                              unsigned long long *__restrict__ stats) {
-    static_assert(ER <= E, "R's merge layout has to fit the scratch sized for C");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int b = blockIdx.x * (blockDim.x >> 6) + wave;
     if (b >= B) return;  // (whole waves leave; no block-wide barrier below)
     unsigned int n_expand = 0, n_eval = 0;
-    const uint32_t hash_n = 1u << hash_bits;
-    const size_t q_bytes = ((size_t)D * 4 + 15) & ~(size_t)15;
-    const size_t per_wave = q_bytes + (size_t)hash_n * 4 + (size_t)E * 64 * 12 + 1024;  // (same formula as launch_walk_admit)
-    float *s_q = (float *)(smem + wave * per_wave);
-    uint32_t *s_hash = (uint32_t *)(smem + wave * per_wave + q_bytes);
-    uint32_t *s_mrg = s_hash + hash_n;
-    for (int j = lane; j < D; j += 64) s_q[j] = q[(int64_t)b * D + j];
-    for (uint32_t i = lane; i < hash_n / 4; i += 64) ((u32x4 *)s_hash)[i] = (u32x4){kEmpty, kEmpty, kEmpty, kEmpty};
-    asm volatile("" ::: "memory");
-    typedef __attribute__((address_space(3))) unsigned char *lds_bytes;
-    const uint32_t hash_ad = (uint32_t)(uintptr_t)(lds_bytes)smem + (uint32_t)(wave * per_wave) + (uint32_t)q_bytes;
     Beam<E, true> bm;
-    bm.init(lane, ef_route, s_mrg, hash_ad, hash_bits);
-    Beam<ER, true> rs;
-    rs.init(lane, ef, s_mrg, hash_ad, hash_bits);
-    rs.tbl_full = n_seeds > bm.cap;
-    // both lists are offered one batch; `mine` lanes hold a node < N
-    auto offer_both = [&](bool mine, uint32_t node, uint32_t key) {
-        const uint32_t word = mine ? admit[node >> 5] : 0u;  // (only a row's own word is read)
-        const bool adm = ((word >> (node & 31)) & 1u) != 0u;
-        bm.offer(mine, node, key);
-        asm volatile("" ::: "memory");  // (C's last reads of the scratch stay ahead of R's first writes)
-        rs.tbl_ovf = bm.tbl_ovf;
-        rs.offer(adm, node, key);
-        asm volatile("" ::: "memory");
-    };
-
-    for (int s0 = 0; s0 < n_seeds; s0 += 64) {
-        const uint32_t node = s0 + lane < n_seeds ? seeds[s0 + lane] : kEmpty;
-        const bool mine = s0 + lane < n_seeds && (int64_t)node < N;
-        const unsigned long long pm = __ballot(mine);
-        const float d = rows_dist<L2>(pm, node, x, D, s_q, lane);
-        n_eval += (unsigned int)__popcll(pm);
-        offer_both(mine, node, f32_to_key(d));
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-        if (bm.L.lo[e] != kIdNone) bm.visit(bm.L.lo[e]);
-
-    auto load_list = [&](uint32_t node, uint32_t &cnt, uint32_t &nb) {
-        const uint32_t *ll = links + (int64_t)node * (lpn + 1);
-        cnt = ll[0];
-        nb = lane < lpn ? ll[1 + lane] : kEmpty;
-    };
-    uint32_t pf_node = kEmpty, pf_cnt = 0, pf_nb = kEmpty;
-    for (;;) {
-        uint32_t node = 0, second = kEmpty;
-        if (!bm.pick_next(node, second)) break;
-        uint32_t cnt, nb;
-        if (pf_node == node) {
-            cnt = pf_cnt;
-            nb = pf_nb;
-        } else {
-            load_list(node, cnt, nb);
-        }
-        pf_node = second;
-        if (second != kEmpty) load_list(second, pf_cnt, pf_nb);
-        ++n_expand;
-        bool mine = lane < lpn && (uint32_t)lane < cnt;
-        mine = mine && (int64_t)nb < N && bm.visit(nb);
-        const unsigned long long pm = __ballot(mine);
-        const float d = rows_dist<L2>(pm, nb, x, D, s_q, lane);
-        n_eval += (unsigned int)__popcll(pm);
-        offer_both(mine, nb, f32_to_key(d));
-    }
-
-    // ---- result: R, ascending; it holds admitted rows only, so the missing places are all at the tail ----
-#pragma unroll
-    for (int e = 0; e < ER; ++e) {
-        const int i = e * 64 + lane;
-        if (i < ef) {
-            const bool none = (rs.L.hi[e] == kKeyInfHi && rs.L.lo[e] == kIdNone) || i >= rs.cap;
-            out_ids[(int64_t)b * ef + i] = none ? (int64_t)-1 : (int64_t)rs.L.lo[e];
-            out_dist[(int64_t)b * ef + i] = none ? __builtin_inff() : ordered_to_f32(rs.L.hi[e]);
-        }
-    }
-    // how far the walk reached: the distance of C's last place (+inf while C is not full).  An entry of R at or below it lies where the
-    // walk looked as closely as the plain walk at ef_route does; one beyond it was only met on the way (the caller's convergence test).
-    if (out_route_worst) {
-        uint32_t whi, wlo;
-        bm.worst(whi, wlo);
-        if (lane == 0) out_route_worst[b] = whi == kKeyInfHi && wlo == kIdNone ? __builtin_inff() : ordered_to_f32(whi);
-    }
-    if (stats && lane == 0) {
-        atomicAdd(stats + 0, (unsigned long long)n_expand);
-        atomicAdd(stats + 1, (unsigned long long)n_eval);
-    }
+    const float *s_q;
+    f32_walk_setup<E>(smem, wave, lane, q, b, D, ef_route, hash_bits, bm, s_q);
+    AdmitList<E, ER> rl;
+    rl.init(bm, ef, n_seeds, admit);
+    auto offer_both = [&](bool mine, uint32_t node, uint32_t key) __attribute__((always_inline)) { rl.offer_both(bm, mine, node, key); };
+    f32_beam_walk<E, L2>(bm, s_q, lane, x, D, N, links, lpn, seeds, n_seeds, offer_both, n_expand, n_eval);
+    rl.write(b, ef, out_ids, out_dist);
+    rl.write_route_worst(bm, b, out_route_worst);
+    f32_walk_add_stats(stats, lane, n_expand, n_eval);
 }
 
 // ---- build --------------------------------------------------------------------------------------------------------------------
@@ -425,14 +356,37 @@ using namespace annlite;
 
 static unsigned long long *g_graph_f32_stats = nullptr;  // debug only (ANNLITE_DEBUG_COUNTERS): leaked 16-byte device buffer
 
-template <int E, bool L2>
-static int launch_walk(const float *q, int64_t B, int64_t D, const float *x, int64_t N, const uint32_t *links, int lpn, const uint32_t *seeds,
-                       int n_seeds, const uint32_t *valid, int ef, int hash_bits, int64_t *out_ids, float *out_dist,
-                       unsigned long long *stats, hipStream_t st) {
-    const size_t q_bytes = ((size_t)D * 4 + 15) & ~(size_t)15;
-    const size_t per_wave = q_bytes + ((size_t)4 << hash_bits) + (size_t)E * 64 * 12 + 1024;
-    // waves per workgroup: the count (<= 4) that lets most waves share a CU's 160 KB -- 21 KB per wave (ef > 128) is one workgroup of
-    // four per CU but two of three
+// *stats: the float walk's debug counters, zeroed on `st` (NULL unless ANNLITE_DEBUG_COUNTERS)
+static int f32_walk_stats(hipStream_t st, unsigned long long **stats) {
+    *stats = nullptr;
+    if (knobs().debug_counters) {
+        if (!g_graph_f32_stats) ANNLITE_HIP_TRY(hipMalloc((void **)&g_graph_f32_stats, 16));
+        ANNLITE_HIP_TRY(hipMemsetAsync(g_graph_f32_stats, 0, 16, st));
+        *stats = g_graph_f32_stats;
+    }
+    return ANNLITE_OK;
+}
+
+// what the two walks check alike, after their own checks on ef / ef_route / admit; a batch of B = 0 may come without pointers
+static int f32_walk_check(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
+                          const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
+                          const int64_t *out_ids_dev, const float *out_dist_dev) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(D >= 1 && D <= 2048, "the float graph takes 1 <= D <= 2048 (D = %lld)", (long long)D);
+    ANNLITE_REQUIRE(links_per_node >= 1 && links_per_node <= 64, "links_per_node in [1, 64] (%d)", links_per_node);
+    ANNLITE_REQUIRE(n_seeds >= 1 && n_seeds < (1ll << 31) && N < (1ll << 32) - 1, "bad graph");
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(B < (1ll << 31), "bad B");
+    ANNLITE_REQUIRE(queries_dev && links_dev && seeds_dev && out_ids_dev && out_dist_dev && (N == 0 || vectors_dev), "null device pointer");
+    return ANNLITE_OK;
+}
+
+// One wave per query of either walk kernel `fn` (`name`: for the launch's error message), whose list has E registers per lane.
+// Waves per workgroup: the count (<= 4) that lets most waves share a CU's 160 KB -- 21 KB per wave (ef > 128) is one workgroup of
+// four per CU but two of three.  (The filtered walk's R lives in registers and shares C's merge scratch: same LDS.)
+template <class... KA, class... A>
+static int launch_f32_walk(void (*fn)(KA...), const char *name, int E, int64_t B, int64_t D, int hash_bits, hipStream_t st, A... args) {
+    const size_t per_wave = f32_walk_lds_per_wave(E, (int)D, hash_bits);
     const size_t lds_cu = (size_t)160 * 1024;
     int wpb = 0, best = 0;
     for (int w = 4; w >= 1; --w) {
@@ -441,39 +395,29 @@ static int launch_walk(const float *q, int64_t B, int64_t D, const float *x, int
     }
     ANNLITE_REQUIRE(wpb >= 1, "query, visited table and merge scratch do not fit the LDS");
     const size_t lds = wpb * per_wave;
-    auto fn = graph_f32_search_kernel<E, L2>;
     ANNLITE_HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(fn, dim3((unsigned)((B + wpb - 1) / wpb)), dim3(wpb * 64), lds, st, q, (int)B, (int)D, x, N, links, lpn, seeds,
-                       n_seeds, valid, ef, hash_bits, out_ids, out_dist, stats);
-    return launch_status("graph_f32_search_kernel");
+    hipLaunchKernelGGL(fn, dim3((unsigned)((B + wpb - 1) / wpb)), dim3(wpb * 64), lds, st, args...);
+    return launch_status(name);
 }
 
 extern "C" int annlite_graph_f32_search(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
                                         const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
                                         const uint32_t *valid_bits_dev, int ef, int64_t *out_ids_dev, float *out_dist_dev, void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
     ANNLITE_REQUIRE(B >= 0 && N >= 0 && ef >= 1 && ef <= 256, "bad B=%lld N=%lld ef=%d (ef <= 256)", (long long)B, (long long)N, ef);
-    ANNLITE_REQUIRE(D >= 1 && D <= 2048, "the float graph takes 1 <= D <= 2048 (D = %lld)", (long long)D);
-    ANNLITE_REQUIRE(links_per_node >= 1 && links_per_node <= 64, "links_per_node in [1, 64] (%d)", links_per_node);
-    ANNLITE_REQUIRE(n_seeds >= 1 && n_seeds < (1ll << 31) && N < (1ll << 32) - 1, "bad graph");
+    if (int rc = f32_walk_check(metric, queries_dev, B, D, vectors_dev, N, links_dev, links_per_node, seeds_dev, n_seeds, out_ids_dev,
+                                out_dist_dev))
+        return rc;
     if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(B < (1ll << 31), "bad B");
-    ANNLITE_REQUIRE(queries_dev && links_dev && seeds_dev && out_ids_dev && out_dist_dev && (N == 0 || vectors_dev), "null device pointer");
     hipStream_t st = (hipStream_t)stream;
-    int hash_bits = ef <= 208 ? 12 : 13;  // (graph.hip: 4096 entries beside a list of up to 208, 8192 beyond; a full table only costs re-evaluations)
-    if (knobs().graph_hash_bits >= 0) hash_bits = knobs().graph_hash_bits;
-    if (hash_bits < 4) hash_bits = 4;
-    if (hash_bits > 15) hash_bits = 15;
+    const int hash_bits = graph_walk_hash_bits(ef);
     unsigned long long *stats = nullptr;
-    if (knobs().debug_counters) {
-        if (!g_graph_f32_stats) ANNLITE_HIP_TRY(hipMalloc((void **)&g_graph_f32_stats, 16));
-        ANNLITE_HIP_TRY(hipMemsetAsync(g_graph_f32_stats, 0, 16, st));
-        stats = g_graph_f32_stats;
-    }
+    if (int rc = f32_walk_stats(st, &stats)) return rc;
     const bool l2 = metric == ANNLITE_METRIC_EUCLIDEAN;
-#define ANNLITE_WALK_ARGS queries_dev, B, D, vectors_dev, N, links_dev, links_per_node, seeds_dev, (int)n_seeds, valid_bits_dev, ef, hash_bits, \
-                          out_ids_dev, out_dist_dev, stats, st
-#define ANNLITE_WALK(EE) (l2 ? launch_walk<EE, true>(ANNLITE_WALK_ARGS) : launch_walk<EE, false>(ANNLITE_WALK_ARGS))
+#define ANNLITE_WALK_ARGS B, D, hash_bits, st, queries_dev, (int)B, (int)D, vectors_dev, N, links_dev, links_per_node, seeds_dev, (int)n_seeds, \
+                          valid_bits_dev, ef, hash_bits, out_ids_dev, out_dist_dev, stats
+#define ANNLITE_WALK(EE)                                                                                   \
+    (l2 ? launch_f32_walk(graph_f32_search_kernel<EE, true>, "graph_f32_search_kernel", EE, ANNLITE_WALK_ARGS) \
+        : launch_f32_walk(graph_f32_search_kernel<EE, false>, "graph_f32_search_kernel", EE, ANNLITE_WALK_ARGS))
     if (ef <= 64) return ANNLITE_WALK(1);
     if (ef <= 128) return ANNLITE_WALK(2);
     return ANNLITE_WALK(4);
@@ -481,57 +425,27 @@ extern "C" int annlite_graph_f32_search(int metric, const float *queries_dev, in
 #undef ANNLITE_WALK_ARGS
 }
 
-template <int E, int ER, bool L2>
-static int launch_walk_admit(const float *q, int64_t B, int64_t D, const float *x, int64_t N, const uint32_t *links, int lpn,
-                             const uint32_t *seeds, int n_seeds, const uint32_t *admit, int ef_route, int ef, int hash_bits, int64_t *out_ids,
-                             float *out_dist, float *out_route_worst, unsigned long long *stats, hipStream_t st) {
-    // launch_walk's LDS per wave and waves per workgroup: R lives in registers and shares C's merge scratch
-    const size_t q_bytes = ((size_t)D * 4 + 15) & ~(size_t)15;
-    const size_t per_wave = q_bytes + ((size_t)4 << hash_bits) + (size_t)E * 64 * 12 + 1024;
-    const size_t lds_cu = (size_t)160 * 1024;
-    int wpb = 0, best = 0;
-    for (int w = 4; w >= 1; --w) {
-        const int waves = (int)(lds_cu / (w * per_wave)) * w;
-        if (waves > best) best = waves, wpb = w;
-    }
-    ANNLITE_REQUIRE(wpb >= 1, "query, visited table and merge scratch do not fit the LDS");
-    const size_t lds = wpb * per_wave;
-    auto fn = graph_f32_admit_kernel<E, ER, L2>;
-    ANNLITE_HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(fn, dim3((unsigned)((B + wpb - 1) / wpb)), dim3(wpb * 64), lds, st, q, (int)B, (int)D, x, N, links, lpn, seeds,
-                       n_seeds, admit, ef_route, ef, hash_bits, out_ids, out_dist, out_route_worst, stats);
-    return launch_status("graph_f32_admit_kernel");
-}
-
 extern "C" int annlite_graph_f32_search_admit(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
                                               const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
                                               const uint32_t *admit_bits_dev, int ef_route, int ef, int64_t *out_ids_dev,
                                               float *out_dist_dev, float *out_route_worst_dev, void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
     ANNLITE_REQUIRE(B >= 0 && N >= 0 && ef >= 1 && ef <= ef_route && ef_route <= 256, "bad B=%lld N=%lld ef=%d ef_route=%d (ef <= ef_route <= 256)",
                     (long long)B, (long long)N, ef, ef_route);
-    ANNLITE_REQUIRE(D >= 1 && D <= 2048, "the float graph takes 1 <= D <= 2048 (D = %lld)", (long long)D);
-    ANNLITE_REQUIRE(links_per_node >= 1 && links_per_node <= 64, "links_per_node in [1, 64] (%d)", links_per_node);
-    ANNLITE_REQUIRE(n_seeds >= 1 && n_seeds < (1ll << 31) && N < (1ll << 32) - 1, "bad graph");
     ANNLITE_REQUIRE(admit_bits_dev != nullptr, "admit_bits_dev is NULL (a walk without a filter is annlite_graph_f32_search)");
+    if (int rc = f32_walk_check(metric, queries_dev, B, D, vectors_dev, N, links_dev, links_per_node, seeds_dev, n_seeds, out_ids_dev,
+                                out_dist_dev))
+        return rc;
     if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(B < (1ll << 31), "bad B");
-    ANNLITE_REQUIRE(queries_dev && links_dev && seeds_dev && out_ids_dev && out_dist_dev && (N == 0 || vectors_dev), "null device pointer");
     hipStream_t st = (hipStream_t)stream;
-    int hash_bits = ef_route <= 208 ? 12 : 13;  // (annlite_graph_f32_search's table at ef = ef_route)
-    if (knobs().graph_hash_bits >= 0) hash_bits = knobs().graph_hash_bits;
-    if (hash_bits < 4) hash_bits = 4;
-    if (hash_bits > 15) hash_bits = 15;
+    const int hash_bits = graph_walk_hash_bits(ef_route);  // (annlite_graph_f32_search's table at ef = ef_route)
     unsigned long long *stats = nullptr;
-    if (knobs().debug_counters) {
-        if (!g_graph_f32_stats) ANNLITE_HIP_TRY(hipMalloc((void **)&g_graph_f32_stats, 16));
-        ANNLITE_HIP_TRY(hipMemsetAsync(g_graph_f32_stats, 0, 16, st));
-        stats = g_graph_f32_stats;
-    }
+    if (int rc = f32_walk_stats(st, &stats)) return rc;
     const bool l2 = metric == ANNLITE_METRIC_EUCLIDEAN;
-#define ANNLITE_WALK_ARGS queries_dev, B, D, vectors_dev, N, links_dev, links_per_node, seeds_dev, (int)n_seeds, admit_bits_dev, ef_route, ef, \
-                          hash_bits, out_ids_dev, out_dist_dev, out_route_worst_dev, stats, st
-#define ANNLITE_WALK(EE, ER) (l2 ? launch_walk_admit<EE, ER, true>(ANNLITE_WALK_ARGS) : launch_walk_admit<EE, ER, false>(ANNLITE_WALK_ARGS))
+#define ANNLITE_WALK_ARGS B, D, hash_bits, st, queries_dev, (int)B, (int)D, vectors_dev, N, links_dev, links_per_node, seeds_dev, (int)n_seeds, \
+                          admit_bits_dev, ef_route, ef, hash_bits, out_ids_dev, out_dist_dev, out_route_worst_dev, stats
+#define ANNLITE_WALK(EE, ER)                                                                                  \
+    (l2 ? launch_f32_walk(graph_f32_admit_kernel<EE, ER, true>, "graph_f32_admit_kernel", EE, ANNLITE_WALK_ARGS) \
+        : launch_f32_walk(graph_f32_admit_kernel<EE, ER, false>, "graph_f32_admit_kernel", EE, ANNLITE_WALK_ARGS))
     // C's registers per lane from ef_route, R's from ef, as annlite_graph_f32_search chooses its own (ef <= ef_route: ER <= E)
     if (ef_route <= 64) return ANNLITE_WALK(1, 1);
     if (ef_route <= 128) return ef <= 64 ? ANNLITE_WALK(2, 1) : ANNLITE_WALK(2, 2);

@@ -292,10 +292,9 @@ __device__ __forceinline__ void pq_walk_add_stats(unsigned long long *stats, con
 }
 
 // host side, graph.hip: the walk's argument checks (n_seeds, M, Ks, record size, expansion width) and what a launch needs beside
-// its lists -- the visited table's size for a routing list of `ef` places, the debug counters' buffer (NULL unless
-// ANNLITE_DEBUG_COUNTERS), zeroed on `st`.
+// its lists (beside graph_beam.h's graph_walk_hash_bits) -- the debug counters' buffer (NULL unless ANNLITE_DEBUG_COUNTERS), zeroed
+// on `st`.
 int graph_walk_check(bool packed, int links_per_node, int64_t n_seeds, int64_t N, int64_t M, int64_t Ks, int64_t B, int width);
-int graph_walk_hash_bits(int ef);
 int graph_walk_stats(hipStream_t st, unsigned long long **stats);
 
 }  // namespace annlite

@@ -159,6 +159,16 @@ def graph_search_packed(packed: torch.Tensor, links_per_node: int, seeds: torch.
     return out_i, out_d
 
 
+def _admit_walk_outputs(B: int, ef: int, N: int, admit_bits: Optional[torch.Tensor], route_worst: Optional[torch.Tensor],
+                        device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """What the two filtered walks ask of ``admit_bits`` and ``route_worst``, and their (ids i64 [B, ef], dist f32 [B, ef]) outputs."""
+    assert route_worst is None or (route_worst.dtype == torch.float32 and route_worst.is_contiguous() and route_worst.numel() == B
+                                   and route_worst.device == device)
+    # (None goes to the library, which refuses it)
+    assert admit_bits is None or (admit_bits.is_contiguous() and admit_bits.element_size() == 4 and admit_bits.numel() * 32 >= N)
+    return torch.empty((B, ef), dtype=torch.int64, device=device), torch.empty((B, ef), dtype=torch.float32, device=device)
+
+
 def graph_search_packed_admit(packed: torch.Tensor, links_per_node: int, seeds: torch.Tensor, codes: torch.Tensor, lut_bmk: torch.Tensor,
                               ef_route: int, ef: int, admit_bits: torch.Tensor, n_rows: Optional[int] = None, expand_width: int = 1,
                               route_worst: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -173,12 +183,7 @@ def graph_search_packed_admit(packed: torch.Tensor, links_per_node: int, seeds: 
     assert codes.shape[1] == M
     N = codes.shape[0] if n_rows is None else int(n_rows)
     assert N <= codes.shape[0] and N <= packed.shape[0]
-    assert route_worst is None or (route_worst.dtype == torch.float32 and route_worst.is_contiguous() and route_worst.numel() == B
-                                   and route_worst.device == codes.device)
-    # (None goes to the library, which refuses it)
-    assert admit_bits is None or (admit_bits.is_contiguous() and admit_bits.element_size() == 4 and admit_bits.numel() * 32 >= N)
-    out_i = torch.empty((B, ef), dtype=torch.int64, device=codes.device)
-    out_d = torch.empty((B, ef), dtype=torch.float32, device=codes.device)
+    out_i, out_d = _admit_walk_outputs(B, ef, N, admit_bits, route_worst, codes.device)
     check(lib().annlite_graph_search_packed_admit(packed.data_ptr(), int(links_per_node), seeds.data_ptr(), seeds.numel(),
                                                   codes.data_ptr(), N, M, Ks, _ptr(admit_bits), lut_bmk.data_ptr(), B, int(ef_route),
                                                   int(ef), int(expand_width), out_i.data_ptr(), out_d.data_ptr(), _ptr(route_worst),
@@ -262,12 +267,7 @@ def graph_f32_search_admit(metric: int, queries: torch.Tensor, vectors: torch.Te
     assert vectors.shape[1] == D
     N = vectors.shape[0] if n_rows is None else int(n_rows)
     assert N <= vectors.shape[0] and N <= links.shape[0]
-    assert route_worst is None or (route_worst.dtype == torch.float32 and route_worst.is_contiguous() and route_worst.numel() == B
-                                   and route_worst.device == vectors.device)
-    # (None goes to the library, which refuses it)
-    assert admit_bits is None or (admit_bits.is_contiguous() and admit_bits.element_size() == 4 and admit_bits.numel() * 32 >= N)
-    out_i = torch.empty((B, ef), dtype=torch.int64, device=vectors.device)
-    out_d = torch.empty((B, ef), dtype=torch.float32, device=vectors.device)
+    out_i, out_d = _admit_walk_outputs(B, ef, N, admit_bits, route_worst, vectors.device)
     check(lib().annlite_graph_f32_search_admit(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, links.data_ptr(),
                                                links.shape[1] - 1, seeds.data_ptr(), seeds.numel(), _ptr(admit_bits), int(ef_route),
                                                int(ef), out_i.data_ptr(), out_d.data_ptr(), _ptr(route_worst), stream_ptr()),

@@ -8,7 +8,7 @@ Two sorted lists:
     then ``width`` nodes expanded per step (the best unexpanded entries among the ``cap`` live ones), a step's unseen neighbours
     tested against C's worst entry before any of them is inserted; 1 / 2 / 3 / 4 registers per lane as there (3: the pair walk's
     list for 128 < ef <= 192).  ``admit`` never touches it.
-  * R, the result list of ``ef`` places (``ResultList``): ``tests/_refs_admit.py``'s second list.  Every batch C is offered R is
+  * R, the result list of ``ef`` places (``ResultList``; ``tests/_refs_admit.py`` is this walk at width 1).  Every batch C is offered R is
     offered too, restricted to admitted nodes; of those, the ones that beat R's worst entry AS IT IS NOW and are not in R already
     (nor came earlier in the same batch) are merged in.
 
