@@ -98,6 +98,7 @@ SYMBOLS = (
     'annlite_kernel_rev',
     'annlite_debug_counters',
     'annlite_debug_split_counters',
+    'annlite_debug_q8_split_width',
     'annlite_debug_timeline',
     'annlite_debug_items',
     'annlite_debug_prep_timeline',
@@ -232,6 +233,7 @@ def lib() -> ctypes.CDLL:
     L.annlite_kernel_rev.argtypes = [ctypes.c_char_p]
     L.annlite_debug_counters.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_debug_split_counters.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    L.annlite_debug_q8_split_width.argtypes = []
     L.annlite_debug_timeline.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_debug_items.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_debug_prep_timeline.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
@@ -467,3 +469,9 @@ def debug_split_counters():
     out = (ctypes.c_uint64 * 4)()
     check(lib().annlite_debug_split_counters(out), 'debug_split_counters')
     return [int(v) for v in out]
+
+
+def debug_q8_split_width():
+    """Sub-spaces in the split step's first phase at the most recent shared-bound M = 16 byte-table launch over skewed rows
+    (10 .. 12), 0 for the one-phase step, -1 before the first such launch (``annlite_debug_q8_split_width``)."""
+    return int(lib().annlite_debug_q8_split_width())

@@ -88,6 +88,8 @@ static Knobs *parse_knobs() {
     k->no_fused_seed = getenv("ANNLITE_NO_FUSED_SEED") != nullptr;
     k->no_prebuilt_tables = getenv("ANNLITE_NO_PREBUILT_TABLES") != nullptr;
     k->q8_split = env_int("ANNLITE_Q8_SPLIT", -1);
+    k->q8_split_rows = env_i64("ANNLITE_Q8_SPLIT_ROWS", -1);
+    if (k->q8_split_rows < 0) k->q8_split_rows = -1;
     k->no_early_merge = getenv("ANNLITE_NO_EARLY_MERGE") != nullptr;
     k->early_merge_patience = env_i64("ANNLITE_EARLY_MERGE_PATIENCE", -1);
     k->no_inkernel_merge = getenv("ANNLITE_NO_INKERNEL_MERGE") != nullptr;

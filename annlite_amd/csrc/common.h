@@ -63,7 +63,11 @@ struct Knobs {
     int seed_chunk_log;         // ANNLITE_SEED_CHUNK_LOG (clamped to [0, 6]; default 3)
     bool no_fused_seed;         // ANNLITE_NO_FUSED_SEED
     bool no_prebuilt_tables;    // ANNLITE_NO_PREBUILT_TABLES
-    int q8_split;               // ANNLITE_Q8_SPLIT=0: the byte-table kernel's one-phase step instead of the split step (M = 16, A/B switch; 12: the split step with 12 sub-spaces first)
+    int q8_split;               // ANNLITE_Q8_SPLIT=0: the byte-table kernel's one-phase step instead of the split step (M = 16, A/B switch); 10, 11, 12: the
+                                // split step with that many sub-spaces first, whatever the launch's slice length; unset or anything else: the width
+                                // comes from the rows one work item scans (q8_split_width, scan_q8.hip)
+    int64_t q8_split_rows;      // ANNLITE_Q8_SPLIT_ROWS: the slice length (rows per work item) from which the split step's first phase takes 10
+                                // sub-spaces instead of 11 (tests and the sweep; unset or negative, -1: the compiled threshold kQ8SplitRows10)
     bool no_early_merge;        // ANNLITE_NO_EARLY_MERGE
     int64_t early_merge_patience;  // ANNLITE_EARLY_MERGE_PATIENCE
     bool no_inkernel_merge;     // ANNLITE_NO_INKERNEL_MERGE

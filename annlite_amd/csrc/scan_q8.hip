@@ -49,6 +49,8 @@
 //         ((half << 16) | (code << 8) | column), candidates as (S, slot, row) entries like the M = 8 shapes.
 #include "scan_lists.h"
 
+#include <atomic>
+
 #ifndef ANNLITE_Q8_EXP
 #define ANNLITE_Q8_EXP 0  // (timing experiments, results wrong: 1 = look-ups without the adds, 2 = adds without the look-ups,
                           // 3 = code rows computed instead of loaded; 5 = one entry per hit row, no enumeration)
@@ -78,9 +80,7 @@ namespace annlite {
 #ifndef ANNLITE_Q8_SPLIT_DEPTH
 #define ANNLITE_Q8_SPLIT_DEPTH 4  // ... in the split step's second phase and where a step finishes in place (rarer: its registers matter more)
 #endif
-#ifndef ANNLITE_Q8_SPLIT_H
-#define ANNLITE_Q8_SPLIT_H 11  // sub-spaces in the split step's first phase (id 1650 with shared bounds and SKEWED rows; ANNLITE_Q8_SPLIT=12: 12)
-#endif
+// (the sub-spaces in the split step's first phase, HS, are chosen per launch: q8_split_width, next to launch_q8_scan)
 #ifndef ANNLITE_Q8_SPLIT_BIAS
 #define ANNLITE_Q8_SPLIT_BIAS 1  // the split step's first phase starts its byte sums from the slots' BIAS bytes and tests bit 7 (q8_st_bound;
                                  // 0: filter words and the round-8 test -- the A/B build of scripts/build_variant.sh)
@@ -2444,6 +2444,31 @@ static int launch_q8(const ScanArgs &a, int grid, hipStream_t st) {
     return launch_status("adc_scan_q8_kernel");
 }
 
+// The split step's first-phase width of one launch (case 1650 below, shared bounds, SKEWED rows): ANNLITE_Q8_SPLIT in {10, 11, 12}
+// forces it (0: the one-phase step); otherwise a monotone step function of the rows ONE work item scans (ScanArgs::slice_rows, the
+// quantity q8_thw_mask is chosen by): 11 below kQ8SplitRows10, 10 from there on.  A short scan spends a larger share of its steps
+// under loose bounds, where a narrower first phase lets more rows through; a long one pays two ds_read_b128 per wave-step and unit
+// of H for nearly all of its steps under tight ones.  The threshold is the smallest swept slice length from which the slowest run
+// at 10 beat the fastest at 11 at every larger one (profiles/r11/h_sweep.txt, DESIGN 10.9: 937 500 and 1 250 000 rows per work item
+// +1.3 %; 625 000 the ranges overlap; 312 500 and 156 250 11 is ahead by 2 %).  9 lost at every length (-5 % at 1.25M rows per work
+// item) and is not compiled.  ANNLITE_Q8_SPLIT_ROWS overrides the threshold (tests, the sweep).  A launch that does not say how
+// long its slices are (slice_rows <= 0) takes 11.
+#ifndef ANNLITE_Q8_SPLIT_ROWS10
+#define ANNLITE_Q8_SPLIT_ROWS10 937500  // rows per work item from which the first phase adds 10 sub-spaces
+#endif
+constexpr int64_t kQ8SplitRows10 = ANNLITE_Q8_SPLIT_ROWS10;
+static_assert(kQ8SplitRows10 > 0, "a launch without a slice length takes the wider first phase");
+static std::atomic<int> g_q8_split_width{-1};  // annlite_debug_q8_split_width
+
+static int q8_split_width(const ScanArgs &a) {
+    const Knobs &kn = knobs();
+    if (kn.q8_split == 0 || (kn.q8_split >= 10 && kn.q8_split <= 12)) return kn.q8_split;
+    const int64_t r10 = kn.q8_split_rows >= 0 ? kn.q8_split_rows : kQ8SplitRows10;
+    return (a.slice_rows > 0 && a.slice_rows >= r10) ? 10 : 11;
+}
+
+extern "C" int annlite_debug_q8_split_width(void) { return g_q8_split_width.load(std::memory_order_relaxed); }
+
 int annlite::launch_q8_scan(int id, bool sk, const ScanArgs &a, int grid, hipStream_t st) {
     switch (id) {
         case 1650:
@@ -2456,9 +2481,16 @@ int annlite::launch_q8_scan(int id, bool sk, const ScanArgs &a, int grid, hipStr
                 if (!sk) return launch_q8<16, 16, false, 2, 1, true>(a, grid, st);
                 // (round 8: the next block's first look-ups issued across the step boundary; 10M rows, the bench, alternating: HS = 12 892-895 k,
                 // 11 906-910, 10 906-911, HEAD's 12 857-861.  ANNLITE_Q8_SPLIT=12 keeps the HS = 12 step as an in-process A/B)
-                if (knobs().q8_split == 0) return launch_q8<16, 16, true, 2, 1, true>(a, grid, st);
-                if (knobs().q8_split == 12 && ANNLITE_Q8_SPLIT_H != 12) return launch_q8<16, 16, true, 2, 1, true, 16, false, 12>(a, grid, st);
-                return launch_q8<16, 16, true, 2, 1, true, 16, false, ANNLITE_Q8_SPLIT_H>(a, grid, st);
+                // (round 11: the width is chosen per launch by the rows a work item scans -- q8_split_width above; the same kernel template at
+                // HS = 10 .. 12, the results bit-identical at every width: a narrower first phase only queues more rows for the unchanged full test)
+                const int hs = q8_split_width(a);
+                g_q8_split_width.store(hs, std::memory_order_relaxed);
+                switch (hs) {
+                    case 0: return launch_q8<16, 16, true, 2, 1, true>(a, grid, st);
+                    case 10: return launch_q8<16, 16, true, 2, 1, true, 16, false, 10>(a, grid, st);
+                    case 12: return launch_q8<16, 16, true, 2, 1, true, 16, false, 12>(a, grid, st);
+                    default: return launch_q8<16, 16, true, 2, 1, true, 16, false, 11>(a, grid, st);
+                }
             }
             return sk ? launch_q8<16, 16, true, 2, 1>(a, grid, st) : launch_q8<16, 16, false, 2, 1>(a, grid, st);
         case 1651:  // M = 16, k <= 16, cell tiles (annlite_ivf_search_topk): one work item per tile of (query, cell) pairs

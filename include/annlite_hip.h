@@ -404,6 +404,10 @@ ANNLITE_API int annlite_debug_counters(uint64_t *out8);
 /* Debug aid, same switch: the byte-table kernel's split step (M = 16, ANNLITE_Q8_SPLIT): [0] rows through its first phase
  * [1] rows that survived it (queued for the second) [2] second-phase wave-steps [3] wave-steps finished in place. */
 ANNLITE_API int annlite_debug_split_counters(uint64_t *out4);
+/* Debug aid (no switch, no device read): the sub-spaces in the first phase of the split step that the most recent shared-bound
+ * launch of the M = 16 byte-table kernel over SKEWED rows took (10 .. 12: ANNLITE_Q8_SPLIT, or chosen by the rows one work item
+ * scans, ANNLITE_Q8_SPLIT_ROWS); 0: the one-phase step; -1: no such launch yet in this process. */
+ANNLITE_API int annlite_debug_q8_split_width(void);
 /* Debug aid, same switch: phase stamps of the byte-table kernel's workgroups (thread 0, 100 MHz wall clock): [0] 2^62 -
  * earliest start, [1] latest end; sums over the work items of [2] start stamp, [3] initialisation + first table build,
  * [4] step loop, [5] wait at the last barrier, [6] list store + merge; [7] work items. */
