@@ -1,4 +1,4 @@
-"""``FlatGpuIndex`` -- exact search over un-quantised float32 vectors on one MI355X: what the reference builds for
+"""``FlatGpuIndex`` -- exact search over un-quantised float vectors on one MI355X: what the reference builds for
 ``AnnLite(n_dim)`` without ``n_subvectors`` (``HnswIndex`` on float vectors, annlite/core/index/hnsw/index.py:139-167; brute-force
 form ``FlatIndex``, annlite/core/index/flat_index.py:15-39: ``cdist`` + ``top_k``).
 
@@ -17,6 +17,14 @@ contracts the rows minus a fixed centre (``centre='mean'``: the mean of the firs
 three bf16 MFMAs, and its slack is relative to ``|x - centre|^2 + |q - centre|^2``; the answer keeps its bits (DESIGN.md section 3.6,
 "split filter").  The all-rows route also serves NaN / infinite queries and searches restricted (``indices=``, deletes) to fewer
 than about k rows in 4096, under either filter.
+
+``dtype=np.float16`` stores the rows in half precision: ``f16 [capacity, D]``, half the bytes in HBM.  Rows are pre-processed as always
+(COSINE: normalised in f32) and rounded to f16 once, to nearest even, when they are written; queries stay f32.  The answer is, bit
+for bit, the f32 index's over the rounded rows widened back to f32: the exact stage keeps its arithmetic, and an f16 row is an exact
+MFMA operand, so the filter (``'f16x2'``: the query carried as two f16 numbers, two f16 MFMAs) needs no centre and no split of the rows
+("f16 rows").  A value beyond the f16 range (65504) is stored as an infinity and behaves as the f32 index
+holding that infinity does.  There is no centre: a common offset destroys f16 data before any filter sees it (1000.37 is stored as
+1000.5) -- centre such data before adding it.
 """
 from pathlib import Path
 from typing import Optional, Tuple, Union
@@ -26,6 +34,7 @@ import torch
 
 from ... import ops
 from ...enums import Metric
+from .base import str2dtype
 from .row_store import RowStoreIndex, empty_answer, float_from_key, float_order_key, like_input, pad_to_k
 
 
@@ -41,11 +50,28 @@ def flat_split_slack_constants(metric: Metric, dim: int) -> Tuple[np.float32, np
     return ops.flat_split_slack(int(Metric(metric)), dim)
 
 
+def flat_f16_slack_constants(metric: Metric, dim: int) -> Tuple[np.float32, np.float32]:
+    """``(c_rel, c_abs)`` of the f16 filter (``dtype=np.float16``); its slack has a third, per-query term the library computes,
+    ``1.001 * 2^-13 * sum |q_j|`` (``annlite_flat_f16_slack``; derivation: DESIGN.md section 3.6, "f16 rows")."""
+    return ops.flat_f16_slack(int(Metric(metric)), dim)
+
+
+def is_f16(dtype) -> bool:
+    """whether a ``dtype=`` argument (any spelling ``base.str2dtype`` takes) selects half-precision rows"""
+    try:
+        return np.dtype(str2dtype(dtype) if isinstance(dtype, str) else dtype) == np.float16
+    except TypeError:
+        return False
+
+
 class FlatGpuIndex(RowStoreIndex):
     """
+    :param dtype: ``np.float32`` (default) or ``np.float16``: how the rows are stored (module docstring).  ``np.float16`` takes neither
+        ``flat_filter='bf16x3'`` nor a ``centre`` and needs ``dim <= 32768``; any other dtype stores f32, as before.
     :param flat_filter: ``'f32'`` (default): the f32 MFMA filter.  ``'bf16x3'``: the split-bf16 filter over centred rows -- the same
         answer bit for bit, a slack that does not grow with a common offset of the data, ``dim <= 32768``.  Searches with
-        ``limit > 64`` keep the f32 filter under either value: offset data stays slow there.
+        ``limit > 64`` keep the f32 filter under either value: offset data stays slow there.  ``'f16x2'``: the filter over f16 rows --
+        what ``dtype=np.float16`` runs (and reports here), at every ``limit``; with f32 rows it is an error.
     :param centre: what ``'bf16x3'`` subtracts from rows and queries before it splits them, EUCLIDEAN only -- INNER_PRODUCT and COSINE
         are not invariant under a shift and run the split filter on the values themselves.  ``'mean'`` (default): the f32 mean of the
         first ``add_with_ids`` batch, frozen until ``reset()``; an array ``[dim]``: that point; ``None``: no centring.  Any centre gives
@@ -54,14 +80,26 @@ class FlatGpuIndex(RowStoreIndex):
     """
     FORMAT = 'annlite_amd.FlatGpuIndex/1'
     STATE_KEYS = ('dim', 'metric')
-    FLAT_FILTERS = ('f32', 'bf16x3')
+    FLAT_FILTERS = ('f32', 'bf16x3', 'f16x2')
     SPLIT_MAX_DIM = 32768    # (annlite_flat_split_slack: the range of the slack's derivation)
     FILTER_MIN_ROWS = 4097   # (kFlatSample + 1 in flat.hip: smaller tables are answered by exact sums, no filter runs)
 
     def __init__(self, dim: int, dtype: np.dtype = np.float32, metric: Metric = Metric.COSINE,
                  index_file: Optional[Union[str, Path]] = None, flat_filter: str = 'f32', centre='mean', **kwargs):
         if flat_filter not in self.FLAT_FILTERS:
-            raise ValueError(f"flat_filter={flat_filter!r}: 'f32' (the f32 MFMA filter) or 'bf16x3' (the split-bf16 filter over centred rows)")
+            raise ValueError(f"flat_filter={flat_filter!r}: 'f32' (the f32 MFMA filter), 'bf16x3' (the split-bf16 filter over centred rows) "
+                             "or, with dtype=np.float16, 'f16x2'")
+        self._f16 = is_f16(dtype)
+        if self._f16:
+            if flat_filter == 'bf16x3':
+                raise ValueError("flat_filter='bf16x3' splits f32 rows: dtype=np.float16 runs 'f16x2'")
+            if not (isinstance(centre, str) and centre == 'mean'):
+                raise ValueError(f'centre={centre!r} with dtype=np.float16: f16 rows have no centre (centre the data before adding it)')
+            if dim > self.SPLIT_MAX_DIM:
+                raise ValueError(f'dtype=np.float16 takes dim <= {self.SPLIT_MAX_DIM}')
+            flat_filter = 'f16x2'
+        elif flat_filter == 'f16x2':
+            raise ValueError("flat_filter='f16x2' is the filter over f16 rows: pass dtype=np.float16")
         if isinstance(centre, str) and centre != 'mean':
             raise ValueError(f"centre={centre!r}: 'mean', None or an array of {dim} coordinates")
         if centre is not None and not isinstance(centre, str):
@@ -72,7 +110,7 @@ class FlatGpuIndex(RowStoreIndex):
             raise ValueError(f"flat_filter='bf16x3' takes dim <= {self.SPLIT_MAX_DIM}")
         self.flat_filter = flat_filter
         self.centre = centre
-        self.last_flat_filter = None  # 'f32' / 'bf16x3': the filter of the last search_batch; None: it ran none
+        self.last_flat_filter = None  # 'f32' / 'bf16x3' / 'f16x2': the filter of the last search_batch; None: it ran none
         self._centre_dev = None
         self._centred = flat_filter == 'bf16x3' and Metric(metric) == Metric.EUCLIDEAN and centre is not None
         super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
@@ -106,10 +144,14 @@ class FlatGpuIndex(RowStoreIndex):
     # ------------------------------------------------------------------ storage (row_store.py)
     def _columns(self):
         """``_cnorms``: the norms of the centred rows, kept only where the split filter has a centre (it reads ``_norms`` otherwise)"""
-        return {'_vectors': ((self.dim,), torch.float32), '_norms': ((), torch.float32),
+        return {'_vectors': ((self.dim,), torch.float16 if self._f16 else torch.float32), '_norms': ((), torch.float32),
                 '_cnorms': ((), torch.float32) if self._centred else None}
 
     def _write_rows(self, x, ids):
+        if self._f16:  # (rounded once, to nearest even; beyond the f16 range: an infinity)
+            self._vectors[ids] = x.to(torch.float16)
+            ops.flat_row_norms_f16(self._vectors, ids=ids, out=self._norms)
+            return
         self._vectors[ids] = x  # flat_index.py:41-50 `_data[ids] = x`
         ops.flat_row_norms(self._vectors, ids=ids, out=self._norms)
         if self._centred:
@@ -117,7 +159,8 @@ class FlatGpuIndex(RowStoreIndex):
             ops.flat_centred_norms(self._vectors, self._centre_dev, ids=ids, out=self._cnorms)
 
     def _dump_state(self, N):
-        """vectors as stored (normalised for COSINE); norms are recomputed on load.  ``centre`` (optional key): the split filter's"""
+        """vectors as stored (normalised for COSINE; in the index's dtype); norms are recomputed on load.  ``centre`` (optional key):
+        the split filter's"""
         state = {'vectors': self._vectors[:N].cpu().numpy()}
         if self._centre_dev is not None:
             state['centre'] = self.centre_
@@ -126,7 +169,11 @@ class FlatGpuIndex(RowStoreIndex):
     def _load_state(self, state, N):
         self._centre_dev = None
         if N:
-            self._vectors[:N] = self._to_dev(state['vectors'])
+            # (a file of the other dtype is converted: f32 into an f16 index rounds, f16 into an f32 index widens)
+            self._vectors[:N] = self._to_dev(state['vectors']).to(self._vectors.dtype)
+            if self._f16:
+                ops.flat_row_norms_f16(self._vectors, n=N, out=self._norms)
+                return
             ops.flat_row_norms(self._vectors, n=N, out=self._norms)
             if self._centred:  # (a file without the key -- an older one, an f32 index's: the mean of the rows it holds)
                 self._fix_centre(self._vectors[:N], stored=state.get('centre'))
@@ -157,7 +204,12 @@ class FlatGpuIndex(RowStoreIndex):
             d, i = empty_answer(B, k, dev)
         else:
             valid = self._valid if indices is None else self._filter_bits(indices)
-            if k <= 64 and self.flat_filter == 'bf16x3':
+            if k <= 64 and self._f16:
+                d, i = ops.flat_search_topk_f16(int(self.metric), q, self._vectors, self._norms, k, valid_bits=valid, n_rows=N,
+                                                sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
+                self._overflowed = None
+                self.last_flat_filter = 'f16x2' if N >= self.FILTER_MIN_ROWS else None
+            elif k <= 64 and self.flat_filter == 'bf16x3':
                 d, i = ops.flat_search_topk_split(int(self.metric), q, self._vectors, self._cnorms if self._centred else self._norms, k,
                                                   centre=self._centre_dev if self._centred else None, valid_bits=valid, n_rows=N,
                                                   sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
@@ -172,11 +224,14 @@ class FlatGpuIndex(RowStoreIndex):
                 d, i = self._search_large_k(q, k, valid, N)
         return like_input(is_np, d, i)
 
+    def _gather_dist(self, q, cand):
+        return (ops.exact_gather_dist_f16 if self._f16 else ops.exact_gather_dist)(int(self.metric), q, self._vectors, cand)
+
     def _keyed_topk(self, q, cand, ok, kk):
         """The ``kk`` nearest of each query's candidates ``cand`` i64 [b, R] (``ok``: which entries count) by exact distance
         (``annlite_exact_gather_dist``: a wave per pair, the numbers of the k <= 64 path): i64 keys -- order-preserving bits of the
         distance << 32 | row id, unique, so the smallest keys ARE the (distance, id) order, NaN last -- and one ``torch.topk``."""
-        dist = ops.exact_gather_dist(int(self.metric), q, self._vectors, cand)
+        dist = self._gather_dist(q, cand)
         # (no `+ 0.0` before keying, unlike PQFlatGpuIndex._search_large_k: key(-0.0) < key(+0.0) is annlite_rerank_topk's order,
         # whose numbers this path returns)
         key_none = torch.iinfo(torch.int64).max
@@ -219,14 +274,19 @@ class FlatGpuIndex(RowStoreIndex):
             bounds = []
             for b0 in range(0, B, chunk):
                 nb = min(chunk, B - b0)
-                ds = ops.exact_gather_dist(int(self.metric), q[b0:b0 + nb].contiguous(), self._vectors, sample[None, :].expand(nb, -1).contiguous())
+                ds = self._gather_dist(q[b0:b0 + nb].contiguous(), sample[None, :].expand(nb, -1).contiguous())
                 ds = torch.where(s_ok[None, :], torch.nan_to_num(ds, nan=float('inf'), posinf=float('inf'), neginf=float('-inf')),
                                  torch.full_like(ds, float('inf')))
                 bounds.append(torch.topk(ds, kk, dim=1, largest=False).values[:, kk - 1] if sample.numel() >= kk
                               else torch.full((nb,), float('inf'), device=dev))
             bound = torch.cat(bounds).contiguous()  # (+inf -- fewer than k valid sampled rows, NaN distances -- passes everything)
-            cand32, count = ops.flat_filter(int(self.metric), q, self._vectors, self._norms, bound, valid_bits=valid, n_rows=N)
-            self.last_flat_filter = 'f32'  # (whatever `flat_filter` says: offset data stays slow for limit > 64)
+            if self._f16:
+                cand32, count = ops.flat_filter_f16(int(self.metric), q, self._vectors, self._norms, bound, valid_bits=valid, n_rows=N,
+                                                    workspace=self._ws)[:2]
+                self.last_flat_filter = 'f16x2'
+            else:
+                cand32, count = ops.flat_filter(int(self.metric), q, self._vectors, self._norms, bound, valid_bits=valid, n_rows=N)
+                self.last_flat_filter = 'f32'  # ('bf16x3' too: offset data stays slow for limit > 64)
             over = count > cap
             ok = torch.arange(cap, device=dev)[None, :] < count[:, None]
             cand = torch.where(ok, cand32.to(torch.int64), torch.full((1, 1), -1, dtype=torch.int64, device=dev))

@@ -29,7 +29,7 @@ import torch
 from ... import ops
 from ...enums import Metric
 from .filter_walk import FilterWalkMixin
-from .flat_gpu import FlatGpuIndex
+from .flat_gpu import FlatGpuIndex, is_f16
 from .row_store import empty_answer, like_input, ranked_answer
 
 
@@ -54,6 +54,9 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
         if not 1 <= int(dim) <= self.MAX_DIM:
             raise ValueError(f'dim={dim}: the float graph takes 1 <= dim <= {self.MAX_DIM}')
         self._check_filter_search(filter_search, "the parent's exact filtered search")
+        if is_f16(dtype):
+            raise NotImplementedError('dtype=np.float16: the float graph walks and builds over f32 rows only (half-precision rows exist '
+                                      'in the exhaustive FlatGpuIndex: no graph, n_cells=1)')
         super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
         self.ef_construction = int(ef_construction)  # hnsw/index.py:66-69
         self.ef_search = int(ef_search)

@@ -28,7 +28,7 @@ from ... import ops
 from ...enums import Metric
 from ..codec.vq import VQCodec
 from .cells import CellColumnMixin
-from .flat_gpu import FlatGpuIndex
+from .flat_gpu import FlatGpuIndex, is_f16
 from .row_store import empty_answer, like_input, pad_to_k
 
 
@@ -46,6 +46,9 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         # over cell tiles is not built)
         kwargs.pop('flat_filter', None)
         kwargs.pop('centre', None)
+        if is_f16(kwargs.get('dtype', 'float32')):
+            raise NotImplementedError('dtype=np.float16: the cell-tile kernels read f32 rows only (half-precision rows exist in the '
+                                      'exhaustive FlatGpuIndex: no graph, n_cells=1)')
         super().__init__(dim, metric=metric, **kwargs)
 
     # ------------------------------------------------------------------ sealed (cell-grouped) view

@@ -174,8 +174,10 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const float *__restr
 }
 
 // ---- exact distances over candidate lists: one wave per (query, candidate) -------------------------
+// T: the row type, float or _Float16 (FlatGpuIndex's half-precision row store): an f16 value widens exactly, the rest is the f32 form's.
+template <class T>
 __global__ __launch_bounds__(256) void exact_gather_kernel(int metric, const float *__restrict__ q, int B, int D,
-                                                          const float *__restrict__ x, int64_t N,
+                                                          const T *__restrict__ x, int64_t N,
                                                           const int64_t *__restrict__ cand, int R,
                                                           float *__restrict__ out) {
     const int lane = threadIdx.x & 63;
@@ -188,15 +190,15 @@ __global__ __launch_bounds__(256) void exact_gather_kernel(int metric, const flo
         return;
     }
     const float *qr = q + (int64_t)b * D;
-    const float *xr = x + row * D;
+    const T *xr = x + row * D;
     float s = 0.f;
     if (metric == ANNLITE_METRIC_EUCLIDEAN) {
         for (int j = lane; j < D; j += 64) {
-            const float d = xr[j] - qr[j];
+            const float d = (float)xr[j] - qr[j];
             s = __builtin_fmaf(d, d, s);
         }
     } else {
-        for (int j = lane; j < D; j += 64) s = __builtin_fmaf(xr[j], qr[j], s);
+        for (int j = lane; j < D; j += 64) s = __builtin_fmaf((float)xr[j], qr[j], s);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -375,7 +377,20 @@ extern "C" int annlite_exact_gather_dist(int metric, const float *queries_dev, i
     if (B * R == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && cand_dev && out_dev && (N == 0 || vectors_dev), "null device pointer");
     const int64_t total = B * R;
-    hipLaunchKernelGGL(exact_gather_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(exact_gather_kernel<float>, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        metric, queries_dev, (int)B, (int)D, vectors_dev, N, cand_dev, (int)R, out_dev);
+    return launch_status("exact_gather_kernel");
+}
+
+extern "C" int annlite_exact_gather_dist_f16(int metric, const float *queries_dev, int64_t B, int64_t D,
+                                             const void *vectors_f16_dev, int64_t N, const int64_t *cand_dev, int64_t R,
+                                             float *out_dev, void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && R >= 0, "bad shape");
+    if (B * R == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && cand_dev && out_dev && (N == 0 || vectors_f16_dev), "null device pointer");
+    const int64_t total = B * R;
+    hipLaunchKernelGGL(exact_gather_kernel<_Float16>, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       metric, queries_dev, (int)B, (int)D, (const _Float16 *)vectors_f16_dev, N, cand_dev, (int)R, out_dev);
     return launch_status("exact_gather_kernel");
 }

@@ -11,6 +11,8 @@
 // of the row offsets.
 #include <math.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace annlite {
@@ -26,8 +28,10 @@ constexpr double kFlatGrowth = 32.0;      // a stage's row set is at most this m
 
 // ---- |x|^2 per row: the lane-strided fmaf chain + butterfly of the exact kernels (relative error <= gamma(ceil(D/64) + 6)) ----
 // CENTRED: the same chain over c_j = fl(x_j - mu_j), the values the split filter contracts (second half of the filter section).
-template <bool CENTRED>
-__global__ __launch_bounds__(256) void flat_norms_kernel(const float *__restrict__ x, int D, const int64_t *__restrict__ ids, int64_t n,
+// T: the row type, float or _Float16 (a half-precision row store, "f16 rows" below): an f16 value widens exactly, and everything after
+// the load is the f32 form's, operation for operation.
+template <bool CENTRED, class T = float>
+__global__ __launch_bounds__(256) void flat_norms_kernel(const T *__restrict__ x, int D, const int64_t *__restrict__ ids, int64_t n,
                                                         int64_t id_base, int64_t capacity, const float *__restrict__ mu,
                                                         float *__restrict__ norms) {
     const int lane = threadIdx.x & 63;
@@ -35,10 +39,11 @@ __global__ __launch_bounds__(256) void flat_norms_kernel(const float *__restrict
     if (i >= n) return;
     const int64_t row = ids ? ids[i] : id_base + i;
     if (row < 0 || row >= capacity) return;
-    const float *xr = x + row * D;
+    const T *xr = x + row * D;
     float s = 0.f;
     for (int j = lane; j < D; j += 64) {
-        const float c = CENTRED ? xr[j] - mu[j] : xr[j];
+        const float xv = (float)xr[j];
+        const float c = CENTRED ? xv - mu[j] : xv;
         s = __builtin_fmaf(c, c, s);
     }
 #pragma unroll
@@ -344,6 +349,183 @@ __global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, cons
     }
 }
 
+// ---- the f16 filter: rows STORED as f16 are exact MFMA operands ("f16 rows") --------------------------------
+// No centring, no split of the rows and no conversion while they are staged: the row tile is copied from HBM to LDS as it is.  Only the
+// f32 query is split: q' = q 2^e (e per query, so that max |q'| lies in [2^14, 2^15): exact, inside the f16 range), q'_h = f16(q'),
+// q'_l = f16(q' - q'_h) (the difference is exact), and  q.x ~ 2^-e (x.q'_h + x.q'_l)  on v_mfma_f32_32x32x16_f16: two MFMAs of K = 16.
+// Three LDS planes (rows, q'_h, q'_l) in the split kernel's image: 32 coordinates per stage, row pitch 40 f16 = 80 bytes.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// qh / ql f16 [B][Dp] (Dp = D rounded up to 16, the padding zero), qnorm[b] = |q|^2 of the UNSCALED query in flat_norms_kernel's chain,
+// qscale[b] = 2^-e, qflush[b] = 1.001 * 2 * 2^-14 * sum |q_j|: what the scores may lose if the MFMA flushes f16 subnormal row operands
+// (an absolute term of the slack, added to the bound).  e = 14 - floor(log2 max |q_j|), clamped to [-126, 126] (2^e and 2^-e stay
+// normal f32 numbers); 0 for an all-zero or non-finite query -- the latter's planes hold inf / NaN: its scores are NaN and pass.
+__global__ __launch_bounds__(256) void flat_f16_queries_kernel(const float *__restrict__ q, int B, int D, int Dp, _Float16 *__restrict__ qh,
+                                                              _Float16 *__restrict__ ql, float *__restrict__ qnorm,
+                                                              float *__restrict__ qscale, float *__restrict__ qflush) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float *qr = q + (int64_t)b * D;
+    float s = 0.f, s1 = 0.f, m = 0.f;
+    bool bad = false;
+    for (int j = lane; j < D; j += 64) {
+        const float c = qr[j];
+        s = __builtin_fmaf(c, c, s);
+        const float a = __builtin_fabsf(c);
+        s1 += a;
+        bad |= !(a < __builtin_inff());
+        m = __builtin_fmaxf(m, a);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        s1 += __shfl_xor(s1, o);
+        m = __builtin_fmaxf(m, __shfl_xor(m, o));
+    }
+    bad = __ballot(bad) != 0ull;
+    int e = 0;
+    if (!bad && m > 0.f) {
+        int ex;
+        (void)frexpf(m, &ex);  // m = f 2^ex, f in [0.5, 1): floor(log2 m) = ex - 1
+        e = 15 - ex;
+        e = e < -126 ? -126 : e > 126 ? 126 : e;
+    }
+    const float up = ldexpf(1.f, e);
+    for (int j = lane; j < Dp; j += 64) {
+        const float c = j < D ? qr[j] * up : 0.f;
+        const _Float16 h = (_Float16)c;
+        qh[(int64_t)b * Dp + j] = h;
+        ql[(int64_t)b * Dp + j] = (_Float16)(c - (float)h);
+    }
+    if (lane == 0) {
+        qnorm[b] = s;
+        qscale[b] = ldexpf(1.f, -e);
+        qflush[b] = s1 * (1.001f * 0x1p-13f);
+    }
+}
+
+// flat_split_filter_kernel's job, grid, tile and epilogue over x f16 [..][D].  VEC: D % 8 == 0 and x aligned to 16 bytes.
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const _Float16 *__restrict__ qh, const _Float16 *__restrict__ ql, int B,
+                                                             int D, int Dp, const _Float16 *__restrict__ x, const float *__restrict__ norms,
+                                                             int64_t S, int64_t stride, const uint32_t *__restrict__ valid,
+                                                             const float *__restrict__ qnorm, const float *__restrict__ qscale,
+                                                             const float *__restrict__ qflush, const float *__restrict__ thr, float c_rel,
+                                                             float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap,
+                                                             int n_qtiles, float *__restrict__ scores) {
+    __shared__ __attribute__((aligned(16))) _Float16 As[kFlatTile * kSplitLd];
+    __shared__ __attribute__((aligned(16))) _Float16 Bh[kFlatTile * kSplitLd];
+    __shared__ __attribute__((aligned(16))) _Float16 Bl[kFlatTile * kSplitLd];
+    __shared__ float nxs[kFlatTile];
+    __shared__ int oks[kFlatTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
+    if (tid < kFlatTile) {
+        const int64_t r = r0 + tid;
+        bool ok = r < S;
+        const int64_t row = ok ? r * stride : 0;
+        if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
+        oks[tid] = ok ? 1 : 0;
+        nxs[tid] = ok ? norms[row] : 0.f;
+    }
+    const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
+    const int l31 = lane & 31, lh = lane >> 5;
+    for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
+        const int q0 = qt * kFlatTile;
+        f32x16 acc00, acc01, acc10, acc11;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        for (int k0 = 0; k0 < D; k0 += kSplitDepth) {
+            __syncthreads();  // the previous stage is consumed (first pass: the row tile's norms and flags are written)
+            // rows: f16 from HBM as they are
+            if constexpr (VEC) {
+#pragma unroll
+                for (int i = 0; i < kSplitDepth / 16; ++i) {
+                    const int e = tid + i * 256;  // slots of 8 f16
+                    const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
+                    f16x8 va;
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) va[t] = (_Float16)0.f;
+                    const int64_t rr = r0 + r;
+                    if (rr < S && k0 + c < D) va = *(const f16x8 *)(x + rr * stride * D + k0 + c);
+                    *(f16x8 *)(As + r * kSplitLd + c) = va;
+                }
+            } else {
+#pragma unroll 4
+                for (int i = 0; i < kSplitDepth / 2; ++i) {
+                    const int e = tid + i * 256;  // single values
+                    const int r = e / kSplitDepth, c = e % kSplitDepth;
+                    const int64_t rr = r0 + r;
+                    As[r * kSplitLd + c] = (rr < S && k0 + c < D) ? x[rr * stride * D + k0 + c] : (_Float16)0.f;
+                }
+            }
+            // queries: the planes of flat_f16_queries_kernel, 16 bytes at a time (Dp is a multiple of 8 coordinates)
+#pragma unroll
+            for (int i = 0; i < kSplitDepth / 16; ++i) {
+                const int e = tid + i * 256;  // slots of 8 f16 per plane
+                const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
+                const int qq = q0 + r;
+                f16x8 vh, vl;
+#pragma unroll
+                for (int t = 0; t < 8; ++t) vh[t] = vl[t] = (_Float16)0.f;
+                if (qq < B && k0 + c < Dp) {
+                    vh = *(const f16x8 *)(qh + (int64_t)qq * Dp + k0 + c);
+                    vl = *(const f16x8 *)(ql + (int64_t)qq * Dp + k0 + c);
+                }
+                *(f16x8 *)(Bh + r * kSplitLd + c) = vh;
+                *(f16x8 *)(Bl + r * kSplitLd + c) = vl;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < kSplitDepth; kk += 16) {
+                if (k0 + kk >= D) break;  // (a K step of padding only)
+                const int kc = kk + 8 * lh;
+                const f16x8 a0 = *(const f16x8 *)(As + (wr + l31) * kSplitLd + kc), a1 = *(const f16x8 *)(As + (wr + 32 + l31) * kSplitLd + kc);
+                const f16x8 b0h = *(const f16x8 *)(Bh + (wq + l31) * kSplitLd + kc), b0l = *(const f16x8 *)(Bl + (wq + l31) * kSplitLd + kc);
+                const f16x8 b1h = *(const f16x8 *)(Bh + (wq + 32 + l31) * kSplitLd + kc), b1l = *(const f16x8 *)(Bl + (wq + 32 + l31) * kSplitLd + kc);
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0h, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1h, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0h, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1h, acc11, 0, 0, 0);
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0l, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1l, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0l, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1l, acc11, 0, 0, 0);
+            }
+        }
+        // epilogue: the accumulator back to the query's scale, then flat_filter_kernel's score, comparison and append
+#pragma unroll
+        for (int qj = 0; qj < 2; ++qj) {
+            const int qi = q0 + wq + qj * 32 + l31;
+            if (qi >= B) continue;
+            const float qn = qnorm[qi], t = thr[qi], down = qscale[qi], flush = qflush[qi];
+            int32_t *my_cnt = cnt + qi;
+            int32_t *my_list = cand + (int64_t)qi * cap;
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri) {
+                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                    const float a = nxs[rl] + qn;
+                    const float dot = acc[reg] * down;
+                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
+                    if (scores && r0 + rl < S) scores[(int64_t)qi * S + r0 + rl] = v;
+                    if (!oks[rl]) continue;
+                    const float bound = t + ((c_rel * a + c_abs) + flush);
+                    if (!(v > bound)) {
+                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
+                            const int pos = atomicAdd(my_cnt, 1);
+                            if (pos < cap) my_list[pos] = (int32_t)((r0 + rl) * stride);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
 // ---- exact distances + top-k, a wave per query, ties by ROW ID ---------------------------------------------------------------------
 // The per-lane partial sums, the butterfly and the epilogue are rerank_topk_kernel's (codec.hip), operation for operation: the
 // distances are bit-equal to annlite_rerank_topk's.  What differs is the order among equal distances -- the row id instead of the
@@ -355,7 +537,8 @@ __global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, cons
 // rows) goes there -- a bound for the next filter stage -- instead of the result arrays.
 // The chain itself, shared by every exact kernel of this file: up to 64 rows (one per lane, -1: none; n_here = lanes that were
 // offered one) are scored against the wave's query and offered to its list.
-__device__ __forceinline__ void flat_exact_chunk(int metric, const float *__restrict__ qr, int D, const float *__restrict__ x, int64_t N,
+template <class T>
+__device__ __forceinline__ void flat_exact_chunk(int metric, const float *__restrict__ qr, int D, const T *__restrict__ x, int64_t N,
                                                  const uint32_t *__restrict__ valid, int64_t row, int n_here, int km1, int lane, WaveList &L,
                                                  uint32_t &th, uint32_t &tl) {
     constexpr int U = 8;
@@ -377,8 +560,21 @@ __device__ __forceinline__ void flat_exact_chunk(int metric, const float *__rest
         for (int j = lane; j < D; j += 64) {
             const float qj = qr[j];
             float xv[U];
+            if constexpr (std::is_same<T, float>::value) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) xv[u] = rw[u] >= 0 ? x[rw[u] * D + j] : 0.f;
+                for (int u = 0; u < U; ++u) xv[u] = rw[u] >= 0 ? x[rw[u] * D + j] : 0.f;
+            } else {
+                // f16: all eight loads are issued before the first value is widened, as the f32 form has them in flight together -- left
+                // to itself the compiler widens each value right behind its load, and every load waits for itself: eight latencies in
+                // a row.  So the loads are unconditional -- row 0 (it exists: some row of this batch is one of the table's) stands in
+                // for a missing one -- and a scheduling barrier keeps the conversions behind them.
+                T raw[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) raw[u] = x[(rw[u] >= 0 ? rw[u] : 0) * D + j];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int u = 0; u < U; ++u) xv[u] = rw[u] >= 0 ? (float)raw[u] : 0.f;
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (metric == ANNLITE_METRIC_EUCLIDEAN) {
@@ -420,7 +616,8 @@ __device__ __forceinline__ void flat_exact_finish(const WaveList &L, int b, int 
     }
 }
 
-__global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+template <class T>
+__global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const T *__restrict__ x,
                                                         int64_t N, const int32_t *__restrict__ list, const int32_t *__restrict__ cnt, int cap,
                                                         int64_t S, int64_t stride, const uint32_t *__restrict__ valid, int k, int do_sqrt,
                                                         int final_list, int only_overflowed, float *__restrict__ thr_out,
@@ -720,26 +917,83 @@ static int flat_split_launch_filter(int metric, int64_t B, int64_t D, const floa
     return launch_status("flat_split_filter_kernel");
 }
 
+// ---- the f16 filter's share of a workspace: the query planes, the scales and the flush terms, behind the FlatWs of the same B ----
+struct FlatF16Ws {
+    FlatWs f;
+    int64_t Dp;  // D rounded up to the MFMA's K step
+    _Float16 *qh, *ql;
+    float *qscale, *qflush;
+    size_t bytes;
+};
+static FlatF16Ws flat_f16_carve(void *ws, int64_t B, int64_t D) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    FlatF16Ws w;
+    w.f = flat_carve(ws, B);
+    w.Dp = (D + 15) / 16 * 16;
+    char *p = (char *)ws;
+    size_t o = w.f.bytes;
+    w.qh = (_Float16 *)(p + o), o += up((size_t)B * w.Dp * 2);
+    w.ql = (_Float16 *)(p + o), o += up((size_t)B * w.Dp * 2);
+    w.qscale = (float *)(p + o), o += up((size_t)B * 4);
+    w.qflush = (float *)(p + o), o += up((size_t)B * 4);
+    w.bytes = o;
+    return w;
+}
+
+// The f16 filter's two constants ("f16 rows"); the third, absolute term is per query (flat_f16_queries_kernel).
+static void flat_f16_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
+    const double u = 5.9604644775390625e-08;
+    const double nl = (double)((D + 63) / 64), dp = (double)((D + 15) / 16 * 16);
+    *c_rel = (float)(1.05 * u * (4.4 * dp + 16.0 + 3.0 * nl + 44.0));
+    *c_abs = metric == ANNLITE_METRIC_EUCLIDEAN ? 2e-30f : (float)(9.0 * u);
+}
+
+static int flat_f16_prepare(const float *q, int64_t B, int64_t D, const FlatF16Ws &w, hipStream_t st) {
+    hipLaunchKernelGGL(flat_f16_queries_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, q, (int)B, (int)D, (int)w.Dp, w.qh, w.ql,
+                       w.f.qnorm, w.qscale, w.qflush);
+    return launch_status("flat_f16_queries_kernel");
+}
+
+static int flat_f16_launch_filter(int metric, int64_t B, int64_t D, const _Float16 *x, const float *norms, int64_t S, int64_t stride,
+                                  const uint32_t *valid, const FlatF16Ws &w, const float *thr, int32_t *cand, int32_t *cnt, float *scores,
+                                  hipStream_t st) {
+    float c_rel, c_abs;
+    flat_f16_slack(metric, D, &c_rel, &c_abs);
+    const int64_t n_rt = (S + kFlatTile - 1) / kFlatTile;
+    const int n_qt = (int)((B + kFlatTile - 1) / kFlatTile);
+    int64_t ny = (4 * (int64_t)device_cu_count() + n_rt - 1) / n_rt;  // (flat_launch_filter's grid)
+    ny = ny < 1 ? 1 : ny > n_qt ? n_qt : ny;
+    const dim3 grid((unsigned)n_rt, (unsigned)ny);
+    const bool vec = D % 8 == 0 && ((uintptr_t)x % 16 == 0);
+    if (vec)
+        hipLaunchKernelGGL(flat_f16_filter_kernel<true>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, norms, S, stride,
+                           valid, w.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
+    else
+        hipLaunchKernelGGL(flat_f16_filter_kernel<false>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, norms, S, stride,
+                           valid, w.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
+    return launch_status("flat_f16_filter_kernel");
+}
+
 // ---- the stages of a search, shared by annlite_flat_search_topk and annlite_flat_search_topk_split: the small-
 // table shortcut, the first exact sample, filter stages over growing row sets, the re-rank of the lists and the route of an overflowed
 // list.  prepare(): what the filter needs from the queries, once per call; filter(S, stride): one filter launch into w.cand / w.cnt
 // against the bounds w.thr. ----
-template <class Prepare, class Filter>
-static int flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
+template <class T, class Prepare, class Filter>
+static int flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const T *vectors_dev, int64_t N,
                               const uint32_t *valid_bits_dev, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, const FlatWs &w,
                               hipStream_t st, Prepare &&prepare, Filter &&filter) {
     const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
     const dim3 qgrid((unsigned)((B + 3) / 4));
     ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
     if (N <= kFlatSample) {  // the first sample would be the whole table: exact sums over all rows
-        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
+        hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
                            kFlatCap, N, (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 0, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
         return launch_status("flat_exact_kernel");
     }
     int rc = prepare();
     if (rc != ANNLITE_OK) return rc;
     // stage 0: the k-th smallest exact distance among kFlatSample rows spread over the table
-    hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap,
+    hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap,
                        kFlatSample, N / kFlatSample, valid_bits_dev, (int)k, 0, 0, 0, w.thr, nullptr, nullptr, w.ovf, w.ovf_total);
     if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
     // stages 1 .. n: row sets growing by the same factor (<= kFlatGrowth) up to the whole table; each takes the bound of the one before
@@ -757,13 +1011,13 @@ static int flat_search_staged(int metric, const float *queries_dev, int64_t B, i
         ANNLITE_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)B * 4, st));
         if ((rc = filter((N + stride - 1) / stride, stride)) != ANNLITE_OK) return rc;
         // (a list that overflowed before the last stage still holds `cap` valid rows: the k-th of ANY k valid rows is a bound)
-        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt, kFlatCap,
+        hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt, kFlatCap,
                            (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr,
                            out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
         if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
     }
     // queries whose last list overflowed: exact sums over all rows (the other waves leave at once)
-    hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap, N,
+    hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap, N,
                        (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 1, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
     return launch_status("flat_exact_kernel");
 }
@@ -971,6 +1225,82 @@ extern "C" int annlite_flat_search_topk_split(int metric, const float *queries_d
         });
 }
 
+// ---- f16 rows ------------------------------------------------------------------------------------------------------------------------
+extern "C" int annlite_flat_row_norms_f16(const void *vectors_f16_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n,
+                                          int64_t id_base, float *norms_dev, void *stream) {
+    ANNLITE_REQUIRE(capacity >= 0 && D >= 1 && n >= 0 && D <= INT32_MAX, "bad shape");
+    if (n == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(vectors_f16_dev && norms_dev, "null device pointer");
+    hipLaunchKernelGGL((flat_norms_kernel<false, _Float16>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const _Float16 *)vectors_f16_dev, (int)D, ids_dev, n, id_base, capacity, (const float *)nullptr, norms_dev);
+    return launch_status("flat_norms_kernel");
+}
+
+extern "C" int annlite_flat_f16_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3 && D >= 1 && D <= kSplitMaxDim && c_rel && c_abs, "bad argument (1 <= D <= %lld)",
+                    (long long)kSplitMaxDim);
+    flat_f16_slack(metric, D, c_rel, c_abs);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_search_f16_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    ANNLITE_REQUIRE(N >= 0 && D >= 1 && D <= kSplitMaxDim && B >= 0 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
+                    (long long)kSplitMaxDim);
+    *bytes = (int64_t)flat_f16_carve(nullptr, B, D).bytes;
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_filter_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                                       const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
+                                       float *query_norms_out_dev, float *query_flush_out_dev, const float *bounds_dev, int32_t *cand_dev,
+                                       int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
+                    "bad shape (D <= %lld)", (long long)kSplitMaxDim);
+    if (B == 0 || N == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && vectors_f16_dev && norms_dev && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
+    const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc = flat_f16_prepare(queries_dev, B, D, w, st);
+    if (rc != ANNLITE_OK) return rc;
+    if (query_norms_out_dev)
+        ANNLITE_HIP_TRY(hipMemcpyAsync(query_norms_out_dev, w.f.qnorm, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    if (query_flush_out_dev)
+        ANNLITE_HIP_TRY(hipMemcpyAsync(query_flush_out_dev, w.qflush, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    return flat_f16_launch_filter(metric, B, D, (const _Float16 *)vectors_f16_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev,
+                                  w, bounds_dev, cand_dev, count_dev, scores_dev, st);
+}
+
+extern "C" int annlite_flat_search_topk_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                                            const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
+                                            float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
+                                            void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
+                    "bad shape (1 <= k <= 64, D <= %lld)", (long long)kSplitMaxDim);
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_f16_dev && norms_dev)),
+                    "null device pointer");
+    const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const _Float16 *x = (const _Float16 *)vectors_f16_dev;
+    return flat_search_staged(
+        metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st,
+        [&]() { return flat_f16_prepare(queries_dev, B, D, w, st); },
+        [&](int64_t S, int64_t stride) {
+            return flat_f16_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st);
+        });
+}
+
 extern "C" int annlite_flat_overflow_count(const void *workspace_dev, void *stream, int64_t *count) {
     ANNLITE_REQUIRE(workspace_dev && count, "null pointer");
     uint32_t v = 0;
@@ -1051,7 +1381,7 @@ extern "C" int annlite_ivf_flat_search_topk(int metric, const float *queries_dev
                                     valid_bits_dev, st);
         if (rc != ANNLITE_OK) return rc;
         // the list re-rank of annlite_flat_search_topk, unchanged: the lists hold offsets
-        hipLaunchKernelGGL(flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.f.cand, w.f.cnt,
+        hipLaunchKernelGGL(flat_exact_kernel<float>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.f.cand, w.f.cnt,
                            kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0,
                            last ? nullptr : w.f.thr, out_dist_dev, out_id_dev, w.f.ovf, w.f.ovf_total);
         if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;

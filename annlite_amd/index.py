@@ -96,6 +96,12 @@ class AnnLite:
     :param flat_filter: ``'f32'`` (default) or ``'bf16x3'``, with ``centre`` (``'mean'``, ``None`` or an array) (kwargs, same channel;
         the float indexes -- no ``n_subvectors`` --, dropped for the indexes over PQ codes, ignored with ``n_cells > 1``): the filter
         of the exact float search; ``'bf16x3'`` is the one for data with a large common offset (``FlatGpuIndex``)
+    :param dtype: ``np.float32`` (default) or ``np.float16`` (kwarg, same channel; the reference's ``dtype`` of its index plug-ins):
+        without ``n_subvectors``, ``n_cells > 1`` and ``graph`` it reaches ``FlatGpuIndex``, which then stores its rows in half
+        precision -- half the HBM, the answer of the f32 index over the rounded rows bit for bit, its own filter ``'f16x2'`` (no
+        ``flat_filter='bf16x3'``, no ``centre``: centre data with a common offset before adding it).  The float graph
+        (``graph=True``) and the cells over floats (``n_cells > 1``) read f32 rows only and raise ``NotImplementedError`` for
+        ``np.float16``; the indexes over PQ codes ignore ``dtype``, as before
     """
 
     def __init__(

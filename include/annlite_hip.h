@@ -490,6 +490,12 @@ ANNLITE_API int annlite_kmeans_update(const float *sums_dev, const int32_t *coun
 ANNLITE_API int annlite_exact_gather_dist(int metric, const float *queries_dev, int64_t B, int64_t D,
                               const float *vectors_dev, int64_t N, const int64_t *cand_dev, int64_t R,
                               float *out_dev, void *stream);
+/* annlite_exact_gather_dist over vectors_f16_dev f16 [N][D] (FlatGpuIndex's half-precision row store): every value is widened exactly
+ * and the arithmetic after the load is the f32 form's, so the result is annlite_exact_gather_dist's over the widened rows, bit for bit.
+ * No reference counterpart (the reference casts to its dtype on the host, hnsw/index.py:20-48, and hnswlib computes in f32). */
+ANNLITE_API int annlite_exact_gather_dist_f16(int metric, const float *queries_dev, int64_t B, int64_t D,
+                                  const void *vectors_f16_dev, int64_t N, const int64_t *cand_dev, int64_t R,
+                                  float *out_dev, void *stream);
 /* The same distances FUSED with the top-k (round 6): out[b][0..k) = the k smallest exact distances among cand[b][0..R) in
  * (distance, position in the list) order -- what annlite_exact_gather_dist + annlite_topk_rows + a gather of the ids give, bit for
  * bit -- as (distance, cand id); candidates < 0, >= N or cleared in valid_bits_dev (may be NULL) are skipped, missing places hold
@@ -563,6 +569,34 @@ ANNLITE_API int annlite_flat_search_topk_split(int metric, const float *queries_
                                    const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const float *centre_dev, int64_t k,
                                    int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
                                    void *stream);
+
+/* The same search over rows STORED in half precision ("f16 rows"): vectors_f16_dev f16 [N][D], rounded once
+ * when they were written; queries stay f32.  replaces: the reference's `dtype` argument of its index plug-ins (BaseIndex(dim, dtype=...),
+ * HnswIndex.pre_process casts to it, annlite/core/index/hnsw/index.py:20-48).  The answer is annlite_flat_search_topk's over the rows
+ * widened back to f32, bit for bit.  An f16 row is an exact MFMA operand: the filter contracts it with the query carried as two f16
+ * numbers (scaled by a power of two per query) on two f16 MFMAs.  1 <= D <= 32768. */
+/* annlite_flat_row_norms over f16 rows (flat_norms_kernel's chain on the widened values).  No reference counterpart. */
+ANNLITE_API int annlite_flat_row_norms_f16(const void *vectors_f16_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n,
+                               int64_t id_base, float *norms_dev, void *stream);
+/* The f16 filter's (c_rel, c_abs) (host only); its slack is c_rel * fl(|x|^2 + |q|^2) + c_abs + a per-query term the library computes,
+ * 1.001 * 2^-13 * sum |q_j| (what a flush of f16 subnormal row operands inside the MFMA could cost).  No reference counterpart. */
+ANNLITE_API int annlite_flat_f16_slack(int metric, int64_t D, float *c_rel, float *c_abs);
+/* No reference counterpart. */
+ANNLITE_API int annlite_flat_search_f16_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes);
+/* annlite_flat_filter over f16 rows.  norms_dev: annlite_flat_row_norms_f16.  The queries are scaled and split into the workspace
+ * (annlite_flat_search_f16_workspace_bytes of the same B, D) by this call; query_norms_out_dev / query_flush_out_dev (may be NULL) f32 [B]
+ * receive |q|^2 and the per-query slack term as the filter used them; scores_dev (may be NULL; tests and measurements)
+ * f32 [B][ceil(N / stride)] receives the filter's score v of every (query, stage row) pair, valid or not.  No reference counterpart. */
+ANNLITE_API int annlite_flat_filter_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                            const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
+                            float *query_norms_out_dev, float *query_flush_out_dev, const float *bounds_dev, int32_t *cand_dev,
+                            int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* annlite_flat_search_topk over f16 rows: the same stages, lists, capacity and overflow route (annlite_flat_overflow_count and
+ * annlite_flat_list_counts read this workspace too).  replaces: HnswIndex.search / FlatIndex.search of an index built with
+ * dtype=np.float16. */
+ANNLITE_API int annlite_flat_search_topk_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                                 const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
+                                 float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Cells over float vectors: the exact search above restricted to the rows of each query's P probed cells.

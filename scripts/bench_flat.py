@@ -6,6 +6,8 @@
     python scripts/bench_flat.py --rows 10000000
     python scripts/bench_flat.py --filter both         # the f32 and the split-bf16 filter, round by round: one JSON line each
     python scripts/bench_flat.py --filter both --offset 1000   # ... on data with a large common offset
+    python scripts/bench_flat.py --rows both           # an f32-row index (default filter) and an f16-row index over the same data,
+                                                       # round by round: one JSON line each (--rows 10000000 --rows both: at 10M)
 
 Baseline: |x|^2 - 2 q x^T by torch.addmm over row chunks (no B x N matrix exists), torch.topk per chunk, one merge.
 Filter time: the full-table filter launch (annlite_flat_filter with the bounds the search would hand it; for bf16x3
@@ -23,11 +25,128 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 ROOF_TFLOPS = 157.3
+ROW_DTYPES = {'f32': ['f32'], 'f16': ['f16'], 'both': ['f32', 'f16']}
+
+
+def row_dtypes(args):
+    """``--rows both`` / ``f16`` / ``f32``: an f32-row FlatGpuIndex on its default filter -- the default path, untouched -- and (or) an
+    f16-row one (``dtype=np.float16``) over the same rows, alternating round by round in one process.  One JSON line per index."""
+    import torch
+    from annlite_amd import ops
+    from annlite_amd.core.index.flat_gpu import FlatGpuIndex
+    from annlite_amd.enums import Metric
+
+    torch.cuda.set_device(0)
+    dev = torch.device('cuda', 0)
+    N, D, B, k = args.rows, args.dim, args.batch, args.k
+    metric = Metric.from_string(args.metric)
+    l2 = metric == Metric.EUCLIDEAN
+    kinds = ROW_DTYPES[args.row_dtype]
+    np_dtype = {'f32': np.float32, 'f16': np.float16}
+    index = {m: FlatGpuIndex(D, dtype=np_dtype[m], metric=metric, initial_size=N) for m in kinds}
+    gen = torch.Generator(device=dev).manual_seed(0)
+    step = 1 << 20
+    truth_rows = []  # the UNROUNDED rows (as pre-processed), for the float64 truth; the f32 index holds them already
+    for r0 in range(0, N, step):
+        xb = torch.randn((min(step, N - r0), D), generator=gen, device=dev) + args.offset
+        for idx in index.values():
+            idx.add_with_ids(xb, torch.arange(r0, r0 + xb.shape[0], device=dev))
+        if 'f32' not in index:
+            truth_rows.append(next(iter(index.values()))._pre(xb))
+    q = torch.randn((B, D), generator=gen, device=dev) + args.offset
+    x_true = index['f32']._vectors[:N] if 'f32' in index else torch.cat(truth_rows)
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.steps):
+            out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.steps, out
+
+    ms, answers, overflowed, last_counts = {m: [] for m in kinds}, {}, {}, {}
+    for _ in range(args.rounds):
+        for m in kinds:
+            t, answers[m] = timed(lambda: index[m].search_batch(q, limit=k))
+            ms[m].append(t)
+            assert index[m].last_flat_filter == ('f16x2' if m == 'f16' else 'f32')
+            overflowed[m] = index[m].last_overflowed
+            last_counts[m] = ops.flat_list_counts(index[m]._ws, B).cpu().numpy()  # what the search's own last stage listed
+
+    # the full-table filter alone, with the bound the search's last stage works with (see main())
+    ratio = N / 4096.0
+    n_stages = max(1, int(np.ceil(np.log(max(ratio, 1.0001)) / np.log(32.0) - 1e-9)))
+    stride = max(1, int(ratio ** (1.0 / n_stages)))
+    filter_ms = {}
+    for m in kinds:
+        idx = index[m]
+        qq = idx._pre(q)
+        n_sub = (N + stride - 1) // stride
+        sub = FlatGpuIndex(D, dtype=np_dtype[m], metric=Metric.INNER_PRODUCT if metric == Metric.COSINE else metric, initial_size=n_sub)
+        sub.add_with_ids(idx._vectors[:N:stride].float().contiguous(), torch.arange(n_sub, device=dev))
+        sd = sub.search_batch(qq, limit=k)[0][:, k - 1]
+        bound = ((sd * sd) if l2 else sd).contiguous()
+        del sub
+        qn = ops.flat_row_norms(qq)
+
+        def filter_once():
+            if m == 'f16':
+                return ops.flat_filter_f16(int(metric), qq, idx._vectors, idx._norms, bound, valid_bits=idx._valid, n_rows=N, workspace=idx._ws)
+            return ops.flat_filter(int(metric), qq, idx._vectors, idx._norms, bound, valid_bits=idx._valid, n_rows=N, query_norms=qn)
+
+        filter_once()
+        f_ms = []
+        for _ in range(args.rounds):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            filter_once()
+            e1.record()
+            torch.cuda.synchronize()
+            f_ms.append(e0.elapsed_time(e1))
+        filter_ms[m] = statistics.median(f_ms)
+
+    # recall@k of each index against float64 distances over the UNROUNDED rows: the price of the storage rounding
+    nt = min(args.truth_queries, B)
+    q64 = next(iter(index.values()))._pre(q)[:nt].double()
+    best = None
+    for r0 in range(0, N, 1 << 18):
+        xc = x_true[r0:r0 + (1 << 18)].double()
+        s = ((xc * xc).sum(1)[None, :] - 2.0 * q64 @ xc.T) if l2 else -(q64 @ xc.T)
+        dd, ii = torch.topk(s, k, dim=1, largest=False)
+        ii = ii + r0
+        if best is not None:
+            dd, ii = torch.cat([best[0], dd], 1), torch.cat([best[1], ii], 1)
+            dd, p = torch.topk(dd, k, dim=1, largest=False)
+            ii = torch.gather(ii, 1, p)
+        best = (dd, ii)
+    truth = best[1].cpu().numpy()
+    flop = 2.0 * B * N * D
+    for m in kinds:
+        idx, med, f, count = index[m], statistics.median(ms[m]), filter_ms[m], last_counts[m]
+        got = answers[m][1][:nt].cpu().numpy()
+        held = sum(t.numel() * t.element_size() for t in (idx._vectors, idx._norms, idx._valid_bool))
+        print(json.dumps({
+            'bench': 'flat_rows', 'row_dtype': m, 'row_dtypes_in_this_run': kinds, 'flat_filter': idx.flat_filter, 'offset': args.offset,
+            'rows': N, 'dim': D, 'batch': B, 'k': k, 'metric': args.metric, 'rounds': args.rounds, 'steps': args.steps,
+            'ms_per_batch': round(med, 4), 'qps': round(B / med * 1e3, 1), 'ms_rounds': [round(v, 4) for v in ms[m]],
+            'filter_ms': round(f, 4), 'filter_tflops': round(flop / f / 1e9, 2),
+            'filter_fraction_of_fp32_roof': round(flop / f / 1e9 / ROOF_TFLOPS, 4), 'filter_bound_rows_stride': stride,
+            'candidates_mean': round(float(count.mean()), 1), 'candidates_max': int(count.max()),
+            'overflowed_queries': int(overflowed[m]), 'hbm_bytes_held': int(held),
+            'recall_at_k_vs_float64_unrounded_rows': float(np.mean([len(set(got[b]) & set(truth[b])) / k for b in range(nt)])),
+            'truth_queries': nt, 'device': torch.cuda.get_device_name(0),
+        }), flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--rows', type=int, default=1_000_000)
+    ap.add_argument('--rows', action='append', default=[],
+                    help="a number: rows of the table (default 1000000); f32 | f16 | both: how the rows are stored -- FlatGpuIndex(dtype=...), "
+                         "'both': an f32-row and an f16-row index alternating (may be given twice: --rows 10000000 --rows both)")
     ap.add_argument('--dim', type=int, default=128)
     ap.add_argument('--batch', type=int, default=1024)
     ap.add_argument('--k', type=int, default=10)
@@ -39,6 +158,15 @@ def main():
     ap.add_argument('--filter', default='f32', choices=['f32', 'bf16x3', 'both'], help="FlatGpuIndex(flat_filter=...); 'both': alternating")
     ap.add_argument('--offset', type=float, default=0.0, help='added to every coordinate of rows and queries')
     args = ap.parse_args()
+    given, args.rows, args.row_dtype = args.rows, 1_000_000, None
+    for v in given:
+        if v in ROW_DTYPES:
+            args.row_dtype = v
+        else:
+            args.rows = int(v)
+    if args.row_dtype is not None:
+        assert args.filter == 'f32', '--rows f32 | f16 | both runs each index on its own default filter'
+        return row_dtypes(args)
 
     import torch
     from annlite_amd import ops
