@@ -125,6 +125,10 @@ SYMBOLS = (
     'annlite_ivf_flat_stages',
     'annlite_ivf_flat_search_workspace_bytes',
     'annlite_ivf_flat_search_topk',
+    'annlite_ivf_flat_centred_norms',
+    'annlite_ivf_flat_search_split_workspace_bytes',
+    'annlite_ivf_flat_filter_split',
+    'annlite_ivf_flat_search_topk_split',
     'annlite_affine_rows',
     'annlite_pca_accumulate_workspace_bytes',
     'annlite_pca_accumulate',
@@ -267,6 +271,12 @@ def lib() -> ctypes.CDLL:
     L.annlite_ivf_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_ivf_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, vp,
                                                vp, sz, vp]
+    L.annlite_ivf_flat_centred_norms.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, vp, vp, vp]
+    L.annlite_ivf_flat_search_split_workspace_bytes.argtypes = [i64, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_ivf_flat_filter_split.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp,
+                                                vp, vp, vp, sz, vp]
+    L.annlite_ivf_flat_search_topk_split.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, vp, vp, i64,
+                                                     i32, vp, vp, vp, sz, vp]
     L.annlite_affine_rows.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, vp, i64, vp]
     L.annlite_pca_accumulate_workspace_bytes.argtypes = [i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_pca_accumulate.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]

@@ -30,16 +30,22 @@ constexpr double kFlatGrowth = 32.0;      // a stage's row set is at most this m
 // CENTRED: the same chain over c_j = fl(x_j - mu_j), the values the split filter contracts (second half of the filter section).
 // T: the row type, float or _Float16 (a half-precision row store, "f16 rows" below): an f16 value widens exactly, and everything after
 // the load is the f32 form's, operation for operation.
+// cell_of != NULL (CENTRED; the split filter over cell tiles, second half of the file): mu is f32 [C][D] and the row's centre is the
+// one of its cell, mu[cell_of[row]] (an id outside [0, C): cell 0, as ivf_flat_cell_range reads it).
 template <bool CENTRED, class T = float>
 __global__ __launch_bounds__(256) void flat_norms_kernel(const T *__restrict__ x, int D, const int64_t *__restrict__ ids, int64_t n,
                                                         int64_t id_base, int64_t capacity, const float *__restrict__ mu,
-                                                        float *__restrict__ norms) {
+                                                        const int32_t *__restrict__ cell_of, int C, float *__restrict__ norms) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
     const int64_t row = ids ? ids[i] : id_base + i;
     if (row < 0 || row >= capacity) return;
     const T *xr = x + row * D;
+    if (CENTRED && cell_of) {
+        const int c = cell_of[row];
+        mu += (int64_t)((unsigned)c < (unsigned)C ? c : 0) * D;
+    }
     float s = 0.f;
     for (int j = lane; j < D; j += 64) {
         const float xv = (float)xr[j];
@@ -812,6 +818,217 @@ __global__ __launch_bounds__(256) void ivf_flat_filter_kernel(int metric, const 
     }
 }
 
+// ---- the split filter over cell tiles ("split filter over cell tiles") -------------------------------------------
+// flat_split_filter_kernel's contraction on ivf_flat_filter_kernel's tiles, with a centre PER TILE: the centroid of the tile's cell
+// (centres f32 [C][D]; NULL: no centring).  Every row of a tile belongs to that cell and every query slot of the tile probes it, so
+// both operands of every pair are centred on the same point -- all section 3.6's claim asks for.
+//
+// The queries, once per call, a wave per (query b, probe p) pair: c = fl(q_b - centres[cells[b][p]]) split into the two bf16 planes of
+// the pair's PLAN SLOT v = slot_of[b P + p] (qh / ql bf16 [n_slots][Dp], Dp = D rounded up to 16, the padding zero): a filter tile reads
+// the planes of its 128 slots back to back, no gather.  qnorm[v] = |c|^2 in flat_split_queries_kernel's chain; pair_norms (may be
+// NULL) f32 [B][P] receives the same number by pair.  A cell id outside [0, C) reads cell 0, as the plan does.
+__global__ __launch_bounds__(256) void ivf_flat_split_queries_kernel(const float *__restrict__ q, int n_pairs, int P, int D, int Dp,
+                                                                    const int32_t *__restrict__ cells, int C,
+                                                                    const float *__restrict__ centres, const int32_t *__restrict__ slot_of,
+                                                                    int n_slots, __bf16 *__restrict__ qh, __bf16 *__restrict__ ql,
+                                                                    float *__restrict__ qnorm, float *__restrict__ pair_norms) {
+    const int lane = threadIdx.x & 63;
+    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pair >= n_pairs) return;
+    const int v = slot_of[pair];
+    if ((unsigned)v >= (unsigned)n_slots) return;
+    const float *qr = q + (int64_t)(pair / P) * D;
+    const float *mu = nullptr;
+    if (centres) {
+        const int c = cells[pair];
+        mu = centres + (int64_t)((unsigned)c < (unsigned)C ? c : 0) * D;
+    }
+    float s = 0.f;
+    for (int j = lane; j < Dp; j += 64) {
+        float c = 0.f;
+        if (j < D) {
+            c = mu ? qr[j] - mu[j] : qr[j];
+            s = __builtin_fmaf(c, c, s);
+        }
+        __bf16 h, l;
+        split_bf16(c, h, l);
+        qh[(int64_t)v * Dp + j] = h;
+        ql[(int64_t)v * Dp + j] = l;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) {
+        qnorm[v] = s;
+        if (pair_norms) pair_norms[pair] = s;
+    }
+}
+
+// ivf_flat_filter_kernel's grid, tile walk, rws / qss and epilogue; flat_split_filter_kernel's LDS planes and MFMAs.  The rows are
+// gathered through perm, centred on the tile's centroid -- the cell of the range's first row, cell_of[perm[begin]] -- and split while
+// they are staged; a thread stages the same four (VEC) / one coordinates of every row it handles, so it loads its piece of the centroid
+// once per stage.  norms: the column of |fl(x - centre of x's cell)|^2 (annlite_ivf_flat_centred_norms; |x|^2 without centres);
+// qnorm: by slot.  scores != NULL (tests, measurements): v of every evaluated (query, live row) pair goes to scores f32 [B][N] by
+// (query, row offset); the others keep what the caller put there.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ivf_flat_split_filter_kernel(int metric, const __bf16 *__restrict__ qh, const __bf16 *__restrict__ ql,
+                                                                   int B, int D, int Dp, const float *__restrict__ x,
+                                                                   const float *__restrict__ centres, int C,
+                                                                   const int32_t *__restrict__ cell_of, const float *__restrict__ norms,
+                                                                   int64_t N, const int32_t *__restrict__ perm, int64_t n_perm,
+                                                                   const int64_t *__restrict__ tile_rows, const int32_t *__restrict__ vmap,
+                                                                   int n_tiles, int64_t stride, const uint32_t *__restrict__ valid,
+                                                                   const float *__restrict__ qnorm, const float *__restrict__ thr,
+                                                                   float c_rel, float c_abs, int32_t *__restrict__ cand,
+                                                                   int32_t *__restrict__ cnt, int cap, float *__restrict__ scores) {
+    __shared__ __attribute__((aligned(16))) __bf16 Ah[kFlatTile * kSplitLd];
+    __shared__ __attribute__((aligned(16))) __bf16 Al[kFlatTile * kSplitLd];
+    __shared__ __attribute__((aligned(16))) __bf16 Bh[kFlatTile * kSplitLd];
+    __shared__ __attribute__((aligned(16))) __bf16 Bl[kFlatTile * kSplitLd];
+    __shared__ float nxs[kFlatTile];
+    __shared__ int rws[kFlatTile];  // offset of the tile's row, -1: none (past the cell's end, not valid)
+    __shared__ int qss[kFlatTile];  // query of the tile's slot, -1: padding
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
+    const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
+    const int l31 = lane & 31, lh = lane >> 5;
+    for (int t = blockIdx.y; t < n_tiles; t += gridDim.y) {
+        int64_t begin = tile_rows[2 * (int64_t)t], end = tile_rows[2 * (int64_t)t + 1];
+        if (begin < 0) continue;
+        if (end > n_perm) end = n_perm;
+        const int64_t S = (end - begin + stride - 1) / stride;
+        if (r0 >= S) continue;  // (both tests are the workgroup's: no barrier is left behind)
+        __syncthreads();        // the previous tile's epilogue has read rws / nxs / qss
+        if (tid < kFlatTile) {
+            const int64_t r = r0 + tid;
+            int64_t row = r < S ? (int64_t)perm[begin + r * stride] : -1;
+            if (row >= N) row = -1;
+            if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
+            rws[tid] = (int)row;
+            nxs[tid] = row >= 0 ? norms[row] : 0.f;
+        } else {
+            const int qi = vmap[(int64_t)t * kFlatTile + tid - kFlatTile];
+            qss[tid - kFlatTile] = (unsigned)qi < (unsigned)B ? qi : -1;
+        }
+        const float *mu = nullptr;  // the tile's centroid (the range is not empty: r0 < S)
+        if (centres) {
+            const int64_t first = perm[begin];
+            const int c = (first >= 0 && first < N) ? cell_of[first] : 0;
+            mu = centres + (int64_t)((unsigned)c < (unsigned)C ? c : 0) * D;
+        }
+        const __bf16 *th = qh + (int64_t)t * kFlatTile * Dp, *tl = ql + (int64_t)t * kFlatTile * Dp;
+        f32x16 acc00, acc01, acc10, acc11;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        for (int k0 = 0; k0 < D; k0 += kSplitDepth) {
+            __syncthreads();  // the previous stage is consumed (first pass: the tile's rows and queries are written)
+            // rows: f32 gathered from HBM, centred, split, two planes
+            if constexpr (VEC) {
+                const int c = (tid % (kSplitDepth / 4)) * 4;
+                f32x4 mv = {0.f, 0.f, 0.f, 0.f};
+                if (mu && k0 + c < D) mv = *(const f32x4 *)(mu + k0 + c);
+#pragma unroll
+                for (int i = 0; i < kSplitDepth / 8; ++i) {
+                    const int r = (tid + i * 256) / (kSplitDepth / 4);  // slots of 4 floats
+                    f32x4 cv = {0.f, 0.f, 0.f, 0.f};
+                    const int rr = rws[r];
+                    if (rr >= 0 && k0 + c < D) cv = *(const f32x4 *)(x + (int64_t)rr * D + k0 + c) - mv;
+                    bf16x4 h4, l4;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        __bf16 h, l;
+                        split_bf16(cv[u], h, l);
+                        h4[u] = h, l4[u] = l;
+                    }
+                    *(bf16x4 *)(Ah + r * kSplitLd + c) = h4;
+                    *(bf16x4 *)(Al + r * kSplitLd + c) = l4;
+                }
+            } else {
+                const int c = tid % kSplitDepth;
+                const float mv = (mu && k0 + c < D) ? mu[k0 + c] : 0.f;
+#pragma unroll 4
+                for (int i = 0; i < kSplitDepth / 2; ++i) {
+                    const int r = (tid + i * 256) / kSplitDepth;  // single floats
+                    const int rr = rws[r];
+                    float cv = 0.f;
+                    if (rr >= 0 && k0 + c < D) cv = x[(int64_t)rr * D + k0 + c] - mv;
+                    __bf16 h, l;
+                    split_bf16(cv, h, l);
+                    Ah[r * kSplitLd + c] = h;
+                    Al[r * kSplitLd + c] = l;
+                }
+            }
+            // queries: the planes of the tile's slots, 16 bytes at a time (Dp is a multiple of 8 coordinates)
+#pragma unroll
+            for (int i = 0; i < kSplitDepth / 16; ++i) {
+                const int e = tid + i * 256;  // slots of 8 bf16 per plane
+                const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
+                bf16x8 vh, vl;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) vh[u] = vl[u] = (__bf16)0.f;
+                if (qss[r] >= 0 && k0 + c < Dp) {
+                    vh = *(const bf16x8 *)(th + (int64_t)r * Dp + k0 + c);
+                    vl = *(const bf16x8 *)(tl + (int64_t)r * Dp + k0 + c);
+                }
+                *(bf16x8 *)(Bh + r * kSplitLd + c) = vh;
+                *(bf16x8 *)(Bl + r * kSplitLd + c) = vl;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < kSplitDepth; kk += 16) {
+                if (k0 + kk >= D) break;  // (a K step of padding only)
+                const int kc = kk + 8 * lh;
+                const bf16x8 a0h = *(const bf16x8 *)(Ah + (wr + l31) * kSplitLd + kc), a0l = *(const bf16x8 *)(Al + (wr + l31) * kSplitLd + kc);
+                const bf16x8 a1h = *(const bf16x8 *)(Ah + (wr + 32 + l31) * kSplitLd + kc), a1l = *(const bf16x8 *)(Al + (wr + 32 + l31) * kSplitLd + kc);
+                const bf16x8 b0h = *(const bf16x8 *)(Bh + (wq + l31) * kSplitLd + kc), b0l = *(const bf16x8 *)(Bl + (wq + l31) * kSplitLd + kc);
+                const bf16x8 b1h = *(const bf16x8 *)(Bh + (wq + 32 + l31) * kSplitLd + kc), b1l = *(const bf16x8 *)(Bl + (wq + 32 + l31) * kSplitLd + kc);
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0h, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1h, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0h, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1h, acc11, 0, 0, 0);
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0l, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1l, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0l, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1l, acc11, 0, 0, 0);
+                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b0h, acc00, 0, 0, 0);
+                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b1h, acc01, 0, 0, 0);
+                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b0h, acc10, 0, 0, 0);
+                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b1h, acc11, 0, 0, 0);
+            }
+        }
+        // epilogue: score, compare, append (ivf_flat_filter_kernel's, on the centred norms of the row and of the slot's pair)
+#pragma unroll
+        for (int qj = 0; qj < 2; ++qj) {
+            const int sl = wq + qj * 32 + l31;
+            const int qi = qss[sl];
+            if (qi < 0) continue;
+            const float qn = qnorm[(int64_t)t * kFlatTile + sl], tq = thr[qi];
+            int32_t *my_cnt = cnt + qi;
+            int32_t *my_list = cand + (int64_t)qi * cap;
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri) {
+                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                    const int off = rws[rl];
+                    if (off < 0) continue;
+                    const float a = nxs[rl] + qn;
+                    const float dot = acc[reg];
+                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
+                    if (scores) scores[(int64_t)qi * N + off] = v;
+                    const float bound = tq + (c_rel * a + c_abs);
+                    if (!(v > bound)) {
+                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
+                            const int pos = atomicAdd(my_cnt, 1);
+                            if (pos < cap) my_list[pos] = off;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
 // ---- workspace of annlite_flat_search_topk -------------------------------------------------------------------------------------------
 struct FlatWs {
     uint32_t *ovf_total;  // queries of the last call whose final list overflowed
@@ -1087,6 +1304,103 @@ static int ivf_flat_launch_filter(int metric, const float *q, int64_t B, int64_t
     return launch_status("ivf_flat_filter_kernel");
 }
 
+// ---- the split filter's share of a cells workspace: the query planes and the pair norms BY PLAN SLOT, behind the IvfFlatWs of the same
+// (B, P, C) (so that the overflow counter and the list counters sit where annlite_flat_overflow_count / annlite_flat_list_counts read
+// them) ----
+struct IvfFlatSplitWs {
+    IvfFlatWs i;
+    int64_t Dp, n_slots;
+    __bf16 *qh, *ql;
+    float *qnorm;
+    size_t bytes;
+};
+static IvfFlatSplitWs ivf_flat_split_carve(void *ws, int64_t B, int64_t P, int64_t C, int64_t D) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    IvfFlatSplitWs w;
+    w.i = ivf_flat_carve(ws, B, P, C);
+    w.Dp = (D + 15) / 16 * 16;
+    w.n_slots = w.i.n_tiles * kFlatTile;
+    char *p = (char *)ws;
+    size_t o = w.i.bytes;
+    w.qh = (__bf16 *)(p + o), o += up((size_t)w.n_slots * w.Dp * 2);
+    w.ql = (__bf16 *)(p + o), o += up((size_t)w.n_slots * w.Dp * 2);
+    w.qnorm = (float *)(p + o), o += up((size_t)w.n_slots * 4);
+    w.bytes = o;
+    return w;
+}
+
+// Per call, after the plan: centre and split the queries of every pair into its slot's planes.
+static int ivf_flat_split_prepare(const float *q, int64_t B, int64_t P, int64_t C, int64_t D, const int32_t *cells, const float *centres,
+                                  const IvfFlatSplitWs &w, float *pair_norms, hipStream_t st) {
+    hipLaunchKernelGGL(ivf_flat_split_queries_kernel, dim3((unsigned)((B * P + 3) / 4)), dim3(256), 0, st, q, (int)(B * P), (int)P, (int)D,
+                       (int)w.Dp, cells, (int)C, centres, w.i.slot_of, (int)w.n_slots, w.qh, w.ql, w.qnorm, pair_norms);
+    return launch_status("ivf_flat_split_queries_kernel");
+}
+
+static int ivf_flat_split_launch_filter(int metric, int64_t B, int64_t D, const float *x, const float *centres, int64_t C,
+                                        const int32_t *cell_of, const float *norms, int64_t N, const int32_t *perm, int64_t n_perm,
+                                        const IvfFlatSplitWs &w, int64_t max_cell_rows, int64_t stride, const uint32_t *valid,
+                                        const float *thr, int32_t *cand, int32_t *cnt, float *scores, hipStream_t st) {
+    float c_rel, c_abs;
+    flat_split_slack(metric, D, &c_rel, &c_abs);
+    const int64_t n_rt = ((max_cell_rows + stride - 1) / stride + kFlatTile - 1) / kFlatTile;  // (ivf_flat_launch_filter's grid)
+    if (n_rt <= 0 || w.i.n_tiles <= 0) return ANNLITE_OK;
+    const dim3 grid((unsigned)n_rt, (unsigned)(w.i.n_tiles < 65535 ? w.i.n_tiles : 65535));
+    const bool vec = D % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)centres % 16 == 0);
+    if (vec)
+        hipLaunchKernelGGL(ivf_flat_split_filter_kernel<true>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, centres,
+                           (int)C, cell_of, norms, N, perm, n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, valid, w.qnorm, thr, c_rel,
+                           c_abs, cand, cnt, kFlatCap, scores);
+    else
+        hipLaunchKernelGGL(ivf_flat_split_filter_kernel<false>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, centres,
+                           (int)C, cell_of, norms, N, perm, n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, valid, w.qnorm, thr, c_rel,
+                           c_abs, cand, cnt, kFlatCap, scores);
+    return launch_status("ivf_flat_split_filter_kernel");
+}
+
+// ---- the stages of a search over cells, shared by annlite_ivf_flat_search_topk and
+// annlite_ivf_flat_search_topk_split: the exact-only shortcut, the plan, the first exact sample, the filter stages, the re-rank of the
+// lists and the route of an overflowed list.  prepare(): what the filter needs from the queries, once per call, after the plan;
+// filter(stride): one filter launch into w.f.cand / w.f.cnt against the bounds w.f.thr. ----
+template <class Prepare, class Filter>
+static int ivf_flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
+                                  const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C, const int32_t *perm_dev,
+                                  int64_t n_perm, const int64_t *cell_rows_dev, const int32_t *cell_order_dev, int64_t max_probed_rows,
+                                  int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, const IvfFlatWs &w, hipStream_t st,
+                                  Prepare &&prepare, Filter &&filter) {
+    const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
+    const dim3 qgrid((unsigned)((B + 3) / 4));
+    ANNLITE_HIP_TRY(hipMemsetAsync(w.f.ovf_total, 0, 256, st));
+    auto exact_cells = [&](int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
+        hipLaunchKernelGGL(ivf_flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, cells_dev, (int)P,
+                           (int)C, cell_rows_dev, perm_dev, n_perm, stride, valid_bits_dev, (int)k, sqrt_out, only_overflowed, thr_out,
+                           out_dist_dev, out_id_dev, w.f.ovf);
+        return launch_status("ivf_flat_exact_kernel");
+    };
+    int64_t strides[kIvfFlatMaxStages];
+    const int n_strides = ivf_flat_strides(max_probed_rows, strides);
+    if (n_strides == 0) return exact_cells(1, do_sqrt, 0, nullptr);  // few probed rows: exact sums over all of them
+    // the (cell, queries that probe it) tiles of the filter stages
+    int rc = annlite_ivf_plan(cells_dev, B, P, C, kFlatTile, cell_rows_dev, cell_order_dev, w.n_tiles, w.vmap, w.slot_of, w.tile_rows, w.n_used,
+                              (void *)st);
+    if (rc != ANNLITE_OK) return rc;
+    if ((rc = prepare()) != ANNLITE_OK) return rc;
+    // stage 0: the k-th smallest exact distance among every strides[0]-th entry of the query's cells
+    if ((rc = exact_cells(strides[0], 0, 0, w.f.thr)) != ANNLITE_OK) return rc;
+    for (int s = 1; s < n_strides; ++s) {
+        const bool last = s == n_strides - 1;  // (strides[n_strides - 1] == 1)
+        ANNLITE_HIP_TRY(hipMemsetAsync(w.f.cnt, 0, (size_t)B * 4, st));
+        if ((rc = filter(strides[s])) != ANNLITE_OK) return rc;
+        // the list re-rank of annlite_flat_search_topk, unchanged: the lists hold offsets
+        hipLaunchKernelGGL(flat_exact_kernel<float>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.f.cand, w.f.cnt,
+                           kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0,
+                           last ? nullptr : w.f.thr, out_dist_dev, out_id_dev, w.f.ovf, w.f.ovf_total);
+        if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
+    }
+    // queries whose last list overflowed: exact sums over all their probed rows (the other waves leave at once)
+    return exact_cells(1, do_sqrt, 1, nullptr);
+}
+
 }  // namespace annlite
 
 using namespace annlite;
@@ -1097,7 +1411,7 @@ extern "C" int annlite_flat_row_norms(const float *vectors_dev, int64_t capacity
     if (n == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(vectors_dev && norms_dev, "null device pointer");
     hipLaunchKernelGGL(flat_norms_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, vectors_dev, (int)D, ids_dev,
-                       n, id_base, capacity, (const float *)nullptr, norms_dev);
+                       n, id_base, capacity, (const float *)nullptr, (const int32_t *)nullptr, 0, norms_dev);
     return launch_status("flat_norms_kernel");
 }
 
@@ -1163,7 +1477,7 @@ extern "C" int annlite_flat_centred_norms(const float *vectors_dev, int64_t capa
     if (n == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(vectors_dev && norms_dev && centre_dev, "null device pointer");
     hipLaunchKernelGGL(flat_norms_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, vectors_dev, (int)D, ids_dev, n,
-                       id_base, capacity, centre_dev, norms_dev);
+                       id_base, capacity, centre_dev, (const int32_t *)nullptr, 0, norms_dev);
     return launch_status("flat_norms_kernel");
 }
 
@@ -1232,7 +1546,7 @@ extern "C" int annlite_flat_row_norms_f16(const void *vectors_f16_dev, int64_t c
     if (n == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(vectors_f16_dev && norms_dev, "null device pointer");
     hipLaunchKernelGGL((flat_norms_kernel<false, _Float16>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const _Float16 *)vectors_f16_dev, (int)D, ids_dev, n, id_base, capacity, (const float *)nullptr, norms_dev);
+                       (const _Float16 *)vectors_f16_dev, (int)D, ids_dev, n, id_base, capacity, (const float *)nullptr, (const int32_t *)nullptr, 0, norms_dev);
     return launch_status("flat_norms_kernel");
 }
 
@@ -1354,38 +1668,102 @@ extern "C" int annlite_ivf_flat_search_topk(int metric, const float *queries_dev
         return ANNLITE_ERR_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
-    const dim3 qgrid((unsigned)((B + 3) / 4));
-    ANNLITE_HIP_TRY(hipMemsetAsync(w.f.ovf_total, 0, 256, st));
-    auto exact_cells = [&](int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
-        hipLaunchKernelGGL(ivf_flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, cells_dev, (int)P,
-                           (int)C, cell_rows_dev, perm_dev, n_perm, stride, valid_bits_dev, (int)k, sqrt_out, only_overflowed, thr_out,
-                           out_dist_dev, out_id_dev, w.f.ovf);
-        return launch_status("ivf_flat_exact_kernel");
-    };
-    int64_t strides[kIvfFlatMaxStages];
-    const int n_strides = ivf_flat_strides(max_probed_rows, strides);
-    if (n_strides == 0) return exact_cells(1, do_sqrt, 0, nullptr);  // few probed rows: exact sums over all of them
-    int rc = annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.f.qnorm, stream);
-    if (rc != ANNLITE_OK) return rc;
-    // the (cell, queries that probe it) tiles of the filter stages
-    rc = annlite_ivf_plan(cells_dev, B, P, C, kFlatTile, cell_rows_dev, cell_order_dev, w.n_tiles, w.vmap, w.slot_of, w.tile_rows, w.n_used,
-                          stream);
-    if (rc != ANNLITE_OK) return rc;
-    // stage 0: the k-th smallest exact distance among every strides[0]-th entry of the query's cells
-    if ((rc = exact_cells(strides[0], 0, 0, w.f.thr)) != ANNLITE_OK) return rc;
-    for (int s = 1; s < n_strides; ++s) {
-        const bool last = s == n_strides - 1;  // (strides[n_strides - 1] == 1)
-        ANNLITE_HIP_TRY(hipMemsetAsync(w.f.cnt, 0, (size_t)B * 4, st));
-        rc = ivf_flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, N, perm_dev, n_perm, w, max_cell_rows, strides[s],
-                                    valid_bits_dev, st);
-        if (rc != ANNLITE_OK) return rc;
-        // the list re-rank of annlite_flat_search_topk, unchanged: the lists hold offsets
-        hipLaunchKernelGGL(flat_exact_kernel<float>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.f.cand, w.f.cnt,
-                           kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0,
-                           last ? nullptr : w.f.thr, out_dist_dev, out_id_dev, w.f.ovf, w.f.ovf_total);
-        if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
+    return ivf_flat_search_staged(
+        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev, cell_order_dev,
+        max_probed_rows, k, flags, out_dist_dev, out_id_dev, w, st,
+        [&]() { return annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.f.qnorm, stream); },
+        [&](int64_t stride) {
+            return ivf_flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, N, perm_dev, n_perm, w, max_cell_rows, stride,
+                                          valid_bits_dev, st);
+        });
+}
+
+// ---- the split filter over cell tiles ---------------------------------------------------------------------------------------------------
+extern "C" int annlite_ivf_flat_centred_norms(const float *vectors_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n,
+                                              int64_t id_base, const float *centres_dev, int64_t C, const int32_t *cell_of_dev,
+                                              float *norms_dev, void *stream) {
+    ANNLITE_REQUIRE(capacity >= 0 && D >= 1 && n >= 0 && D <= INT32_MAX && C >= 1 && C <= 16384, "bad shape");
+    if (n == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(vectors_dev && norms_dev && centres_dev && cell_of_dev, "null device pointer");
+    hipLaunchKernelGGL(flat_norms_kernel<true>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, vectors_dev, (int)D, ids_dev, n,
+                       id_base, capacity, centres_dev, cell_of_dev, (int)C, norms_dev);
+    return launch_status("flat_norms_kernel");
+}
+
+extern "C" int annlite_ivf_flat_search_split_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t D, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    ANNLITE_REQUIRE(B >= 0 && P >= 1 && C >= 1 && D >= 1 && D <= kSplitMaxDim && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
+                    (long long)kSplitMaxDim);
+    *bytes = (int64_t)ivf_flat_split_carve(nullptr, B, P, C, D).bytes;
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_ivf_flat_filter_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                             const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev,
+                                             int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                             const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t stride, const float *centres_dev,
+                                             const int32_t *cell_of_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
+                                             float *pair_norms_out_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes,
+                                             void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
+                    "bad shape (D <= %lld)", (long long)kSplitMaxDim);
+    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && B * P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
+                        max_cell_rows <= n_perm,
+                    "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld", (long long)P, (long long)C, (long long)n_perm,
+                    (long long)max_cell_rows);
+    ANNLITE_REQUIRE(!centres_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "centres are for EUCLIDEAN only");
+    ANNLITE_REQUIRE(!centres_dev || cell_of_dev, "centres need cell_of_dev");
+    if (B == 0 || n_perm == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && perm_dev && cells_dev && cell_rows_dev && cell_order_dev && bounds_dev &&
+                        cand_dev && count_dev && workspace_dev,
+                    "null device pointer");
+    const IvfFlatSplitWs w = ivf_flat_split_carve(workspace_dev, B, P, C, D);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
     }
-    // queries whose last list overflowed: exact sums over all their probed rows (the other waves leave at once)
-    return exact_cells(1, do_sqrt, 1, nullptr);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = annlite_ivf_plan(cells_dev, B, P, C, kFlatTile, cell_rows_dev, cell_order_dev, w.i.n_tiles, w.i.vmap, w.i.slot_of, w.i.tile_rows,
+                              w.i.n_used, stream);
+    if (rc != ANNLITE_OK) return rc;
+    if ((rc = ivf_flat_split_prepare(queries_dev, B, P, C, D, cells_dev, centres_dev, w, pair_norms_out_dev, st)) != ANNLITE_OK) return rc;
+    return ivf_flat_split_launch_filter(metric, B, D, vectors_dev, centres_dev, C, cell_of_dev, norms_dev, N, perm_dev, n_perm, w, max_cell_rows,
+                                        stride, valid_bits_dev, bounds_dev, cand_dev, count_dev, scores_dev, st);
+}
+
+extern "C" int annlite_ivf_flat_search_topk_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                                  const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev,
+                                                  const int32_t *cells_dev, int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm,
+                                                  const int64_t *cell_rows_dev, const int32_t *cell_order_dev, int64_t max_cell_rows,
+                                                  int64_t max_probed_rows, const float *centres_dev, const int32_t *cell_of_dev, int64_t k,
+                                                  int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
+                                                  size_t workspace_bytes, void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
+                    "bad shape (1 <= k <= 64, D <= %lld)", (long long)kSplitMaxDim);
+    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && B * P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
+                        max_cell_rows <= n_perm && max_probed_rows >= 0,
+                    "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld max_probed_rows=%lld", (long long)P, (long long)C,
+                    (long long)n_perm, (long long)max_cell_rows, (long long)max_probed_rows);
+    ANNLITE_REQUIRE(!centres_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "centres are for EUCLIDEAN only");
+    ANNLITE_REQUIRE(!centres_dev || cell_of_dev, "centres need cell_of_dev");
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && cells_dev && cell_rows_dev && cell_order_dev &&
+                        (n_perm == 0 || (vectors_dev && norms_dev && perm_dev)),
+                    "null device pointer");
+    const IvfFlatSplitWs w = ivf_flat_split_carve(workspace_dev, B, P, C, D);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    return ivf_flat_search_staged(
+        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev, cell_order_dev,
+        max_probed_rows, k, flags, out_dist_dev, out_id_dev, w.i, st,
+        [&]() { return ivf_flat_split_prepare(queries_dev, B, P, C, D, cells_dev, centres_dev, w, nullptr, st); },
+        [&](int64_t stride) {
+            return ivf_flat_split_launch_filter(metric, B, D, vectors_dev, centres_dev, C, cell_of_dev, norms_dev, N, perm_dev, n_perm, w,
+                                                max_cell_rows, stride, valid_bits_dev, w.i.f.thr, w.i.f.cand, w.i.f.cnt, nullptr, st);
+        });
 }

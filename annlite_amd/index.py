@@ -96,6 +96,9 @@ class AnnLite:
     :param flat_filter: ``'f32'`` (default) or ``'bf16x3'``, with ``centre`` (``'mean'``, ``None`` or an array) (kwargs, same channel;
         the float indexes -- no ``n_subvectors`` --, dropped for the indexes over PQ codes, ignored with ``n_cells > 1``): the filter
         of the exact float search; ``'bf16x3'`` is the one for data with a large common offset (``FlatGpuIndex``)
+    :param cell_filter: ``'f32'`` (default) or ``'bf16x3'`` (kwarg, same channel; ``n_cells > 1`` with ``ivf_prune=True`` and no
+        ``n_subvectors``, dropped for every other index): the filter over the cell tiles of ``IvfFlatGpuIndex``; ``'bf16x3'`` centres
+        every tile on its cell's centroid -- the one for data with a common offset, the same answer bit for bit
     :param dtype: ``np.float32`` (default) or ``np.float16`` (kwarg, same channel; the reference's ``dtype`` of its index plug-ins):
         without ``n_subvectors``, ``n_cells > 1`` and ``graph`` it reaches ``FlatGpuIndex``, which then stores its rows in half
         precision -- half the HBM, the answer of the f32 index over the rounded rows bit for bit, its own filter ``'f16x2'`` (no
@@ -241,6 +244,8 @@ class AnnLite:
             if graph:  # (build='gpu', n_cells == 1: the constructor refuses the rest)
                 from .core.index.hnsw_flat_gpu import HnswFlatGpuIndex
 
+                kw.pop('cell_filter', None)  # (the cells' option)
+
                 return HnswFlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
             kw.pop('build', None)
             kw.pop('filter_search', None)  # (the float graph's option: these indexes answer a filter exactly)
@@ -248,10 +253,11 @@ class AnnLite:
                 from .core.index.ivf_flat_gpu import IvfFlatGpuIndex
 
                 return IvfFlatGpuIndex(dim=self._index_dim, metric=self.metric, vq_codec=self._vq_codec, n_probe=self._n_probe_arg, **kw)
+            kw.pop('cell_filter', None)  # (the cells' option)
             return FlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
         if not (self._vq_codec is None and kw.get('graph')):
             kw.pop('filter_search', None)  # (the graph indexes' option: the other indexes over PQ codes answer a filter exactly)
-        for name in ('flat_filter', 'centre'):  # (the float indexes' options: nothing over PQ codes runs that filter)
+        for name in ('flat_filter', 'centre', 'cell_filter'):  # (the float indexes' options: nothing over PQ codes runs that filter)
             kw.pop(name, None)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')

@@ -1040,6 +1040,80 @@ def ivf_flat_search_topk(metric: int, queries: torch.Tensor, vectors: torch.Tens
     return od, oi
 
 
+def ivf_flat_centred_norms(vectors: torch.Tensor, centres: torch.Tensor, cell_of: torch.Tensor, ids: Optional[torch.Tensor] = None,
+                           n: Optional[int] = None, id_base: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``annlite_ivf_flat_centred_norms``: ``out[row] = |fl(vectors[row] - centres[cell_of[row]])|^2`` for the rows ``ids`` (i64) or
+    ``id_base .. id_base + n``: ``flat_centred_norms`` with the centre chosen per row (``centres`` f32 [C, D], ``cell_of`` i32
+    [capacity])."""
+    cap, D = vectors.shape
+    assert centres.dtype == torch.float32 and centres.ndim == 2 and centres.shape[1] == D and centres.is_contiguous()
+    assert cell_of.dtype == torch.int32 and cell_of.numel() >= cap and cell_of.is_contiguous()
+    if out is None:
+        out = torch.zeros((cap,), dtype=torch.float32, device=vectors.device)
+    cnt = ids.numel() if ids is not None else (cap - id_base if n is None else n)
+    check(lib().annlite_ivf_flat_centred_norms(vectors.data_ptr(), cap, D, _ptr(ids), cnt, id_base, centres.data_ptr(), centres.shape[0],
+                                               cell_of.data_ptr(), out.data_ptr(), stream_ptr()), 'ivf_flat_centred_norms')
+    return out
+
+
+def _ivf_flat_split_workspace(B: int, P: int, n_cells: int, D: int, k: int, dev, workspace: Optional[ScanWorkspace]) -> torch.Tensor:
+    need = ctypes.c_int64(0)
+    check(lib().annlite_ivf_flat_search_split_workspace_bytes(B, P, n_cells, D, k, ctypes.byref(need)),
+          'ivf_flat_search_split_workspace_bytes')
+    return (workspace or ScanWorkspace()).get(int(need.value), dev)
+
+
+def ivf_flat_filter_split(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
+                          cells: torch.Tensor, n_cells: int, perm: torch.Tensor, cell_rows: torch.Tensor, cell_order: torch.Tensor,
+                          max_cell_rows: int, centres: Optional[torch.Tensor] = None, cell_of: Optional[torch.Tensor] = None,
+                          valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, stride: int = 1, scores: bool = False,
+                          workspace: Optional[ScanWorkspace] = None):
+    """``annlite_ivf_flat_filter_split``: the split-bf16 filter stage over the (cell, queries) tiles alone -- ``flat_filter_split`` of the
+    cells.  ``norms`` are ``ivf_flat_centred_norms`` with the same ``centres`` (``flat_row_norms`` without).  ``(cand i32 [B, cap],
+    count i32 [B], pair_norms f32 [B, P])`` -- the last as the filter used them -- and, with ``scores=True``, the filter's score by
+    (query, row offset), f32 [B, N]: NaN where the filter evaluated nothing (cell not probed, row not valid)."""
+    B, D = queries.shape
+    P = cells.shape[1]
+    N = vectors.shape[0] if n_rows is None else n_rows
+    cap = flat_list_capacity()
+    dev = queries.device
+    ws = _ivf_flat_split_workspace(B, P, n_cells, D, 1, dev, workspace)
+    cand = torch.empty((B, cap), dtype=torch.int32, device=dev)
+    count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    pn = torch.empty((B, P), dtype=torch.float32, device=dev)
+    sc = torch.full((B, N), float('nan'), dtype=torch.float32, device=dev) if scores else None
+    check(lib().annlite_ivf_flat_filter_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
+                                              cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
+                                              cell_order.data_ptr(), int(max_cell_rows), int(stride), _ptr(centres), _ptr(cell_of),
+                                              bounds.data_ptr(), cand.data_ptr(), count.data_ptr(), pn.data_ptr(), _ptr(sc),
+                                              ws.data_ptr(), ws.numel(), stream_ptr()), 'ivf_flat_filter_split')
+    return (cand, count, pn, sc) if scores else (cand, count, pn)
+
+
+def ivf_flat_search_topk_split(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, cells: torch.Tensor,
+                               n_cells: int, perm: torch.Tensor, cell_rows: torch.Tensor, cell_order: torch.Tensor, max_cell_rows: int,
+                               max_probed_rows: int, k: int, centres: Optional[torch.Tensor] = None,
+                               cell_of: Optional[torch.Tensor] = None, valid_bits: Optional[torch.Tensor] = None,
+                               n_rows: Optional[int] = None, sqrt: bool = False,
+                               workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_ivf_flat_search_topk_split``: ``ivf_flat_search_topk`` with the split-bf16 filter over the cell tiles, every tile
+    centred on its cell's row of ``centres`` f32 [C, D] (``norms``: see ``ivf_flat_filter_split``); the same answer, bit for bit.
+    ``flat_overflow_count`` / ``flat_list_counts`` read this workspace too."""
+    B, D = queries.shape
+    P = cells.shape[1]
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    ws = _ivf_flat_split_workspace(B, P, n_cells, D, k, dev, workspace)
+    od = torch.empty((B, k), dtype=torch.float32, device=dev)
+    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
+    check(lib().annlite_ivf_flat_search_topk_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N,
+                                                   _ptr(valid_bits), cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(),
+                                                   cell_rows.data_ptr(), cell_order.data_ptr(), int(max_cell_rows), int(max_probed_rows),
+                                                   _ptr(centres), _ptr(cell_of), int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), stream_ptr()), 'ivf_flat_search_topk_split')
+    return od, oi
+
+
 # ---------------------------------------------------------------------------------------------- PCA projector
 def _row_stride(t: torch.Tensor, what: str) -> int:
     assert t.dim() == 2 and t.dtype == torch.float32, f'{what} must be a 2-D float32 tensor'

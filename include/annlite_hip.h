@@ -627,6 +627,41 @@ ANNLITE_API int annlite_ivf_flat_search_topk(int metric, const float *queries_de
                                  int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
                                  void *stream);
 
+/* The same search with the SPLIT filter over the cell tiles ("split filter over cell tiles"): replaces the
+ * f32 filter stage of annlite_ivf_flat_search_topk with annlite_flat_search_topk_split's contraction -- three bf16 MFMAs over centred
+ * values -- where the centre of a (cell, queries) tile is the CENTROID OF ITS CELL: centres_dev f32 [C][D] (NULL: no centring; a
+ * centre is taken for EUCLIDEAN only), cell_of_dev i32 [capacity] the cell of every row offset.  The slack is relative to
+ * |x - centroid|^2 + |q - centroid|^2, so data with a common offset no longer passes every probed row.  The exact stages and
+ * therefore the answer are annlite_ivf_flat_search_topk's, bit for bit.  1 <= D <= 32768.  No reference counterpart. */
+/* annlite_flat_centred_norms with the centre chosen per row: norms_dev[row] = |fl(vectors[row] - centres[cell_of[row]])|^2, the norms
+ * column the split filter reads when it has centres.  A cell id outside [0, C) reads cell 0, as annlite_ivf_plan does. */
+ANNLITE_API int annlite_ivf_flat_centred_norms(const float *vectors_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n,
+                                   int64_t id_base, const float *centres_dev, int64_t C, const int32_t *cell_of_dev, float *norms_dev,
+                                   void *stream);
+ANNLITE_API int annlite_ivf_flat_search_split_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t D, int64_t k, int64_t *bytes);
+/* The split filter stage alone (tests and measurements): the annlite_flat_filter_split of the cells.  The call plans the tiles,
+ * centres and splits the queries of every (query, probe) pair into the workspace (annlite_ivf_flat_search_split_workspace_bytes of
+ * the same B, P, C, D) and filters every stride-th entry of each probed cell against bounds_dev f32 [B].  norms_dev:
+ * annlite_ivf_flat_centred_norms with the same centres (annlite_flat_row_norms without).  cand_dev i32 [B][capacity] /
+ * count_dev i32 [B] (zeroed by the caller) as annlite_flat_filter; pair_norms_out_dev (may be NULL) f32 [B][P] receives
+ * |fl(q - centre of the pair's cell)|^2 as the filter used it; scores_dev (may be NULL) f32 [B][N] receives the filter's score v by
+ * (query, row offset) for every pair it evaluated -- a row that is not valid or not probed keeps the caller's value. */
+ANNLITE_API int annlite_ivf_flat_filter_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                  const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev,
+                                  int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                  const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t stride, const float *centres_dev,
+                                  const int32_t *cell_of_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
+                                  float *pair_norms_out_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes,
+                                  void *stream);
+/* annlite_ivf_flat_search_topk with the split filter: the same stages, lists, capacity and overflow route (annlite_flat_overflow_count
+ * and annlite_flat_list_counts read this workspace too).  norms_dev as for annlite_ivf_flat_filter_split. */
+ANNLITE_API int annlite_ivf_flat_search_topk_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                       const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev,
+                                       int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                       const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t max_probed_rows,
+                                       const float *centres_dev, const int32_t *cell_of_dev, int64_t k, int flags, float *out_dist_dev,
+                                       int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Pruned (IVF) search over cells (follow-on of rank 4).
  * Reference structure: AnnLite(n_cells > 1): VQCodec coarse quantiser (annlite/core/codec/vq.py),
