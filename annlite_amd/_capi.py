@@ -79,6 +79,7 @@ SYMBOLS = (
     'annlite_kmeans_update',
     'annlite_exact_gather_dist',
     'annlite_exact_gather_dist_f16',
+    'annlite_exact_gather_dist_i8',
     'annlite_ivf_select_cells',
     'annlite_ivf_max_tiles',
     'annlite_ivf_plan',
@@ -122,6 +123,11 @@ SYMBOLS = (
     'annlite_flat_search_f16_workspace_bytes',
     'annlite_flat_filter_f16',
     'annlite_flat_search_topk_f16',
+    'annlite_flat_row_norms_i8',
+    'annlite_flat_i8_slack',
+    'annlite_flat_search_i8_workspace_bytes',
+    'annlite_flat_filter_i8',
+    'annlite_flat_search_topk_i8',
     'annlite_ivf_flat_stages',
     'annlite_ivf_flat_search_workspace_bytes',
     'annlite_ivf_flat_search_topk',
@@ -220,6 +226,7 @@ def lib() -> ctypes.CDLL:
     L.annlite_kmeans_update.argtypes = [vp, vp, i64, i64, i64, vp, vp]
     L.annlite_exact_gather_dist.argtypes = [i32, vp, i64, i64, vp, i64, vp, i64, vp, vp]
     L.annlite_exact_gather_dist_f16.argtypes = [i32, vp, i64, i64, vp, i64, vp, i64, vp, vp]
+    L.annlite_exact_gather_dist_i8.argtypes = [i32, vp, i64, i64, vp, ctypes.c_float, i64, vp, i64, vp, vp]
     L.annlite_codes_skew.argtypes = [vp, i64, i64, vp, i64, vp, i32, vp]
     L.annlite_ivf_select_cells.argtypes = [i32, vp, i64, i64, vp, i64, i64, vp, vp]
     L.annlite_ivf_max_tiles.argtypes = [i64, i64, i64, i64]
@@ -267,6 +274,11 @@ def lib() -> ctypes.CDLL:
     L.annlite_flat_search_f16_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_flat_filter_f16.argtypes = [i32, vp, i64, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.annlite_flat_search_topk_f16.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, i64, i32, vp, vp, vp, sz, vp]
+    L.annlite_flat_row_norms_i8.argtypes = [vp, ctypes.c_float, i64, i64, vp, i64, i64, vp, vp]
+    L.annlite_flat_i8_slack.argtypes = [i32, i64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.annlite_flat_search_i8_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_flat_filter_i8.argtypes = [i32, vp, i64, i64, vp, ctypes.c_float, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.annlite_flat_search_topk_i8.argtypes = [i32, vp, i64, i64, vp, ctypes.c_float, vp, i64, vp, i64, i32, vp, vp, vp, sz, vp]
     L.annlite_ivf_flat_stages.argtypes = [i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32)]
     L.annlite_ivf_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_ivf_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, vp,

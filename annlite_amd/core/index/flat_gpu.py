@@ -25,7 +25,17 @@ MFMA operand, so the filter (``'f16x2'``: the query carried as two f16 numbers, 
 ("f16 rows").  A value beyond the f16 range (65504) is stored as an infinity and behaves as the f32 index
 holding that infinity does.  There is no centre: a common offset destroys f16 data before any filter sees it (1000.37 is stored as
 1000.5) -- centre such data before adding it.
+
+``dtype=np.int8`` stores the rows as int8 codes: ``int8 [capacity, D]``, a quarter of the bytes.  A coordinate ``x`` (pre-processed as
+always: COSINE normalises in f32 first) is stored as ``c = clamp(rne(x / s), -127, 127)`` and stands for the value ``s * c``; the scale
+``s = int8_scale`` is a power of two in ``[2**-24, 2**24]``, so ``x / s`` and ``s * c`` are exact in f32 (default ``1.0`` for EUCLIDEAN and
+INNER_PRODUCT -- int8 embeddings as given -- and ``2**-7`` for COSINE, whose coordinates lie in [-1, 1]).  Rounding is to nearest even;
+values beyond ``+-127 s``, the infinities included, saturate; a NaN coordinate is stored as 0; -128 is never stored.  Queries stay f32.
+The answer is, bit for bit, what the f32 index returns when it holds the rows ``s * c``: the exact stage keeps its arithmetic on the
+widened values, and the filter (``'i8x3'``: the query rounded to a 21-bit integer and carried as three int8 digits, three i8 MFMAs
+into integer accumulators) contracts without any rounding at all ("int8 rows").  No centre, as for f16.
 """
+import math
 from pathlib import Path
 from typing import Optional, Tuple, Union
 
@@ -56,22 +66,66 @@ def flat_f16_slack_constants(metric: Metric, dim: int) -> Tuple[np.float32, np.f
     return ops.flat_f16_slack(int(Metric(metric)), dim)
 
 
-def is_f16(dtype) -> bool:
-    """whether a ``dtype=`` argument (any spelling ``base.str2dtype`` takes) selects half-precision rows"""
+def flat_i8_slack_constants(metric: Metric, dim: int) -> Tuple[np.float32, np.float32]:
+    """``(c_rel, c_abs)`` of the int8 filter (``dtype=np.int8``); its slack has a third, per-query term the library computes,
+    ``1.001 * 127 * dim * 2^-e`` with ``2^e`` the query's power of two (``annlite_flat_i8_slack``; derivation:
+    DESIGN.md section 3.6, "int8 rows")."""
+    return ops.flat_i8_slack(int(Metric(metric)), dim)
+
+
+def row_kind(dtype) -> str:
+    """How a ``dtype=`` argument (any spelling ``base.str2dtype`` takes) has ``FlatGpuIndex`` store its rows: ``'f16'``, ``'i8'`` or
+    -- every other dtype -- ``'f32'``."""
     try:
-        return np.dtype(str2dtype(dtype) if isinstance(dtype, str) else dtype) == np.float16
+        dt = np.dtype(str2dtype(dtype) if isinstance(dtype, str) else dtype)
     except TypeError:
-        return False
+        return 'f32'
+    return 'f16' if dt == np.float16 else 'i8' if dt == np.int8 else 'f32'
+
+
+def is_f16(dtype) -> bool:
+    """whether a ``dtype=`` argument selects half-precision rows"""
+    return row_kind(dtype) == 'f16'
+
+
+def is_i8(dtype) -> bool:
+    """whether a ``dtype=`` argument selects int8 rows"""
+    return row_kind(dtype) == 'i8'
+
+
+I8_SCALE_LOG2_RANGE = (-24, 24)
+
+
+def check_i8_scale(scale) -> float:
+    """``int8_scale`` as a float: a positive power of two in ``[2**-24, 2**24]``, else ``ValueError``"""
+    try:
+        value = float(scale)
+        mant, exp = math.frexp(value)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f'int8_scale={scale!r}: a power of two in [2**-24, 2**24]') from None
+    if not (value > 0 and mant == 0.5 and I8_SCALE_LOG2_RANGE[0] <= exp - 1 <= I8_SCALE_LOG2_RANGE[1]):
+        raise ValueError(f'int8_scale={scale!r}: a power of two in [2**-24, 2**24]')
+    return value
+
+
+def quantise_i8(x: torch.Tensor, scale: float) -> torch.Tensor:
+    """f32 ``x`` -> the int8 codes ``clamp(rne(x / scale), -127, 127)``, NaN -> 0 (``x / scale`` is exact: the scale is a power of
+    two; ``torch.round`` rounds halves to even)."""
+    t = torch.nan_to_num(x.to(torch.float32) * (1.0 / scale), nan=0.0, posinf=127.0, neginf=-127.0)
+    return torch.round(t).clamp_(-127.0, 127.0).to(torch.int8)
 
 
 class FlatGpuIndex(RowStoreIndex):
     """
-    :param dtype: ``np.float32`` (default) or ``np.float16``: how the rows are stored (module docstring).  ``np.float16`` takes neither
-        ``flat_filter='bf16x3'`` nor a ``centre`` and needs ``dim <= 32768``; any other dtype stores f32, as before.
+    :param dtype: ``np.float32`` (default), ``np.float16`` or ``np.int8``: how the rows are stored (module docstring).  ``np.float16``
+        and ``np.int8`` take neither ``flat_filter='bf16x3'`` nor a ``centre`` and need ``dim <= 32768``; any other dtype stores f32.
+    :param int8_scale: with ``dtype=np.int8`` only: the value of one code step, a power of two in ``[2**-24, 2**24]``.  ``None``
+        (default): ``1.0`` for EUCLIDEAN and INNER_PRODUCT, ``2**-7`` for COSINE.  ``int8_scale_`` reads the one in use.
     :param flat_filter: ``'f32'`` (default): the f32 MFMA filter.  ``'bf16x3'``: the split-bf16 filter over centred rows -- the same
         answer bit for bit, a slack that does not grow with a common offset of the data, ``dim <= 32768``.  Searches with
         ``limit > 64`` keep the f32 filter under either value: offset data stays slow there.  ``'f16x2'``: the filter over f16 rows --
-        what ``dtype=np.float16`` runs (and reports here), at every ``limit``; with f32 rows it is an error.
+        what ``dtype=np.float16`` runs (and reports here), at every ``limit``; with f32 rows it is an error.  ``'i8x3'``: the same
+        for ``dtype=np.int8``.
     :param centre: what ``'bf16x3'`` subtracts from rows and queries before it splits them, EUCLIDEAN only -- INNER_PRODUCT and COSINE
         are not invariant under a shift and run the split filter on the values themselves.  ``'mean'`` (default): the f32 mean of the
         first ``add_with_ids`` batch, frozen until ``reset()``; an array ``[dim]``: that point; ``None``: no centring.  Any centre gives
@@ -80,16 +134,31 @@ class FlatGpuIndex(RowStoreIndex):
     """
     FORMAT = 'annlite_amd.FlatGpuIndex/1'
     STATE_KEYS = ('dim', 'metric')
-    FLAT_FILTERS = ('f32', 'bf16x3', 'f16x2')
+    FLAT_FILTERS = ('f32', 'bf16x3', 'f16x2', 'i8x3')
     SPLIT_MAX_DIM = 32768    # (annlite_flat_split_slack: the range of the slack's derivation)
     FILTER_MIN_ROWS = 4097   # (kFlatSample + 1 in flat.hip: smaller tables are answered by exact sums, no filter runs)
 
     def __init__(self, dim: int, dtype: np.dtype = np.float32, metric: Metric = Metric.COSINE,
-                 index_file: Optional[Union[str, Path]] = None, flat_filter: str = 'f32', centre='mean', **kwargs):
+                 index_file: Optional[Union[str, Path]] = None, flat_filter: str = 'f32', centre='mean', int8_scale=None, **kwargs):
         if flat_filter not in self.FLAT_FILTERS:
             raise ValueError(f"flat_filter={flat_filter!r}: 'f32' (the f32 MFMA filter), 'bf16x3' (the split-bf16 filter over centred rows) "
-                             "or, with dtype=np.float16, 'f16x2'")
-        self._f16 = is_f16(dtype)
+                             "or, with dtype=np.float16, 'f16x2', with dtype=np.int8, 'i8x3'")
+        kind = row_kind(dtype)
+        self._f16, self._i8 = kind == 'f16', kind == 'i8'
+        self._i8_scale = None
+        if self._i8:
+            if flat_filter in ('bf16x3', 'f16x2'):
+                raise ValueError(f"flat_filter={flat_filter!r} is not a filter over int8 rows: dtype=np.int8 runs 'i8x3'")
+            if not (isinstance(centre, str) and centre == 'mean'):
+                raise ValueError(f'centre={centre!r} with dtype=np.int8: int8 rows have no centre (centre the data before adding it)')
+            if dim > self.SPLIT_MAX_DIM:
+                raise ValueError(f'dtype=np.int8 takes dim <= {self.SPLIT_MAX_DIM}')
+            self._i8_scale = check_i8_scale((2.0 ** -7 if Metric(metric) == Metric.COSINE else 1.0) if int8_scale is None else int8_scale)
+            flat_filter = 'i8x3'
+        elif int8_scale is not None:
+            raise ValueError(f'int8_scale={int8_scale!r} is the scale of int8 rows: pass dtype=np.int8')
+        elif flat_filter == 'i8x3':
+            raise ValueError("flat_filter='i8x3' is the filter over int8 rows: pass dtype=np.int8")
         if self._f16:
             if flat_filter == 'bf16x3':
                 raise ValueError("flat_filter='bf16x3' splits f32 rows: dtype=np.float16 runs 'f16x2'")
@@ -110,7 +179,7 @@ class FlatGpuIndex(RowStoreIndex):
             raise ValueError(f"flat_filter='bf16x3' takes dim <= {self.SPLIT_MAX_DIM}")
         self.flat_filter = flat_filter
         self.centre = centre
-        self.last_flat_filter = None  # 'f32' / 'bf16x3' / 'f16x2': the filter of the last search_batch; None: it ran none
+        self.last_flat_filter = None  # 'f32' / 'bf16x3' / 'f16x2' / 'i8x3': the filter of the last search_batch; None: it ran none
         self._centre_dev = None
         self._centred = flat_filter == 'bf16x3' and Metric(metric) == Metric.EUCLIDEAN and centre is not None
         super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
@@ -118,6 +187,11 @@ class FlatGpuIndex(RowStoreIndex):
         self._overflowed = 0  # (of the last search_batch; None: ask the library's workspace)
         if index_file:
             self.load(index_file)
+
+    @property
+    def int8_scale_(self) -> Optional[float]:
+        """The value of one code step of an int8 row store; None for the other dtypes."""
+        return self._i8_scale
 
     # ------------------------------------------------------------------ the split filter's centre
     @property
@@ -144,10 +218,15 @@ class FlatGpuIndex(RowStoreIndex):
     # ------------------------------------------------------------------ storage (row_store.py)
     def _columns(self):
         """``_cnorms``: the norms of the centred rows, kept only where the split filter has a centre (it reads ``_norms`` otherwise)"""
-        return {'_vectors': ((self.dim,), torch.float16 if self._f16 else torch.float32), '_norms': ((), torch.float32),
+        vt = torch.float16 if self._f16 else torch.int8 if self._i8 else torch.float32
+        return {'_vectors': ((self.dim,), vt), '_norms': ((), torch.float32),
                 '_cnorms': ((), torch.float32) if self._centred else None}
 
     def _write_rows(self, x, ids):
+        if self._i8:  # (rounded once, to nearest even, saturating at +-127; NaN: 0)
+            self._vectors[ids] = quantise_i8(x, self._i8_scale)
+            ops.flat_row_norms_i8(self._vectors, self._i8_scale, ids=ids, out=self._norms)
+            return
         if self._f16:  # (rounded once, to nearest even; beyond the f16 range: an infinity)
             self._vectors[ids] = x.to(torch.float16)
             ops.flat_row_norms_f16(self._vectors, ids=ids, out=self._norms)
@@ -160,8 +239,10 @@ class FlatGpuIndex(RowStoreIndex):
 
     def _dump_state(self, N):
         """vectors as stored (normalised for COSINE; in the index's dtype); norms are recomputed on load.  ``centre`` (optional key):
-        the split filter's"""
+        the split filter's; ``int8_scale`` (optional key): what one step of int8 ``vectors`` stands for"""
         state = {'vectors': self._vectors[:N].cpu().numpy()}
+        if self._i8:
+            state['int8_scale'] = float(self._i8_scale)
         if self._centre_dev is not None:
             state['centre'] = self.centre_
         return state
@@ -169,8 +250,23 @@ class FlatGpuIndex(RowStoreIndex):
     def _load_state(self, state, N):
         self._centre_dev = None
         if N:
-            # (a file of the other dtype is converted: f32 into an f16 index rounds, f16 into an f32 index widens)
-            self._vectors[:N] = self._to_dev(state['vectors']).to(self._vectors.dtype)
+            # (a file of another dtype is converted: f32 into an f16 index rounds, f16 into an f32 index widens, floats into an int8
+            # index are quantised with the index's scale, int8 codes into a float index are widened with the file's)
+            stored = self._to_dev(state['vectors'])
+            if stored.dtype == torch.int8:
+                file_scale = check_i8_scale(state.get('int8_scale', 1.0))
+                if self._i8 and file_scale != self._i8_scale:
+                    raise ValueError(f'the file holds int8 rows of int8_scale={file_scale!r}, this index stores int8_scale={self._i8_scale!r}: '
+                                     'codes of one scale are not codes of another (load into a float index, or construct with the '
+                                     "file's scale)")
+                if not self._i8:
+                    stored = stored.to(torch.float32) * file_scale  # (exact)
+            elif self._i8:
+                stored = quantise_i8(stored, self._i8_scale)
+            self._vectors[:N] = stored.to(self._vectors.dtype)
+            if self._i8:
+                ops.flat_row_norms_i8(self._vectors, self._i8_scale, n=N, out=self._norms)
+                return
             if self._f16:
                 ops.flat_row_norms_f16(self._vectors, n=N, out=self._norms)
                 return
@@ -204,7 +300,12 @@ class FlatGpuIndex(RowStoreIndex):
             d, i = empty_answer(B, k, dev)
         else:
             valid = self._valid if indices is None else self._filter_bits(indices)
-            if k <= 64 and self._f16:
+            if k <= 64 and self._i8:
+                d, i = ops.flat_search_topk_i8(int(self.metric), q, self._vectors, self._norms, k, self._i8_scale, valid_bits=valid,
+                                               n_rows=N, sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
+                self._overflowed = None
+                self.last_flat_filter = 'i8x3' if N >= self.FILTER_MIN_ROWS else None
+            elif k <= 64 and self._f16:
                 d, i = ops.flat_search_topk_f16(int(self.metric), q, self._vectors, self._norms, k, valid_bits=valid, n_rows=N,
                                                 sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
                 self._overflowed = None
@@ -225,6 +326,8 @@ class FlatGpuIndex(RowStoreIndex):
         return like_input(is_np, d, i)
 
     def _gather_dist(self, q, cand):
+        if self._i8:
+            return ops.exact_gather_dist_i8(int(self.metric), q, self._vectors, cand, self._i8_scale)
         return (ops.exact_gather_dist_f16 if self._f16 else ops.exact_gather_dist)(int(self.metric), q, self._vectors, cand)
 
     def _keyed_topk(self, q, cand, ok, kk):
@@ -280,7 +383,11 @@ class FlatGpuIndex(RowStoreIndex):
                 bounds.append(torch.topk(ds, kk, dim=1, largest=False).values[:, kk - 1] if sample.numel() >= kk
                               else torch.full((nb,), float('inf'), device=dev))
             bound = torch.cat(bounds).contiguous()  # (+inf -- fewer than k valid sampled rows, NaN distances -- passes everything)
-            if self._f16:
+            if self._i8:
+                cand32, count = ops.flat_filter_i8(int(self.metric), q, self._vectors, self._norms, bound, self._i8_scale, valid_bits=valid,
+                                                   n_rows=N, workspace=self._ws)[:2]
+                self.last_flat_filter = 'i8x3'
+            elif self._f16:
                 cand32, count = ops.flat_filter_f16(int(self.metric), q, self._vectors, self._norms, bound, valid_bits=valid, n_rows=N,
                                                     workspace=self._ws)[:2]
                 self.last_flat_filter = 'f16x2'

@@ -29,7 +29,7 @@ import torch
 from ... import ops
 from ...enums import Metric
 from .filter_walk import FilterWalkMixin
-from .flat_gpu import FlatGpuIndex, is_f16
+from .flat_gpu import FlatGpuIndex, is_f16, is_i8
 from .row_store import empty_answer, like_input, ranked_answer
 
 
@@ -56,6 +56,9 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
         self._check_filter_search(filter_search, "the parent's exact filtered search")
         if is_f16(dtype):
             raise NotImplementedError('dtype=np.float16: the float graph walks and builds over f32 rows only (half-precision rows exist '
+                                      'in the exhaustive FlatGpuIndex: no graph, n_cells=1)')
+        if is_i8(dtype):
+            raise NotImplementedError('dtype=np.int8: the float graph walks and builds over f32 rows only (int8 rows exist '
                                       'in the exhaustive FlatGpuIndex: no graph, n_cells=1)')
         super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
         self.ef_construction = int(ef_construction)  # hnsw/index.py:66-69

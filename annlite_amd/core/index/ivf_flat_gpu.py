@@ -31,7 +31,7 @@ from ... import ops
 from ...enums import Metric
 from ..codec.vq import VQCodec
 from .cells import CellColumnMixin
-from .flat_gpu import FlatGpuIndex, is_f16
+from .flat_gpu import FlatGpuIndex, is_f16, is_i8
 from .row_store import empty_answer, like_input, pad_to_k
 
 
@@ -70,6 +70,9 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         kwargs.pop('centre', None)
         if is_f16(kwargs.get('dtype', 'float32')):
             raise NotImplementedError('dtype=np.float16: the cell-tile kernels read f32 rows only (half-precision rows exist in the '
+                                      'exhaustive FlatGpuIndex: no graph, n_cells=1)')
+        if is_i8(kwargs.get('dtype', 'float32')):
+            raise NotImplementedError('dtype=np.int8: the cell-tile kernels read f32 rows only (int8 rows exist in the '
                                       'exhaustive FlatGpuIndex: no graph, n_cells=1)')
         super().__init__(dim, metric=metric, **kwargs)
 

@@ -7,6 +7,8 @@
 //   l2_normalize  annlite/math.py:6-18
 //   fit           annlite/core/codec/pq.py:89-115   (sklearn KMeans per sub-space: Lloyd iterations)
 //   exact dist    annlite/math.py:21-61 (cdist) as used by FlatIndex.search, flat_index.py:15-39
+#include <type_traits>
+
 #include "common.h"
 
 namespace annlite {
@@ -175,11 +177,18 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const float *__restr
 
 // ---- exact distances over candidate lists: one wave per (query, candidate) -------------------------
 // T: the row type, float or _Float16 (FlatGpuIndex's half-precision row store): an f16 value widens exactly, the rest is the f32 form's.
+// int8_t (its int8 row store): a code c stands for scale * c, scale a power of two -- exact as well; `scale` is read by that form only.
+template <class T>
+__device__ __forceinline__ float exact_gather_widen(T v, float scale) {
+    if constexpr (std::is_same<T, int8_t>::value) return scale * (float)v;
+    else return (float)v;
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void exact_gather_kernel(int metric, const float *__restrict__ q, int B, int D,
                                                           const T *__restrict__ x, int64_t N,
                                                           const int64_t *__restrict__ cand, int R,
-                                                          float *__restrict__ out) {
+                                                          float *__restrict__ out, float scale = 1.f) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= (int64_t)B * R) return;
@@ -194,11 +203,11 @@ __global__ __launch_bounds__(256) void exact_gather_kernel(int metric, const flo
     float s = 0.f;
     if (metric == ANNLITE_METRIC_EUCLIDEAN) {
         for (int j = lane; j < D; j += 64) {
-            const float d = (float)xr[j] - qr[j];
+            const float d = exact_gather_widen(xr[j], scale) - qr[j];
             s = __builtin_fmaf(d, d, s);
         }
     } else {
-        for (int j = lane; j < D; j += 64) s = __builtin_fmaf((float)xr[j], qr[j], s);
+        for (int j = lane; j < D; j += 64) s = __builtin_fmaf(exact_gather_widen(xr[j], scale), qr[j], s);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
@@ -379,6 +388,20 @@ extern "C" int annlite_exact_gather_dist(int metric, const float *queries_dev, i
     const int64_t total = B * R;
     hipLaunchKernelGGL(exact_gather_kernel<float>, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        metric, queries_dev, (int)B, (int)D, vectors_dev, N, cand_dev, (int)R, out_dev);
+    return launch_status("exact_gather_kernel");
+}
+
+extern "C" int annlite_exact_gather_dist_i8(int metric, const float *queries_dev, int64_t B, int64_t D,
+                                            const void *vectors_i8_dev, float scale, int64_t N, const int64_t *cand_dev, int64_t R,
+                                            float *out_dev, void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && R >= 0, "bad shape");
+    ANNLITE_REQUIRE_I8_SCALE(scale);
+    if (B * R == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && cand_dev && out_dev && (N == 0 || vectors_i8_dev), "null device pointer");
+    const int64_t total = B * R;
+    hipLaunchKernelGGL(exact_gather_kernel<int8_t>, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       metric, queries_dev, (int)B, (int)D, (const int8_t *)vectors_i8_dev, N, cand_dev, (int)R, out_dev, scale);
     return launch_status("exact_gather_kernel");
 }
 

@@ -26,6 +26,15 @@ int hip_fail(hipError_t e, const char *what);
         }                                       \
     } while (0)
 
+// log2 of a row scale the int8 row store accepts (a power of two in [2^-24, 2^24]: flat.hip, codec.hip); INT32_MIN for anything else
+inline int i8_scale_log2(float scale) {
+    int ex;
+    if (!(scale > 0.f) || !(scale < __builtin_inff()) || __builtin_frexpf(scale, &ex) != 0.5f || ex - 1 < -24 || ex - 1 > 24) return INT32_MIN;
+    return ex - 1;
+}
+#define ANNLITE_REQUIRE_I8_SCALE(scale) \
+    ANNLITE_REQUIRE(::annlite::i8_scale_log2(scale) != INT32_MIN, "bad int8 scale %g (a power of two in [2^-24, 2^24])", (double)(scale))
+
 inline int launch_status(const char *kernel) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, kernel);

@@ -29,13 +29,15 @@ constexpr double kFlatGrowth = 32.0;      // a stage's row set is at most this m
 // ---- |x|^2 per row: the lane-strided fmaf chain + butterfly of the exact kernels (relative error <= gamma(ceil(D/64) + 6)) ----
 // CENTRED: the same chain over c_j = fl(x_j - mu_j), the values the split filter contracts (second half of the filter section).
 // T: the row type, float or _Float16 (a half-precision row store, "f16 rows" below): an f16 value widens exactly, and everything after
-// the load is the f32 form's, operation for operation.
+// the load is the f32 form's, operation for operation.  int8_t ("int8 rows" below): a code c stands for scale * c, scale a power of
+// two, so the widened value is exact as well; `scale` is read by that instantiation only.
 // cell_of != NULL (CENTRED; the split filter over cell tiles, second half of the file): mu is f32 [C][D] and the row's centre is the
 // one of its cell, mu[cell_of[row]] (an id outside [0, C): cell 0, as ivf_flat_cell_range reads it).
 template <bool CENTRED, class T = float>
 __global__ __launch_bounds__(256) void flat_norms_kernel(const T *__restrict__ x, int D, const int64_t *__restrict__ ids, int64_t n,
                                                         int64_t id_base, int64_t capacity, const float *__restrict__ mu,
-                                                        const int32_t *__restrict__ cell_of, int C, float *__restrict__ norms) {
+                                                        const int32_t *__restrict__ cell_of, int C, float *__restrict__ norms,
+                                                        float scale = 1.f) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(256) void flat_norms_kernel(const T *__restrict__ x
     }
     float s = 0.f;
     for (int j = lane; j < D; j += 64) {
-        const float xv = (float)xr[j];
+        const float xv = std::is_same<T, int8_t>::value ? scale * (float)xr[j] : (float)xr[j];
         const float c = CENTRED ? xv - mu[j] : xv;
         s = __builtin_fmaf(c, c, s);
     }
@@ -532,6 +534,200 @@ __global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const 
     }
 }
 
+// ---- the int8 filter: rows STORED as int8 codes, an exact-integer contraction ("int8 rows") -------------------
+// A stored byte c (|c| <= 127) stands for the value s c, s = 2^ls the store's scale.  The f32 query becomes an integer: q' = q s 2^e (e per
+// query, so that max |q'| lies in [2^19, 2^20): s is folded in, so that <q, s c> = 2^-e sum q'_j c_j), Q = rne(q'), |Q| <= 2^20, split into
+// three balanced base-128 digits Q = d2 2^14 + d1 2^7 + d0, d0, d1 in [-64, 63], d2 in [-64, 64]: three int8 planes.  Per K step of 32
+// three v_mfma_i32_32x32x32_i8, one per plane, each into i32 accumulators of its own (|sum c d| <= D 127 64 < 2^31 for D <= 32768); the
+// epilogue recombines T = S2 2^14 + S1 2^7 + S0 in 64-bit integers -- exactly sum Q_j c_j: the contraction has NO rounding -- converts
+// T to f32 once and multiplies by 2^-e.  What is left of the error is |q' - Q| <= 1/2 per coordinate, carried by the per-query term.
+//
+// Operand map of v_mfma_i32_32x32x32_i8 as used here (four VGPRs = 16 bytes per operand and lane): lane l, r = l & 31, h = l >> 5,
+// holds A[row r][k = 16 h + j] and B[k = 16 h + j][col r] in byte j = 0 .. 15 of its fragment, bytes signed; C/D is the map of every
+// 32 x 32 form (col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)).  Checked with exact data, an asymmetric B and
+// D = 5 / 32 / 40 / 96 in tests/test_flat_i8_search.py -- once with small integer queries, whose Q = 8 q 2^14 lives in the d2 plane alone, and
+// once with queries whose Q has all three digits non-zero and a known fractional part (the three planes share the fragment loads, but the
+// weights 2^14 / 2^7 / 1 of the recombination and Q = rne(q') are pinned only by the second): which operand is rows and which queries, the
+// two lane halves taking different 16-byte chunks that together cover the K step, and the C tile's orientation all show there.  (A permutation of k INSIDE a lane's 16 bytes that is
+// the same for A and B cannot show in a contraction and does not matter to one.)
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kI8Depth = 64;            // coordinates = bytes per LDS stage: two K steps of 32
+constexpr int kI8Ld = kI8Depth + 16;    // LDS row pitch in bytes: 80, the image of the split and f16 kernels
+constexpr int kI8Threads = 512;         // 8 waves: 64 rows x 32 queries each, 2 MFMA tiles x 3 planes = 96 accumulator registers
+
+// p0 / p1 / p2 int8 [B][Dp] (Dp = D rounded up to 32, the padding zero): the digits d0, d1, d2.  qnorm[b] = |q|^2 of the UNSCALED query in
+// flat_norms_kernel's chain, qscale[b] = 2^-e, qslack[b] = 1.001 * 127 * D * 2^-e: the per-query term of the slack -- |q'_j - Q_j| <= 1/2
+// and |c_j| <= 127 put at most D 127 / 2 between sum q'_j c_j and sum Q_j c_j, twice that on 2 dot -- (0 for an all-zero query, whose
+// planes are exact).  E = e + ls = 20 - ex (max |q_j| = f 2^ex, f in [0.5, 1)), clamped from
+// above so that 2^E and 2^-e stay normal f32 numbers -- a smaller E only makes |Q| smaller.  A query with a NaN or an infinity, or one so large
+// that E would have to be RAISED to stay normal (|q|^2 is infinite there), has no integer planes: they are zero and qslack = +inf --
+// every row passes, the list overflows and the query takes the all-rows route.
+__global__ __launch_bounds__(256) void flat_i8_queries_kernel(const float *__restrict__ q, int B, int D, int Dp, int ls, int8_t *__restrict__ p0,
+                                                             int8_t *__restrict__ p1, int8_t *__restrict__ p2, float *__restrict__ qnorm,
+                                                             float *__restrict__ qscale, float *__restrict__ qslack) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float *qr = q + (int64_t)b * D;
+    float s = 0.f, m = 0.f;
+    bool bad = false;
+    for (int j = lane; j < D; j += 64) {
+        const float c = qr[j];
+        s = __builtin_fmaf(c, c, s);
+        const float a = __builtin_fabsf(c);
+        bad |= !(a < __builtin_inff());
+        m = __builtin_fmaxf(m, a);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s += __shfl_xor(s, o);
+        m = __builtin_fmaxf(m, __shfl_xor(m, o));
+    }
+    bad = __ballot(bad) != 0ull;
+    const bool zero = !bad && !(m > 0.f);
+    int E = ls;  // (e = 0: what an all-zero or unexpressible query is given)
+    if (!bad && !zero) {
+        int ex;
+        (void)frexpf(m, &ex);
+        E = 20 - ex;
+        const int lo = ls - 126 > -126 ? ls - 126 : -126, hi = ls + 126 < 126 ? ls + 126 : 126;
+        if (E < lo) bad = true, E = ls;
+        else if (E > hi) E = hi;
+    }
+    const float up = ldexpf(1.f, E);
+    for (int j = lane; j < Dp; j += 64) {
+        int Q = 0;
+        if (!bad && j < D) Q = (int)rintf(qr[j] * up);  // (|q' | < 2^20 (1 + 2^-23): the conversion is exact)
+        const int d0 = ((Q + 64) & 127) - 64;
+        const int Q1 = (Q - d0) >> 7;  // (a multiple of 128: the shift is exact)
+        const int d1 = ((Q1 + 64) & 127) - 64;
+        const int d2 = (Q1 - d1) >> 7;
+        p0[(int64_t)b * Dp + j] = (int8_t)d0;
+        p1[(int64_t)b * Dp + j] = (int8_t)d1;
+        p2[(int64_t)b * Dp + j] = (int8_t)d2;
+    }
+    if (lane == 0) {
+        qnorm[b] = s;
+        qscale[b] = ldexpf(1.f, ls - E);
+        qslack[b] = bad ? __builtin_inff() : zero ? 0.f : ldexpf(1.f, ls - E) * (127.f * 1.001f * (float)D);
+    }
+}
+
+// flat_f16_filter_kernel's job, grid, 128 x 128 workgroup tile, epilogue and `scores` output over x int8 [..][D], on 8 waves of 64 rows x
+// 32 queries.  VEC: D % 16 == 0 and x aligned to 16 bytes.
+template <bool VEC>
+__global__ __launch_bounds__(kI8Threads) void flat_i8_filter_kernel(int metric, const int8_t *__restrict__ p0, const int8_t *__restrict__ p1,
+                                                                   const int8_t *__restrict__ p2, int B, int D, int Dp,
+                                                                   const int8_t *__restrict__ x, const float *__restrict__ norms, int64_t S,
+                                                                   int64_t stride, const uint32_t *__restrict__ valid,
+                                                                   const float *__restrict__ qnorm, const float *__restrict__ qscale,
+                                                                   const float *__restrict__ qslack, const float *__restrict__ thr, float c_rel,
+                                                                   float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap,
+                                                                   int n_qtiles, float *__restrict__ scores) {
+    __shared__ __attribute__((aligned(16))) int8_t As[kFlatTile * kI8Ld];
+    __shared__ __attribute__((aligned(16))) int8_t B0[kFlatTile * kI8Ld];
+    __shared__ __attribute__((aligned(16))) int8_t B1[kFlatTile * kI8Ld];
+    __shared__ __attribute__((aligned(16))) int8_t B2[kFlatTile * kI8Ld];
+    __shared__ float nxs[kFlatTile];
+    __shared__ int oks[kFlatTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
+    if (tid < kFlatTile) {
+        const int64_t r = r0 + tid;
+        bool ok = r < S;
+        const int64_t row = ok ? r * stride : 0;
+        if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
+        oks[tid] = ok ? 1 : 0;
+        nxs[tid] = ok ? norms[row] : 0.f;
+    }
+    const int wr = (wave >> 2) * 64, wq = (wave & 3) * 32;
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int sr = tid >> 2, sc = (tid & 3) * 16;  // the thread's slot of 16 bytes in a stage: 128 rows x 4 slots
+    for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
+        const int q0 = qt * kFlatTile;
+        i32x16 s0a, s0b, s1a, s1b, s2a, s2b;  // plane 0 / 1 / 2, rows wr .. wr + 31 (a) and wr + 32 .. wr + 63 (b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s0a[e] = s0b[e] = s1a[e] = s1b[e] = s2a[e] = s2b[e] = 0;
+        for (int k0 = 0; k0 < D; k0 += kI8Depth) {
+            __syncthreads();  // the previous stage is consumed (first pass: the row tile's norms and flags are written)
+            // rows: the bytes from HBM as they are
+            if constexpr (VEC) {
+                i32x4 va = {0, 0, 0, 0};
+                const int64_t rr = r0 + sr;
+                if (rr < S && k0 + sc < D) va = *(const i32x4 *)(x + rr * stride * D + k0 + sc);
+                *(i32x4 *)(As + sr * kI8Ld + sc) = va;
+            } else {
+#pragma unroll 4
+                for (int i = 0; i < kFlatTile * kI8Depth / kI8Threads; ++i) {
+                    const int e = tid + i * kI8Threads;  // single bytes
+                    const int r = e / kI8Depth, c = e % kI8Depth;
+                    const int64_t rr = r0 + r;
+                    As[r * kI8Ld + c] = (rr < S && k0 + c < D) ? x[rr * stride * D + k0 + c] : (int8_t)0;
+                }
+            }
+            // queries: the planes of flat_i8_queries_kernel, 16 bytes at a time (Dp is a multiple of 32 coordinates)
+            {
+                i32x4 v0 = {0, 0, 0, 0}, v1 = {0, 0, 0, 0}, v2 = {0, 0, 0, 0};
+                const int qq = q0 + sr;
+                if (qq < B && k0 + sc < Dp) {
+                    v0 = *(const i32x4 *)(p0 + (int64_t)qq * Dp + k0 + sc);
+                    v1 = *(const i32x4 *)(p1 + (int64_t)qq * Dp + k0 + sc);
+                    v2 = *(const i32x4 *)(p2 + (int64_t)qq * Dp + k0 + sc);
+                }
+                *(i32x4 *)(B0 + sr * kI8Ld + sc) = v0;
+                *(i32x4 *)(B1 + sr * kI8Ld + sc) = v1;
+                *(i32x4 *)(B2 + sr * kI8Ld + sc) = v2;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < kI8Depth; kk += 32) {
+                if (k0 + kk >= D) break;  // (a K step of padding only)
+                const int kc = kk + 16 * lh;
+                const i32x4 a0 = *(const i32x4 *)(As + (wr + l31) * kI8Ld + kc), a1 = *(const i32x4 *)(As + (wr + 32 + l31) * kI8Ld + kc);
+                const i32x4 b0 = *(const i32x4 *)(B0 + (wq + l31) * kI8Ld + kc);
+                const i32x4 b1 = *(const i32x4 *)(B1 + (wq + l31) * kI8Ld + kc);
+                const i32x4 b2 = *(const i32x4 *)(B2 + (wq + l31) * kI8Ld + kc);
+                s0a = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, s0a, 0, 0, 0);
+                s0b = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b0, s0b, 0, 0, 0);
+                s1a = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b1, s1a, 0, 0, 0);
+                s1b = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, s1b, 0, 0, 0);
+                s2a = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b2, s2a, 0, 0, 0);
+                s2b = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b2, s2b, 0, 0, 0);
+            }
+        }
+        // epilogue: the three sums back into ONE integer, one conversion, the query's scale; then flat_filter_kernel's score, comparison and
+        // append.  A lane owns one query.
+        const int qi = q0 + wq + l31;
+        if (qi >= B) continue;
+        const float qn = qnorm[qi], t = thr[qi], down = qscale[qi], extra = qslack[qi];
+        int32_t *my_cnt = cnt + qi;
+        int32_t *my_list = cand + (int64_t)qi * cap;
+#pragma unroll
+        for (int ri = 0; ri < 2; ++ri) {
+            const i32x16 &S0 = ri == 0 ? s0a : s0b, &S1 = ri == 0 ? s1a : s1b, &S2 = ri == 0 ? s2a : s2b;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                const float a = nxs[rl] + qn;
+                const int64_t T = (int64_t)S2[reg] * 16384 + (int64_t)S1[reg] * 128 + (int64_t)S0[reg];  // = sum Q_j c_j, |T| < 2^43
+                const float dot = (float)T * down;
+                const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
+                if (scores && r0 + rl < S) scores[(int64_t)qi * S + r0 + rl] = v;
+                if (!oks[rl]) continue;
+                const float bound = t + ((c_rel * a + c_abs) + extra);
+                if (!(v > bound)) {
+                    if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
+                        const int pos = atomicAdd(my_cnt, 1);
+                        if (pos < cap) my_list[pos] = (int32_t)((r0 + rl) * stride);
+                    }
+                }
+            }
+        }
+    }
+}
+
 // ---- exact distances + top-k, a wave per query, ties by ROW ID ---------------------------------------------------------------------
 // The per-lane partial sums, the butterfly and the epilogue are rerank_topk_kernel's (codec.hip), operation for operation: the
 // distances are bit-equal to annlite_rerank_topk's.  What differs is the order among equal distances -- the row id instead of the
@@ -546,7 +742,7 @@ __global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const 
 template <class T>
 __device__ __forceinline__ void flat_exact_chunk(int metric, const float *__restrict__ qr, int D, const T *__restrict__ x, int64_t N,
                                                  const uint32_t *__restrict__ valid, int64_t row, int n_here, int km1, int lane, WaveList &L,
-                                                 uint32_t &th, uint32_t &tl) {
+                                                 uint32_t &th, uint32_t &tl, float scale = 1.f) {
     constexpr int U = 8;
     if (row >= N) row = -1;
     if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
@@ -570,7 +766,7 @@ __device__ __forceinline__ void flat_exact_chunk(int metric, const float *__rest
 #pragma unroll
                 for (int u = 0; u < U; ++u) xv[u] = rw[u] >= 0 ? x[rw[u] * D + j] : 0.f;
             } else {
-                // f16: all eight loads are issued before the first value is widened, as the f32 form has them in flight together -- left
+                // f16, int8: all eight loads are issued before the first value is widened, as the f32 form has them in flight together -- left
                 // to itself the compiler widens each value right behind its load, and every load waits for itself: eight latencies in
                 // a row.  So the loads are unconditional -- row 0 (it exists: some row of this batch is one of the table's) stands in
                 // for a missing one -- and a scheduling barrier keeps the conversions behind them.
@@ -579,7 +775,11 @@ __device__ __forceinline__ void flat_exact_chunk(int metric, const float *__rest
                 for (int u = 0; u < U; ++u) raw[u] = x[(rw[u] >= 0 ? rw[u] : 0) * D + j];
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int u = 0; u < U; ++u) xv[u] = rw[u] >= 0 ? (float)raw[u] : 0.f;
+                for (int u = 0; u < U; ++u) {
+                    // (int8: the code times the store's power-of-two scale, exact; nothing else differs)
+                    if constexpr (std::is_same<T, int8_t>::value) xv[u] = rw[u] >= 0 ? scale * (float)raw[u] : 0.f;
+                    else xv[u] = rw[u] >= 0 ? (float)raw[u] : 0.f;
+                }
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -628,7 +828,7 @@ __global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float
                                                         int64_t S, int64_t stride, const uint32_t *__restrict__ valid, int k, int do_sqrt,
                                                         int final_list, int only_overflowed, float *__restrict__ thr_out,
                                                         float *__restrict__ out_d, int64_t *__restrict__ out_i, int32_t *__restrict__ ovf,
-                                                        uint32_t *__restrict__ ovf_total) {
+                                                        uint32_t *__restrict__ ovf_total, float scale = 1.f) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
@@ -657,7 +857,7 @@ __global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float
         const int64_t ci = c0 + lane;
         int64_t row = -1;
         if (ci < n) row = lr ? (int64_t)lr[ci] : ci * stride;
-        flat_exact_chunk(metric, qr, D, x, N, valid, row, n - c0 < 64 ? (int)(n - c0) : 64, k - 1, lane, L, th, tl);
+        flat_exact_chunk(metric, qr, D, x, N, valid, row, n - c0 < 64 ? (int)(n - c0) : 64, k - 1, lane, L, th, tl, scale);
     }
     flat_exact_finish(L, b, k, lane, do_sqrt, thr_out, out_d, out_i);
 }
@@ -1191,27 +1391,87 @@ static int flat_f16_launch_filter(int metric, int64_t B, int64_t D, const _Float
     return launch_status("flat_f16_filter_kernel");
 }
 
+// ---- the int8 filter's share of a workspace: the three digit planes, the scales and the per-query slack terms, behind the FlatWs of the
+// same B ----
+struct FlatI8Ws {
+    FlatWs f;
+    int64_t Dp;  // D rounded up to the MFMA's K step
+    int8_t *p0, *p1, *p2;
+    float *qscale, *qslack;
+    size_t bytes;
+};
+static FlatI8Ws flat_i8_carve(void *ws, int64_t B, int64_t D) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    FlatI8Ws w;
+    w.f = flat_carve(ws, B);
+    w.Dp = (D + 31) / 32 * 32;
+    char *p = (char *)ws;
+    size_t o = w.f.bytes;
+    w.p0 = (int8_t *)(p + o), o += up((size_t)B * w.Dp);
+    w.p1 = (int8_t *)(p + o), o += up((size_t)B * w.Dp);
+    w.p2 = (int8_t *)(p + o), o += up((size_t)B * w.Dp);
+    w.qscale = (float *)(p + o), o += up((size_t)B * 4);
+    w.qslack = (float *)(p + o), o += up((size_t)B * 4);
+    w.bytes = o;
+    return w;
+}
+
+// The int8 filter's two constants ("int8 rows"); the third term is per query (flat_i8_queries_kernel).  The
+// contraction is exact, so D enters through the norms' lane chains alone.
+static void flat_i8_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
+    const double u = 5.9604644775390625e-08;
+    const double nl = (double)((D + 63) / 64);
+    *c_rel = (float)(1.05 * u * (3.0 * nl + 48.0));
+    *c_abs = metric == ANNLITE_METRIC_EUCLIDEAN ? 3e-30f : (float)(9.0 * u);
+}
+
+static int flat_i8_prepare(const float *q, int64_t B, int64_t D, float scale, const FlatI8Ws &w, hipStream_t st) {
+    hipLaunchKernelGGL(flat_i8_queries_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, q, (int)B, (int)D, (int)w.Dp,
+                       i8_scale_log2(scale), w.p0, w.p1, w.p2, w.f.qnorm, w.qscale, w.qslack);
+    return launch_status("flat_i8_queries_kernel");
+}
+
+static int flat_i8_launch_filter(int metric, int64_t B, int64_t D, const int8_t *x, const float *norms, int64_t S, int64_t stride,
+                                 const uint32_t *valid, const FlatI8Ws &w, const float *thr, int32_t *cand, int32_t *cnt, float *scores,
+                                 hipStream_t st) {
+    float c_rel, c_abs;
+    flat_i8_slack(metric, D, &c_rel, &c_abs);
+    const int64_t n_rt = (S + kFlatTile - 1) / kFlatTile;
+    const int n_qt = (int)((B + kFlatTile - 1) / kFlatTile);
+    int64_t ny = (4 * (int64_t)device_cu_count() + n_rt - 1) / n_rt;  // (flat_launch_filter's grid)
+    ny = ny < 1 ? 1 : ny > n_qt ? n_qt : ny;
+    const dim3 grid((unsigned)n_rt, (unsigned)ny);
+    const bool vec = D % 16 == 0 && ((uintptr_t)x % 16 == 0);
+    if (vec)
+        hipLaunchKernelGGL(flat_i8_filter_kernel<true>, grid, dim3(kI8Threads), 0, st, metric, w.p0, w.p1, w.p2, (int)B, (int)D, (int)w.Dp, x,
+                           norms, S, stride, valid, w.f.qnorm, w.qscale, w.qslack, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
+    else
+        hipLaunchKernelGGL(flat_i8_filter_kernel<false>, grid, dim3(kI8Threads), 0, st, metric, w.p0, w.p1, w.p2, (int)B, (int)D, (int)w.Dp, x,
+                           norms, S, stride, valid, w.f.qnorm, w.qscale, w.qslack, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
+    return launch_status("flat_i8_filter_kernel");
+}
+
 // ---- the stages of a search, shared by annlite_flat_search_topk and annlite_flat_search_topk_split: the small-
 // table shortcut, the first exact sample, filter stages over growing row sets, the re-rank of the lists and the route of an overflowed
 // list.  prepare(): what the filter needs from the queries, once per call; filter(S, stride): one filter launch into w.cand / w.cnt
-// against the bounds w.thr. ----
+// against the bounds w.thr; row_scale: what one code step of an int8 row stands for (1 for the float row types, which do not read it). ----
 template <class T, class Prepare, class Filter>
 static int flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const T *vectors_dev, int64_t N,
                               const uint32_t *valid_bits_dev, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, const FlatWs &w,
-                              hipStream_t st, Prepare &&prepare, Filter &&filter) {
+                              hipStream_t st, float row_scale, Prepare &&prepare, Filter &&filter) {
     const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
     const dim3 qgrid((unsigned)((B + 3) / 4));
     ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
     if (N <= kFlatSample) {  // the first sample would be the whole table: exact sums over all rows
         hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
-                           kFlatCap, N, (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 0, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
+                           kFlatCap, N, (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 0, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale);
         return launch_status("flat_exact_kernel");
     }
     int rc = prepare();
     if (rc != ANNLITE_OK) return rc;
     // stage 0: the k-th smallest exact distance among kFlatSample rows spread over the table
     hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap,
-                       kFlatSample, N / kFlatSample, valid_bits_dev, (int)k, 0, 0, 0, w.thr, nullptr, nullptr, w.ovf, w.ovf_total);
+                       kFlatSample, N / kFlatSample, valid_bits_dev, (int)k, 0, 0, 0, w.thr, nullptr, nullptr, w.ovf, w.ovf_total, row_scale);
     if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
     // stages 1 .. n: row sets growing by the same factor (<= kFlatGrowth) up to the whole table; each takes the bound of the one before
     const double ratio = (double)N / (double)kFlatSample;
@@ -1230,12 +1490,12 @@ static int flat_search_staged(int metric, const float *queries_dev, int64_t B, i
         // (a list that overflowed before the last stage still holds `cap` valid rows: the k-th of ANY k valid rows is a bound)
         hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt, kFlatCap,
                            (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr,
-                           out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
+                           out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale);
         if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
     }
     // queries whose last list overflowed: exact sums over all rows (the other waves leave at once)
     hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap, N,
-                       (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 1, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total);
+                       (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 1, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale);
     return launch_status("flat_exact_kernel");
 }
 
@@ -1456,7 +1716,7 @@ extern "C" int annlite_flat_search_topk(int metric, const float *queries_dev, in
     }
     hipStream_t st = (hipStream_t)stream;
     return flat_search_staged(
-        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w, st,
+        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w, st, 1.f,
         [&]() { return annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream); },
         [&](int64_t S, int64_t stride) {
             return flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, S, stride, valid_bits_dev, w.qnorm, w.thr, w.cand, w.cnt,
@@ -1531,7 +1791,7 @@ extern "C" int annlite_flat_search_topk_split(int metric, const float *queries_d
     }
     hipStream_t st = (hipStream_t)stream;
     return flat_search_staged(
-        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st,
+        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
         [&]() { return flat_split_prepare(queries_dev, B, D, centre_dev, w, st); },
         [&](int64_t S, int64_t stride) {
             return flat_split_launch_filter(metric, B, D, vectors_dev, centre_dev, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand,
@@ -1608,10 +1868,90 @@ extern "C" int annlite_flat_search_topk_f16(int metric, const float *queries_dev
     hipStream_t st = (hipStream_t)stream;
     const _Float16 *x = (const _Float16 *)vectors_f16_dev;
     return flat_search_staged(
-        metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st,
+        metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
         [&]() { return flat_f16_prepare(queries_dev, B, D, w, st); },
         [&](int64_t S, int64_t stride) {
             return flat_f16_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st);
+        });
+}
+
+// ---- int8 rows -----------------------------------------------------------------------------------------------------------------------
+extern "C" int annlite_flat_row_norms_i8(const void *vectors_i8_dev, float scale, int64_t capacity, int64_t D, const int64_t *ids_dev,
+                                         int64_t n, int64_t id_base, float *norms_dev, void *stream) {
+    ANNLITE_REQUIRE(capacity >= 0 && D >= 1 && n >= 0 && D <= INT32_MAX, "bad shape");
+    ANNLITE_REQUIRE_I8_SCALE(scale);
+    if (n == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(vectors_i8_dev && norms_dev, "null device pointer");
+    hipLaunchKernelGGL((flat_norms_kernel<false, int8_t>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const int8_t *)vectors_i8_dev, (int)D, ids_dev, n, id_base, capacity, (const float *)nullptr, (const int32_t *)nullptr, 0,
+                       norms_dev, scale);
+    return launch_status("flat_norms_kernel");
+}
+
+extern "C" int annlite_flat_i8_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3 && D >= 1 && D <= kSplitMaxDim && c_rel && c_abs, "bad argument (1 <= D <= %lld)",
+                    (long long)kSplitMaxDim);
+    flat_i8_slack(metric, D, c_rel, c_abs);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_search_i8_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    ANNLITE_REQUIRE(N >= 0 && D >= 1 && D <= kSplitMaxDim && B >= 0 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
+                    (long long)kSplitMaxDim);
+    *bytes = (int64_t)flat_i8_carve(nullptr, B, D).bytes;
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_filter_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev, float scale,
+                                      const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
+                                      float *query_norms_out_dev, float *query_slack_out_dev, const float *bounds_dev, int32_t *cand_dev,
+                                      int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
+                    "bad shape (D <= %lld)", (long long)kSplitMaxDim);
+    ANNLITE_REQUIRE_I8_SCALE(scale);
+    if (B == 0 || N == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && vectors_i8_dev && norms_dev && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
+    const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc = flat_i8_prepare(queries_dev, B, D, scale, w, st);
+    if (rc != ANNLITE_OK) return rc;
+    if (query_norms_out_dev)
+        ANNLITE_HIP_TRY(hipMemcpyAsync(query_norms_out_dev, w.f.qnorm, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    if (query_slack_out_dev)
+        ANNLITE_HIP_TRY(hipMemcpyAsync(query_slack_out_dev, w.qslack, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    return flat_i8_launch_filter(metric, B, D, (const int8_t *)vectors_i8_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev, w,
+                                 bounds_dev, cand_dev, count_dev, scores_dev, st);
+}
+
+extern "C" int annlite_flat_search_topk_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev, float scale,
+                                           const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
+                                           float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
+                                           void *stream) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
+                    "bad shape (1 <= k <= 64, D <= %lld)", (long long)kSplitMaxDim);
+    ANNLITE_REQUIRE_I8_SCALE(scale);
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_i8_dev && norms_dev)),
+                    "null device pointer");
+    const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
+    if (workspace_bytes < w.bytes) {
+        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
+        return ANNLITE_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int8_t *x = (const int8_t *)vectors_i8_dev;
+    return flat_search_staged(
+        metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, scale,
+        [&]() { return flat_i8_prepare(queries_dev, B, D, scale, w, st); },
+        [&](int64_t S, int64_t stride) {
+            return flat_i8_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st);
         });
 }
 

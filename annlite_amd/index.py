@@ -104,7 +104,10 @@ class AnnLite:
         precision -- half the HBM, the answer of the f32 index over the rounded rows bit for bit, its own filter ``'f16x2'`` (no
         ``flat_filter='bf16x3'``, no ``centre``: centre data with a common offset before adding it).  The float graph
         (``graph=True``) and the cells over floats (``n_cells > 1``) read f32 rows only and raise ``NotImplementedError`` for
-        ``np.float16``; the indexes over PQ codes ignore ``dtype``, as before
+        ``np.float16``; the indexes over PQ codes ignore ``dtype``, as before.  ``np.int8`` with ``int8_scale`` (a power of two, same
+        channel; default 1.0, ``2**-7`` for cosine) rides the same way: ``FlatGpuIndex`` then stores int8 codes -- a quarter of the HBM,
+        the answer of the f32 index over the rows ``int8_scale * code`` bit for bit, its own filter ``'i8x3'``; the float graph and
+        the cells over floats raise ``NotImplementedError``, the indexes over PQ codes drop both keywords
     """
 
     def __init__(
@@ -257,7 +260,7 @@ class AnnLite:
             return FlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
         if not (self._vq_codec is None and kw.get('graph')):
             kw.pop('filter_search', None)  # (the graph indexes' option: the other indexes over PQ codes answer a filter exactly)
-        for name in ('flat_filter', 'centre', 'cell_filter'):  # (the float indexes' options: nothing over PQ codes runs that filter)
+        for name in ('flat_filter', 'centre', 'cell_filter', 'int8_scale'):  # (the float indexes' options: nothing over PQ codes runs that filter)
             kw.pop(name, None)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')

@@ -1006,6 +1006,88 @@ def flat_search_topk_f16(metric: int, queries: torch.Tensor, vectors: torch.Tens
     return od, oi
 
 
+# ---------------------------------------------------------------------------------------------- exact search over int8 rows
+def exact_gather_dist_i8(metric: int, queries: torch.Tensor, vectors: torch.Tensor, cand: torch.Tensor, scale: float) -> torch.Tensor:
+    """``annlite_exact_gather_dist_i8``: ``exact_gather_dist`` over ``vectors`` int8 [N, D], the bits of the rows ``scale * c``."""
+    assert vectors.dtype == torch.int8
+    B, D = queries.shape
+    N = vectors.shape[0]
+    R = cand.shape[1]
+    out = torch.empty((B, R), dtype=torch.float32, device=queries.device)
+    check(lib().annlite_exact_gather_dist_i8(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), N,
+                                             cand.data_ptr(), R, out.data_ptr(), stream_ptr()), 'exact_gather_dist_i8')
+    return out
+
+
+def flat_row_norms_i8(vectors: torch.Tensor, scale: float, ids: Optional[torch.Tensor] = None, n: Optional[int] = None,
+                      id_base: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``annlite_flat_row_norms_i8``: ``flat_row_norms`` over ``vectors`` int8 [capacity, D] read as ``scale * c``."""
+    assert vectors.dtype == torch.int8
+    cap, D = vectors.shape
+    if out is None:
+        out = torch.zeros((cap,), dtype=torch.float32, device=vectors.device)
+    cnt = ids.numel() if ids is not None else (cap - id_base if n is None else n)
+    check(lib().annlite_flat_row_norms_i8(vectors.data_ptr(), float(scale), cap, D, _ptr(ids), cnt, id_base, out.data_ptr(), stream_ptr()),
+          'flat_row_norms_i8')
+    return out
+
+
+def flat_i8_slack(metric: int, dim: int) -> Tuple[np.float32, np.float32]:
+    """``annlite_flat_i8_slack``: the ``(c_rel, c_abs)`` the int8 filter kernel is launched with (host only, needs no GPU)."""
+    c_rel, c_abs = ctypes.c_float(0), ctypes.c_float(0)
+    check(lib().annlite_flat_i8_slack(int(metric), int(dim), ctypes.byref(c_rel), ctypes.byref(c_abs)), 'flat_i8_slack')
+    return np.float32(c_rel.value), np.float32(c_abs.value)
+
+
+def _flat_i8_workspace(N: int, D: int, B: int, k: int, dev, workspace: Optional[ScanWorkspace]) -> torch.Tensor:
+    need = ctypes.c_int64(0)
+    check(lib().annlite_flat_search_i8_workspace_bytes(N, D, B, k, ctypes.byref(need)), 'flat_search_i8_workspace_bytes')
+    return (workspace or ScanWorkspace()).get(int(need.value), dev)
+
+
+def flat_filter_i8(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor, scale: float,
+                   valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, stride: int = 1, scores: bool = False,
+                   workspace: Optional[ScanWorkspace] = None):
+    """``annlite_flat_filter_i8``: ``flat_filter`` over ``vectors`` int8 [N, D] read as ``scale * c``; ``norms`` are
+    ``flat_row_norms_i8`` with the same scale.  ``(cand i32 [B, cap], count i32 [B], query_norms f32 [B], query_slack f32 [B])`` --
+    the last two as the filter used them: ``|q|^2`` and the per-query term of the slack -- and, with ``scores=True``, the filter's
+    score of every (query, stage row) pair, f32 [B, ceil(N / stride)]."""
+    assert vectors.dtype == torch.int8
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    cap = flat_list_capacity()
+    dev = queries.device
+    ws = _flat_i8_workspace(N, D, B, 1, dev, workspace)
+    cand = torch.empty((B, cap), dtype=torch.int32, device=dev)
+    count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    qn = torch.empty((B,), dtype=torch.float32, device=dev)
+    qs = torch.empty((B,), dtype=torch.float32, device=dev)
+    sc = torch.full((B, (N + stride - 1) // stride), float('nan'), dtype=torch.float32, device=dev) if scores else None
+    check(lib().annlite_flat_filter_i8(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(), N, stride,
+                                       _ptr(valid_bits), qn.data_ptr(), qs.data_ptr(), bounds.data_ptr(), cand.data_ptr(),
+                                       count.data_ptr(), _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_filter_i8')
+    return (cand, count, qn, qs, sc) if scores else (cand, count, qn, qs)
+
+
+def flat_search_topk_i8(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, k: int, scale: float,
+                        valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, sqrt: bool = False,
+                        workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_flat_search_topk_i8``: ``flat_search_topk`` over ``vectors`` int8 [N, D] read as ``scale * c`` (``norms``:
+    ``flat_row_norms_i8``): the answer of ``flat_search_topk`` over those f32 rows, bit for bit.  ``flat_overflow_count`` /
+    ``flat_list_counts`` read this workspace too."""
+    assert vectors.dtype == torch.int8
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    ws = _flat_i8_workspace(N, D, B, k, dev, workspace)
+    od = torch.empty((B, k), dtype=torch.float32, device=dev)
+    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
+    check(lib().annlite_flat_search_topk_i8(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(), N,
+                                            _ptr(valid_bits), int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_search_topk_i8')
+    return od, oi
+
+
 # ---------------------------------------------------------------------------------------------- cells over float vectors
 def ivf_flat_stages(max_probed_rows: int) -> List[int]:
     """``annlite_ivf_flat_stages``: the strides ``ivf_flat_search_topk`` uses for queries that probe at most ``max_probed_rows``

@@ -496,6 +496,12 @@ ANNLITE_API int annlite_exact_gather_dist(int metric, const float *queries_dev, 
 ANNLITE_API int annlite_exact_gather_dist_f16(int metric, const float *queries_dev, int64_t B, int64_t D,
                                   const void *vectors_f16_dev, int64_t N, const int64_t *cand_dev, int64_t R,
                                   float *out_dev, void *stream);
+/* annlite_exact_gather_dist over vectors_i8_dev int8 [N][D] (FlatGpuIndex's int8 row store): a code c stands for scale * c, scale a
+ * power of two in [2^-24, 2^24] -- the widened value is exact and the arithmetic after it is the f32 form's, so the result is
+ * annlite_exact_gather_dist's over the rows scale * c, bit for bit.  No reference counterpart. */
+ANNLITE_API int annlite_exact_gather_dist_i8(int metric, const float *queries_dev, int64_t B, int64_t D,
+                                 const void *vectors_i8_dev, float scale, int64_t N, const int64_t *cand_dev, int64_t R,
+                                 float *out_dev, void *stream);
 /* The same distances FUSED with the top-k (round 6): out[b][0..k) = the k smallest exact distances among cand[b][0..R) in
  * (distance, position in the list) order -- what annlite_exact_gather_dist + annlite_topk_rows + a gather of the ids give, bit for
  * bit -- as (distance, cand id); candidates < 0, >= N or cleared in valid_bits_dev (may be NULL) are skipped, missing places hold
@@ -597,6 +603,37 @@ ANNLITE_API int annlite_flat_filter_f16(int metric, const float *queries_dev, in
 ANNLITE_API int annlite_flat_search_topk_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
                                  const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
                                  float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
+/* The same search over rows STORED as int8 codes ("int8 rows"): vectors_i8_dev int8 [N][D], a byte c in
+ * [-127, 127] standing for the value scale * c, `scale` a power of two in [2^-24, 2^24] (anything else: ANNLITE_ERR_INVALID); queries
+ * stay f32.  replaces: the reference's `dtype` argument of its index plug-ins, as the f16 form does.  The answer is
+ * annlite_flat_search_topk's over the f32 rows scale * c, bit for bit.  An int8 row is an exact MFMA operand and the accumulator an
+ * integer: the filter contracts it with the query rounded to a 21-bit integer (scaled by a power of two per query) and carried as three
+ * base-128 digits, on three i8 MFMAs -- the contraction itself has no rounding error.  1 <= D <= 32768. */
+/* annlite_flat_row_norms over int8 rows (flat_norms_kernel's chain on the widened values scale * c).  No reference counterpart. */
+ANNLITE_API int annlite_flat_row_norms_i8(const void *vectors_i8_dev, float scale, int64_t capacity, int64_t D, const int64_t *ids_dev,
+                              int64_t n, int64_t id_base, float *norms_dev, void *stream);
+/* The int8 filter's (c_rel, c_abs) (host only; they do not depend on the scale); its slack is c_rel * fl(|x|^2 + |q|^2) + c_abs + a
+ * per-query term the library computes, 1.001 * 127 * D * 2^-e with 2^e the query's power of two (what rounding the scaled query to
+ * integers can cost against codes of magnitude <= 127; +inf for a query that has no integer form).  No reference counterpart. */
+ANNLITE_API int annlite_flat_i8_slack(int metric, int64_t D, float *c_rel, float *c_abs);
+/* No reference counterpart. */
+ANNLITE_API int annlite_flat_search_i8_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes);
+/* annlite_flat_filter over int8 rows.  norms_dev: annlite_flat_row_norms_i8 with the same scale.  The queries are scaled, rounded and
+ * split into the workspace (annlite_flat_search_i8_workspace_bytes of the same B, D) by this call; query_norms_out_dev /
+ * query_slack_out_dev (may be NULL) f32 [B] receive |q|^2 and the per-query slack term as the filter used them; scores_dev (may be NULL;
+ * tests and measurements) f32 [B][ceil(N / stride)] receives the filter's score v of every (query, stage row) pair, valid or not.
+ * No reference counterpart. */
+ANNLITE_API int annlite_flat_filter_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev, float scale,
+                           const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
+                           float *query_norms_out_dev, float *query_slack_out_dev, const float *bounds_dev, int32_t *cand_dev,
+                           int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* annlite_flat_search_topk over int8 rows: the same stages, lists, capacity and overflow route (annlite_flat_overflow_count and
+ * annlite_flat_list_counts read this workspace too).  replaces: HnswIndex.search / FlatIndex.search of an index built with
+ * dtype=np.int8. */
+ANNLITE_API int annlite_flat_search_topk_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev,
+                                float scale, const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
+                                float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Cells over float vectors: the exact search above restricted to the rows of each query's P probed cells.

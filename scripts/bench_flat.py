@@ -8,6 +8,9 @@
     python scripts/bench_flat.py --filter both --offset 1000   # ... on data with a large common offset
     python scripts/bench_flat.py --rows both           # an f32-row index (default filter) and an f16-row index over the same data,
                                                        # round by round: one JSON line each (--rows 10000000 --rows both: at 10M)
+    python scripts/bench_flat.py --rows all --data-scale 40    # ... and an int8-row index (dtype=np.int8) as the third: normal data
+                                                       # scaled to the int8 range (3 sigma = 120 code steps)
+    python scripts/bench_flat.py --rows f16i8 --data-scale 40  # the f16-row and the int8-row index alone (where the f32 twin does not fit)
 
 Baseline: |x|^2 - 2 q x^T by torch.addmm over row chunks (no B x N matrix exists), torch.topk per chunk, one merge.
 Filter time: the full-table filter launch (annlite_flat_filter with the bounds the search would hand it; for bf16x3
@@ -25,12 +28,14 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 ROOF_TFLOPS = 157.3
-ROW_DTYPES = {'f32': ['f32'], 'f16': ['f16'], 'both': ['f32', 'f16']}
+ROW_DTYPES = {'f32': ['f32'], 'f16': ['f16'], 'i8': ['i8'], 'both': ['f32', 'f16'], 'all': ['f32', 'f16', 'i8'], 'f16i8': ['f16', 'i8']}
+ROW_FILTER = {'f32': 'f32', 'f16': 'f16x2', 'i8': 'i8x3'}
 
 
 def row_dtypes(args):
-    """``--rows both`` / ``f16`` / ``f32``: an f32-row FlatGpuIndex on its default filter -- the default path, untouched -- and (or) an
-    f16-row one (``dtype=np.float16``) over the same rows, alternating round by round in one process.  One JSON line per index."""
+    """``--rows both`` / ``all`` / ``f16i8`` / ``f32`` / ``f16`` / ``i8``: an f32-row FlatGpuIndex on its default filter -- the default
+    path, untouched --, an f16-row one (``dtype=np.float16``) and an int8-row one (``dtype=np.int8``, default scale) over the same rows,
+    alternating round by round in one process.  One JSON line per index."""
     import torch
     from annlite_amd import ops
     from annlite_amd.core.index.flat_gpu import FlatGpuIndex
@@ -42,18 +47,18 @@ def row_dtypes(args):
     metric = Metric.from_string(args.metric)
     l2 = metric == Metric.EUCLIDEAN
     kinds = ROW_DTYPES[args.row_dtype]
-    np_dtype = {'f32': np.float32, 'f16': np.float16}
+    np_dtype = {'f32': np.float32, 'f16': np.float16, 'i8': np.int8}
     index = {m: FlatGpuIndex(D, dtype=np_dtype[m], metric=metric, initial_size=N) for m in kinds}
     gen = torch.Generator(device=dev).manual_seed(0)
     step = 1 << 20
     truth_rows = []  # the UNROUNDED rows (as pre-processed), for the float64 truth; the f32 index holds them already
     for r0 in range(0, N, step):
-        xb = torch.randn((min(step, N - r0), D), generator=gen, device=dev) + args.offset
+        xb = torch.randn((min(step, N - r0), D), generator=gen, device=dev) * args.data_scale + args.offset
         for idx in index.values():
             idx.add_with_ids(xb, torch.arange(r0, r0 + xb.shape[0], device=dev))
         if 'f32' not in index:
             truth_rows.append(next(iter(index.values()))._pre(xb))
-    q = torch.randn((B, D), generator=gen, device=dev) + args.offset
+    q = torch.randn((B, D), generator=gen, device=dev) * args.data_scale + args.offset
     x_true = index['f32']._vectors[:N] if 'f32' in index else torch.cat(truth_rows)
 
     def timed(fn):
@@ -72,7 +77,7 @@ def row_dtypes(args):
         for m in kinds:
             t, answers[m] = timed(lambda: index[m].search_batch(q, limit=k))
             ms[m].append(t)
-            assert index[m].last_flat_filter == ('f16x2' if m == 'f16' else 'f32')
+            assert index[m].last_flat_filter == ROW_FILTER[m]
             overflowed[m] = index[m].last_overflowed
             last_counts[m] = ops.flat_list_counts(index[m]._ws, B).cpu().numpy()  # what the search's own last stage listed
 
@@ -85,14 +90,22 @@ def row_dtypes(args):
         idx = index[m]
         qq = idx._pre(q)
         n_sub = (N + stride - 1) // stride
-        sub = FlatGpuIndex(D, dtype=np_dtype[m], metric=Metric.INNER_PRODUCT if metric == Metric.COSINE else metric, initial_size=n_sub)
-        sub.add_with_ids(idx._vectors[:N:stride].float().contiguous(), torch.arange(n_sub, device=dev))
+        scale_kw = dict(int8_scale=idx.int8_scale_) if m == 'i8' else {}
+        sub = FlatGpuIndex(D, dtype=np_dtype[m], metric=Metric.INNER_PRODUCT if metric == Metric.COSINE else metric, initial_size=n_sub,
+                           **scale_kw)
+        sub_rows = idx._vectors[:N:stride].float()
+        if m == 'i8':
+            sub_rows = sub_rows * idx.int8_scale_  # (the values the codes stand for: quantised again to the same codes)
+        sub.add_with_ids(sub_rows.contiguous(), torch.arange(n_sub, device=dev))
         sd = sub.search_batch(qq, limit=k)[0][:, k - 1]
         bound = ((sd * sd) if l2 else sd).contiguous()
         del sub
         qn = ops.flat_row_norms(qq)
 
         def filter_once():
+            if m == 'i8':
+                return ops.flat_filter_i8(int(metric), qq, idx._vectors, idx._norms, bound, idx.int8_scale_, valid_bits=idx._valid, n_rows=N,
+                                          workspace=idx._ws)
             if m == 'f16':
                 return ops.flat_filter_f16(int(metric), qq, idx._vectors, idx._norms, bound, valid_bits=idx._valid, n_rows=N, workspace=idx._ws)
             return ops.flat_filter(int(metric), qq, idx._vectors, idx._norms, bound, valid_bits=idx._valid, n_rows=N, query_norms=qn)
@@ -131,6 +144,7 @@ def row_dtypes(args):
         held = sum(t.numel() * t.element_size() for t in (idx._vectors, idx._norms, idx._valid_bool))
         print(json.dumps({
             'bench': 'flat_rows', 'row_dtype': m, 'row_dtypes_in_this_run': kinds, 'flat_filter': idx.flat_filter, 'offset': args.offset,
+            'data_scale': args.data_scale, 'int8_scale': idx.int8_scale_,
             'rows': N, 'dim': D, 'batch': B, 'k': k, 'metric': args.metric, 'rounds': args.rounds, 'steps': args.steps,
             'ms_per_batch': round(med, 4), 'qps': round(B / med * 1e3, 1), 'ms_rounds': [round(v, 4) for v in ms[m]],
             'filter_ms': round(f, 4), 'filter_tflops': round(flop / f / 1e9, 2),
@@ -145,8 +159,9 @@ def row_dtypes(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', action='append', default=[],
-                    help="a number: rows of the table (default 1000000); f32 | f16 | both: how the rows are stored -- FlatGpuIndex(dtype=...), "
-                         "'both': an f32-row and an f16-row index alternating (may be given twice: --rows 10000000 --rows both)")
+                    help="a number: rows of the table (default 1000000); f32 | f16 | i8 | both | all | f16i8: how the rows are stored -- "
+                         "FlatGpuIndex(dtype=...), 'both': an f32-row and an f16-row index alternating, 'all': those and an int8-row one, "
+                         "'f16i8': f16 and int8 alone (may be given twice: --rows 10000000 --rows all)")
     ap.add_argument('--dim', type=int, default=128)
     ap.add_argument('--batch', type=int, default=1024)
     ap.add_argument('--k', type=int, default=10)
@@ -157,6 +172,9 @@ def main():
     ap.add_argument('--chunk', type=int, default=65536, help='rows per chunk of the torch baseline')
     ap.add_argument('--filter', default='f32', choices=['f32', 'bf16x3', 'both'], help="FlatGpuIndex(flat_filter=...); 'both': alternating")
     ap.add_argument('--offset', type=float, default=0.0, help='added to every coordinate of rows and queries')
+    ap.add_argument('--data-scale', type=float, default=1.0,
+                    help='with --rows f32 | f16 | i8 | both | all | f16i8 only (an error otherwise): the standard deviation of every coordinate '
+                         'of rows and queries (40: normal data in the int8 range)')
     args = ap.parse_args()
     given, args.rows, args.row_dtype = args.rows, 1_000_000, None
     for v in given:
@@ -165,8 +183,9 @@ def main():
         else:
             args.rows = int(v)
     if args.row_dtype is not None:
-        assert args.filter == 'f32', '--rows f32 | f16 | both runs each index on its own default filter'
+        assert args.filter == 'f32', '--rows f32 | f16 | i8 | both | all | f16i8 runs each index on its own default filter'
         return row_dtypes(args)
+    assert args.data_scale == 1.0, '--data-scale belongs to the --rows f32 | f16 | i8 | both | all | f16i8 runs'
 
     import torch
     from annlite_amd import ops
