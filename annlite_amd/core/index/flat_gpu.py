@@ -36,8 +36,9 @@ widened values, and the filter (``'i8x3'``: the query rounded to a 21-bit intege
 into integer accumulators) contracts without any rounding at all ("int8 rows").  No centre, as for f16.
 """
 import math
+from functools import partial
 from pathlib import Path
-from typing import Optional, Tuple, Union
+from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -115,6 +116,39 @@ def quantise_i8(x: torch.Tensor, scale: float) -> torch.Tensor:
     return torch.round(t).clamp_(-127.0, 127.0).to(torch.int8)
 
 
+def _rows_f32(x: torch.Tensor) -> torch.Tensor:
+    return x
+
+
+def _rows_f16(x: torch.Tensor) -> torch.Tensor:
+    return x.to(torch.float16)
+
+
+class _RowKind(NamedTuple):
+    """What serves the rows of one store -- f32, f16 or int8 --, with the scale of an int8 store bound in: resolved once per index."""
+    dtype: torch.dtype
+    encode: Callable       # f32 rows -> the stored values (f16: rounded once, to nearest even; int8: quantise_i8)
+    norms: Callable        # ops.flat_row_norms(vectors, ids=, n=, out=) of the store
+    gather_dist: Callable  # ops.exact_gather_dist(metric, queries, vectors, cand) of the store
+    topk: Callable         # ops.flat_search_topk(metric, queries, vectors, norms, k, ...) of the store and its filter
+    tag: str               # that filter's name in ``last_flat_filter``
+    stage: Callable        # one filter stage, (metric, queries, vectors, norms, bounds, ...) -> (cand, count, ...): the k > 64 search
+    stage_tag: str
+
+
+def _resolve_row_kind(kind: str, i8_scale: Optional[float], workspace) -> _RowKind:
+    if kind == 'i8':
+        s = i8_scale
+        return _RowKind(torch.int8, partial(quantise_i8, scale=s), partial(ops.flat_row_norms_i8, scale=s),
+                       partial(ops.exact_gather_dist_i8, scale=s), partial(ops.flat_search_topk_i8, scale=s), 'i8x3',
+                       partial(ops.flat_filter_i8, scale=s, workspace=workspace), 'i8x3')
+    if kind == 'f16':
+        return _RowKind(torch.float16, _rows_f16, ops.flat_row_norms_f16, ops.exact_gather_dist_f16,
+                       ops.flat_search_topk_f16, 'f16x2', partial(ops.flat_filter_f16, workspace=workspace), 'f16x2')
+    # (f32 rows have a second filter, 'bf16x3': ``flat_filter`` is read at every search, by search_batch)
+    return _RowKind(torch.float32, _rows_f32, ops.flat_row_norms, ops.exact_gather_dist, ops.flat_search_topk, 'f32', ops.flat_filter, 'f32')
+
+
 class FlatGpuIndex(RowStoreIndex):
     """
     :param dtype: ``np.float32`` (default), ``np.float16`` or ``np.int8``: how the rows are stored (module docstring).  ``np.float16``
@@ -182,8 +216,9 @@ class FlatGpuIndex(RowStoreIndex):
         self.last_flat_filter = None  # 'f32' / 'bf16x3' / 'f16x2' / 'i8x3': the filter of the last search_batch; None: it ran none
         self._centre_dev = None
         self._centred = flat_filter == 'bf16x3' and Metric(metric) == Metric.EUCLIDEAN and centre is not None
-        super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
         self._ws = ops.ScanWorkspace()
+        self._kind = _resolve_row_kind(kind, self._i8_scale, self._ws)
+        super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
         self._overflowed = 0  # (of the last search_batch; None: ask the library's workspace)
         if index_file:
             self.load(index_file)
@@ -218,21 +253,14 @@ class FlatGpuIndex(RowStoreIndex):
     # ------------------------------------------------------------------ storage (row_store.py)
     def _columns(self):
         """``_cnorms``: the norms of the centred rows, kept only where the split filter has a centre (it reads ``_norms`` otherwise)"""
-        vt = torch.float16 if self._f16 else torch.int8 if self._i8 else torch.float32
-        return {'_vectors': ((self.dim,), vt), '_norms': ((), torch.float32),
+        return {'_vectors': ((self.dim,), self._kind.dtype), '_norms': ((), torch.float32),
                 '_cnorms': ((), torch.float32) if self._centred else None}
 
     def _write_rows(self, x, ids):
-        if self._i8:  # (rounded once, to nearest even, saturating at +-127; NaN: 0)
-            self._vectors[ids] = quantise_i8(x, self._i8_scale)
-            ops.flat_row_norms_i8(self._vectors, self._i8_scale, ids=ids, out=self._norms)
-            return
-        if self._f16:  # (rounded once, to nearest even; beyond the f16 range: an infinity)
-            self._vectors[ids] = x.to(torch.float16)
-            ops.flat_row_norms_f16(self._vectors, ids=ids, out=self._norms)
-            return
-        self._vectors[ids] = x  # flat_index.py:41-50 `_data[ids] = x`
-        ops.flat_row_norms(self._vectors, ids=ids, out=self._norms)
+        # flat_index.py:41-50 `_data[ids] = x`; f16: rounded once, to nearest even, beyond the f16 range an infinity; int8: rounded once, to
+        # nearest even, saturating at +-127, NaN: 0
+        self._vectors[ids] = self._kind.encode(x)
+        self._kind.norms(self._vectors, ids=ids, out=self._norms)
         if self._centred:
             self._fix_centre(x)
             ops.flat_centred_norms(self._vectors, self._centre_dev, ids=ids, out=self._cnorms)
@@ -261,16 +289,10 @@ class FlatGpuIndex(RowStoreIndex):
                                      "file's scale)")
                 if not self._i8:
                     stored = stored.to(torch.float32) * file_scale  # (exact)
-            elif self._i8:
-                stored = quantise_i8(stored, self._i8_scale)
+            else:
+                stored = self._kind.encode(stored)
             self._vectors[:N] = stored.to(self._vectors.dtype)
-            if self._i8:
-                ops.flat_row_norms_i8(self._vectors, self._i8_scale, n=N, out=self._norms)
-                return
-            if self._f16:
-                ops.flat_row_norms_f16(self._vectors, n=N, out=self._norms)
-                return
-            ops.flat_row_norms(self._vectors, n=N, out=self._norms)
+            self._kind.norms(self._vectors, n=N, out=self._norms)
             if self._centred:  # (a file without the key -- an older one, an f32 index's: the mean of the rows it holds)
                 self._fix_centre(self._vectors[:N], stored=state.get('centre'))
                 ops.flat_centred_norms(self._vectors, self._centre_dev, n=N, out=self._cnorms)
@@ -300,35 +322,21 @@ class FlatGpuIndex(RowStoreIndex):
             d, i = empty_answer(B, k, dev)
         else:
             valid = self._valid if indices is None else self._filter_bits(indices)
-            if k <= 64 and self._i8:
-                d, i = ops.flat_search_topk_i8(int(self.metric), q, self._vectors, self._norms, k, self._i8_scale, valid_bits=valid,
-                                               n_rows=N, sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
-                self._overflowed = None
-                self.last_flat_filter = 'i8x3' if N >= self.FILTER_MIN_ROWS else None
-            elif k <= 64 and self._f16:
-                d, i = ops.flat_search_topk_f16(int(self.metric), q, self._vectors, self._norms, k, valid_bits=valid, n_rows=N,
-                                                sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
-                self._overflowed = None
-                self.last_flat_filter = 'f16x2' if N >= self.FILTER_MIN_ROWS else None
-            elif k <= 64 and self.flat_filter == 'bf16x3':
-                d, i = ops.flat_search_topk_split(int(self.metric), q, self._vectors, self._cnorms if self._centred else self._norms, k,
-                                                  centre=self._centre_dev if self._centred else None, valid_bits=valid, n_rows=N,
-                                                  sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
-                self._overflowed = None
-                self.last_flat_filter = 'bf16x3' if N >= self.FILTER_MIN_ROWS else None
-            elif k <= 64:
-                d, i = ops.flat_search_topk(int(self.metric), q, self._vectors, self._norms, k, valid_bits=valid, n_rows=N,
-                                            sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)  # hnsw/index.py:164-165
+            if k <= 64:  # hnsw/index.py:164-165
+                topk, tag, norms = self._kind.topk, self._kind.tag, self._norms
+                if self.flat_filter == 'bf16x3' and tag == 'f32':  # (the split filter is over f32 rows; k > 64 keeps the f32 filter)
+                    centre = self._centre_dev if self._centred else None
+                    topk, tag, norms = partial(ops.flat_search_topk_split, centre=centre), 'bf16x3', self._cnorms if self._centred else norms
+                d, i = topk(int(self.metric), q, self._vectors, norms, k, valid_bits=valid, n_rows=N, sqrt=self.metric == Metric.EUCLIDEAN,
+                            workspace=self._ws)
                 self._overflowed = None  # (read from the workspace when asked for: it costs a synchronisation)
-                self.last_flat_filter = 'f32' if N >= self.FILTER_MIN_ROWS else None
+                self.last_flat_filter = tag if N >= self.FILTER_MIN_ROWS else None
             else:
                 d, i = self._search_large_k(q, k, valid, N)
         return like_input(is_np, d, i)
 
     def _gather_dist(self, q, cand):
-        if self._i8:
-            return ops.exact_gather_dist_i8(int(self.metric), q, self._vectors, cand, self._i8_scale)
-        return (ops.exact_gather_dist_f16 if self._f16 else ops.exact_gather_dist)(int(self.metric), q, self._vectors, cand)
+        return self._kind.gather_dist(int(self.metric), q, self._vectors, cand)
 
     def _keyed_topk(self, q, cand, ok, kk):
         """The ``kk`` nearest of each query's candidates ``cand`` i64 [b, R] (``ok``: which entries count) by exact distance
@@ -383,17 +391,8 @@ class FlatGpuIndex(RowStoreIndex):
                 bounds.append(torch.topk(ds, kk, dim=1, largest=False).values[:, kk - 1] if sample.numel() >= kk
                               else torch.full((nb,), float('inf'), device=dev))
             bound = torch.cat(bounds).contiguous()  # (+inf -- fewer than k valid sampled rows, NaN distances -- passes everything)
-            if self._i8:
-                cand32, count = ops.flat_filter_i8(int(self.metric), q, self._vectors, self._norms, bound, self._i8_scale, valid_bits=valid,
-                                                   n_rows=N, workspace=self._ws)[:2]
-                self.last_flat_filter = 'i8x3'
-            elif self._f16:
-                cand32, count = ops.flat_filter_f16(int(self.metric), q, self._vectors, self._norms, bound, valid_bits=valid, n_rows=N,
-                                                    workspace=self._ws)[:2]
-                self.last_flat_filter = 'f16x2'
-            else:
-                cand32, count = ops.flat_filter(int(self.metric), q, self._vectors, self._norms, bound, valid_bits=valid, n_rows=N)
-                self.last_flat_filter = 'f32'  # ('bf16x3' too: offset data stays slow for limit > 64)
+            cand32, count = self._kind.stage(int(self.metric), q, self._vectors, self._norms, bound, valid_bits=valid, n_rows=N)[:2]
+            self.last_flat_filter = self._kind.stage_tag
             over = count > cap
             ok = torch.arange(cap, device=dev)[None, :] < count[:, None]
             cand = torch.where(ok, cand32.to(torch.int64), torch.full((1, 1), -1, dtype=torch.int64, device=dev))

@@ -9,6 +9,15 @@
 // Second half of the file: the same search over the rows of each query's probed CELLS (the reference's n_cells > 1 structure over that
 // index, container.py:88-144) -- the filter over (cell, queries that probe it) tiles, the cells a permutation
 // of the row offsets.
+//
+// Six MFMA filter kernels (f32, split-bf16, f16 and int8 rows over the table; f32 and split-bf16 over cell tiles) differ in their
+// contraction and share the rest, each piece written once:
+//   flat_tile_rows / ivf_flat_tile_range + ivf_flat_tile_rows   the row tile's prologue: bounds, bitmap, norms
+//   flat_stage_planes                                            16-byte slots of 2-byte planes from HBM into an LDS stage
+//   flat_f32_stage + flat_f32_contract                           the f32 stage and its 4-MFMA K loop
+//   FLAT_BF16X3_CONTRACT                                         the split filter's 12-MFMA K loop (a macro: see there)
+//   flat_tile_epilogue -> flat_admit                             C-tile row map, score, `scores`, the negated comparison, the append
+// and on the host: WsBump (workspace carving), flat_filter_grid, FLAT_LAUNCH_VEC, flat_check_workspace, flat_check_shape.
 #include <math.h>
 
 #include <type_traits>
@@ -68,6 +77,138 @@ __global__ __launch_bounds__(256) void flat_norms_kernel(const T *__restrict__ x
 // A row passes when   !(v > thr + (c_rel * a + c_abs))   with a = fl(|x|^2 + |q|^2), v = fl(a - 2 dot) (EUCLIDEAN) or fl(1 - dot):
 // every exact distance <= thr passes (proof: DESIGN.md section 3.6), and a NaN or infinite thr, a, dot or slack passes EVERYTHING
 // (the comparison is written negated for that: section 4's convention).
+//
+// The pieces below are every filter kernel's; only the contraction between the prologue and the epilogue is a kernel's own.
+
+// Where the row or query of a tile slot lies: `off` elements behind its operand's base pointer; !ok: the slot is staged as zeros.
+struct FlatSlot {
+    bool ok;
+    int64_t off;
+};
+
+// A wave's 2 x 2 C tiles of 32 x 32: c<row half><query half>.
+struct FlatAcc {
+    f32x16 c00, c01, c10, c11;
+    __device__ __forceinline__ void zero() {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) c00[e] = c01[e] = c10[e] = c11[e] = 0.f;
+    }
+    __device__ __forceinline__ const f32x16 &tile(int ri, int qj) const { return ri == 0 ? (qj == 0 ? c00 : c01) : (qj == 0 ? c10 : c11); }
+};
+
+// The row tile of a table kernel, by its first kFlatTile threads: oks[i] = stage row r0 + i exists and is valid in the bitmap, nxs[i] =
+// its norm (0 without a row).
+__device__ __forceinline__ void flat_tile_rows(int tid, int64_t r0, int64_t S, int64_t stride, const uint32_t *__restrict__ valid,
+                                               const float *__restrict__ norms, int *oks, float *nxs) {
+    if (tid >= kFlatTile) return;
+    const int64_t r = r0 + tid;
+    bool ok = r < S;
+    const int64_t row = ok ? r * stride : 0;
+    if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
+    oks[tid] = ok ? 1 : 0;
+    nxs[tid] = ok ? norms[row] : 0.f;
+}
+
+// One more entry for a query's list.
+__device__ __forceinline__ void flat_admit(int32_t *cnt, int32_t *list, int cap, int32_t value) {
+    // (a list that has already overflowed takes the slower route whatever else arrives: stop counting)
+    if (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
+        const int pos = atomicAdd(cnt, 1);
+        if (pos < cap) list[pos] = value;
+    }
+}
+
+// What a lane holds of the ONE query it owns in a C tile: |q|^2, the bound, the per-query term of the slack (read by the kernels that
+// have one), the query's counter and list, and its row of the `scores` output (NULL: none).
+struct FlatQuery {
+    float qn, thr, extra;
+    int32_t *cnt, *list;
+    float *scores;
+};
+__device__ __forceinline__ FlatQuery flat_query(int qi, float qn, const float *__restrict__ thr, float extra, int32_t *cand, int32_t *cnt,
+                                                int cap, float *scores, int64_t scores_ld) {
+    return {qn, thr[qi], extra, cnt + qi, cand + (int64_t)qi * cap, scores ? scores + (int64_t)qi * scores_ld : nullptr};
+}
+
+// A tile row as the epilogue sees it: is it offered to the lists and as which value; does its score go to the `scores` row and to
+// which column.
+struct FlatRow {
+    bool listed;
+    int32_t value;
+    bool scored;
+    int64_t col;
+};
+
+// THE epilogue of a 32 x 32 C tile whose first row is tile row rt: score, `scores`, comparison, append.  dot_of(reg): the f32 dot
+// product of the lane's accumulator element reg; row_of(rl): the FlatRow of tile row rl.  EXTRA: the slack has the per-query term.
+// SCORE_UNLISTED: the kernel's `scores` output also takes rows that are not listed (the table kernels that have one); without it such a
+// row is left before any arithmetic.
+template <bool EXTRA, bool SCORE_UNLISTED, class Dot, class Row>
+__device__ __forceinline__ void flat_tile_epilogue(int metric, float c_rel, float c_abs, int cap, const FlatQuery &Q, const float *nxs, int rt,
+                                                   int lh, Dot &&dot_of, Row &&row_of) {
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int rl = rt + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+        const FlatRow row = row_of(rl);
+        if (!SCORE_UNLISTED && !row.listed) continue;
+        const float a = nxs[rl] + Q.qn;
+        const float dot = dot_of(reg);
+        const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
+        if (Q.scores && row.scored) Q.scores[row.col] = v;
+        if (!row.listed) continue;
+        float bound;
+        if constexpr (EXTRA) bound = Q.thr + ((c_rel * a + c_abs) + Q.extra);
+        else bound = Q.thr + (c_rel * a + c_abs);
+        if (!(v > bound)) flat_admit(Q.cnt, Q.list, cap, row.value);
+    }
+}
+
+// One f32 LDS stage: coordinates k0 .. k0 + kFlatDepth of the tile's kFlatTile rows (x + row_at(r).off) into As and of its kFlatTile
+// queries (q + query_at(r).off) into Bs, zeros past D and for a slot that is not ok.  256 threads.
+template <bool VEC, class RowAt, class QueryAt>
+__device__ __forceinline__ void flat_f32_stage(int tid, int k0, int D, const float *__restrict__ x, const float *__restrict__ q, float *As,
+                                               float *Bs, RowAt &&row_at, QueryAt &&query_at) {
+    if constexpr (VEC) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + i * 256;  // 1024 slots of 4 floats
+            const int r = e >> 3, c = (e & 7) * 4;
+            f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
+            const FlatSlot sa = row_at(r), sb = query_at(r);
+            if (sa.ok && k0 + c < D) va = *(const f32x4 *)(x + sa.off + k0 + c);
+            if (sb.ok && k0 + c < D) vb = *(const f32x4 *)(q + sb.off + k0 + c);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                As[r * kFlatLd + c + t] = va[t];
+                Bs[r * kFlatLd + c + t] = vb[t];
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int i = 0; i < 16; ++i) {
+            const int e = tid + i * 256;  // 4096 floats
+            const int r = e >> 5, c = e & 31;
+            const FlatSlot sa = row_at(r), sb = query_at(r);
+            As[r * kFlatLd + c] = (sa.ok && k0 + c < D) ? x[sa.off + k0 + c] : 0.f;
+            Bs[r * kFlatLd + c] = (sb.ok && k0 + c < D) ? q[sb.off + k0 + c] : 0.f;
+        }
+    }
+}
+
+// ... and its K loop: the wave's 64 rows (from wr) x 64 queries (from wq) of the stage, four v_mfma_f32_32x32x2_f32 per K step of 2.
+__device__ __forceinline__ void flat_f32_contract(const float *As, const float *Bs, int wr, int wq, int l31, int lh, FlatAcc &acc) {
+#pragma unroll
+    for (int kk = 0; kk < kFlatDepth; kk += 2) {
+        const int kc = kk + lh;
+        const float a0 = As[(wr + l31) * kFlatLd + kc], a1 = As[(wr + 32 + l31) * kFlatLd + kc];
+        const float b0 = Bs[(wq + l31) * kFlatLd + kc], b1 = Bs[(wq + 32 + l31) * kFlatLd + kc];
+        acc.c00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc.c00, 0, 0, 0);
+        acc.c01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc.c01, 0, 0, 0);
+        acc.c10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc.c10, 0, 0, 0);
+        acc.c11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc.c11, 0, 0, 0);
+    }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
                                                          const float *__restrict__ norms, int64_t S, int64_t stride,
@@ -80,90 +221,30 @@ __global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const floa
     __shared__ int oks[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
-    if (tid < kFlatTile) {
-        const int64_t r = r0 + tid;
-        bool ok = r < S;
-        const int64_t row = ok ? r * stride : 0;
-        if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
-        oks[tid] = ok ? 1 : 0;
-        nxs[tid] = ok ? norms[row] : 0.f;
-    }
+    flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
     const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
     const int l31 = lane & 31, lh = lane >> 5;
+    const auto row_of = [&](int rl) { return FlatRow{oks[rl] != 0, (int32_t)((r0 + rl) * stride), false, 0}; };
     for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
         const int q0 = qt * kFlatTile;
-        f32x16 acc00, acc01, acc10, acc11;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        FlatAcc acc;
+        acc.zero();
         for (int k0 = 0; k0 < D; k0 += kFlatDepth) {
             __syncthreads();  // the previous stage is consumed (first pass: the row tile's norms and flags are written)
-            if constexpr (VEC) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int e = tid + i * 256;  // 1024 slots of 4 floats
-                    const int r = e >> 3, c = (e & 7) * 4;
-                    f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
-                    const int64_t rr = r0 + r;
-                    const int qq = q0 + r;
-                    if (rr < S && k0 + c < D) va = *(const f32x4 *)(x + rr * stride * D + k0 + c);
-                    if (qq < B && k0 + c < D) vb = *(const f32x4 *)(q + (int64_t)qq * D + k0 + c);
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        As[r * kFlatLd + c + t] = va[t];
-                        Bs[r * kFlatLd + c + t] = vb[t];
-                    }
-                }
-            } else {
-#pragma unroll 4
-                for (int i = 0; i < 16; ++i) {
-                    const int e = tid + i * 256;  // 4096 floats
-                    const int r = e >> 5, c = e & 31;
-                    const int64_t rr = r0 + r;
-                    const int qq = q0 + r;
-                    As[r * kFlatLd + c] = (rr < S && k0 + c < D) ? x[rr * stride * D + k0 + c] : 0.f;
-                    Bs[r * kFlatLd + c] = (qq < B && k0 + c < D) ? q[(int64_t)qq * D + k0 + c] : 0.f;
-                }
-            }
+            flat_f32_stage<VEC>(
+                tid, k0, D, x, q, As, Bs, [&](int r) { return FlatSlot{r0 + r < S, (r0 + r) * stride * D}; },
+                [&](int r) { return FlatSlot{q0 + r < B, (int64_t)(q0 + r) * D}; });
             __syncthreads();
-#pragma unroll
-            for (int kk = 0; kk < kFlatDepth; kk += 2) {
-                const int kc = kk + lh;
-                const float a0 = As[(wr + l31) * kFlatLd + kc], a1 = As[(wr + 32 + l31) * kFlatLd + kc];
-                const float b0 = Bs[(wq + l31) * kFlatLd + kc], b1 = Bs[(wq + 32 + l31) * kFlatLd + kc];
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11, 0, 0, 0);
-            }
+            flat_f32_contract(As, Bs, wr, wq, l31, lh, acc);
         }
-        // epilogue: score, compare, append
 #pragma unroll
         for (int qj = 0; qj < 2; ++qj) {
             const int qi = q0 + wq + qj * 32 + l31;
             if (qi >= B) continue;
-            const float qn = qnorm[qi], t = thr[qi];
-            int32_t *my_cnt = cnt + qi;
-            int32_t *my_list = cand + (int64_t)qi * cap;
+            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, 0.f, cand, cnt, cap, nullptr, 0);
 #pragma unroll
-            for (int ri = 0; ri < 2; ++ri) {
-                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                    if (!oks[rl]) continue;
-                    const float a = nxs[rl] + qn;
-                    const float dot = acc[reg];
-                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
-                    const float bound = t + (c_rel * a + c_abs);
-                    if (!(v > bound)) {
-                        // (a list that has already overflowed takes the slower route whatever else arrives: stop counting)
-                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
-                            const int pos = atomicAdd(my_cnt, 1);
-                            if (pos < cap) my_list[pos] = (int32_t)((r0 + rl) * stride);
-                        }
-                    }
-                }
-            }
+            for (int ri = 0; ri < 2; ++ri)
+                flat_tile_epilogue<false, false>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
         }
     }
 }
@@ -212,7 +293,62 @@ __global__ __launch_bounds__(256) void flat_split_queries_kernel(const float *__
     if (lane == 0) qnorm[b] = s;
 }
 
-// flat_filter_kernel's job, grid, tile and epilogue.  scores != NULL (tests, measurements): v of every (query, stage row) pair goes to
+// One LDS stage of NP planes of 2-byte values (V: eight of them, one 16-byte slot; bf16 or f16): coordinates k0 .. k0 + kSplitDepth of
+// the tile's kFlatTile rows, plane p of row r from src[p] + row_at(r).off -- zeros at or past coordinate `lim` (a multiple of 8) and
+// for a slot that is not ok -- to dst[p] at pitch kSplitLd.  256 threads.
+template <class V, int NP, class E, class RowAt>
+__device__ __forceinline__ void flat_stage_planes(int tid, int k0, int lim, const E *const (&src)[NP], E *const (&dst)[NP], RowAt &&row_at) {
+#pragma unroll
+    for (int i = 0; i < kSplitDepth / 16; ++i) {
+        const int e = tid + i * 256;  // slots of 8 values per plane
+        const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
+        const FlatSlot s = row_at(r);
+        V v[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) v[p][t] = (E)0.f;
+        }
+        if (s.ok && k0 + c < lim) {  // (every plane's load before the first store)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) v[p] = *(const V *)(src[p] + s.off + k0 + c);
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) *(V *)(dst[p] + r * kSplitLd + c) = v[p];
+    }
+}
+
+// The split filter's K loop over one stage: the wave's 64 rows (from wr) x 64 queries (from wq), per K step of 16 the products h.h, h.l
+// and l.h on v_mfma_f32_32x32x16_bf16 -- twelve MFMAs; a K step of padding only ends the loop.  A macro, not a function like
+// flat_f32_contract: as an inlined function over the four planes (whole loop or single step, with or without the early exit, generic or
+// LDS pointers) all eight fragment loads of a K step are issued ahead of its first MFMA where the text form issues four and interleaves
+// the rest -- four more fragments live at once, 18 VGPRs in ivf_flat_split_filter_kernel; as text in the kernel, none.
+#define FLAT_BF16X3_CONTRACT(Ah, Al, Bh, Bl, k0, D, wr, wq, l31, lh, acc)                                                                              \
+    do {                                                                                                                                               \
+    _Pragma("unroll")                                                                                                                                  \
+        for (int kk = 0; kk < kSplitDepth; kk += 16) {                                                                                                 \
+            if (k0 + kk >= D) break;                                                                                                                   \
+            const int kc = kk + 8 * lh;                                                                                                                \
+            const bf16x8 a0h = *(const bf16x8 *)(Ah + (wr + l31) * kSplitLd + kc), a0l = *(const bf16x8 *)(Al + (wr + l31) * kSplitLd + kc);           \
+            const bf16x8 a1h = *(const bf16x8 *)(Ah + (wr + 32 + l31) * kSplitLd + kc), a1l = *(const bf16x8 *)(Al + (wr + 32 + l31) * kSplitLd + kc); \
+            const bf16x8 b0h = *(const bf16x8 *)(Bh + (wq + l31) * kSplitLd + kc), b0l = *(const bf16x8 *)(Bl + (wq + l31) * kSplitLd + kc);           \
+            const bf16x8 b1h = *(const bf16x8 *)(Bh + (wq + 32 + l31) * kSplitLd + kc), b1l = *(const bf16x8 *)(Bl + (wq + 32 + l31) * kSplitLd + kc); \
+            acc.c00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0h, acc.c00, 0, 0, 0);                                                             \
+            acc.c01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1h, acc.c01, 0, 0, 0);                                                             \
+            acc.c10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0h, acc.c10, 0, 0, 0);                                                             \
+            acc.c11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1h, acc.c11, 0, 0, 0);                                                             \
+            acc.c00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0l, acc.c00, 0, 0, 0);                                                             \
+            acc.c01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1l, acc.c01, 0, 0, 0);                                                             \
+            acc.c10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0l, acc.c10, 0, 0, 0);                                                             \
+            acc.c11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1l, acc.c11, 0, 0, 0);                                                             \
+            acc.c00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b0h, acc.c00, 0, 0, 0);                                                             \
+            acc.c01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b1h, acc.c01, 0, 0, 0);                                                             \
+            acc.c10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b0h, acc.c10, 0, 0, 0);                                                             \
+            acc.c11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b1h, acc.c11, 0, 0, 0);                                                             \
+        }                                                                                                                                              \
+    } while (0)
+
+// flat_filter_kernel's job, grid and tile.  scores != NULL (tests, measurements): v of every (query, stage row) pair goes to
 // scores f32 [B][S] as well.
 template <bool VEC>
 __global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, const __bf16 *__restrict__ qh, const __bf16 *__restrict__ ql, int B,
@@ -230,21 +366,16 @@ __global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, cons
     __shared__ int oks[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
-    if (tid < kFlatTile) {
-        const int64_t r = r0 + tid;
-        bool ok = r < S;
-        const int64_t row = ok ? r * stride : 0;
-        if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
-        oks[tid] = ok ? 1 : 0;
-        nxs[tid] = ok ? norms[row] : 0.f;
-    }
+    flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
     const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
     const int l31 = lane & 31, lh = lane >> 5;
+    const __bf16 *const qp[2] = {qh, ql};
+    __bf16 *const bp[2] = {Bh, Bl};
+    const auto row_of = [&](int rl) { return FlatRow{oks[rl] != 0, (int32_t)((r0 + rl) * stride), r0 + rl < S, r0 + rl}; };
     for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
         const int q0 = qt * kFlatTile;
-        f32x16 acc00, acc01, acc10, acc11;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        FlatAcc acc;
+        acc.zero();
         for (int k0 = 0; k0 < D; k0 += kSplitDepth) {
             __syncthreads();  // the previous stage is consumed (first pass: the row tile's norms and flags are written)
             // rows: f32 from HBM, centred, split, two planes
@@ -286,73 +417,19 @@ __global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, cons
                     Al[r * kSplitLd + c] = l;
                 }
             }
-            // queries: the planes of flat_split_queries_kernel, 16 bytes at a time (Dp is a multiple of 8 coordinates)
-#pragma unroll
-            for (int i = 0; i < kSplitDepth / 16; ++i) {
-                const int e = tid + i * 256;  // slots of 8 bf16 per plane
-                const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
-                const int qq = q0 + r;
-                bf16x8 vh, vl;
-#pragma unroll
-                for (int t = 0; t < 8; ++t) vh[t] = vl[t] = (__bf16)0.f;
-                if (qq < B && k0 + c < Dp) {
-                    vh = *(const bf16x8 *)(qh + (int64_t)qq * Dp + k0 + c);
-                    vl = *(const bf16x8 *)(ql + (int64_t)qq * Dp + k0 + c);
-                }
-                *(bf16x8 *)(Bh + r * kSplitLd + c) = vh;
-                *(bf16x8 *)(Bl + r * kSplitLd + c) = vl;
-            }
+            // queries: the planes of flat_split_queries_kernel (Dp is a multiple of 8 coordinates)
+            flat_stage_planes<bf16x8>(tid, k0, Dp, qp, bp, [&](int r) { return FlatSlot{q0 + r < B, (int64_t)(q0 + r) * Dp}; });
             __syncthreads();
-#pragma unroll
-            for (int kk = 0; kk < kSplitDepth; kk += 16) {
-                if (k0 + kk >= D) break;  // (a K step of padding only)
-                const int kc = kk + 8 * lh;
-                const bf16x8 a0h = *(const bf16x8 *)(Ah + (wr + l31) * kSplitLd + kc), a0l = *(const bf16x8 *)(Al + (wr + l31) * kSplitLd + kc);
-                const bf16x8 a1h = *(const bf16x8 *)(Ah + (wr + 32 + l31) * kSplitLd + kc), a1l = *(const bf16x8 *)(Al + (wr + 32 + l31) * kSplitLd + kc);
-                const bf16x8 b0h = *(const bf16x8 *)(Bh + (wq + l31) * kSplitLd + kc), b0l = *(const bf16x8 *)(Bl + (wq + l31) * kSplitLd + kc);
-                const bf16x8 b1h = *(const bf16x8 *)(Bh + (wq + 32 + l31) * kSplitLd + kc), b1l = *(const bf16x8 *)(Bl + (wq + 32 + l31) * kSplitLd + kc);
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0h, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1h, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0h, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1h, acc11, 0, 0, 0);
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0l, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1l, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0l, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1l, acc11, 0, 0, 0);
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b0h, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b1h, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b0h, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b1h, acc11, 0, 0, 0);
-            }
+            FLAT_BF16X3_CONTRACT(Ah, Al, Bh, Bl, k0, D, wr, wq, l31, lh, acc);
         }
-        // epilogue: score, compare, append (flat_filter_kernel's, on the centred norms)
 #pragma unroll
         for (int qj = 0; qj < 2; ++qj) {
             const int qi = q0 + wq + qj * 32 + l31;
             if (qi >= B) continue;
-            const float qn = qnorm[qi], t = thr[qi];
-            int32_t *my_cnt = cnt + qi;
-            int32_t *my_list = cand + (int64_t)qi * cap;
+            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, 0.f, cand, cnt, cap, scores, S);
 #pragma unroll
-            for (int ri = 0; ri < 2; ++ri) {
-                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                    const float a = nxs[rl] + qn;
-                    const float dot = acc[reg];
-                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
-                    if (scores && r0 + rl < S) scores[(int64_t)qi * S + r0 + rl] = v;
-                    if (!oks[rl]) continue;
-                    const float bound = t + (c_rel * a + c_abs);
-                    if (!(v > bound)) {
-                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
-                            const int pos = atomicAdd(my_cnt, 1);
-                            if (pos < cap) my_list[pos] = (int32_t)((r0 + rl) * stride);
-                        }
-                    }
-                }
-            }
+            for (int ri = 0; ri < 2; ++ri)
+                flat_tile_epilogue<false, true>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
         }
     }
 }
@@ -429,36 +506,21 @@ __global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const 
     __shared__ int oks[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
-    if (tid < kFlatTile) {
-        const int64_t r = r0 + tid;
-        bool ok = r < S;
-        const int64_t row = ok ? r * stride : 0;
-        if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
-        oks[tid] = ok ? 1 : 0;
-        nxs[tid] = ok ? norms[row] : 0.f;
-    }
+    flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
     const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
     const int l31 = lane & 31, lh = lane >> 5;
+    const _Float16 *const xp[1] = {x}, *const qp[2] = {qh, ql};
+    _Float16 *const ap[1] = {As}, *const bp[2] = {Bh, Bl};
+    const auto row_of = [&](int rl) { return FlatRow{oks[rl] != 0, (int32_t)((r0 + rl) * stride), r0 + rl < S, r0 + rl}; };
     for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
         const int q0 = qt * kFlatTile;
-        f32x16 acc00, acc01, acc10, acc11;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        FlatAcc acc;
+        acc.zero();
         for (int k0 = 0; k0 < D; k0 += kSplitDepth) {
             __syncthreads();  // the previous stage is consumed (first pass: the row tile's norms and flags are written)
             // rows: f16 from HBM as they are
             if constexpr (VEC) {
-#pragma unroll
-                for (int i = 0; i < kSplitDepth / 16; ++i) {
-                    const int e = tid + i * 256;  // slots of 8 f16
-                    const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
-                    f16x8 va;
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) va[t] = (_Float16)0.f;
-                    const int64_t rr = r0 + r;
-                    if (rr < S && k0 + c < D) va = *(const f16x8 *)(x + rr * stride * D + k0 + c);
-                    *(f16x8 *)(As + r * kSplitLd + c) = va;
-                }
+                flat_stage_planes<f16x8>(tid, k0, D, xp, ap, [&](int r) { return FlatSlot{r0 + r < S, (r0 + r) * stride * D}; });
             } else {
 #pragma unroll 4
                 for (int i = 0; i < kSplitDepth / 2; ++i) {
@@ -468,22 +530,8 @@ __global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const 
                     As[r * kSplitLd + c] = (rr < S && k0 + c < D) ? x[rr * stride * D + k0 + c] : (_Float16)0.f;
                 }
             }
-            // queries: the planes of flat_f16_queries_kernel, 16 bytes at a time (Dp is a multiple of 8 coordinates)
-#pragma unroll
-            for (int i = 0; i < kSplitDepth / 16; ++i) {
-                const int e = tid + i * 256;  // slots of 8 f16 per plane
-                const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
-                const int qq = q0 + r;
-                f16x8 vh, vl;
-#pragma unroll
-                for (int t = 0; t < 8; ++t) vh[t] = vl[t] = (_Float16)0.f;
-                if (qq < B && k0 + c < Dp) {
-                    vh = *(const f16x8 *)(qh + (int64_t)qq * Dp + k0 + c);
-                    vl = *(const f16x8 *)(ql + (int64_t)qq * Dp + k0 + c);
-                }
-                *(f16x8 *)(Bh + r * kSplitLd + c) = vh;
-                *(f16x8 *)(Bl + r * kSplitLd + c) = vl;
-            }
+            // queries: the planes of flat_f16_queries_kernel (Dp is a multiple of 8 coordinates)
+            flat_stage_planes<f16x8>(tid, k0, Dp, qp, bp, [&](int r) { return FlatSlot{q0 + r < B, (int64_t)(q0 + r) * Dp}; });
             __syncthreads();
 #pragma unroll
             for (int kk = 0; kk < kSplitDepth; kk += 16) {
@@ -492,44 +540,27 @@ __global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const 
                 const f16x8 a0 = *(const f16x8 *)(As + (wr + l31) * kSplitLd + kc), a1 = *(const f16x8 *)(As + (wr + 32 + l31) * kSplitLd + kc);
                 const f16x8 b0h = *(const f16x8 *)(Bh + (wq + l31) * kSplitLd + kc), b0l = *(const f16x8 *)(Bl + (wq + l31) * kSplitLd + kc);
                 const f16x8 b1h = *(const f16x8 *)(Bh + (wq + 32 + l31) * kSplitLd + kc), b1l = *(const f16x8 *)(Bl + (wq + 32 + l31) * kSplitLd + kc);
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0h, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1h, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0h, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1h, acc11, 0, 0, 0);
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0l, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1l, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0l, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1l, acc11, 0, 0, 0);
+                acc.c00 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0h, acc.c00, 0, 0, 0);
+                acc.c01 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1h, acc.c01, 0, 0, 0);
+                acc.c10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0h, acc.c10, 0, 0, 0);
+                acc.c11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1h, acc.c11, 0, 0, 0);
+                acc.c00 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0l, acc.c00, 0, 0, 0);
+                acc.c01 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1l, acc.c01, 0, 0, 0);
+                acc.c10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0l, acc.c10, 0, 0, 0);
+                acc.c11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1l, acc.c11, 0, 0, 0);
             }
         }
-        // epilogue: the accumulator back to the query's scale, then flat_filter_kernel's score, comparison and append
+        // the accumulator back to the query's scale: that is this kernel's dot product
 #pragma unroll
         for (int qj = 0; qj < 2; ++qj) {
             const int qi = q0 + wq + qj * 32 + l31;
             if (qi >= B) continue;
-            const float qn = qnorm[qi], t = thr[qi], down = qscale[qi], flush = qflush[qi];
-            int32_t *my_cnt = cnt + qi;
-            int32_t *my_list = cand + (int64_t)qi * cap;
+            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, qflush[qi], cand, cnt, cap, scores, S);
+            const float down = qscale[qi];
 #pragma unroll
-            for (int ri = 0; ri < 2; ++ri) {
-                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                    const float a = nxs[rl] + qn;
-                    const float dot = acc[reg] * down;
-                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
-                    if (scores && r0 + rl < S) scores[(int64_t)qi * S + r0 + rl] = v;
-                    if (!oks[rl]) continue;
-                    const float bound = t + ((c_rel * a + c_abs) + flush);
-                    if (!(v > bound)) {
-                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
-                            const int pos = atomicAdd(my_cnt, 1);
-                            if (pos < cap) my_list[pos] = (int32_t)((r0 + rl) * stride);
-                        }
-                    }
-                }
-            }
+            for (int ri = 0; ri < 2; ++ri)
+                flat_tile_epilogue<true, true>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg] * down; },
+                                         row_of);
         }
     }
 }
@@ -634,17 +665,11 @@ __global__ __launch_bounds__(kI8Threads) void flat_i8_filter_kernel(int metric, 
     __shared__ int oks[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
-    if (tid < kFlatTile) {
-        const int64_t r = r0 + tid;
-        bool ok = r < S;
-        const int64_t row = ok ? r * stride : 0;
-        if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
-        oks[tid] = ok ? 1 : 0;
-        nxs[tid] = ok ? norms[row] : 0.f;
-    }
+    flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
     const int wr = (wave >> 2) * 64, wq = (wave & 3) * 32;
     const int l31 = lane & 31, lh = lane >> 5;
     const int sr = tid >> 2, sc = (tid & 3) * 16;  // the thread's slot of 16 bytes in a stage: 128 rows x 4 slots
+    const auto row_of = [&](int rl) { return FlatRow{oks[rl] != 0, (int32_t)((r0 + rl) * stride), r0 + rl < S, r0 + rl}; };
     for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
         const int q0 = qt * kFlatTile;
         i32x16 s0a, s0b, s1a, s1b, s2a, s2b;  // plane 0 / 1 / 2, rows wr .. wr + 31 (a) and wr + 32 .. wr + 63 (b)
@@ -697,33 +722,21 @@ __global__ __launch_bounds__(kI8Threads) void flat_i8_filter_kernel(int metric, 
                 s2b = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b2, s2b, 0, 0, 0);
             }
         }
-        // epilogue: the three sums back into ONE integer, one conversion, the query's scale; then flat_filter_kernel's score, comparison and
-        // append.  A lane owns one query.
+        // the three sums back into ONE integer, one conversion, the query's scale: that is this kernel's dot product.  A lane owns one query.
         const int qi = q0 + wq + l31;
         if (qi >= B) continue;
-        const float qn = qnorm[qi], t = thr[qi], down = qscale[qi], extra = qslack[qi];
-        int32_t *my_cnt = cnt + qi;
-        int32_t *my_list = cand + (int64_t)qi * cap;
+        const FlatQuery Q = flat_query(qi, qnorm[qi], thr, qslack[qi], cand, cnt, cap, scores, S);
+        const float down = qscale[qi];
 #pragma unroll
         for (int ri = 0; ri < 2; ++ri) {
             const i32x16 &S0 = ri == 0 ? s0a : s0b, &S1 = ri == 0 ? s1a : s1b, &S2 = ri == 0 ? s2a : s2b;
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                const float a = nxs[rl] + qn;
-                const int64_t T = (int64_t)S2[reg] * 16384 + (int64_t)S1[reg] * 128 + (int64_t)S0[reg];  // = sum Q_j c_j, |T| < 2^43
-                const float dot = (float)T * down;
-                const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
-                if (scores && r0 + rl < S) scores[(int64_t)qi * S + r0 + rl] = v;
-                if (!oks[rl]) continue;
-                const float bound = t + ((c_rel * a + c_abs) + extra);
-                if (!(v > bound)) {
-                    if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
-                        const int pos = atomicAdd(my_cnt, 1);
-                        if (pos < cap) my_list[pos] = (int32_t)((r0 + rl) * stride);
-                    }
-                }
-            }
+            flat_tile_epilogue<true, true>(
+                metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh,
+                [&](int reg) {
+                    const int64_t T = (int64_t)S2[reg] * 16384 + (int64_t)S1[reg] * 128 + (int64_t)S0[reg];  // = sum Q_j c_j, |T| < 2^43
+                    return (float)T * down;
+                },
+                row_of);
         }
     }
 }
@@ -907,8 +920,40 @@ __global__ __launch_bounds__(256) void ivf_flat_exact_kernel(int metric, const f
 // flat_filter_kernel over (plan tile t, row tile of t's cell): tile t = the 128 slots vmap[128 t ..] of queries that probe ONE cell
 // (annlite_ivf_plan; -1: a padding slot), whose range of perm is tile_rows[t] (begin -1: an unused tile).  blockIdx.x = the row tile
 // inside the cell at this stride, blockIdx.y (+ gridDim.y, ...) = t.  A operand: rows gathered through perm, B operand: queries
-// gathered through vmap; the contraction, the score, the comparison and the append are flat_filter_kernel's, and what is appended is
+// gathered through vmap; the contraction is flat_filter_kernel's (flat_f32_stage, flat_f32_contract), the score, the comparison and
+// the append are flat_tile_epilogue's as in every filter, and what is appended is
 // the row's OFFSET.  A query sits in at most one slot per cell and a row in one cell, so a list takes no pair twice.
+
+// Plan tile t's range of perm, from `begin`, and S, its stage rows at this stride.  False: an unused tile.
+__device__ __forceinline__ bool ivf_flat_tile_range(const int64_t *__restrict__ tile_rows, int t, int64_t n_perm, int64_t stride, int64_t &begin,
+                                                    int64_t &S) {
+    begin = tile_rows[2 * (int64_t)t];
+    int64_t end = tile_rows[2 * (int64_t)t + 1];
+    if (begin < 0) return false;
+    if (end > n_perm) end = n_perm;
+    S = (end - begin + stride - 1) / stride;
+    return true;
+}
+
+// The row tile and the query slots of a cell kernel, by its 2 kFlatTile threads: rws[i] = offset of stage row r0 + i of the tile's range,
+// -1: none (past the cell's end, not valid); nxs[i] = its norm; qss[i] = query of the tile's slot i, -1: padding.
+__device__ __forceinline__ void ivf_flat_tile_rows(int tid, int t, int64_t r0, int64_t S, int64_t begin, int64_t stride,
+                                                   const int32_t *__restrict__ perm, int64_t N, const uint32_t *__restrict__ valid,
+                                                   const float *__restrict__ norms, const int32_t *__restrict__ vmap, int B, int *rws, float *nxs,
+                                                   int *qss) {
+    if (tid < kFlatTile) {
+        const int64_t r = r0 + tid;
+        int64_t row = r < S ? (int64_t)perm[begin + r * stride] : -1;
+        if (row >= N) row = -1;
+        if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
+        rws[tid] = (int)row;
+        nxs[tid] = row >= 0 ? norms[row] : 0.f;
+    } else {
+        const int qi = vmap[(int64_t)t * kFlatTile + tid - kFlatTile];
+        qss[tid - kFlatTile] = (unsigned)qi < (unsigned)B ? qi : -1;
+    }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void ivf_flat_filter_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
                                                              const float *__restrict__ norms, int64_t N, const int32_t *__restrict__ perm,
@@ -920,100 +965,36 @@ __global__ __launch_bounds__(256) void ivf_flat_filter_kernel(int metric, const 
     __shared__ float As[kFlatTile * kFlatLd];
     __shared__ float Bs[kFlatTile * kFlatLd];
     __shared__ float nxs[kFlatTile];
-    __shared__ int rws[kFlatTile];  // offset of the tile's row, -1: none (past the cell's end, not valid)
-    __shared__ int qss[kFlatTile];  // query of the tile's slot, -1: padding
+    __shared__ int rws[kFlatTile];
+    __shared__ int qss[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
     const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
     const int l31 = lane & 31, lh = lane >> 5;
+    const auto row_of = [&](int rl) { return FlatRow{rws[rl] >= 0, rws[rl], false, 0}; };
     for (int t = blockIdx.y; t < n_tiles; t += gridDim.y) {
-        int64_t begin = tile_rows[2 * (int64_t)t], end = tile_rows[2 * (int64_t)t + 1];
-        if (begin < 0) continue;
-        if (end > n_perm) end = n_perm;
-        const int64_t S = (end - begin + stride - 1) / stride;
-        if (r0 >= S) continue;  // (both tests are the workgroup's: no barrier is left behind)
-        __syncthreads();        // the previous tile's epilogue has read rws / nxs / qss
-        if (tid < kFlatTile) {
-            const int64_t r = r0 + tid;
-            int64_t row = r < S ? (int64_t)perm[begin + r * stride] : -1;
-            if (row >= N) row = -1;
-            if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
-            rws[tid] = (int)row;
-            nxs[tid] = row >= 0 ? norms[row] : 0.f;
-        } else {
-            const int qi = vmap[(int64_t)t * kFlatTile + tid - kFlatTile];
-            qss[tid - kFlatTile] = (unsigned)qi < (unsigned)B ? qi : -1;
-        }
-        f32x16 acc00, acc01, acc10, acc11;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        int64_t begin, S;
+        if (!ivf_flat_tile_range(tile_rows, t, n_perm, stride, begin, S) || r0 >= S) continue;  // (the workgroup's: no barrier is left behind)
+        __syncthreads();  // the previous tile's epilogue has read rws / nxs / qss
+        ivf_flat_tile_rows(tid, t, r0, S, begin, stride, perm, N, valid, norms, vmap, B, rws, nxs, qss);
+        FlatAcc acc;
+        acc.zero();
         for (int k0 = 0; k0 < D; k0 += kFlatDepth) {
             __syncthreads();  // the previous stage is consumed (first pass: the tile's rows and queries are written)
-            if constexpr (VEC) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int e = tid + i * 256;  // 1024 slots of 4 floats
-                    const int r = e >> 3, c = (e & 7) * 4;
-                    f32x4 va = {0.f, 0.f, 0.f, 0.f}, vb = {0.f, 0.f, 0.f, 0.f};
-                    const int rr = rws[r], qq = qss[r];
-                    if (rr >= 0 && k0 + c < D) va = *(const f32x4 *)(x + (int64_t)rr * D + k0 + c);
-                    if (qq >= 0 && k0 + c < D) vb = *(const f32x4 *)(q + (int64_t)qq * D + k0 + c);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        As[r * kFlatLd + c + u] = va[u];
-                        Bs[r * kFlatLd + c + u] = vb[u];
-                    }
-                }
-            } else {
-#pragma unroll 4
-                for (int i = 0; i < 16; ++i) {
-                    const int e = tid + i * 256;  // 4096 floats
-                    const int r = e >> 5, c = e & 31;
-                    const int rr = rws[r], qq = qss[r];
-                    As[r * kFlatLd + c] = (rr >= 0 && k0 + c < D) ? x[(int64_t)rr * D + k0 + c] : 0.f;
-                    Bs[r * kFlatLd + c] = (qq >= 0 && k0 + c < D) ? q[(int64_t)qq * D + k0 + c] : 0.f;
-                }
-            }
+            flat_f32_stage<VEC>(
+                tid, k0, D, x, q, As, Bs, [&](int r) { return FlatSlot{rws[r] >= 0, (int64_t)rws[r] * D}; },
+                [&](int r) { return FlatSlot{qss[r] >= 0, (int64_t)qss[r] * D}; });
             __syncthreads();
-#pragma unroll
-            for (int kk = 0; kk < kFlatDepth; kk += 2) {
-                const int kc = kk + lh;
-                const float a0 = As[(wr + l31) * kFlatLd + kc], a1 = As[(wr + 32 + l31) * kFlatLd + kc];
-                const float b0 = Bs[(wq + l31) * kFlatLd + kc], b1 = Bs[(wq + 32 + l31) * kFlatLd + kc];
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11, 0, 0, 0);
-            }
+            flat_f32_contract(As, Bs, wr, wq, l31, lh, acc);
         }
-        // epilogue: score, compare, append (flat_filter_kernel's)
 #pragma unroll
         for (int qj = 0; qj < 2; ++qj) {
             const int qi = qss[wq + qj * 32 + l31];
             if (qi < 0) continue;
-            const float qn = qnorm[qi], tq = thr[qi];
-            int32_t *my_cnt = cnt + qi;
-            int32_t *my_list = cand + (int64_t)qi * cap;
+            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, 0.f, cand, cnt, cap, nullptr, 0);
 #pragma unroll
-            for (int ri = 0; ri < 2; ++ri) {
-                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                    const int off = rws[rl];
-                    if (off < 0) continue;
-                    const float a = nxs[rl] + qn;
-                    const float dot = acc[reg];
-                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
-                    const float bound = tq + (c_rel * a + c_abs);
-                    if (!(v > bound)) {
-                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
-                            const int pos = atomicAdd(my_cnt, 1);
-                            if (pos < cap) my_list[pos] = off;
-                        }
-                    }
-                }
-            }
+            for (int ri = 0; ri < 2; ++ri)
+                flat_tile_epilogue<false, false>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
         }
     }
 }
@@ -1063,7 +1044,7 @@ __global__ __launch_bounds__(256) void ivf_flat_split_queries_kernel(const float
     }
 }
 
-// ivf_flat_filter_kernel's grid, tile walk, rws / qss and epilogue; flat_split_filter_kernel's LDS planes and MFMAs.  The rows are
+// ivf_flat_filter_kernel's grid, tile walk and rws / qss; flat_split_filter_kernel's LDS planes and MFMAs; flat_tile_epilogue.  The rows are
 // gathered through perm, centred on the tile's centroid -- the cell of the range's first row, cell_of[perm[begin]] -- and split while
 // they are staged; a thread stages the same four (VEC) / one coordinates of every row it handles, so it loads its piece of the centroid
 // once per stage.  norms: the column of |fl(x - centre of x's cell)|^2 (annlite_ivf_flat_centred_norms; |x|^2 without centres);
@@ -1085,40 +1066,28 @@ __global__ __launch_bounds__(256) void ivf_flat_split_filter_kernel(int metric, 
     __shared__ __attribute__((aligned(16))) __bf16 Bh[kFlatTile * kSplitLd];
     __shared__ __attribute__((aligned(16))) __bf16 Bl[kFlatTile * kSplitLd];
     __shared__ float nxs[kFlatTile];
-    __shared__ int rws[kFlatTile];  // offset of the tile's row, -1: none (past the cell's end, not valid)
-    __shared__ int qss[kFlatTile];  // query of the tile's slot, -1: padding
+    __shared__ int rws[kFlatTile];
+    __shared__ int qss[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
     const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
     const int l31 = lane & 31, lh = lane >> 5;
+    __bf16 *const bp[2] = {Bh, Bl};
+    const auto row_of = [&](int rl) { return FlatRow{rws[rl] >= 0, rws[rl], rws[rl] >= 0, (int64_t)rws[rl]}; };
     for (int t = blockIdx.y; t < n_tiles; t += gridDim.y) {
-        int64_t begin = tile_rows[2 * (int64_t)t], end = tile_rows[2 * (int64_t)t + 1];
-        if (begin < 0) continue;
-        if (end > n_perm) end = n_perm;
-        const int64_t S = (end - begin + stride - 1) / stride;
-        if (r0 >= S) continue;  // (both tests are the workgroup's: no barrier is left behind)
-        __syncthreads();        // the previous tile's epilogue has read rws / nxs / qss
-        if (tid < kFlatTile) {
-            const int64_t r = r0 + tid;
-            int64_t row = r < S ? (int64_t)perm[begin + r * stride] : -1;
-            if (row >= N) row = -1;
-            if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
-            rws[tid] = (int)row;
-            nxs[tid] = row >= 0 ? norms[row] : 0.f;
-        } else {
-            const int qi = vmap[(int64_t)t * kFlatTile + tid - kFlatTile];
-            qss[tid - kFlatTile] = (unsigned)qi < (unsigned)B ? qi : -1;
-        }
+        int64_t begin, S;
+        if (!ivf_flat_tile_range(tile_rows, t, n_perm, stride, begin, S) || r0 >= S) continue;  // (the workgroup's: no barrier is left behind)
+        __syncthreads();  // the previous tile's epilogue has read rws / nxs / qss
+        ivf_flat_tile_rows(tid, t, r0, S, begin, stride, perm, N, valid, norms, vmap, B, rws, nxs, qss);
         const float *mu = nullptr;  // the tile's centroid (the range is not empty: r0 < S)
         if (centres) {
             const int64_t first = perm[begin];
             const int c = (first >= 0 && first < N) ? cell_of[first] : 0;
             mu = centres + (int64_t)((unsigned)c < (unsigned)C ? c : 0) * D;
         }
-        const __bf16 *th = qh + (int64_t)t * kFlatTile * Dp, *tl = ql + (int64_t)t * kFlatTile * Dp;
-        f32x16 acc00, acc01, acc10, acc11;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.f;
+        const __bf16 *const tp[2] = {qh + (int64_t)t * kFlatTile * Dp, ql + (int64_t)t * kFlatTile * Dp};  // the planes of the tile's slots
+        FlatAcc acc;
+        acc.zero();
         for (int k0 = 0; k0 < D; k0 += kSplitDepth) {
             __syncthreads();  // the previous stage is consumed (first pass: the tile's rows and queries are written)
             // rows: f32 gathered from HBM, centred, split, two planes
@@ -1157,74 +1126,21 @@ __global__ __launch_bounds__(256) void ivf_flat_split_filter_kernel(int metric, 
                     Al[r * kSplitLd + c] = l;
                 }
             }
-            // queries: the planes of the tile's slots, 16 bytes at a time (Dp is a multiple of 8 coordinates)
-#pragma unroll
-            for (int i = 0; i < kSplitDepth / 16; ++i) {
-                const int e = tid + i * 256;  // slots of 8 bf16 per plane
-                const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
-                bf16x8 vh, vl;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) vh[u] = vl[u] = (__bf16)0.f;
-                if (qss[r] >= 0 && k0 + c < Dp) {
-                    vh = *(const bf16x8 *)(th + (int64_t)r * Dp + k0 + c);
-                    vl = *(const bf16x8 *)(tl + (int64_t)r * Dp + k0 + c);
-                }
-                *(bf16x8 *)(Bh + r * kSplitLd + c) = vh;
-                *(bf16x8 *)(Bl + r * kSplitLd + c) = vl;
-            }
+            // queries: the planes of the tile's slots, back to back (Dp is a multiple of 8 coordinates)
+            flat_stage_planes<bf16x8>(tid, k0, Dp, tp, bp, [&](int r) { return FlatSlot{qss[r] >= 0, (int64_t)r * Dp}; });
             __syncthreads();
-#pragma unroll
-            for (int kk = 0; kk < kSplitDepth; kk += 16) {
-                if (k0 + kk >= D) break;  // (a K step of padding only)
-                const int kc = kk + 8 * lh;
-                const bf16x8 a0h = *(const bf16x8 *)(Ah + (wr + l31) * kSplitLd + kc), a0l = *(const bf16x8 *)(Al + (wr + l31) * kSplitLd + kc);
-                const bf16x8 a1h = *(const bf16x8 *)(Ah + (wr + 32 + l31) * kSplitLd + kc), a1l = *(const bf16x8 *)(Al + (wr + 32 + l31) * kSplitLd + kc);
-                const bf16x8 b0h = *(const bf16x8 *)(Bh + (wq + l31) * kSplitLd + kc), b0l = *(const bf16x8 *)(Bl + (wq + l31) * kSplitLd + kc);
-                const bf16x8 b1h = *(const bf16x8 *)(Bh + (wq + 32 + l31) * kSplitLd + kc), b1l = *(const bf16x8 *)(Bl + (wq + 32 + l31) * kSplitLd + kc);
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0h, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1h, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0h, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1h, acc11, 0, 0, 0);
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b0l, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0h, b1l, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b0l, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1h, b1l, acc11, 0, 0, 0);
-                acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b0h, acc00, 0, 0, 0);
-                acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, b1h, acc01, 0, 0, 0);
-                acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b0h, acc10, 0, 0, 0);
-                acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, b1h, acc11, 0, 0, 0);
-            }
+            FLAT_BF16X3_CONTRACT(Ah, Al, Bh, Bl, k0, D, wr, wq, l31, lh, acc);
         }
-        // epilogue: score, compare, append (ivf_flat_filter_kernel's, on the centred norms of the row and of the slot's pair)
+        // (the norms are the centred ones: of the row, and of the slot's pair)
 #pragma unroll
         for (int qj = 0; qj < 2; ++qj) {
             const int sl = wq + qj * 32 + l31;
             const int qi = qss[sl];
             if (qi < 0) continue;
-            const float qn = qnorm[(int64_t)t * kFlatTile + sl], tq = thr[qi];
-            int32_t *my_cnt = cnt + qi;
-            int32_t *my_list = cand + (int64_t)qi * cap;
+            const FlatQuery Q = flat_query(qi, qnorm[(int64_t)t * kFlatTile + sl], thr, 0.f, cand, cnt, cap, scores, N);
 #pragma unroll
-            for (int ri = 0; ri < 2; ++ri) {
-                const f32x16 &acc = ri == 0 ? (qj == 0 ? acc00 : acc01) : (qj == 0 ? acc10 : acc11);
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) {
-                    const int rl = wr + ri * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                    const int off = rws[rl];
-                    if (off < 0) continue;
-                    const float a = nxs[rl] + qn;
-                    const float dot = acc[reg];
-                    const float v = (metric == ANNLITE_METRIC_EUCLIDEAN) ? a - 2.f * dot : 1.f - dot;
-                    if (scores) scores[(int64_t)qi * N + off] = v;
-                    const float bound = tq + (c_rel * a + c_abs);
-                    if (!(v > bound)) {
-                        if (__hip_atomic_load(my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= cap) {
-                            const int pos = atomicAdd(my_cnt, 1);
-                            if (pos < cap) my_list[pos] = off;
-                        }
-                    }
-                }
-            }
+            for (int ri = 0; ri < 2; ++ri)
+                flat_tile_epilogue<false, false>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
         }
     }
 }
@@ -1236,25 +1152,80 @@ struct FlatWs {
     int32_t *cnt, *ovf, *cand;
     size_t bytes;
 };
+// Carving a workspace: every piece starts on a 256-byte boundary; `o` is what has been handed out.
+struct WsBump {
+    char *p;
+    size_t o;
+    template <class T>
+    T *take(size_t bytes) {
+        T *r = (T *)(p + o);
+        o += (bytes + 255) & ~(size_t)255;
+        return r;
+    }
+};
 static FlatWs flat_carve(void *ws, int64_t B) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    WsBump b{(char *)ws, 0};
     FlatWs w;
-    char *p = (char *)ws;
-    size_t o = 0;
-    w.ovf_total = (uint32_t *)(p + o), o += 256;
-    w.thr = (float *)(p + o), o += up((size_t)B * 4);
-    w.qnorm = (float *)(p + o), o += up((size_t)B * 4);
-    w.cnt = (int32_t *)(p + o), o += up((size_t)B * 4);
-    w.ovf = (int32_t *)(p + o), o += up((size_t)B * 4);
-    w.cand = (int32_t *)(p + o), o += up((size_t)B * kFlatCap * 4);
-    w.bytes = o;
+    w.ovf_total = b.take<uint32_t>(256);
+    w.thr = b.take<float>((size_t)B * 4);
+    w.qnorm = b.take<float>((size_t)B * 4);
+    w.cnt = b.take<int32_t>((size_t)B * 4);
+    w.ovf = b.take<int32_t>((size_t)B * 4);
+    w.cand = b.take<int32_t>((size_t)B * kFlatCap * 4);
+    w.bytes = b.o;
     return w;
 }
+static int flat_check_workspace(size_t have, size_t need) {
+    if (have >= need) return ANNLITE_OK;
+    set_error("workspace too small: %zu < %zu bytes", have, need);
+    return ANNLITE_ERR_WORKSPACE;
+}
 
-// The slack's two constants.  u = 2^-24.
+// The argument checks every filter entry (kFlatStage: one stage, arg = its stride) and every search entry (kFlatSearch: arg = k)
+// starts with.  max_dim: INT32_MAX for the f32 contraction's entries, kSplitMaxDim for the others, whose message names it.
+enum FlatEntry { kFlatStage, kFlatSearch };
+static int flat_check_shape(FlatEntry what, int metric, int64_t B, int64_t D, int64_t N, int64_t arg, int64_t max_dim) {
+    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
+    const bool search = what == kFlatSearch;
+    const bool ok = B >= 0 && D >= 1 && N >= 0 && arg >= 1 && (!search || arg <= 64) && N <= INT32_MAX && B <= INT32_MAX && D <= max_dim;
+    if (max_dim == INT32_MAX) ANNLITE_REQUIRE(ok, search ? "bad shape (1 <= k <= 64)" : "bad shape");
+    else ANNLITE_REQUIRE(ok, search ? "bad shape (1 <= k <= 64, D <= %lld)" : "bad shape (D <= %lld)", (long long)max_dim);
+    return ANNLITE_OK;
+}
+
+// The grid of a table filter over S stage rows and B queries: a workgroup per row tile, and the query tiles spread over y while the
+// row tiles alone would leave CUs idle.
+struct FlatGrid {
+    dim3 grid;
+    int n_qt;
+};
+static FlatGrid flat_filter_grid(int64_t S, int64_t B) {
+    const int64_t n_rt = (S + kFlatTile - 1) / kFlatTile;
+    const int n_qt = (int)((B + kFlatTile - 1) / kFlatTile);
+    int64_t ny = (4 * (int64_t)device_cu_count() + n_rt - 1) / n_rt;  // few row tiles: spread the query tiles too
+    ny = ny < 1 ? 1 : ny > n_qt ? n_qt : ny;
+    return {dim3((unsigned)n_rt, (unsigned)ny), n_qt};
+}
+// ... and of a cell filter: the row tiles of the largest cell at this stride x the plan's tiles (the kernel walks y).  Nothing to do: x or y 0.
+static dim3 ivf_flat_filter_grid(int64_t max_cell_rows, int64_t stride, int64_t n_tiles) {
+    const int64_t n_rt = ((max_cell_rows + stride - 1) / stride + kFlatTile - 1) / kFlatTile;
+    return dim3((unsigned)(n_rt > 0 ? n_rt : 0), (unsigned)(n_tiles < 0 ? 0 : n_tiles < 65535 ? n_tiles : 65535));
+}
+
+// kernel<VEC> over the same arguments, VEC chosen at run time.
+#define FLAT_LAUNCH_VEC(vec, kernel, grid, block, st, ...)                                         \
+    do {                                                                                           \
+        if (vec) hipLaunchKernelGGL(kernel<true>, grid, block, 0, st, __VA_ARGS__);                \
+        else hipLaunchKernelGGL(kernel<false>, grid, block, 0, st, __VA_ARGS__);                   \
+    } while (0)
+
+// The slack's constants: u = 2^-24, and n_l, the terms of a lane's chain in the norms.
+constexpr double kFlatU = 5.9604644775390625e-08;
+static double flat_lane_terms(int64_t D) { return (double)((D + 63) / 64); }
+
+// The f32 filter's two.
 static void flat_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
-    const double u = 5.9604644775390625e-08;
-    const double nl = (double)((D + 63) / 64);
+    const double u = kFlatU, nl = flat_lane_terms(D);
     *c_rel = (float)(1.05 * u * ((double)D + 3.0 * nl + 40.0));
     *c_abs = metric == ANNLITE_METRIC_EUCLIDEAN ? 1e-30f : (float)(8.0 * u);
 }
@@ -1263,18 +1234,10 @@ static int flat_launch_filter(int metric, const float *q, int64_t B, int64_t D, 
                               const uint32_t *valid, const float *qnorm, const float *thr, int32_t *cand, int32_t *cnt, hipStream_t st) {
     float c_rel, c_abs;
     flat_slack(metric, D, &c_rel, &c_abs);
-    const int64_t n_rt = (S + kFlatTile - 1) / kFlatTile;
-    const int n_qt = (int)((B + kFlatTile - 1) / kFlatTile);
-    int64_t ny = (4 * (int64_t)device_cu_count() + n_rt - 1) / n_rt;  // few row tiles: spread the query tiles too
-    ny = ny < 1 ? 1 : ny > n_qt ? n_qt : ny;
-    const dim3 grid((unsigned)n_rt, (unsigned)ny);
+    const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 4 == 0 && ((uintptr_t)q % 16 == 0) && ((uintptr_t)x % 16 == 0);
-    if (vec)
-        hipLaunchKernelGGL(flat_filter_kernel<true>, grid, dim3(256), 0, st, metric, q, (int)B, (int)D, x, norms, S, stride, valid, qnorm, thr,
-                           c_rel, c_abs, cand, cnt, kFlatCap, n_qt);
-    else
-        hipLaunchKernelGGL(flat_filter_kernel<false>, grid, dim3(256), 0, st, metric, q, (int)B, (int)D, x, norms, S, stride, valid, qnorm, thr,
-                           c_rel, c_abs, cand, cnt, kFlatCap, n_qt);
+    FLAT_LAUNCH_VEC(vec, flat_filter_kernel, g.grid, dim3(256), st, metric, q, (int)B, (int)D, x, norms, S, stride, valid, qnorm, thr, c_rel, c_abs,
+                    cand, cnt, kFlatCap, g.n_qt);
     return launch_status("flat_filter_kernel");
 }
 
@@ -1287,22 +1250,19 @@ struct FlatSplitWs {
     size_t bytes;
 };
 static FlatSplitWs flat_split_carve(void *ws, int64_t B, int64_t D) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     FlatSplitWs w;
     w.f = flat_carve(ws, B);
     w.Dp = (D + 15) / 16 * 16;
-    char *p = (char *)ws;
-    size_t o = w.f.bytes;
-    w.qh = (__bf16 *)(p + o), o += up((size_t)B * w.Dp * 2);
-    w.ql = (__bf16 *)(p + o), o += up((size_t)B * w.Dp * 2);
-    w.bytes = o;
+    WsBump b{(char *)ws, w.f.bytes};
+    w.qh = b.take<__bf16>((size_t)B * w.Dp * 2);
+    w.ql = b.take<__bf16>((size_t)B * w.Dp * 2);
+    w.bytes = b.o;
     return w;
 }
 
 // The split filter's two constants ("split filter").  u = 2^-24, Dp = 16 ceil(D / 16).
 static void flat_split_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
-    const double u = 5.9604644775390625e-08;
-    const double nl = (double)((D + 63) / 64), dp = (double)((D + 15) / 16 * 16);
+    const double u = kFlatU, nl = flat_lane_terms(D), dp = (double)((D + 15) / 16 * 16);
     *c_rel = (float)(1.05 * u * (6.6 * dp + 780.0 + 3.0 * nl + 44.0));
     *c_abs = metric == ANNLITE_METRIC_EUCLIDEAN ? 2e-30f : (float)(9.0 * u);
 }
@@ -1319,18 +1279,10 @@ static int flat_split_launch_filter(int metric, int64_t B, int64_t D, const floa
                                     int32_t *cnt, float *scores, hipStream_t st) {
     float c_rel, c_abs;
     flat_split_slack(metric, D, &c_rel, &c_abs);
-    const int64_t n_rt = (S + kFlatTile - 1) / kFlatTile;
-    const int n_qt = (int)((B + kFlatTile - 1) / kFlatTile);
-    int64_t ny = (4 * (int64_t)device_cu_count() + n_rt - 1) / n_rt;  // (flat_launch_filter's grid)
-    ny = ny < 1 ? 1 : ny > n_qt ? n_qt : ny;
-    const dim3 grid((unsigned)n_rt, (unsigned)ny);
+    const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)mu % 16 == 0);
-    if (vec)
-        hipLaunchKernelGGL(flat_split_filter_kernel<true>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, mu, norms, S,
-                           stride, valid, w.f.qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
-    else
-        hipLaunchKernelGGL(flat_split_filter_kernel<false>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, mu, norms, S,
-                           stride, valid, w.f.qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
+    FLAT_LAUNCH_VEC(vec, flat_split_filter_kernel, g.grid, dim3(256), st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, mu, norms, S, stride,
+                    valid, w.f.qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
     return launch_status("flat_split_filter_kernel");
 }
 
@@ -1343,24 +1295,21 @@ struct FlatF16Ws {
     size_t bytes;
 };
 static FlatF16Ws flat_f16_carve(void *ws, int64_t B, int64_t D) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     FlatF16Ws w;
     w.f = flat_carve(ws, B);
     w.Dp = (D + 15) / 16 * 16;
-    char *p = (char *)ws;
-    size_t o = w.f.bytes;
-    w.qh = (_Float16 *)(p + o), o += up((size_t)B * w.Dp * 2);
-    w.ql = (_Float16 *)(p + o), o += up((size_t)B * w.Dp * 2);
-    w.qscale = (float *)(p + o), o += up((size_t)B * 4);
-    w.qflush = (float *)(p + o), o += up((size_t)B * 4);
-    w.bytes = o;
+    WsBump b{(char *)ws, w.f.bytes};
+    w.qh = b.take<_Float16>((size_t)B * w.Dp * 2);
+    w.ql = b.take<_Float16>((size_t)B * w.Dp * 2);
+    w.qscale = b.take<float>((size_t)B * 4);
+    w.qflush = b.take<float>((size_t)B * 4);
+    w.bytes = b.o;
     return w;
 }
 
 // The f16 filter's two constants ("f16 rows"); the third, absolute term is per query (flat_f16_queries_kernel).
 static void flat_f16_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
-    const double u = 5.9604644775390625e-08;
-    const double nl = (double)((D + 63) / 64), dp = (double)((D + 15) / 16 * 16);
+    const double u = kFlatU, nl = flat_lane_terms(D), dp = (double)((D + 15) / 16 * 16);
     *c_rel = (float)(1.05 * u * (4.4 * dp + 16.0 + 3.0 * nl + 44.0));
     *c_abs = metric == ANNLITE_METRIC_EUCLIDEAN ? 2e-30f : (float)(9.0 * u);
 }
@@ -1376,18 +1325,10 @@ static int flat_f16_launch_filter(int metric, int64_t B, int64_t D, const _Float
                                   hipStream_t st) {
     float c_rel, c_abs;
     flat_f16_slack(metric, D, &c_rel, &c_abs);
-    const int64_t n_rt = (S + kFlatTile - 1) / kFlatTile;
-    const int n_qt = (int)((B + kFlatTile - 1) / kFlatTile);
-    int64_t ny = (4 * (int64_t)device_cu_count() + n_rt - 1) / n_rt;  // (flat_launch_filter's grid)
-    ny = ny < 1 ? 1 : ny > n_qt ? n_qt : ny;
-    const dim3 grid((unsigned)n_rt, (unsigned)ny);
+    const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 8 == 0 && ((uintptr_t)x % 16 == 0);
-    if (vec)
-        hipLaunchKernelGGL(flat_f16_filter_kernel<true>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, norms, S, stride,
-                           valid, w.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
-    else
-        hipLaunchKernelGGL(flat_f16_filter_kernel<false>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, norms, S, stride,
-                           valid, w.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
+    FLAT_LAUNCH_VEC(vec, flat_f16_filter_kernel, g.grid, dim3(256), st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, norms, S, stride, valid,
+                    w.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
     return launch_status("flat_f16_filter_kernel");
 }
 
@@ -1401,26 +1342,23 @@ struct FlatI8Ws {
     size_t bytes;
 };
 static FlatI8Ws flat_i8_carve(void *ws, int64_t B, int64_t D) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     FlatI8Ws w;
     w.f = flat_carve(ws, B);
     w.Dp = (D + 31) / 32 * 32;
-    char *p = (char *)ws;
-    size_t o = w.f.bytes;
-    w.p0 = (int8_t *)(p + o), o += up((size_t)B * w.Dp);
-    w.p1 = (int8_t *)(p + o), o += up((size_t)B * w.Dp);
-    w.p2 = (int8_t *)(p + o), o += up((size_t)B * w.Dp);
-    w.qscale = (float *)(p + o), o += up((size_t)B * 4);
-    w.qslack = (float *)(p + o), o += up((size_t)B * 4);
-    w.bytes = o;
+    WsBump b{(char *)ws, w.f.bytes};
+    w.p0 = b.take<int8_t>((size_t)B * w.Dp);
+    w.p1 = b.take<int8_t>((size_t)B * w.Dp);
+    w.p2 = b.take<int8_t>((size_t)B * w.Dp);
+    w.qscale = b.take<float>((size_t)B * 4);
+    w.qslack = b.take<float>((size_t)B * 4);
+    w.bytes = b.o;
     return w;
 }
 
 // The int8 filter's two constants ("int8 rows"); the third term is per query (flat_i8_queries_kernel).  The
 // contraction is exact, so D enters through the norms' lane chains alone.
 static void flat_i8_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
-    const double u = 5.9604644775390625e-08;
-    const double nl = (double)((D + 63) / 64);
+    const double u = kFlatU, nl = flat_lane_terms(D);
     *c_rel = (float)(1.05 * u * (3.0 * nl + 48.0));
     *c_abs = metric == ANNLITE_METRIC_EUCLIDEAN ? 3e-30f : (float)(9.0 * u);
 }
@@ -1436,18 +1374,10 @@ static int flat_i8_launch_filter(int metric, int64_t B, int64_t D, const int8_t 
                                  hipStream_t st) {
     float c_rel, c_abs;
     flat_i8_slack(metric, D, &c_rel, &c_abs);
-    const int64_t n_rt = (S + kFlatTile - 1) / kFlatTile;
-    const int n_qt = (int)((B + kFlatTile - 1) / kFlatTile);
-    int64_t ny = (4 * (int64_t)device_cu_count() + n_rt - 1) / n_rt;  // (flat_launch_filter's grid)
-    ny = ny < 1 ? 1 : ny > n_qt ? n_qt : ny;
-    const dim3 grid((unsigned)n_rt, (unsigned)ny);
+    const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 16 == 0 && ((uintptr_t)x % 16 == 0);
-    if (vec)
-        hipLaunchKernelGGL(flat_i8_filter_kernel<true>, grid, dim3(kI8Threads), 0, st, metric, w.p0, w.p1, w.p2, (int)B, (int)D, (int)w.Dp, x,
-                           norms, S, stride, valid, w.f.qnorm, w.qscale, w.qslack, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
-    else
-        hipLaunchKernelGGL(flat_i8_filter_kernel<false>, grid, dim3(kI8Threads), 0, st, metric, w.p0, w.p1, w.p2, (int)B, (int)D, (int)w.Dp, x,
-                           norms, S, stride, valid, w.f.qnorm, w.qscale, w.qslack, thr, c_rel, c_abs, cand, cnt, kFlatCap, n_qt, scores);
+    FLAT_LAUNCH_VEC(vec, flat_i8_filter_kernel, g.grid, dim3(kI8Threads), st, metric, w.p0, w.p1, w.p2, (int)B, (int)D, (int)w.Dp, x, norms, S,
+                    stride, valid, w.f.qnorm, w.qscale, w.qslack, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
     return launch_status("flat_i8_filter_kernel");
 }
 
@@ -1510,17 +1440,15 @@ struct IvfFlatWs {
     size_t bytes;
 };
 static IvfFlatWs ivf_flat_carve(void *ws, int64_t B, int64_t P, int64_t C) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     IvfFlatWs w;
     w.f = flat_carve(ws, B);
     w.n_tiles = annlite_ivf_max_tiles(B, P, C, kFlatTile);
-    char *p = (char *)ws;
-    size_t o = w.f.bytes;
-    w.tile_rows = (int64_t *)(p + o), o += up((size_t)w.n_tiles * 16);
-    w.vmap = (int32_t *)(p + o), o += up((size_t)w.n_tiles * kFlatTile * 4);
-    w.slot_of = (int32_t *)(p + o), o += up((size_t)B * P * 4);
-    w.n_used = (int32_t *)(p + o), o += 256;
-    w.bytes = o;
+    WsBump b{(char *)ws, w.f.bytes};
+    w.tile_rows = b.take<int64_t>((size_t)w.n_tiles * 16);
+    w.vmap = b.take<int32_t>((size_t)w.n_tiles * kFlatTile * 4);
+    w.slot_of = b.take<int32_t>((size_t)B * P * 4);
+    w.n_used = b.take<int32_t>(256);
+    w.bytes = b.o;
     return w;
 }
 
@@ -1551,16 +1479,11 @@ static int ivf_flat_launch_filter(int metric, const float *q, int64_t B, int64_t
                                   const uint32_t *valid, hipStream_t st) {
     float c_rel, c_abs;
     flat_slack(metric, D, &c_rel, &c_abs);
-    const int64_t n_rt = ((max_cell_rows + stride - 1) / stride + kFlatTile - 1) / kFlatTile;
-    if (n_rt <= 0 || w.n_tiles <= 0) return ANNLITE_OK;
-    const dim3 grid((unsigned)n_rt, (unsigned)(w.n_tiles < 65535 ? w.n_tiles : 65535));
+    const dim3 grid = ivf_flat_filter_grid(max_cell_rows, stride, w.n_tiles);
+    if (grid.x == 0 || grid.y == 0) return ANNLITE_OK;
     const bool vec = D % 4 == 0 && ((uintptr_t)q % 16 == 0) && ((uintptr_t)x % 16 == 0);
-    if (vec)
-        hipLaunchKernelGGL(ivf_flat_filter_kernel<true>, grid, dim3(256), 0, st, metric, q, (int)B, (int)D, x, norms, N, perm, n_perm, w.tile_rows,
-                           w.vmap, (int)w.n_tiles, stride, valid, w.f.qnorm, w.f.thr, c_rel, c_abs, w.f.cand, w.f.cnt, kFlatCap);
-    else
-        hipLaunchKernelGGL(ivf_flat_filter_kernel<false>, grid, dim3(256), 0, st, metric, q, (int)B, (int)D, x, norms, N, perm, n_perm, w.tile_rows,
-                           w.vmap, (int)w.n_tiles, stride, valid, w.f.qnorm, w.f.thr, c_rel, c_abs, w.f.cand, w.f.cnt, kFlatCap);
+    FLAT_LAUNCH_VEC(vec, ivf_flat_filter_kernel, grid, dim3(256), st, metric, q, (int)B, (int)D, x, norms, N, perm, n_perm, w.tile_rows, w.vmap,
+                    (int)w.n_tiles, stride, valid, w.f.qnorm, w.f.thr, c_rel, c_abs, w.f.cand, w.f.cnt, kFlatCap);
     return launch_status("ivf_flat_filter_kernel");
 }
 
@@ -1575,17 +1498,15 @@ struct IvfFlatSplitWs {
     size_t bytes;
 };
 static IvfFlatSplitWs ivf_flat_split_carve(void *ws, int64_t B, int64_t P, int64_t C, int64_t D) {
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     IvfFlatSplitWs w;
     w.i = ivf_flat_carve(ws, B, P, C);
     w.Dp = (D + 15) / 16 * 16;
     w.n_slots = w.i.n_tiles * kFlatTile;
-    char *p = (char *)ws;
-    size_t o = w.i.bytes;
-    w.qh = (__bf16 *)(p + o), o += up((size_t)w.n_slots * w.Dp * 2);
-    w.ql = (__bf16 *)(p + o), o += up((size_t)w.n_slots * w.Dp * 2);
-    w.qnorm = (float *)(p + o), o += up((size_t)w.n_slots * 4);
-    w.bytes = o;
+    WsBump b{(char *)ws, w.i.bytes};
+    w.qh = b.take<__bf16>((size_t)w.n_slots * w.Dp * 2);
+    w.ql = b.take<__bf16>((size_t)w.n_slots * w.Dp * 2);
+    w.qnorm = b.take<float>((size_t)w.n_slots * 4);
+    w.bytes = b.o;
     return w;
 }
 
@@ -1603,18 +1524,12 @@ static int ivf_flat_split_launch_filter(int metric, int64_t B, int64_t D, const 
                                         const float *thr, int32_t *cand, int32_t *cnt, float *scores, hipStream_t st) {
     float c_rel, c_abs;
     flat_split_slack(metric, D, &c_rel, &c_abs);
-    const int64_t n_rt = ((max_cell_rows + stride - 1) / stride + kFlatTile - 1) / kFlatTile;  // (ivf_flat_launch_filter's grid)
-    if (n_rt <= 0 || w.i.n_tiles <= 0) return ANNLITE_OK;
-    const dim3 grid((unsigned)n_rt, (unsigned)(w.i.n_tiles < 65535 ? w.i.n_tiles : 65535));
+    const dim3 grid = ivf_flat_filter_grid(max_cell_rows, stride, w.i.n_tiles);
+    if (grid.x == 0 || grid.y == 0) return ANNLITE_OK;
     const bool vec = D % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)centres % 16 == 0);
-    if (vec)
-        hipLaunchKernelGGL(ivf_flat_split_filter_kernel<true>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, centres,
-                           (int)C, cell_of, norms, N, perm, n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, valid, w.qnorm, thr, c_rel,
-                           c_abs, cand, cnt, kFlatCap, scores);
-    else
-        hipLaunchKernelGGL(ivf_flat_split_filter_kernel<false>, grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, centres,
-                           (int)C, cell_of, norms, N, perm, n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, valid, w.qnorm, thr, c_rel,
-                           c_abs, cand, cnt, kFlatCap, scores);
+    FLAT_LAUNCH_VEC(vec, ivf_flat_split_filter_kernel, grid, dim3(256), st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, centres, (int)C,
+                    cell_of, norms, N, perm, n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, valid, w.qnorm, thr, c_rel, c_abs, cand,
+                    cnt, kFlatCap, scores);
     return launch_status("ivf_flat_split_filter_kernel");
 }
 
@@ -1686,8 +1601,7 @@ extern "C" int annlite_flat_slack(int metric, int64_t D, float *c_rel, float *c_
 extern "C" int annlite_flat_filter(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, const float *norms_dev,
                                    int64_t N, int64_t stride, const uint32_t *valid_bits_dev, const float *query_norms_dev,
                                    const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev, void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= INT32_MAX, "bad shape");
+    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, INT32_MAX)) return rc;
     if (B == 0 || N == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && query_norms_dev && bounds_dev && cand_dev && count_dev, "null device pointer");
     return flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev,
@@ -1704,16 +1618,11 @@ extern "C" int annlite_flat_search_workspace_bytes(int64_t N, int64_t D, int64_t
 extern "C" int annlite_flat_search_topk(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
                                         const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
                                         float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= INT32_MAX,
-                    "bad shape (1 <= k <= 64)");
+    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, INT32_MAX)) return rc;
     if (B == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_dev && norms_dev)), "null device pointer");
     const FlatWs w = flat_carve(workspace_dev, B);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     return flat_search_staged(
         metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w, st, 1.f,
@@ -1754,17 +1663,12 @@ extern "C" int annlite_flat_filter_split(int metric, const float *queries_dev, i
                                          float *query_norms_out_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
                                          const float *centre_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes,
                                          void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
-                    "bad shape (D <= %lld)", (long long)kSplitMaxDim);
+    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
     ANNLITE_REQUIRE(!centre_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "a centre is for EUCLIDEAN only");
     if (B == 0 || N == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
     const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     int rc = flat_split_prepare(queries_dev, B, D, centre_dev, w, st);
     if (rc != ANNLITE_OK) return rc;
@@ -1778,17 +1682,12 @@ extern "C" int annlite_flat_search_topk_split(int metric, const float *queries_d
                                               const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const float *centre_dev,
                                               int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
                                               size_t workspace_bytes, void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
-                    "bad shape (1 <= k <= 64, D <= %lld)", (long long)kSplitMaxDim);
+    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
     ANNLITE_REQUIRE(!centre_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "a centre is for EUCLIDEAN only");
     if (B == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_dev && norms_dev)), "null device pointer");
     const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     return flat_search_staged(
         metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
@@ -1829,16 +1728,11 @@ extern "C" int annlite_flat_filter_f16(int metric, const float *queries_dev, int
                                        const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
                                        float *query_norms_out_dev, float *query_flush_out_dev, const float *bounds_dev, int32_t *cand_dev,
                                        int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
-                    "bad shape (D <= %lld)", (long long)kSplitMaxDim);
+    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
     if (B == 0 || N == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && vectors_f16_dev && norms_dev && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
     const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     int rc = flat_f16_prepare(queries_dev, B, D, w, st);
     if (rc != ANNLITE_OK) return rc;
@@ -1854,17 +1748,12 @@ extern "C" int annlite_flat_search_topk_f16(int metric, const float *queries_dev
                                             const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
                                             float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
                                             void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
-                    "bad shape (1 <= k <= 64, D <= %lld)", (long long)kSplitMaxDim);
+    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
     if (B == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_f16_dev && norms_dev)),
                     "null device pointer");
     const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const _Float16 *x = (const _Float16 *)vectors_f16_dev;
     return flat_search_staged(
@@ -1907,17 +1796,12 @@ extern "C" int annlite_flat_filter_i8(int metric, const float *queries_dev, int6
                                       const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
                                       float *query_norms_out_dev, float *query_slack_out_dev, const float *bounds_dev, int32_t *cand_dev,
                                       int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
-                    "bad shape (D <= %lld)", (long long)kSplitMaxDim);
+    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
     ANNLITE_REQUIRE_I8_SCALE(scale);
     if (B == 0 || N == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && vectors_i8_dev && norms_dev && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
     const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     int rc = flat_i8_prepare(queries_dev, B, D, scale, w, st);
     if (rc != ANNLITE_OK) return rc;
@@ -1933,18 +1817,13 @@ extern "C" int annlite_flat_search_topk_i8(int metric, const float *queries_dev,
                                            const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
                                            float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
                                            void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
-                    "bad shape (1 <= k <= 64, D <= %lld)", (long long)kSplitMaxDim);
+    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
     ANNLITE_REQUIRE_I8_SCALE(scale);
     if (B == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_i8_dev && norms_dev)),
                     "null device pointer");
     const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int8_t *x = (const int8_t *)vectors_i8_dev;
     return flat_search_staged(
@@ -1991,9 +1870,7 @@ extern "C" int annlite_ivf_flat_search_topk(int metric, const float *queries_dev
                                             const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t max_probed_rows, int64_t k,
                                             int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
                                             size_t workspace_bytes, void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= INT32_MAX,
-                    "bad shape (1 <= k <= 64)");
+    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, INT32_MAX)) return rc;
     ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
                         max_cell_rows <= n_perm && max_probed_rows >= 0,
                     "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld max_probed_rows=%lld", (long long)P, (long long)C,
@@ -2003,10 +1880,7 @@ extern "C" int annlite_ivf_flat_search_topk(int metric, const float *queries_dev
                         (n_perm == 0 || (vectors_dev && norms_dev && perm_dev)),
                     "null device pointer");
     const IvfFlatWs w = ivf_flat_carve(workspace_dev, B, P, C);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     return ivf_flat_search_staged(
         metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev, cell_order_dev,
@@ -2045,9 +1919,7 @@ extern "C" int annlite_ivf_flat_filter_split(int metric, const float *queries_de
                                              const int32_t *cell_of_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
                                              float *pair_norms_out_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes,
                                              void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && stride >= 1 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
-                    "bad shape (D <= %lld)", (long long)kSplitMaxDim);
+    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
     ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && B * P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
                         max_cell_rows <= n_perm,
                     "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld", (long long)P, (long long)C, (long long)n_perm,
@@ -2059,10 +1931,7 @@ extern "C" int annlite_ivf_flat_filter_split(int metric, const float *queries_de
                         cand_dev && count_dev && workspace_dev,
                     "null device pointer");
     const IvfFlatSplitWs w = ivf_flat_split_carve(workspace_dev, B, P, C, D);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     int rc = annlite_ivf_plan(cells_dev, B, P, C, kFlatTile, cell_rows_dev, cell_order_dev, w.i.n_tiles, w.i.vmap, w.i.slot_of, w.i.tile_rows,
                               w.i.n_used, stream);
@@ -2079,9 +1948,7 @@ extern "C" int annlite_ivf_flat_search_topk_split(int metric, const float *queri
                                                   int64_t max_probed_rows, const float *centres_dev, const int32_t *cell_of_dev, int64_t k,
                                                   int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
                                                   size_t workspace_bytes, void *stream) {
-    ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    ANNLITE_REQUIRE(B >= 0 && D >= 1 && N >= 0 && k >= 1 && k <= 64 && N <= INT32_MAX && B <= INT32_MAX && D <= kSplitMaxDim,
-                    "bad shape (1 <= k <= 64, D <= %lld)", (long long)kSplitMaxDim);
+    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
     ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && B * P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
                         max_cell_rows <= n_perm && max_probed_rows >= 0,
                     "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld max_probed_rows=%lld", (long long)P, (long long)C,
@@ -2093,10 +1960,7 @@ extern "C" int annlite_ivf_flat_search_topk_split(int metric, const float *queri
                         (n_perm == 0 || (vectors_dev && norms_dev && perm_dev)),
                     "null device pointer");
     const IvfFlatSplitWs w = ivf_flat_split_carve(workspace_dev, B, P, C, D);
-    if (workspace_bytes < w.bytes) {
-        set_error("workspace too small: %zu < %zu bytes", workspace_bytes, w.bytes);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     return ivf_flat_search_staged(
         metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev, cell_order_dev,

@@ -795,11 +795,67 @@ def flat_list_capacity() -> int:
     return int(lib().annlite_flat_list_capacity())
 
 
+def _flat_slack(entry: str, metric: int, dim: int) -> Tuple[np.float32, np.float32]:
+    """the ``(c_rel, c_abs)`` pair of the C entry ``annlite_<entry>``"""
+    c_rel, c_abs = ctypes.c_float(0), ctypes.c_float(0)
+    check(getattr(lib(), 'annlite_' + entry)(int(metric), int(dim), ctypes.byref(c_rel), ctypes.byref(c_abs)), entry)
+    return np.float32(c_rel.value), np.float32(c_abs.value)
+
+
+def _flat_workspace(entry: str, shape: Tuple[int, ...], dev, workspace: Optional[ScanWorkspace]) -> torch.Tensor:
+    """this stream's buffer of ``workspace`` (of a throw-away one without), sized by the C entry ``annlite_<entry>(*shape, &bytes)``"""
+    need = ctypes.c_int64(0)
+    check(getattr(lib(), 'annlite_' + entry)(*shape, ctypes.byref(need)), entry)
+    return (workspace or ScanWorkspace()).get(int(need.value), dev)
+
+
+def _flat_topk_outputs(B: int, k: int, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    return torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.int64, device=dev)
+
+
+def _flat_lists(B: int, dev, score_cols: Optional[int] = None):
+    """``(cand i32 [B, cap], count i32 [B] of zeros, scores)`` -- scores f32 [B, score_cols] of NaN, or None without ``score_cols``"""
+    cand = torch.empty((B, flat_list_capacity()), dtype=torch.int32, device=dev)
+    count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    sc = None if score_cols is None else torch.full((B, score_cols), float('nan'), dtype=torch.float32, device=dev)
+    return cand, count, sc
+
+
+def _flat_filter_stage(entry: str, ws_entry: str, metric: int, queries, vectors, norms, bounds, valid_bits, n_rows, stride: int, scores: bool,
+                       workspace, n_query_outputs: int, after_vectors=(), after_count=()):
+    """One filter stage over the table through ``annlite_<entry>``: ``(cand, count, *per-query f32 [B] outputs[, scores])``.  The
+    entries differ in what follows the vectors (int8: the scale), in how many per-query outputs they have and in what follows the
+    count (split: the centre)."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    ws = _flat_workspace(ws_entry, (N, D, B, 1), dev, workspace)
+    cand, count, sc = _flat_lists(B, dev, (N + stride - 1) // stride if scores else None)
+    outs = [torch.empty((B,), dtype=torch.float32, device=dev) for _ in range(n_query_outputs)]
+    check(getattr(lib(), 'annlite_' + entry)(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), *after_vectors, norms.data_ptr(), N, stride,
+                                             _ptr(valid_bits), *[o.data_ptr() for o in outs], bounds.data_ptr(), cand.data_ptr(),
+                                             count.data_ptr(), *after_count, _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()), entry)
+    return (cand, count, *outs, sc) if scores else (cand, count, *outs)
+
+
+def _flat_search(entry: str, ws_entry: str, metric: int, queries, vectors, norms, k: int, valid_bits, n_rows, sqrt: bool, workspace,
+                 after_vectors=(), after_valid=()) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A search over the table through ``annlite_<entry>``; the entries differ in what follows the vectors (int8: the scale) and the
+    bitmap (split: the centre)."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    ws = _flat_workspace(ws_entry, (N, D, B, k), dev, workspace)
+    od, oi = _flat_topk_outputs(B, k, dev)
+    check(getattr(lib(), 'annlite_' + entry)(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), *after_vectors, norms.data_ptr(), N,
+                                             _ptr(valid_bits), *after_valid, int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), stream_ptr()), entry)
+    return od, oi
+
+
 def flat_slack(metric: int, dim: int) -> Tuple[np.float32, np.float32]:
     """``annlite_flat_slack``: the ``(c_rel, c_abs)`` the filter kernel is launched with (host only, needs no GPU)."""
-    c_rel, c_abs = ctypes.c_float(0), ctypes.c_float(0)
-    check(lib().annlite_flat_slack(int(metric), int(dim), ctypes.byref(c_rel), ctypes.byref(c_abs)), 'flat_slack')
-    return np.float32(c_rel.value), np.float32(c_abs.value)
+    return _flat_slack('flat_slack', metric, dim)
 
 
 def flat_filter(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
@@ -809,11 +865,9 @@ def flat_filter(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms
     ``bounds`` f32 [B] of each query; ``count > cap`` marks an overflowed list."""
     B, D = queries.shape
     N = vectors.shape[0] if n_rows is None else n_rows
-    cap = flat_list_capacity()
     if query_norms is None:
         query_norms = flat_row_norms(queries)
-    cand = torch.empty((B, cap), dtype=torch.int32, device=queries.device)
-    count = torch.zeros((B,), dtype=torch.int32, device=queries.device)
+    cand, count, _ = _flat_lists(B, queries.device)
     check(lib().annlite_flat_filter(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, stride, _ptr(valid_bits),
                                     query_norms.data_ptr(), bounds.data_ptr(), cand.data_ptr(), count.data_ptr(), stream_ptr()), 'flat_filter')
     return cand, count
@@ -824,18 +878,7 @@ def flat_search_topk(metric: int, queries: torch.Tensor, vectors: torch.Tensor, 
                      workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``annlite_flat_search_topk``: exact k nearest rows (k <= 64), ``(dist f32 [B, k], ids i64 [B, k])`` ascending by
     (distance, id), (+inf, -1) padded.  ``flat_overflow_count(workspace)`` reads the call's overflow counter afterwards."""
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    need = ctypes.c_int64(0)
-    check(lib().annlite_flat_search_workspace_bytes(N, D, B, k, ctypes.byref(need)), 'flat_search_workspace_bytes')
-    dev = queries.device
-    ws = (workspace or ScanWorkspace()).get(int(need.value), dev)
-    od = torch.empty((B, k), dtype=torch.float32, device=dev)
-    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
-    check(lib().annlite_flat_search_topk(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
-                                         int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()),
-          'flat_search_topk')
-    return od, oi
+    return _flat_search('flat_search_topk', 'flat_search_workspace_bytes', metric, queries, vectors, norms, k, valid_bits, n_rows, sqrt, workspace)
 
 
 def flat_overflow_count(workspace: ScanWorkspace) -> int:
@@ -859,9 +902,7 @@ def flat_list_counts(workspace: ScanWorkspace, B: int) -> torch.Tensor:
 
 def flat_split_slack(metric: int, dim: int) -> Tuple[np.float32, np.float32]:
     """``annlite_flat_split_slack``: the ``(c_rel, c_abs)`` the split filter kernel is launched with (host only, needs no GPU)."""
-    c_rel, c_abs = ctypes.c_float(0), ctypes.c_float(0)
-    check(lib().annlite_flat_split_slack(int(metric), int(dim), ctypes.byref(c_rel), ctypes.byref(c_abs)), 'flat_split_slack')
-    return np.float32(c_rel.value), np.float32(c_abs.value)
+    return _flat_slack('flat_split_slack', metric, dim)
 
 
 def flat_centred_norms(vectors: torch.Tensor, centre: torch.Tensor, ids: Optional[torch.Tensor] = None, n: Optional[int] = None,
@@ -878,12 +919,6 @@ def flat_centred_norms(vectors: torch.Tensor, centre: torch.Tensor, ids: Optiona
     return out
 
 
-def _flat_split_workspace(N: int, D: int, B: int, k: int, dev, workspace: Optional[ScanWorkspace]) -> torch.Tensor:
-    need = ctypes.c_int64(0)
-    check(lib().annlite_flat_search_split_workspace_bytes(N, D, B, k, ctypes.byref(need)), 'flat_search_split_workspace_bytes')
-    return (workspace or ScanWorkspace()).get(int(need.value), dev)
-
-
 def flat_filter_split(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
                       centre: Optional[torch.Tensor] = None, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
                       stride: int = 1, scores: bool = False, workspace: Optional[ScanWorkspace] = None):
@@ -891,19 +926,8 @@ def flat_filter_split(metric: int, queries: torch.Tensor, vectors: torch.Tensor,
     ``flat_centred_norms`` with the same centre (``flat_row_norms`` without one).  ``(cand i32 [B, cap], count i32 [B],
     query_norms f32 [B])`` -- the last as the filter used them -- and, with ``scores=True``, the filter's score of every
     (query, stage row) pair, f32 [B, ceil(N / stride)]."""
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    cap = flat_list_capacity()
-    dev = queries.device
-    ws = _flat_split_workspace(N, D, B, 1, dev, workspace)
-    cand = torch.empty((B, cap), dtype=torch.int32, device=dev)
-    count = torch.zeros((B,), dtype=torch.int32, device=dev)
-    qn = torch.empty((B,), dtype=torch.float32, device=dev)
-    sc = torch.full((B, (N + stride - 1) // stride), float('nan'), dtype=torch.float32, device=dev) if scores else None
-    check(lib().annlite_flat_filter_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, stride,
-                                          _ptr(valid_bits), qn.data_ptr(), bounds.data_ptr(), cand.data_ptr(), count.data_ptr(),
-                                          _ptr(centre), _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_filter_split')
-    return (cand, count, qn, sc) if scores else (cand, count, qn)
+    return _flat_filter_stage('flat_filter_split', 'flat_search_split_workspace_bytes', metric, queries, vectors, norms, bounds, valid_bits,
+                              n_rows, stride, scores, workspace, 1, after_count=(_ptr(centre),))
 
 
 def flat_search_topk_split(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, k: int,
@@ -912,16 +936,8 @@ def flat_search_topk_split(metric: int, queries: torch.Tensor, vectors: torch.Te
                            workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``annlite_flat_search_topk_split``: ``flat_search_topk`` with the split-bf16 filter (``norms``: see ``flat_filter_split``);
     the same answer, bit for bit.  ``flat_overflow_count`` / ``flat_list_counts`` read this workspace too."""
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    ws = _flat_split_workspace(N, D, B, k, dev, workspace)
-    od = torch.empty((B, k), dtype=torch.float32, device=dev)
-    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
-    check(lib().annlite_flat_search_topk_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N,
-                                               _ptr(valid_bits), _ptr(centre), int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
-                                               ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_search_topk_split')
-    return od, oi
+    return _flat_search('flat_search_topk_split', 'flat_search_split_workspace_bytes', metric, queries, vectors, norms, k, valid_bits, n_rows,
+                        sqrt, workspace, after_valid=(_ptr(centre),))
 
 
 # ---------------------------------------------------------------------------------------------- exact search over f16 rows
@@ -952,15 +968,7 @@ def flat_row_norms_f16(vectors: torch.Tensor, ids: Optional[torch.Tensor] = None
 
 def flat_f16_slack(metric: int, dim: int) -> Tuple[np.float32, np.float32]:
     """``annlite_flat_f16_slack``: the ``(c_rel, c_abs)`` the f16 filter kernel is launched with (host only, needs no GPU)."""
-    c_rel, c_abs = ctypes.c_float(0), ctypes.c_float(0)
-    check(lib().annlite_flat_f16_slack(int(metric), int(dim), ctypes.byref(c_rel), ctypes.byref(c_abs)), 'flat_f16_slack')
-    return np.float32(c_rel.value), np.float32(c_abs.value)
-
-
-def _flat_f16_workspace(N: int, D: int, B: int, k: int, dev, workspace: Optional[ScanWorkspace]) -> torch.Tensor:
-    need = ctypes.c_int64(0)
-    check(lib().annlite_flat_search_f16_workspace_bytes(N, D, B, k, ctypes.byref(need)), 'flat_search_f16_workspace_bytes')
-    return (workspace or ScanWorkspace()).get(int(need.value), dev)
+    return _flat_slack('flat_f16_slack', metric, dim)
 
 
 def flat_filter_f16(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
@@ -971,20 +979,8 @@ def flat_filter_f16(metric: int, queries: torch.Tensor, vectors: torch.Tensor, n
     ``|q|^2`` and the per-query term of the slack -- and, with ``scores=True``, the filter's score of every (query, stage row)
     pair, f32 [B, ceil(N / stride)]."""
     assert vectors.dtype == torch.float16
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    cap = flat_list_capacity()
-    dev = queries.device
-    ws = _flat_f16_workspace(N, D, B, 1, dev, workspace)
-    cand = torch.empty((B, cap), dtype=torch.int32, device=dev)
-    count = torch.zeros((B,), dtype=torch.int32, device=dev)
-    qn = torch.empty((B,), dtype=torch.float32, device=dev)
-    qf = torch.empty((B,), dtype=torch.float32, device=dev)
-    sc = torch.full((B, (N + stride - 1) // stride), float('nan'), dtype=torch.float32, device=dev) if scores else None
-    check(lib().annlite_flat_filter_f16(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, stride,
-                                        _ptr(valid_bits), qn.data_ptr(), qf.data_ptr(), bounds.data_ptr(), cand.data_ptr(),
-                                        count.data_ptr(), _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_filter_f16')
-    return (cand, count, qn, qf, sc) if scores else (cand, count, qn, qf)
+    return _flat_filter_stage('flat_filter_f16', 'flat_search_f16_workspace_bytes', metric, queries, vectors, norms, bounds, valid_bits, n_rows,
+                              stride, scores, workspace, 2)
 
 
 def flat_search_topk_f16(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, k: int,
@@ -994,16 +990,8 @@ def flat_search_topk_f16(metric: int, queries: torch.Tensor, vectors: torch.Tens
     answer of ``flat_search_topk`` over the widened rows, bit for bit.  ``flat_overflow_count`` / ``flat_list_counts`` read this
     workspace too."""
     assert vectors.dtype == torch.float16
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    ws = _flat_f16_workspace(N, D, B, k, dev, workspace)
-    od = torch.empty((B, k), dtype=torch.float32, device=dev)
-    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
-    check(lib().annlite_flat_search_topk_f16(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N,
-                                             _ptr(valid_bits), int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
-                                             ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_search_topk_f16')
-    return od, oi
+    return _flat_search('flat_search_topk_f16', 'flat_search_f16_workspace_bytes', metric, queries, vectors, norms, k, valid_bits, n_rows, sqrt,
+                        workspace)
 
 
 # ---------------------------------------------------------------------------------------------- exact search over int8 rows
@@ -1034,15 +1022,7 @@ def flat_row_norms_i8(vectors: torch.Tensor, scale: float, ids: Optional[torch.T
 
 def flat_i8_slack(metric: int, dim: int) -> Tuple[np.float32, np.float32]:
     """``annlite_flat_i8_slack``: the ``(c_rel, c_abs)`` the int8 filter kernel is launched with (host only, needs no GPU)."""
-    c_rel, c_abs = ctypes.c_float(0), ctypes.c_float(0)
-    check(lib().annlite_flat_i8_slack(int(metric), int(dim), ctypes.byref(c_rel), ctypes.byref(c_abs)), 'flat_i8_slack')
-    return np.float32(c_rel.value), np.float32(c_abs.value)
-
-
-def _flat_i8_workspace(N: int, D: int, B: int, k: int, dev, workspace: Optional[ScanWorkspace]) -> torch.Tensor:
-    need = ctypes.c_int64(0)
-    check(lib().annlite_flat_search_i8_workspace_bytes(N, D, B, k, ctypes.byref(need)), 'flat_search_i8_workspace_bytes')
-    return (workspace or ScanWorkspace()).get(int(need.value), dev)
+    return _flat_slack('flat_i8_slack', metric, dim)
 
 
 def flat_filter_i8(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor, scale: float,
@@ -1053,20 +1033,8 @@ def flat_filter_i8(metric: int, queries: torch.Tensor, vectors: torch.Tensor, no
     the last two as the filter used them: ``|q|^2`` and the per-query term of the slack -- and, with ``scores=True``, the filter's
     score of every (query, stage row) pair, f32 [B, ceil(N / stride)]."""
     assert vectors.dtype == torch.int8
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    cap = flat_list_capacity()
-    dev = queries.device
-    ws = _flat_i8_workspace(N, D, B, 1, dev, workspace)
-    cand = torch.empty((B, cap), dtype=torch.int32, device=dev)
-    count = torch.zeros((B,), dtype=torch.int32, device=dev)
-    qn = torch.empty((B,), dtype=torch.float32, device=dev)
-    qs = torch.empty((B,), dtype=torch.float32, device=dev)
-    sc = torch.full((B, (N + stride - 1) // stride), float('nan'), dtype=torch.float32, device=dev) if scores else None
-    check(lib().annlite_flat_filter_i8(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(), N, stride,
-                                       _ptr(valid_bits), qn.data_ptr(), qs.data_ptr(), bounds.data_ptr(), cand.data_ptr(),
-                                       count.data_ptr(), _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_filter_i8')
-    return (cand, count, qn, qs, sc) if scores else (cand, count, qn, qs)
+    return _flat_filter_stage('flat_filter_i8', 'flat_search_i8_workspace_bytes', metric, queries, vectors, norms, bounds, valid_bits, n_rows,
+                              stride, scores, workspace, 2, after_vectors=(float(scale),))
 
 
 def flat_search_topk_i8(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, k: int, scale: float,
@@ -1076,16 +1044,8 @@ def flat_search_topk_i8(metric: int, queries: torch.Tensor, vectors: torch.Tenso
     ``flat_row_norms_i8``): the answer of ``flat_search_topk`` over those f32 rows, bit for bit.  ``flat_overflow_count`` /
     ``flat_list_counts`` read this workspace too."""
     assert vectors.dtype == torch.int8
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    ws = _flat_i8_workspace(N, D, B, k, dev, workspace)
-    od = torch.empty((B, k), dtype=torch.float32, device=dev)
-    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
-    check(lib().annlite_flat_search_topk_i8(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(), N,
-                                            _ptr(valid_bits), int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
-                                            ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_search_topk_i8')
-    return od, oi
+    return _flat_search('flat_search_topk_i8', 'flat_search_i8_workspace_bytes', metric, queries, vectors, norms, k, valid_bits, n_rows, sqrt,
+                        workspace, after_vectors=(float(scale),))
 
 
 # ---------------------------------------------------------------------------------------------- cells over float vectors
@@ -1109,12 +1069,9 @@ def ivf_flat_search_topk(metric: int, queries: torch.Tensor, vectors: torch.Tens
     B, D = queries.shape
     P = cells.shape[1]
     N = vectors.shape[0] if n_rows is None else n_rows
-    need = ctypes.c_int64(0)
-    check(lib().annlite_ivf_flat_search_workspace_bytes(B, P, n_cells, k, ctypes.byref(need)), 'ivf_flat_search_workspace_bytes')
     dev = queries.device
-    ws = (workspace or ScanWorkspace()).get(int(need.value), dev)
-    od = torch.empty((B, k), dtype=torch.float32, device=dev)
-    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
+    ws = _flat_workspace('ivf_flat_search_workspace_bytes', (B, P, n_cells, k), dev, workspace)
+    od, oi = _flat_topk_outputs(B, k, dev)
     check(lib().annlite_ivf_flat_search_topk(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
                                              cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
                                              cell_order.data_ptr(), int(max_cell_rows), int(max_probed_rows), int(k), 1 if sqrt else 0,
@@ -1138,13 +1095,6 @@ def ivf_flat_centred_norms(vectors: torch.Tensor, centres: torch.Tensor, cell_of
     return out
 
 
-def _ivf_flat_split_workspace(B: int, P: int, n_cells: int, D: int, k: int, dev, workspace: Optional[ScanWorkspace]) -> torch.Tensor:
-    need = ctypes.c_int64(0)
-    check(lib().annlite_ivf_flat_search_split_workspace_bytes(B, P, n_cells, D, k, ctypes.byref(need)),
-          'ivf_flat_search_split_workspace_bytes')
-    return (workspace or ScanWorkspace()).get(int(need.value), dev)
-
-
 def ivf_flat_filter_split(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
                           cells: torch.Tensor, n_cells: int, perm: torch.Tensor, cell_rows: torch.Tensor, cell_order: torch.Tensor,
                           max_cell_rows: int, centres: Optional[torch.Tensor] = None, cell_of: Optional[torch.Tensor] = None,
@@ -1157,13 +1107,10 @@ def ivf_flat_filter_split(metric: int, queries: torch.Tensor, vectors: torch.Ten
     B, D = queries.shape
     P = cells.shape[1]
     N = vectors.shape[0] if n_rows is None else n_rows
-    cap = flat_list_capacity()
     dev = queries.device
-    ws = _ivf_flat_split_workspace(B, P, n_cells, D, 1, dev, workspace)
-    cand = torch.empty((B, cap), dtype=torch.int32, device=dev)
-    count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    ws = _flat_workspace('ivf_flat_search_split_workspace_bytes', (B, P, n_cells, D, 1), dev, workspace)
+    cand, count, sc = _flat_lists(B, dev, N if scores else None)
     pn = torch.empty((B, P), dtype=torch.float32, device=dev)
-    sc = torch.full((B, N), float('nan'), dtype=torch.float32, device=dev) if scores else None
     check(lib().annlite_ivf_flat_filter_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
                                               cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
                                               cell_order.data_ptr(), int(max_cell_rows), int(stride), _ptr(centres), _ptr(cell_of),
@@ -1185,9 +1132,8 @@ def ivf_flat_search_topk_split(metric: int, queries: torch.Tensor, vectors: torc
     P = cells.shape[1]
     N = vectors.shape[0] if n_rows is None else n_rows
     dev = queries.device
-    ws = _ivf_flat_split_workspace(B, P, n_cells, D, k, dev, workspace)
-    od = torch.empty((B, k), dtype=torch.float32, device=dev)
-    oi = torch.empty((B, k), dtype=torch.int64, device=dev)
+    ws = _flat_workspace('ivf_flat_search_split_workspace_bytes', (B, P, n_cells, D, k), dev, workspace)
+    od, oi = _flat_topk_outputs(B, k, dev)
     check(lib().annlite_ivf_flat_search_topk_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N,
                                                    _ptr(valid_bits), cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(),
                                                    cell_rows.data_ptr(), cell_order.data_ptr(), int(max_cell_rows), int(max_probed_rows),
