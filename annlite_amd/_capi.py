@@ -138,7 +138,38 @@ SYMBOLS = (
     'annlite_affine_rows',
     'annlite_pca_accumulate_workspace_bytes',
     'annlite_pca_accumulate',
+    'annlite_filter_eval',
 )
+
+# filterable columns (include/annlite_hip.h: ANNLITE_FILTER_* / ANNLITE_COL_*)
+FILTER_MAX_LEAVES, FILTER_MAX_LITERALS, FILTER_MAX_CODE, FILTER_MAX_STACK, FILTER_MAX_BLOCKS = 32, 64, 128, 32, 2048
+COL_I64, COL_F64, COL_CODE = 0, 1, 2
+
+
+class FilterLeaf(ctypes.Structure):
+    _fields_ = [
+        ('values_dev', ctypes.c_void_p),
+        ('present_dev', ctypes.c_void_p),
+        ('set_bits_dev', ctypes.c_void_p),
+        ('kind', ctypes.c_uint8),
+        ('op', ctypes.c_uint8),
+        ('lit_begin', ctypes.c_uint8),
+        ('lit_count', ctypes.c_uint8),
+        ('set_words', ctypes.c_uint32),
+    ]
+
+
+class FilterProgram(ctypes.Structure):
+    """``annlite_filter_program``: built on the host, handed to ``annlite_filter_eval`` by pointer, to its kernel by value"""
+    _fields_ = [
+        ('n_leaves', ctypes.c_int32),
+        ('n_literals', ctypes.c_int32),
+        ('n_code', ctypes.c_int32),
+        ('reserved', ctypes.c_int32),
+        ('leaves', FilterLeaf * FILTER_MAX_LEAVES),
+        ('literals', ctypes.c_uint64 * FILTER_MAX_LITERALS),
+        ('code', ctypes.c_uint8 * FILTER_MAX_CODE),
+    ]
 
 
 class ScanPlan(ctypes.Structure):
@@ -292,6 +323,7 @@ def lib() -> ctypes.CDLL:
     L.annlite_affine_rows.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, vp, i64, vp]
     L.annlite_pca_accumulate_workspace_bytes.argtypes = [i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_pca_accumulate.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]
+    L.annlite_filter_eval.argtypes = [ctypes.POINTER(FilterProgram), i64, vp, vp, i64, vp, i32, vp]
     L.annlite_graph_search_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_graph_search_stats_ex.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     for name in SYMBOLS:

@@ -33,6 +33,7 @@ import torch
 
 from ... import ops
 from ..._capi import CODES_SKEWED, LUT_IPDIST, LUT_L2, scan_plan, scan_plan_tiles
+from ...columns import RowMask
 from ...enums import Metric
 from ..codec.pq import PQCodec
 from ..codec.vq import VQCodec
@@ -153,6 +154,11 @@ class IvfPQGpuIndex(CellColumnMixin, PQFlatGpuIndex):
         """``indices`` filter (offsets) as a bitmap over TABLE rows; None = every stored row."""
         if indices is None:
             return None  # the cell ranges hold live rows only; padding lies outside every range
+        if isinstance(indices, RowMask):  # (a filter evaluated on the device: its flags gathered through the table's row ids)
+            sel = torch.zeros((((self._n_table + 31) // 32 + 2) * 32,), dtype=torch.bool, device=self._row_ids.device)
+            flags = indices.flags(max(self._n_rows, 1))
+            sel[: self._n_table] = (self._row_ids >= 0) & flags[self._row_ids.clamp(0, flags.numel() - 1)]
+            return self._pack_bits(sel)
         idx = self._ids_to_dev(indices)
         idx = idx[(idx >= 0) & (idx < self._pos_of.numel())]
         pos = self._pos_of[idx]

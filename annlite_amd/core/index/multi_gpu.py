@@ -154,6 +154,8 @@ class MultiGpuPQIndex(BaseIndex):
     def _split_filter(self, indices):
         if indices is None:
             return [None] * self.n_shards
+        if hasattr(indices, 'offsets'):  # (a RowMask, columns.py: its rows live on one device; the shards take offsets)
+            indices = indices.offsets()
         sh, loc = self.shard_of(np.asarray(indices, dtype=np.int64))
         return [loc[sh == g] for g in range(self.n_shards)]
 

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from ... import ops
+from ...columns import RowMask
 from ...enums import Metric
 from ...math import l2_normalize_host
 from .base import BaseIndex, drop_hnsw_kwargs
@@ -178,7 +179,10 @@ class RowStoreIndex(BaseIndex):
         self._valid_bits_cache = None
 
     def _filter_bits(self, indices) -> torch.Tensor:
-        """`indices` argument of search (flat_index.py:24-27, pq_index.py:42-44, container.py:107-120): restrict to a subset."""
+        """`indices` argument of search (flat_index.py:24-27, pq_index.py:42-44, container.py:107-120): restrict to a subset.
+        Offsets, or a ``RowMask`` (a filter evaluated on the device, columns.py): its words are the subset already."""
+        if isinstance(indices, RowMask):
+            return indices.words_for(self._valid.numel()) & self._valid
         sel = torch.zeros_like(self._valid_bool)
         sel[self._ids_to_dev(indices)] = True
         return self._pack_bits(sel & self._valid_bool)

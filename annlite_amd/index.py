@@ -40,7 +40,10 @@ through the projector's state after that batch -- a caller who wants them traine
 
 Out of scope of this tier: RocksDB/SQLite
 persistence of documents, remote backup.  Documents and tags live in memory; the Mongo-style ``filter`` dict is
-evaluated on the host and handed to the GPU scan as a row bitmap (section 8f-3).
+evaluated on the host and handed to the GPU scan as a row bitmap (section 8f-3) -- unless it names declared ``columns`` only:
+those are kept as typed device arrays beside the vectors (``ColumnStore``, columns.py), the filter compiles to a predicate program
+and ONE kernel evaluates it into the bitmap the indexes read (``annlite_filter_eval``).  The rows selected
+are the same; ``filter_eval='host'`` keeps the host path, ``last_filter_eval`` says which one answered.
 """
 import hashlib
 import logging
@@ -54,6 +57,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .columns import ColumnStore, RowMask
 from .core.codec.pq import PQCodec
 from .core.index.pq_flat_gpu import PQFlatGpuIndex
 from .enums import Metric
@@ -108,6 +112,12 @@ class AnnLite:
         channel; default 1.0, ``2**-7`` for cosine) rides the same way: ``FlatGpuIndex`` then stores int8 codes -- a quarter of the HBM,
         the answer of the f32 index over the rows ``int8_scale * code`` bit for bit, its own filter ``'i8x3'``; the float graph and
         the cells over floats raise ``NotImplementedError``, the indexes over PQ codes drop both keywords
+    :param columns: ``[(name, type), ...]`` (or ``filterable_attrs={name: type}``): the tags a filter may name and have evaluated on
+        the device -- ``int`` / ``bool``, ``float`` and ``str`` columns (``ColumnStore``); tags that are not declared stay filterable
+        on the host, as before
+    :param filter_eval: ``'auto'`` (default; kwarg): a filter that compiles over the declared columns is evaluated by
+        ``annlite_filter_eval``, any other by ``filter.select``; ``'host'``: ``filter.select`` always.  ``last_filter_eval`` reports
+        ``'gpu'`` / ``'host'`` for the last filter (``None`` before the first)
     """
 
     def __init__(
@@ -218,6 +228,13 @@ class AnnLite:
         if columns is not None:
             filterable_attrs = {n: t for n, t in (columns.items() if isinstance(columns, dict) else columns)}
         self.filterable_attrs = filterable_attrs or {}
+        # the declared columns as device arrays of the row range (columns.py; nothing is allocated before the first rows arrive).
+        # filter_eval='auto': a filter that compiles over them is evaluated on the device; 'host': `filter.select`, always
+        self.filter_eval = kwargs.pop('filter_eval', 'auto')
+        if self.filter_eval not in ('auto', 'host'):
+            raise ValueError(f"filter_eval={self.filter_eval!r}: 'auto' (the device where the filter compiles) or 'host'")
+        self._columns = ColumnStore(self.filterable_attrs)
+        self.last_filter_eval = None  # 'gpu' / 'host': what evaluated the last filter (None: no filter yet)
 
         self._index_kwargs = dict(initial_size=initial_size, expand_step_size=expand_step_size, **kwargs)
         self._vec_indexes = [self._new_index()]
@@ -449,6 +466,8 @@ class AnnLite:
         with open(snap / 'cell_0.db', 'rb') as f:
             st = pickle.load(f)
         self._offset2id, self._tags, self._docs, self._tomb = st['offset2id'], st['tags'], st['docs'], {}
+        self._columns.clear()  # (the columns are not part of the snapshot: refilled from the restored tags)
+        self._columns.append(self._tags)
         self._offset2int = None
         self._id2offset = {d: o for o, d in enumerate(self._offset2id) if d is not None}
 
@@ -494,6 +513,8 @@ class AnnLite:
             self._offset2id.append(d.id)
             self._tags.append(dict(d.tags) if getattr(d, 'tags', None) else {})
             self._docs[d.id] = d
+        if self._columns.kinds:
+            self._columns.append(self._tags[first:])
 
     def update(self, docs, raise_errors_on_not_found: bool = False, insert_if_not_found: bool = True, **kwargs):
         """index.py:297-332: delete + re-insert under a fresh offset (container.py:323-375)."""
@@ -540,19 +561,29 @@ class AnnLite:
             offs.append(off)
         if offs:
             self.vec_index(0).delete(offs)
+            self._columns.drop(offs)
 
     def clear(self):
         self.vec_index(0).reset()
         self._offset2id, self._id2offset, self._tags, self._docs, self._tomb = [], {}, [], {}, {}
         self._offset2int = None
+        self._columns.clear()
 
     def close(self):
         pass
 
     # ------------------------------------------------------------------ search
     def _filter_offsets(self, filter: Optional[dict]):
+        """The rows a filter selects: a ``RowMask`` where the filter compiles over the declared columns (evaluated on the device), else
+        the offsets ``filter.select`` finds (None: no filter).  The same rows either way."""
         if not filter:
             return None
+        if self.filter_eval == 'auto' and len(self._columns) > 0:
+            program = self._columns.compile(filter)
+            if program is not None:
+                self.last_filter_eval = 'gpu'
+                return self._columns.evaluate(program)
+        self.last_filter_eval = 'host'
         return np.asarray(_filter_select(self._tags, filter), dtype=np.int64)
 
     def _search_arrays(self, query_np, filter, limit):
@@ -672,7 +703,11 @@ class AnnLite:
                ascending: bool = True, include_metadata: bool = True):
         """index.py:389-423 -> CellContainer.filter_cells (container.py:146-199): the documents whose tags satisfy
         the filter, in insertion order or ordered by a tag, ``offset`` skipped, at most ``limit`` (<= 0: all)."""
-        offs = _filter_select(self._tags, filter or {})
+        sel = self._filter_offsets(filter)
+        if sel is None:  # (no filter: every live row)
+            offs = _filter_select(self._tags, {})
+        else:
+            offs = (sel.offsets() if isinstance(sel, RowMask) else sel).tolist()  # (ascending either way)
         if order_by:
             # documents without the tag sort as NULLs do in the reference's SQL ORDER BY (SQLite: NULLs first ascending,
             # last descending) instead of raising on a None comparison

@@ -1187,3 +1187,25 @@ def pca_accumulate(x: torch.Tensor, shift: torch.Tensor, sum64: torch.Tensor, gr
 def pca_chunk_rows() -> int:
     """Rows of one partial product of ``pca_accumulate`` (a compile-time constant of the library)."""
     return 512
+
+
+# ---------------------------------------------------------------------------------------------- filterable columns
+def filter_eval(program: '_capi.FilterProgram', n_rows: int, n_words: int, and_bits: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None, max_blocks: int = 0,
+                dev: Optional[torch.device] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_filter_eval``: the program (``_capi.FilterProgram``, its pointers device arrays over ``n_rows`` rows) evaluated into
+    ``out`` i32 [n_words] -- bit r = row r passes, ANDed with ``and_bits`` i32 [n_words] where given, every word behind the rows 0 --
+    and the number of set bits ADDED to ``count`` i64 [1] (a fresh zero by default).  Returns ``(out, count)``."""
+    _capi.require_gpu()
+    if dev is None:
+        dev = and_bits.device if and_bits is not None else out.device if out is not None else device()
+    if out is None:
+        out = torch.empty((n_words,), dtype=torch.int32, device=dev)
+    if count is None:
+        count = torch.zeros((1,), dtype=torch.int64, device=dev)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == n_words
+    assert count.dtype == torch.int64 and count.numel() == 1
+    assert and_bits is None or (and_bits.dtype == torch.int32 and and_bits.is_contiguous() and and_bits.numel() >= n_words)
+    check(lib().annlite_filter_eval(ctypes.byref(program), n_rows, _ptr(and_bits), out.data_ptr(), n_words, count.data_ptr(), max_blocks,
+                                    stream_ptr()), 'filter_eval')
+    return out, count

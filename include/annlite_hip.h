@@ -861,6 +861,72 @@ ANNLITE_API int annlite_pca_accumulate_workspace_bytes(int64_t n, int64_t D, int
 ANNLITE_API int annlite_pca_accumulate(const float *x_dev, int64_t n, int64_t D, int64_t ldx, const float *shift_dev, double *sum_dev,
                            double *gram_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* Filterable columns: a filter over typed columns of the row range, evaluated into the packed row bitmap
+ * the searches take as valid_bits.  The host compiles the filter dict (annlite_amd/columns.py) into this program; the kernel takes it
+ * BY VALUE as a kernel argument -- it is uniform, the compiler reads it with scalar loads.
+ *   leaf: one comparison of one column.  values_dev: i64 [N] (ANNLITE_COL_I64), f64 [N] (ANNLITE_COL_F64; never NaN) or i32 [N]
+ *     dictionary codes (ANNLITE_COL_CODE); present_dev u32 [ceil(N / 32)]: bit r = row r has a value of the column's type.  A leaf is
+ *     `present && compare`: a row without the value satisfies no comparison, NE and NIN included (SQL NULL).
+ *     I64 / F64 ops: LT GT LE GE EQ NE against literals[lit_begin] (lit_count = 1), IN / NIN against literals[lit_begin .. + lit_count)
+ *     (lit_count >= 0); the literals are raw 8-byte values of the column's own type.
+ *     CODE op: IN_SET -- bit `code` of set_bits_dev u32 [set_words] (a code at or beyond 32 * set_words is not in the set).
+ *   code: postfix over a stack of booleans, one u32 of bits per lane: 0 .. 31 push leaf i; AND / OR pop two and push one; NOT negates
+ *     the top; TRUE pushes 1.  The stack never underflows, never holds more than ANNLITE_FILTER_MAX_STACK values and ends with one.
+ * The limits are conditions: a filter beyond one of them has no program (the host evaluates it). */
+#define ANNLITE_FILTER_MAX_LEAVES 32
+#define ANNLITE_FILTER_MAX_LITERALS 64
+#define ANNLITE_FILTER_MAX_CODE 128
+#define ANNLITE_FILTER_MAX_STACK 32
+#define ANNLITE_FILTER_MAX_BLOCKS 2048 /* the default cap of the grid (256 rows per workgroup and pass) */
+#define ANNLITE_COL_I64 0
+#define ANNLITE_COL_F64 1
+#define ANNLITE_COL_CODE 2
+#define ANNLITE_FOP_LT 0
+#define ANNLITE_FOP_GT 1
+#define ANNLITE_FOP_LE 2
+#define ANNLITE_FOP_GE 3
+#define ANNLITE_FOP_EQ 4
+#define ANNLITE_FOP_NE 5
+#define ANNLITE_FOP_IN 6
+#define ANNLITE_FOP_NIN 7
+#define ANNLITE_FOP_IN_SET 8
+#define ANNLITE_FCODE_AND 0x80
+#define ANNLITE_FCODE_OR 0x81
+#define ANNLITE_FCODE_NOT 0x82
+#define ANNLITE_FCODE_TRUE 0x83
+
+typedef struct annlite_filter_leaf {
+    const void *values_dev;
+    const uint32_t *present_dev;
+    const uint32_t *set_bits_dev; /* IN_SET only, else NULL */
+    uint8_t kind;                 /* ANNLITE_COL_* */
+    uint8_t op;                   /* ANNLITE_FOP_* */
+    uint8_t lit_begin;
+    uint8_t lit_count;
+    uint32_t set_words;           /* IN_SET only, else 0 */
+} annlite_filter_leaf;
+
+typedef struct annlite_filter_program {
+    int32_t n_leaves;
+    int32_t n_literals;
+    int32_t n_code;
+    int32_t reserved; /* 0 */
+    annlite_filter_leaf leaves[ANNLITE_FILTER_MAX_LEAVES];
+    uint64_t literals[ANNLITE_FILTER_MAX_LITERALS];
+    uint8_t code[ANNLITE_FILTER_MAX_CODE];
+} annlite_filter_program;
+
+/* out_bits_dev u32 [n_words] <- bit r = (row r < N satisfies the program) & bit r of and_bits_dev (u32 [n_words], may be NULL: the
+ * caller's validity or row-present words).  EVERY word is written: the words of rows >= N are 0, so with n_words = (capacity + 31) /
+ * 32 + 2 the result is a valid_bits array of every search here.  n_words * 32 >= N.  count_dev (may be NULL) u64 [1] += the number
+ * of bits set (one atomic per workgroup; the caller zeroes it).  One row per lane, 256 lanes per workgroup, the verdicts of a wave
+ * packed by ballot; the grid is capped at max_blocks workgroups (0: ANNLITE_FILTER_MAX_BLOCKS) that stride over the rows.
+ * `program` is a HOST pointer (copied into the launch); it is checked against the limits and the stack discipline above.
+ * replaces: the query path of the reference's cell table (annlite/storage/table.py: CellTable.query -- the SQL WHERE clause over the
+ * declared columns that yields the offsets a filtered search is given). */
+ANNLITE_API int annlite_filter_eval(const annlite_filter_program *program, int64_t N, const uint32_t *and_bits_dev, uint32_t *out_bits_dev,
+                        int64_t n_words, uint64_t *count_dev, int max_blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
