@@ -139,11 +139,16 @@ SYMBOLS = (
     'annlite_pca_accumulate_workspace_bytes',
     'annlite_pca_accumulate',
     'annlite_filter_eval',
+    'annlite_page_workspace_bytes',
+    'annlite_order_page',
+    'annlite_bitmap_page',
 )
 
 # filterable columns (include/annlite_hip.h: ANNLITE_FILTER_* / ANNLITE_COL_*)
 FILTER_MAX_LEAVES, FILTER_MAX_LITERALS, FILTER_MAX_CODE, FILTER_MAX_STACK, FILTER_MAX_BLOCKS = 32, 64, 128, 32, 2048
 COL_I64, COL_F64, COL_CODE = 0, 1, 2
+# pages of the document listing (ANNLITE_PAGE_*): rows of one page at most, rows a workgroup takes per stride, the default grid cap
+PAGE_MAX, PAGE_BLOCK_ROWS, PAGE_MAX_BLOCKS = 4096, 1024, 2048
 
 
 class FilterLeaf(ctypes.Structure):
@@ -324,6 +329,9 @@ def lib() -> ctypes.CDLL:
     L.annlite_pca_accumulate_workspace_bytes.argtypes = [i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_pca_accumulate.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]
     L.annlite_filter_eval.argtypes = [ctypes.POINTER(FilterProgram), i64, vp, vp, i64, vp, i32, vp]
+    L.annlite_page_workspace_bytes.argtypes = [ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_order_page.argtypes = [vp, vp, vp, i32, vp, vp, i64, i64, i64, i32, i64, i64, vp, vp, vp, sz, i32, vp]
+    L.annlite_bitmap_page.argtypes = [vp, vp, i64, i64, i64, i64, vp, vp, vp, sz, i32, vp]
     L.annlite_graph_search_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_graph_search_stats_ex.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     for name in SYMBOLS:

@@ -9,7 +9,10 @@ The reference keeps its declared columns in a SQLite cell table and turns the fi
   * ``ColumnStore.compile`` is the symbolic twin of ``filter._tokens`` / ``filter._reduce``: the same grammar, the same splice into
     one flat clause, the same errors -- but its operands are leaves over columns instead of booleans, and what it returns is a
     postfix program (or ``None``: the host evaluates the filter, as before);
-  * ``ColumnStore.evaluate`` launches the kernel and returns a ``RowMask``: the packed words a search takes as its bitmap.
+  * ``ColumnStore.evaluate`` launches the kernel and returns a ``RowMask``: the packed words a search takes as its bitmap;
+  * ``ColumnStore.page`` selects one page of the document listing (``AnnLite.filter`` / ``get_docs``: ``order_by``, ``offset``,
+    ``limit``) on the device -- a radix select over ``order_key`` of a regular column, ``annlite_order_page`` -- and brings only the
+    page's offsets to the host.
 
 The rule that keeps the answer equal to Python's: only values and literals whose comparison the kernel reproduces EXACTLY are taken
 (8-byte integers against 8-byte integers, doubles against doubles, every mixed case lowered by the table in ``_lower_i64``); anything
@@ -81,6 +84,35 @@ def _lower_i64(op: int, c: float):
     if t < INT64_MIN:
         return _NEVER if op in (OP_LT, OP_LE) else (OP_GE, INT64_MIN)
     return op, t
+
+
+PAGE_MAX = _capi.PAGE_MAX  # rows of one page taken on the device
+_U64 = 2 ** 64 - 1
+
+
+def order_key(kind: int, value) -> int:
+    """The value of a regular column as the 64-bit unsigned key the page kernels order by (``annlite_order_page``): ``key(a) < key(b)``
+    exactly where Python has ``a < b``, equal keys where it has ``a == b``.  ``I64``: ``x ^ 2**63`` over the int64 (``True`` is 1);
+    ``F64``: the monotone flip of the double's bits, -0.0 first made +0.0 (ints in the column are the doubles that hold them
+    exactly); ``CODE``: the value is the word's rank in the sorted dictionary already (``rank_table``).  Descending order is by
+    ``~key``."""
+    if kind == I64:
+        return (int(value) & _U64) ^ (1 << 63)
+    if kind == F64:
+        u = struct.unpack('<Q', struct.pack('<d', float(value)))[0]
+        if (u << 1) & _U64 == 0:  # (-0.0 == 0.0)
+            u = 0
+        return u ^ (_U64 if u >> 63 else 1 << 63)
+    assert kind == CODE, kind
+    return int(value)
+
+
+def rank_table(words: Sequence[str]) -> np.ndarray:
+    """i32 [len(words)]: code (the position in ``words``, a column's dictionary in insertion order) -> the word's position in
+    ``sorted(words)`` -- Python's order of str, by code point."""
+    rank = np.zeros((len(words),), dtype=np.int32)
+    rank[sorted(range(len(words)), key=words.__getitem__)] = np.arange(len(words), dtype=np.int32)
+    return rank
 
 
 class Leaf:
@@ -327,6 +359,8 @@ class ColumnStore:
         self._h_present: Dict[str, np.ndarray] = {}
         self._h_rows: Optional[np.ndarray] = None
         self._codes: Dict[str, Dict[str, int]] = {n: {} for n, k in self.kinds.items() if k == CODE}
+        self._ranks: Dict[str, torch.Tensor] = {}  # (per str column: code -> rank in the sorted dictionary, for pages)
+        self._workspace = None
 
     def __len__(self) -> int:
         return self._n
@@ -487,3 +521,44 @@ class ColumnStore:
         P, keep = self.bind(program)
         words, count = ops.filter_eval(P, self._n, self.n_words, and_bits=self.rows, max_blocks=max_blocks)
         return RowMask(words, count, self._n, keep=keep)
+
+    # ------------------------------------------------------------------ pages
+    def _rank(self, column: str) -> torch.Tensor:
+        """the str column's code -> rank table on the device, made again when the dictionary has grown"""
+        words = self.dictionary(column)
+        cached = self._ranks.get(column)
+        if cached is None or cached.numel() != max(1, len(words)):
+            table = rank_table(words) if words else np.zeros((1,), dtype=np.int32)  # (no word yet: every row is NULL)
+            cached = self._ranks[column] = torch.from_numpy(table).to(self.rows.device)
+        return cached
+
+    def page(self, mask: Optional[RowMask], order_by: Optional[str], ascending: bool, offset: int, limit: int,
+             max_blocks: int = 0) -> Optional[np.ndarray]:
+        """One page of the document listing, selected on the device: of the rows of ``mask`` (None: every present row) the offsets of
+        rank ``[offset, offset + limit)`` in ``AnnLite.filter``'s order -- by the declared column ``order_by`` (rows without a value
+        first ascending, last descending; equal values in ascending offset) or, without one, in ascending offset --, as i64 [<= limit].
+        Only the page crosses to the host: one copy of ``limit + 1`` ints.  None where the host has to answer: ``order_by`` is not
+        declared or is irregular, ``limit`` is not in ``1 .. PAGE_MAX``, ``offset`` is negative, ``offset + limit >= 2**31``, or the
+        store holds no rows."""
+        if self._n == 0 or type(limit) not in (int, bool) or type(offset) not in (int, bool):
+            return None
+        if not 1 <= limit <= PAGE_MAX or offset < 0 or offset + limit >= 2 ** 31:
+            return None
+        if order_by is not None and (self.kinds.get(order_by) is None or order_by in self.irregular):
+            return None
+        from . import ops
+
+        if self._workspace is None:
+            self._workspace = ops.ScanWorkspace()
+        W = self.n_words
+        words = None if mask is None else mask.words_for(W)
+        out = torch.empty((limit + 1,), dtype=torch.int32, device=self.rows.device)  # (the rows, and behind them their number)
+        if order_by is None:
+            bits, and_bits = (self.rows, None) if words is None else (words, self.rows)
+            ops.bitmap_page(bits, self._n, W, offset, limit, and_bits=and_bits, out=out, workspace=self._workspace, max_blocks=max_blocks)
+        else:
+            kind = self.kinds[order_by]
+            ops.order_page(words, self.rows, self.values[order_by], kind, self.present[order_by], self._n, W, not ascending, offset, limit,
+                           rank=self._rank(order_by) if kind == CODE else None, out=out, workspace=self._workspace, max_blocks=max_blocks)
+        host = out.cpu().numpy()
+        return host[: int(host[limit])].astype(np.int64)

@@ -43,7 +43,9 @@ persistence of documents, remote backup.  Documents and tags live in memory; the
 evaluated on the host and handed to the GPU scan as a row bitmap (section 8f-3) -- unless it names declared ``columns`` only:
 those are kept as typed device arrays beside the vectors (``ColumnStore``, columns.py), the filter compiles to a predicate program
 and ONE kernel evaluates it into the bitmap the indexes read (``annlite_filter_eval``).  The rows selected
-are the same; ``filter_eval='host'`` keeps the host path, ``last_filter_eval`` says which one answered.
+are the same; ``filter_eval='host'`` keeps the host path, ``last_filter_eval`` says which one answered.  ``filter()`` /
+``get_docs()`` then select their page (``order_by``, ``offset``, ``limit``) on the device too (``ColumnStore.page``, DESIGN.md section
+3.10.1); ``last_filter_page`` says whether they did.
 """
 import hashlib
 import logging
@@ -117,7 +119,9 @@ class AnnLite:
         on the host, as before
     :param filter_eval: ``'auto'`` (default; kwarg): a filter that compiles over the declared columns is evaluated by
         ``annlite_filter_eval``, any other by ``filter.select``; ``'host'``: ``filter.select`` always.  ``last_filter_eval`` reports
-        ``'gpu'`` / ``'host'`` for the last filter (``None`` before the first)
+        ``'gpu'`` / ``'host'`` for the last filter (``None`` before the first).  With ``'auto'`` ``filter()`` / ``get_docs()`` also select
+        their page -- ``order_by`` a declared column or none, ``offset``, ``1 <= limit <= 4096`` -- on the device
+        (``annlite_order_page`` / ``annlite_bitmap_page``); ``last_filter_page`` reports ``'gpu'`` / ``'host'`` for the last page
     """
 
     def __init__(
@@ -235,6 +239,7 @@ class AnnLite:
             raise ValueError(f"filter_eval={self.filter_eval!r}: 'auto' (the device where the filter compiles) or 'host'")
         self._columns = ColumnStore(self.filterable_attrs)
         self.last_filter_eval = None  # 'gpu' / 'host': what evaluated the last filter (None: no filter yet)
+        self.last_filter_page = None  # 'gpu' / 'host': what selected the last page of filter() / get_docs() (None: no call yet)
 
         self._index_kwargs = dict(initial_size=initial_size, expand_step_size=expand_step_size, **kwargs)
         self._vec_indexes = [self._new_index()]
@@ -702,8 +707,19 @@ class AnnLite:
     def filter(self, filter: Optional[dict], limit: int = 10, offset: int = 0, order_by: Optional[str] = None,
                ascending: bool = True, include_metadata: bool = True):
         """index.py:389-423 -> CellContainer.filter_cells (container.py:146-199): the documents whose tags satisfy
-        the filter, in insertion order or ordered by a tag, ``offset`` skipped, at most ``limit`` (<= 0: all)."""
+        the filter, in insertion order or ordered by a tag, ``offset`` skipped, at most ``limit`` (<= 0: all).
+
+        Where the rows are a device mask (or every row) and the page is one the device selects -- ``order_by`` a declared regular
+        column or none, ``1 <= limit <= 4096`` --, only the page's offsets come to the host (``ColumnStore.page``: a radix select
+        over the column); any other call is answered below, as before.  The same documents in the same
+        order either way; ``last_filter_page`` says which one answered."""
         sel = self._filter_offsets(filter)
+        page = None
+        if self.filter_eval == 'auto' and (sel is None or isinstance(sel, RowMask)):
+            page = self._columns.page(sel, order_by or None, ascending, offset, limit)
+        self.last_filter_page = 'host' if page is None else 'gpu'
+        if page is not None:
+            return self._documents(page.tolist(), include_metadata)
         if sel is None:  # (no filter: every live row)
             offs = _filter_select(self._tags, {})
         else:
@@ -718,6 +734,9 @@ class AnnLite:
         offs = offs[offset:]
         if limit > 0:
             offs = offs[:limit]
+        return self._documents(offs, include_metadata)
+
+    def _documents(self, offs, include_metadata: bool):
         out = DocumentArray()
         for o in offs:
             doc_id = self._offset2id[o]

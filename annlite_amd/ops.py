@@ -1209,3 +1209,60 @@ def filter_eval(program: '_capi.FilterProgram', n_rows: int, n_words: int, and_b
     check(lib().annlite_filter_eval(ctypes.byref(program), n_rows, _ptr(and_bits), out.data_ptr(), n_words, count.data_ptr(), max_blocks,
                                     stream_ptr()), 'filter_eval')
     return out, count
+
+
+def _page_out(count: int, out: Optional[torch.Tensor], dev) -> torch.Tensor:
+    """i32 [count + 1]: the page's rows and, behind them, their number -- one buffer, so that one copy brings both to the host"""
+    if out is None:
+        out = torch.empty((count + 1,), dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == count + 1
+    return out
+
+
+def _page_workspace(workspace: Optional[ScanWorkspace], dev) -> torch.Tensor:
+    need = ctypes.c_int64(0)
+    check(lib().annlite_page_workspace_bytes(ctypes.byref(need)), 'page_workspace_bytes')
+    return (workspace or ScanWorkspace()).get(int(need.value), dev)
+
+
+def _bitmap(t: Optional[torch.Tensor], n_words: int, name: str):
+    assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.numel() >= n_words), f'{name}: i32 [>= {n_words}], contiguous'
+
+
+def order_page(mask: Optional[torch.Tensor], rows: torch.Tensor, values: torch.Tensor, kind: int, present: torch.Tensor, n_rows: int,
+               n_words: int, descending: bool, first: int, count: int, rank: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, workspace: Optional[ScanWorkspace] = None,
+               max_blocks: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_order_page``: of the rows set in ``mask & rows`` (i32 [n_words] each; ``mask`` None: every row of ``rows``, the
+    row-present words) the ones of rank ``[first, first + count)`` in the listing's order by the column -- ``values`` (i64 / f64 / i32
+    codes, [>= n_rows]) of ``kind`` (``_capi.COL_*``), ``present`` i32 [n_words], for a str column ``rank`` i32 [dictionary]: code ->
+    position in the sorted dictionary.  Rows without a value come first ascending, last descending; equal values stay in ascending
+    row.  ``out`` i32 [count + 1] (made here by default) takes the rows and, behind them, their number.  Returns ``(out[:count],
+    out[count:])``: the rows -- valid up to the number -- and the number, both still on the device."""
+    _capi.require_gpu()
+    out = _page_out(count, out, rows.device)
+    for t, name in ((mask, 'mask'), (rows, 'rows'), (present, 'present')):
+        _bitmap(t, n_words, name)
+    want = {_capi.COL_I64: torch.int64, _capi.COL_F64: torch.float64, _capi.COL_CODE: torch.int32}.get(kind)
+    assert want is None or (values.dtype == want and values.is_contiguous() and values.numel() >= n_rows), 'values: the kind\'s type, [>= n_rows]'
+    assert rank is None or (rank.dtype == torch.int32 and rank.is_contiguous())
+    ws = _page_workspace(workspace, rows.device)
+    check(lib().annlite_order_page(_ptr(mask), rows.data_ptr(), values.data_ptr(), kind, present.data_ptr(), _ptr(rank),
+                                   0 if rank is None else rank.numel(), n_rows, n_words, int(bool(descending)), first, count, out.data_ptr(),
+                                   out.data_ptr() + 4 * count, ws.data_ptr(), ws.numel(), max_blocks, stream_ptr()), 'order_page')
+    return out[:count], out[count:]
+
+
+def bitmap_page(bits: torch.Tensor, n_rows: int, n_words: int, first: int, count: int, and_bits: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None, workspace: Optional[ScanWorkspace] = None,
+                max_blocks: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_bitmap_page``: the rows ``< n_rows`` set in ``bits`` (``& and_bits`` where given; i32 [n_words] each) of rank
+    ``[first, first + count)``, ascending.  ``out`` and the return value as ``order_page``'s."""
+    _capi.require_gpu()
+    out = _page_out(count, out, bits.device)
+    _bitmap(bits, n_words, 'bits')
+    _bitmap(and_bits, n_words, 'and_bits')
+    ws = _page_workspace(workspace, bits.device)
+    check(lib().annlite_bitmap_page(bits.data_ptr(), _ptr(and_bits), n_rows, n_words, first, count, out.data_ptr(), out.data_ptr() + 4 * count,
+                                    ws.data_ptr(), ws.numel(), max_blocks, stream_ptr()), 'bitmap_page')
+    return out[:count], out[count:]

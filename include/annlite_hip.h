@@ -927,6 +927,37 @@ typedef struct annlite_filter_program {
 ANNLITE_API int annlite_filter_eval(const annlite_filter_program *program, int64_t N, const uint32_t *and_bits_dev, uint32_t *out_bits_dev,
                         int64_t n_words, uint64_t *count_dev, int max_blocks, void *stream);
 
+/* Pages of the document listing (page.hip): the rows of a bitmap whose rank in the listing's order lies in
+ * [first, first + count).  The order is the host's (AnnLite.filter): the rows WITH a value of the column sorted by it -- ties in
+ * ascending row, in both directions (Python's stable sort) --, the rows without one (present bit 0) in ascending row before them
+ * (ascending) or behind them (descending).  Per row the composite (class, key, row) is distinct; the page is selected by MSB radix
+ * select over its 8-bit digits and sorted by one workgroup, so the answer does not depend on the order of any atomic.
+ *   key: I64 (ints, bools)  x ^ 2^63;   F64  the monotone bit flip of the double, -0.0 first made +0.0 (never NaN);
+ *        CODE  rank_dev[code] (u32 [rank_len], 1 <= rank_len <= 65536: the position of the word in the sorted dictionary);
+ *        descending: ~key.
+ * mask_dev u32 [n_words] (may be NULL: every row of rows_dev) is ANDed with rows_dev u32 [n_words], the row-present words; rows >= N
+ * are never read or returned (n_words * 32 >= N, N < 2^31).  first >= 0, 1 <= count <= ANNLITE_PAGE_MAX, first + count < 2^31.
+ * out_rows_dev i32 [count] <- the page, in order; out_n_dev i32 [1] <- its rows: min(first + count, selected) - first, 0 where first
+ * is at or beyond the selection (the rest of out_rows_dev is left as it was).  workspace: annlite_page_workspace_bytes, 16-byte
+ * aligned.  One launch per digit that can differ (13 at most), each over the mask words and the 8-byte (CODE: 4-byte) values, then a
+ * collect and a sort; the grids are capped at max_blocks workgroups (0: ANNLITE_PAGE_MAX_BLOCKS) of ANNLITE_PAGE_BLOCK_ROWS rows per
+ * stride.  A bad kind, a negative first, a count out of range, n_words * 32 < N or a NULL pointer is an error; nothing is launched.
+ * replaces: the reference's document listing (annlite/storage/table.py: the SQL ORDER BY ... LIMIT ... OFFSET behind
+ * AnnLite.filter / get_docs). */
+#define ANNLITE_PAGE_MAX 4096
+#define ANNLITE_PAGE_BLOCK_ROWS 1024
+#define ANNLITE_PAGE_MAX_BLOCKS 2048
+ANNLITE_API int annlite_page_workspace_bytes(int64_t *bytes);
+ANNLITE_API int annlite_order_page(const uint32_t *mask_dev, const uint32_t *rows_dev, const void *values_dev, int kind,
+                        const uint32_t *present_dev, const uint32_t *rank_dev, int64_t rank_len, int64_t N, int64_t n_words,
+                        int descending, int64_t first, int64_t count, int32_t *out_rows_dev, int32_t *out_n_dev, void *workspace,
+                        size_t workspace_bytes, int max_blocks, void *stream);
+/* ... without an order: the set bits of bits_dev & and_bits_dev (u32 [n_words] each; and_bits_dev may be NULL) of rank
+ * [first, first + count), ascending -- the same select over the row digits alone.  Same outputs, limits and errors. */
+ANNLITE_API int annlite_bitmap_page(const uint32_t *bits_dev, const uint32_t *and_bits_dev, int64_t N, int64_t n_words, int64_t first,
+                        int64_t count, int32_t *out_rows_dev, int32_t *out_n_dev, void *workspace, size_t workspace_bytes,
+                        int max_blocks, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
