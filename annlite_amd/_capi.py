@@ -128,6 +128,9 @@ SYMBOLS = (
     'annlite_flat_search_i8_workspace_bytes',
     'annlite_flat_filter_i8',
     'annlite_flat_search_topk_i8',
+    'annlite_flat_search_rows_workspace_bytes',
+    'annlite_flat_search_topk_rows',
+    'annlite_flat_filter_rows',
     'annlite_ivf_flat_stages',
     'annlite_ivf_flat_search_workspace_bytes',
     'annlite_ivf_flat_search_topk',
@@ -142,11 +145,15 @@ SYMBOLS = (
     'annlite_page_workspace_bytes',
     'annlite_order_page',
     'annlite_bitmap_page',
+    'annlite_bitmap_rows_workspace_bytes',
+    'annlite_bitmap_rows',
 )
 
 # filterable columns (include/annlite_hip.h: ANNLITE_FILTER_* / ANNLITE_COL_*)
 FILTER_MAX_LEAVES, FILTER_MAX_LITERALS, FILTER_MAX_CODE, FILTER_MAX_STACK, FILTER_MAX_BLOCKS = 32, 64, 128, 32, 2048
 COL_I64, COL_F64, COL_CODE = 0, 1, 2
+# the filters of the searches over selected rows (ANNLITE_FLAT_FILTER_*), by their name in ``FlatGpuIndex.last_flat_filter``
+FLAT_FILTER = {'f32': 0, 'bf16x3': 1, 'f16x2': 2, 'i8x3': 3}
 # pages of the document listing (ANNLITE_PAGE_*): rows of one page at most, rows a workgroup takes per stride, the default grid cap
 PAGE_MAX, PAGE_BLOCK_ROWS, PAGE_MAX_BLOCKS = 4096, 1024, 2048
 
@@ -315,6 +322,9 @@ def lib() -> ctypes.CDLL:
     L.annlite_flat_search_i8_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_flat_filter_i8.argtypes = [i32, vp, i64, i64, vp, ctypes.c_float, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.annlite_flat_search_topk_i8.argtypes = [i32, vp, i64, i64, vp, ctypes.c_float, vp, i64, vp, i64, i32, vp, vp, vp, sz, vp]
+    L.annlite_flat_search_rows_workspace_bytes.argtypes = [i32, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_flat_search_topk_rows.argtypes = [i32, i32, vp, i64, i64, vp, ctypes.c_float, vp, vp, i64, vp, i64, i64, i32, vp, vp, vp, sz, vp]
+    L.annlite_flat_filter_rows.argtypes = [i32, i32, vp, i64, i64, vp, ctypes.c_float, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]
     L.annlite_ivf_flat_stages.argtypes = [i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32)]
     L.annlite_ivf_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_ivf_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, vp,
@@ -332,6 +342,8 @@ def lib() -> ctypes.CDLL:
     L.annlite_page_workspace_bytes.argtypes = [ctypes.POINTER(ctypes.c_int64)]
     L.annlite_order_page.argtypes = [vp, vp, vp, i32, vp, vp, i64, i64, i64, i32, i64, i64, vp, vp, vp, sz, i32, vp]
     L.annlite_bitmap_page.argtypes = [vp, vp, i64, i64, i64, i64, vp, vp, vp, sz, i32, vp]
+    L.annlite_bitmap_rows_workspace_bytes.argtypes = [i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_bitmap_rows.argtypes = [vp, vp, i64, i64, vp, i64, vp, vp, sz, vp]
     L.annlite_graph_search_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.annlite_graph_search_stats_ex.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     for name in SYMBOLS:

@@ -165,15 +165,34 @@ class FlatGpuIndex(RowStoreIndex):
         first ``add_with_ids`` batch, frozen until ``reset()``; an array ``[dim]``: that point; ``None``: no centring.  Any centre gives
         the exact answer; it only moves the slack (a NaN or infinite one -- the mean of a first batch that holds such a value --
         lets every row pass: every query then takes the all-rows route).  ``centre_`` reads the one in use.
+    :param filter_route: how a search restricted to a subset -- ``indices`` (offsets or a ``RowMask``) or deleted rows -- scans.
+        ``'mask'`` (default): the whole table, a row's bit tested once its score exists: a row that fails costs what one that passes
+        does.  ``'rows'``: the selection is compacted into an ascending list of offsets (``annlite_bitmap_rows``; 4 bytes per row of
+        capacity, kept by the index) and the search -- first sample, filter stages, overflow route -- runs over that list: the work
+        follows the number of selected rows ("selected rows").  Reading that number is one host read per
+        search.  At most 4096 selected rows are answered by exact sums over the list (no filter runs), none by the empty answer.
+        ``'auto'``: ``'rows'`` where the selection holds at most ``ROWS_MAX_FRACTION`` of the rows, else ``'mask'``
+        (``choose_filter_route``).  The answer is the same bit for bit under every value.  A search with no ``indices`` and no
+        deleted rows has nothing to compact, and ``limit > 64`` keeps the masked ``_search_large_k``: both stay ``'mask'`` under every
+        value.  ``search_batch`` takes the keyword per call; ``last_filter_route`` reports ``'mask'`` / ``'rows'`` for the last search
+        (``None``: none yet, or an empty index or batch), and ``last_overflowed`` counts the queries sent to exact sums over all rows
+        of whatever set was scanned.
     """
     FORMAT = 'annlite_amd.FlatGpuIndex/1'
     STATE_KEYS = ('dim', 'metric')
     FLAT_FILTERS = ('f32', 'bf16x3', 'f16x2', 'i8x3')
     SPLIT_MAX_DIM = 32768    # (annlite_flat_split_slack: the range of the slack's derivation)
     FILTER_MIN_ROWS = 4097   # (kFlatSample + 1 in flat.hip: smaller tables are answered by exact sums, no filter runs)
+    FILTER_ROUTES = ('mask', 'rows', 'auto')
+    ROWS_MAX_FRACTION = 0.5  # (measured: DESIGN.md section 3.6, "selected rows")
 
     def __init__(self, dim: int, dtype: np.dtype = np.float32, metric: Metric = Metric.COSINE,
-                 index_file: Optional[Union[str, Path]] = None, flat_filter: str = 'f32', centre='mean', int8_scale=None, **kwargs):
+                 index_file: Optional[Union[str, Path]] = None, flat_filter: str = 'f32', centre='mean', int8_scale=None,
+                 filter_route: str = 'mask', **kwargs):
+        self.filter_route = self._check_filter_route(filter_route)
+        self.last_filter_route = None  # 'mask' / 'rows': how the last search_batch scanned; None: it scanned nothing
+        self._sel_rows = None          # i32 [capacity]: the compacted selection of the last 'rows' search
+        self._rows_ws = ops.ScanWorkspace()
         if flat_filter not in self.FLAT_FILTERS:
             raise ValueError(f"flat_filter={flat_filter!r}: 'f32' (the f32 MFMA filter), 'bf16x3' (the split-bf16 filter over centred rows) "
                              "or, with dtype=np.float16, 'f16x2', with dtype=np.int8, 'i8x3'")
@@ -250,6 +269,10 @@ class FlatGpuIndex(RowStoreIndex):
         super().reset(capacity=capacity)
         self._centre_dev = None
 
+    def _alloc(self, capacity: int):
+        super()._alloc(capacity)
+        self._sel_rows = None  # (made at the new capacity by the next 'rows' search)
+
     # ------------------------------------------------------------------ storage (row_store.py)
     def _columns(self):
         """``_cnorms``: the norms of the centred rows, kept only where the split filter has a centre (it reads ``_norms`` otherwise)"""
@@ -306,9 +329,49 @@ class FlatGpuIndex(RowStoreIndex):
             self._overflowed = ops.flat_overflow_count(self._ws)
         return self._overflowed
 
-    def search_batch(self, x, limit: int = 10, indices=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    @classmethod
+    def _check_filter_route(cls, route) -> str:
+        if route not in cls.FILTER_ROUTES:
+            raise ValueError(f"filter_route={route!r}: 'mask' (scan the table, test a row's bit), 'rows' (compact the selection, scan "
+                             "only its rows) or 'auto' (by the selection's share of the rows)")
+        return route
+
+    def choose_filter_route(self, n_sel: Optional[int], n_rows: int, k: int, route: Optional[str] = None) -> str:
+        """``'mask'`` or ``'rows'`` for a search of ``limit`` ``k`` whose selection holds ``n_sel`` of ``n_rows`` rows (``None``: nothing
+        to compact -- no ``indices``, no deleted rows) under ``route`` (default: the index's ``filter_route``).  Pure: no device work."""
+        route = self.filter_route if route is None else self._check_filter_route(route)
+        if route == 'mask' or n_sel is None or k > 64:
+            return 'mask'
+        if route == 'rows':
+            return 'rows'
+        return 'rows' if n_sel <= self.ROWS_MAX_FRACTION * n_rows else 'mask'
+
+    def _search_rows(self, q, k: int, valid, N: int, route: str):
+        """The ``'rows'`` route of a k <= 64 search over the rows set in ``valid``; None where ``'auto'`` decides for the mask."""
+        if self._sel_rows is None or self._sel_rows.numel() < self._capacity:
+            self._sel_rows = torch.empty((max(self._capacity, N),), dtype=torch.int32, device=q.device)
+        _, n_sel = ops.bitmap_rows(valid, n_rows=N, out=self._sel_rows, workspace=self._rows_ws)  # (the one host read)
+        if self.choose_filter_route(n_sel, N, k, route) != 'rows':
+            return None
+        self.last_filter_route = 'rows'
+        if n_sel == 0:
+            return empty_answer(q.shape[0], k, q.device)
+        tag, norms, centre = self._kind.tag, self._norms, None
+        if self.flat_filter == 'bf16x3' and tag == 'f32':
+            tag = 'bf16x3'
+            if self._centred:
+                norms, centre = self._cnorms, self._centre_dev
+        d, i = ops.flat_search_topk_rows(tag, int(self.metric), q, self._vectors, norms, self._sel_rows, k, n_sel=n_sel, n_rows=N, centre=centre,
+                                         scale=self._i8_scale or 1.0, sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
+        self._overflowed = None
+        self.last_flat_filter = tag if n_sel >= self.FILTER_MIN_ROWS else None
+        return d, i
+
+    def search_batch(self, x, limit: int = 10, indices=None, filter_route: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """All queries of ``x`` [B, D] in one call.  ``(dists f32 [B, k], ids i64 [B, k])`` ascending by (distance, id), NaN
-        distances last; missing -> (+inf, -1).  numpy in gives numpy out, device tensors stay on the device."""
+        distances last; missing -> (+inf, -1).  numpy in gives numpy out, device tensors stay on the device.  ``filter_route``: this
+        call's, else the constructor's (class docstring); ``limit > 64`` keeps the masked search under every value."""
+        route = self.filter_route if filter_route is None else self._check_filter_route(filter_route)
         is_np = not isinstance(x, torch.Tensor)
         q = self._pre(x)
         B = q.shape[0]
@@ -318,10 +381,19 @@ class FlatGpuIndex(RowStoreIndex):
         dev = q.device
         self._overflowed = 0
         self.last_flat_filter = None
+        self.last_filter_route = None
         if N == 0 or B == 0:
             d, i = empty_answer(B, k, dev)
         else:
             valid = self._valid if indices is None else self._filter_bits(indices)
+            answer = None
+            # (something to compact: a subset was asked for, or rows below the highest one are not valid)
+            if k <= 64 and route != 'mask' and (indices is not None or self._size < N):
+                answer = self._search_rows(q, k, valid, N, route)
+            if answer is not None:
+                d, i = answer
+                return like_input(is_np, d, i)
+            self.last_filter_route = 'mask'
             if k <= 64:  # hnsw/index.py:164-165
                 topk, tag, norms = self._kind.topk, self._kind.tag, self._norms
                 if self.flat_filter == 'bf16x3' and tag == 'f32':  # (the split filter is over f32 rows; k > 64 keeps the f32 filter)

@@ -17,8 +17,9 @@ exact search of the parent: never worse.  ``filter_search='graph'`` (constructor
 instead, as hnswlib's ``searchBaseLayerSTWithFilter`` does: ``annlite_graph_f32_search_admit`` walks through every node and keeps the
 best admitted rows among everything it evaluates ("filtered walk").  Ids must be dense in insertion order
 (0, 1, 2, ...: what AnnLite's offsets are); rows are not updated in place (delete + add a new offset, hnsw/index.py:173-177); a delete
-clears the validity bit only -- the row keeps routing the walk.  ``flat_filter`` / ``centre`` are the parent's keywords and reach it
-unchanged: they choose the filter of those exact searches (``search_exhaustive`` included), never the walk.
+clears the validity bit only -- the row keeps routing the walk.  ``flat_filter`` / ``centre`` / ``filter_route`` are the parent's keywords
+and reach it unchanged: they choose the filter of those exact searches (``search_exhaustive`` included) and whether a filtered one scans
+the table or the selected rows, never the walk.
 """
 from pathlib import Path
 from typing import List, Optional, Tuple, Union
@@ -159,17 +160,17 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
         gg = self._gg
         no_walk = gg is None or gg.n == 0 or gg.n != self._n_rows or k > self.MAX_EF or ef > self.MAX_EF
         if indices is not None:
-            self._overflowed, self.last_flat_filter = 0, None  # (a walk runs no filter; the parent's search sets its own)
+            self._overflowed, self.last_flat_filter, self.last_filter_route = 0, None, None  # (a walk runs no filter; the parent's search sets its own)
             answer = self._filtered_answer(x, k, ef, indices, filter_search, not no_walk)
             if answer is not None:
                 return answer
         if indices is not None or no_walk:
-            return super().search_batch(x, limit=limit, indices=indices)
+            return super().search_batch(x, limit=limit, indices=indices, filter_route=kwargs.get('filter_route'))
         is_np = not isinstance(x, torch.Tensor)
         q = self._pre(x)
         B = q.shape[0]
         self._overflowed = 0
-        self.last_flat_filter = None  # (a walk: no filter ran)
+        self.last_flat_filter = self.last_filter_route = None  # (a walk: no filter ran, no table was scanned)
         if B == 0:
             return like_input(is_np, *empty_answer(B, k, q.device))
         cand, cand_d = self.candidates(q, ef)

@@ -150,13 +150,15 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         self._sealed = True
 
     # ------------------------------------------------------------------ search
-    def search_batch(self, x, limit: int = 10, indices=None, n_probe: Optional[int] = None):
-        """``FlatGpuIndex.search_batch`` over the rows of each query's ``n_probe`` nearest cells (every cell: that search itself)."""
+    def search_batch(self, x, limit: int = 10, indices=None, n_probe: Optional[int] = None, filter_route: Optional[str] = None):
+        """``FlatGpuIndex.search_batch`` over the rows of each query's ``n_probe`` nearest cells (every cell: that search itself, with
+        its ``filter_route``; the pruned search scans cell tiles under the bitmap whatever the route, and reports ``'mask'``)."""
         P = self.n_probe if n_probe is None else n_probe
         C = self.n_cells
         self.last_cell_filter = None
         if P is None or P >= C:
-            return super().search_batch(x, limit=limit, indices=indices)
+            return super().search_batch(x, limit=limit, indices=indices, filter_route=filter_route)
+        self.last_filter_route = 'mask'
         is_np = not isinstance(x, torch.Tensor)
         q = self._pre(x)
         B, k = q.shape[0], int(limit)

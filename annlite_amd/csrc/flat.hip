@@ -17,6 +17,8 @@
 //   flat_f32_stage + flat_f32_contract                           the f32 stage and its 4-MFMA K loop
 //   FLAT_BF16X3_CONTRACT                                         the split filter's 12-MFMA K loop (a macro: see there)
 //   flat_tile_epilogue -> flat_admit                             C-tile row map, score, `scores`, the negated comparison, the append
+// The four table filters also run over a LIST of selected rows (flat_tile_rows_mapped, flat_row_slot: each body is a function of
+// <VEC, MAPPED> behind the table kernel and a flat_rows_* twin; DESIGN.md section 3.6, "selected rows").
 // and on the host: WsBump (workspace carving), flat_filter_grid, FLAT_LAUNCH_VEC, flat_check_workspace, flat_check_shape.
 #include <math.h>
 
@@ -107,6 +109,35 @@ __device__ __forceinline__ void flat_tile_rows(int tid, int64_t r0, int64_t S, i
     if (ok && valid) ok = (valid[row >> 5] >> (row & 31)) & 1u;
     oks[tid] = ok ? 1 : 0;
     nxs[tid] = ok ? norms[row] : 0.f;
+}
+
+// ... of a MAPPED table kernel ("selected rows"): stage row r is rows[r * stride] of an ascending list of S
+// selected offsets, not table row r * stride.  rws[i] = the offset of stage row r0 + i, -1: none (past the list's end, or an entry outside
+// [0, N)), as ivf_flat_tile_rows has it; nxs[i] = its norm.  No bitmap: a row in the list is selected.
+__device__ __forceinline__ void flat_tile_rows_mapped(int tid, int64_t r0, int64_t S, int64_t stride, const int32_t *__restrict__ rows, int64_t N,
+                                                      const float *__restrict__ norms, int *rws, float *nxs) {
+    if (tid >= kFlatTile) return;
+    const int64_t r = r0 + tid;
+    int64_t row = r < S ? (int64_t)rows[r * stride] : -1;
+    if (row < 0 || row >= N) row = -1;
+    rws[tid] = (int)row;
+    nxs[tid] = row >= 0 ? norms[row] : 0.f;
+}
+
+// The two forms of "stage row r0 + r of the tile" and of its place in the epilogue, by the kernel's MAPPED flag (oks holds flags
+// unmapped, offsets mapped).
+template <bool MAPPED>
+__device__ __forceinline__ FlatSlot flat_row_slot(const int *oks, int r, int64_t r0, int64_t S, int64_t stride, int D) {
+    if constexpr (MAPPED) return FlatSlot{oks[r] >= 0, (int64_t)oks[r] * D};
+    else return FlatSlot{r0 + r < S, (r0 + r) * stride * D};
+}
+template <bool MAPPED>
+__device__ __forceinline__ bool flat_row_listed(const int *oks, int rl) {
+    return MAPPED ? oks[rl] >= 0 : oks[rl] != 0;
+}
+template <bool MAPPED>
+__device__ __forceinline__ int32_t flat_row_value(const int *oks, int rl, int64_t r0, int64_t stride) {
+    return MAPPED ? oks[rl] : (int32_t)((r0 + rl) * stride);
 }
 
 // One more entry for a query's list.
@@ -209,22 +240,26 @@ __device__ __forceinline__ void flat_f32_contract(const float *As, const float *
     }
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+// MAPPED (every table filter kernel has the flag): the stage rows are the entries of `rows`, offsets < N (flat_tile_rows_mapped); `valid`
+// is not read.  Without the flag `rows` and N are not read.
+template <bool VEC, bool MAPPED>
+__device__ __forceinline__ void flat_filter_tile(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
                                                          const float *__restrict__ norms, int64_t S, int64_t stride,
                                                          const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
                                                          const float *__restrict__ thr, float c_rel, float c_abs,
-                                                         int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles) {
+                                                         int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles,
+                                                         const int32_t *__restrict__ rows, int64_t N) {
     __shared__ float As[kFlatTile * kFlatLd];
     __shared__ float Bs[kFlatTile * kFlatLd];
     __shared__ float nxs[kFlatTile];
     __shared__ int oks[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
-    flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
+    if constexpr (MAPPED) flat_tile_rows_mapped(tid, r0, S, stride, rows, N, norms, oks, nxs);
+    else flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
     const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
     const int l31 = lane & 31, lh = lane >> 5;
-    const auto row_of = [&](int rl) { return FlatRow{oks[rl] != 0, (int32_t)((r0 + rl) * stride), false, 0}; };
+    const auto row_of = [&](int rl) { return FlatRow{flat_row_listed<MAPPED>(oks, rl), flat_row_value<MAPPED>(oks, rl, r0, stride), false, 0}; };
     for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
         const int q0 = qt * kFlatTile;
         FlatAcc acc;
@@ -232,7 +267,7 @@ __global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const floa
         for (int k0 = 0; k0 < D; k0 += kFlatDepth) {
             __syncthreads();  // the previous stage is consumed (first pass: the row tile's norms and flags are written)
             flat_f32_stage<VEC>(
-                tid, k0, D, x, q, As, Bs, [&](int r) { return FlatSlot{r0 + r < S, (r0 + r) * stride * D}; },
+                tid, k0, D, x, q, As, Bs, [&](int r) { return flat_row_slot<MAPPED>(oks, r, r0, S, stride, D); },
                 [&](int r) { return FlatSlot{q0 + r < B, (int64_t)(q0 + r) * D}; });
             __syncthreads();
             flat_f32_contract(As, Bs, wr, wq, l31, lh, acc);
@@ -247,6 +282,21 @@ __global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const floa
                 flat_tile_epilogue<false, false>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
         }
     }
+}
+// The kernel over the table (what ran before there were lists), and the MAPPED one over a list of selected rows.
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+                             const float *__restrict__ norms, int64_t S, int64_t stride, const uint32_t *__restrict__ valid,
+                             const float *__restrict__ qnorm, const float *__restrict__ thr, float c_rel, float c_abs, int32_t *__restrict__ cand,
+                             int32_t *__restrict__ cnt, int cap, int n_qtiles) {
+    flat_filter_tile<VEC, false>(metric, q, B, D, x, norms, S, stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, cap, n_qtiles, nullptr, 0);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_rows_filter_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+                             const float *__restrict__ norms, int64_t S, int64_t stride, const uint32_t *__restrict__ valid,
+                             const float *__restrict__ qnorm, const float *__restrict__ thr, float c_rel, float c_abs, int32_t *__restrict__ cand,
+                             int32_t *__restrict__ cnt, int cap, int n_qtiles, const int32_t *__restrict__ rows, int64_t N) {
+    flat_filter_tile<VEC, true>(metric, q, B, D, x, norms, S, stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, cap, n_qtiles, rows, N);
 }
 
 // ---- the split filter: the same scores from three bf16 MFMAs over CENTRED rows ("split filter") -----------
@@ -350,14 +400,14 @@ __device__ __forceinline__ void flat_stage_planes(int tid, int k0, int lim, cons
 
 // flat_filter_kernel's job, grid and tile.  scores != NULL (tests, measurements): v of every (query, stage row) pair goes to
 // scores f32 [B][S] as well.
-template <bool VEC>
-__global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, const __bf16 *__restrict__ qh, const __bf16 *__restrict__ ql, int B,
+template <bool VEC, bool MAPPED>
+__device__ __forceinline__ void flat_split_filter_tile(int metric, const __bf16 *__restrict__ qh, const __bf16 *__restrict__ ql, int B,
                                                                int D, int Dp, const float *__restrict__ x, const float *__restrict__ mu,
                                                                const float *__restrict__ norms, int64_t S, int64_t stride,
                                                                const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
                                                                const float *__restrict__ thr, float c_rel, float c_abs,
                                                                int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles,
-                                                               float *__restrict__ scores) {
+                                                               float *__restrict__ scores, const int32_t *__restrict__ rows, int64_t N) {
     __shared__ __attribute__((aligned(16))) __bf16 Ah[kFlatTile * kSplitLd];
     __shared__ __attribute__((aligned(16))) __bf16 Al[kFlatTile * kSplitLd];
     __shared__ __attribute__((aligned(16))) __bf16 Bh[kFlatTile * kSplitLd];
@@ -366,12 +416,15 @@ __global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, cons
     __shared__ int oks[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
-    flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
+    if constexpr (MAPPED) flat_tile_rows_mapped(tid, r0, S, stride, rows, N, norms, oks, nxs);
+    else flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
     const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
     const int l31 = lane & 31, lh = lane >> 5;
     const __bf16 *const qp[2] = {qh, ql};
     __bf16 *const bp[2] = {Bh, Bl};
-    const auto row_of = [&](int rl) { return FlatRow{oks[rl] != 0, (int32_t)((r0 + rl) * stride), r0 + rl < S, r0 + rl}; };
+    const auto row_of = [&](int rl) {
+        return FlatRow{flat_row_listed<MAPPED>(oks, rl), flat_row_value<MAPPED>(oks, rl, r0, stride), r0 + rl < S, r0 + rl};
+    };
     for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
         const int q0 = qt * kFlatTile;
         FlatAcc acc;
@@ -385,9 +438,9 @@ __global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, cons
                     const int e = tid + i * 256;  // slots of 4 floats
                     const int r = e / (kSplitDepth / 4), c = (e % (kSplitDepth / 4)) * 4;
                     f32x4 cv = {0.f, 0.f, 0.f, 0.f};
-                    const int64_t rr = r0 + r;
-                    if (rr < S && k0 + c < D) {
-                        cv = *(const f32x4 *)(x + rr * stride * D + k0 + c);
+                    const FlatSlot sa = flat_row_slot<MAPPED>(oks, r, r0, S, stride, D);
+                    if (sa.ok && k0 + c < D) {
+                        cv = *(const f32x4 *)(x + sa.off + k0 + c);
                         if (mu) cv = cv - *(const f32x4 *)(mu + k0 + c);
                     }
                     bf16x4 h4, l4;
@@ -405,10 +458,10 @@ __global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, cons
                 for (int i = 0; i < kSplitDepth / 2; ++i) {
                     const int e = tid + i * 256;  // single floats
                     const int r = e / kSplitDepth, c = e % kSplitDepth;
-                    const int64_t rr = r0 + r;
+                    const FlatSlot sa = flat_row_slot<MAPPED>(oks, r, r0, S, stride, D);
                     float cv = 0.f;
-                    if (rr < S && k0 + c < D) {
-                        cv = x[rr * stride * D + k0 + c];
+                    if (sa.ok && k0 + c < D) {
+                        cv = x[sa.off + k0 + c];
                         if (mu) cv = cv - mu[k0 + c];
                     }
                     __bf16 h, l;
@@ -432,6 +485,25 @@ __global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, cons
                 flat_tile_epilogue<false, true>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
         }
     }
+}
+// The kernel over the table (what ran before there were lists), and the MAPPED one over a list of selected rows.
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_split_filter_kernel(int metric, const __bf16 *__restrict__ qh, const __bf16 *__restrict__ ql, int B,
+                             int D, int Dp, const float *__restrict__ x, const float *__restrict__ mu, const float *__restrict__ norms, int64_t S,
+                             int64_t stride, const uint32_t *__restrict__ valid, const float *__restrict__ qnorm, const float *__restrict__ thr,
+                             float c_rel, float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles,
+                             float *__restrict__ scores) {
+    flat_split_filter_tile<VEC, false>(metric, qh, ql, B, D, Dp, x, mu, norms, S, stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, cap, n_qtiles,
+                                       scores, nullptr, 0);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_rows_split_filter_kernel(int metric, const __bf16 *__restrict__ qh, const __bf16 *__restrict__ ql, int B,
+                             int D, int Dp, const float *__restrict__ x, const float *__restrict__ mu, const float *__restrict__ norms, int64_t S,
+                             int64_t stride, const uint32_t *__restrict__ valid, const float *__restrict__ qnorm, const float *__restrict__ thr,
+                             float c_rel, float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles,
+                             float *__restrict__ scores, const int32_t *__restrict__ rows, int64_t N) {
+    flat_split_filter_tile<VEC, true>(metric, qh, ql, B, D, Dp, x, mu, norms, S, stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, cap, n_qtiles,
+                                      scores, rows, N);
 }
 
 // ---- the f16 filter: rows STORED as f16 are exact MFMA operands ("f16 rows") --------------------------------
@@ -491,14 +563,15 @@ __global__ __launch_bounds__(256) void flat_f16_queries_kernel(const float *__re
 }
 
 // flat_split_filter_kernel's job, grid, tile and epilogue over x f16 [..][D].  VEC: D % 8 == 0 and x aligned to 16 bytes.
-template <bool VEC>
-__global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const _Float16 *__restrict__ qh, const _Float16 *__restrict__ ql, int B,
+template <bool VEC, bool MAPPED>
+__device__ __forceinline__ void flat_f16_filter_tile(int metric, const _Float16 *__restrict__ qh, const _Float16 *__restrict__ ql, int B,
                                                              int D, int Dp, const _Float16 *__restrict__ x, const float *__restrict__ norms,
                                                              int64_t S, int64_t stride, const uint32_t *__restrict__ valid,
                                                              const float *__restrict__ qnorm, const float *__restrict__ qscale,
                                                              const float *__restrict__ qflush, const float *__restrict__ thr, float c_rel,
                                                              float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap,
-                                                             int n_qtiles, float *__restrict__ scores) {
+                                                             int n_qtiles, float *__restrict__ scores, const int32_t *__restrict__ rows,
+                                                             int64_t N) {
     __shared__ __attribute__((aligned(16))) _Float16 As[kFlatTile * kSplitLd];
     __shared__ __attribute__((aligned(16))) _Float16 Bh[kFlatTile * kSplitLd];
     __shared__ __attribute__((aligned(16))) _Float16 Bl[kFlatTile * kSplitLd];
@@ -506,12 +579,15 @@ __global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const 
     __shared__ int oks[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
-    flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
+    if constexpr (MAPPED) flat_tile_rows_mapped(tid, r0, S, stride, rows, N, norms, oks, nxs);
+    else flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
     const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
     const int l31 = lane & 31, lh = lane >> 5;
     const _Float16 *const xp[1] = {x}, *const qp[2] = {qh, ql};
     _Float16 *const ap[1] = {As}, *const bp[2] = {Bh, Bl};
-    const auto row_of = [&](int rl) { return FlatRow{oks[rl] != 0, (int32_t)((r0 + rl) * stride), r0 + rl < S, r0 + rl}; };
+    const auto row_of = [&](int rl) {
+        return FlatRow{flat_row_listed<MAPPED>(oks, rl), flat_row_value<MAPPED>(oks, rl, r0, stride), r0 + rl < S, r0 + rl};
+    };
     for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
         const int q0 = qt * kFlatTile;
         FlatAcc acc;
@@ -520,14 +596,14 @@ __global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const 
             __syncthreads();  // the previous stage is consumed (first pass: the row tile's norms and flags are written)
             // rows: f16 from HBM as they are
             if constexpr (VEC) {
-                flat_stage_planes<f16x8>(tid, k0, D, xp, ap, [&](int r) { return FlatSlot{r0 + r < S, (r0 + r) * stride * D}; });
+                flat_stage_planes<f16x8>(tid, k0, D, xp, ap, [&](int r) { return flat_row_slot<MAPPED>(oks, r, r0, S, stride, D); });
             } else {
 #pragma unroll 4
                 for (int i = 0; i < kSplitDepth / 2; ++i) {
                     const int e = tid + i * 256;  // single values
                     const int r = e / kSplitDepth, c = e % kSplitDepth;
-                    const int64_t rr = r0 + r;
-                    As[r * kSplitLd + c] = (rr < S && k0 + c < D) ? x[rr * stride * D + k0 + c] : (_Float16)0.f;
+                    const FlatSlot sa = flat_row_slot<MAPPED>(oks, r, r0, S, stride, D);
+                    As[r * kSplitLd + c] = (sa.ok && k0 + c < D) ? x[sa.off + k0 + c] : (_Float16)0.f;
                 }
             }
             // queries: the planes of flat_f16_queries_kernel (Dp is a multiple of 8 coordinates)
@@ -563,6 +639,26 @@ __global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const 
                                          row_of);
         }
     }
+}
+// The kernel over the table (what ran before there were lists), and the MAPPED one over a list of selected rows.
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_f16_filter_kernel(int metric, const _Float16 *__restrict__ qh, const _Float16 *__restrict__ ql, int B,
+                             int D, int Dp, const _Float16 *__restrict__ x, const float *__restrict__ norms, int64_t S, int64_t stride,
+                             const uint32_t *__restrict__ valid, const float *__restrict__ qnorm, const float *__restrict__ qscale,
+                             const float *__restrict__ qflush, const float *__restrict__ thr, float c_rel, float c_abs, int32_t *__restrict__ cand,
+                             int32_t *__restrict__ cnt, int cap, int n_qtiles, float *__restrict__ scores) {
+    flat_f16_filter_tile<VEC, false>(metric, qh, ql, B, D, Dp, x, norms, S, stride, valid, qnorm, qscale, qflush, thr, c_rel, c_abs, cand, cnt, cap,
+                                     n_qtiles, scores, nullptr, 0);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_rows_f16_filter_kernel(int metric, const _Float16 *__restrict__ qh, const _Float16 *__restrict__ ql,
+                             int B, int D, int Dp, const _Float16 *__restrict__ x, const float *__restrict__ norms, int64_t S, int64_t stride,
+                             const uint32_t *__restrict__ valid, const float *__restrict__ qnorm, const float *__restrict__ qscale,
+                             const float *__restrict__ qflush, const float *__restrict__ thr, float c_rel, float c_abs, int32_t *__restrict__ cand,
+                             int32_t *__restrict__ cnt, int cap, int n_qtiles, float *__restrict__ scores, const int32_t *__restrict__ rows,
+                             int64_t N) {
+    flat_f16_filter_tile<VEC, true>(metric, qh, ql, B, D, Dp, x, norms, S, stride, valid, qnorm, qscale, qflush, thr, c_rel, c_abs, cand, cnt, cap,
+                                    n_qtiles, scores, rows, N);
 }
 
 // ---- the int8 filter: rows STORED as int8 codes, an exact-integer contraction ("int8 rows") -------------------
@@ -648,15 +744,16 @@ __global__ __launch_bounds__(256) void flat_i8_queries_kernel(const float *__res
 
 // flat_f16_filter_kernel's job, grid, 128 x 128 workgroup tile, epilogue and `scores` output over x int8 [..][D], on 8 waves of 64 rows x
 // 32 queries.  VEC: D % 16 == 0 and x aligned to 16 bytes.
-template <bool VEC>
-__global__ __launch_bounds__(kI8Threads) void flat_i8_filter_kernel(int metric, const int8_t *__restrict__ p0, const int8_t *__restrict__ p1,
+template <bool VEC, bool MAPPED>
+__device__ __forceinline__ void flat_i8_filter_tile(int metric, const int8_t *__restrict__ p0, const int8_t *__restrict__ p1,
                                                                    const int8_t *__restrict__ p2, int B, int D, int Dp,
                                                                    const int8_t *__restrict__ x, const float *__restrict__ norms, int64_t S,
                                                                    int64_t stride, const uint32_t *__restrict__ valid,
                                                                    const float *__restrict__ qnorm, const float *__restrict__ qscale,
                                                                    const float *__restrict__ qslack, const float *__restrict__ thr, float c_rel,
                                                                    float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap,
-                                                                   int n_qtiles, float *__restrict__ scores) {
+                                                                   int n_qtiles, float *__restrict__ scores, const int32_t *__restrict__ rows,
+                                                                   int64_t N) {
     __shared__ __attribute__((aligned(16))) int8_t As[kFlatTile * kI8Ld];
     __shared__ __attribute__((aligned(16))) int8_t B0[kFlatTile * kI8Ld];
     __shared__ __attribute__((aligned(16))) int8_t B1[kFlatTile * kI8Ld];
@@ -665,11 +762,14 @@ __global__ __launch_bounds__(kI8Threads) void flat_i8_filter_kernel(int metric, 
     __shared__ int oks[kFlatTile];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
-    flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
+    if constexpr (MAPPED) flat_tile_rows_mapped(tid, r0, S, stride, rows, N, norms, oks, nxs);
+    else flat_tile_rows(tid, r0, S, stride, valid, norms, oks, nxs);
     const int wr = (wave >> 2) * 64, wq = (wave & 3) * 32;
     const int l31 = lane & 31, lh = lane >> 5;
     const int sr = tid >> 2, sc = (tid & 3) * 16;  // the thread's slot of 16 bytes in a stage: 128 rows x 4 slots
-    const auto row_of = [&](int rl) { return FlatRow{oks[rl] != 0, (int32_t)((r0 + rl) * stride), r0 + rl < S, r0 + rl}; };
+    const auto row_of = [&](int rl) {
+        return FlatRow{flat_row_listed<MAPPED>(oks, rl), flat_row_value<MAPPED>(oks, rl, r0, stride), r0 + rl < S, r0 + rl};
+    };
     for (int qt = blockIdx.y; qt < n_qtiles; qt += gridDim.y) {
         const int q0 = qt * kFlatTile;
         i32x16 s0a, s0b, s1a, s1b, s2a, s2b;  // plane 0 / 1 / 2, rows wr .. wr + 31 (a) and wr + 32 .. wr + 63 (b)
@@ -680,16 +780,16 @@ __global__ __launch_bounds__(kI8Threads) void flat_i8_filter_kernel(int metric, 
             // rows: the bytes from HBM as they are
             if constexpr (VEC) {
                 i32x4 va = {0, 0, 0, 0};
-                const int64_t rr = r0 + sr;
-                if (rr < S && k0 + sc < D) va = *(const i32x4 *)(x + rr * stride * D + k0 + sc);
+                const FlatSlot sa = flat_row_slot<MAPPED>(oks, sr, r0, S, stride, D);
+                if (sa.ok && k0 + sc < D) va = *(const i32x4 *)(x + sa.off + k0 + sc);
                 *(i32x4 *)(As + sr * kI8Ld + sc) = va;
             } else {
 #pragma unroll 4
                 for (int i = 0; i < kFlatTile * kI8Depth / kI8Threads; ++i) {
                     const int e = tid + i * kI8Threads;  // single bytes
                     const int r = e / kI8Depth, c = e % kI8Depth;
-                    const int64_t rr = r0 + r;
-                    As[r * kI8Ld + c] = (rr < S && k0 + c < D) ? x[rr * stride * D + k0 + c] : (int8_t)0;
+                    const FlatSlot sa = flat_row_slot<MAPPED>(oks, r, r0, S, stride, D);
+                    As[r * kI8Ld + c] = (sa.ok && k0 + c < D) ? x[sa.off + k0 + c] : (int8_t)0;
                 }
             }
             // queries: the planes of flat_i8_queries_kernel, 16 bytes at a time (Dp is a multiple of 32 coordinates)
@@ -739,6 +839,26 @@ __global__ __launch_bounds__(kI8Threads) void flat_i8_filter_kernel(int metric, 
                 row_of);
         }
     }
+}
+// The kernel over the table (what ran before there were lists), and the MAPPED one over a list of selected rows.
+template <bool VEC>
+__global__ __launch_bounds__(kI8Threads) void flat_i8_filter_kernel(int metric, const int8_t *__restrict__ p0, const int8_t *__restrict__ p1,
+                             const int8_t *__restrict__ p2, int B, int D, int Dp, const int8_t *__restrict__ x, const float *__restrict__ norms,
+                             int64_t S, int64_t stride, const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
+                             const float *__restrict__ qscale, const float *__restrict__ qslack, const float *__restrict__ thr, float c_rel,
+                             float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles, float *__restrict__ scores) {
+    flat_i8_filter_tile<VEC, false>(metric, p0, p1, p2, B, D, Dp, x, norms, S, stride, valid, qnorm, qscale, qslack, thr, c_rel, c_abs, cand, cnt,
+                                    cap, n_qtiles, scores, nullptr, 0);
+}
+template <bool VEC>
+__global__ __launch_bounds__(kI8Threads) void flat_rows_i8_filter_kernel(int metric, const int8_t *__restrict__ p0, const int8_t *__restrict__ p1,
+                             const int8_t *__restrict__ p2, int B, int D, int Dp, const int8_t *__restrict__ x, const float *__restrict__ norms,
+                             int64_t S, int64_t stride, const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
+                             const float *__restrict__ qscale, const float *__restrict__ qslack, const float *__restrict__ thr, float c_rel,
+                             float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles, float *__restrict__ scores,
+                             const int32_t *__restrict__ rows, int64_t N) {
+    flat_i8_filter_tile<VEC, true>(metric, p0, p1, p2, B, D, Dp, x, norms, S, stride, valid, qnorm, qscale, qslack, thr, c_rel, c_abs, cand, cnt, cap,
+                                   n_qtiles, scores, rows, N);
 }
 
 // ---- exact distances + top-k, a wave per query, ties by ROW ID ---------------------------------------------------------------------
@@ -835,13 +955,15 @@ __device__ __forceinline__ void flat_exact_finish(const WaveList &L, int b, int 
     }
 }
 
-template <class T>
+// MAPPED (the `list == NULL` modes only): candidate c is rows[c * stride] of an ascending list of S selected offsets, not row c * stride.
+template <class T, bool MAPPED = false>
 __global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const T *__restrict__ x,
                                                         int64_t N, const int32_t *__restrict__ list, const int32_t *__restrict__ cnt, int cap,
                                                         int64_t S, int64_t stride, const uint32_t *__restrict__ valid, int k, int do_sqrt,
                                                         int final_list, int only_overflowed, float *__restrict__ thr_out,
                                                         float *__restrict__ out_d, int64_t *__restrict__ out_i, int32_t *__restrict__ ovf,
-                                                        uint32_t *__restrict__ ovf_total, float scale = 1.f) {
+                                                        uint32_t *__restrict__ ovf_total, float scale = 1.f,
+                                                        const int32_t *__restrict__ rows = nullptr) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
@@ -869,7 +991,10 @@ __global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float
     for (int64_t c0 = 0; c0 < n; c0 += 64) {
         const int64_t ci = c0 + lane;
         int64_t row = -1;
-        if (ci < n) row = lr ? (int64_t)lr[ci] : ci * stride;
+        if (ci < n) {
+            if constexpr (MAPPED) row = lr ? (int64_t)lr[ci] : (int64_t)rows[ci * stride];
+            else row = lr ? (int64_t)lr[ci] : ci * stride;
+        }
         flat_exact_chunk(metric, qr, D, x, N, valid, row, n - c0 < 64 ? (int)(n - c0) : 64, k - 1, lane, L, th, tl, scale);
     }
     flat_exact_finish(L, b, k, lane, do_sqrt, thr_out, out_d, out_i);
@@ -1218,6 +1343,12 @@ static dim3 ivf_flat_filter_grid(int64_t max_cell_rows, int64_t stride, int64_t 
         if (vec) hipLaunchKernelGGL(kernel<true>, grid, block, 0, st, __VA_ARGS__);                \
         else hipLaunchKernelGGL(kernel<false>, grid, block, 0, st, __VA_ARGS__);                   \
     } while (0)
+// kernel<VEC> over the table, or rows_kernel<VEC> over a list of selected rows -- the same arguments and, behind them, the list and N.
+#define FLAT_LAUNCH_VEC_MAPPED(vec, kernel, rows_kernel, rows, N, grid, block, st, ...)            \
+    do {                                                                                           \
+        if (rows) FLAT_LAUNCH_VEC(vec, rows_kernel, grid, block, st, __VA_ARGS__, rows, N);        \
+        else FLAT_LAUNCH_VEC(vec, kernel, grid, block, st, __VA_ARGS__);                           \
+    } while (0)
 
 // The slack's constants: u = 2^-24, and n_l, the terms of a lane's chain in the norms.
 constexpr double kFlatU = 5.9604644775390625e-08;
@@ -1231,13 +1362,14 @@ static void flat_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
 }
 
 static int flat_launch_filter(int metric, const float *q, int64_t B, int64_t D, const float *x, const float *norms, int64_t S, int64_t stride,
-                              const uint32_t *valid, const float *qnorm, const float *thr, int32_t *cand, int32_t *cnt, hipStream_t st) {
+                              const uint32_t *valid, const float *qnorm, const float *thr, int32_t *cand, int32_t *cnt, hipStream_t st,
+                              const int32_t *rows = nullptr, int64_t N = 0) {
     float c_rel, c_abs;
     flat_slack(metric, D, &c_rel, &c_abs);
     const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 4 == 0 && ((uintptr_t)q % 16 == 0) && ((uintptr_t)x % 16 == 0);
-    FLAT_LAUNCH_VEC(vec, flat_filter_kernel, g.grid, dim3(256), st, metric, q, (int)B, (int)D, x, norms, S, stride, valid, qnorm, thr, c_rel, c_abs,
-                    cand, cnt, kFlatCap, g.n_qt);
+    FLAT_LAUNCH_VEC_MAPPED(vec, flat_filter_kernel, flat_rows_filter_kernel, rows, N, g.grid, dim3(256), st, metric, q, (int)B, (int)D, x, norms, S,
+                           stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt);
     return launch_status("flat_filter_kernel");
 }
 
@@ -1276,13 +1408,13 @@ static int flat_split_prepare(const float *q, int64_t B, int64_t D, const float 
 
 static int flat_split_launch_filter(int metric, int64_t B, int64_t D, const float *x, const float *mu, const float *norms, int64_t S,
                                     int64_t stride, const uint32_t *valid, const FlatSplitWs &w, const float *thr, int32_t *cand,
-                                    int32_t *cnt, float *scores, hipStream_t st) {
+                                    int32_t *cnt, float *scores, hipStream_t st, const int32_t *rows = nullptr, int64_t N = 0) {
     float c_rel, c_abs;
     flat_split_slack(metric, D, &c_rel, &c_abs);
     const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)mu % 16 == 0);
-    FLAT_LAUNCH_VEC(vec, flat_split_filter_kernel, g.grid, dim3(256), st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, mu, norms, S, stride,
-                    valid, w.f.qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
+    FLAT_LAUNCH_VEC_MAPPED(vec, flat_split_filter_kernel, flat_rows_split_filter_kernel, rows, N, g.grid, dim3(256), st, metric, w.qh, w.ql, (int)B,
+                           (int)D, (int)w.Dp, x, mu, norms, S, stride, valid, w.f.qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
     return launch_status("flat_split_filter_kernel");
 }
 
@@ -1322,13 +1454,14 @@ static int flat_f16_prepare(const float *q, int64_t B, int64_t D, const FlatF16W
 
 static int flat_f16_launch_filter(int metric, int64_t B, int64_t D, const _Float16 *x, const float *norms, int64_t S, int64_t stride,
                                   const uint32_t *valid, const FlatF16Ws &w, const float *thr, int32_t *cand, int32_t *cnt, float *scores,
-                                  hipStream_t st) {
+                                  hipStream_t st, const int32_t *rows = nullptr, int64_t N = 0) {
     float c_rel, c_abs;
     flat_f16_slack(metric, D, &c_rel, &c_abs);
     const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 8 == 0 && ((uintptr_t)x % 16 == 0);
-    FLAT_LAUNCH_VEC(vec, flat_f16_filter_kernel, g.grid, dim3(256), st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, norms, S, stride, valid,
-                    w.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
+    FLAT_LAUNCH_VEC_MAPPED(vec, flat_f16_filter_kernel, flat_rows_f16_filter_kernel, rows, N, g.grid, dim3(256), st, metric, w.qh, w.ql, (int)B,
+                           (int)D, (int)w.Dp, x, norms, S, stride, valid, w.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs, cand, cnt, kFlatCap,
+                           g.n_qt, scores);
     return launch_status("flat_f16_filter_kernel");
 }
 
@@ -1371,13 +1504,14 @@ static int flat_i8_prepare(const float *q, int64_t B, int64_t D, float scale, co
 
 static int flat_i8_launch_filter(int metric, int64_t B, int64_t D, const int8_t *x, const float *norms, int64_t S, int64_t stride,
                                  const uint32_t *valid, const FlatI8Ws &w, const float *thr, int32_t *cand, int32_t *cnt, float *scores,
-                                 hipStream_t st) {
+                                 hipStream_t st, const int32_t *rows = nullptr, int64_t N = 0) {
     float c_rel, c_abs;
     flat_i8_slack(metric, D, &c_rel, &c_abs);
     const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 16 == 0 && ((uintptr_t)x % 16 == 0);
-    FLAT_LAUNCH_VEC(vec, flat_i8_filter_kernel, g.grid, dim3(kI8Threads), st, metric, w.p0, w.p1, w.p2, (int)B, (int)D, (int)w.Dp, x, norms, S,
-                    stride, valid, w.f.qnorm, w.qscale, w.qslack, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
+    FLAT_LAUNCH_VEC_MAPPED(vec, flat_i8_filter_kernel, flat_rows_i8_filter_kernel, rows, N, g.grid, dim3(kI8Threads), st, metric, w.p0, w.p1, w.p2,
+                           (int)B, (int)D, (int)w.Dp, x, norms, S, stride, valid, w.f.qnorm, w.qscale, w.qslack, thr, c_rel, c_abs, cand, cnt,
+                           kFlatCap, g.n_qt, scores);
     return launch_status("flat_i8_filter_kernel");
 }
 
@@ -1388,45 +1522,55 @@ static int flat_i8_launch_filter(int metric, int64_t B, int64_t D, const int8_t 
 template <class T, class Prepare, class Filter>
 static int flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const T *vectors_dev, int64_t N,
                               const uint32_t *valid_bits_dev, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, const FlatWs &w,
-                              hipStream_t st, float row_scale, Prepare &&prepare, Filter &&filter) {
+                              hipStream_t st, float row_scale, Prepare &&prepare, Filter &&filter, const int32_t *rows_dev = nullptr,
+                              int64_t n_sel = 0) {
+    // rows_dev != NULL ("selected rows"): the search runs over the n_sel offsets of that list as it runs over a
+    // table of n_sel rows -- M below --, every "row r" one indirection away (the MAPPED kernels); N stays the bound of an offset.
+    const int64_t M = rows_dev ? n_sel : N;
     const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
     const dim3 qgrid((unsigned)((B + 3) / 4));
     ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
-    if (N <= kFlatSample) {  // the first sample would be the whole table: exact sums over all rows
-        hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
-                           kFlatCap, N, (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 0, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale);
+    // exact sums over every stride-th of S rows of the set (flat_exact_kernel's `list == NULL` modes)
+    auto exact_set = [&](int64_t S, int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
+        if (rows_dev)
+            hipLaunchKernelGGL((flat_exact_kernel<T, true>), qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
+                               kFlatCap, S, stride, valid_bits_dev, (int)k, sqrt_out, 0, only_overflowed, thr_out, out_dist_dev, out_id_dev, w.ovf,
+                               w.ovf_total, row_scale, rows_dev);
+        else
+            hipLaunchKernelGGL((flat_exact_kernel<T, false>), qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
+                               kFlatCap, S, stride, valid_bits_dev, (int)k, sqrt_out, 0, only_overflowed, thr_out, out_dist_dev, out_id_dev, w.ovf,
+                               w.ovf_total, row_scale);
         return launch_status("flat_exact_kernel");
-    }
+    };
+    if (M <= kFlatSample)  // the first sample would be the whole set: exact sums over all its rows
+        return exact_set(M, 1, do_sqrt, 0, nullptr);
     int rc = prepare();
     if (rc != ANNLITE_OK) return rc;
-    // stage 0: the k-th smallest exact distance among kFlatSample rows spread over the table
-    hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap,
-                       kFlatSample, N / kFlatSample, valid_bits_dev, (int)k, 0, 0, 0, w.thr, nullptr, nullptr, w.ovf, w.ovf_total, row_scale);
-    if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
-    // stages 1 .. n: row sets growing by the same factor (<= kFlatGrowth) up to the whole table; each takes the bound of the one before
-    const double ratio = (double)N / (double)kFlatSample;
+    // stage 0: the k-th smallest exact distance among kFlatSample rows spread over the set
+    if ((rc = exact_set(kFlatSample, M / kFlatSample, 0, 0, w.thr)) != ANNLITE_OK) return rc;
+    // stages 1 .. n: row sets growing by the same factor (<= kFlatGrowth) up to the whole set; each takes the bound of the one before
+    const double ratio = (double)M / (double)kFlatSample;
     int n_stages = (int)ceil(log(ratio) / log(kFlatGrowth) - 1e-9);
     if (n_stages < 1) n_stages = 1;
     for (int s = 1; s <= n_stages; ++s) {
         int64_t stride = 1;
         if (s < n_stages) {
             const double want = (double)kFlatSample * pow(ratio, (double)s / n_stages);
-            stride = (int64_t)((double)N / want);
-            if (stride <= 1) continue;  // (as large as the table already: leave it to the last stage)
+            stride = (int64_t)((double)M / want);
+            if (stride <= 1) continue;  // (as large as the set already: leave it to the last stage)
         }
         const bool last = s == n_stages;
         ANNLITE_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)B * 4, st));
-        if ((rc = filter((N + stride - 1) / stride, stride)) != ANNLITE_OK) return rc;
+        if ((rc = filter((M + stride - 1) / stride, stride)) != ANNLITE_OK) return rc;
         // (a list that overflowed before the last stage still holds `cap` valid rows: the k-th of ANY k valid rows is a bound)
+        // (the lists hold offsets under either form: the re-rank is the unmapped kernel)
         hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt, kFlatCap,
                            (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr,
                            out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale);
         if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
     }
-    // queries whose last list overflowed: exact sums over all rows (the other waves leave at once)
-    hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr, kFlatCap, N,
-                       (int64_t)1, valid_bits_dev, (int)k, do_sqrt, 0, 1, nullptr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale);
-    return launch_status("flat_exact_kernel");
+    // queries whose last list overflowed: exact sums over all rows of the set (the other waves leave at once)
+    return exact_set(M, 1, do_sqrt, 1, nullptr);
 }
 
 // ---- cells: workspace, stages, launchers ---------------------------------------------------------------------------------------------
@@ -1832,6 +1976,139 @@ extern "C" int annlite_flat_search_topk_i8(int metric, const float *queries_dev,
         [&](int64_t S, int64_t stride) {
             return flat_i8_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st);
         });
+}
+
+// ---- selected rows: the searches above over an ascending list of offsets ("selected rows") ------------------------
+// One entry per job, dispatching over the four filters: what differs between them is the workspace's query planes, prepare() and the
+// launcher, all of which exist above.
+static size_t flat_rows_workspace(int filter, int64_t B, int64_t D) {
+    switch (filter) {
+    case ANNLITE_FLAT_FILTER_F32: return flat_carve(nullptr, B).bytes;
+    case ANNLITE_FLAT_FILTER_BF16X3: return flat_split_carve(nullptr, B, D).bytes;
+    case ANNLITE_FLAT_FILTER_F16X2: return flat_f16_carve(nullptr, B, D).bytes;
+    default: return flat_i8_carve(nullptr, B, D).bytes;
+    }
+}
+
+// what both entries ask of the filter, the shape and the list
+static int flat_rows_check(FlatEntry what, int filter, int metric, int64_t B, int64_t D, int64_t N, int64_t n_sel, int64_t arg, float row_scale,
+                           const float *centre_dev) {
+    ANNLITE_REQUIRE(filter >= ANNLITE_FLAT_FILTER_F32 && filter <= ANNLITE_FLAT_FILTER_I8X3, "bad filter %d", filter);
+    if (int rc = flat_check_shape(what, metric, B, D, N, arg, filter == ANNLITE_FLAT_FILTER_F32 ? (int64_t)INT32_MAX : kSplitMaxDim)) return rc;
+    ANNLITE_REQUIRE(n_sel >= 0 && n_sel <= N, "bad n_sel=%lld (0 .. N=%lld)", (long long)n_sel, (long long)N);
+    ANNLITE_REQUIRE(!centre_dev || (filter == ANNLITE_FLAT_FILTER_BF16X3 && metric == ANNLITE_METRIC_EUCLIDEAN),
+                    "a centre is for the bf16x3 filter and EUCLIDEAN only");
+    if (filter == ANNLITE_FLAT_FILTER_I8X3) ANNLITE_REQUIRE_I8_SCALE(row_scale);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_search_rows_workspace_bytes(int filter, int64_t n_sel, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    if (int rc = flat_rows_check(kFlatSearch, filter, ANNLITE_METRIC_EUCLIDEAN, B, D, n_sel, n_sel, k, 1.f, nullptr)) return rc;
+    *bytes = (int64_t)flat_rows_workspace(filter, B, D);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_search_topk_rows(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                                             float row_scale, const float *norms_dev, const float *centre_dev, int64_t N,
+                                             const int32_t *rows_dev, int64_t n_sel, int64_t k, int flags, float *out_dist_dev,
+                                             int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (int rc = flat_rows_check(kFlatSearch, filter, metric, B, D, N, n_sel, k, row_scale, centre_dev)) return rc;
+    if (B == 0) return ANNLITE_OK;
+    // (rows_dev also with n_sel = 0: a NULL list is the staged search's word for "the whole table")
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && rows_dev && (n_sel == 0 || (vectors_dev && norms_dev)),
+                    "null device pointer");
+    if (int rc = flat_check_workspace(workspace_bytes, flat_rows_workspace(filter, B, D))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // (no bitmap anywhere below: a row in the list is selected)
+    switch (filter) {
+    case ANNLITE_FLAT_FILTER_F32: {
+        const FlatWs w = flat_carve(workspace_dev, B);
+        const float *x = (const float *)vectors_dev;
+        return flat_search_staged(
+            metric, queries_dev, B, D, x, N, nullptr, k, flags, out_dist_dev, out_id_dev, w, st, 1.f,
+            [&]() { return annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream); },
+            [&](int64_t S, int64_t stride) {
+                return flat_launch_filter(metric, queries_dev, B, D, x, norms_dev, S, stride, nullptr, w.qnorm, w.thr, w.cand, w.cnt, st, rows_dev, N);
+            },
+            rows_dev, n_sel);
+    }
+    case ANNLITE_FLAT_FILTER_BF16X3: {
+        const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
+        const float *x = (const float *)vectors_dev;
+        return flat_search_staged(
+            metric, queries_dev, B, D, x, N, nullptr, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
+            [&]() { return flat_split_prepare(queries_dev, B, D, centre_dev, w, st); },
+            [&](int64_t S, int64_t stride) {
+                return flat_split_launch_filter(metric, B, D, x, centre_dev, norms_dev, S, stride, nullptr, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st,
+                                                rows_dev, N);
+            },
+            rows_dev, n_sel);
+    }
+    case ANNLITE_FLAT_FILTER_F16X2: {
+        const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
+        const _Float16 *x = (const _Float16 *)vectors_dev;
+        return flat_search_staged(
+            metric, queries_dev, B, D, x, N, nullptr, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
+            [&]() { return flat_f16_prepare(queries_dev, B, D, w, st); },
+            [&](int64_t S, int64_t stride) {
+                return flat_f16_launch_filter(metric, B, D, x, norms_dev, S, stride, nullptr, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st, rows_dev, N);
+            },
+            rows_dev, n_sel);
+    }
+    default: {
+        const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
+        const int8_t *x = (const int8_t *)vectors_dev;
+        return flat_search_staged(
+            metric, queries_dev, B, D, x, N, nullptr, k, flags, out_dist_dev, out_id_dev, w.f, st, row_scale,
+            [&]() { return flat_i8_prepare(queries_dev, B, D, row_scale, w, st); },
+            [&](int64_t S, int64_t stride) {
+                return flat_i8_launch_filter(metric, B, D, x, norms_dev, S, stride, nullptr, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st, rows_dev, N);
+            },
+            rows_dev, n_sel);
+    }
+    }
+}
+
+extern "C" int annlite_flat_filter_rows(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                                        float row_scale, const float *norms_dev, const float *centre_dev, int64_t N, const int32_t *rows_dev,
+                                        int64_t n_sel, int64_t stride, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
+                                        float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (int rc = flat_rows_check(kFlatStage, filter, metric, B, D, N, n_sel, stride, row_scale, centre_dev)) return rc;
+    ANNLITE_REQUIRE(!scores_dev || filter != ANNLITE_FLAT_FILTER_F32, "the f32 filter has no scores output");
+    if (B == 0 || n_sel == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && rows_dev && bounds_dev && cand_dev && count_dev && workspace_dev,
+                    "null device pointer");
+    if (int rc = flat_check_workspace(workspace_bytes, flat_rows_workspace(filter, B, D))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t S = (n_sel + stride - 1) / stride;
+    int rc;
+    switch (filter) {
+    case ANNLITE_FLAT_FILTER_F32: {
+        const FlatWs w = flat_carve(workspace_dev, B);
+        if ((rc = annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream)) != ANNLITE_OK) return rc;
+        return flat_launch_filter(metric, queries_dev, B, D, (const float *)vectors_dev, norms_dev, S, stride, nullptr, w.qnorm, bounds_dev, cand_dev,
+                                  count_dev, st, rows_dev, N);
+    }
+    case ANNLITE_FLAT_FILTER_BF16X3: {
+        const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
+        if ((rc = flat_split_prepare(queries_dev, B, D, centre_dev, w, st)) != ANNLITE_OK) return rc;
+        return flat_split_launch_filter(metric, B, D, (const float *)vectors_dev, centre_dev, norms_dev, S, stride, nullptr, w, bounds_dev, cand_dev,
+                                        count_dev, scores_dev, st, rows_dev, N);
+    }
+    case ANNLITE_FLAT_FILTER_F16X2: {
+        const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
+        if ((rc = flat_f16_prepare(queries_dev, B, D, w, st)) != ANNLITE_OK) return rc;
+        return flat_f16_launch_filter(metric, B, D, (const _Float16 *)vectors_dev, norms_dev, S, stride, nullptr, w, bounds_dev, cand_dev, count_dev,
+                                      scores_dev, st, rows_dev, N);
+    }
+    default: {
+        const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
+        if ((rc = flat_i8_prepare(queries_dev, B, D, row_scale, w, st)) != ANNLITE_OK) return rc;
+        return flat_i8_launch_filter(metric, B, D, (const int8_t *)vectors_dev, norms_dev, S, stride, nullptr, w, bounds_dev, cand_dev, count_dev,
+                                     scores_dev, st, rows_dev, N);
+    }
+    }
 }
 
 extern "C" int annlite_flat_overflow_count(const void *workspace_dev, void *stream, int64_t *count) {

@@ -102,6 +102,10 @@ class AnnLite:
     :param flat_filter: ``'f32'`` (default) or ``'bf16x3'``, with ``centre`` (``'mean'``, ``None`` or an array) (kwargs, same channel;
         the float indexes -- no ``n_subvectors`` --, dropped for the indexes over PQ codes, ignored with ``n_cells > 1``): the filter
         of the exact float search; ``'bf16x3'`` is the one for data with a large common offset (``FlatGpuIndex``)
+    :param filter_route: ``'mask'`` (default), ``'rows'`` or ``'auto'`` (kwarg, same channel; the float indexes, dropped for the indexes
+        over PQ codes): whether a filtered exact search over float vectors scans the table under the filter's bitmap or only the rows
+        the filter selects, compacted into a list first -- the same answer bit for bit (``FlatGpuIndex``; the float graph's exact
+        fallback and the cells' every-cell search inherit it)
     :param cell_filter: ``'f32'`` (default) or ``'bf16x3'`` (kwarg, same channel; ``n_cells > 1`` with ``ivf_prune=True`` and no
         ``n_subvectors``, dropped for every other index): the filter over the cell tiles of ``IvfFlatGpuIndex``; ``'bf16x3'`` centres
         every tile on its cell's centroid -- the one for data with a common offset, the same answer bit for bit
@@ -282,7 +286,7 @@ class AnnLite:
             return FlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
         if not (self._vq_codec is None and kw.get('graph')):
             kw.pop('filter_search', None)  # (the graph indexes' option: the other indexes over PQ codes answer a filter exactly)
-        for name in ('flat_filter', 'centre', 'cell_filter', 'int8_scale'):  # (the float indexes' options: nothing over PQ codes runs that filter)
+        for name in ('flat_filter', 'centre', 'cell_filter', 'int8_scale', 'filter_route'):  # (the float indexes' options: nothing over PQ codes runs that filter)
             kw.pop(name, None)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')

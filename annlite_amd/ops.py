@@ -1266,3 +1266,73 @@ def bitmap_page(bits: torch.Tensor, n_rows: int, n_words: int, first: int, count
     check(lib().annlite_bitmap_page(bits.data_ptr(), _ptr(and_bits), n_rows, n_words, first, count, out.data_ptr(), out.data_ptr() + 4 * count,
                                     ws.data_ptr(), ws.numel(), max_blocks, stream_ptr()), 'bitmap_page')
     return out[:count], out[count:]
+
+
+# ---------------------------------------------------------------------------------------------- selected rows
+def bitmap_rows(words: torch.Tensor, and_words: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+                out: Optional[torch.Tensor] = None, workspace: Optional[ScanWorkspace] = None, sync: bool = True):
+    """``annlite_bitmap_rows``: the rows ``< n_rows`` (default: every bit of ``words``) set in ``words`` (``& and_words`` where given;
+    i32 words) as ascending offsets in ``out`` i32 (made here by default, ``n_rows`` entries; a shorter one takes the first
+    ``out.numel()``).  Returns ``(rows, n)``: ``n`` the number of such rows -- also where ``out`` is shorter -- and ``rows =
+    out[:min(n, out.numel())]``.  Reading ``n`` synchronises; ``sync=False`` returns ``(out, count i64 [1] on the device)`` instead."""
+    _capi.require_gpu()
+    n_words = words.numel()
+    N = n_words * 32 if n_rows is None else int(n_rows)
+    _bitmap(words, (N + 31) // 32, 'words')
+    _bitmap(and_words, (N + 31) // 32, 'and_words')
+    dev = words.device
+    if out is None:
+        out = torch.empty((N,), dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.is_contiguous()
+    need = ctypes.c_int64(0)
+    check(lib().annlite_bitmap_rows_workspace_bytes(N, ctypes.byref(need)), 'bitmap_rows_workspace_bytes')
+    # (the count behind the block counts, 8-byte aligned: one buffer)
+    ws = (workspace or ScanWorkspace()).get(int(need.value) + 8, dev)
+    count = ws[int(need.value):int(need.value) + 8].view(torch.int64)
+    check(lib().annlite_bitmap_rows(words.data_ptr(), _ptr(and_words), N, n_words, out.data_ptr(), out.numel(), count.data_ptr(), ws.data_ptr(),
+                                    int(need.value), stream_ptr()), 'bitmap_rows')
+    if not sync:
+        return out, count
+    n = int(count.item())
+    return out[:min(n, out.numel())], n
+
+
+def flat_search_topk_rows(flat_filter: str, metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, rows: torch.Tensor,
+                          k: int, n_sel: Optional[int] = None, n_rows: Optional[int] = None, centre: Optional[torch.Tensor] = None,
+                          scale: float = 1.0, sqrt: bool = False, workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_flat_search_topk_rows``: ``flat_search_topk`` (``flat_filter`` ``'f32'``), ``_split`` (``'bf16x3'``), ``_f16``
+    (``'f16x2'``) or ``_i8`` (``'i8x3'``) over the ``n_sel`` (default: all) ascending offsets ``rows`` i32 instead of the table: the answer
+    of that search with the list's rows as its bitmap, bit for bit.  ``flat_overflow_count`` / ``flat_list_counts`` read this workspace
+    too."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    n_sel = rows.numel() if n_sel is None else int(n_sel)
+    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= n_sel
+    dev = queries.device
+    code = _capi.FLAT_FILTER[flat_filter]
+    ws = _flat_workspace('flat_search_rows_workspace_bytes', (code, n_sel, D, B, k), dev, workspace)
+    od, oi = _flat_topk_outputs(B, k, dev)
+    check(lib().annlite_flat_search_topk_rows(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(),
+                                              _ptr(centre), N, rows.data_ptr(), n_sel, int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_search_topk_rows')
+    return od, oi
+
+
+def flat_filter_rows(flat_filter: str, metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
+                     rows: torch.Tensor, n_sel: Optional[int] = None, n_rows: Optional[int] = None, centre: Optional[torch.Tensor] = None,
+                     scale: float = 1.0, stride: int = 1, scores: bool = False, workspace: Optional[ScanWorkspace] = None):
+    """``annlite_flat_filter_rows``: one stage of the ``flat_filter`` filter over every ``stride``-th of the ``n_sel`` offsets ``rows``:
+    ``(cand i32 [B, cap] -- offsets --, count i32 [B])`` and, with ``scores=True`` (not ``'f32'``), the filter's score of every
+    (query, stage row) pair by LIST POSITION, f32 [B, ceil(n_sel / stride)]."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    n_sel = rows.numel() if n_sel is None else int(n_sel)
+    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= n_sel
+    dev = queries.device
+    code = _capi.FLAT_FILTER[flat_filter]
+    ws = _flat_workspace('flat_search_rows_workspace_bytes', (code, n_sel, D, B, 1), dev, workspace)
+    cand, count, sc = _flat_lists(B, dev, (n_sel + stride - 1) // stride if scores else None)
+    check(lib().annlite_flat_filter_rows(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(),
+                                         _ptr(centre), N, rows.data_ptr(), n_sel, stride, bounds.data_ptr(), cand.data_ptr(), count.data_ptr(),
+                                         _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_filter_rows')
+    return (cand, count, sc) if scores else (cand, count)

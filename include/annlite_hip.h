@@ -635,6 +635,37 @@ ANNLITE_API int annlite_flat_search_topk_i8(int metric, const float *queries_dev
                                 float scale, const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
                                 float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* The same searches over SELECTED rows ("selected rows"): rows_dev i32 [n_sel], ascending offsets < N -- the set
+ * bits of a filter's bitmap (annlite_bitmap_rows) -- take the place of the table: the first sample, the filter stages and the overflow
+ * route run over the list as they run over a table of n_sel rows, each row one indirection away, so the work follows n_sel, not N.
+ * No bitmap is read: a row in the list is selected (an entry outside [0, N) is skipped).  The answer is, bit for bit, that of the search
+ * over the whole table with the list's rows as its bitmap.
+ *   filter       ANNLITE_FLAT_FILTER_*: the filter and with it the row type of vectors_dev -- F32 and BF16X3: f32 [N][D]; F16X2: f16;
+ *                I8X3: int8 codes of value row_scale * c (row_scale is read by I8X3 only)
+ *   norms_dev    the norms that filter takes in its table form (BF16X3 with a centre: annlite_flat_centred_norms)
+ *   centre_dev   BF16X3 + EUCLIDEAN: the centre, or NULL; every other filter: NULL
+ * replaces: the reference's filtered search (annlite/index.py: the offsets CellTable.query yields, handed to the index as `indices`). */
+#define ANNLITE_FLAT_FILTER_F32 0
+#define ANNLITE_FLAT_FILTER_BF16X3 1
+#define ANNLITE_FLAT_FILTER_F16X2 2
+#define ANNLITE_FLAT_FILTER_I8X3 3
+/* No reference counterpart. */
+ANNLITE_API int annlite_flat_search_rows_workspace_bytes(int filter, int64_t n_sel, int64_t D, int64_t B, int64_t k, int64_t *bytes);
+/* Outputs, order, padding, flags, lists and overflow route as annlite_flat_search_topk (annlite_flat_overflow_count and
+ * annlite_flat_list_counts read this workspace too); n_sel <= 4096: exact sums over the list, no filter.  rows_dev is never NULL. */
+ANNLITE_API int annlite_flat_search_topk_rows(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                                  float row_scale, const float *norms_dev, const float *centre_dev, int64_t N, const int32_t *rows_dev,
+                                  int64_t n_sel, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
+                                  size_t workspace_bytes, void *stream);
+/* ONE filter stage over every stride-th entry of the list (tests and measurements, as annlite_flat_filter_f16 / _i8 are over the
+ * table): cand_dev / count_dev / bounds_dev as annlite_flat_filter, the candidates OFFSETS; scores_dev (may be NULL; not with F32) f32
+ * [B][ceil(n_sel / stride)] receives the filter's score of every (query, stage row) pair BY LIST POSITION.  The queries are prepared
+ * into the workspace (annlite_flat_search_rows_workspace_bytes of the same filter, B, D) by this call.  No reference counterpart. */
+ANNLITE_API int annlite_flat_filter_rows(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                             float row_scale, const float *norms_dev, const float *centre_dev, int64_t N, const int32_t *rows_dev,
+                             int64_t n_sel, int64_t stride, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev, float *scores_dev,
+                             void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Cells over float vectors: the exact search above restricted to the rows of each query's P probed cells.
  * replaces: the reference's n_cells > 1 structure over its default float index -- AnnLite._cell_selection's consumers, one float
@@ -957,6 +988,17 @@ ANNLITE_API int annlite_order_page(const uint32_t *mask_dev, const uint32_t *row
 ANNLITE_API int annlite_bitmap_page(const uint32_t *bits_dev, const uint32_t *and_bits_dev, int64_t N, int64_t n_words, int64_t first,
                         int64_t count, int32_t *out_rows_dev, int32_t *out_n_dev, void *workspace, size_t workspace_bytes,
                         int max_blocks, void *stream);
+
+/* A bitmap as a list (bitmap_rows.hip; DESIGN.md section 3.6, "selected rows"): out_rows_dev i32 [0 .. min(n, out_capacity)) <- the
+ * offsets r < N whose bit is set in bits_dev (and in and_bits_dev, may be NULL; u32 [n_words] each, n_words * 32 >= N, N < 2^31),
+ * ASCENDING; out_n_dev i64 [1] <- n, the number of such rows, also where n > out_capacity (nothing is written at or behind
+ * out_capacity).  Bits at positions >= N are ignored.  Three stream-ordered launches -- set bits per workgroup of 1024 words, their
+ * prefix sum by one workgroup, the scatter --, no workgroup waits for another and no position depends on an atomic: the same input
+ * gives the same array.  workspace: annlite_bitmap_rows_workspace_bytes(N).
+ * replaces: CellTable.query's list of offsets (annlite/storage/table.py), as annlite_filter_eval replaces its WHERE clause. */
+ANNLITE_API int annlite_bitmap_rows_workspace_bytes(int64_t N, int64_t *bytes);
+ANNLITE_API int annlite_bitmap_rows(const uint32_t *bits_dev, const uint32_t *and_bits_dev, int64_t N, int64_t n_words, int32_t *out_rows_dev,
+                        int64_t out_capacity, int64_t *out_n_dev, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
