@@ -131,6 +131,9 @@ SYMBOLS = (
     'annlite_flat_search_rows_workspace_bytes',
     'annlite_flat_search_topk_rows',
     'annlite_flat_filter_rows',
+    'annlite_flat_search_grouped_workspace_bytes',
+    'annlite_flat_search_topk_grouped',
+    'annlite_flat_filter_grouped',
     'annlite_ivf_flat_stages',
     'annlite_ivf_flat_search_workspace_bytes',
     'annlite_ivf_flat_search_topk',
@@ -325,6 +328,11 @@ def lib() -> ctypes.CDLL:
     L.annlite_flat_search_rows_workspace_bytes.argtypes = [i32, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_flat_search_topk_rows.argtypes = [i32, i32, vp, i64, i64, vp, ctypes.c_float, vp, vp, i64, vp, i64, i64, i32, vp, vp, vp, sz, vp]
     L.annlite_flat_filter_rows.argtypes = [i32, i32, vp, i64, i64, vp, ctypes.c_float, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, sz, vp]
+    L.annlite_flat_search_grouped_workspace_bytes.argtypes = [i32, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_flat_search_topk_grouped.argtypes = [i32, i32, vp, i64, i64, vp, ctypes.c_float, vp, vp, i64, vp, vp, i64, i64, vp, i64, i32, vp, vp,
+                                                   vp, sz, vp]
+    L.annlite_flat_filter_grouped.argtypes = [i32, i32, vp, i64, i64, vp, ctypes.c_float, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp,
+                                              sz, vp]
     L.annlite_ivf_flat_stages.argtypes = [i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32)]
     L.annlite_ivf_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_ivf_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, vp,

@@ -46,7 +46,7 @@ import torch
 from ... import ops
 from ...enums import Metric
 from .base import str2dtype
-from .row_store import RowStoreIndex, empty_answer, float_from_key, float_order_key, like_input, pad_to_k
+from .row_store import RowStoreIndex, empty_answer, float_from_key, float_order_key, group_chunks, like_input, pad_to_k
 
 
 def flat_slack_constants(metric: Metric, dim: int) -> Tuple[np.float32, np.float32]:
@@ -405,6 +405,56 @@ class FlatGpuIndex(RowStoreIndex):
                 self.last_flat_filter = tag if N >= self.FILTER_MIN_ROWS else None
             else:
                 d, i = self._search_large_k(q, k, valid, N)
+        return like_input(is_np, d, i)
+
+    def search_batch_grouped(self, x, limit: int = 10, selections=(), group_of=()):
+        """``RowStoreIndex.search_batch_grouped`` in ONE launch for ``limit <= 64`` on a non-empty index (``last_filter_batch =
+        'grouped'``): the selections become a ``[G, n_words]`` mask tensor (``_filter_bits`` each, None: the live bitmap) and the
+        search is ``annlite_flat_search_topk_grouped`` with the index's row kind and filter -- full query tiles, one first sample per
+        query, a bit test per pair that passed the bound ("a filter per query").  Row b is, bit for bit, what
+        ``search_batch`` answers query b under its selection.  More than ``MAX_FILTER_GROUPS`` groups with queries: the queries are split
+        by group into several such launches.  ``limit > 64`` and an empty index take the looping form.  ``last_flat_filter`` and
+        ``last_overflowed`` as after ``search_batch``; the scan is over the table (``last_filter_route = 'mask'``)."""
+        k = int(limit)
+        assert k >= 1
+        if k > 64 or self._n_rows == 0:
+            return super().search_batch_grouped(x, limit=limit, selections=selections, group_of=group_of)
+        is_np = not isinstance(x, torch.Tensor)
+        q = self._pre(x)
+        B, N, dev = q.shape[0], self._n_rows, q.device
+        group = self._check_groups(B, selections, group_of)
+        self._overflowed = 0
+        self.last_flat_filter = None
+        self.last_filter_route = None
+        self.last_filter_batch = 'grouped'
+        if B == 0:
+            return like_input(is_np, *empty_answer(B, k, dev))
+        tag, norms, centre = self._kind.tag, self._norms, None
+        if self.flat_filter == 'bf16x3' and tag == 'f32':
+            tag = 'bf16x3'
+            if self._centred:
+                norms, centre = self._cnorms, self._centre_dev
+        d, i = None, None
+        for groups, queries, local in group_chunks(group, self.MAX_FILTER_GROUPS):
+            masks = torch.stack([self._valid if selections[int(g)] is None else self._filter_bits(selections[int(g)]) for g in groups]).contiguous()
+            at, qs = None, q
+            if queries is not None:
+                at = torch.as_tensor(queries, device=dev)
+                qs = q[at].contiguous()
+                if d is None:
+                    d, i = empty_answer(B, k, dev)
+            cd, ci = ops.flat_search_topk_grouped(tag, int(self.metric), qs, self._vectors, norms, masks,
+                                                  torch.as_tensor(local.astype(np.int32), device=dev), k, valid_bits=self._valid, n_rows=N,
+                                                  centre=centre, scale=self._i8_scale or 1.0, sqrt=self.metric == Metric.EUCLIDEAN,
+                                                  workspace=self._ws)
+            if at is None:
+                d, i = cd, ci
+                self._overflowed = None  # (read from the workspace when asked for: it costs a synchronisation)
+            else:
+                d[at], i[at] = cd, ci
+                self._overflowed += ops.flat_overflow_count(self._ws)  # (the next launch takes the counter over)
+        self.last_filter_route = 'mask'
+        self.last_flat_filter = tag if N >= self.FILTER_MIN_ROWS else None
         return like_input(is_np, d, i)
 
     def _gather_dist(self, q, cand):

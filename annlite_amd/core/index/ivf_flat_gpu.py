@@ -32,7 +32,7 @@ from ...enums import Metric
 from ..codec.vq import VQCodec
 from .cells import CellColumnMixin
 from .flat_gpu import FlatGpuIndex, is_f16, is_i8
-from .row_store import empty_answer, like_input, pad_to_k
+from .row_store import RowStoreIndex, empty_answer, like_input, pad_to_k
 
 
 class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
@@ -47,6 +47,8 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
     """
     FORMAT = 'annlite_amd.IvfFlatGpuIndex/1'
     CELL_FILTERS = ('f32', 'bf16x3')
+    # (a filter per query: one search_batch per group -- the pruned search stays the search it is under every selection)
+    search_batch_grouped = RowStoreIndex.search_batch_grouped
 
     def __init__(self, dim: int, vq_codec: Optional[VQCodec] = None, n_probe: Optional[int] = None, metric: Metric = Metric.COSINE,
                  cell_filter: str = 'f32', **kwargs):

@@ -72,6 +72,43 @@ def like_input(is_np: bool, d: torch.Tensor, i: torch.Tensor):
     return (d.cpu().numpy(), i.cpu().numpy()) if is_np else (d, i)
 
 
+# ---------------------------------------------------------------------- a filter per query: the grouping (pure, host)
+def group_filters(filters, n_queries: int):
+    """One filter per query -> ``(distinct, group_of)``: the distinct filters in the order they first appear -- equal ones (by ``==``)
+    are one group; ``{}`` and None are both "no filter", kept as None -- and i64 [B], the group of every query.  ``filters`` must
+    be a list or tuple of ``n_queries`` dicts / None, else ``ValueError``."""
+    if len(filters) != n_queries:
+        raise ValueError(f'filter is a list of {len(filters)} entries for {n_queries} queries: one filter per query')
+    distinct, group_of = [], np.empty((n_queries,), dtype=np.int64)
+    for b, flt in enumerate(filters):
+        if flt is not None and not isinstance(flt, dict):
+            raise ValueError(f'filter[{b}] is a {type(flt).__name__}: a dict, {{}} or None per query')
+        flt = flt or None
+        for g, have in enumerate(distinct):
+            if have == flt:
+                break
+        else:
+            g = len(distinct)
+            distinct.append(flt)
+        group_of[b] = g
+    return distinct, group_of
+
+
+def group_chunks(group_of: np.ndarray, max_groups: int):
+    """The launches of a grouped search that takes at most ``max_groups`` bitmaps at a time: ``[(groups, queries, local), ...]`` --
+    the ascending ids of up to ``max_groups`` groups THAT HAVE QUERIES, the ascending positions of their queries (None: every query,
+    where one launch takes them all) and those queries' group as an index into ``groups``."""
+    used = np.unique(group_of)
+    if used.size <= max_groups:
+        return [(used, None, np.searchsorted(used, group_of))]
+    out = []
+    for c0 in range(0, used.size, max_groups):
+        groups = used[c0:c0 + max_groups]
+        queries = np.nonzero(np.isin(group_of, groups))[0]
+        out.append((groups, queries, np.searchsorted(groups, group_of[queries])))
+    return out
+
+
 # ---------------------------------------------------------------------- the row store
 class RowStoreIndex(BaseIndex):
     FORMAT: str = ''                  # the `format` string of the index's files
@@ -85,6 +122,7 @@ class RowStoreIndex(BaseIndex):
         # device storage is allocated on first use: constructing an index (and the host-side error paths, e.g. "not trained")
         # needs no GPU
         self._drop_storage()
+        self.last_filter_batch = None  # 'grouped' / 'looped': how the last search_batch_grouped answered; None: none yet
 
     # ------------------------------------------------------------------ what a subclass provides
     def _columns(self) -> Dict[str, Optional[Tuple[tuple, torch.dtype]]]:
@@ -242,6 +280,48 @@ class RowStoreIndex(BaseIndex):
     # ------------------------------------------------------------------ search
     def search_batch(self, x, limit: int = 10, indices=None):
         raise NotImplementedError
+
+    MAX_FILTER_GROUPS = 64  # bitmaps per grouped launch (FlatGpuIndex): 64 masks are 8 MB at 1M rows, 80 MB at 10M
+
+    @staticmethod
+    def _check_groups(n_queries: int, selections, group_of) -> np.ndarray:
+        """``group_of`` as i64 [B] on the host, every entry in ``[0, len(selections))``, else ``ValueError``"""
+        g = np.asarray(group_of.cpu() if isinstance(group_of, torch.Tensor) else group_of, dtype=np.int64).reshape(-1)
+        if g.size != n_queries:
+            raise ValueError(f'group_of has {g.size} entries for {n_queries} queries')
+        if g.size and (int(g.min()) < 0 or int(g.max()) >= len(selections)):
+            raise ValueError(f'group_of must lie in [0, {len(selections)})')
+        return g
+
+    def search_batch_grouped(self, x, limit: int = 10, selections=(), group_of=()):
+        """A filter per query ("a filter per query"): ``selections`` is a sequence of G values, each anything
+        ``search_batch(indices=...)`` takes -- offsets, a ``RowMask``, None for no filter --, and query b is searched under
+        ``selections[group_of[b]]``.  ``(dists [B, limit], ids [B, limit])`` as ``search_batch`` returns them, every row what
+        ``search_batch`` answers that query under its selection, padded with (+inf, -1).
+
+        This is the form every index has: one ``search_batch`` per group that has queries (``last_filter_batch = 'looped'``), so a
+        pruned or graph search stays the search it is per group.  ``FlatGpuIndex`` answers ``limit <= 64`` in one launch."""
+        is_np = not isinstance(x, torch.Tensor)
+        xs = x.reshape(1, -1) if x.ndim == 1 else x
+        B, k = xs.shape[0], int(limit)
+        assert k >= 1
+        group = self._check_groups(B, selections, group_of)
+        self.last_filter_batch = 'looped'
+        out = None
+        for g in np.unique(group):
+            idx = np.nonzero(group == g)[0]
+            sel = selections[int(g)]
+            if sel is not None and len(sel) == 0:
+                continue  # (no rows: the padding is the answer)
+            gd, gi = self.search_batch(xs[idx if is_np else torch.as_tensor(idx, device=xs.device)], limit=k, indices=sel)
+            gd, gi = pad_to_k(torch.as_tensor(gd), torch.as_tensor(gi), k)
+            if out is None:
+                out = empty_answer(B, k, gd.device)
+            at = torch.as_tensor(idx, device=gd.device)
+            out[0][at], out[1][at] = gd[:, :k], gi[:, :k]
+        if out is None:
+            out = empty_answer(B, k, torch.device('cpu') if is_np else self._device())
+        return (out[0].numpy(), out[1].numpy()) if is_np else out
 
     def search(self, x, limit: int = 10, indices=None):
         """ONE query, reference signature (hnsw/index.py:139-167): ``(dists[k'], ids[k'])`` numpy, ``k' <= limit`` valid entries

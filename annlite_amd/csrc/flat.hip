@@ -18,7 +18,9 @@
 //   FLAT_BF16X3_CONTRACT                                         the split filter's 12-MFMA K loop (a macro: see there)
 //   flat_tile_epilogue -> flat_admit                             C-tile row map, score, `scores`, the negated comparison, the append
 // The four table filters also run over a LIST of selected rows (flat_tile_rows_mapped, flat_row_slot: each body is a function of
-// <VEC, MAPPED> behind the table kernel and a flat_rows_* twin; DESIGN.md section 3.6, "selected rows").
+// <VEC, MAPPED> behind the table kernel and a flat_rows_* twin; DESIGN.md section 3.6, "selected rows"), and over the table with a
+// BITMAP PER QUERY (FlatGroups, the GROUPED mode of the same bodies and of flat_exact_kernel behind flat_grouped_* kernels; DESIGN.md
+// section 3.6, "a filter per query").
 // and on the host: WsBump (workspace carving), flat_filter_grid, FLAT_LAUNCH_VEC, flat_check_workspace, flat_check_shape.
 #include <math.h>
 
@@ -151,14 +153,31 @@ __device__ __forceinline__ void flat_admit(int32_t *cnt, int32_t *list, int cap,
 
 // What a lane holds of the ONE query it owns in a C tile: |q|^2, the bound, the per-query term of the slack (read by the kernels that
 // have one), the query's counter and list, and its row of the `scores` output (NULL: none).
+// mask: the GROUPED kernels' row bitmap of the query (below); the others neither set nor read it.
 struct FlatQuery {
     float qn, thr, extra;
     int32_t *cnt, *list;
     float *scores;
+    const uint32_t *mask;
 };
 __device__ __forceinline__ FlatQuery flat_query(int qi, float qn, const float *__restrict__ thr, float extra, int32_t *cand, int32_t *cnt,
-                                                int cap, float *scores, int64_t scores_ld) {
-    return {qn, thr[qi], extra, cnt + qi, cand + (int64_t)qi * cap, scores ? scores + (int64_t)qi * scores_ld : nullptr};
+                                                int cap, float *scores, int64_t scores_ld, const uint32_t *mask = nullptr) {
+    return {qn, thr[qi], extra, cnt + qi, cand + (int64_t)qi * cap, scores ? scores + (int64_t)qi * scores_ld : nullptr, mask};
+}
+
+// A filter per query ("a filter per query"): masks u32 [G][ld] are G row bitmaps in `valid`'s word layout (bit r
+// of row g: table row r is selected by filter g AND live), group i32 [B] names the bitmap of every query.  The GROUPED kernels prepare
+// their row tiles from `valid` -- the union -- as ever, and a (query, row) pair is admitted only if the row's bit is set in the QUERY's
+// bitmap.  A group id outside [0, G) selects nothing (no bitmap is read for it).  Over the table only: never with MAPPED.
+struct FlatGroups {
+    const uint32_t *masks;
+    int64_t ld;
+    int G;
+    const int32_t *group;
+};
+__device__ __forceinline__ const uint32_t *flat_group_mask(const FlatGroups &g, int qi) {
+    const int gi = g.group[qi];
+    return (unsigned)gi < (unsigned)g.G ? g.masks + (int64_t)gi * g.ld : nullptr;
 }
 
 // A tile row as the epilogue sees it: is it offered to the lists and as which value; does its score go to the `scores` row and to
@@ -173,8 +192,9 @@ struct FlatRow {
 // THE epilogue of a 32 x 32 C tile whose first row is tile row rt: score, `scores`, comparison, append.  dot_of(reg): the f32 dot
 // product of the lane's accumulator element reg; row_of(rl): the FlatRow of tile row rl.  EXTRA: the slack has the per-query term.
 // SCORE_UNLISTED: the kernel's `scores` output also takes rows that are not listed (the table kernels that have one); without it such a
-// row is left before any arithmetic.
-template <bool EXTRA, bool SCORE_UNLISTED, class Dot, class Row>
+// row is left before any arithmetic.  GROUPED: a pair that passed the bound is admitted only if bit row.value (the table row) is set in
+// Q.mask -- tested BEHIND the comparison, so only the few pairs that pass the bound pay the load; a NULL mask admits nothing.
+template <bool EXTRA, bool SCORE_UNLISTED, bool GROUPED = false, class Dot, class Row>
 __device__ __forceinline__ void flat_tile_epilogue(int metric, float c_rel, float c_abs, int cap, const FlatQuery &Q, const float *nxs, int rt,
                                                    int lh, Dot &&dot_of, Row &&row_of) {
 #pragma unroll
@@ -190,7 +210,16 @@ __device__ __forceinline__ void flat_tile_epilogue(int metric, float c_rel, floa
         float bound;
         if constexpr (EXTRA) bound = Q.thr + ((c_rel * a + c_abs) + Q.extra);
         else bound = Q.thr + (c_rel * a + c_abs);
-        if (!(v > bound)) flat_admit(Q.cnt, Q.list, cap, row.value);
+        if (!(v > bound)) {
+            if constexpr (GROUPED) {
+                // (opaque to the optimiser: left visible, the word offsets of a wave's 64 tile rows are computed once ahead of the
+                // 2 x 2 C tiles and kept live across them -- about 100 VGPRs, one workgroup per CU where the ungrouped kernel has two)
+                int32_t rv = row.value;
+                asm volatile("" : "+v"(rv));
+                if (!Q.mask || !((Q.mask[rv >> 5] >> (rv & 31)) & 1u)) continue;
+            }
+            flat_admit(Q.cnt, Q.list, cap, row.value);
+        }
     }
 }
 
@@ -242,13 +271,14 @@ __device__ __forceinline__ void flat_f32_contract(const float *As, const float *
 
 // MAPPED (every table filter kernel has the flag): the stage rows are the entries of `rows`, offsets < N (flat_tile_rows_mapped); `valid`
 // is not read.  Without the flag `rows` and N are not read.
-template <bool VEC, bool MAPPED>
+template <bool VEC, bool MAPPED, bool GROUPED = false>
 __device__ __forceinline__ void flat_filter_tile(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
                                                          const float *__restrict__ norms, int64_t S, int64_t stride,
                                                          const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
                                                          const float *__restrict__ thr, float c_rel, float c_abs,
                                                          int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles,
-                                                         const int32_t *__restrict__ rows, int64_t N) {
+                                                         const int32_t *__restrict__ rows, int64_t N, const FlatGroups grp = {}) {
+    static_assert(!(MAPPED && GROUPED), "the grouped mode is over the table only");
     __shared__ float As[kFlatTile * kFlatLd];
     __shared__ float Bs[kFlatTile * kFlatLd];
     __shared__ float nxs[kFlatTile];
@@ -276,14 +306,18 @@ __device__ __forceinline__ void flat_filter_tile(int metric, const float *__rest
         for (int qj = 0; qj < 2; ++qj) {
             const int qi = q0 + wq + qj * 32 + l31;
             if (qi >= B) continue;
-            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, 0.f, cand, cnt, cap, nullptr, 0);
+            const uint32_t *mask = nullptr;
+            if constexpr (GROUPED) mask = flat_group_mask(grp, qi);
+            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, 0.f, cand, cnt, cap, nullptr, 0, mask);
 #pragma unroll
             for (int ri = 0; ri < 2; ++ri)
-                flat_tile_epilogue<false, false>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
+                flat_tile_epilogue<false, false, GROUPED>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh,
+                                                          [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
         }
     }
 }
-// The kernel over the table (what ran before there were lists), and the MAPPED one over a list of selected rows.
+// The kernel over the table (what ran before there were lists), the MAPPED one over a list of selected rows, and the GROUPED one over
+// the table with a bitmap per query.
 template <bool VEC>
 __global__ __launch_bounds__(256) void flat_filter_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
                              const float *__restrict__ norms, int64_t S, int64_t stride, const uint32_t *__restrict__ valid,
@@ -297,6 +331,14 @@ __global__ __launch_bounds__(256) void flat_rows_filter_kernel(int metric, const
                              const float *__restrict__ qnorm, const float *__restrict__ thr, float c_rel, float c_abs, int32_t *__restrict__ cand,
                              int32_t *__restrict__ cnt, int cap, int n_qtiles, const int32_t *__restrict__ rows, int64_t N) {
     flat_filter_tile<VEC, true>(metric, q, B, D, x, norms, S, stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, cap, n_qtiles, rows, N);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_grouped_filter_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+                             const float *__restrict__ norms, int64_t S, int64_t stride, const uint32_t *__restrict__ valid,
+                             const float *__restrict__ qnorm, const float *__restrict__ thr, float c_rel, float c_abs, int32_t *__restrict__ cand,
+                             int32_t *__restrict__ cnt, int cap, int n_qtiles, const FlatGroups grp) {
+    flat_filter_tile<VEC, false, true>(metric, q, B, D, x, norms, S, stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, cap, n_qtiles, nullptr, 0,
+                                       grp);
 }
 
 // ---- the split filter: the same scores from three bf16 MFMAs over CENTRED rows ("split filter") -----------
@@ -400,14 +442,16 @@ __device__ __forceinline__ void flat_stage_planes(int tid, int k0, int lim, cons
 
 // flat_filter_kernel's job, grid and tile.  scores != NULL (tests, measurements): v of every (query, stage row) pair goes to
 // scores f32 [B][S] as well.
-template <bool VEC, bool MAPPED>
+template <bool VEC, bool MAPPED, bool GROUPED = false>
 __device__ __forceinline__ void flat_split_filter_tile(int metric, const __bf16 *__restrict__ qh, const __bf16 *__restrict__ ql, int B,
                                                                int D, int Dp, const float *__restrict__ x, const float *__restrict__ mu,
                                                                const float *__restrict__ norms, int64_t S, int64_t stride,
                                                                const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
                                                                const float *__restrict__ thr, float c_rel, float c_abs,
                                                                int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles,
-                                                               float *__restrict__ scores, const int32_t *__restrict__ rows, int64_t N) {
+                                                               float *__restrict__ scores, const int32_t *__restrict__ rows, int64_t N,
+                                                               const FlatGroups grp = {}) {
+    static_assert(!(MAPPED && GROUPED), "the grouped mode is over the table only");
     __shared__ __attribute__((aligned(16))) __bf16 Ah[kFlatTile * kSplitLd];
     __shared__ __attribute__((aligned(16))) __bf16 Al[kFlatTile * kSplitLd];
     __shared__ __attribute__((aligned(16))) __bf16 Bh[kFlatTile * kSplitLd];
@@ -479,10 +523,13 @@ __device__ __forceinline__ void flat_split_filter_tile(int metric, const __bf16 
         for (int qj = 0; qj < 2; ++qj) {
             const int qi = q0 + wq + qj * 32 + l31;
             if (qi >= B) continue;
-            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, 0.f, cand, cnt, cap, scores, S);
+            const uint32_t *mask = nullptr;
+            if constexpr (GROUPED) mask = flat_group_mask(grp, qi);
+            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, 0.f, cand, cnt, cap, scores, S, mask);
 #pragma unroll
             for (int ri = 0; ri < 2; ++ri)
-                flat_tile_epilogue<false, true>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
+                flat_tile_epilogue<false, true, GROUPED>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh,
+                                                         [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
         }
     }
 }
@@ -504,6 +551,15 @@ __global__ __launch_bounds__(256) void flat_rows_split_filter_kernel(int metric,
                              float *__restrict__ scores, const int32_t *__restrict__ rows, int64_t N) {
     flat_split_filter_tile<VEC, true>(metric, qh, ql, B, D, Dp, x, mu, norms, S, stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, cap, n_qtiles,
                                       scores, rows, N);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_grouped_split_filter_kernel(int metric, const __bf16 *__restrict__ qh, const __bf16 *__restrict__ ql,
+                             int B, int D, int Dp, const float *__restrict__ x, const float *__restrict__ mu, const float *__restrict__ norms,
+                             int64_t S, int64_t stride, const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
+                             const float *__restrict__ thr, float c_rel, float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap,
+                             int n_qtiles, float *__restrict__ scores, const FlatGroups grp) {
+    flat_split_filter_tile<VEC, false, true>(metric, qh, ql, B, D, Dp, x, mu, norms, S, stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, cap,
+                                             n_qtiles, scores, nullptr, 0, grp);
 }
 
 // ---- the f16 filter: rows STORED as f16 are exact MFMA operands ("f16 rows") --------------------------------
@@ -563,7 +619,7 @@ __global__ __launch_bounds__(256) void flat_f16_queries_kernel(const float *__re
 }
 
 // flat_split_filter_kernel's job, grid, tile and epilogue over x f16 [..][D].  VEC: D % 8 == 0 and x aligned to 16 bytes.
-template <bool VEC, bool MAPPED>
+template <bool VEC, bool MAPPED, bool GROUPED = false>
 __device__ __forceinline__ void flat_f16_filter_tile(int metric, const _Float16 *__restrict__ qh, const _Float16 *__restrict__ ql, int B,
                                                              int D, int Dp, const _Float16 *__restrict__ x, const float *__restrict__ norms,
                                                              int64_t S, int64_t stride, const uint32_t *__restrict__ valid,
@@ -571,7 +627,8 @@ __device__ __forceinline__ void flat_f16_filter_tile(int metric, const _Float16 
                                                              const float *__restrict__ qflush, const float *__restrict__ thr, float c_rel,
                                                              float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap,
                                                              int n_qtiles, float *__restrict__ scores, const int32_t *__restrict__ rows,
-                                                             int64_t N) {
+                                                             int64_t N, const FlatGroups grp = {}) {
+    static_assert(!(MAPPED && GROUPED), "the grouped mode is over the table only");
     __shared__ __attribute__((aligned(16))) _Float16 As[kFlatTile * kSplitLd];
     __shared__ __attribute__((aligned(16))) _Float16 Bh[kFlatTile * kSplitLd];
     __shared__ __attribute__((aligned(16))) _Float16 Bl[kFlatTile * kSplitLd];
@@ -631,12 +688,14 @@ __device__ __forceinline__ void flat_f16_filter_tile(int metric, const _Float16 
         for (int qj = 0; qj < 2; ++qj) {
             const int qi = q0 + wq + qj * 32 + l31;
             if (qi >= B) continue;
-            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, qflush[qi], cand, cnt, cap, scores, S);
+            const uint32_t *mask = nullptr;
+            if constexpr (GROUPED) mask = flat_group_mask(grp, qi);
+            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, qflush[qi], cand, cnt, cap, scores, S, mask);
             const float down = qscale[qi];
 #pragma unroll
             for (int ri = 0; ri < 2; ++ri)
-                flat_tile_epilogue<true, true>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg] * down; },
-                                         row_of);
+                flat_tile_epilogue<true, true, GROUPED>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh,
+                                                        [&](int reg) { return acc.tile(ri, qj)[reg] * down; }, row_of);
         }
     }
 }
@@ -659,6 +718,15 @@ __global__ __launch_bounds__(256) void flat_rows_f16_filter_kernel(int metric, c
                              int64_t N) {
     flat_f16_filter_tile<VEC, true>(metric, qh, ql, B, D, Dp, x, norms, S, stride, valid, qnorm, qscale, qflush, thr, c_rel, c_abs, cand, cnt, cap,
                                     n_qtiles, scores, rows, N);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void flat_grouped_f16_filter_kernel(int metric, const _Float16 *__restrict__ qh, const _Float16 *__restrict__ ql,
+                             int B, int D, int Dp, const _Float16 *__restrict__ x, const float *__restrict__ norms, int64_t S, int64_t stride,
+                             const uint32_t *__restrict__ valid, const float *__restrict__ qnorm, const float *__restrict__ qscale,
+                             const float *__restrict__ qflush, const float *__restrict__ thr, float c_rel, float c_abs, int32_t *__restrict__ cand,
+                             int32_t *__restrict__ cnt, int cap, int n_qtiles, float *__restrict__ scores, const FlatGroups grp) {
+    flat_f16_filter_tile<VEC, false, true>(metric, qh, ql, B, D, Dp, x, norms, S, stride, valid, qnorm, qscale, qflush, thr, c_rel, c_abs, cand, cnt,
+                                           cap, n_qtiles, scores, nullptr, 0, grp);
 }
 
 // ---- the int8 filter: rows STORED as int8 codes, an exact-integer contraction ("int8 rows") -------------------
@@ -744,7 +812,7 @@ __global__ __launch_bounds__(256) void flat_i8_queries_kernel(const float *__res
 
 // flat_f16_filter_kernel's job, grid, 128 x 128 workgroup tile, epilogue and `scores` output over x int8 [..][D], on 8 waves of 64 rows x
 // 32 queries.  VEC: D % 16 == 0 and x aligned to 16 bytes.
-template <bool VEC, bool MAPPED>
+template <bool VEC, bool MAPPED, bool GROUPED = false>
 __device__ __forceinline__ void flat_i8_filter_tile(int metric, const int8_t *__restrict__ p0, const int8_t *__restrict__ p1,
                                                                    const int8_t *__restrict__ p2, int B, int D, int Dp,
                                                                    const int8_t *__restrict__ x, const float *__restrict__ norms, int64_t S,
@@ -753,7 +821,8 @@ __device__ __forceinline__ void flat_i8_filter_tile(int metric, const int8_t *__
                                                                    const float *__restrict__ qslack, const float *__restrict__ thr, float c_rel,
                                                                    float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap,
                                                                    int n_qtiles, float *__restrict__ scores, const int32_t *__restrict__ rows,
-                                                                   int64_t N) {
+                                                                   int64_t N, const FlatGroups grp = {}) {
+    static_assert(!(MAPPED && GROUPED), "the grouped mode is over the table only");
     __shared__ __attribute__((aligned(16))) int8_t As[kFlatTile * kI8Ld];
     __shared__ __attribute__((aligned(16))) int8_t B0[kFlatTile * kI8Ld];
     __shared__ __attribute__((aligned(16))) int8_t B1[kFlatTile * kI8Ld];
@@ -825,12 +894,14 @@ __device__ __forceinline__ void flat_i8_filter_tile(int metric, const int8_t *__
         // the three sums back into ONE integer, one conversion, the query's scale: that is this kernel's dot product.  A lane owns one query.
         const int qi = q0 + wq + l31;
         if (qi >= B) continue;
-        const FlatQuery Q = flat_query(qi, qnorm[qi], thr, qslack[qi], cand, cnt, cap, scores, S);
+        const uint32_t *mask = nullptr;
+        if constexpr (GROUPED) mask = flat_group_mask(grp, qi);
+        const FlatQuery Q = flat_query(qi, qnorm[qi], thr, qslack[qi], cand, cnt, cap, scores, S, mask);
         const float down = qscale[qi];
 #pragma unroll
         for (int ri = 0; ri < 2; ++ri) {
             const i32x16 &S0 = ri == 0 ? s0a : s0b, &S1 = ri == 0 ? s1a : s1b, &S2 = ri == 0 ? s2a : s2b;
-            flat_tile_epilogue<true, true>(
+            flat_tile_epilogue<true, true, GROUPED>(
                 metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh,
                 [&](int reg) {
                     const int64_t T = (int64_t)S2[reg] * 16384 + (int64_t)S1[reg] * 128 + (int64_t)S0[reg];  // = sum Q_j c_j, |T| < 2^43
@@ -859,6 +930,16 @@ __global__ __launch_bounds__(kI8Threads) void flat_rows_i8_filter_kernel(int met
                              const int32_t *__restrict__ rows, int64_t N) {
     flat_i8_filter_tile<VEC, true>(metric, p0, p1, p2, B, D, Dp, x, norms, S, stride, valid, qnorm, qscale, qslack, thr, c_rel, c_abs, cand, cnt, cap,
                                    n_qtiles, scores, rows, N);
+}
+template <bool VEC>
+__global__ __launch_bounds__(kI8Threads) void flat_grouped_i8_filter_kernel(int metric, const int8_t *__restrict__ p0, const int8_t *__restrict__ p1,
+                             const int8_t *__restrict__ p2, int B, int D, int Dp, const int8_t *__restrict__ x, const float *__restrict__ norms,
+                             int64_t S, int64_t stride, const uint32_t *__restrict__ valid, const float *__restrict__ qnorm,
+                             const float *__restrict__ qscale, const float *__restrict__ qslack, const float *__restrict__ thr, float c_rel,
+                             float c_abs, int32_t *__restrict__ cand, int32_t *__restrict__ cnt, int cap, int n_qtiles, float *__restrict__ scores,
+                             const FlatGroups grp) {
+    flat_i8_filter_tile<VEC, false, true>(metric, p0, p1, p2, B, D, Dp, x, norms, S, stride, valid, qnorm, qscale, qslack, thr, c_rel, c_abs, cand,
+                                          cnt, cap, n_qtiles, scores, nullptr, 0, grp);
 }
 
 // ---- exact distances + top-k, a wave per query, ties by ROW ID ---------------------------------------------------------------------
@@ -956,14 +1037,17 @@ __device__ __forceinline__ void flat_exact_finish(const WaveList &L, int b, int 
 }
 
 // MAPPED (the `list == NULL` modes only): candidate c is rows[c * stride] of an ascending list of S selected offsets, not row c * stride.
-template <class T, bool MAPPED = false>
+// GROUPED (every mode; never with MAPPED): wave b reads its query's bitmap grp.masks + grp.group[b] * grp.ld where the others read `valid`;
+// a query whose group id lies outside [0, G) is offered no row.
+template <class T, bool MAPPED = false, bool GROUPED = false>
 __global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const T *__restrict__ x,
                                                         int64_t N, const int32_t *__restrict__ list, const int32_t *__restrict__ cnt, int cap,
                                                         int64_t S, int64_t stride, const uint32_t *__restrict__ valid, int k, int do_sqrt,
                                                         int final_list, int only_overflowed, float *__restrict__ thr_out,
                                                         float *__restrict__ out_d, int64_t *__restrict__ out_i, int32_t *__restrict__ ovf,
                                                         uint32_t *__restrict__ ovf_total, float scale = 1.f,
-                                                        const int32_t *__restrict__ rows = nullptr) {
+                                                        const int32_t *__restrict__ rows = nullptr, const FlatGroups grp = {}) {
+    static_assert(!(MAPPED && GROUPED), "the grouped mode is over the table only");
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
@@ -982,6 +1066,10 @@ __global__ __launch_bounds__(256) void flat_exact_kernel(int metric, const float
     } else {
         if (only_overflowed && !ovf[b]) return;
         n = S;
+    }
+    if constexpr (GROUPED) {
+        valid = flat_group_mask(grp, b);
+        if (!valid) n = 0;  // (no bitmap: no row -- NULL is "every row" to the chunk below)
     }
     const float *qr = q + (int64_t)b * D;
     const int32_t *lr = list ? list + (int64_t)b * cap : nullptr;
@@ -1349,6 +1437,12 @@ static dim3 ivf_flat_filter_grid(int64_t max_cell_rows, int64_t stride, int64_t 
         if (rows) FLAT_LAUNCH_VEC(vec, rows_kernel, grid, block, st, __VA_ARGS__, rows, N);        \
         else FLAT_LAUNCH_VEC(vec, kernel, grid, block, st, __VA_ARGS__);                           \
     } while (0)
+// ... or grouped_kernel<VEC> over the table with a bitmap per query (grp.masks != NULL) -- the same arguments and, behind them, grp.
+#define FLAT_LAUNCH_VEC_MODE(vec, kernel, rows_kernel, grouped_kernel, rows, N, grp, grid, block, st, ...)             \
+    do {                                                                                                               \
+        if ((grp).masks) FLAT_LAUNCH_VEC(vec, grouped_kernel, grid, block, st, __VA_ARGS__, grp);                      \
+        else FLAT_LAUNCH_VEC_MAPPED(vec, kernel, rows_kernel, rows, N, grid, block, st, __VA_ARGS__);                  \
+    } while (0)
 
 // The slack's constants: u = 2^-24, and n_l, the terms of a lane's chain in the norms.
 constexpr double kFlatU = 5.9604644775390625e-08;
@@ -1363,13 +1457,13 @@ static void flat_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
 
 static int flat_launch_filter(int metric, const float *q, int64_t B, int64_t D, const float *x, const float *norms, int64_t S, int64_t stride,
                               const uint32_t *valid, const float *qnorm, const float *thr, int32_t *cand, int32_t *cnt, hipStream_t st,
-                              const int32_t *rows = nullptr, int64_t N = 0) {
+                              const int32_t *rows = nullptr, int64_t N = 0, const FlatGroups grp = {}) {
     float c_rel, c_abs;
     flat_slack(metric, D, &c_rel, &c_abs);
     const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 4 == 0 && ((uintptr_t)q % 16 == 0) && ((uintptr_t)x % 16 == 0);
-    FLAT_LAUNCH_VEC_MAPPED(vec, flat_filter_kernel, flat_rows_filter_kernel, rows, N, g.grid, dim3(256), st, metric, q, (int)B, (int)D, x, norms, S,
-                           stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt);
+    FLAT_LAUNCH_VEC_MODE(vec, flat_filter_kernel, flat_rows_filter_kernel, flat_grouped_filter_kernel, rows, N, grp, g.grid, dim3(256), st, metric, q,
+                         (int)B, (int)D, x, norms, S, stride, valid, qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt);
     return launch_status("flat_filter_kernel");
 }
 
@@ -1408,13 +1502,15 @@ static int flat_split_prepare(const float *q, int64_t B, int64_t D, const float 
 
 static int flat_split_launch_filter(int metric, int64_t B, int64_t D, const float *x, const float *mu, const float *norms, int64_t S,
                                     int64_t stride, const uint32_t *valid, const FlatSplitWs &w, const float *thr, int32_t *cand,
-                                    int32_t *cnt, float *scores, hipStream_t st, const int32_t *rows = nullptr, int64_t N = 0) {
+                                    int32_t *cnt, float *scores, hipStream_t st, const int32_t *rows = nullptr, int64_t N = 0,
+                                    const FlatGroups grp = {}) {
     float c_rel, c_abs;
     flat_split_slack(metric, D, &c_rel, &c_abs);
     const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)mu % 16 == 0);
-    FLAT_LAUNCH_VEC_MAPPED(vec, flat_split_filter_kernel, flat_rows_split_filter_kernel, rows, N, g.grid, dim3(256), st, metric, w.qh, w.ql, (int)B,
-                           (int)D, (int)w.Dp, x, mu, norms, S, stride, valid, w.f.qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
+    FLAT_LAUNCH_VEC_MODE(vec, flat_split_filter_kernel, flat_rows_split_filter_kernel, flat_grouped_split_filter_kernel, rows, N, grp, g.grid,
+                         dim3(256), st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, mu, norms, S, stride, valid, w.f.qnorm, thr, c_rel, c_abs,
+                         cand, cnt, kFlatCap, g.n_qt, scores);
     return launch_status("flat_split_filter_kernel");
 }
 
@@ -1454,14 +1550,14 @@ static int flat_f16_prepare(const float *q, int64_t B, int64_t D, const FlatF16W
 
 static int flat_f16_launch_filter(int metric, int64_t B, int64_t D, const _Float16 *x, const float *norms, int64_t S, int64_t stride,
                                   const uint32_t *valid, const FlatF16Ws &w, const float *thr, int32_t *cand, int32_t *cnt, float *scores,
-                                  hipStream_t st, const int32_t *rows = nullptr, int64_t N = 0) {
+                                  hipStream_t st, const int32_t *rows = nullptr, int64_t N = 0, const FlatGroups grp = {}) {
     float c_rel, c_abs;
     flat_f16_slack(metric, D, &c_rel, &c_abs);
     const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 8 == 0 && ((uintptr_t)x % 16 == 0);
-    FLAT_LAUNCH_VEC_MAPPED(vec, flat_f16_filter_kernel, flat_rows_f16_filter_kernel, rows, N, g.grid, dim3(256), st, metric, w.qh, w.ql, (int)B,
-                           (int)D, (int)w.Dp, x, norms, S, stride, valid, w.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs, cand, cnt, kFlatCap,
-                           g.n_qt, scores);
+    FLAT_LAUNCH_VEC_MODE(vec, flat_f16_filter_kernel, flat_rows_f16_filter_kernel, flat_grouped_f16_filter_kernel, rows, N, grp, g.grid, dim3(256),
+                         st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, norms, S, stride, valid, w.f.qnorm, w.qscale, w.qflush, thr, c_rel,
+                         c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
     return launch_status("flat_f16_filter_kernel");
 }
 
@@ -1504,14 +1600,14 @@ static int flat_i8_prepare(const float *q, int64_t B, int64_t D, float scale, co
 
 static int flat_i8_launch_filter(int metric, int64_t B, int64_t D, const int8_t *x, const float *norms, int64_t S, int64_t stride,
                                  const uint32_t *valid, const FlatI8Ws &w, const float *thr, int32_t *cand, int32_t *cnt, float *scores,
-                                 hipStream_t st, const int32_t *rows = nullptr, int64_t N = 0) {
+                                 hipStream_t st, const int32_t *rows = nullptr, int64_t N = 0, const FlatGroups grp = {}) {
     float c_rel, c_abs;
     flat_i8_slack(metric, D, &c_rel, &c_abs);
     const FlatGrid g = flat_filter_grid(S, B);
     const bool vec = D % 16 == 0 && ((uintptr_t)x % 16 == 0);
-    FLAT_LAUNCH_VEC_MAPPED(vec, flat_i8_filter_kernel, flat_rows_i8_filter_kernel, rows, N, g.grid, dim3(kI8Threads), st, metric, w.p0, w.p1, w.p2,
-                           (int)B, (int)D, (int)w.Dp, x, norms, S, stride, valid, w.f.qnorm, w.qscale, w.qslack, thr, c_rel, c_abs, cand, cnt,
-                           kFlatCap, g.n_qt, scores);
+    FLAT_LAUNCH_VEC_MODE(vec, flat_i8_filter_kernel, flat_rows_i8_filter_kernel, flat_grouped_i8_filter_kernel, rows, N, grp, g.grid,
+                         dim3(kI8Threads), st, metric, w.p0, w.p1, w.p2, (int)B, (int)D, (int)w.Dp, x, norms, S, stride, valid, w.f.qnorm, w.qscale,
+                         w.qslack, thr, c_rel, c_abs, cand, cnt, kFlatCap, g.n_qt, scores);
     return launch_status("flat_i8_filter_kernel");
 }
 
@@ -1523,16 +1619,24 @@ template <class T, class Prepare, class Filter>
 static int flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const T *vectors_dev, int64_t N,
                               const uint32_t *valid_bits_dev, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, const FlatWs &w,
                               hipStream_t st, float row_scale, Prepare &&prepare, Filter &&filter, const int32_t *rows_dev = nullptr,
-                              int64_t n_sel = 0) {
+                              int64_t n_sel = 0, const FlatGroups grp = {}) {
     // rows_dev != NULL ("selected rows"): the search runs over the n_sel offsets of that list as it runs over a
     // table of n_sel rows -- M below --, every "row r" one indirection away (the MAPPED kernels); N stays the bound of an offset.
+    // grp.masks != NULL ("a filter per query"; never with rows_dev): every exact launch is the GROUPED kernel -- a
+    // wave reads its query's bitmap where it reads valid_bits_dev otherwise -- and filter() launches the GROUPED tiles.  The stages, the
+    // lists and the overflow route are the same: a query whose bitmap keeps fewer than k sampled rows gets the bound +inf, overflows its
+    // list and is answered over all rows under its own bitmap.
     const int64_t M = rows_dev ? n_sel : N;
     const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
     const dim3 qgrid((unsigned)((B + 3) / 4));
     ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
     // exact sums over every stride-th of S rows of the set (flat_exact_kernel's `list == NULL` modes)
     auto exact_set = [&](int64_t S, int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
-        if (rows_dev)
+        if (grp.masks)
+            hipLaunchKernelGGL((flat_exact_kernel<T, false, true>), qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr,
+                               nullptr, kFlatCap, S, stride, valid_bits_dev, (int)k, sqrt_out, 0, only_overflowed, thr_out, out_dist_dev, out_id_dev,
+                               w.ovf, w.ovf_total, row_scale, nullptr, grp);
+        else if (rows_dev)
             hipLaunchKernelGGL((flat_exact_kernel<T, true>), qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
                                kFlatCap, S, stride, valid_bits_dev, (int)k, sqrt_out, 0, only_overflowed, thr_out, out_dist_dev, out_id_dev, w.ovf,
                                w.ovf_total, row_scale, rows_dev);
@@ -1564,9 +1668,14 @@ static int flat_search_staged(int metric, const float *queries_dev, int64_t B, i
         if ((rc = filter((M + stride - 1) / stride, stride)) != ANNLITE_OK) return rc;
         // (a list that overflowed before the last stage still holds `cap` valid rows: the k-th of ANY k valid rows is a bound)
         // (the lists hold offsets under either form: the re-rank is the unmapped kernel)
-        hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt, kFlatCap,
-                           (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr,
-                           out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale);
+        if (grp.masks)
+            hipLaunchKernelGGL((flat_exact_kernel<T, false, true>), qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand,
+                               w.cnt, kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0,
+                               last ? nullptr : w.thr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale, nullptr, grp);
+        else
+            hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt,
+                               kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr,
+                               out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale);
         if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
     }
     // queries whose last list overflowed: exact sums over all rows of the set (the other waves leave at once)
@@ -2107,6 +2216,130 @@ extern "C" int annlite_flat_filter_rows(int filter, int metric, const float *que
         if ((rc = flat_i8_prepare(queries_dev, B, D, row_scale, w, st)) != ANNLITE_OK) return rc;
         return flat_i8_launch_filter(metric, B, D, (const int8_t *)vectors_dev, norms_dev, S, stride, nullptr, w, bounds_dev, cand_dev, count_dev,
                                      scores_dev, st, rows_dev, N);
+    }
+    }
+}
+
+// ---- a filter per query: the searches above over the table with G bitmaps ("a filter per query") --------------------
+// One entry per job, dispatching over the four filters as the selected-rows entries do; the workspace is the filter's own carve.
+static int flat_grouped_check(FlatEntry what, int filter, int metric, int64_t B, int64_t D, int64_t N, int64_t mask_ld, int64_t G, int64_t arg,
+                              float row_scale, const float *centre_dev) {
+    if (int rc = flat_rows_check(what, filter, metric, B, D, N, 0, arg, row_scale, centre_dev)) return rc;
+    ANNLITE_REQUIRE(G >= 1 && G <= INT32_MAX, "bad G=%lld (>= 1)", (long long)G);
+    ANNLITE_REQUIRE(mask_ld >= 0 && mask_ld * 32 >= N, "bad mask_ld=%lld (32 mask_ld >= N=%lld)", (long long)mask_ld, (long long)N);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_search_grouped_workspace_bytes(int filter, int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    if (int rc = flat_rows_check(kFlatSearch, filter, ANNLITE_METRIC_EUCLIDEAN, B, D, N, 0, k, 1.f, nullptr)) return rc;
+    *bytes = (int64_t)flat_rows_workspace(filter, B, D);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_flat_search_topk_grouped(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                                                float row_scale, const float *norms_dev, const float *centre_dev, int64_t N,
+                                                const uint32_t *valid_bits_dev, const uint32_t *masks_dev, int64_t mask_ld, int64_t G,
+                                                const int32_t *group_dev, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev,
+                                                void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (int rc = flat_grouped_check(kFlatSearch, filter, metric, B, D, N, mask_ld, G, k, row_scale, centre_dev)) return rc;
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && masks_dev && group_dev && (N == 0 || (vectors_dev && norms_dev)),
+                    "null device pointer");
+    if (int rc = flat_check_workspace(workspace_bytes, flat_rows_workspace(filter, B, D))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const FlatGroups grp{masks_dev, mask_ld, (int)G, group_dev};
+    switch (filter) {
+    case ANNLITE_FLAT_FILTER_F32: {
+        const FlatWs w = flat_carve(workspace_dev, B);
+        const float *x = (const float *)vectors_dev;
+        return flat_search_staged(
+            metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w, st, 1.f,
+            [&]() { return annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream); },
+            [&](int64_t S, int64_t stride) {
+                return flat_launch_filter(metric, queries_dev, B, D, x, norms_dev, S, stride, valid_bits_dev, w.qnorm, w.thr, w.cand, w.cnt, st, nullptr,
+                                          0, grp);
+            },
+            nullptr, 0, grp);
+    }
+    case ANNLITE_FLAT_FILTER_BF16X3: {
+        const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
+        const float *x = (const float *)vectors_dev;
+        return flat_search_staged(
+            metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
+            [&]() { return flat_split_prepare(queries_dev, B, D, centre_dev, w, st); },
+            [&](int64_t S, int64_t stride) {
+                return flat_split_launch_filter(metric, B, D, x, centre_dev, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt,
+                                                nullptr, st, nullptr, 0, grp);
+            },
+            nullptr, 0, grp);
+    }
+    case ANNLITE_FLAT_FILTER_F16X2: {
+        const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
+        const _Float16 *x = (const _Float16 *)vectors_dev;
+        return flat_search_staged(
+            metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
+            [&]() { return flat_f16_prepare(queries_dev, B, D, w, st); },
+            [&](int64_t S, int64_t stride) {
+                return flat_f16_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st,
+                                              nullptr, 0, grp);
+            },
+            nullptr, 0, grp);
+    }
+    default: {
+        const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
+        const int8_t *x = (const int8_t *)vectors_dev;
+        return flat_search_staged(
+            metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, row_scale,
+            [&]() { return flat_i8_prepare(queries_dev, B, D, row_scale, w, st); },
+            [&](int64_t S, int64_t stride) {
+                return flat_i8_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st, nullptr,
+                                             0, grp);
+            },
+            nullptr, 0, grp);
+    }
+    }
+}
+
+extern "C" int annlite_flat_filter_grouped(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                                           float row_scale, const float *norms_dev, const float *centre_dev, int64_t N,
+                                           const uint32_t *valid_bits_dev, const uint32_t *masks_dev, int64_t mask_ld, int64_t G,
+                                           const int32_t *group_dev, int64_t stride, const float *bounds_dev, int32_t *cand_dev,
+                                           int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+    if (int rc = flat_grouped_check(kFlatStage, filter, metric, B, D, N, mask_ld, G, stride, row_scale, centre_dev)) return rc;
+    ANNLITE_REQUIRE(!scores_dev || filter != ANNLITE_FLAT_FILTER_F32, "the f32 filter has no scores output");
+    if (B == 0 || N == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && masks_dev && group_dev && bounds_dev && cand_dev && count_dev && workspace_dev,
+                    "null device pointer");
+    if (int rc = flat_check_workspace(workspace_bytes, flat_rows_workspace(filter, B, D))) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const FlatGroups grp{masks_dev, mask_ld, (int)G, group_dev};
+    const int64_t S = (N + stride - 1) / stride;
+    int rc;
+    switch (filter) {
+    case ANNLITE_FLAT_FILTER_F32: {
+        const FlatWs w = flat_carve(workspace_dev, B);
+        if ((rc = annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream)) != ANNLITE_OK) return rc;
+        return flat_launch_filter(metric, queries_dev, B, D, (const float *)vectors_dev, norms_dev, S, stride, valid_bits_dev, w.qnorm, bounds_dev,
+                                  cand_dev, count_dev, st, nullptr, 0, grp);
+    }
+    case ANNLITE_FLAT_FILTER_BF16X3: {
+        const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
+        if ((rc = flat_split_prepare(queries_dev, B, D, centre_dev, w, st)) != ANNLITE_OK) return rc;
+        return flat_split_launch_filter(metric, B, D, (const float *)vectors_dev, centre_dev, norms_dev, S, stride, valid_bits_dev, w, bounds_dev,
+                                        cand_dev, count_dev, scores_dev, st, nullptr, 0, grp);
+    }
+    case ANNLITE_FLAT_FILTER_F16X2: {
+        const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
+        if ((rc = flat_f16_prepare(queries_dev, B, D, w, st)) != ANNLITE_OK) return rc;
+        return flat_f16_launch_filter(metric, B, D, (const _Float16 *)vectors_dev, norms_dev, S, stride, valid_bits_dev, w, bounds_dev, cand_dev,
+                                      count_dev, scores_dev, st, nullptr, 0, grp);
+    }
+    default: {
+        const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
+        if ((rc = flat_i8_prepare(queries_dev, B, D, row_scale, w, st)) != ANNLITE_OK) return rc;
+        return flat_i8_launch_filter(metric, B, D, (const int8_t *)vectors_dev, norms_dev, S, stride, valid_bits_dev, w, bounds_dev, cand_dev,
+                                     count_dev, scores_dev, st, nullptr, 0, grp);
     }
     }
 }

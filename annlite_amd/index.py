@@ -45,7 +45,9 @@ those are kept as typed device arrays beside the vectors (``ColumnStore``, colum
 and ONE kernel evaluates it into the bitmap the indexes read (``annlite_filter_eval``).  The rows selected
 are the same; ``filter_eval='host'`` keeps the host path, ``last_filter_eval`` says which one answered.  ``filter()`` /
 ``get_docs()`` then select their page (``order_by``, ``offset``, ``limit``) on the device too (``ColumnStore.page``, DESIGN.md section
-3.10.1); ``last_filter_page`` says whether they did.
+3.10.1); ``last_filter_page`` says whether they did.  ``filter=`` of the searches may also be a list with a filter PER QUERY: equal
+filters form a group, each distinct one is evaluated once, and the float index answers the batch in one search under all of them
+(``search_batch_grouped``, DESIGN.md section 3.6, "a filter per query"; ``last_filter_batch`` / ``last_filter_groups``).
 """
 import hashlib
 import logging
@@ -62,6 +64,7 @@ from . import ops
 from .columns import ColumnStore, RowMask
 from .core.codec.pq import PQCodec
 from .core.index.pq_flat_gpu import PQFlatGpuIndex
+from .core.index.row_store import group_filters
 from .enums import Metric
 from .filter import select as _filter_select
 
@@ -244,6 +247,8 @@ class AnnLite:
         self._columns = ColumnStore(self.filterable_attrs)
         self.last_filter_eval = None  # 'gpu' / 'host': what evaluated the last filter (None: no filter yet)
         self.last_filter_page = None  # 'gpu' / 'host': what selected the last page of filter() / get_docs() (None: no call yet)
+        self.last_filter_batch = None   # 'grouped' / 'looped': how the last search with a filter PER QUERY was answered (None: one filter)
+        self.last_filter_groups = None  # the distinct filters of that search (None: `filter` was not a list)
 
         self._index_kwargs = dict(initial_size=initial_size, expand_step_size=expand_step_size, **kwargs)
         self._vec_indexes = [self._new_index()]
@@ -595,8 +600,40 @@ class AnnLite:
         self.last_filter_eval = 'host'
         return np.asarray(_filter_select(self._tags, filter), dtype=np.int64)
 
+    def _search_arrays_grouped(self, query_np, filters, group_of, limit):
+        """``_search_arrays`` with a filter per query: ``filters`` are the distinct ones (``group_filters``), each evaluated ONCE -- on
+        the device where it compiles, on the host where it does not --, and the vector index answers the batch under all of them
+        (``search_batch_grouped``; DESIGN.md section 3.6, "a filter per query").  ``[B, k]`` arrays, ``k = min(limit, index_size)``:
+        a query whose filter selects fewer rows has the (+inf, -1) tail the callers cut."""
+        B = query_np.shape[0]
+        selections, any_host = [], False
+        for flt in filters:
+            selections.append(self._filter_offsets(flt))
+            any_host = any_host or (flt is not None and self.last_filter_eval == 'host')
+        if any_host:
+            self.last_filter_eval = 'host'
+        k = min(int(limit), max(self.index_size, 0))
+        if k <= 0:
+            return np.full((B, 0), np.inf, np.float32), np.full((B, 0), -1, np.int64)
+        index = self.vec_index(0)
+        if not hasattr(index, 'search_batch_grouped'):
+            raise NotImplementedError(f'a filter per query is not implemented over {type(index).__name__} (devices=)')
+        d, i = index.search_batch_grouped(self._project(np.ascontiguousarray(query_np, dtype=np.float32)), limit=k, selections=selections,
+                                          group_of=group_of)
+        self.last_filter_batch = index.last_filter_batch
+        if isinstance(d, torch.Tensor):
+            d, i = d.cpu().numpy(), i.cpu().numpy()
+        return d, i
+
     def _search_arrays(self, query_np, filter, limit):
         self._sanity_check(query_np)
+        self.last_filter_batch = self.last_filter_groups = None
+        if isinstance(filter, (list, tuple)):  # a filter per query; all equal: the one-filter call below, as if it had been passed once
+            filters, group_of = group_filters(filter, query_np.shape[0])
+            self.last_filter_groups = len(filters)
+            if len(filters) > 1:
+                return self._search_arrays_grouped(query_np, filters, group_of, limit)
+            filter = filters[0] if filters else None
         indices = self._filter_offsets(filter)
         if indices is not None and len(indices) == 0:
             B = query_np.shape[0]
@@ -611,8 +648,9 @@ class AnnLite:
             d, i = d.cpu().numpy(), i.cpu().numpy()
         return d, i
 
-    def search(self, docs, filter: Optional[dict] = None, limit: int = 10, include_metadata: bool = True, **kwargs):
-        """index.py:334-359: attaches ``doc.matches`` in place; one batched GPU launch for all docs."""
+    def search(self, docs, filter: Union[dict, list, tuple, None] = None, limit: int = 10, include_metadata: bool = True, **kwargs):
+        """index.py:334-359: attaches ``doc.matches`` in place; one batched GPU launch for all docs.  ``filter``: one dict for the
+        batch, or a list / tuple with a filter (a dict, ``{}`` or None) PER DOCUMENT (``search_by_vectors``)."""
         if not self.is_trained:
             raise RuntimeError('The indexer is not trained, cannot add new documents')
         query_np = to_numpy_array(docs.embeddings)
@@ -661,8 +699,11 @@ class AnnLite:
         cnt = (i >= 0).sum(axis=1)
         return [d[b, :c] for b, c in enumerate(cnt)], [i[b, :c] for b, c in enumerate(cnt)]
 
-    def search_by_vectors(self, query_np, filter: Optional[dict] = None, limit: int = 10, include_metadata: bool = True):
-        """index.py:361-387 -> CellContainer.search_cells (container.py:201-235).  The per-query match lists are LAZY
+    def search_by_vectors(self, query_np, filter: Union[dict, list, tuple, None] = None, limit: int = 10, include_metadata: bool = True):
+        """index.py:361-387 -> CellContainer.search_cells (container.py:201-235).  ``filter`` may be a list or tuple of B entries, a
+        filter (a dict, ``{}`` or None) PER QUERY -- any other length is a ``ValueError``: query b is answered as the call for that
+        query alone with ``filter[b]`` is, the batch in one search where the index has one (``last_filter_batch``: ``'grouped'`` /
+        ``'looped'``; ``last_filter_groups``: the distinct filters, each evaluated once).  The per-query match lists are LAZY
         (``LazyMatches``: the documents are built when a list is first read -- same ids, scores and metadata as the
         reference's eager loop, which costs tens of milliseconds per 1024-query batch next to a 1.4 ms scan)."""
         d, i = self._search_arrays(query_np, filter, limit)
@@ -688,9 +729,10 @@ class AnnLite:
             self._offset2int = cache
         return cache
 
-    def search_numpy(self, query_np, filter: Dict = {}, limit: int = 10, **kwargs):
+    def search_numpy(self, query_np, filter: Union[Dict, list, tuple, None] = {}, limit: int = 10, **kwargs):
         """index.py:485-522: (list of dists[k], list of doc-id arrays).  Ids are returned as the
-        stored document ids converted with ``int`` like container.py:260."""
+        stored document ids converted with ``int`` like container.py:260.  ``filter``: one dict, or a filter per query
+        (``search_by_vectors``)."""
         if not self.is_trained:
             raise RuntimeError('The indexer is not trained, cannot add new documents')
         d, i = self._search_arrays(query_np, filter, limit)

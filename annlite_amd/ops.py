@@ -1336,3 +1336,52 @@ def flat_filter_rows(flat_filter: str, metric: int, queries: torch.Tensor, vecto
                                          _ptr(centre), N, rows.data_ptr(), n_sel, stride, bounds.data_ptr(), cand.data_ptr(), count.data_ptr(),
                                          _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_filter_rows')
     return (cand, count, sc) if scores else (cand, count)
+
+
+# ---------------------------------------------------------------------------------------------- a filter per query
+def _group_args(masks: torch.Tensor, group: torch.Tensor, B: int, N: int):
+    """``(masks, mask_ld, G, group)`` as the grouped entries take them: i32 [G, mask_ld] bitmaps, i32 [B] group ids"""
+    assert masks.dtype == torch.int32 and masks.ndim == 2 and masks.is_contiguous() and masks.shape[1] * 32 >= N
+    assert group.dtype == torch.int32 and group.is_contiguous() and group.numel() == B
+    return masks.data_ptr(), masks.shape[1], masks.shape[0], group.data_ptr()
+
+
+def flat_search_topk_grouped(flat_filter: str, metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, masks: torch.Tensor,
+                             group: torch.Tensor, k: int, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+                             centre: Optional[torch.Tensor] = None, scale: float = 1.0, sqrt: bool = False,
+                             workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_flat_search_topk_grouped``: ``flat_search_topk`` (``flat_filter`` ``'f32'``), ``_split`` (``'bf16x3'``), ``_f16``
+    (``'f16x2'``) or ``_i8`` (``'i8x3'``) with a bitmap per query: ``masks`` i32 [G, n_words] (each ANDed with the live bitmap by the
+    caller), ``group`` i32 [B] in ``[0, G)`` -- an id outside selects nothing.  Row b of the answer is that search's for query b with
+    ``masks[group[b]]`` as its bitmap, bit for bit.  ``valid_bits``: the live bitmap (which rows are scored at all).
+    ``flat_overflow_count`` / ``flat_list_counts`` read this workspace too."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    code = _capi.FLAT_FILTER[flat_filter]
+    ws = _flat_workspace('flat_search_grouped_workspace_bytes', (code, N, D, B, k), dev, workspace)
+    od, oi = _flat_topk_outputs(B, k, dev)
+    check(lib().annlite_flat_search_topk_grouped(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(),
+                                                 _ptr(centre), N, _ptr(valid_bits), *_group_args(masks, group, B, N), int(k), 1 if sqrt else 0,
+                                                 od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_search_topk_grouped')
+    return od, oi
+
+
+def flat_filter_grouped(flat_filter: str, metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
+                        masks: torch.Tensor, group: torch.Tensor, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+                        centre: Optional[torch.Tensor] = None, scale: float = 1.0, stride: int = 1, scores: bool = False,
+                        workspace: Optional[ScanWorkspace] = None):
+    """``annlite_flat_filter_grouped``: one stage of the ``flat_filter`` filter over every ``stride``-th row of the table with a bitmap
+    per query (``masks`` / ``group`` as ``flat_search_topk_grouped``): ``(cand i32 [B, cap], count i32 [B])`` and, with ``scores=True``
+    (not ``'f32'``), the filter's score of every (query, stage row) pair, f32 [B, ceil(N / stride)]."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    code = _capi.FLAT_FILTER[flat_filter]
+    ws = _flat_workspace('flat_search_grouped_workspace_bytes', (code, N, D, B, 1), dev, workspace)
+    cand, count, sc = _flat_lists(B, dev, (N + stride - 1) // stride if scores else None)
+    check(lib().annlite_flat_filter_grouped(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(),
+                                            _ptr(centre), N, _ptr(valid_bits), *_group_args(masks, group, B, N), stride, bounds.data_ptr(),
+                                            cand.data_ptr(), count.data_ptr(), _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()),
+          'flat_filter_grouped')
+    return (cand, count, sc) if scores else (cand, count)

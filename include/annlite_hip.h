@@ -666,6 +666,34 @@ ANNLITE_API int annlite_flat_filter_rows(int filter, int metric, const float *qu
                              int64_t n_sel, int64_t stride, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev, float *scores_dev,
                              void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* The same searches with A FILTER PER QUERY ("a filter per query"): one batch, G row bitmaps.
+ *   masks_dev    u32 [G][mask_ld], 32 mask_ld >= N: bitmap g in valid_bits_dev's word layout -- bit r set: row r is selected by filter g
+ *                AND live (the caller ANDs the live bitmap in)
+ *   group_dev    i32 [B]: the bitmap of every query, in [0, G).  A query whose id lies outside that range selects NOTHING: no bitmap
+ *                is read for it and its answer is all (+inf, -1)
+ *   valid_bits_dev  the table's live bitmap or NULL, as in the table searches: it only decides which rows of a row tile are staged
+ *                and scored (the union of the G selections); whether a (query, row) pair is admitted is decided by the query's bitmap
+ *   filter, vectors_dev, row_scale, norms_dev, centre_dev: as in the selected-rows entries above
+ * Query b's answer is, bit for bit, that of the filter's table search for that query with masks_dev[group_dev[b]] as its bitmap.  The
+ * stages, the lists and the overflow route are the table search's (annlite_flat_overflow_count and annlite_flat_list_counts read this
+ * workspace too): a query whose bitmap keeps fewer than k of the 4096 sampled rows takes the all-rows route under its own bitmap.
+ * replaces: one filtered search per distinct filter of a batch (annlite/index.py: `filter` is one dict per call).
+ * No reference counterpart. */
+ANNLITE_API int annlite_flat_search_grouped_workspace_bytes(int filter, int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes);
+ANNLITE_API int annlite_flat_search_topk_grouped(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                                     float row_scale, const float *norms_dev, const float *centre_dev, int64_t N,
+                                     const uint32_t *valid_bits_dev, const uint32_t *masks_dev, int64_t mask_ld, int64_t G,
+                                     const int32_t *group_dev, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev,
+                                     void *workspace_dev, size_t workspace_bytes, void *stream);
+/* ONE grouped filter stage over every stride-th row of the table (tests and measurements): cand_dev / count_dev / bounds_dev as
+ * annlite_flat_filter; scores_dev (may be NULL; not with F32) f32 [B][ceil(N / stride)] as the table stages have it.  The queries are
+ * prepared into the workspace (annlite_flat_search_grouped_workspace_bytes of the same filter, B, D) by this call. */
+ANNLITE_API int annlite_flat_filter_grouped(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                                float row_scale, const float *norms_dev, const float *centre_dev, int64_t N, const uint32_t *valid_bits_dev,
+                                const uint32_t *masks_dev, int64_t mask_ld, int64_t G, const int32_t *group_dev, int64_t stride,
+                                const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev, float *scores_dev, void *workspace_dev,
+                                size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Cells over float vectors: the exact search above restricted to the rows of each query's P probed cells.
  * replaces: the reference's n_cells > 1 structure over its default float index -- AnnLite._cell_selection's consumers, one float
