@@ -1,6 +1,6 @@
 """``annlite_bitmap_rows`` ("selected rows"): the set bits of a bitmap as an ascending list of offsets, against
 ``numpy.flatnonzero`` of the unpacked bits.  Sizes around a word (32 rows), around what one workgroup owns (1024 words = 32768 rows) and
-across many workgroups; bits behind the rows, a second bitmap, an output shorter than the selection, and the same array twice."""
+across many workgroups -- once across more than the scan takes in one pass (1024); bits behind the rows, a second bitmap, an output shorter than the selection, and the same array twice."""
 import numpy as np
 import pytest
 
@@ -61,6 +61,35 @@ def test_rows_are_flatnonzero_of_the_bits(ops, N):
             assert n == len(want), (pattern, N, tail, n, len(want))
             assert rows.dtype.is_floating_point is False and rows.numel() == n
             assert np.array_equal(rows.cpu().numpy(), want), (pattern, N, tail)
+
+
+@pytest.mark.parametrize('pattern', ['last', 'first', 'sparse'])
+def test_more_workgroup_counts_than_the_scan_takes_at_once(ops, pattern):
+    """N = 1024 * 32768 + 1: 1025 workgroup counts, so ``bitmap_rows_scan_kernel`` -- 1024 counts per pass -- runs a second pass and carries
+    the total of the first into it (300 001 rows are 10 counts: one pass).  The last workgroup owns row N - 1 alone.  Sparse selections
+    only: the output stays small."""
+    import torch
+
+    WG = 32768
+    N = 1024 * WG + 1
+    flags = np.zeros(N, dtype=bool)
+    if pattern == 'last':
+        flags[N - 1] = True
+    elif pattern == 'first':
+        flags[0] = True
+    else:  # about 1000 rows, some of them in the workgroups 0, 1023 and 1024
+        rs = np.random.RandomState(7)
+        flags[rs.randint(0, N, size=1000)] = True
+        flags[[5, WG - 1, 1023 * WG, 1023 * WG + 77, 1024 * WG - 1, N - 1]] = True
+    want = np.flatnonzero(flags)
+    assert len(want) <= 1006
+    for tail in (False, True):
+        words = ops.to_dev(_pack(flags, spare_words=2, tail=tail))
+        buf = torch.full((2048,), -7, dtype=torch.int32, device=words.device)
+        rows, n = ops.bitmap_rows(words, n_rows=N, out=buf)
+        assert n == len(want), (pattern, tail, n, len(want))
+        got = buf.cpu().numpy()
+        assert np.array_equal(got[:n], want) and (got[n:] == -7).all(), (pattern, tail)
 
 
 @pytest.mark.parametrize('N', [33, 32769, 300_001])
