@@ -133,7 +133,6 @@ class _RowKind(NamedTuple):
     topk: Callable         # ops.flat_search_topk(metric, queries, vectors, norms, k, ...) of the store and its filter
     tag: str               # that filter's name in ``last_flat_filter``
     stage: Callable        # one filter stage, (metric, queries, vectors, norms, bounds, ...) -> (cand, count, ...): the k > 64 search
-    stage_tag: str
 
 
 def _resolve_row_kind(kind: str, i8_scale: Optional[float], workspace) -> _RowKind:
@@ -141,12 +140,12 @@ def _resolve_row_kind(kind: str, i8_scale: Optional[float], workspace) -> _RowKi
         s = i8_scale
         return _RowKind(torch.int8, partial(quantise_i8, scale=s), partial(ops.flat_row_norms_i8, scale=s),
                        partial(ops.exact_gather_dist_i8, scale=s), partial(ops.flat_search_topk_i8, scale=s), 'i8x3',
-                       partial(ops.flat_filter_i8, scale=s, workspace=workspace), 'i8x3')
+                       partial(ops.flat_filter_i8, scale=s, workspace=workspace))
     if kind == 'f16':
         return _RowKind(torch.float16, _rows_f16, ops.flat_row_norms_f16, ops.exact_gather_dist_f16,
-                       ops.flat_search_topk_f16, 'f16x2', partial(ops.flat_filter_f16, workspace=workspace), 'f16x2')
+                       ops.flat_search_topk_f16, 'f16x2', partial(ops.flat_filter_f16, workspace=workspace))
     # (f32 rows have a second filter, 'bf16x3': ``flat_filter`` is read at every search, by search_batch)
-    return _RowKind(torch.float32, _rows_f32, ops.flat_row_norms, ops.exact_gather_dist, ops.flat_search_topk, 'f32', ops.flat_filter, 'f32')
+    return _RowKind(torch.float32, _rows_f32, ops.flat_row_norms, ops.exact_gather_dist, ops.flat_search_topk, 'f32', ops.flat_filter)
 
 
 class FlatGpuIndex(RowStoreIndex):
@@ -346,6 +345,16 @@ class FlatGpuIndex(RowStoreIndex):
             return 'rows'
         return 'rows' if n_sel <= self.ROWS_MAX_FRACTION * n_rows else 'mask'
 
+    def _filter_operands(self):
+        """``(tag, norms, centre)`` of the filter a ``limit <= 64`` search runs: the row kind's own or, over f32 rows with
+        ``flat_filter='bf16x3'``, the split filter with the centred norms and the centre where the index keeps one (k > 64: the f32 filter)."""
+        tag, norms, centre = self._kind.tag, self._norms, None
+        if self.flat_filter == 'bf16x3' and tag == 'f32':
+            tag = 'bf16x3'
+            if self._centred:
+                norms, centre = self._cnorms, self._centre_dev
+        return tag, norms, centre
+
     def _search_rows(self, q, k: int, valid, N: int, route: str):
         """The ``'rows'`` route of a k <= 64 search over the rows set in ``valid``; None where ``'auto'`` decides for the mask."""
         if self._sel_rows is None or self._sel_rows.numel() < self._capacity:
@@ -356,11 +365,7 @@ class FlatGpuIndex(RowStoreIndex):
         self.last_filter_route = 'rows'
         if n_sel == 0:
             return empty_answer(q.shape[0], k, q.device)
-        tag, norms, centre = self._kind.tag, self._norms, None
-        if self.flat_filter == 'bf16x3' and tag == 'f32':
-            tag = 'bf16x3'
-            if self._centred:
-                norms, centre = self._cnorms, self._centre_dev
+        tag, norms, centre = self._filter_operands()
         d, i = ops.flat_search_topk_rows(tag, int(self.metric), q, self._vectors, norms, self._sel_rows, k, n_sel=n_sel, n_rows=N, centre=centre,
                                          scale=self._i8_scale or 1.0, sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
         self._overflowed = None
@@ -395,10 +400,8 @@ class FlatGpuIndex(RowStoreIndex):
                 return like_input(is_np, d, i)
             self.last_filter_route = 'mask'
             if k <= 64:  # hnsw/index.py:164-165
-                topk, tag, norms = self._kind.topk, self._kind.tag, self._norms
-                if self.flat_filter == 'bf16x3' and tag == 'f32':  # (the split filter is over f32 rows; k > 64 keeps the f32 filter)
-                    centre = self._centre_dev if self._centred else None
-                    topk, tag, norms = partial(ops.flat_search_topk_split, centre=centre), 'bf16x3', self._cnorms if self._centred else norms
+                tag, norms, centre = self._filter_operands()
+                topk = partial(ops.flat_search_topk_split, centre=centre) if tag == 'bf16x3' else self._kind.topk
                 d, i = topk(int(self.metric), q, self._vectors, norms, k, valid_bits=valid, n_rows=N, sqrt=self.metric == Metric.EUCLIDEAN,
                             workspace=self._ws)
                 self._overflowed = None  # (read from the workspace when asked for: it costs a synchronisation)
@@ -429,11 +432,7 @@ class FlatGpuIndex(RowStoreIndex):
         self.last_filter_batch = 'grouped'
         if B == 0:
             return like_input(is_np, *empty_answer(B, k, dev))
-        tag, norms, centre = self._kind.tag, self._norms, None
-        if self.flat_filter == 'bf16x3' and tag == 'f32':
-            tag = 'bf16x3'
-            if self._centred:
-                norms, centre = self._cnorms, self._centre_dev
+        tag, norms, centre = self._filter_operands()
         d, i = None, None
         for groups, queries, local in group_chunks(group, self.MAX_FILTER_GROUPS):
             masks = torch.stack([self._valid if selections[int(g)] is None else self._filter_bits(selections[int(g)]) for g in groups]).contiguous()
@@ -514,7 +513,7 @@ class FlatGpuIndex(RowStoreIndex):
                               else torch.full((nb,), float('inf'), device=dev))
             bound = torch.cat(bounds).contiguous()  # (+inf -- fewer than k valid sampled rows, NaN distances -- passes everything)
             cand32, count = self._kind.stage(int(self.metric), q, self._vectors, self._norms, bound, valid_bits=valid, n_rows=N)[:2]
-            self.last_flat_filter = self._kind.stage_tag
+            self.last_flat_filter = self._kind.tag
             over = count > cap
             ok = torch.arange(cap, device=dev)[None, :] < count[:, None]
             cand = torch.where(ok, cand32.to(torch.int64), torch.full((1, 1), -1, dtype=torch.int64, device=dev))

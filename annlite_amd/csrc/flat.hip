@@ -21,7 +21,8 @@
 // <VEC, MAPPED> behind the table kernel and a flat_rows_* twin; DESIGN.md section 3.6, "selected rows"), and over the table with a
 // BITMAP PER QUERY (FlatGroups, the GROUPED mode of the same bodies and of flat_exact_kernel behind flat_grouped_* kernels; DESIGN.md
 // section 3.6, "a filter per query").
-// and on the host: WsBump (workspace carving), flat_filter_grid, FLAT_LAUNCH_VEC, flat_check_workspace, flat_check_shape.
+// and on the host: WsBump (workspace carving), flat_filter_grid, FLAT_LAUNCH_VEC, flat_check_workspace, flat_check_shape; for the table
+// filters one description per filter (FlatF32 ...), one struct of operands (FlatCall) and one body per job (flat_search, flat_stage).
 #include <math.h>
 
 #include <type_traits>
@@ -1611,47 +1612,151 @@ static int flat_i8_launch_filter(int metric, int64_t B, int64_t D, const int8_t 
     return launch_status("flat_i8_filter_kernel");
 }
 
-// ---- the stages of a search, shared by annlite_flat_search_topk and annlite_flat_search_topk_split: the small-
-// table shortcut, the first exact sample, filter stages over growing row sets, the re-rank of the lists and the route of an overflowed
-// list.  prepare(): what the filter needs from the queries, once per call; filter(S, stride): one filter launch into w.cand / w.cnt
-// against the bounds w.thr; row_scale: what one code step of an int8 row stands for (1 for the float row types, which do not read it). ----
-template <class T, class Prepare, class Filter>
-static int flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const T *vectors_dev, int64_t N,
-                              const uint32_t *valid_bits_dev, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, const FlatWs &w,
-                              hipStream_t st, float row_scale, Prepare &&prepare, Filter &&filter, const int32_t *rows_dev = nullptr,
-                              int64_t n_sel = 0, const FlatGroups grp = {}) {
-    // rows_dev != NULL ("selected rows"): the search runs over the n_sel offsets of that list as it runs over a
+// ---- one call's operands, and one description per filter ("the host routine") -----------------------------------
+// The row set of a call: the whole table (no list, no groups), a list of selected rows (no bitmap: a row in the list is selected), or
+// the table with a bitmap per query (groups, behind the live bitmap).
+enum FlatRowSet { kFlatTable, kFlatRows, kFlatGrouped };
+struct FlatCall {
+    FlatRowSet set;
+    int metric;
+    const float *q;
+    int64_t B, D;
+    const void *x;    // [N][D] of the filter's row type
+    float row_scale;  // what one code step of an int8 row stands for (the float row types do not read it)
+    const float *norms, *centre;
+    int64_t N;
+    const uint32_t *valid;
+    const int32_t *rows;  // kFlatRows: n_sel ascending offsets below N
+    int64_t n_sel;
+    FlatGroups grp;  // kFlatGrouped
+    hipStream_t st;
+    int64_t set_rows() const { return set == kFlatRows ? n_sel : N; }
+    bool set_given() const { return set == kFlatRows ? rows != nullptr : set == kFlatGrouped ? grp.masks && grp.group : true; }
+};
+
+// What a filter is to the host: its row type, its largest D, whether it takes a centre / reads an int8 scale / writes scores, its
+// workspace (base(): the FlatWs at its head), prepare() -- what the filter needs from the queries, once per call -- and launch(), one
+// filter stage over every stride-th of the set's rows (S of them) into cand / cnt against the bounds thr.  A new filter is one such
+// struct and one line in flat_with_filter.
+struct FlatF32 {
+    using Row = float;
+    using Ws = FlatWs;
+    static constexpr int64_t kMaxDim = INT32_MAX;
+    static constexpr bool kCentre = false, kScale = false, kScores = false;
+    static Ws carve(void *ws, int64_t B, int64_t) { return flat_carve(ws, B); }
+    static const FlatWs &base(const Ws &w) { return w; }
+    static int prepare(const FlatCall &c, const Ws &w) { return annlite_flat_row_norms(c.q, c.B, c.D, nullptr, c.B, 0, w.qnorm, (void *)c.st); }
+    static int launch(const FlatCall &c, const Ws &w, int64_t S, int64_t stride, const float *thr, int32_t *cand, int32_t *cnt, float *) {
+        return flat_launch_filter(c.metric, c.q, c.B, c.D, (const Row *)c.x, c.norms, S, stride, c.valid, w.qnorm, thr, cand, cnt, c.st, c.rows, c.N,
+                                  c.grp);
+    }
+};
+struct FlatBf16x3 {
+    using Row = float;
+    using Ws = FlatSplitWs;
+    static constexpr int64_t kMaxDim = kSplitMaxDim;
+    static constexpr bool kCentre = true, kScale = false, kScores = true;
+    static Ws carve(void *ws, int64_t B, int64_t D) { return flat_split_carve(ws, B, D); }
+    static const FlatWs &base(const Ws &w) { return w.f; }
+    static int prepare(const FlatCall &c, const Ws &w) { return flat_split_prepare(c.q, c.B, c.D, c.centre, w, c.st); }
+    static int launch(const FlatCall &c, const Ws &w, int64_t S, int64_t stride, const float *thr, int32_t *cand, int32_t *cnt, float *scores) {
+        return flat_split_launch_filter(c.metric, c.B, c.D, (const Row *)c.x, c.centre, c.norms, S, stride, c.valid, w, thr, cand, cnt, scores, c.st,
+                                        c.rows, c.N, c.grp);
+    }
+};
+struct FlatF16x2 {
+    using Row = _Float16;
+    using Ws = FlatF16Ws;
+    static constexpr int64_t kMaxDim = kSplitMaxDim;
+    static constexpr bool kCentre = false, kScale = false, kScores = true;
+    static Ws carve(void *ws, int64_t B, int64_t D) { return flat_f16_carve(ws, B, D); }
+    static const FlatWs &base(const Ws &w) { return w.f; }
+    static int prepare(const FlatCall &c, const Ws &w) { return flat_f16_prepare(c.q, c.B, c.D, w, c.st); }
+    static int launch(const FlatCall &c, const Ws &w, int64_t S, int64_t stride, const float *thr, int32_t *cand, int32_t *cnt, float *scores) {
+        return flat_f16_launch_filter(c.metric, c.B, c.D, (const Row *)c.x, c.norms, S, stride, c.valid, w, thr, cand, cnt, scores, c.st, c.rows, c.N,
+                                      c.grp);
+    }
+};
+struct FlatI8x3 {
+    using Row = int8_t;
+    using Ws = FlatI8Ws;
+    static constexpr int64_t kMaxDim = kSplitMaxDim;
+    static constexpr bool kCentre = false, kScale = true, kScores = true;
+    static Ws carve(void *ws, int64_t B, int64_t D) { return flat_i8_carve(ws, B, D); }
+    static const FlatWs &base(const Ws &w) { return w.f; }
+    static int prepare(const FlatCall &c, const Ws &w) { return flat_i8_prepare(c.q, c.B, c.D, c.row_scale, w, c.st); }
+    static int launch(const FlatCall &c, const Ws &w, int64_t S, int64_t stride, const float *thr, int32_t *cand, int32_t *cnt, float *scores) {
+        return flat_i8_launch_filter(c.metric, c.B, c.D, (const Row *)c.x, c.norms, S, stride, c.valid, w, thr, cand, cnt, scores, c.st, c.rows, c.N,
+                                     c.grp);
+    }
+};
+
+// The run-time filter code of the rows / grouped entries becomes the static type here, and nowhere else: fn(F{}) for the code's F.
+template <class Fn>
+static int flat_with_filter(int filter, Fn &&fn) {
+    switch (filter) {
+    case ANNLITE_FLAT_FILTER_F32: return fn(FlatF32{});
+    case ANNLITE_FLAT_FILTER_BF16X3: return fn(FlatBf16x3{});
+    case ANNLITE_FLAT_FILTER_F16X2: return fn(FlatF16x2{});
+    case ANNLITE_FLAT_FILTER_I8X3: return fn(FlatI8x3{});
+    default: set_error("bad filter %d", filter); return ANNLITE_ERR_INVALID;
+    }
+}
+
+// What every search entry (kFlatSearch: arg = k) and every stage entry (kFlatStage: arg = its stride, scores = its scores output) asks
+// of the shape, of the row set and of what only some filters take.  A new kind of row set adds its line here.
+template <class F>
+static int flat_check(FlatEntry what, const FlatCall &c, int64_t arg, const float *scores = nullptr) {
+    if (int rc = flat_check_shape(what, c.metric, c.B, c.D, c.N, arg, F::kMaxDim)) return rc;
+    if (c.set == kFlatRows) ANNLITE_REQUIRE(c.n_sel >= 0 && c.n_sel <= c.N, "bad n_sel=%lld (0 .. N=%lld)", (long long)c.n_sel, (long long)c.N);
+    if (c.set == kFlatGrouped)
+        ANNLITE_REQUIRE(c.grp.ld >= 0 && c.grp.ld * 32 >= c.N, "bad mask_ld=%lld (32 mask_ld >= N=%lld)", (long long)c.grp.ld, (long long)c.N);
+    ANNLITE_REQUIRE(!c.centre || (F::kCentre && c.metric == ANNLITE_METRIC_EUCLIDEAN), "a centre is for the bf16x3 filter and EUCLIDEAN only");
+    if (F::kScale) ANNLITE_REQUIRE_I8_SCALE(c.row_scale);
+    ANNLITE_REQUIRE(!scores || F::kScores, "the f32 filter has no scores output");
+    return ANNLITE_OK;
+}
+// The groups of a call.  G is checked here, before it narrows to the kernels' int.
+static int flat_groups(const uint32_t *masks, int64_t mask_ld, int64_t G, const int32_t *group, FlatGroups *grp) {
+    ANNLITE_REQUIRE(G >= 1 && G <= INT32_MAX, "bad G=%lld (>= 1)", (long long)G);
+    *grp = FlatGroups{masks, mask_ld, (int)G, group};
+    return ANNLITE_OK;
+}
+
+// ---- the stages of a search, the same for every filter F and every row set: the small-table shortcut, the first
+// exact sample, filter stages (F::launch into w.cand / w.cnt against the bounds w.thr) over growing row sets, the re-rank of the lists
+// and the route of an overflowed list.  fw: F's carved workspace. ----
+template <class F>
+static int flat_search_staged(F, const FlatCall &c, const typename F::Ws &fw, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev) {
+    // c.rows != NULL ("selected rows"): the search runs over the n_sel offsets of that list as it runs over a
     // table of n_sel rows -- M below --, every "row r" one indirection away (the MAPPED kernels); N stays the bound of an offset.
-    // grp.masks != NULL ("a filter per query"; never with rows_dev): every exact launch is the GROUPED kernel -- a
-    // wave reads its query's bitmap where it reads valid_bits_dev otherwise -- and filter() launches the GROUPED tiles.  The stages, the
+    // c.grp.masks != NULL ("a filter per query"; never with c.rows): every exact launch is the GROUPED kernel -- a
+    // wave reads its query's bitmap where it reads c.valid otherwise -- and F::launch launches the GROUPED tiles.  The stages, the
     // lists and the overflow route are the same: a query whose bitmap keeps fewer than k sampled rows gets the bound +inf, overflows its
     // list and is answered over all rows under its own bitmap.
-    const int64_t M = rows_dev ? n_sel : N;
+    using T = typename F::Row;
+    const FlatWs &w = F::base(fw);
+    const int64_t B = c.B, M = c.set_rows();
+    hipStream_t st = c.st;
     const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
-    const dim3 qgrid((unsigned)((B + 3) / 4));
     ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
-    // exact sums over every stride-th of S rows of the set (flat_exact_kernel's `list == NULL` modes)
-    auto exact_set = [&](int64_t S, int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
-        if (grp.masks)
-            hipLaunchKernelGGL((flat_exact_kernel<T, false, true>), qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr,
-                               nullptr, kFlatCap, S, stride, valid_bits_dev, (int)k, sqrt_out, 0, only_overflowed, thr_out, out_dist_dev, out_id_dev,
-                               w.ovf, w.ovf_total, row_scale, nullptr, grp);
-        else if (rows_dev)
-            hipLaunchKernelGGL((flat_exact_kernel<T, true>), qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
-                               kFlatCap, S, stride, valid_bits_dev, (int)k, sqrt_out, 0, only_overflowed, thr_out, out_dist_dev, out_id_dev, w.ovf,
-                               w.ovf_total, row_scale, rows_dev);
-        else
-            hipLaunchKernelGGL((flat_exact_kernel<T, false>), qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, nullptr, nullptr,
-                               kFlatCap, S, stride, valid_bits_dev, (int)k, sqrt_out, 0, only_overflowed, thr_out, out_dist_dev, out_id_dev, w.ovf,
-                               w.ovf_total, row_scale);
+    // Every flat_exact_kernel launch.  list != NULL: exact sums over the lists, which hold offsets under either form -- the unmapped
+    // kernel, also when a row list is given.  list == NULL: over every stride-th of S rows of the set, through the list when there is one.
+    auto exact = [&](const int32_t *list, const int32_t *cnt, int64_t S, int64_t stride, int sqrt_out, int final_list, int only_overflowed,
+                     float *thr_out) {
+        const int32_t *rows = list ? nullptr : c.rows;
+        const auto kernel = c.grp.masks ? &flat_exact_kernel<T, false, true> : rows ? &flat_exact_kernel<T, true> : &flat_exact_kernel<T>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, c.metric, c.q, (int)B, (int)c.D, (const T *)c.x, c.N, list, cnt,
+                           kFlatCap, S, stride, c.valid, (int)k, sqrt_out, final_list, only_overflowed, thr_out, out_dist_dev, out_id_dev, w.ovf,
+                           w.ovf_total, F::kScale ? c.row_scale : 1.f, rows, c.grp);
         return launch_status("flat_exact_kernel");
     };
     if (M <= kFlatSample)  // the first sample would be the whole set: exact sums over all its rows
-        return exact_set(M, 1, do_sqrt, 0, nullptr);
-    int rc = prepare();
+        return exact(nullptr, nullptr, M, 1, do_sqrt, 0, 0, nullptr);
+    int rc = F::prepare(c, fw);
     if (rc != ANNLITE_OK) return rc;
     // stage 0: the k-th smallest exact distance among kFlatSample rows spread over the set
-    if ((rc = exact_set(kFlatSample, M / kFlatSample, 0, 0, w.thr)) != ANNLITE_OK) return rc;
+    if ((rc = exact(nullptr, nullptr, kFlatSample, M / kFlatSample, 0, 0, 0, w.thr)) != ANNLITE_OK) return rc;
     // stages 1 .. n: row sets growing by the same factor (<= kFlatGrowth) up to the whole set; each takes the bound of the one before
     const double ratio = (double)M / (double)kFlatSample;
     int n_stages = (int)ceil(log(ratio) / log(kFlatGrowth) - 1e-9);
@@ -1665,21 +1770,59 @@ static int flat_search_staged(int metric, const float *queries_dev, int64_t B, i
         }
         const bool last = s == n_stages;
         ANNLITE_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)B * 4, st));
-        if ((rc = filter((M + stride - 1) / stride, stride)) != ANNLITE_OK) return rc;
+        if ((rc = F::launch(c, fw, (M + stride - 1) / stride, stride, w.thr, w.cand, w.cnt, nullptr)) != ANNLITE_OK) return rc;
         // (a list that overflowed before the last stage still holds `cap` valid rows: the k-th of ANY k valid rows is a bound)
-        // (the lists hold offsets under either form: the re-rank is the unmapped kernel)
-        if (grp.masks)
-            hipLaunchKernelGGL((flat_exact_kernel<T, false, true>), qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand,
-                               w.cnt, kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0,
-                               last ? nullptr : w.thr, out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale, nullptr, grp);
-        else
-            hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.cand, w.cnt,
-                               kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr,
-                               out_dist_dev, out_id_dev, w.ovf, w.ovf_total, row_scale);
-        if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
+        if ((rc = exact(w.cand, w.cnt, 0, 1, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr)) != ANNLITE_OK) return rc;
     }
     // queries whose last list overflowed: exact sums over all rows of the set (the other waves leave at once)
-    return exact_set(M, 1, do_sqrt, 1, nullptr);
+    return exact(nullptr, nullptr, M, 1, do_sqrt, 0, 1, nullptr);
+}
+
+// ---- the one body behind the six search entries, and the one behind the stage entries: check, carve, check the workspace, run ----------
+template <class F>
+static int flat_search(const FlatCall &c, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
+                       size_t workspace_bytes) {
+    if (int rc = flat_check<F>(kFlatSearch, c, k)) return rc;
+    if (c.B == 0) return ANNLITE_OK;
+    // (the set's own pointers also where it is empty: a NULL list is the staged search's word for "the whole table")
+    ANNLITE_REQUIRE(c.q && out_dist_dev && out_id_dev && workspace_dev && c.set_given() && (c.set_rows() == 0 || (c.x && c.norms)),
+                    "null device pointer");
+    const typename F::Ws w = F::carve(workspace_dev, c.B, c.D);
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
+    return flat_search_staged(F{}, c, w, k, flags, out_dist_dev, out_id_dev);
+}
+
+// One filter stage over every stride-th row of the set, into the caller's lists.  *used (where asked for): the carved workspace, for the
+// entries that hand back what prepare() left per query; it is left alone where the call is refused or has nothing to do.
+template <class F>
+static int flat_stage(const FlatCall &c, int64_t stride, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev, float *scores_dev,
+                      void *workspace_dev, size_t workspace_bytes, typename F::Ws *used = nullptr) {
+    if (int rc = flat_check<F>(kFlatStage, c, stride, scores_dev)) return rc;
+    const int64_t M = c.set_rows();
+    if (c.B == 0 || M == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(c.q && c.x && c.norms && c.set_given() && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
+    const typename F::Ws w = F::carve(workspace_dev, c.B, c.D);
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
+    if (int rc = F::prepare(c, w)) return rc;
+    if (used) *used = w;
+    return F::launch(c, w, (M + stride - 1) / stride, stride, bounds_dev, cand_dev, count_dev, scores_dev);
+}
+// ... and such a per-query array handed back, on the stage's stream (per_query NULL: the stage had nothing to do).
+static int flat_hand_back(float *out_dev, const float *per_query, int64_t B, hipStream_t st) {
+    if (out_dev && per_query) ANNLITE_HIP_TRY(hipMemcpyAsync(out_dev, per_query, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
+    return ANNLITE_OK;
+}
+
+// The workspace of a search or a stage: the filter's own carve.  The typed entries (`typed`) have never bounded B, N and the f32 filter's
+// D by INT32_MAX as the searches do, and keep accepting what they accepted.
+static int flat_workspace_bytes(int filter, bool typed, int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    return flat_with_filter(filter, [&](auto F) -> int {
+        auto held = [&](int64_t v) { return typed && v > INT32_MAX ? (int64_t)INT32_MAX : v; };
+        if (int rc = flat_check_shape(kFlatSearch, ANNLITE_METRIC_EUCLIDEAN, held(B), held(D), held(N), k, F.kMaxDim)) return rc;
+        *bytes = (int64_t)F.carve(nullptr, B, D).bytes;
+        return ANNLITE_OK;
+    });
 }
 
 // ---- cells: workspace, stages, launchers ---------------------------------------------------------------------------------------------
@@ -1854,6 +1997,7 @@ extern "C" int annlite_flat_slack(int metric, int64_t D, float *c_rel, float *c_
 extern "C" int annlite_flat_filter(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, const float *norms_dev,
                                    int64_t N, int64_t stride, const uint32_t *valid_bits_dev, const float *query_norms_dev,
                                    const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev, void *stream) {
+    // (the caller's query norms and no workspace: not flat_stage)
     if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, INT32_MAX)) return rc;
     if (B == 0 || N == 0) return ANNLITE_OK;
     ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && query_norms_dev && bounds_dev && cand_dev && count_dev, "null device pointer");
@@ -1862,28 +2006,21 @@ extern "C" int annlite_flat_filter(int metric, const float *queries_dev, int64_t
 }
 
 extern "C" int annlite_flat_search_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    ANNLITE_REQUIRE(N >= 0 && D >= 1 && B >= 0 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64)");
-    *bytes = (int64_t)flat_carve(nullptr, B).bytes;
-    return ANNLITE_OK;
+    return flat_workspace_bytes(ANNLITE_FLAT_FILTER_F32, true, N, D, B, k, bytes);
+}
+
+// The typed entries: each fills the operands of a search or a stage over the whole table -- no list, no groups -- and forwards.
+static FlatCall flat_table_call(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev, float row_scale,
+                                const float *norms_dev, const float *centre_dev, int64_t N, const uint32_t *valid_bits_dev, void *stream) {
+    return FlatCall{kFlatTable, metric, queries_dev, B, D, vectors_dev, row_scale, norms_dev, centre_dev, N, valid_bits_dev, nullptr, 0, {},
+                    (hipStream_t)stream};
 }
 
 extern "C" int annlite_flat_search_topk(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
                                         const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
                                         float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, INT32_MAX)) return rc;
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_dev && norms_dev)), "null device pointer");
-    const FlatWs w = flat_carve(workspace_dev, B);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return flat_search_staged(
-        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w, st, 1.f,
-        [&]() { return annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream); },
-        [&](int64_t S, int64_t stride) {
-            return flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, S, stride, valid_bits_dev, w.qnorm, w.thr, w.cand, w.cnt,
-                                      st);
-        });
+    const FlatCall c = flat_table_call(metric, queries_dev, B, D, vectors_dev, 1.f, norms_dev, nullptr, N, valid_bits_dev, stream);
+    return flat_search<FlatF32>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
 }
 
 extern "C" int annlite_flat_split_slack(int metric, int64_t D, float *c_rel, float *c_abs) {
@@ -1904,11 +2041,7 @@ extern "C" int annlite_flat_centred_norms(const float *vectors_dev, int64_t capa
 }
 
 extern "C" int annlite_flat_search_split_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    ANNLITE_REQUIRE(N >= 0 && D >= 1 && D <= kSplitMaxDim && B >= 0 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
-                    (long long)kSplitMaxDim);
-    *bytes = (int64_t)flat_split_carve(nullptr, B, D).bytes;
-    return ANNLITE_OK;
+    return flat_workspace_bytes(ANNLITE_FLAT_FILTER_BF16X3, true, N, D, B, k, bytes);
 }
 
 extern "C" int annlite_flat_filter_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
@@ -1916,39 +2049,18 @@ extern "C" int annlite_flat_filter_split(int metric, const float *queries_dev, i
                                          float *query_norms_out_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
                                          const float *centre_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes,
                                          void *stream) {
-    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
-    ANNLITE_REQUIRE(!centre_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "a centre is for EUCLIDEAN only");
-    if (B == 0 || N == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
-    const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = flat_split_prepare(queries_dev, B, D, centre_dev, w, st);
-    if (rc != ANNLITE_OK) return rc;
-    if (query_norms_out_dev)
-        ANNLITE_HIP_TRY(hipMemcpyAsync(query_norms_out_dev, w.f.qnorm, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-    return flat_split_launch_filter(metric, B, D, vectors_dev, centre_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev, w,
-                                    bounds_dev, cand_dev, count_dev, scores_dev, st);
+    const FlatCall c = flat_table_call(metric, queries_dev, B, D, vectors_dev, 1.f, norms_dev, centre_dev, N, valid_bits_dev, stream);
+    FlatSplitWs w{};
+    if (int rc = flat_stage<FlatBf16x3>(c, stride, bounds_dev, cand_dev, count_dev, scores_dev, workspace_dev, workspace_bytes, &w)) return rc;
+    return flat_hand_back(query_norms_out_dev, w.f.qnorm, B, c.st);
 }
 
 extern "C" int annlite_flat_search_topk_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
                                               const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const float *centre_dev,
                                               int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
                                               size_t workspace_bytes, void *stream) {
-    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
-    ANNLITE_REQUIRE(!centre_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "a centre is for EUCLIDEAN only");
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_dev && norms_dev)), "null device pointer");
-    const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return flat_search_staged(
-        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
-        [&]() { return flat_split_prepare(queries_dev, B, D, centre_dev, w, st); },
-        [&](int64_t S, int64_t stride) {
-            return flat_split_launch_filter(metric, B, D, vectors_dev, centre_dev, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand,
-                                            w.f.cnt, nullptr, st);
-        });
+    const FlatCall c = flat_table_call(metric, queries_dev, B, D, vectors_dev, 1.f, norms_dev, centre_dev, N, valid_bits_dev, stream);
+    return flat_search<FlatBf16x3>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
 }
 
 // ---- f16 rows ------------------------------------------------------------------------------------------------------------------------
@@ -1970,51 +2082,26 @@ extern "C" int annlite_flat_f16_slack(int metric, int64_t D, float *c_rel, float
 }
 
 extern "C" int annlite_flat_search_f16_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    ANNLITE_REQUIRE(N >= 0 && D >= 1 && D <= kSplitMaxDim && B >= 0 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
-                    (long long)kSplitMaxDim);
-    *bytes = (int64_t)flat_f16_carve(nullptr, B, D).bytes;
-    return ANNLITE_OK;
+    return flat_workspace_bytes(ANNLITE_FLAT_FILTER_F16X2, true, N, D, B, k, bytes);
 }
 
 extern "C" int annlite_flat_filter_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
                                        const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
                                        float *query_norms_out_dev, float *query_flush_out_dev, const float *bounds_dev, int32_t *cand_dev,
                                        int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
-    if (B == 0 || N == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && vectors_f16_dev && norms_dev && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
-    const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = flat_f16_prepare(queries_dev, B, D, w, st);
-    if (rc != ANNLITE_OK) return rc;
-    if (query_norms_out_dev)
-        ANNLITE_HIP_TRY(hipMemcpyAsync(query_norms_out_dev, w.f.qnorm, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-    if (query_flush_out_dev)
-        ANNLITE_HIP_TRY(hipMemcpyAsync(query_flush_out_dev, w.qflush, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-    return flat_f16_launch_filter(metric, B, D, (const _Float16 *)vectors_f16_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev,
-                                  w, bounds_dev, cand_dev, count_dev, scores_dev, st);
+    const FlatCall c = flat_table_call(metric, queries_dev, B, D, vectors_f16_dev, 1.f, norms_dev, nullptr, N, valid_bits_dev, stream);
+    FlatF16Ws w{};
+    if (int rc = flat_stage<FlatF16x2>(c, stride, bounds_dev, cand_dev, count_dev, scores_dev, workspace_dev, workspace_bytes, &w)) return rc;
+    if (int rc = flat_hand_back(query_norms_out_dev, w.f.qnorm, B, c.st)) return rc;
+    return flat_hand_back(query_flush_out_dev, w.qflush, B, c.st);
 }
 
 extern "C" int annlite_flat_search_topk_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
                                             const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
                                             float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
                                             void *stream) {
-    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_f16_dev && norms_dev)),
-                    "null device pointer");
-    const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const _Float16 *x = (const _Float16 *)vectors_f16_dev;
-    return flat_search_staged(
-        metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
-        [&]() { return flat_f16_prepare(queries_dev, B, D, w, st); },
-        [&](int64_t S, int64_t stride) {
-            return flat_f16_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st);
-        });
+    const FlatCall c = flat_table_call(metric, queries_dev, B, D, vectors_f16_dev, 1.f, norms_dev, nullptr, N, valid_bits_dev, stream);
+    return flat_search<FlatF16x2>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
 }
 
 // ---- int8 rows -----------------------------------------------------------------------------------------------------------------------
@@ -2038,203 +2125,61 @@ extern "C" int annlite_flat_i8_slack(int metric, int64_t D, float *c_rel, float 
 }
 
 extern "C" int annlite_flat_search_i8_workspace_bytes(int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    ANNLITE_REQUIRE(N >= 0 && D >= 1 && D <= kSplitMaxDim && B >= 0 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
-                    (long long)kSplitMaxDim);
-    *bytes = (int64_t)flat_i8_carve(nullptr, B, D).bytes;
-    return ANNLITE_OK;
+    return flat_workspace_bytes(ANNLITE_FLAT_FILTER_I8X3, true, N, D, B, k, bytes);
 }
 
 extern "C" int annlite_flat_filter_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev, float scale,
                                       const float *norms_dev, int64_t N, int64_t stride, const uint32_t *valid_bits_dev,
                                       float *query_norms_out_dev, float *query_slack_out_dev, const float *bounds_dev, int32_t *cand_dev,
                                       int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
-    ANNLITE_REQUIRE_I8_SCALE(scale);
-    if (B == 0 || N == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && vectors_i8_dev && norms_dev && bounds_dev && cand_dev && count_dev && workspace_dev, "null device pointer");
-    const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = flat_i8_prepare(queries_dev, B, D, scale, w, st);
-    if (rc != ANNLITE_OK) return rc;
-    if (query_norms_out_dev)
-        ANNLITE_HIP_TRY(hipMemcpyAsync(query_norms_out_dev, w.f.qnorm, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-    if (query_slack_out_dev)
-        ANNLITE_HIP_TRY(hipMemcpyAsync(query_slack_out_dev, w.qslack, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
-    return flat_i8_launch_filter(metric, B, D, (const int8_t *)vectors_i8_dev, norms_dev, (N + stride - 1) / stride, stride, valid_bits_dev, w,
-                                 bounds_dev, cand_dev, count_dev, scores_dev, st);
+    const FlatCall c = flat_table_call(metric, queries_dev, B, D, vectors_i8_dev, scale, norms_dev, nullptr, N, valid_bits_dev, stream);
+    FlatI8Ws w{};
+    if (int rc = flat_stage<FlatI8x3>(c, stride, bounds_dev, cand_dev, count_dev, scores_dev, workspace_dev, workspace_bytes, &w)) return rc;
+    if (int rc = flat_hand_back(query_norms_out_dev, w.f.qnorm, B, c.st)) return rc;
+    return flat_hand_back(query_slack_out_dev, w.qslack, B, c.st);
 }
 
 extern "C" int annlite_flat_search_topk_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev, float scale,
                                            const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
                                            float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
                                            void *stream) {
-    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
-    ANNLITE_REQUIRE_I8_SCALE(scale);
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && (N == 0 || (vectors_i8_dev && norms_dev)),
-                    "null device pointer");
-    const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int8_t *x = (const int8_t *)vectors_i8_dev;
-    return flat_search_staged(
-        metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, scale,
-        [&]() { return flat_i8_prepare(queries_dev, B, D, scale, w, st); },
-        [&](int64_t S, int64_t stride) {
-            return flat_i8_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st);
-        });
+    const FlatCall c = flat_table_call(metric, queries_dev, B, D, vectors_i8_dev, scale, norms_dev, nullptr, N, valid_bits_dev, stream);
+    return flat_search<FlatI8x3>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
 }
 
 // ---- selected rows: the searches above over an ascending list of offsets ("selected rows") ------------------------
-// One entry per job, dispatching over the four filters: what differs between them is the workspace's query planes, prepare() and the
-// launcher, all of which exist above.
-static size_t flat_rows_workspace(int filter, int64_t B, int64_t D) {
-    switch (filter) {
-    case ANNLITE_FLAT_FILTER_F32: return flat_carve(nullptr, B).bytes;
-    case ANNLITE_FLAT_FILTER_BF16X3: return flat_split_carve(nullptr, B, D).bytes;
-    case ANNLITE_FLAT_FILTER_F16X2: return flat_f16_carve(nullptr, B, D).bytes;
-    default: return flat_i8_carve(nullptr, B, D).bytes;
-    }
-}
-
-// what both entries ask of the filter, the shape and the list
-static int flat_rows_check(FlatEntry what, int filter, int metric, int64_t B, int64_t D, int64_t N, int64_t n_sel, int64_t arg, float row_scale,
-                           const float *centre_dev) {
-    ANNLITE_REQUIRE(filter >= ANNLITE_FLAT_FILTER_F32 && filter <= ANNLITE_FLAT_FILTER_I8X3, "bad filter %d", filter);
-    if (int rc = flat_check_shape(what, metric, B, D, N, arg, filter == ANNLITE_FLAT_FILTER_F32 ? (int64_t)INT32_MAX : kSplitMaxDim)) return rc;
-    ANNLITE_REQUIRE(n_sel >= 0 && n_sel <= N, "bad n_sel=%lld (0 .. N=%lld)", (long long)n_sel, (long long)N);
-    ANNLITE_REQUIRE(!centre_dev || (filter == ANNLITE_FLAT_FILTER_BF16X3 && metric == ANNLITE_METRIC_EUCLIDEAN),
-                    "a centre is for the bf16x3 filter and EUCLIDEAN only");
-    if (filter == ANNLITE_FLAT_FILTER_I8X3) ANNLITE_REQUIRE_I8_SCALE(row_scale);
-    return ANNLITE_OK;
-}
-
+// One entry per job: the filter code picks F once (flat_with_filter), and the list goes into the operands.  No bitmap: a row in the
+// list is selected.
 extern "C" int annlite_flat_search_rows_workspace_bytes(int filter, int64_t n_sel, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    if (int rc = flat_rows_check(kFlatSearch, filter, ANNLITE_METRIC_EUCLIDEAN, B, D, n_sel, n_sel, k, 1.f, nullptr)) return rc;
-    *bytes = (int64_t)flat_rows_workspace(filter, B, D);
-    return ANNLITE_OK;
+    return flat_workspace_bytes(filter, false, n_sel, D, B, k, bytes);
 }
 
 extern "C" int annlite_flat_search_topk_rows(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
                                              float row_scale, const float *norms_dev, const float *centre_dev, int64_t N,
                                              const int32_t *rows_dev, int64_t n_sel, int64_t k, int flags, float *out_dist_dev,
                                              int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    if (int rc = flat_rows_check(kFlatSearch, filter, metric, B, D, N, n_sel, k, row_scale, centre_dev)) return rc;
-    if (B == 0) return ANNLITE_OK;
-    // (rows_dev also with n_sel = 0: a NULL list is the staged search's word for "the whole table")
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && rows_dev && (n_sel == 0 || (vectors_dev && norms_dev)),
-                    "null device pointer");
-    if (int rc = flat_check_workspace(workspace_bytes, flat_rows_workspace(filter, B, D))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    // (no bitmap anywhere below: a row in the list is selected)
-    switch (filter) {
-    case ANNLITE_FLAT_FILTER_F32: {
-        const FlatWs w = flat_carve(workspace_dev, B);
-        const float *x = (const float *)vectors_dev;
-        return flat_search_staged(
-            metric, queries_dev, B, D, x, N, nullptr, k, flags, out_dist_dev, out_id_dev, w, st, 1.f,
-            [&]() { return annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream); },
-            [&](int64_t S, int64_t stride) {
-                return flat_launch_filter(metric, queries_dev, B, D, x, norms_dev, S, stride, nullptr, w.qnorm, w.thr, w.cand, w.cnt, st, rows_dev, N);
-            },
-            rows_dev, n_sel);
-    }
-    case ANNLITE_FLAT_FILTER_BF16X3: {
-        const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
-        const float *x = (const float *)vectors_dev;
-        return flat_search_staged(
-            metric, queries_dev, B, D, x, N, nullptr, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
-            [&]() { return flat_split_prepare(queries_dev, B, D, centre_dev, w, st); },
-            [&](int64_t S, int64_t stride) {
-                return flat_split_launch_filter(metric, B, D, x, centre_dev, norms_dev, S, stride, nullptr, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st,
-                                                rows_dev, N);
-            },
-            rows_dev, n_sel);
-    }
-    case ANNLITE_FLAT_FILTER_F16X2: {
-        const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
-        const _Float16 *x = (const _Float16 *)vectors_dev;
-        return flat_search_staged(
-            metric, queries_dev, B, D, x, N, nullptr, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
-            [&]() { return flat_f16_prepare(queries_dev, B, D, w, st); },
-            [&](int64_t S, int64_t stride) {
-                return flat_f16_launch_filter(metric, B, D, x, norms_dev, S, stride, nullptr, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st, rows_dev, N);
-            },
-            rows_dev, n_sel);
-    }
-    default: {
-        const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
-        const int8_t *x = (const int8_t *)vectors_dev;
-        return flat_search_staged(
-            metric, queries_dev, B, D, x, N, nullptr, k, flags, out_dist_dev, out_id_dev, w.f, st, row_scale,
-            [&]() { return flat_i8_prepare(queries_dev, B, D, row_scale, w, st); },
-            [&](int64_t S, int64_t stride) {
-                return flat_i8_launch_filter(metric, B, D, x, norms_dev, S, stride, nullptr, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st, rows_dev, N);
-            },
-            rows_dev, n_sel);
-    }
-    }
+    const FlatCall c{kFlatRows, metric, queries_dev, B, D, vectors_dev, row_scale, norms_dev, centre_dev, N, nullptr, rows_dev, n_sel, {},
+                     (hipStream_t)stream};
+    return flat_with_filter(filter, [&](auto F) {
+        return flat_search<decltype(F)>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
+    });
 }
 
 extern "C" int annlite_flat_filter_rows(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
                                         float row_scale, const float *norms_dev, const float *centre_dev, int64_t N, const int32_t *rows_dev,
                                         int64_t n_sel, int64_t stride, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
                                         float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    if (int rc = flat_rows_check(kFlatStage, filter, metric, B, D, N, n_sel, stride, row_scale, centre_dev)) return rc;
-    ANNLITE_REQUIRE(!scores_dev || filter != ANNLITE_FLAT_FILTER_F32, "the f32 filter has no scores output");
-    if (B == 0 || n_sel == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && rows_dev && bounds_dev && cand_dev && count_dev && workspace_dev,
-                    "null device pointer");
-    if (int rc = flat_check_workspace(workspace_bytes, flat_rows_workspace(filter, B, D))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t S = (n_sel + stride - 1) / stride;
-    int rc;
-    switch (filter) {
-    case ANNLITE_FLAT_FILTER_F32: {
-        const FlatWs w = flat_carve(workspace_dev, B);
-        if ((rc = annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream)) != ANNLITE_OK) return rc;
-        return flat_launch_filter(metric, queries_dev, B, D, (const float *)vectors_dev, norms_dev, S, stride, nullptr, w.qnorm, bounds_dev, cand_dev,
-                                  count_dev, st, rows_dev, N);
-    }
-    case ANNLITE_FLAT_FILTER_BF16X3: {
-        const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
-        if ((rc = flat_split_prepare(queries_dev, B, D, centre_dev, w, st)) != ANNLITE_OK) return rc;
-        return flat_split_launch_filter(metric, B, D, (const float *)vectors_dev, centre_dev, norms_dev, S, stride, nullptr, w, bounds_dev, cand_dev,
-                                        count_dev, scores_dev, st, rows_dev, N);
-    }
-    case ANNLITE_FLAT_FILTER_F16X2: {
-        const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
-        if ((rc = flat_f16_prepare(queries_dev, B, D, w, st)) != ANNLITE_OK) return rc;
-        return flat_f16_launch_filter(metric, B, D, (const _Float16 *)vectors_dev, norms_dev, S, stride, nullptr, w, bounds_dev, cand_dev, count_dev,
-                                      scores_dev, st, rows_dev, N);
-    }
-    default: {
-        const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
-        if ((rc = flat_i8_prepare(queries_dev, B, D, row_scale, w, st)) != ANNLITE_OK) return rc;
-        return flat_i8_launch_filter(metric, B, D, (const int8_t *)vectors_dev, norms_dev, S, stride, nullptr, w, bounds_dev, cand_dev, count_dev,
-                                     scores_dev, st, rows_dev, N);
-    }
-    }
+    const FlatCall c{kFlatRows, metric, queries_dev, B, D, vectors_dev, row_scale, norms_dev, centre_dev, N, nullptr, rows_dev, n_sel, {},
+                     (hipStream_t)stream};
+    return flat_with_filter(filter, [&](auto F) {
+        return flat_stage<decltype(F)>(c, stride, bounds_dev, cand_dev, count_dev, scores_dev, workspace_dev, workspace_bytes);
+    });
 }
 
 // ---- a filter per query: the searches above over the table with G bitmaps ("a filter per query") --------------------
-// One entry per job, dispatching over the four filters as the selected-rows entries do; the workspace is the filter's own carve.
-static int flat_grouped_check(FlatEntry what, int filter, int metric, int64_t B, int64_t D, int64_t N, int64_t mask_ld, int64_t G, int64_t arg,
-                              float row_scale, const float *centre_dev) {
-    if (int rc = flat_rows_check(what, filter, metric, B, D, N, 0, arg, row_scale, centre_dev)) return rc;
-    ANNLITE_REQUIRE(G >= 1 && G <= INT32_MAX, "bad G=%lld (>= 1)", (long long)G);
-    ANNLITE_REQUIRE(mask_ld >= 0 && mask_ld * 32 >= N, "bad mask_ld=%lld (32 mask_ld >= N=%lld)", (long long)mask_ld, (long long)N);
-    return ANNLITE_OK;
-}
-
+// One entry per job, as the selected-rows entries: the groups go into the operands, behind the live bitmap.
 extern "C" int annlite_flat_search_grouped_workspace_bytes(int filter, int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    if (int rc = flat_rows_check(kFlatSearch, filter, ANNLITE_METRIC_EUCLIDEAN, B, D, N, 0, k, 1.f, nullptr)) return rc;
-    *bytes = (int64_t)flat_rows_workspace(filter, B, D);
-    return ANNLITE_OK;
+    return flat_workspace_bytes(filter, false, N, D, B, k, bytes);
 }
 
 extern "C" int annlite_flat_search_topk_grouped(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
@@ -2242,63 +2187,12 @@ extern "C" int annlite_flat_search_topk_grouped(int filter, int metric, const fl
                                                 const uint32_t *valid_bits_dev, const uint32_t *masks_dev, int64_t mask_ld, int64_t G,
                                                 const int32_t *group_dev, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev,
                                                 void *workspace_dev, size_t workspace_bytes, void *stream) {
-    if (int rc = flat_grouped_check(kFlatSearch, filter, metric, B, D, N, mask_ld, G, k, row_scale, centre_dev)) return rc;
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && masks_dev && group_dev && (N == 0 || (vectors_dev && norms_dev)),
-                    "null device pointer");
-    if (int rc = flat_check_workspace(workspace_bytes, flat_rows_workspace(filter, B, D))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const FlatGroups grp{masks_dev, mask_ld, (int)G, group_dev};
-    switch (filter) {
-    case ANNLITE_FLAT_FILTER_F32: {
-        const FlatWs w = flat_carve(workspace_dev, B);
-        const float *x = (const float *)vectors_dev;
-        return flat_search_staged(
-            metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w, st, 1.f,
-            [&]() { return annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream); },
-            [&](int64_t S, int64_t stride) {
-                return flat_launch_filter(metric, queries_dev, B, D, x, norms_dev, S, stride, valid_bits_dev, w.qnorm, w.thr, w.cand, w.cnt, st, nullptr,
-                                          0, grp);
-            },
-            nullptr, 0, grp);
-    }
-    case ANNLITE_FLAT_FILTER_BF16X3: {
-        const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
-        const float *x = (const float *)vectors_dev;
-        return flat_search_staged(
-            metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
-            [&]() { return flat_split_prepare(queries_dev, B, D, centre_dev, w, st); },
-            [&](int64_t S, int64_t stride) {
-                return flat_split_launch_filter(metric, B, D, x, centre_dev, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt,
-                                                nullptr, st, nullptr, 0, grp);
-            },
-            nullptr, 0, grp);
-    }
-    case ANNLITE_FLAT_FILTER_F16X2: {
-        const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
-        const _Float16 *x = (const _Float16 *)vectors_dev;
-        return flat_search_staged(
-            metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, 1.f,
-            [&]() { return flat_f16_prepare(queries_dev, B, D, w, st); },
-            [&](int64_t S, int64_t stride) {
-                return flat_f16_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st,
-                                              nullptr, 0, grp);
-            },
-            nullptr, 0, grp);
-    }
-    default: {
-        const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
-        const int8_t *x = (const int8_t *)vectors_dev;
-        return flat_search_staged(
-            metric, queries_dev, B, D, x, N, valid_bits_dev, k, flags, out_dist_dev, out_id_dev, w.f, st, row_scale,
-            [&]() { return flat_i8_prepare(queries_dev, B, D, row_scale, w, st); },
-            [&](int64_t S, int64_t stride) {
-                return flat_i8_launch_filter(metric, B, D, x, norms_dev, S, stride, valid_bits_dev, w, w.f.thr, w.f.cand, w.f.cnt, nullptr, st, nullptr,
-                                             0, grp);
-            },
-            nullptr, 0, grp);
-    }
-    }
+    FlatCall c{kFlatGrouped, metric, queries_dev, B, D, vectors_dev, row_scale, norms_dev, centre_dev, N, valid_bits_dev, nullptr, 0, {},
+               (hipStream_t)stream};
+    if (int rc = flat_groups(masks_dev, mask_ld, G, group_dev, &c.grp)) return rc;
+    return flat_with_filter(filter, [&](auto F) {
+        return flat_search<decltype(F)>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
+    });
 }
 
 extern "C" int annlite_flat_filter_grouped(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
@@ -2306,42 +2200,12 @@ extern "C" int annlite_flat_filter_grouped(int filter, int metric, const float *
                                            const uint32_t *valid_bits_dev, const uint32_t *masks_dev, int64_t mask_ld, int64_t G,
                                            const int32_t *group_dev, int64_t stride, const float *bounds_dev, int32_t *cand_dev,
                                            int32_t *count_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    if (int rc = flat_grouped_check(kFlatStage, filter, metric, B, D, N, mask_ld, G, stride, row_scale, centre_dev)) return rc;
-    ANNLITE_REQUIRE(!scores_dev || filter != ANNLITE_FLAT_FILTER_F32, "the f32 filter has no scores output");
-    if (B == 0 || N == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && masks_dev && group_dev && bounds_dev && cand_dev && count_dev && workspace_dev,
-                    "null device pointer");
-    if (int rc = flat_check_workspace(workspace_bytes, flat_rows_workspace(filter, B, D))) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const FlatGroups grp{masks_dev, mask_ld, (int)G, group_dev};
-    const int64_t S = (N + stride - 1) / stride;
-    int rc;
-    switch (filter) {
-    case ANNLITE_FLAT_FILTER_F32: {
-        const FlatWs w = flat_carve(workspace_dev, B);
-        if ((rc = annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.qnorm, stream)) != ANNLITE_OK) return rc;
-        return flat_launch_filter(metric, queries_dev, B, D, (const float *)vectors_dev, norms_dev, S, stride, valid_bits_dev, w.qnorm, bounds_dev,
-                                  cand_dev, count_dev, st, nullptr, 0, grp);
-    }
-    case ANNLITE_FLAT_FILTER_BF16X3: {
-        const FlatSplitWs w = flat_split_carve(workspace_dev, B, D);
-        if ((rc = flat_split_prepare(queries_dev, B, D, centre_dev, w, st)) != ANNLITE_OK) return rc;
-        return flat_split_launch_filter(metric, B, D, (const float *)vectors_dev, centre_dev, norms_dev, S, stride, valid_bits_dev, w, bounds_dev,
-                                        cand_dev, count_dev, scores_dev, st, nullptr, 0, grp);
-    }
-    case ANNLITE_FLAT_FILTER_F16X2: {
-        const FlatF16Ws w = flat_f16_carve(workspace_dev, B, D);
-        if ((rc = flat_f16_prepare(queries_dev, B, D, w, st)) != ANNLITE_OK) return rc;
-        return flat_f16_launch_filter(metric, B, D, (const _Float16 *)vectors_dev, norms_dev, S, stride, valid_bits_dev, w, bounds_dev, cand_dev,
-                                      count_dev, scores_dev, st, nullptr, 0, grp);
-    }
-    default: {
-        const FlatI8Ws w = flat_i8_carve(workspace_dev, B, D);
-        if ((rc = flat_i8_prepare(queries_dev, B, D, row_scale, w, st)) != ANNLITE_OK) return rc;
-        return flat_i8_launch_filter(metric, B, D, (const int8_t *)vectors_dev, norms_dev, S, stride, valid_bits_dev, w, bounds_dev, cand_dev,
-                                     count_dev, scores_dev, st, nullptr, 0, grp);
-    }
-    }
+    FlatCall c{kFlatGrouped, metric, queries_dev, B, D, vectors_dev, row_scale, norms_dev, centre_dev, N, valid_bits_dev, nullptr, 0, {},
+               (hipStream_t)stream};
+    if (int rc = flat_groups(masks_dev, mask_ld, G, group_dev, &c.grp)) return rc;
+    return flat_with_filter(filter, [&](auto F) {
+        return flat_stage<decltype(F)>(c, stride, bounds_dev, cand_dev, count_dev, scores_dev, workspace_dev, workspace_bytes);
+    });
 }
 
 extern "C" int annlite_flat_overflow_count(const void *workspace_dev, void *stream, int64_t *count) {

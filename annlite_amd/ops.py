@@ -1297,6 +1297,45 @@ def bitmap_rows(words: torch.Tensor, and_words: Optional[torch.Tensor] = None, n
     return out[:min(n, out.numel())], n
 
 
+def _flat_row_set_call(kind: str, flat_filter: str, metric: int, queries, vectors, norms, n_rows, row_set, centre, scale, workspace,
+                       k: Optional[int] = None, sqrt: bool = False, bounds=None, stride: int = 1, scores: bool = False):
+    """A search (``k``) or one filter stage (``bounds``) of the ``flat_filter`` filter over a row set, through ``annlite_flat_search_topk_<kind>``
+    or ``annlite_flat_filter_<kind>``.  The two kinds differ in ``row_set(B, N) -> (n_set, args)`` alone: the rows of the set, which size the
+    workspace and the scores, and what the entry takes behind N (``'rows'``: the list and n_sel; ``'grouped'``: the bitmaps)."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    code = _capi.FLAT_FILTER[flat_filter]
+    n_set, set_args = row_set(B, N)
+    ws = _flat_workspace(f'flat_search_{kind}_workspace_bytes', (code, n_set, D, B, 1 if k is None else k), dev, workspace)
+    if k is not None:
+        entry, out = f'flat_search_topk_{kind}', _flat_topk_outputs(B, k, dev)
+        job = (int(k), 1 if sqrt else 0, out[0].data_ptr(), out[1].data_ptr())
+    else:
+        entry, out = f'flat_filter_{kind}', _flat_lists(B, dev, (n_set + stride - 1) // stride if scores else None)
+        job = (stride, bounds.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), _ptr(out[2]))
+        out = out if scores else out[:2]
+    check(getattr(lib(), 'annlite_' + entry)(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(),
+                                             _ptr(centre), N, *set_args, *job, ws.data_ptr(), ws.numel(), stream_ptr()), entry)
+    return out
+
+
+def _listed_rows(rows: torch.Tensor, n_sel: Optional[int]):
+    """the ``row_set`` of the selected-rows entries: the first ``n_sel`` (default: all) of the ascending offsets ``rows`` i32"""
+    n_sel = rows.numel() if n_sel is None else int(n_sel)
+    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= n_sel
+    return lambda B, N: (n_sel, (rows.data_ptr(), n_sel))
+
+
+def _grouped_rows(valid_bits: Optional[torch.Tensor], masks: torch.Tensor, group: torch.Tensor):
+    """the ``row_set`` of the grouped entries: the table under the live bitmap, i32 [G, mask_ld] bitmaps and i32 [B] group ids"""
+    def row_set(B: int, N: int):
+        assert masks.dtype == torch.int32 and masks.ndim == 2 and masks.is_contiguous() and masks.shape[1] * 32 >= N
+        assert group.dtype == torch.int32 and group.is_contiguous() and group.numel() == B
+        return N, (_ptr(valid_bits), masks.data_ptr(), masks.shape[1], masks.shape[0], group.data_ptr())
+    return row_set
+
+
 def flat_search_topk_rows(flat_filter: str, metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, rows: torch.Tensor,
                           k: int, n_sel: Optional[int] = None, n_rows: Optional[int] = None, centre: Optional[torch.Tensor] = None,
                           scale: float = 1.0, sqrt: bool = False, workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1304,18 +1343,8 @@ def flat_search_topk_rows(flat_filter: str, metric: int, queries: torch.Tensor, 
     (``'f16x2'``) or ``_i8`` (``'i8x3'``) over the ``n_sel`` (default: all) ascending offsets ``rows`` i32 instead of the table: the answer
     of that search with the list's rows as its bitmap, bit for bit.  ``flat_overflow_count`` / ``flat_list_counts`` read this workspace
     too."""
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    n_sel = rows.numel() if n_sel is None else int(n_sel)
-    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= n_sel
-    dev = queries.device
-    code = _capi.FLAT_FILTER[flat_filter]
-    ws = _flat_workspace('flat_search_rows_workspace_bytes', (code, n_sel, D, B, k), dev, workspace)
-    od, oi = _flat_topk_outputs(B, k, dev)
-    check(lib().annlite_flat_search_topk_rows(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(),
-                                              _ptr(centre), N, rows.data_ptr(), n_sel, int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_search_topk_rows')
-    return od, oi
+    return _flat_row_set_call('rows', flat_filter, metric, queries, vectors, norms, n_rows, _listed_rows(rows, n_sel), centre, scale, workspace,
+                              k=k, sqrt=sqrt)
 
 
 def flat_filter_rows(flat_filter: str, metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
@@ -1324,28 +1353,11 @@ def flat_filter_rows(flat_filter: str, metric: int, queries: torch.Tensor, vecto
     """``annlite_flat_filter_rows``: one stage of the ``flat_filter`` filter over every ``stride``-th of the ``n_sel`` offsets ``rows``:
     ``(cand i32 [B, cap] -- offsets --, count i32 [B])`` and, with ``scores=True`` (not ``'f32'``), the filter's score of every
     (query, stage row) pair by LIST POSITION, f32 [B, ceil(n_sel / stride)]."""
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    n_sel = rows.numel() if n_sel is None else int(n_sel)
-    assert rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= n_sel
-    dev = queries.device
-    code = _capi.FLAT_FILTER[flat_filter]
-    ws = _flat_workspace('flat_search_rows_workspace_bytes', (code, n_sel, D, B, 1), dev, workspace)
-    cand, count, sc = _flat_lists(B, dev, (n_sel + stride - 1) // stride if scores else None)
-    check(lib().annlite_flat_filter_rows(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(),
-                                         _ptr(centre), N, rows.data_ptr(), n_sel, stride, bounds.data_ptr(), cand.data_ptr(), count.data_ptr(),
-                                         _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_filter_rows')
-    return (cand, count, sc) if scores else (cand, count)
+    return _flat_row_set_call('rows', flat_filter, metric, queries, vectors, norms, n_rows, _listed_rows(rows, n_sel), centre, scale, workspace,
+                              bounds=bounds, stride=stride, scores=scores)
 
 
 # ---------------------------------------------------------------------------------------------- a filter per query (DESIGN.md section 3.6)
-def _group_args(masks: torch.Tensor, group: torch.Tensor, B: int, N: int):
-    """``(masks, mask_ld, G, group)`` as the grouped entries take them: i32 [G, mask_ld] bitmaps, i32 [B] group ids"""
-    assert masks.dtype == torch.int32 and masks.ndim == 2 and masks.is_contiguous() and masks.shape[1] * 32 >= N
-    assert group.dtype == torch.int32 and group.is_contiguous() and group.numel() == B
-    return masks.data_ptr(), masks.shape[1], masks.shape[0], group.data_ptr()
-
-
 def flat_search_topk_grouped(flat_filter: str, metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, masks: torch.Tensor,
                              group: torch.Tensor, k: int, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
                              centre: Optional[torch.Tensor] = None, scale: float = 1.0, sqrt: bool = False,
@@ -1355,16 +1367,8 @@ def flat_search_topk_grouped(flat_filter: str, metric: int, queries: torch.Tenso
     caller), ``group`` i32 [B] in ``[0, G)`` -- an id outside selects nothing.  Row b of the answer is that search's for query b with
     ``masks[group[b]]`` as its bitmap, bit for bit.  ``valid_bits``: the live bitmap (which rows are scored at all).
     ``flat_overflow_count`` / ``flat_list_counts`` read this workspace too."""
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    code = _capi.FLAT_FILTER[flat_filter]
-    ws = _flat_workspace('flat_search_grouped_workspace_bytes', (code, N, D, B, k), dev, workspace)
-    od, oi = _flat_topk_outputs(B, k, dev)
-    check(lib().annlite_flat_search_topk_grouped(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(),
-                                                 _ptr(centre), N, _ptr(valid_bits), *_group_args(masks, group, B, N), int(k), 1 if sqrt else 0,
-                                                 od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), 'flat_search_topk_grouped')
-    return od, oi
+    return _flat_row_set_call('grouped', flat_filter, metric, queries, vectors, norms, n_rows, _grouped_rows(valid_bits, masks, group), centre,
+                              scale, workspace, k=k, sqrt=sqrt)
 
 
 def flat_filter_grouped(flat_filter: str, metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
@@ -1374,14 +1378,5 @@ def flat_filter_grouped(flat_filter: str, metric: int, queries: torch.Tensor, ve
     """``annlite_flat_filter_grouped``: one stage of the ``flat_filter`` filter over every ``stride``-th row of the table with a bitmap
     per query (``masks`` / ``group`` as ``flat_search_topk_grouped``): ``(cand i32 [B, cap], count i32 [B])`` and, with ``scores=True``
     (not ``'f32'``), the filter's score of every (query, stage row) pair, f32 [B, ceil(N / stride)]."""
-    B, D = queries.shape
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    code = _capi.FLAT_FILTER[flat_filter]
-    ws = _flat_workspace('flat_search_grouped_workspace_bytes', (code, N, D, B, 1), dev, workspace)
-    cand, count, sc = _flat_lists(B, dev, (N + stride - 1) // stride if scores else None)
-    check(lib().annlite_flat_filter_grouped(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(),
-                                            _ptr(centre), N, _ptr(valid_bits), *_group_args(masks, group, B, N), stride, bounds.data_ptr(),
-                                            cand.data_ptr(), count.data_ptr(), _ptr(sc), ws.data_ptr(), ws.numel(), stream_ptr()),
-          'flat_filter_grouped')
-    return (cand, count, sc) if scores else (cand, count)
+    return _flat_row_set_call('grouped', flat_filter, metric, queries, vectors, norms, n_rows, _grouped_rows(valid_bits, masks, group), centre,
+                              scale, workspace, bounds=bounds, stride=stride, scores=scores)
