@@ -105,6 +105,7 @@ SYMBOLS = (
     'annlite_debug_items',
     'annlite_debug_prep_timeline',
     'annlite_debug_seed_candidates',
+    'annlite_debug_scan_resolve',
     'annlite_flat_row_norms',
     'annlite_flat_list_capacity',
     'annlite_flat_slack',

@@ -434,44 +434,35 @@ struct FastCfg {
 
 // Kernel variants per M.  ANNLITE_SCAN_VARIANT (environment, parsed at load -- common.h: Knobs; A/B measurements) selects among the
 // instantiations; variant 0 is the default plan for every M.  Which of the two M = 16 kernels serves a table -- byte or u16
-// filter tables -- is otherwise decided inside the library, per call (search_policy below): the entry points scope their
-// choice to the call through this thread-local (never visible to the caller, never left set).
-static thread_local int g_variant_scope = -1;
-struct VariantScope {
-    int prev;
-    explicit VariantScope(int v) : prev(g_variant_scope) { g_variant_scope = v; }
-    ~VariantScope() { g_variant_scope = prev; }
-};
-static int env_variant() { return knobs().scan_variant; }  // (ANNLITE_SCAN_VARIANT as parsed at load / the last reload)
-static int scan_variant() {
-    if (g_variant_scope >= 0) return g_variant_scope;
-    const int e = env_variant();
-    return e >= 0 ? e : 0;
-}
+// filter tables -- is otherwise decided inside the library, per call (search_policy below): the entry points hand their
+// choice down as a ScanVariant argument (never visible to the caller); kn.scan_variant is the only process-wide input.
+enum ScanVariant { kVariantEnv = -1, kVariantU16 = 31, kVariantByte = 50 };  // as the environment says / u16 tables / byte tables, as the library asks
+// (neither the library's caller chain nor ANNLITE_SCAN_VARIANT names a variant: the per-call choice and the two-region plans apply)
+static bool variant_free(ScanVariant v, const Knobs &kn) { return v == kVariantEnv && kn.scan_variant < 0; }
 
 // tiles: the plan of annlite_pq_search_tiles (IVF cells) -- the u16 kernels' tile mode
-static bool fast_cfg(int64_t M, int64_t Ks, int code_bytes, int64_t k, FastCfg *c, bool tiles = false) {
+static bool fast_cfg(int64_t M, int64_t Ks, int code_bytes, int64_t k, FastCfg *c, bool tiles, ScanVariant variant, const Knobs &kn) {
     if (Ks < 1 || k > 64 || k < 1) return false;
+    const int v = variant != kVariantEnv ? (int)variant : kn.scan_variant >= 0 ? kn.scan_variant : 0;
     if (code_bytes == 2) {
         // uint16 codes (Ks > 256; the reference's PQ tests run Ks = 512 and 768 at M = 8): the u16-table kernel with 8 queries
         // per workgroup, as many codes as fit the LDS, PLAIN layout, row slices only
-        if (tiles || knobs().no_fast_code16) return false;  // (the switch: A/B against the generic kernel)
+        if (tiles || kn.no_fast_code16) return false;  // (the switch: A/B against the generic kernel)
         // M = 8, Ks <= 512, k <= 16: the byte-table kernel (scan_q8.hip, C16: table [Ks][2][8][16 B], 32 queries per workgroup,
         // conflict-free); ANNLITE_SCAN_VARIANT=31: the u16-table kernel (A/B)
-        if (M == 8 && Ks <= 512 && k <= 16 && (scan_variant() == 0 || scan_variant() == 50)) { *c = {8, 4, 2, 16, 4, 1, 850, 5}; return true; }
+        if (M == 8 && Ks <= 512 && k <= 16 && (v == 0 || v == 50)) { *c = {8, 4, 2, 16, 4, 1, 850, 5}; return true; }
         // (16 < k <= 64, round 6: the same kernel with 64-key lists -- only where the library asks for it, variant 50, as for M = 16)
-        if (M == 8 && Ks <= 512 && k <= 64 && scan_variant() == 50) { *c = {8, 4, 2, 16, 4, 1, 8650, 5}; return true; }
+        if (M == 8 && Ks <= 512 && k <= 64 && v == 50) { *c = {8, 4, 2, 16, 4, 1, 8650, 5}; return true; }
         if (M == 8 && Ks <= 512) { *c = {8, 4, 2, 16, 4, 1, 8217, 4}; return true; }   // u16 tables, 16 queries per workgroup
         // 512 < Ks <= 1024: byte tables of ONE entry group (16 queries per workgroup; 2-way bank conflicts, inherent -- still
         // half the LDS time per query of the u16 tables' 8)
-        if (M == 8 && Ks <= 1024 && k <= 16 && (scan_variant() == 0 || scan_variant() == 50)) { *c = {8, 4, 1, 16, 4, 1, 851, 5}; return true; }
-        if (M == 8 && Ks <= 1024 && k <= 64 && scan_variant() == 50) { *c = {8, 4, 1, 16, 4, 1, 8651, 5}; return true; }
+        if (M == 8 && Ks <= 1024 && k <= 16 && (v == 0 || v == 50)) { *c = {8, 4, 1, 16, 4, 1, 851, 5}; return true; }
+        if (M == 8 && Ks <= 1024 && k <= 64 && v == 50) { *c = {8, 4, 1, 16, 4, 1, 8651, 5}; return true; }
         if (M == 8 && Ks <= 1024) { *c = {8, 4, 1, 16, 4, 1, 8216, 4}; return true; }
         if (M == 16 && Ks <= 512) { *c = {16, 4, 1, 16, 4, 1, 16216, 4}; return true; }
         return false;
     }
     if (code_bytes != 1 || Ks > 256) return false;
-    const int v = scan_variant();
     switch (M) {
         case 8:
             // default: byte tables (scan_q8.hip, M8 shape: table [Ks][2][8][16 B] = 64 KB, 32 queries / WG); k > 16, tile mode and
@@ -520,7 +511,6 @@ static bool lk64_shape(int64_t M, int64_t Ks, int code_bytes, int64_t k) {
 // shapes without a filter kernel whose fp32 table [M][Ks] fits the LDS beside the waves' merge scratch: adc_scan_lds_kernel
 static bool generic_table_in_lds(int64_t M, int64_t Ks) { return M * Ks * 4 <= 144 * 1024; }
 
-static int round_up(int64_t x, int64_t m) { return (int)(((x + m - 1) / m) * m); }
 // queries the per-query workspace arrays are sized for: whole tiles, at least the 16 the fp32 TILED table is padded to
 static int64_t pad_queries(int64_t B, int qt) {
     const int64_t p = qt > 16 ? qt : 16;
@@ -533,7 +523,7 @@ static int64_t pad_queries(int64_t B, int qt) {
 static bool m32_wants_8_slices(int64_t N, int n_tiles) { return N >= 8000000 && n_tiles >= 32 && n_tiles <= 128; }
 
 static void plan_slices(int64_t N, int n_tiles, int waves, int n_cu, bool xcd8, int *n_slices, int64_t *slice_rows,
-                        int64_t B = 0, bool m32_bytes = false) {
+                        const Knobs &kn, int64_t B = 0, bool m32_bytes = false) {
     // at least one slice per XCD; more when few query tiles exist, as long as every wave keeps
     // >= 8 steps of 64 rows
     const int64_t min_rows = (int64_t)waves * 64 * (xcd8 ? 16 : 8);
@@ -551,10 +541,8 @@ static void plan_slices(int64_t N, int n_tiles, int waves, int n_cu, bool xcd8, 
     if (ns < 1) ns = 1;
     if (xcd8 && m32_bytes && ns == 4 && m32_wants_8_slices(N, n_tiles)) ns = 8;
     if (xcd8) {
-        {
-            const int64_t v = knobs().scan_slices;  // (ANNLITE_SCAN_SLICES)
-            if (v == 1 || v == 2 || v == 4 || (v >= 8 && v % 8 == 0 && v <= 4096)) ns = v;
-        }
+        const int64_t v = kn.scan_slices;  // (ANNLITE_SCAN_SLICES)
+        if (v == 1 || v == 2 || v == 4 || (v >= 8 && v % 8 == 0 && v <= 4096)) ns = v;
     }
     int64_t rows = (N + ns - 1) / ns;
     rows = ((rows + 63) / 64) * 64;
@@ -567,81 +555,125 @@ static void plan_slices(int64_t N, int n_tiles, int waves, int n_cu, bool xcd8, 
 
 using namespace annlite;
 
-static int plan_query_impl(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t B, int64_t k, int force_ns,
-                           annlite_scan_plan *plan);
+static size_t r256z(size_t x) { return (x + 255) / 256 * 256; }
 
-// force_ns > 0: tile mode (every query tile scans its own row range as ONE work item)
-static int plan_query_impl(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t B, int64_t k, int force_ns,
-                           annlite_scan_plan *plan) {
-    ANNLITE_REQUIRE(plan != nullptr, "plan is NULL");
-    ANNLITE_REQUIRE(N >= 0 && M >= 1 && Ks >= 1 && B >= 0, "bad shape N=%lld M=%lld Ks=%lld B=%lld", (long long)N,
-                    (long long)M, (long long)Ks, (long long)B);
-    ANNLITE_REQUIRE(code_bytes == 1 || code_bytes == 2 || code_bytes == 4, "code_bytes must be 1, 2 or 4");
-    ANNLITE_REQUIRE(k >= 1 && k <= 64, "k=%lld outside [1,64] (larger k: annlite_adc_dist + host-side selection)",
-                    (long long)k);
-    ANNLITE_REQUIRE(N < (1ll << 32) - 1, "N must be < 2^32-1 rows per call (shard the table)");
-    FastCfg c;
-    const int n_cu = device_cu_count();
-    memset(plan, 0, sizeof(*plan));
+// The scan workspace of the filter plans, ONE ordered table of regions (all 256-byte aligned): the offsets the launches use, the
+// extent the reset fills (the first six regions: slots of slices that hold no rows stay "none", counters and guard all-ones) and the
+// bytes the plan reports all come from it.
+//   [lists u64 x tiles*qt*slices*k][gkey u64 x Bpad][gk2][tile_done u32 x tiles][item counter][guard block][Smax f32 x Bpad]
+//   [qstep f32 x Bpad][qlo f64 x Bpad][big: q16 u16 x Bpad*M*Ks (u16 plan) | qlom, gseed0, btab, MFMA nominees (byte plan)]
+enum ScanRegion { kRegLists, kRegGkey, kRegGk2, kRegTileDone, kRegItemCounter, kRegGuard, kRegSmax, kRegQstep, kRegQlo, kRegBig, kRegCount };
+struct ScanLayout {
+    int64_t off[kRegCount];  // from the workspace base
+    int64_t fill;            // end of the guard block
+    int64_t counted;         // what the plan reports: size + 256 per region, a flat 256 for the counter and the guard block, the big
+                             // region at the u16 tables' size whatever the plan (more than the carve's round256: kept as it has been)
+    int64_t qlom, gseed0, btab, cand;  // byte plan, inside the big region (gseed0 / btab: with prebuilt tables; cand: where it fits)
+};
+static ScanLayout scan_layout(const FastCfg &c, int64_t M, int64_t Ks, int64_t k, int64_t n_tiles, int64_t ns, int64_t bpad, bool prebuilt) {
+    // (the byte-table kernel publishes up to kGk2Keys keys per (query, slice) cell whatever M is)
+    const int64_t size[kRegCount] = {n_tiles * c.qt() * ns * k * 8, bpad * 8, bpad * ns * 8 * (c.mode == 5 ? kGk2Keys : gk2_cell_keys(M)),
+                                     n_tiles * 4, 4, 64 /* (reset to all-ones by the fill, like the counters) */, bpad * 4, bpad * 4, bpad * 8,
+                                     bpad * M * Ks * 2};
+    ScanLayout l = {};
+    int64_t off = 0;
+    for (int i = 0; i < kRegCount; ++i) {
+        l.off[i] = off;
+        if (i < kRegBig) off += (int64_t)r256z((size_t)size[i]);
+        if (i == kRegGuard) l.fill = off;
+        l.counted += (i == kRegItemCounter || i == kRegGuard) ? 256 : size[i] + 256;
+    }
+    // byte-table kernel: no u16 tables, the per-(query, sub-space) minima instead (same region, smaller), then the seed keys and the
+    // prebuilt byte tables of the ONE preparation launch (inside the region the u16 plan uses for q16), then the MFMA nominees
+    l.qlom = off;
+    l.gseed0 = l.qlom + (int64_t)r256z((size_t)(bpad * M * 4));
+    l.btab = l.gseed0 + (prebuilt ? (int64_t)r256z((size_t)(bpad * 8)) : 0);
+    l.cand = l.btab + (prebuilt ? (int64_t)r256z((size_t)(n_tiles * kQ8Image16)) : 0);
+    return l;
+}
+
+struct ScanShape {  // tiles: tile mode (every query tile scans its own row range as ONE work item)
+    int64_t N, M, Ks; int code_bytes; int64_t B, k; bool tiles;
+};
+struct ScanPlanned {
+    annlite_scan_plan plan;  // what the public entries report
+    bool fast;
+    FastCfg c;               // (fast)
+    ScanLayout lay;          // (fast with the filter) of the region this variant's launch works in
+    int n_tiles;
+    int64_t slice_rows, bpad;
+};
+
+// one variant's plan: its kernel, slices and region
+static void plan_region(const ScanShape &s, ScanVariant variant, const Knobs &kn, int n_cu, ScanPlanned *out) {
+    annlite_scan_plan *plan = &out->plan;
+    memset(out, 0, sizeof(*out));
     plan->max_k = 64;
-    if (fast_cfg(M, Ks, code_bytes, k, &c, force_ns > 0)) {
-        plan->fast = 1;
-        plan->qi = c.QI;
-        plan->qt = c.qt();
-        plan->waves = c.NW;
-        const int n_tiles = (int)((B + plan->qt - 1) / plan->qt);
-        int ns;
-        int64_t sr;
-        plan_slices(N > 0 ? N : 1, n_tiles > 0 ? n_tiles : 1, c.NW, n_cu, true, &ns, &sr, B, c.mode == 5 && M == 32 && force_ns == 0);
-        if (force_ns > 0) ns = force_ns;
-        plan->n_slices = ns;
-        plan->lut_floats = ((B + 15) / 16) * 16 * M * Ks;  // padded to 16 queries
-        // [partial keys][Smax f32 x Bpad][qstep f32 x Bpad][qlo f64 x Bpad][lo,hi f32 x Bpad*M][q16 u16 x Bpad*M*Ks]
-        const int64_t bpad = pad_queries(B, plan->qt);
-        plan->workspace_bytes = (int64_t)n_tiles * plan->qt * ns * k * 8 + 256 + bpad * 4 + 256;
-        if (c.qf())
-            plan->workspace_bytes += bpad * 4 + 256 + 2 * (bpad * 8 + 256) + (bpad * ns * 8 * (c.mode == 5 ? kGk2Keys : gk2_cell_keys(M)) + 256) + (n_tiles * 4 + 256) +
-                                     256 /* item counter */ + 256 /* guard block */ + bpad * M * Ks * 2 + 256;
+    int ns;
+    out->fast = fast_cfg(s.M, s.Ks, s.code_bytes, s.k, &out->c, s.tiles, variant, kn);
+    if (out->fast) {
+        const FastCfg &c = out->c;
+        plan->fast = 1, plan->qi = c.QI, plan->qt = c.qt(), plan->waves = c.NW;
+        out->n_tiles = (int)((s.B + plan->qt - 1) / plan->qt);
+        plan_slices(s.N > 0 ? s.N : 1, out->n_tiles > 0 ? out->n_tiles : 1, c.NW, n_cu, true, &ns, &out->slice_rows, kn, s.B,
+                    c.mode == 5 && s.M == 32 && !s.tiles);
+        if (s.tiles) ns = 1;
+        plan->lut_floats = ((s.B + 15) / 16) * 16 * s.M * s.Ks;  // padded to 16 queries
+        out->bpad = pad_queries(s.B, plan->qt);
+        out->lay = scan_layout(c, s.M, s.Ks, s.k, out->n_tiles, ns, out->bpad, !kn.no_prebuilt_tables);
+        plan->workspace_bytes = c.qf() ? out->lay.counted : (int64_t)out->n_tiles * plan->qt * ns * s.k * 8 + 256 + out->bpad * 4 + 256;
+    } else {
+        plan->qi = plan->qt = 1;
+        plan->waves = generic_table_in_lds(s.M, s.Ks) ? 16 : 4;  // (adc_scan_lds_kernel: one 16-wave workgroup per query and row slice)
+        out->n_tiles = (int)s.B;
+        plan_slices(s.N > 0 ? s.N : 1, s.B > 0 ? (int)s.B : 1, plan->waves, n_cu, false, &ns, &out->slice_rows, kn);
+        plan->lut_floats = s.B * s.M * s.Ks;
+        plan->workspace_bytes = s.B * ns * s.k * 8;
+    }
+    plan->n_slices = ns;
+    if (plan->workspace_bytes < 8) plan->workspace_bytes = 8;
+}
+
+static int plan_scan(const ScanShape &s, ScanVariant variant, const Knobs &kn, int n_cu, ScanPlanned *out) {
+    ANNLITE_REQUIRE(s.N >= 0 && s.M >= 1 && s.Ks >= 1 && s.B >= 0, "bad shape N=%lld M=%lld Ks=%lld B=%lld", (long long)s.N,
+                    (long long)s.M, (long long)s.Ks, (long long)s.B);
+    ANNLITE_REQUIRE(s.code_bytes == 1 || s.code_bytes == 2 || s.code_bytes == 4, "code_bytes must be 1, 2 or 4");
+    ANNLITE_REQUIRE(s.k >= 1 && s.k <= 64, "k=%lld outside [1,64] (larger k: annlite_adc_dist + host-side selection)",
+                    (long long)s.k);
+    ANNLITE_REQUIRE(s.N < (1ll << 32) - 1, "N must be < 2^32-1 rows per call (shard the table)");
+    plan_region(s, variant, kn, n_cu, out);
+    if (!out->fast || !variant_free(variant, kn)) return ANNLITE_OK;
+    ScanPlanned other;
+    int64_t *ws = &out->plan.workspace_bytes;
+    if (out->c.mode == 5) {
         // byte-table plan chosen by default: the gated u16-table launch that redoes the scan if the byte-table launch gives
         // up (search_policy) works in its own region behind this one
-        if (c.mode == 5 && g_variant_scope < 0 && env_variant() < 0) {
-            annlite_scan_plan p2;
-            VariantScope vs(31);
-            if (plan_query_impl(N, M, Ks, code_bytes, B, k, force_ns, &p2) == ANNLITE_OK)
-                plan->workspace_bytes = ((plan->workspace_bytes + 255) / 256) * 256 + p2.workspace_bytes;
-        }
+        plan_region(s, kVariantU16, kn, n_cu, &other);
+        *ws = (int64_t)r256z((size_t)*ws) + other.plan.workspace_bytes;
+    } else if (s.k > 16 && lk64_shape(s.M, s.Ks, s.code_bytes, s.k) && !s.tiles) {
         // ... and the other way round for 16 < k <= 64 at M = 16: the public plan is the u16 plan, the library's search runs the
         // byte-table kernel (64-key lists) in a region of its own IN FRONT of it
-        if (c.mode == 4 && k > 16 && lk64_shape(M, Ks, code_bytes, k) && force_ns == 0 && g_variant_scope < 0 && env_variant() < 0) {
-            annlite_scan_plan p1;
-            VariantScope vs(50);
-            if (plan_query_impl(N, M, Ks, code_bytes, B, k, force_ns, &p1) == ANNLITE_OK)
-                plan->workspace_bytes = ((p1.workspace_bytes + 255) / 256) * 256 + plan->workspace_bytes;
-        }
-    } else {
-        plan->fast = 0;
-        plan->qi = 1;
-        plan->qt = 1;
-        plan->waves = generic_table_in_lds(M, Ks) ? 16 : 4;  // (adc_scan_lds_kernel: one 16-wave workgroup per query and row slice)
-        int ns;
-        int64_t sr;
-        plan_slices(N > 0 ? N : 1, B > 0 ? (int)B : 1, plan->waves, n_cu, false, &ns, &sr);
-        plan->n_slices = ns;
-        plan->lut_floats = B * M * Ks;
-        plan->workspace_bytes = B * ns * k * 8;
+        plan_region(s, kVariantByte, kn, n_cu, &other);
+        *ws = (int64_t)r256z((size_t)other.plan.workspace_bytes) + *ws;
     }
-    if (plan->workspace_bytes < 8) plan->workspace_bytes = 8;
     return ANNLITE_OK;
 }
 
-extern "C" int annlite_scan_plan_query(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t B, int64_t k,
-                                       annlite_scan_plan *plan) {
-    return plan_query_impl(N, M, Ks, code_bytes, B, k, 0, plan);
+static int plan_query_impl(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t B, int64_t k, bool tiles, annlite_scan_plan *plan,
+                           ScanVariant variant = kVariantEnv) {
+    ANNLITE_REQUIRE(plan != nullptr, "plan is NULL");
+    ScanPlanned p;
+    const int rc = plan_scan({N, M, Ks, code_bytes, B, k, tiles}, variant, knobs(), device_cu_count(), &p);
+    if (rc == ANNLITE_OK) *plan = p.plan;
+    return rc;
 }
 
-extern "C" int annlite_scan_plan_tiles(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t V, int64_t k,
-                                       annlite_scan_plan *plan) {
-    return plan_query_impl(N, M, Ks, code_bytes, V, k, 1, plan);
+extern "C" int annlite_scan_plan_query(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t B, int64_t k, annlite_scan_plan *plan) {
+    return plan_query_impl(N, M, Ks, code_bytes, B, k, false, plan);
+}
+
+extern "C" int annlite_scan_plan_tiles(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t V, int64_t k, annlite_scan_plan *plan) {
+    return plan_query_impl(N, M, Ks, code_bytes, V, k, true, plan);
 }
 
 static unsigned long long *g_dbg = nullptr;  // debug only (ANNLITE_DEBUG_COUNTERS): leaked device buffer: 16 counters + 4096 per-item records of 8
@@ -685,15 +717,10 @@ static void prof_end(hipStream_t st) {
     g_ev_valid = 1;
 }
 
-// run the scan kernels: fills workspace with the per-(query, slice) sorted key lists [B][NS][k]
 // where a scan that can merge its slices itself puts the final result (merged is set when it did)
 struct ScanOut {
-    float *d;
-    int64_t *i;
-    int64_t *packed;
-    int64_t row_base;
-    int sqrt_out;
-    bool merged;
+    float *d; int64_t *i; int64_t *packed;
+    int64_t row_base; int sqrt_out; bool merged;
 };
 // tile mode (annlite_pq_search_tiles): query tile t = queries [t*qt, (t+1)*qt) scans rows tile_rows[t]
 struct TileMode {
@@ -721,104 +748,113 @@ struct SplitOpt {
     unsigned long long *seed_keys;  // PREPARE: [B][kSeedKeys] out
 };
 
-static int scan_partial(const void *codes_dev, int code_bytes, int codes_layout, int64_t N, int64_t M, int64_t Ks,
-                        const uint32_t *valid_bits_dev, const float *lut_dev, int64_t B, int64_t k,
-                        void *workspace_dev, size_t workspace_bytes, hipStream_t st, annlite_scan_plan *plan_out,
-                        bool share_across_slices, const LutBuild *build = nullptr, ScanOut *outp = nullptr,
-                        const TileMode *tm = nullptr, GuardOpt *gopt = nullptr, const SplitOpt *split = nullptr,
-                        bool cand_seed = false) {
-    annlite_scan_plan plan;
-    int rc = plan_query_impl(N, M, Ks, code_bytes, B, k, tm ? 1 : 0, &plan);
-    if (rc != ANNLITE_OK) return rc;
-    *plan_out = plan;
-    if (B == 0) return ANNLITE_OK;
-    if (tm) {
-        FastCfg ct;
-        ANNLITE_REQUIRE(plan.fast && fast_cfg(M, Ks, code_bytes, k, &ct, true) && ct.mode == 4,
-                        "tile mode needs the quantised-filter plan (M in {8,16,32,64}, Ks <= 256, uint8 codes)");
-        ANNLITE_REQUIRE(B % plan.qt == 0 && tm->tile_rows && tm->vmap && tm->cand && tm->cand_count && tm->cand_cap >= 64,
-                        "tile mode: B=%lld must be a multiple of the tile size %d", (long long)B, plan.qt);
+// one statement per code width (T = the code type)
+#define ANNLITE_BY_CODE_BYTES(cb, ...)                                                                                            \
+    if ((cb) == 1) { using T = uint8_t; __VA_ARGS__; } else if ((cb) == 2) { using T = uint16_t; __VA_ARGS__; } else { using T = uint32_t; __VA_ARGS__; }
+
+// the operands of one scan: what the entries hand to resolve() and issue()
+struct ScanCall {
+    const void *codes; int code_bytes, codes_layout; int64_t N, M, Ks;  // the table: [N][M] codes, PLAIN or SKEWED, Ks centroids per sub-space
+    const uint32_t *valid;
+    const float *lut; int64_t B, k;  // the queries' fp32 tables (with build: where they go)
+    void *ws; size_t ws_bytes;
+    bool share;             // the slices share their bounds (the top-k searches); false: every slice keeps its complete list
+    const LutBuild *build;  // the tables are built inside the call
+    ScanOut *out; const TileMode *tm; GuardOpt *guard; const SplitOpt *split;  // (each optional)
+    bool cand_seed;         // the candidate generator may start its slices from ONE seed bound (annlite_pq_search_candidates)
+};
+
+// ScanArgs' pointer fields / scalar fields, in struct order (clk and stats_seq are wired by issue(): profiling, the caller's count)
+#define ANNLITE_SCAN_PTRS(X)                                                                                                       \
+    X(codes) X(valid) X(lut) X(partial) X(smax) X(q16) X(qstep) X(qlo) X(qlom) X(gkey) X(gk2) X(gseed) X(tile_done) X(out_d) X(out_i) \
+    X(out_packed) X(dbg) X(tile_rows) X(vmap) X(item_counter) X(cand) X(cand_count) X(guard) X(gate) X(host_stats) X(gseed0) X(btab)
+#define ANNLITE_SCAN_SCALARS(X)                                                                                                    \
+    X(N) X(Ks) X(B) X(k) X(n_tiles) X(n_slices) X(n_items) X(slice_rows) X(jm1) X(row_base) X(sqrt_out) X(flush_mask) X(dbg_skip)    \
+    X(tl_private) X(cand_cap) X(q8_epoch0) X(q8_epoch_mul) X(q8_ring_limit) X(q8_import_mask) X(q8_target) X(q8_thw_mask)            \
+    X(q8_rebuild_8ths) X(guard_abort) X(guard_base) X(q8_early_merge) X(q8_merge_patience) X(q8_map_slices) X(q8_pos) X(q8_ilv_log)
+enum ScanPtr {
+#define X(f) kP_##f,
+    ANNLITE_SCAN_PTRS(X)
+#undef X
+    kPtrCount
+};
+constexpr int64_t kPtrNull = -1, kPtrCaller = -2;  // ScanLaunch::ptr: >= 0 is an offset from the workspace base
+enum ScanFamily { kFamQ8, kFamQfilter, kFamLds, kFamGeneric };
+enum ScanPrep { kPrepNone, kPrepQuantise /* quantise + seed bound */, kPrepOne /* ONE preparation launch */, kPrepDone /* by the PREPARE half */ };
+enum ScanStage { kStageNone, kStageFill /* N == 0 */, kStagePrepare /* the PREPARE half */, kStageScan };
+
+// what resolve() fixes and issue() launches from
+struct ScanLaunch {
+    int rc, stage;
+    ScanPlanned p;
+    ScanArgs a;               // the scalars; issue() fills the pointers from ptr[]
+    int64_t ptr[kPtrCount];
+    int family, id, grid;
+    size_t lds;               // (generic kernels)
+    bool skewed, fused_fill, merged, guarded, dbg, mfma;
+    int64_t fill_bytes;
+    int prep;
+    int64_t Bq;                     // queries whose tables are quantised (tile mode: the real queries)
+    int64_t S, S_prep, seed_extent;  // seed rows of the shared first bound / as the preparation launch takes them / spread over
+    int64_t S_slice;                // per-slice seed of the candidate generator (0: none)
+};
+
+static int scan_call_check(const ScanCall &q, const ScanPlanned &p) {
+    const annlite_scan_plan &plan = p.plan;
+    if (q.tm) {
+        ANNLITE_REQUIRE(p.fast && p.c.mode == 4, "tile mode needs the quantised-filter plan (M in {8,16,32,64}, Ks <= 256, uint8 codes)");
+        ANNLITE_REQUIRE(q.B % plan.qt == 0 && q.tm->tile_rows && q.tm->vmap && q.tm->cand && q.tm->cand_count && q.tm->cand_cap >= 64,
+                        "tile mode: B=%lld must be a multiple of the tile size %d", (long long)q.B, plan.qt);
     }
-    ANNLITE_REQUIRE(codes_layout == ANNLITE_CODES_PLAIN || (codes_layout == ANNLITE_CODES_SKEWED && plan.fast && code_bytes == 1),
-                    "codes_layout %d not supported by this plan (SKEWED needs the fast plan and uint8 codes)", codes_layout);
-    ANNLITE_REQUIRE(lut_dev && workspace_dev, "null device pointer");
-    ANNLITE_REQUIRE(N == 0 || codes_dev, "codes_dev is NULL");
-    if (workspace_bytes < (size_t)plan.workspace_bytes) {
-        set_error("workspace %zu B < required %lld B", workspace_bytes, (long long)plan.workspace_bytes);
+    ANNLITE_REQUIRE(q.codes_layout == ANNLITE_CODES_PLAIN || (q.codes_layout == ANNLITE_CODES_SKEWED && p.fast && q.code_bytes == 1),
+                    "codes_layout %d not supported by this plan (SKEWED needs the fast plan and uint8 codes)", q.codes_layout);
+    ANNLITE_REQUIRE(q.lut && q.ws, "null device pointer");
+    ANNLITE_REQUIRE(q.N == 0 || q.codes, "codes_dev is NULL");
+    if (q.ws_bytes < (size_t)plan.workspace_bytes) {
+        set_error("workspace %zu B < required %lld B", q.ws_bytes, (long long)plan.workspace_bytes);
         return ANNLITE_ERR_WORKSPACE;
     }
-    const int n_cu = device_cu_count();
-    ScanArgs a = {};
-    a.codes = codes_dev;
-    a.valid = valid_bits_dev;
-    a.lut = lut_dev;
-    a.partial = (unsigned long long *)workspace_dev;
-    a.N = N;
-    a.Ks = (int)Ks;
-    a.B = (int)B;
-    a.k = (int)k;
-    a.n_tiles = (int)((B + plan.qt - 1) / plan.qt);
-    a.n_slices = plan.n_slices;
-    a.smax = nullptr;
-    a.q16 = nullptr;
-    a.qstep = nullptr;
-    a.qlo = nullptr;
-    a.gkey = nullptr;
-    a.dbg = nullptr;
-    const Knobs &kn = knobs();  // (one block for the whole call)
-    a.dbg_skip = kn.debug_skip;
-    if (kn.debug_counters && !(gopt && gopt->gate)) {  // (the gated pass leaves the first launch's counters alone)
-        if (!g_dbg) ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg, 8 * (kDbgSplit + 4)));
-        if (!g_dbg_prep) {
-            ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg_prep, 64));
-            ANNLITE_HIP_TRY(hipMemset(g_dbg_prep, 0, 64));
-        }
-        ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg, 0, 128, st));
-        ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg + kDbgSplit, 0, 32, st));
-        a.dbg = g_dbg;
-        if (kn.debug_counters == 2) a.dbg_skip |= 8;  // phase stamps only (annlite_debug_timeline): the
-                                                                           // per-wave event counters cost tens of microseconds
-    }
-    {
-        int ns;
-        int64_t sr;
-        FastCfg cs;
-        const bool m32_bytes = plan.fast && !tm && M == 32 && fast_cfg(M, Ks, code_bytes, k, &cs, false) && cs.mode == 5;
-        plan_slices(N > 0 ? N : 1, a.n_tiles, plan.waves, n_cu, plan.fast != 0, &ns, &sr, B, m32_bytes);
-        a.slice_rows = tm ? ((N + 63) / 64) * 64 : sr;
-    }
-    // slots of slices that hold no rows stay "none"
-    size_t fill_bytes = 0;
-    bool fused_fill = false;
-    {
-        // partial lists, and (quantised-filter plan) the shared bounds right behind them; the rest is scratch
-        size_t fill = (size_t)plan.workspace_bytes;
-        FastCfg c0;
-        if (plan.fast && fast_cfg(M, Ks, code_bytes, k, &c0, tm != nullptr) && c0.qf()) {
-            const size_t bpad = (size_t)pad_queries(B, plan.qt);
-            auto r256 = [](size_t x) { return (x + 255) / 256 * 256; };
-            fill = r256((size_t)a.n_tiles * plan.qt * plan.n_slices * k * 8) + r256(bpad * 8) +
-                   r256(bpad * plan.n_slices * 8 * (c0.mode == 5 ? kGk2Keys : gk2_cell_keys(M))) + r256((size_t)a.n_tiles * 4) + 256 /* item counter */ +
-                   256 /* guard block */;
-        }
-        fill_bytes = fill;
-        FastCfg c1;
-        fused_fill = N > 0 && plan.fast && fast_cfg(M, Ks, code_bytes, k, &c1, tm != nullptr) && c1.qf() && M != 64;  // lut_quantise_fused_kernel
-        // (own kernel: one launch like any other of the plan, no second mechanism on the stream)
-        if (split && !fused_fill) return ANNLITE_NOT_APPLICABLE;  // (the split search is the fused preparation launch's)
-        if (!fused_fill) {
-            const int64_t n16 = (int64_t)((fill + 15) / 16);
-            hipLaunchKernelGGL(fill_ones_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, (u32x4 *)workspace_dev, n16);
-        }
-    }
-    if (N == 0) return ANNLITE_OK;
-    const int n_items = tm ? a.n_tiles
-                           : (plan.fast && a.n_slices < 8) ? ((a.n_tiles + 8 / a.n_slices - 1) / (8 / a.n_slices)) * 8
-                                                           : a.n_tiles * a.n_slices;
-    a.n_items = n_items;
-    if (plan.fast) {
-        FastCfg c;
-        fast_cfg(M, Ks, code_bytes, k, &c, tm != nullptr);
+    return ANNLITE_OK;
+}
+
+// Everything a scan decides, from the shape, the options, the variant and the switches alone: pure host code -- no HIP call, no
+// device pointer followed -- so annlite_debug_scan_resolve can show it without a GPU.
+static ScanLaunch resolve(const ScanCall &q, ScanVariant variant, const Knobs &kn, int n_cu) {
+    ScanLaunch L = {};
+    ScanArgs &a = L.a;
+    const int64_t N = q.N, M = q.M, Ks = q.Ks, B = q.B, k = q.k;
+    const TileMode *tm = q.tm; const GuardOpt *gopt = q.guard; const SplitOpt *split = q.split;
+    for (int64_t &p : L.ptr) p = kPtrNull;
+    L.rc = plan_scan({N, M, Ks, q.code_bytes, B, k, tm != nullptr}, variant, kn, n_cu, &L.p);
+    if (L.rc != ANNLITE_OK || B == 0) return L;
+    if ((L.rc = scan_call_check(q, L.p)) != ANNLITE_OK) return L;
+    const annlite_scan_plan &plan = L.p.plan;
+    const FastCfg &c = L.p.c; const ScanLayout &lay = L.p.lay;
+    const bool fast = L.p.fast;
+    if (q.codes) L.ptr[kP_codes] = kPtrCaller;
+    if (q.valid) L.ptr[kP_valid] = kPtrCaller;
+    L.ptr[kP_lut] = kPtrCaller, L.ptr[kP_partial] = 0;
+    a.N = N, a.Ks = (int)Ks, a.B = (int)B, a.k = (int)k;
+    a.n_tiles = L.p.n_tiles, a.n_slices = plan.n_slices;
+    L.dbg = kn.debug_counters && !(gopt && gopt->gate);  // (the gated pass leaves the first launch's counters alone)
+    if (L.dbg) L.ptr[kP_dbg] = kPtrCaller;
+    // (debug_counters == 2: phase stamps only (annlite_debug_timeline): the per-wave event counters cost tens of microseconds)
+    a.dbg_skip = kn.debug_skip | (L.dbg && kn.debug_counters == 2 ? 8 : 0);
+    a.slice_rows = tm ? ((N + 63) / 64) * 64 : L.p.slice_rows;
+    // slots of slices that hold no rows stay "none": partial lists, and (quantised-filter plan) the shared bounds right behind them;
+    // the rest is scratch
+    L.fill_bytes = fast && c.qf() ? lay.fill : plan.workspace_bytes;
+    // (own kernel otherwise: one launch like any other of the plan, no second mechanism on the stream)
+    L.fused_fill = N > 0 && fast && c.qf() && M != 64;  // lut_quantise_fused_kernel
+    if (split && !L.fused_fill) return L.rc = ANNLITE_NOT_APPLICABLE, L;  // (the split search is the fused preparation launch's)
+    L.stage = N == 0 ? kStageFill : kStageScan;
+    if (N == 0) return L;
+    L.skewed = q.codes_layout == ANNLITE_CODES_SKEWED;
+    a.n_items = tm ? a.n_tiles
+                   : (fast && a.n_slices < 8) ? ((a.n_tiles + 8 / a.n_slices - 1) / (8 / a.n_slices)) * 8
+                                              : a.n_tiles * a.n_slices;
+    if (fast) {
+        L.family = c.mode == 5 ? kFamQ8 : kFamQfilter, L.id = c.id;
         // M = 64 (64-byte rows: 640 MB at 10M rows): tile-per-XCD makes every XCD stream the whole table (FETCH_SIZE 6.2 GB per
         // launch, 36 % of the HBM peak, L2 hit rate 71 %) and its candidates are few -- slice-per-XCD instead: an XCD streams its
         // row slices once for all the query tiles that walk them together.  ANNLITE_Q8_MAP=0/1 overrides (A/B).
@@ -833,22 +869,15 @@ static int scan_partial(const void *codes_dev, int code_bytes, int codes_layout,
         // 0.326 -> 0.337 at 1.25M (every slice now inserts the hot region's rows into its own list); the bench's tables -0.3 % (noise).  Exact
         // either way (332 GPU tests with it on); not adopted.  Never for the candidate generator of the re-rank stage: its per-slice seed
         // bounds are bounds of the slice's OWN contiguous rows.
-        a.q8_ilv_log = 0;
-        {
-            const int t = kn.q8_ilv;
-            if (c.mode == 5 && share_across_slices && !tm && a.n_slices >= 2 && t >= 0 && t <= 8) a.q8_ilv_log = t;
-        }
+        a.q8_ilv_log = (c.mode == 5 && q.share && !tm && a.n_slices >= 2 && kn.q8_ilv >= 0 && kn.q8_ilv <= 8) ? kn.q8_ilv : 0;
         // epochs end after steps 15, 255, 4095 (x 15 blocks of 64 rows) and a slot asks for a new table when its T has halved:
         // 10M rows x 1024 queries 1.497 ms per launch with {3, 15, 63, ...} / T 64 / rebuild at 7/8, 1.445 with this, 1.441 with no
         // epoch at all (1.25M rows: 0.284 / 0.261 / 0.254) -- on the bench's data a barrier of all 16 waves costs more than a
         // finer table saves; the sparse schedule stays as the guard against a seed bound that is far off
-        a.q8_epoch0 = 15;
-        a.q8_epoch_mul = 16;
-        a.q8_ring_limit = 384;
-        a.q8_import_mask = 3;
+        a.q8_epoch0 = 15, a.q8_epoch_mul = 16, a.q8_ring_limit = 384;
         // (64-key lists: an import ranks 32 published keys per slot -- every 8th batch instead of every 4th: 1.79 against 1.87 ms at
         // k = 50, 10M rows; every 2nd 1.89, every 16th 1.84 -- profiles/r05/k50_knobs.txt)
-        if (c.mode == 5 && k > 16) a.q8_import_mask = 7;
+        a.q8_import_mask = (c.mode == 5 && k > 16) ? 7 : 3;
         // (M = 64: u16 sums of 64 entries clipped at 15.  10M x 768-d, 256 queries, ms per launch at T = 256 / 384 / 512 / 768: 2.09 / 2.04 /
         // 2.03 / 3.54 -- a finer table clips more entries of a row near the bound: at 768 the filter leaks)
         // (M = 16, k <= 16: 88 -- at 1.25M rows, where the consumer wave is 75-85 % busy, T = 80 / 88 take 0.2367 / 0.2368 ms per batch against
@@ -865,93 +894,63 @@ static int scan_partial(const void *codes_dev, int code_bytes, int codes_layout,
         if (kn.q8_rebuild >= 0 && kn.q8_rebuild <= 8) a.q8_rebuild_8ths = kn.q8_rebuild;
         if (kn.q8_target >= 16 && kn.q8_target <= (M == 64 ? 960 : 127)) a.q8_target = kn.q8_target;
         if (kn.q8_tune_ok) {  // ANNLITE_Q8_TUNE = "epoch0,mul,ring_limit,import_mask" (measurements; validated when parsed)
-            a.q8_epoch0 = kn.q8_tune[0];
-            a.q8_epoch_mul = kn.q8_tune[1];
-            a.q8_ring_limit = kn.q8_tune[2];
-            a.q8_import_mask = kn.q8_tune[3];
+            a.q8_epoch0 = kn.q8_tune[0], a.q8_epoch_mul = kn.q8_tune[1], a.q8_ring_limit = kn.q8_tune[2], a.q8_import_mask = kn.q8_tune[3];
         }
-        int grid = a.n_items < n_cu * c.wg_per_cu ? a.n_items : n_cu * c.wg_per_cu;
-        const bool sk = codes_layout == ANNLITE_CODES_SKEWED;
+        L.grid = a.n_items < n_cu * c.wg_per_cu ? a.n_items : n_cu * c.wg_per_cu;
         if (c.qf()) {
             // quantise the fp32 tables: min/max -> (step, L, Smax) -> 12-bit codes, all inside the workspace
-            const int64_t bpad = pad_queries(B, plan.qt);
-            char *wp = (char *)workspace_dev + (((int64_t)a.n_tiles * plan.qt * plan.n_slices * k * 8 + 255) / 256) * 256;
-            auto carve = [&](int64_t bytes) { char *r = wp; wp += ((bytes + 255) / 256) * 256; return r; };
             // [gkey][gk2][tile_done] directly behind the partial lists: the one fill covers exactly these four
-            unsigned long long *gk = (unsigned long long *)carve(bpad * 8);
-            // (the byte-table kernel publishes up to kGk2Keys keys per (query, slice) cell whatever M is)
-            unsigned long long *gk2 = (unsigned long long *)carve(bpad * plan.n_slices * 8 * (c.mode == 5 ? kGk2Keys : gk2_cell_keys(M)));
-            unsigned int *tile_done = (unsigned int *)carve((int64_t)a.n_tiles * 4);
-            unsigned int *item_counter = (unsigned int *)carve(4);
-            unsigned int *guard_blk = (unsigned int *)carve(64);  // (reset to all-ones by the fill, like the counters)
-            if (gopt) {
-                if (c.mode == 5) {
-                    a.guard = guard_blk;
-                    a.guard_abort = gopt->abort_enabled;
-                    a.guard_base = 1024u * (uint32_t)((k + 15) / 16);  // (k > 16: the legitimate candidates grow with k -- the transient alone is ~k per query)
-                    if (kn.guard_base >= 0) a.guard_base = (uint32_t)kn.guard_base;  // (ANNLITE_GUARD_BASE, tests: force the give-up path)
-                    a.host_stats = gopt->host_stats;
-                    a.stats_seq = gopt->seq;
-                    gopt->guard_out = guard_blk;
-                } else {
-                    a.gate = gopt->gate;
-                }
+            if (gopt && c.mode == 5) {
+                L.ptr[kP_guard] = lay.off[kRegGuard];
+                L.guarded = true;  // (issue: the guard block's address goes out as the gate of the launch behind this one)
+                a.guard_abort = gopt->abort_enabled;
+                a.guard_base = 1024u * (uint32_t)((k + 15) / 16);  // (k > 16: the legitimate candidates grow with k -- the transient alone is ~k per query)
+                if (kn.guard_base >= 0) a.guard_base = (uint32_t)kn.guard_base;  // (ANNLITE_GUARD_BASE, tests: force the give-up path)
+                if (gopt->host_stats) L.ptr[kP_host_stats] = kPtrCaller;
+            } else if (gopt && gopt->gate) {
+                L.ptr[kP_gate] = kPtrCaller;
             }
             if (tm) {
-                a.tile_rows = tm->tile_rows;
-                a.vmap = tm->vmap;
-                a.item_counter = item_counter;
-                a.cand = tm->cand;
-                a.cand_count = tm->cand_count;
+                L.ptr[kP_tile_rows] = L.ptr[kP_vmap] = L.ptr[kP_cand] = L.ptr[kP_cand_count] = kPtrCaller;
+                L.ptr[kP_item_counter] = lay.off[kRegItemCounter];
                 a.cand_cap = (int32_t)tm->cand_cap;
-                if (outp) outp->merged = true;  // (the tile scan's result is the candidate lists)
+                L.merged = true;  // (the tile scan's result is the candidate lists)
             }
             // (64-key lists: the slices are merged by merge_partial_kernel, not in the scan)
-            if (share_across_slices && outp && (outp->packed || (outp->d && outp->i)) && !(c.mode == 5 && k > 16)) {
-                a.tile_done = tile_done;
-                a.out_d = outp->d;
-                a.out_i = outp->i;
-                a.out_packed = outp->packed;
-                a.row_base = outp->row_base;
-                a.sqrt_out = outp->sqrt_out;
-                outp->merged = true;
+            if (q.share && q.out && (q.out->packed || (q.out->d && q.out->i)) && !(c.mode == 5 && k > 16)) {
+                L.ptr[kP_tile_done] = lay.off[kRegTileDone];
+                if (q.out->d) L.ptr[kP_out_d] = kPtrCaller;
+                if (q.out->i) L.ptr[kP_out_i] = kPtrCaller;
+                if (q.out->packed) L.ptr[kP_out_packed] = kPtrCaller;
+                a.row_base = q.out->row_base;
+                a.sqrt_out = q.out->sqrt_out;
+                L.merged = true;
             }
-            float *smax = (float *)carve(bpad * 4);
-            float *qstep = (float *)carve(bpad * 4);
-            double *qlo = (double *)carve(bpad * 8);
             // per-slice lists stay complete (a superset generator for re-rank) unless sharing is requested
-            a.gkey = share_across_slices ? gk : nullptr;
-            a.gk2 = share_across_slices ? gk2 : nullptr;
-            {
-                const int64_t grp = plan.n_slices < 8 ? plan.n_slices : 8;  // slices scanned concurrently
-                a.jm1 = (int)((k + grp - 1) / grp) - 1;
-                if (c.mode == 5 && k > 16) {
-                    // 64-key lists: a slice publishes the keys at four list positions, ~0.64 / 0.96 / 1.28 / 1.92 of its share k / G of
-                    // the k best rows (8 slices, k = 50: positions 4, 6, 8, 12 -- the weighted bound sits near rank 56; q8_weighted_bound)
-                    const double share = (double)k / (double)grp;
-                    double f[4] = {0.64, 0.96, 1.28, 1.92};
-                    if (kn.q8_pos_ok)  // ANNLITE_Q8_POS = "f0,f1,f2,f3" (measurements)
-                        for (int i = 0; i < 4; ++i) f[i] = kn.q8_pos[i];
-                    int prev = 0;
-                    a.q8_pos = 0;
-                    for (int i = 0; i < 4; ++i) {
-                        int p = (int)ceil(f[i] * share);
-                        if (p <= prev) p = prev + 1;
-                        if (p > 61 + i) p = 61 + i;  // (positions stay inside the 64-key list, strictly ascending)
-                        prev = p;
-                        a.q8_pos |= (uint32_t)(p - 1) << (8 * i);
-                    }
-                    a.jm1 = prev - 1;
+            if (q.share) L.ptr[kP_gkey] = lay.off[kRegGkey], L.ptr[kP_gk2] = lay.off[kRegGk2];
+            const int64_t grp = plan.n_slices < 8 ? plan.n_slices : 8;  // slices scanned concurrently
+            a.jm1 = (int)((k + grp - 1) / grp) - 1;
+            if (c.mode == 5 && k > 16) {
+                // 64-key lists: a slice publishes the keys at four list positions, ~0.64 / 0.96 / 1.28 / 1.92 of its share k / G of
+                // the k best rows (8 slices, k = 50: positions 4, 6, 8, 12 -- the weighted bound sits near rank 56; q8_weighted_bound)
+                const double share = (double)k / (double)grp;
+                double f[4] = {0.64, 0.96, 1.28, 1.92};
+                if (kn.q8_pos_ok)  // ANNLITE_Q8_POS = "f0,f1,f2,f3" (measurements)
+                    for (int i = 0; i < 4; ++i) f[i] = kn.q8_pos[i];
+                int prev = 0;
+                for (int i = 0; i < 4; ++i) {
+                    int p = (int)ceil(f[i] * share);
+                    if (p <= prev) p = prev + 1;
+                    if (p > 61 + i) p = 61 + i;  // (positions stay inside the 64-key list, strictly ascending)
+                    prev = p;
+                    a.q8_pos |= (uint32_t)(p - 1) << (8 * i);
                 }
-                a.flush_mask = 63;
-                if (kn.flush_mask >= 0) a.flush_mask = kn.flush_mask;
+                a.jm1 = prev - 1;
             }
-            // (the q16 table sits behind the small arrays; carve order is irrelevant to the kernels)
-            // byte-table kernel: no u16 tables, the per-(query, sub-space) minima instead (same region, smaller)
-            uint16_t *q16 = c.mode == 5 ? nullptr : (uint16_t *)carve(bpad * M * Ks * 2);
-            float *qlom = c.mode == 5 ? (float *)carve(bpad * M * 4) : nullptr;
+            a.flush_mask = kn.flush_mask >= 0 ? kn.flush_mask : 63;
             // (tile mode with the fused L2 build: the slots' fp32 tables are never read -- do not store them)
-            const int64_t Bq = tm ? tm->n_queries : B;  // tile mode: tables of the real queries only
+            L.Bq = tm ? tm->n_queries : B;  // tile mode: tables of the real queries only
+            const bool build16 = c.mode == 5 && q.build && M == 16 && q.build->D <= 256 && ((q.build->D / M) % 4) == 0 && !kn.no_fused_seed;
             // seed rows of the shared first bound (tile mode seeds inside the scan kernel)
             int64_t S = 0;
             // (round 6) the candidate generator of the re-rank stage through the ONE preparation launch: its slices share nothing while
@@ -959,9 +958,8 @@ static int scan_partial(const void *codes_dev, int code_bytes, int codes_layout,
             // table is at or above the k-th key of the TABLE, so no slice can lose a row of the table's top-k to it; what a slice far
             // from the query loses are rows beyond that bound, of no use to a re-rank.  Saves the per-slice seed launch (8 x 8192 rows
             // against 32768), the separate table build / quantise launches and the work items' own table builds (prebuilt images).
-            const bool cand_prep = cand_seed && !share_across_slices && c.mode == 5 && build && M == 16 && build->D <= 256 &&
-                                   ((build->D / M) % 4) == 0 && !kn.no_fused_seed && !tm && N >= 4096 && k <= 16;
-            if ((share_across_slices || cand_prep) && N >= 4096 && !tm) {
+            const bool cand_prep = q.cand_seed && !q.share && build16 && !tm && N >= 4096 && k <= 16;
+            if ((q.share || cand_prep) && N >= 4096 && !tm) {
                 S = 8192;
                 // byte-table kernel: its candidate transient shrinks with a tighter first bound faster than the seed launch
                 // grows (12 us per 8192 rows): 1.25M rows x 1024 queries 0.425 / 0.407 / 0.405 / 0.437 ms per batch at
@@ -983,30 +981,22 @@ static int scan_partial(const void *codes_dev, int code_bytes, int codes_layout,
             }
             // the S seed rows are 64-row blocks spread evenly over the table (ANNLITE_SEED_CONTIGUOUS=1: its first S rows -- A/B switch)
             const int64_t seed_extent = kn.seed_contiguous ? S : N;
+            L.S = L.S_prep = S;
+            L.seed_extent = seed_extent;
             // with a first bound from rows spread over the whole table the early epoch end only costs its barrier (ms per batch with the
             // first end after step 15 / 255 / never: 1.25M rows 0.2387 / 0.2339 / 0.2338, 1M rows 0.2157 / 0.2099 / 0.2099, 10M rows 1.352 /
             // 1.347 / 1.342 -- profiles/r05/epoch_schedule_sweep.txt): the first end moves to step 255; the early one stays where the
             // scan starts without such a bound
             if (c.mode == 5 && S >= 8192 && seed_extent > S && !kn.q8_tune_set) a.q8_epoch0 = 255;
             // byte-table plan behind annlite_pq_search_topk: tables, parameters, reset and seed bound in ONE launch
-            const bool one_prep = c.mode == 5 && build && S > 0 && M == 16 && build->D <= 256 && ((build->D / M) % 4) == 0 &&
-                                  !kn.no_fused_seed;
-            if (split && !one_prep) return ANNLITE_NOT_APPLICABLE;  // (nothing has been launched)
-            if (one_prep && split && split->phase == ANNLITE_PHASE_SCAN) {
-                // the batch was prepared by the PREPARE half on this workspace: the same carving, no launch
-                if (!kn.no_prebuilt_tables) {
-                    a.gseed0 = (unsigned long long *)carve(bpad * 8);
-                    a.btab = (uint8_t *)carve((int64_t)a.n_tiles * kQ8Image16);
-                }
-            } else if (one_prep) {
-                // ... and the scan work items' FIRST byte tables, once per query tile instead of once per (tile, slice) work item
-                // (ANNLITE_NO_PREBUILT_TABLES: the workgroups convert the fp32 tables themselves, as before round 4 -- A/B switch)
-                unsigned long long *gseed0 = nullptr;
-                uint8_t *btab = nullptr;
-                if (!kn.no_prebuilt_tables) {
-                    gseed0 = (unsigned long long *)carve(bpad * 8);
-                    btab = (uint8_t *)carve((int64_t)a.n_tiles * kQ8Image16);  // (inside the region the u16 plan uses for q16)
-                }
+            const bool one_prep = build16 && S > 0;
+            if (split && !one_prep) return L.rc = ANNLITE_NOT_APPLICABLE, L;  // (nothing has been launched)
+            L.prep = !one_prep ? kPrepQuantise : (split && split->phase == ANNLITE_PHASE_SCAN) ? kPrepDone : kPrepOne;
+            // kPrepDone: the batch was prepared by the PREPARE half on this workspace: the same carving, no launch
+            // ... and the scan work items' FIRST byte tables, once per query tile instead of once per (tile, slice) work item
+            // (ANNLITE_NO_PREBUILT_TABLES: the workgroups convert the fp32 tables themselves, as before round 4 -- A/B switch)
+            if (one_prep && !kn.no_prebuilt_tables) L.ptr[kP_gseed0] = lay.gseed0, L.ptr[kP_btab] = lay.btab;
+            if (L.prep == kPrepOne) {
                 // Round 6, OPT-IN (ANNLITE_MFMA_SEED): the seed rows' exact scan (S x B x M look-up-adds on the VALU: 22 of the launch's
                 // 40 us) replaced by an MFMA launch that NOMINATES kSeedCand rows per query (seed_mfma.hip) and the exact sums of those
                 // nominees here.  Where it applies: 128-d vectors (8-float sub-vectors: one code word = one MFMA operand half), a batch
@@ -1015,156 +1005,172 @@ static int scan_partial(const void *codes_dev, int code_bytes, int codes_layout,
                 // Measured (profiles/r06/mfma_seed_ab.txt): the preparation launch shrinks from 40.3 to 20.6 us, the nomination launch
                 // takes more than that back (its A operand is gathered from a bf16 codebook in LDS -- bank conflicts of random codes --
                 // behind a 6 us prologue that converts the codebooks): not the default.
-                const uint32_t *cand = nullptr;
-                int64_t S_prep = S;
-                {
-                    const int64_t S_m = ((S + 8191) / 8192) * 8192;
-                    const size_t cand_bytes = (size_t)bpad * kSeedCand * 4;
-                    char *ws_end = (char *)workspace_dev + plan.workspace_bytes;
-                    char *cp = (char *)((((uintptr_t)wp + 255) / 256) * 256);
-                    if (kn.mfma_seed && build->D == 128 && B >= 64 && S >= 8192 && S_m <= 131072 && S_m <= N && seed_extent == N &&
-                        code_bytes == 1 && !(split && split->seed_rows > 0) && cp + cand_bytes <= ws_end) {
-                        rc = launch_seed_mfma(codes_layout == ANNLITE_CODES_SKEWED, build->queries, B, build->codebooks, Ks, codes_dev,
-                                              valid_bits_dev, N, S_m, knobs().seed_chunk_log, (uint32_t *)cp, st);
-                        if (rc != ANNLITE_OK) return rc;
-                        cand = (const uint32_t *)cp;
-                        wp = cp + cand_bytes;
-                        S_prep = S_m;
-                    }
+                const int64_t S_m = ((S + 8191) / 8192) * 8192;
+                if (kn.mfma_seed && q.build->D == 128 && B >= 64 && S >= 8192 && S_m <= 131072 && S_m <= N && seed_extent == N && q.code_bytes == 1 &&
+                    !(split && split->seed_rows > 0) && lay.cand + L.p.bpad * kSeedCand * 4 <= plan.workspace_bytes) {
+                    L.mfma = true;
+                    L.S_prep = S_m;
                 }
-                rc = launch_seed_build(codes_layout == ANNLITE_CODES_SKEWED, codes_dev, S_prep, seed_extent, valid_bits_dev, *build, const_cast<float *>(lut_dev),
-                                       B, Ks, k, qstep, qlo, smax, qlom, gk, workspace_dev, fill_bytes, (size_t)(((bpad * 8 + 255) / 256) * 256), st,
-                                       gseed0, btab, a.q8_target, a.dbg ? g_dbg_prep : nullptr, split ? split->seed_keys : nullptr, cand, kSeedCand);
-                if (rc != ANNLITE_OK) return rc;
-                a.gseed0 = gseed0;
-                a.btab = btab;
-                if (split && split->phase == ANNLITE_PHASE_PREPARE) return ANNLITE_OK;  // (the scan follows the seed exchange)
-            } else {
-                const unsigned int *gate = (gopt && c.mode != 5) ? gopt->gate : nullptr;
-                rc = launch_lut_quantise(M, Ks, Bq, ((Bq + 15) / 16) * 16, (tm && build) ? nullptr : lut_dev, build, q16, qstep,
-                                         qlo, smax, qlom, workspace_dev, fill_bytes, st, gate);
-                if (rc != ANNLITE_OK) return rc;
-                if (S > 0) {
-                    rc = launch_seed_bound(M, codes_layout == ANNLITE_CODES_SKEWED, codes_dev, code_bytes, S, valid_bits_dev, lut_dev,
-                                           B, Ks, k, smax, gk, st, seed_extent, 1, 0, 0, gate);
-                    if (rc != ANNLITE_OK) return rc;
-                }
+                if (split && split->phase == ANNLITE_PHASE_PREPARE) return L.stage = kStagePrepare, L;  // (the scan follows the seed exchange)
             }
-            if (!share_across_slices && c.mode == 5 && !tm && N >= 4096 && !(cand_prep && one_prep)) {
+            if (!q.share && c.mode == 5 && !tm && N >= 4096 && !(cand_prep && one_prep)) {
                 // the byte-table kernel as the candidate generator of the re-rank stage: every slice keeps its own complete
                 // list, so every (query, slice) gets its own first bound -- the k-th of the slice's first rows (the gk2 array,
                 // unused without sharing and reset by the fill, holds them).  Without one the slice's table would start "open"
                 // (everything passes until the first epoch end: 15k rows x 32 queries through the consumer wave).
-                int64_t S = a.slice_rows / 64 < 2048 ? 2048 : a.slice_rows / 64 > 8192 ? 8192 : ((a.slice_rows / 64 + 1023) / 1024) * 1024;
-                if (kn.seed_rows_set) S = kn.seed_rows;
-                if (S > a.slice_rows) S = a.slice_rows;
-                if (S > 0) {
-                    rc = launch_seed_bound(M, codes_layout == ANNLITE_CODES_SKEWED, codes_dev, code_bytes, S, valid_bits_dev, lut_dev,
-                                           B, Ks, k, smax, gk2, st, N, plan.n_slices, a.slice_rows, (int64_t)a.n_tiles * plan.qt);
-                    if (rc != ANNLITE_OK) return rc;
-                    a.gseed = gk2;
-                }
+                int64_t S2 = a.slice_rows / 64 < 2048 ? 2048 : a.slice_rows / 64 > 8192 ? 8192 : ((a.slice_rows / 64 + 1023) / 1024) * 1024;
+                if (kn.seed_rows_set) S2 = kn.seed_rows;
+                if (S2 > a.slice_rows) S2 = a.slice_rows;
+                if (S2 > 0) L.S_slice = S2, L.ptr[kP_gseed] = lay.off[kRegGk2];
             }
-            a.smax = smax;
-            a.qstep = qstep;
-            a.qlo = qlo;
-            a.q16 = q16;
-            a.qlom = qlom;
+            // (the q16 table sits behind the small arrays; carve order is irrelevant to the kernels)
+            L.ptr[kP_smax] = lay.off[kRegSmax], L.ptr[kP_qstep] = lay.off[kRegQstep], L.ptr[kP_qlo] = lay.off[kRegQlo];
+            L.ptr[c.mode == 5 ? kP_qlom : kP_q16] = lay.off[kRegBig];
         }
         // early merger (scan_q8.hip: q8_early_merge): every work item must have its own resident workgroup
-        a.q8_early_merge = (c.mode == 5 && a.tile_done && a.n_slices >= 2 && a.n_slices <= 31 && a.n_items <= grid &&
+        a.q8_early_merge = (c.mode == 5 && L.ptr[kP_tile_done] >= 0 && a.n_slices >= 2 && a.n_slices <= 31 && a.n_items <= L.grid &&
                             !kn.no_early_merge) ? 1 : 0;
-        a.q8_merge_patience = 20000u;
-        if (g_prof_on && c.mode == 5 && !(gopt && gopt->gate)) {
+        a.q8_merge_patience = kn.early_merge_patience >= 0 ? (uint32_t)kn.early_merge_patience : 20000u;
+        return L;
+    }
+    if (generic_table_in_lds(M, Ks)) {
+        const size_t tab = (((size_t)M * Ks * 4 + 15) / 16) * 16;
+        const int per_cu = tab > 64 * 1024 ? 1 : 2;
+        L.family = kFamLds, L.lds = tab + (size_t)16 * 64 * 8, L.grid = a.n_items < n_cu * per_cu ? a.n_items : n_cu * per_cu;
+    } else {
+        L.family = kFamGeneric, L.lds = 4 * 64 * 8, L.grid = a.n_items < n_cu * 8 ? a.n_items : n_cu * 8;
+    }
+    return L;
+}
+
+// ANNLITE_DEBUG_COUNTERS: the (leaked) counter buffer, reset in the stream -- and the preparation launch's stamps where asked for
+static int debug_counters_reset(bool prep_stamps, hipStream_t st) {
+    if (!g_dbg) ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg, 8 * (kDbgSplit + 4)));
+    if (prep_stamps && !g_dbg_prep) {
+        ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg_prep, 64));
+        ANNLITE_HIP_TRY(hipMemset(g_dbg_prep, 0, 64));
+    }
+    ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg, 0, 128, st));
+    ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg + kDbgSplit, 0, 32, st));
+    return ANNLITE_OK;
+}
+
+// run the scan kernels as resolved: fills the workspace with the per-(query, slice) sorted key lists [B][NS][k], or -- where the
+// scan can merge its slices itself (out->merged) -- the caller's outputs with the final result
+static int issue(const ScanLaunch &L, const ScanCall &q, hipStream_t st) {
+    if (L.rc != ANNLITE_OK || L.stage == kStageNone) return L.rc;
+    int rc;
+    if (L.dbg && (rc = debug_counters_reset(true, st)) != ANNLITE_OK) return rc;
+    const void *caller[kPtrCount] = {};
+    caller[kP_codes] = q.codes, caller[kP_valid] = q.valid, caller[kP_lut] = q.lut, caller[kP_dbg] = g_dbg;
+    if (q.out) caller[kP_out_d] = q.out->d, caller[kP_out_i] = q.out->i, caller[kP_out_packed] = q.out->packed;
+    if (q.tm) caller[kP_tile_rows] = q.tm->tile_rows, caller[kP_vmap] = q.tm->vmap, caller[kP_cand] = q.tm->cand, caller[kP_cand_count] = q.tm->cand_count;
+    if (q.guard) caller[kP_gate] = q.guard->gate, caller[kP_host_stats] = q.guard->host_stats;
+    void *p[kPtrCount];
+    for (int i = 0; i < kPtrCount; ++i)
+        p[i] = L.ptr[i] >= 0 ? (char *)q.ws + L.ptr[i] : L.ptr[i] == kPtrCaller ? const_cast<void *>(caller[i]) : nullptr;
+    ScanArgs a = L.a;
+#define X(f) a.f = (decltype(a.f))p[kP_##f];
+    ANNLITE_SCAN_PTRS(X)
+#undef X
+    if (L.guarded) a.stats_seq = q.guard->seq, q.guard->guard_out = a.guard;
+    if (L.merged && q.out) q.out->merged = true;
+    if (!L.fused_fill) {
+        const int64_t n16 = (L.fill_bytes + 15) / 16;
+        hipLaunchKernelGGL(fill_ones_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, (u32x4 *)q.ws, n16);
+    }
+    if (L.stage == kStageFill) return ANNLITE_OK;
+    const ScanLayout &lay = L.p.lay;
+    if (L.family == kFamQ8 || L.family == kFamQfilter) {
+        auto at = [&](int region) { return (char *)q.ws + lay.off[region]; };
+        unsigned long long *gk = (unsigned long long *)at(kRegGkey);
+        float *smax = (float *)at(kRegSmax), *qstep = (float *)at(kRegQstep);
+        double *qlo = (double *)at(kRegQlo);
+        if (L.prep == kPrepOne) {
+            uint32_t *cand = L.mfma ? (uint32_t *)((char *)q.ws + lay.cand) : nullptr;
+            if (cand) {
+                rc = launch_seed_mfma(L.skewed, q.build->queries, q.B, q.build->codebooks, q.Ks, q.codes, q.valid, q.N, L.S_prep,
+                                      knobs().seed_chunk_log, cand, st);
+                if (rc != ANNLITE_OK) return rc;
+            }
+            rc = launch_seed_build(L.skewed, q.codes, L.S_prep, L.seed_extent, q.valid, *q.build, const_cast<float *>(q.lut), q.B, q.Ks, q.k, qstep, qlo,
+                                   smax, (float *)((char *)q.ws + lay.qlom), gk, q.ws, (size_t)L.fill_bytes, r256z((size_t)L.p.bpad * 8), st,
+                                   (unsigned long long *)p[kP_gseed0], (uint8_t *)p[kP_btab], a.q8_target, a.dbg ? g_dbg_prep : nullptr,
+                                   q.split ? q.split->seed_keys : nullptr, cand, kSeedCand);
+            if (rc != ANNLITE_OK || L.stage == kStagePrepare) return rc;
+        } else if (L.prep == kPrepQuantise) {
+            rc = launch_lut_quantise(q.M, q.Ks, L.Bq, ((L.Bq + 15) / 16) * 16, (q.tm && q.build) ? nullptr : q.lut, q.build, (uint16_t *)p[kP_q16],
+                                     qstep, qlo, smax, (float *)p[kP_qlom], q.ws, (size_t)L.fill_bytes, st, a.gate);
+            if (rc != ANNLITE_OK) return rc;
+            if (L.S > 0) {
+                rc = launch_seed_bound(q.M, L.skewed, q.codes, q.code_bytes, L.S, q.valid, q.lut, q.B, q.Ks, q.k, smax, gk, st, L.seed_extent, 1,
+                                       0, 0, a.gate);
+                if (rc != ANNLITE_OK) return rc;
+            }
+        }
+        if (L.S_slice > 0) {
+            rc = launch_seed_bound(q.M, L.skewed, q.codes, q.code_bytes, L.S_slice, q.valid, q.lut, q.B, q.Ks, q.k, smax,
+                                   (unsigned long long *)at(kRegGk2), st, q.N, a.n_slices, a.slice_rows, (int64_t)a.n_tiles * L.p.plan.qt);
+            if (rc != ANNLITE_OK) return rc;
+        }
+        const bool bracket = !(q.guard && q.guard->gate);  // (measurement hooks: the launch that does the work, not the gated pass)
+        if (g_prof_on && bracket && L.family == kFamQ8) {
             a.clk = clk_buffer(true);  // (this device's)
-        } else if (g_prof_on && !(gopt && gopt->gate)) {
+        } else if (g_prof_on && bracket) {
             if (unsigned long long *clk = clk_buffer(false))
                 ANNLITE_HIP_TRY(hipMemsetAsync(clk, 0, 32, st));  // (another kernel serves this launch: no stale stamps)
         }
-        if (kn.early_merge_patience >= 0) a.q8_merge_patience = (uint32_t)kn.early_merge_patience;
-        const bool bracket = !(gopt && gopt->gate);  // (measurement hooks: the launch that does the work, not the gated pass)
         if (bracket) prof_begin(st);
-        rc = c.mode == 5 ? launch_q8_scan(c.id, sk, a, grid, st) : launch_qfilter_scan(c.id, sk, a, grid, st);
+        rc = L.family == kFamQ8 ? launch_q8_scan(L.id, L.skewed, a, L.grid, st) : launch_qfilter_scan(L.id, L.skewed, a, L.grid, st);
         if (bracket) prof_end(st);
         return rc;
     }
-    if (generic_table_in_lds(M, Ks)) {
+    const int M = (int)q.M, grid = L.grid;
+    const size_t lds = L.lds;
+    prof_begin(st);
+    if (L.family == kFamLds) {
         constexpr int NW = 16;
-        const size_t tab = (((size_t)M * Ks * 4 + 15) / 16) * 16;
-        const size_t lds_need = tab + (size_t)NW * 64 * 8;
-        const int per_cu = tab > 64 * 1024 ? 1 : 2;
-        const int grid_l = n_items < n_cu * per_cu ? n_items : n_cu * per_cu;
-        const int64_t rb = M * code_bytes;
-        const bool al16 = rb % 16 == 0 && ((uintptr_t)codes_dev % 16) == 0, al4 = rb % 4 == 0 && ((uintptr_t)codes_dev % 4) == 0;
-        prof_begin(st);
+        const int64_t rb = q.M * q.code_bytes;
+        const bool al16 = rb % 16 == 0 && ((uintptr_t)q.codes % 16) == 0, al4 = rb % 4 == 0 && ((uintptr_t)q.codes % 4) == 0;
 #define ANNLITE_LDS_SCAN(T)                                                                                                       \
     {                                                                                                                             \
         auto fn = al16 ? adc_scan_lds_kernel<T, NW, 16> : al4 ? adc_scan_lds_kernel<T, NW, 4> : adc_scan_lds_kernel<T, NW, (int)sizeof(T)>; \
-        ANNLITE_HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_need));       \
-        hipLaunchKernelGGL(fn, dim3(grid_l), dim3(NW * 64), lds_need, st, a, (int)M);                                             \
+        ANNLITE_HIP_TRY(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(NW * 64), lds, st, a, M);                                                         \
     }
-        if (code_bytes == 1) ANNLITE_LDS_SCAN(uint8_t)
-        else if (code_bytes == 2) ANNLITE_LDS_SCAN(uint16_t)
-        else ANNLITE_LDS_SCAN(uint32_t)
+        ANNLITE_BY_CODE_BYTES(q.code_bytes, ANNLITE_LDS_SCAN(T))
 #undef ANNLITE_LDS_SCAN
-        prof_end(st);
-        return launch_status("adc_scan_lds_kernel");
+    } else {
+        ANNLITE_BY_CODE_BYTES(q.code_bytes, hipLaunchKernelGGL((adc_scan_generic_kernel<T, 4>), dim3(grid), dim3(256), lds, st, a, M))
     }
-    const int grid = n_items < n_cu * 8 ? n_items : n_cu * 8;
-    const size_t lds = 4 * 64 * 8;
-    prof_begin(st);
-    if (code_bytes == 1)
-        hipLaunchKernelGGL((adc_scan_generic_kernel<uint8_t, 4>), dim3(grid), dim3(256), lds, st, a, (int)M);
-    else if (code_bytes == 2)
-        hipLaunchKernelGGL((adc_scan_generic_kernel<uint16_t, 4>), dim3(grid), dim3(256), lds, st, a, (int)M);
-    else
-        hipLaunchKernelGGL((adc_scan_generic_kernel<uint32_t, 4>), dim3(grid), dim3(256), lds, st, a, (int)M);
     prof_end(st);
-    return launch_status("adc_scan_generic_kernel");
+    return launch_status(L.family == kFamLds ? "adc_scan_lds_kernel" : "adc_scan_generic_kernel");
 }
 
-extern "C" int annlite_debug_counters(uint64_t *out8) {
-    ANNLITE_REQUIRE(out8 != nullptr, "out8 is NULL");
-    if (!g_dbg) {
+static int scan_partial(const ScanCall &q, ScanVariant variant, hipStream_t st, annlite_scan_plan *plan_out) {
+    const ScanLaunch L = resolve(q, variant, knobs(), device_cu_count());
+    *plan_out = L.p.plan;
+    return issue(L, q, st);
+}
+
+// the debug getters: wait for the device, copy `bytes` from word `first` of a debug buffer
+static int debug_read(uint64_t *out, const unsigned long long *buf, int first, size_t bytes) {
+    ANNLITE_REQUIRE(out != nullptr, "out is NULL");
+    if (!buf) {
         set_error("no counters recorded (set ANNLITE_DEBUG_COUNTERS=1 before the scan)");
         return ANNLITE_ERR_INVALID;
     }
     ANNLITE_HIP_TRY(hipDeviceSynchronize());
-    ANNLITE_HIP_TRY(hipMemcpy(out8, g_dbg, 64, hipMemcpyDeviceToHost));
+    ANNLITE_HIP_TRY(hipMemcpy(out, buf + first, bytes, hipMemcpyDeviceToHost));
     return ANNLITE_OK;
 }
-
-extern "C" int annlite_debug_split_counters(uint64_t *out4) {
-    ANNLITE_REQUIRE(out4 != nullptr, "out4 is NULL");
-    if (!g_dbg) {
-        set_error("no counters recorded (set ANNLITE_DEBUG_COUNTERS=1 before the scan)");
-        return ANNLITE_ERR_INVALID;
-    }
-    ANNLITE_HIP_TRY(hipDeviceSynchronize());
-    ANNLITE_HIP_TRY(hipMemcpy(out4, g_dbg + kDbgSplit, 32, hipMemcpyDeviceToHost));
-    return ANNLITE_OK;
-}
-
-extern "C" int annlite_debug_timeline(uint64_t *out8) {
-    ANNLITE_REQUIRE(out8 != nullptr, "out8 is NULL");
-    if (!g_dbg) {
-        set_error("no counters recorded (set ANNLITE_DEBUG_COUNTERS=1 before the scan)");
-        return ANNLITE_ERR_INVALID;
-    }
-    ANNLITE_HIP_TRY(hipDeviceSynchronize());
-    ANNLITE_HIP_TRY(hipMemcpy(out8, g_dbg + 8, 64, hipMemcpyDeviceToHost));
-    return ANNLITE_OK;
-}
-
+extern "C" int annlite_debug_counters(uint64_t *out8) { return debug_read(out8, g_dbg, 0, 64); }
+extern "C" int annlite_debug_split_counters(uint64_t *out4) { return debug_read(out4, g_dbg, kDbgSplit, 32); }
+extern "C" int annlite_debug_timeline(uint64_t *out8) { return debug_read(out8, g_dbg, 8, 64); }
 extern "C" int annlite_debug_prep_timeline(uint64_t *out8) {
-    ANNLITE_REQUIRE(out8 != nullptr, "out8 is NULL");
-    if (!g_dbg_prep) {
-        set_error("no stamps recorded (set ANNLITE_DEBUG_COUNTERS before a search through annlite_pq_search_topk)");
-        return ANNLITE_ERR_INVALID;
-    }
-    ANNLITE_HIP_TRY(hipDeviceSynchronize());
-    ANNLITE_HIP_TRY(hipMemcpy(out8, g_dbg_prep, 64, hipMemcpyDeviceToHost));
-    return ANNLITE_OK;
+    if (g_dbg_prep || !out8) return debug_read(out8, g_dbg_prep, 0, 64);
+    set_error("no stamps recorded (set ANNLITE_DEBUG_COUNTERS before a search through annlite_pq_search_topk)");
+    return ANNLITE_ERR_INVALID;
 }
 
 extern "C" int annlite_debug_seed_candidates(const float *queries_dev, int64_t B, int64_t D, const float *codebooks_dev,
@@ -1176,6 +1182,33 @@ extern "C" int annlite_debug_seed_candidates(const float *queries_dev, int64_t B
         return ANNLITE_NOT_APPLICABLE;
     return launch_seed_mfma(codes_layout == ANNLITE_CODES_SKEWED, queries_dev, B, codebooks_dev, Ks, codes_dev, valid_bits_dev, N, seed_rows,
                             knobs().seed_chunk_log, cand_dev, (hipStream_t)stream);
+}
+
+// resolve() on a shape and option flags alone (include/annlite_hip.h documents the record): no GPU needed
+extern "C" int annlite_debug_scan_resolve(int64_t N, int64_t M, int64_t Ks, int code_bytes, int codes_layout, int64_t B, int64_t k, int variant,
+                                          int flags, int64_t D, int64_t V, int split_phase, int64_t seed_rows, int64_t *out, int64_t n_out) {
+    ANNLITE_REQUIRE(out != nullptr && n_out >= ANNLITE_SCAN_RESOLVE_FIELDS, "out needs room for %d values", ANNLITE_SCAN_RESOLVE_FIELDS);
+    ANNLITE_REQUIRE(variant == kVariantEnv || variant == kVariantU16 || variant == kVariantByte, "variant must be -1, 31 or 50");
+    void *const some = (void *)(uintptr_t)256;  // (stands for the caller's buffers: resolve() only asks whether they are there)
+    const LutBuild lb = {(const float *)some, (const float *)some, D};
+    ScanOut so = {(flags & 128) ? nullptr : (float *)some, (flags & 128) ? nullptr : (int64_t *)some, (flags & 128) ? (int64_t *)some : nullptr, 0, 0, false};
+    const TileMode tm = {(const int64_t *)some, (const int32_t *)some, (uint32_t *)some, (uint32_t *)some, 256, V};
+    GuardOpt g = {(flags & 8) ? 1 : 0, (flags & 32) ? (unsigned int *)some : nullptr, 0, (flags & 16) ? (const unsigned int *)some : nullptr, nullptr};
+    const SplitOpt sp = {split_phase, seed_rows, (unsigned long long *)some};
+    const ScanCall q = {some, code_bytes, codes_layout, N, M, Ks, (flags & 512) ? (const uint32_t *)some : nullptr, (const float *)some, B, k, some,
+                        ~(size_t)0 >> 1, (flags & 1) != 0, (flags & 2) ? &lb : nullptr, (flags & 256) ? nullptr : &so,
+                        (flags & 4) ? &tm : nullptr, (flags & (8 | 16 | 32)) ? &g : nullptr, split_phase ? &sp : nullptr, (flags & 64) != 0};
+    const ScanLaunch L = resolve(q, (ScanVariant)variant, knobs(), device_cu_count());
+    const int64_t head[] = {L.rc, L.stage, L.family, L.id, L.grid, L.skewed, L.fused_fill, L.fill_bytes, L.prep, L.mfma, L.S, L.S_prep, L.seed_extent,
+                            L.S_slice, L.merged, L.p.plan.workspace_bytes, L.p.plan.n_slices, (int64_t)L.lds};
+    int64_t *o = out;
+    for (int64_t h : head) *o++ = h;
+#define X(f) *o++ = (int64_t)L.a.f;
+    ANNLITE_SCAN_SCALARS(X)
+#undef X
+    for (int64_t p : L.ptr) *o++ = p;
+    static_assert(sizeof(head) / 8 + 29 + kPtrCount == ANNLITE_SCAN_RESOLVE_FIELDS, "annlite_hip.h: ANNLITE_SCAN_RESOLVE_FIELDS");
+    return L.rc;
 }
 
 extern "C" int annlite_debug_items(uint64_t *out, int64_t max_items, int64_t *n_items) {
@@ -1287,12 +1320,12 @@ struct annlite_scan_state {
 enum SearchMode { kModePlain, kModeGuarded, kModeByteStats, kModeU16, kModeU16Probe };
 
 static SearchMode search_policy(annlite_scan_state *s, int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t B, int64_t k,
-                                bool tiles) {
+                                bool tiles, ScanVariant variant) {
     // the shapes with both a byte-table and a u16-table kernel: M = 8 / 16 / 32 with u8 codes, M = 8 / u16 codes up to Ks = 1024
     const bool both = ((M == 16 || M == 8 || M == 32) && code_bytes == 1 && Ks <= 256) || (M == 8 && code_bytes == 2 && Ks <= 1024);
     // (k > 16: the byte-table kernel with 64-key lists exists for M = 16 / uint8 codes; it needs a table worth seeding)
     if (tiles || !both || (k > 16 && !(lk64_shape(M, Ks, code_bytes, k) && N >= 65536)) || N <= 0 || B <= 0) return kModePlain;
-    if (g_variant_scope >= 0 || env_variant() >= 0) return kModePlain;        // (an explicit variant: A/B measurements)
+    if (!variant_free(variant, knobs())) return kModePlain;          // (an explicit variant: A/B measurements, the library's own passes)
     if (knobs().no_inkernel_merge) return kModePlain;                // (debug switch: no guarded pass)
     if (!s) return kModeGuarded;
     const uint32_t seq = __atomic_load_n(s->host, __ATOMIC_ACQUIRE);
@@ -1391,22 +1424,38 @@ extern "C" int annlite_scan_state_info(annlite_scan_state *s, int32_t *kernel, i
     return ANNLITE_OK;
 }
 
+// the slices' lists [B][n_slices][k] at the front of the workspace -> the final result
+static int launch_merge_partial(const void *lists, int64_t B, int n_slices, int64_t k, int64_t row_base, float *out_d, int64_t *out_i,
+                                int64_t *out_packed, int sqrt_out, hipStream_t st) {
+    hipLaunchKernelGGL(merge_partial_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, (const unsigned long long *)lists, (int)B,
+                       n_slices, (int)k, row_base, out_d, out_i, out_packed, sqrt_out);
+    return launch_status("merge_partial_kernel");
+}
+// ... -> every slice's list as it is (the candidate generators)
+static int launch_export_partial(const void *lists, int64_t total, int64_t row_base, float *out_d, int64_t *out_i, hipStream_t st) {
+    hipLaunchKernelGGL(export_partial_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const unsigned long long *)lists, total,
+                       row_base, out_d, out_i);
+    return launch_status("export_partial_kernel");
+}
+
+// variant: kVariantEnv from the entries; kVariantU16 from this function itself, for the scan it has decided to run on u16 tables
 static int scan_topk_impl(const void *codes_dev, int code_bytes, int codes_layout, int64_t N, int64_t M, int64_t Ks,
                           const uint32_t *valid_bits_dev, const float *lut_dev, int64_t B, int64_t k, int64_t row_base,
                           float *out_dist_dev, int64_t *out_id_dev, int64_t *out_packed_dev, void *workspace_dev,
                           size_t workspace_bytes, void *stream, const LutBuild *build = nullptr, int flags = 0,
-                          const TileMode *tm = nullptr, annlite_scan_state *state = nullptr) {
+                          const TileMode *tm = nullptr, annlite_scan_state *state = nullptr, ScanVariant variant = kVariantEnv) {
     annlite_scan_plan plan;
     hipStream_t st = (hipStream_t)stream;
     ANNLITE_REQUIRE(B == 0 || tm || out_packed_dev || (out_dist_dev && out_id_dev), "null output pointer");
     const int sqrt_out = (flags & ANNLITE_FLAG_SQRT) && !out_packed_dev ? 1 : 0;
     ScanOut so = {out_dist_dev, out_id_dev, out_packed_dev, row_base, sqrt_out, false};
     if (knobs().no_inkernel_merge && !tm) so.d = nullptr, so.i = nullptr, so.packed = nullptr;
-    const SearchMode mode = search_policy(state, N, M, Ks, code_bytes, B, k, tm != nullptr);
+    ScanCall sc = {codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut_dev, B, k, workspace_dev, workspace_bytes, true, build, &so, tm};
+    const SearchMode mode = search_policy(state, N, M, Ks, code_bytes, B, k, tm != nullptr, variant);
     if (mode != kModePlain) {
         // (workspace: the public plan's size = byte-table region + u16 region; each pass checks its own)
         annlite_scan_plan pub;
-        int rc0 = plan_query_impl(N, M, Ks, code_bytes, B, k, 0, &pub);
+        int rc0 = plan_query_impl(N, M, Ks, code_bytes, B, k, false, &pub);
         if (rc0 != ANNLITE_OK) return rc0;
         if (workspace_bytes < (size_t)pub.workspace_bytes) {
             set_error("workspace %zu B < required %lld B", workspace_bytes, (long long)pub.workspace_bytes);
@@ -1414,11 +1463,10 @@ static int scan_topk_impl(const void *codes_dev, int code_bytes, int codes_layou
         }
         const double work = (double)((B + 31) / 32) * (double)N;
         if (mode == kModeU16 || mode == kModeU16Probe) {
-            VariantScope vs(31);
             const bool timed = mode == kModeU16Probe;
             if (timed) ANNLITE_HIP_TRY(hipEventRecord(state->ev[1][0], st));
             const int rc = scan_topk_impl(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut_dev, B, k, row_base, out_dist_dev,
-                                          out_id_dev, out_packed_dev, workspace_dev, workspace_bytes, stream, build, flags, tm, nullptr);
+                                          out_id_dev, out_packed_dev, workspace_dev, workspace_bytes, stream, build, flags, tm, nullptr, kVariantU16);
             if (timed && rc == ANNLITE_OK) {
                 ANNLITE_HIP_TRY(hipEventRecord(state->ev[1][1], st));
                 state->work[1] = work;
@@ -1434,33 +1482,26 @@ static int scan_topk_impl(const void *codes_dev, int code_bytes, int codes_layou
             g.host_stats = state->dev;
             g.seq = ++state->seq ? state->seq : ++state->seq;  // (0 means "nothing completed yet")
         }
-        int rc;
-        size_t used;
-        {
-            VariantScope vs(50);
-            annlite_scan_plan p1;
-            rc = scan_partial(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut_dev, B, k, workspace_dev,
-                              workspace_bytes, st, &p1, true, build, &so, nullptr, &g);
-            if (rc != ANNLITE_OK || B == 0) return rc;
-            if (!so.merged) {  // 16 < k <= 64: the 64-key lists of the slices, merged here (a launch that gave up leaves garbage: the
-                               // gated pass below overwrites it)
-                ANNLITE_REQUIRE(k > 16, "the byte-table launch did not merge in-kernel");
-                hipLaunchKernelGGL(merge_partial_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, (const unsigned long long *)workspace_dev,
-                                   (int)B, p1.n_slices, (int)k, row_base, out_dist_dev, out_id_dev, out_packed_dev, sqrt_out);
-                rc = launch_status("merge_partial_kernel");
-                if (rc != ANNLITE_OK) return rc;
-            }
-            used = ((size_t)p1.workspace_bytes + 255) / 256 * 256;
+        annlite_scan_plan p1;
+        sc.guard = &g;
+        int rc = scan_partial(sc, kVariantByte, st, &p1);
+        if (rc != ANNLITE_OK || B == 0) return rc;
+        if (!so.merged) {  // 16 < k <= 64: the 64-key lists of the slices, merged here (a launch that gave up leaves garbage: the
+                           // gated pass below overwrites it)
+            ANNLITE_REQUIRE(k > 16, "the byte-table launch did not merge in-kernel");
+            rc = launch_merge_partial(workspace_dev, B, p1.n_slices, k, row_base, out_dist_dev, out_id_dev, out_packed_dev, sqrt_out, st);
+            if (rc != ANNLITE_OK) return rc;
         }
+        const size_t used = r256z((size_t)p1.workspace_bytes);
         if (mode == kModeGuarded && g.guard_out) {
             // the same scan through the u16-table kernel, every launch of it gated on the byte-table launch having given up
-            VariantScope vs(31);
             annlite_scan_plan p2;
             GuardOpt g2 = {};
             g2.gate = g.guard_out;
             ScanOut so2 = {out_dist_dev, out_id_dev, out_packed_dev, row_base, sqrt_out, false};
-            rc = scan_partial(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut_dev, B, k, (char *)workspace_dev + used,
-                              workspace_bytes - used, st, &p2, true, nullptr, &so2, nullptr, &g2);
+            ScanCall sc2 = sc;
+            sc2.ws = (char *)workspace_dev + used, sc2.ws_bytes = workspace_bytes - used, sc2.build = nullptr, sc2.out = &so2, sc2.guard = &g2;
+            rc = scan_partial(sc2, kVariantU16, st, &p2);
             if (rc != ANNLITE_OK) return rc;
             ANNLITE_REQUIRE(so2.merged, "the gated u16-table launch did not merge in-kernel");
         }
@@ -1471,14 +1512,10 @@ static int scan_topk_impl(const void *codes_dev, int code_bytes, int codes_layou
         }
         return ANNLITE_OK;
     }
-    int rc = scan_partial(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut_dev, B, k, workspace_dev,
-                          workspace_bytes, st, &plan, true, build, &so, tm);
+    int rc = scan_partial(sc, variant, st, &plan);
     if (rc != ANNLITE_OK || B == 0 || so.merged) return rc;
     ANNLITE_REQUIRE(!tm, "tile mode: the scan did not merge in-kernel");
-    hipLaunchKernelGGL(merge_partial_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st,
-                       (const unsigned long long *)workspace_dev, (int)B, plan.n_slices, (int)k, row_base,
-                       out_dist_dev, out_id_dev, out_packed_dev, sqrt_out);
-    return launch_status("merge_partial_kernel");
+    return launch_merge_partial(workspace_dev, B, plan.n_slices, k, row_base, out_dist_dev, out_id_dev, out_packed_dev, sqrt_out, st);
 }
 
 extern "C" int annlite_adc_scan_topk(const void *codes_dev, int code_bytes, int codes_layout, int64_t N, int64_t M,
@@ -1498,16 +1535,39 @@ extern "C" int annlite_adc_scan_topk_packed(const void *codes_dev, int code_byte
                           nullptr, out_packed_dev, workspace_dev, workspace_bytes, stream);
 }
 
-static size_t r256z(size_t x) { return (x + 255) / 256 * 256; }
-
-extern "C" int annlite_pq_search_workspace_bytes(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t B, int64_t k,
-                                                 int64_t *bytes) {
+// the workspace of the searches that build their tables: [scan region(s) of the plan][fp32 tables] (annlite_pq_search_workspace_bytes)
+struct SearchWs {
+    annlite_scan_plan plan;
+    size_t scan_ws;
+    float *lut;
+};
+static int search_ws_bytes(const ScanShape &s, int64_t *bytes) {
     ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
     annlite_scan_plan plan;
-    int rc = annlite_scan_plan_query(N, M, Ks, code_bytes, B, k, &plan);
-    if (rc != ANNLITE_OK) return rc;
-    *bytes = (int64_t)(r256z((size_t)plan.workspace_bytes) + r256z((size_t)plan.lut_floats * 4));
+    int rc = plan_query_impl(s.N, s.M, s.Ks, s.code_bytes, s.B, s.k, s.tiles, &plan);
+    if (rc == ANNLITE_OK) *bytes = (int64_t)(r256z((size_t)plan.workspace_bytes) + r256z((size_t)plan.lut_floats * 4));
+    return rc;
+}
+// empty (no queries): the plan's argument checks only
+static int search_ws(const ScanShape &s, ScanVariant variant, bool empty, void *workspace_dev, size_t workspace_bytes, SearchWs *w) {
+    int rc = plan_query_impl(s.N, s.M, s.Ks, s.code_bytes, s.B, s.k, s.tiles, &w->plan, variant);
+    if (rc != ANNLITE_OK || empty) return rc;
+    w->scan_ws = r256z((size_t)w->plan.workspace_bytes);
+    const size_t need = w->scan_ws + r256z((size_t)w->plan.lut_floats * 4);
+    if (workspace_bytes < need) {
+        set_error("workspace %zu B < required %zu B (annlite_pq_search_workspace_bytes)", workspace_bytes, need);
+        return ANNLITE_ERR_WORKSPACE;
+    }
+    w->lut = (float *)((char *)workspace_dev + w->scan_ws);
     return ANNLITE_OK;
+}
+// the L2 tables are built by the scan's own preparation (LutBuild): a filter plan other than M = 64, sub-vectors of a multiple of 4 floats
+static bool fused_tables(const annlite_scan_plan &plan, int lut_kind, int64_t N, int64_t M, int64_t Ks, int64_t D) {
+    return N > 0 && plan.fast && M != 64 && Ks <= 256 && lut_kind == ANNLITE_LUT_L2 && ((D / M) % 4) == 0 && !knobs().no_fused_lut;
+}
+
+extern "C" int annlite_pq_search_workspace_bytes(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t B, int64_t k, int64_t *bytes) {
+    return search_ws_bytes({N, M, Ks, code_bytes, B, k, false}, bytes);
 }
 
 static int pq_search_impl(int lut_kind, const float *queries_dev, int64_t B, int64_t D, const float *codebooks_dev,
@@ -1520,32 +1580,21 @@ static int pq_search_impl(int lut_kind, const float *queries_dev, int64_t B, int
                     "input dimension must be dividable by number of sub-space (D=%lld, M=%lld)", (long long)D, (long long)M);
     // tile mode: B real queries (tables), n_slots >= B scan slots (lists, bounds)
     const int64_t Bs = tm ? n_slots : B;
-    annlite_scan_plan plan;
-    int rc = plan_query_impl(N, M, Ks, code_bytes, Bs, k, tm ? 1 : 0, &plan);
-    if (rc != ANNLITE_OK) return rc;
-    if (Bs == 0 || B == 0) return ANNLITE_OK;
-    const size_t scan_ws = r256z((size_t)plan.workspace_bytes);
-    const size_t need = scan_ws + r256z((size_t)plan.lut_floats * 4);
-    if (workspace_bytes < need) {
-        set_error("workspace %zu B < required %zu B (annlite_pq_search_workspace_bytes)", workspace_bytes, need);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    const bool empty = Bs == 0 || B == 0;
+    SearchWs w;
+    int rc = search_ws({N, M, Ks, code_bytes, Bs, k, tm != nullptr}, kVariantEnv, empty, workspace_dev, workspace_bytes, &w);
+    if (rc != ANNLITE_OK || empty) return rc;
     ANNLITE_REQUIRE(queries_dev && codebooks_dev && workspace_dev, "null device pointer");
     ANNLITE_REQUIRE(!tm || B <= Bs, "tile mode: more queries (%lld) than slots (%lld)", (long long)B, (long long)Bs);
-    float *lut = (float *)((char *)workspace_dev + scan_ws);
-    FastCfg c;
-    const bool fuse = N > 0 && plan.fast && fast_cfg(M, Ks, code_bytes, k, &c, tm != nullptr) && c.qf() && M != 64 && Ks <= 256 &&
-                      lut_kind == ANNLITE_LUT_L2 && ((D / M) % 4) == 0 && !knobs().no_fused_lut;
+    const bool fuse = fused_tables(w.plan, lut_kind, N, M, Ks, D);
     if (!fuse) {
-        rc = annlite_lut_build(lut_kind, queries_dev, B, D, codebooks_dev, M, Ks, lut,
-                               plan.fast ? ANNLITE_LAYOUT_TILED : ANNLITE_LAYOUT_BMK, plan.qi, stream);
+        rc = annlite_lut_build(lut_kind, queries_dev, B, D, codebooks_dev, M, Ks, w.lut, w.plan.fast ? ANNLITE_LAYOUT_TILED : ANNLITE_LAYOUT_BMK,
+                               w.plan.qi, stream);
         if (rc != ANNLITE_OK) return rc;
-        return scan_topk_impl(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut, Bs, k, row_base,
-                              out_dist_dev, out_id_dev, out_packed_dev, workspace_dev, scan_ws, stream, nullptr, flags, tm, state);
     }
     const LutBuild lb = {queries_dev, codebooks_dev, D};
-    return scan_topk_impl(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut, Bs, k, row_base, out_dist_dev,
-                          out_id_dev, out_packed_dev, workspace_dev, scan_ws, stream, &lb, flags, tm, state);
+    return scan_topk_impl(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, w.lut, Bs, k, row_base, out_dist_dev, out_id_dev,
+                          out_packed_dev, workspace_dev, w.scan_ws, stream, fuse ? &lb : nullptr, flags, tm, state);
 }
 
 extern "C" int annlite_pq_search_topk_ex(int lut_kind, const float *queries_dev, int64_t B, int64_t D,
@@ -1564,16 +1613,15 @@ extern "C" int annlite_pq_search_topk(int lut_kind, const float *queries_dev, in
                                       int64_t N, int64_t M, int64_t Ks, const uint32_t *valid_bits_dev, int64_t k,
                                       int64_t row_base, float *out_dist_dev, int64_t *out_id_dev, int64_t *out_packed_dev,
                                       int flags, void *workspace_dev, size_t workspace_bytes, void *stream) {
-    return pq_search_impl(lut_kind, queries_dev, B, D, codebooks_dev, codes_dev, code_bytes, codes_layout, N, M, Ks,
-                          valid_bits_dev, k, row_base, out_dist_dev, out_id_dev, out_packed_dev, flags, workspace_dev,
-                          workspace_bytes, stream, nullptr);
+    return annlite_pq_search_topk_ex(lut_kind, queries_dev, B, D, codebooks_dev, codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, k,
+                                     row_base, out_dist_dev, out_id_dev, out_packed_dev, flags, workspace_dev, workspace_bytes, stream, nullptr);
 }
 
 // ---- the search in two halves with the ranks' seed exchange in between (annlite_hip.h: annlite_pq_search_split) ----------------
 static bool split_shape_ok(int lut_kind, int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t B, int64_t D, int64_t k) {
     return lut_kind == ANNLITE_LUT_L2 && M == 16 && code_bytes == 1 && Ks <= 256 && k >= 1 && k <= 16 && B >= 1 && N >= 4096 &&
            D <= 256 && D % M == 0 && ((D / M) % 4) == 0 && !knobs().no_fused_seed && !knobs().no_fused_lut &&
-           !knobs().no_inkernel_merge && env_variant() < 0;
+           !knobs().no_inkernel_merge && knobs().scan_variant < 0;
 }
 
 extern "C" int annlite_pq_search_split(int phase, int64_t seed_rows, int lut_kind, const float *queries_dev, int64_t B, int64_t D,
@@ -1588,22 +1636,14 @@ extern "C" int annlite_pq_search_split(int phase, int64_t seed_rows, int lut_kin
     if (phase == ANNLITE_PHASE_PREPARE) {
         ANNLITE_REQUIRE(seed_keys_dev != nullptr, "seed_keys_dev is NULL");
         // only once the library has settled on the byte-table kernel for this table (no guarded second pass to split)
-        if (search_policy(state, N, M, Ks, code_bytes, B, k, false) != kModeByteStats) return ANNLITE_NOT_APPLICABLE;
+        if (search_policy(state, N, M, Ks, code_bytes, B, k, false, kVariantEnv) != kModeByteStats) return ANNLITE_NOT_APPLICABLE;
     } else {
         ANNLITE_REQUIRE(out_packed_dev || (out_dist_dev && out_id_dev), "null output pointer");
     }
-    VariantScope vs(50);
-    annlite_scan_plan plan;
-    int rc = plan_query_impl(N, M, Ks, code_bytes, B, k, 0, &plan);
+    SearchWs w;
+    int rc = search_ws({N, M, Ks, code_bytes, B, k, false}, kVariantByte, false, workspace_dev, workspace_bytes, &w);
     if (rc != ANNLITE_OK) return rc;
-    const size_t scan_ws = r256z((size_t)plan.workspace_bytes);
-    const size_t need = scan_ws + r256z((size_t)plan.lut_floats * 4);
-    if (workspace_bytes < need) {
-        set_error("workspace %zu B < required %zu B (annlite_pq_search_workspace_bytes)", workspace_bytes, need);
-        return ANNLITE_ERR_WORKSPACE;
-    }
     ANNLITE_REQUIRE(queries_dev && codebooks_dev && workspace_dev && codes_dev, "null device pointer");
-    float *lut = (float *)((char *)workspace_dev + scan_ws);
     const LutBuild lb = {queries_dev, codebooks_dev, D};
     const int sqrt_out = (flags & ANNLITE_FLAG_SQRT) && !out_packed_dev ? 1 : 0;
     ScanOut so = {out_dist_dev, out_id_dev, out_packed_dev, row_base, sqrt_out, false};
@@ -1614,8 +1654,8 @@ extern "C" int annlite_pq_search_split(int phase, int64_t seed_rows, int lut_kin
     if (phase == ANNLITE_PHASE_SCAN) g.seq = ++state->seq ? state->seq : ++state->seq;
     const SplitOpt sp = {phase, seed_rows, (unsigned long long *)seed_keys_dev};
     annlite_scan_plan p1;
-    rc = scan_partial(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut, B, k, workspace_dev, scan_ws,
-                      (hipStream_t)stream, &p1, true, &lb, &so, nullptr, &g, &sp);
+    const ScanCall sc = {codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, w.lut, B, k, workspace_dev, w.scan_ws, true, &lb, &so, nullptr, &g, &sp};
+    rc = scan_partial(sc, kVariantByte, (hipStream_t)stream, &p1);
     if (rc != ANNLITE_OK) return rc;
     if (phase == ANNLITE_PHASE_SCAN) ANNLITE_REQUIRE(so.merged, "the byte-table launch did not merge in-kernel");
     return ANNLITE_OK;
@@ -1627,29 +1667,20 @@ extern "C" int annlite_pq_search_seed_union(const uint64_t *all_keys_dev, int64_
     ANNLITE_REQUIRE(all_keys_dev && workspace_dev, "null device pointer");
     ANNLITE_REQUIRE(G >= 1 && G <= 8, "G=%lld outside [1, 8] (one node)", (long long)G);
     ANNLITE_REQUIRE(k >= 1 && k <= kSeedKeys && B >= 1, "bad B=%lld k=%lld", (long long)B, (long long)k);
-    VariantScope vs(50);
-    annlite_scan_plan plan;
-    int rc = plan_query_impl(N, M, Ks, code_bytes, B, k, 0, &plan);
+    ScanPlanned p;
+    int rc = plan_scan({N, M, Ks, code_bytes, B, k, false}, kVariantByte, knobs(), device_cu_count(), &p);
     if (rc != ANNLITE_OK) return rc;
-    ANNLITE_REQUIRE(plan.fast && plan.qt == 32, "no byte-table plan for this shape");
-    // the shared bounds sit right behind the per-(query, slice) lists (scan_partial's carving)
-    const int64_t n_tiles = (B + plan.qt - 1) / plan.qt;
-    const size_t off = r256z((size_t)n_tiles * plan.qt * plan.n_slices * k * 8);
-    ANNLITE_REQUIRE(off + (size_t)pad_queries(B, plan.qt) * 8 <= workspace_bytes, "workspace too small");
+    ANNLITE_REQUIRE(p.fast && p.plan.qt == 32, "no byte-table plan for this shape");
+    const size_t off = (size_t)p.lay.off[kRegGkey];  // the shared bounds (scan_layout)
+    ANNLITE_REQUIRE(off + (size_t)p.bpad * 8 <= workspace_bytes, "workspace too small");
     unsigned long long *gk = (unsigned long long *)((char *)workspace_dev + off);
     hipLaunchKernelGGL(seed_union_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned long long *)all_keys_dev, (int)G, (int)B, (int)k, gk);
     return launch_status("seed_union_kernel");
 }
 
-extern "C" int annlite_pq_search_tiles_workspace_bytes(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t V,
-                                                       int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    annlite_scan_plan plan;
-    int rc = plan_query_impl(N, M, Ks, code_bytes, V, k, 1, &plan);
-    if (rc != ANNLITE_OK) return rc;
-    *bytes = (int64_t)(r256z((size_t)plan.workspace_bytes) + r256z((size_t)plan.lut_floats * 4));
-    return ANNLITE_OK;
+extern "C" int annlite_pq_search_tiles_workspace_bytes(int64_t N, int64_t M, int64_t Ks, int code_bytes, int64_t V, int64_t k, int64_t *bytes) {
+    return search_ws_bytes({N, M, Ks, code_bytes, V, k, true}, bytes);
 }
 
 extern "C" int annlite_pq_search_tiles(int lut_kind, const float *queries_dev, int64_t B, int64_t D,
@@ -1798,10 +1829,8 @@ static int ivf_search_impl(int lut_kind, const float *queries_dev, int64_t B, in
     a.q8_thw_mask = 1;
     a.flush_mask = 63;
     a.dbg_skip = kn.debug_skip;
-    if (kn.debug_counters) {  // (ANNLITE_DEBUG_COUNTERS: the scan's event counters / per-item stamps, as scan_partial wires them)
-        if (!g_dbg) ANNLITE_HIP_TRY(hipMalloc((void **)&g_dbg, 8 * (kDbgSplit + 4)));
-        ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg, 0, 128, st));
-        ANNLITE_HIP_TRY(hipMemsetAsync(g_dbg + kDbgSplit, 0, 32, st));
+    if (kn.debug_counters) {  // (ANNLITE_DEBUG_COUNTERS: the scan's event counters / per-item stamps, as issue() wires them)
+        if ((rc = debug_counters_reset(false, st)) != ANNLITE_OK) return rc;
         a.dbg = g_dbg;
         if (kn.debug_counters == 2) a.dbg_skip |= 8;
     }
@@ -1847,14 +1876,11 @@ extern "C" int annlite_adc_scan_candidates(const void *codes_dev, int code_bytes
                                            size_t workspace_bytes, void *stream) {
     annlite_scan_plan plan;
     hipStream_t st = (hipStream_t)stream;
-    int rc = scan_partial(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut_dev, B, k, workspace_dev,
-                          workspace_bytes, st, &plan, false);
+    const ScanCall sc = {codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut_dev, B, k, workspace_dev, workspace_bytes, false};
+    int rc = scan_partial(sc, kVariantEnv, st, &plan);
     if (rc != ANNLITE_OK || B == 0) return rc;
     ANNLITE_REQUIRE(out_dist_dev && out_id_dev, "null output pointer");
-    const int64_t total = B * plan.n_slices * k;
-    hipLaunchKernelGGL(export_partial_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       (const unsigned long long *)workspace_dev, total, row_base, out_dist_dev, out_id_dev);
-    return launch_status("export_partial_kernel");
+    return launch_export_partial(workspace_dev, B * plan.n_slices * k, row_base, out_dist_dev, out_id_dev, st);
 }
 
 // The candidate generator with the tables built inside the call (round 6): annlite_lut_build + annlite_adc_scan_candidates in one
@@ -1866,36 +1892,24 @@ extern "C" int annlite_pq_search_candidates(int lut_kind, const float *queries_d
                                             int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
     ANNLITE_REQUIRE(M >= 1 && D >= M && D % M == 0,
                     "input dimension must be dividable by number of sub-space (D=%lld, M=%lld)", (long long)D, (long long)M);
-    annlite_scan_plan plan;
-    int rc = plan_query_impl(N, M, Ks, code_bytes, B, k, 0, &plan);
-    if (rc != ANNLITE_OK) return rc;
-    if (B == 0) return ANNLITE_OK;
-    const size_t scan_ws = r256z((size_t)plan.workspace_bytes);
-    const size_t need = scan_ws + r256z((size_t)plan.lut_floats * 4);
-    if (workspace_bytes < need) {
-        set_error("workspace %zu B < required %zu B (annlite_pq_search_workspace_bytes)", workspace_bytes, need);
-        return ANNLITE_ERR_WORKSPACE;
-    }
+    SearchWs w;
+    int rc = search_ws({N, M, Ks, code_bytes, B, k, false}, kVariantEnv, B == 0, workspace_dev, workspace_bytes, &w);
+    if (rc != ANNLITE_OK || B == 0) return rc;
     ANNLITE_REQUIRE(queries_dev && codebooks_dev && workspace_dev && out_dist_dev && out_id_dev, "null device pointer");
     hipStream_t st = (hipStream_t)stream;
-    float *lut = (float *)((char *)workspace_dev + scan_ws);
-    FastCfg c;
-    const bool fuse = N > 0 && plan.fast && fast_cfg(M, Ks, code_bytes, k, &c, false) && c.qf() && M != 64 && Ks <= 256 &&
-                      lut_kind == ANNLITE_LUT_L2 && ((D / M) % 4) == 0 && !knobs().no_fused_lut;
+    const bool fuse = fused_tables(w.plan, lut_kind, N, M, Ks, D);
     const LutBuild lb = {queries_dev, codebooks_dev, D};
     if (!fuse) {
-        rc = annlite_lut_build(lut_kind, queries_dev, B, D, codebooks_dev, M, Ks, lut, plan.fast ? ANNLITE_LAYOUT_TILED : ANNLITE_LAYOUT_BMK,
-                               plan.qi, stream);
+        rc = annlite_lut_build(lut_kind, queries_dev, B, D, codebooks_dev, M, Ks, w.lut, w.plan.fast ? ANNLITE_LAYOUT_TILED : ANNLITE_LAYOUT_BMK,
+                               w.plan.qi, stream);
         if (rc != ANNLITE_OK) return rc;
     }
     annlite_scan_plan used;
-    rc = scan_partial(codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, lut, B, k, workspace_dev, scan_ws, st, &used, false,
-                      fuse ? &lb : nullptr, nullptr, nullptr, nullptr, nullptr, /*cand_seed=*/fuse && !knobs().no_cand_seed);
+    const ScanCall sc = {codes_dev, code_bytes, codes_layout, N, M, Ks, valid_bits_dev, w.lut, B, k, workspace_dev, w.scan_ws, false,
+                         fuse ? &lb : nullptr, nullptr, nullptr, nullptr, nullptr, /*cand_seed=*/fuse && !knobs().no_cand_seed};
+    rc = scan_partial(sc, kVariantEnv, st, &used);
     if (rc != ANNLITE_OK) return rc;
-    const int64_t total = B * used.n_slices * k;
-    hipLaunchKernelGGL(export_partial_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       (const unsigned long long *)workspace_dev, total, row_base, out_dist_dev, out_id_dev);
-    return launch_status("export_partial_kernel");
+    return launch_export_partial(workspace_dev, B * used.n_slices * k, row_base, out_dist_dev, out_id_dev, st);
 }
 
 extern "C" int annlite_codes_skew(const void *in_dev, int64_t N, int64_t M, const int64_t *ids_dev, int64_t id_base,
@@ -1956,15 +1970,8 @@ extern "C" int annlite_adc_dist(const float *adtable_dev, int64_t M, int64_t Ks,
     const int64_t cap = (int64_t)device_cu_count() * 8;
     if (blocks > cap) blocks = cap;
     hipStream_t st = (hipStream_t)stream;
-    if (code_bytes == 1)
-        hipLaunchKernelGGL(adc_dist_kernel<uint8_t>, dim3((unsigned)blocks), dim3(256), lds, st, adtable_dev, (int)M,
-                           (int)Ks, (const uint8_t *)codes_dev, N, out_dev);
-    else if (code_bytes == 2)
-        hipLaunchKernelGGL(adc_dist_kernel<uint16_t>, dim3((unsigned)blocks), dim3(256), lds, st, adtable_dev, (int)M,
-                           (int)Ks, (const uint16_t *)codes_dev, N, out_dev);
-    else
-        hipLaunchKernelGGL(adc_dist_kernel<uint32_t>, dim3((unsigned)blocks), dim3(256), lds, st, adtable_dev, (int)M,
-                           (int)Ks, (const uint32_t *)codes_dev, N, out_dev);
+    ANNLITE_BY_CODE_BYTES(code_bytes, hipLaunchKernelGGL(adc_dist_kernel<T>, dim3((unsigned)blocks), dim3(256), lds, st, adtable_dev, (int)M, (int)Ks,
+                                                         (const T *)codes_dev, N, out_dev))
     return launch_status("adc_dist_kernel");
 }
 
@@ -1978,14 +1985,7 @@ extern "C" int annlite_adc_gather(const float *lut_bmk_dev, int64_t B, int64_t M
     const int64_t total = B * R;
     const unsigned blocks = (unsigned)((total + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
-    if (code_bytes == 1)
-        hipLaunchKernelGGL(adc_gather_kernel<uint8_t>, dim3(blocks), dim3(256), 0, st, lut_bmk_dev, (int)B, (int)M,
-                           (int)Ks, (const uint8_t *)codes_dev, N, cand_dev, (int)R, out_dev);
-    else if (code_bytes == 2)
-        hipLaunchKernelGGL(adc_gather_kernel<uint16_t>, dim3(blocks), dim3(256), 0, st, lut_bmk_dev, (int)B, (int)M,
-                           (int)Ks, (const uint16_t *)codes_dev, N, cand_dev, (int)R, out_dev);
-    else
-        hipLaunchKernelGGL(adc_gather_kernel<uint32_t>, dim3(blocks), dim3(256), 0, st, lut_bmk_dev, (int)B, (int)M,
-                           (int)Ks, (const uint32_t *)codes_dev, N, cand_dev, (int)R, out_dev);
+    ANNLITE_BY_CODE_BYTES(code_bytes, hipLaunchKernelGGL(adc_gather_kernel<T>, dim3(blocks), dim3(256), 0, st, lut_bmk_dev, (int)B, (int)M, (int)Ks,
+                                                         (const T *)codes_dev, N, cand_dev, (int)R, out_dev))
     return launch_status("adc_gather_kernel");
 }

@@ -426,6 +426,29 @@ ANNLITE_API int annlite_debug_prep_timeline(uint64_t *out8);
 ANNLITE_API int annlite_debug_seed_candidates(const float *queries_dev, int64_t B, int64_t D, const float *codebooks_dev,
                                   const void *codes_dev, int codes_layout, int64_t N, int64_t M, int64_t Ks,
                                   const uint32_t *valid_bits_dev, int64_t seed_rows, uint32_t *cand_dev, void *stream);
+/* Debug aid (pure host code: no GPU, no device memory): what one scan launch sequence resolves to -- plan, workspace layout, kernel,
+ * grid, every kernel argument -- for a shape, a kernel variant (-1: as ANNLITE_SCAN_VARIANT says, 31: u16 tables, 50: byte tables as the
+ * library asks for them) and the options of the call as `flags`: 1 the slices share their bounds (top-k searches), 2 the tables are built
+ * inside the call from D-dimensional queries, 4 tile mode (B slots, V real queries), 8 byte-table launch that may give up (guarded),
+ * 16 launch gated on the one in front, 32 the table's state is attached (statistics block), 64 the candidate generator may take ONE
+ * seed bound, 128 packed output instead of distances + ids, 256 no output buffers, 512 a valid-row bitmap; split_phase 0 or
+ * ANNLITE_PHASE_*, with seed_rows.  Returns the status the scan would return before its first launch and fills
+ * out[ANNLITE_SCAN_RESOLVE_FIELDS]:
+ *   [0..17]  status, stage (0 nothing to do, 1 reset only, 2 up to the preparation launch, 3 scan), kernel family (0 byte tables, 1 u16
+ *            tables, 2 generic with the table in LDS, 3 generic), kernel id, grid, SKEWED rows, reset fused into the preparation, reset bytes,
+ *            preparation (0 none, 1 quantise + seed bound, 2 one preparation launch, 3 done by the PREPARE half), MFMA nominees, seed rows S,
+ *            S as the preparation launch takes them, rows the seed is spread over, per-slice seed rows, merged in the scan, the plan's
+ *            workspace_bytes and n_slices, dynamic LDS bytes (generic kernels)
+ *   [18..46] the scan kernel's scalar arguments: N, Ks, B, k, n_tiles, n_slices, n_items, slice_rows, jm1, row_base, sqrt_out, flush_mask,
+ *            dbg_skip, tl_private, cand_cap, q8_epoch0, q8_epoch_mul, q8_ring_limit, q8_import_mask, q8_target, q8_thw_mask, q8_rebuild_8ths,
+ *            guard_abort, guard_base, q8_early_merge, q8_merge_patience, q8_map_slices, q8_pos, q8_ilv_log
+ *   [47..73] its pointer arguments as byte offsets from the workspace base, -1 for NULL, -2 for a buffer of the caller's: codes, valid, lut,
+ *            partial, smax, q16, qstep, qlo, qlom, gkey, gk2, gseed, tile_done, out_d, out_i, out_packed, dbg, tile_rows, vmap, item_counter,
+ *            cand, cand_count, guard, gate, host_stats, gseed0, btab */
+#define ANNLITE_SCAN_RESOLVE_FIELDS 74
+ANNLITE_API int annlite_debug_scan_resolve(int64_t N, int64_t M, int64_t Ks, int code_bytes, int codes_layout, int64_t B, int64_t k,
+                                  int variant, int flags, int64_t D, int64_t V, int split_phase, int64_t seed_rows, int64_t *out,
+                                  int64_t n_out);
 
 /* Convert between the PLAIN and the SKEWED code-table layout (uint8 codes).
  * forward (inverse=0): table_out[id][j] = codes_in[i][(j + id) mod M]   -- scatter rows i -> id
