@@ -135,6 +135,9 @@ SYMBOLS = (
     'annlite_flat_search_grouped_workspace_bytes',
     'annlite_flat_search_topk_grouped',
     'annlite_flat_filter_grouped',
+    'annlite_flat_search_wide_workspace_bytes',
+    'annlite_flat_search_topk_wide',
+    'annlite_ivf_flat_search_topk_wide',
     'annlite_ivf_flat_stages',
     'annlite_ivf_flat_search_workspace_bytes',
     'annlite_ivf_flat_search_topk',
@@ -334,6 +337,9 @@ def lib() -> ctypes.CDLL:
                                                    vp, sz, vp]
     L.annlite_flat_filter_grouped.argtypes = [i32, i32, vp, i64, i64, vp, ctypes.c_float, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp, vp,
                                               sz, vp]
+    L.annlite_flat_search_wide_workspace_bytes.argtypes = [i32, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_flat_search_topk_wide.argtypes = [i32, i32, vp, i64, i64, vp, ctypes.c_float, vp, i64, vp, i64, i32, vp, vp, vp, sz, vp]
+    L.annlite_ivf_flat_search_topk_wide.argtypes = [i32, vp, i64, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp, i64, i32, vp, vp, vp]
     L.annlite_ivf_flat_stages.argtypes = [i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(i32)]
     L.annlite_ivf_flat_search_workspace_bytes.argtypes = [i64, i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_ivf_flat_search_topk.argtypes = [i32, vp, i64, i64, vp, vp, i64, vp, vp, i64, i64, vp, i64, vp, vp, i64, i64, i64, i32, vp, vp,

@@ -176,6 +176,14 @@ class FlatGpuIndex(RowStoreIndex):
         value.  ``search_batch`` takes the keyword per call; ``last_filter_route`` reports ``'mask'`` / ``'rows'`` for the last search
         (``None``: none yet, or an empty index or batch), and ``last_overflowed`` counts the queries sent to exact sums over all rows
         of whatever set was scanned.
+    :param large_k: how a search with ``limit > 64`` -- more than a wave's list holds -- is answered.  ``'host'`` (default) / ``'wide'``
+        (opt-in: measured faster at batches of 1024 queries, slower at 64, where a workgroup per query leaves most of the device
+        idle; DESIGN.md section 3.6, "limit above 64").  ``'wide'``: in HIP end to end for
+        ``limit <= 1024`` (``annlite_flat_search_topk_wide``: one bound, one stage of the row kind's filter, a workgroup per query that
+        selects in LDS; DESIGN.md section 3.6, "limit above 64"), no host read.  ``'host'``: ``_search_large_k`` -- the same plan with the
+        distances gathered a wave per pair and the selection by ``torch.topk``; it also serves ``limit > 1024`` under either value.  The
+        answer is the same bit for bit.  ``search_batch`` takes the keyword per call; ``last_large_k`` reports ``'wide'`` / ``'host'``
+        for the last search (``None``: ``limit <= 64``, or nothing ran).
     """
     FORMAT = 'annlite_amd.FlatGpuIndex/1'
     STATE_KEYS = ('dim', 'metric')
@@ -184,11 +192,15 @@ class FlatGpuIndex(RowStoreIndex):
     FILTER_MIN_ROWS = 4097   # (kFlatSample + 1 in flat.hip: smaller tables are answered by exact sums, no filter runs)
     FILTER_ROUTES = ('mask', 'rows', 'auto')
     ROWS_MAX_FRACTION = 0.5  # (measured: DESIGN.md section 3.6, "selected rows")
+    LARGE_K = ('wide', 'host')
+    WIDE_MAX_K = 1024        # (kWideMaxK in flat.hip: a quarter of the selection buffer)
 
     def __init__(self, dim: int, dtype: np.dtype = np.float32, metric: Metric = Metric.COSINE,
                  index_file: Optional[Union[str, Path]] = None, flat_filter: str = 'f32', centre='mean', int8_scale=None,
-                 filter_route: str = 'mask', **kwargs):
+                 filter_route: str = 'mask', large_k: str = 'host', **kwargs):
         self.filter_route = self._check_filter_route(filter_route)
+        self.large_k = self._check_large_k(large_k)
+        self.last_large_k = None       # 'wide' / 'host': what answered the last search_batch with limit > 64; None: none did
         self.last_filter_route = None  # 'mask' / 'rows': how the last search_batch scanned; None: it scanned nothing
         self._sel_rows = None          # i32 [capacity]: the compacted selection of the last 'rows' search
         self._rows_ws = ops.ScanWorkspace()
@@ -335,6 +347,13 @@ class FlatGpuIndex(RowStoreIndex):
                              "only its rows) or 'auto' (by the selection's share of the rows)")
         return route
 
+    @classmethod
+    def _check_large_k(cls, large_k) -> str:
+        if large_k not in cls.LARGE_K:
+            raise ValueError(f"large_k={large_k!r}: 'wide' (limit 65 .. 1024 selected by a workgroup per query, in HIP) or 'host' "
+                             "(gathered distances and torch.topk)")
+        return large_k
+
     def choose_filter_route(self, n_sel: Optional[int], n_rows: int, k: int, route: Optional[str] = None) -> str:
         """``'mask'`` or ``'rows'`` for a search of ``limit`` ``k`` whose selection holds ``n_sel`` of ``n_rows`` rows (``None``: nothing
         to compact -- no ``indices``, no deleted rows) under ``route`` (default: the index's ``filter_route``).  Pure: no device work."""
@@ -372,11 +391,15 @@ class FlatGpuIndex(RowStoreIndex):
         self.last_flat_filter = tag if n_sel >= self.FILTER_MIN_ROWS else None
         return d, i
 
-    def search_batch(self, x, limit: int = 10, indices=None, filter_route: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search_batch(self, x, limit: int = 10, indices=None, filter_route: Optional[str] = None,
+                     large_k: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """All queries of ``x`` [B, D] in one call.  ``(dists f32 [B, k], ids i64 [B, k])`` ascending by (distance, id), NaN
         distances last; missing -> (+inf, -1).  numpy in gives numpy out, device tensors stay on the device.  ``filter_route``: this
-        call's, else the constructor's (class docstring); ``limit > 64`` keeps the masked search under every value."""
+        call's, else the constructor's (class docstring); ``limit > 64`` keeps the masked search under every value.  ``large_k``: this
+        call's, else the constructor's."""
         route = self.filter_route if filter_route is None else self._check_filter_route(filter_route)
+        large_k = self.large_k if large_k is None else self._check_large_k(large_k)
+        self.last_large_k = None
         is_np = not isinstance(x, torch.Tensor)
         q = self._pre(x)
         B = q.shape[0]
@@ -406,8 +429,15 @@ class FlatGpuIndex(RowStoreIndex):
                             workspace=self._ws)
                 self._overflowed = None  # (read from the workspace when asked for: it costs a synchronisation)
                 self.last_flat_filter = tag if N >= self.FILTER_MIN_ROWS else None
+            elif large_k == 'wide' and k <= self.WIDE_MAX_K:
+                d, i = ops.flat_search_topk_wide(self._kind.tag, int(self.metric), q, self._vectors, self._norms, k, valid_bits=valid, n_rows=N,
+                                                 scale=self._i8_scale or 1.0, sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
+                self._overflowed = None
+                self.last_flat_filter = self._kind.tag if N > 2 * ops.flat_list_capacity() else None  # (smaller tables: all rows, no filter)
+                self.last_large_k = 'wide'
             else:
                 d, i = self._search_large_k(q, k, valid, N)
+                self.last_large_k = 'host'
         return like_input(is_np, d, i)
 
     def search_batch_grouped(self, x, limit: int = 10, selections=(), group_of=()):

@@ -167,12 +167,12 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
             if answer is not None:
                 return answer
         if indices is not None or no_walk:
-            return super().search_batch(x, limit=limit, indices=indices, filter_route=kwargs.get('filter_route'))
+            return super().search_batch(x, limit=limit, indices=indices, filter_route=kwargs.get('filter_route'), large_k=kwargs.get('large_k'))
         is_np = not isinstance(x, torch.Tensor)
         q = self._pre(x)
         B = q.shape[0]
         self._overflowed = 0
-        self.last_flat_filter = self.last_filter_route = None  # (a walk: no filter ran, no table was scanned)
+        self.last_flat_filter = self.last_filter_route = self.last_large_k = None  # (a walk: no filter ran, no table was scanned)
         if B == 0:
             return like_input(is_np, *empty_answer(B, k, q.device))
         cand, cand_d = self.candidates(q, ef)

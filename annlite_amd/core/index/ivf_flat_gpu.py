@@ -152,15 +152,19 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         self._sealed = True
 
     # ------------------------------------------------------------------ search
-    def search_batch(self, x, limit: int = 10, indices=None, n_probe: Optional[int] = None, filter_route: Optional[str] = None):
+    def search_batch(self, x, limit: int = 10, indices=None, n_probe: Optional[int] = None, filter_route: Optional[str] = None,
+                     large_k: Optional[str] = None):
         """``FlatGpuIndex.search_batch`` over the rows of each query's ``n_probe`` nearest cells (every cell: that search itself, with
-        its ``filter_route``; the pruned search scans cell tiles under the bitmap whatever the route, and reports ``'mask'``)."""
+        its ``filter_route``; the pruned search scans cell tiles under the bitmap whatever the route, and reports ``'mask'``).  ``large_k``:
+        as there; ``'wide'`` answers a pruned search with ``64 < limit <= 1024`` by ``annlite_ivf_flat_search_topk_wide``."""
+        large_k = self.large_k if large_k is None else self._check_large_k(large_k)
         P = self.n_probe if n_probe is None else n_probe
         C = self.n_cells
         self.last_cell_filter = None
         if P is None or P >= C:
-            return super().search_batch(x, limit=limit, indices=indices, filter_route=filter_route)
+            return super().search_batch(x, limit=limit, indices=indices, filter_route=filter_route, large_k=large_k)
         self.last_filter_route = 'mask'
+        self.last_large_k = None
         is_np = not isinstance(x, torch.Tensor)
         q = self._pre(x)
         B, k = q.shape[0], int(limit)
@@ -189,8 +193,13 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
                                                 sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)  # hnsw/index.py:164-165
                 self._overflowed = None  # (read from the workspace when asked for: it costs a synchronisation)
                 self.last_cell_filter = 'f32' if max_probed >= self.FILTER_MIN_ROWS else None
+            elif large_k == 'wide' and k <= self.WIDE_MAX_K:
+                d, i = ops.ivf_flat_search_topk_wide(int(self.metric), q, self._vectors, cells, C, self._perm, self._cell_rows, k, valid_bits=valid,
+                                                     n_rows=self._n_rows, sqrt=self.metric == Metric.EUCLIDEAN)
+                self.last_large_k = 'wide'
             else:
                 d, i = self._search_large_k_cells(q, k, valid, cells, max_probed)
+                self.last_large_k = 'host'
         return like_input(is_np, d, i)
 
     def _probed_rows(self, cells: torch.Tensor, R: int):

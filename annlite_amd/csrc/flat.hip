@@ -954,15 +954,17 @@ __global__ __launch_bounds__(kI8Threads) void flat_grouped_i8_filter_kernel(int 
 // rows) goes there -- a bound for the next filter stage -- instead of the result arrays.
 // The chain itself, shared by every exact kernel of this file: up to 64 rows (one per lane, -1: none; n_here = lanes that were
 // offered one) are scored against the wave's query and offered to its list.
+// The scoring half, every exact kernel's: `row` becomes -1 where it lies outside the table or the bitmap, `mine` this lane's distance
+// (+inf without a row).  False: no lane holds a row, nothing was scored.
 template <class T>
-__device__ __forceinline__ void flat_exact_chunk(int metric, const float *__restrict__ qr, int D, const T *__restrict__ x, int64_t N,
-                                                 const uint32_t *__restrict__ valid, int64_t row, int n_here, int km1, int lane, WaveList &L,
-                                                 uint32_t &th, uint32_t &tl, float scale = 1.f) {
+__device__ __forceinline__ bool flat_exact_score(int metric, const float *__restrict__ qr, int D, const T *__restrict__ x, int64_t N,
+                                                 const uint32_t *__restrict__ valid, int64_t &row, int n_here, int lane, float scale,
+                                                 float &mine) {
     constexpr int U = 8;
     if (row >= N) row = -1;
     if (row >= 0 && valid && !((valid[row >> 5] >> (row & 31)) & 1u)) row = -1;
-    if (__ballot(row >= 0) == 0ull) return;
-    float mine = __builtin_inff();
+    mine = __builtin_inff();
+    if (__ballot(row >= 0) == 0ull) return false;
     for (int u0 = 0; u0 < n_here; u0 += U) {
         float s[U];
         int64_t rw[U];
@@ -1014,6 +1016,16 @@ __device__ __forceinline__ void flat_exact_chunk(int metric, const float *__rest
             if (lane == u0 + u) mine = dist;
         }
     }
+    return true;
+}
+
+// ... and the offer to the wave's list: the k <= 64 kernels' chunk.
+template <class T>
+__device__ __forceinline__ void flat_exact_chunk(int metric, const float *__restrict__ qr, int D, const T *__restrict__ x, int64_t N,
+                                                 const uint32_t *__restrict__ valid, int64_t row, int n_here, int km1, int lane, WaveList &L,
+                                                 uint32_t &th, uint32_t &tl, float scale = 1.f) {
+    float mine;
+    if (!flat_exact_score(metric, qr, D, x, N, valid, row, n_here, lane, scale, mine)) return;
     const float tf = (th == kKeyInfHi) ? __builtin_inff() : ordered_to_f32(th);
     const unsigned long long pm = __ballot(row >= 0 && !(mine > tf));  // (NaN: behind +inf, numpy's order)
     if (pm) wavelist_offer(L, pm, f32_to_key(mine), (uint32_t)row, km1, th, tl, lane);
@@ -1129,6 +1141,166 @@ __global__ __launch_bounds__(256) void ivf_flat_exact_kernel(int metric, const f
         }
     }
     flat_exact_finish(L, b, k, lane, do_sqrt, thr_out, out_d, out_i);
+}
+
+// ---- exact distances + top-k of 65 .. 1024, a WORKGROUP per query ("limit above 64") ---------------------------
+// flat_exact_kernel's modes and outputs for a k a wave's list cannot hold.  The four waves of a workgroup score 64 candidates each per
+// round (flat_exact_score: the distances are the k <= 64 kernels', bit for bit) and select through ONE buffer in LDS:
+//   s_key[kWideCap]   64-bit keys f32_to_key(dist) << 32 | row -- unique, so their order IS (distance, id), NaN behind +inf, and what
+//                     the buffer holds does not depend on the order in which the waves appended
+//   thr               the k-th smallest key at the last compaction (~0: none yet); only keys strictly below it are appended
+//   s_count           keys in the buffer
+// Invariant: every candidate offered so far that belongs to the k smallest is in s_key[0 .. s_count).  When another round of 256 might
+// not fit, the buffer is ordered (wide_sort, a bitonic network), cut to its k smallest and thr becomes the k-th.
+//
+// Barriers.  Every __syncthreads() below is reached by all 256 threads the same number of times, because nothing on the way to one
+// depends on a thread or a wave: the early returns test kernel arguments and per-query words (cnt[b], ovf[b]) before the first barrier;
+// the trip counts -- segments of the source, rounds of a segment -- come from the same words and from the cell ranges; a wave without
+// candidates in a round (n_here = 0) scores nothing and still walks the round; and whether a round compacts is decided on s_count as
+// read BETWEEN the round's two barriers, when no thread writes it (the appends lie before the first, the reset and the next round's
+// appends behind the second), never on a value one wave holds.  wide_sort's stage count is a function of that same number.
+constexpr int kWideCap = kFlatCap;  // keys the buffer holds: a whole candidate list without a compaction
+constexpr int kWideRound = 256;     // candidates per round: 64 per wave
+constexpr int kWideMaxK = 1024;
+
+// Ascending bitonic sort of s_key[0 .. size), size a power of two (block-uniform), by 256 threads; barriers in front and behind.
+__device__ __forceinline__ void wide_sort(uint64_t *s_key, int size, int tid) {
+    __syncthreads();
+    for (int len = 2; len <= size; len <<= 1) {
+        for (int j = len >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < size / 2; t += 256) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
+                const bool up = (i & len) == 0;
+                const uint64_t a = s_key[i], c = s_key[p];
+                if ((c < a) == up) s_key[i] = c, s_key[p] = a;
+            }
+            __syncthreads();
+        }
+    }
+}
+// s_key[0 .. n) in order: the places up to the next power of two are filled with ~0 ("none": behind every key) first.
+__device__ __forceinline__ void wide_order(uint64_t *s_key, int n, int tid) {
+    int size = 2;
+    while (size < n) size <<= 1;
+    for (int i = n + tid; i < size; i += 256) s_key[i] = ~0ull;
+    wide_sort(s_key, size, tid);
+}
+
+// The candidate sources.  open(b): false -- the query is not this launch's (block-uniform; it may mark the query first).  The candidates
+// come in segments() runs; segment(s) opens run s and returns its length, row(ci) is candidate ci of the open run.
+// The table: the query's filter list (list != NULL; final: the overflow mark of flat_exact_kernel's final_list) or the rows c * stride,
+// c < S (only_overflowed: for the queries a final list marked).
+struct WideTable {
+    const int32_t *list, *cnt;
+    int cap;
+    int64_t S, stride;
+    int only_overflowed;
+    int32_t *ovf;
+    uint32_t *ovf_total;
+    int64_t n;
+    __device__ __forceinline__ bool open(int b, int tid) {
+        if (list) {
+            const int c = cnt[b];
+            const bool over = c > cap;
+            if (tid == 0) {
+                ovf[b] = over ? 1 : 0;
+                if (over) atomicAdd(ovf_total, 1u);
+            }
+            if (over) return false;  // (answered by the launch that follows, over all rows)
+            n = c < 0 ? 0 : c;
+            list += (int64_t)b * cap;
+        } else {
+            if (only_overflowed && !ovf[b]) return false;
+            n = S;
+        }
+        return true;
+    }
+    __device__ __forceinline__ int segments() const { return 1; }
+    __device__ __forceinline__ int64_t segment(int) { return n; }
+    __device__ __forceinline__ int64_t row(int64_t ci) const { return list ? (int64_t)list[ci] : ci * stride; }
+};
+// The probed cells of ivf_flat_exact_kernel: P ranges of perm.
+struct WideCells {
+    const int32_t *cells;
+    int P, C;
+    const int64_t *cell_rows;
+    const int32_t *perm;
+    int64_t n_perm;
+    int64_t begin;
+    __device__ __forceinline__ bool open(int b, int) {
+        cells += (int64_t)b * P;
+        return true;
+    }
+    __device__ __forceinline__ int segments() const { return P; }
+    __device__ __forceinline__ int64_t segment(int p) {
+        int64_t end;
+        ivf_flat_cell_range(cells[p], C, cell_rows, n_perm, begin, end);
+        return end > begin ? end - begin : 0;
+    }
+    __device__ __forceinline__ int64_t row(int64_t ci) const { return (int64_t)perm[begin + ci]; }
+};
+
+template <class T, class Source>
+__global__ __launch_bounds__(256) void flat_exact_wide_kernel(int metric, const float *__restrict__ q, int D, const T *__restrict__ x, int64_t N,
+                                                             Source src, const uint32_t *__restrict__ valid, int k, int do_sqrt,
+                                                             float *__restrict__ thr_out, float *__restrict__ out_d,
+                                                             int64_t *__restrict__ out_i, float scale) {
+    __shared__ uint64_t s_key[kWideCap];
+    __shared__ int s_count;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x;
+    if (!src.open(b, tid)) return;
+    const float *qr = q + (int64_t)b * D;
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+    uint64_t thr = ~0ull;
+    const int n_seg = src.segments();
+    for (int s = 0; s < n_seg; ++s) {
+        const int64_t n = src.segment(s);
+        for (int64_t c0 = 0; c0 < n; c0 += kWideRound) {
+            const int64_t w0 = c0 + wave * 64, left = n - w0;
+            const int n_here = left <= 0 ? 0 : left < 64 ? (int)left : 64;
+            int64_t row = lane < n_here ? src.row(w0 + lane) : -1;
+            float mine;
+            if (flat_exact_score(metric, qr, D, x, N, valid, row, n_here, lane, scale, mine)) {
+                const uint64_t key = ((uint64_t)f32_to_key(mine) << 32) | (uint32_t)row;
+                const bool pass = row >= 0 && key < thr;
+                const unsigned long long pm = __ballot(pass);
+                if (pm) {  // one LDS atomic per wave; the lanes write behind it at their prefix offsets
+                    int base = 0;
+                    if (lane == 0) base = atomicAdd(&s_count, __popcll(pm));
+                    base = __shfl(base, 0);
+                    if (pass) s_key[base + __popcll(pm & ((1ull << lane) - 1ull))] = key;
+                }
+            }
+            __syncthreads();
+            const int have = s_count;  // (<= kWideCap: the round before left room for 256)
+            if (have + kWideRound > kWideCap) {
+                wide_order(s_key, have, tid);
+                thr = s_key[k - 1];  // (have > kWideCap - kWideRound >= k: a real key)
+                if (tid == 0) s_count = k;
+            }
+            __syncthreads();
+        }
+    }
+    const int have = s_count;
+    wide_order(s_key, have, tid);
+    // flat_exact_finish's rules, a place per thread
+    if (thr_out) {
+        if (tid == 0) {
+            const float d = k <= have ? ordered_to_f32((uint32_t)(s_key[k - 1] >> 32)) : __builtin_inff();
+            thr_out[b] = d != d ? __builtin_inff() : d;
+        }
+        return;
+    }
+    for (int j = tid; j < k; j += 256) {
+        const bool none = j >= have;
+        float d = none ? __builtin_inff() : ordered_to_f32((uint32_t)(s_key[j] >> 32));
+        const int64_t id = (none || d == __builtin_inff()) ? (int64_t)-1 : (int64_t)(uint32_t)s_key[j];
+        if (do_sqrt) d = __builtin_sqrtf(d);
+        out_d[(int64_t)b * k + j] = d;
+        out_i[(int64_t)b * k + j] = id;
+    }
 }
 
 // flat_filter_kernel over (plan tile t, row tile of t's cell): tile t = the 128 slots vmap[128 t ..] of queries that probe ONE cell
@@ -1397,13 +1569,17 @@ static int flat_check_workspace(size_t have, size_t need) {
 
 // The argument checks every filter entry (kFlatStage: one stage, arg = its stride) and every search entry (kFlatSearch: arg = k)
 // starts with.  max_dim: INT32_MAX for the f32 contraction's entries, kSplitMaxDim for the others, whose message names it.
-enum FlatEntry { kFlatStage, kFlatSearch };
+// kFlatSearchWide: the searches of flat_exact_wide_kernel, arg = k in (64, kWideMaxK].
+enum FlatEntry { kFlatStage, kFlatSearch, kFlatSearchWide };
 static int flat_check_shape(FlatEntry what, int metric, int64_t B, int64_t D, int64_t N, int64_t arg, int64_t max_dim) {
     ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
-    const bool search = what == kFlatSearch;
-    const bool ok = B >= 0 && D >= 1 && N >= 0 && arg >= 1 && (!search || arg <= 64) && N <= INT32_MAX && B <= INT32_MAX && D <= max_dim;
-    if (max_dim == INT32_MAX) ANNLITE_REQUIRE(ok, search ? "bad shape (1 <= k <= 64)" : "bad shape");
-    else ANNLITE_REQUIRE(ok, search ? "bad shape (1 <= k <= 64, D <= %lld)" : "bad shape (D <= %lld)", (long long)max_dim);
+    const bool search = what == kFlatSearch, wide = what == kFlatSearchWide;
+    const bool ok = B >= 0 && D >= 1 && N >= 0 && arg >= 1 && (!search || arg <= 64) && (!wide || (arg > 64 && arg <= kWideMaxK)) &&
+                    N <= INT32_MAX && B <= INT32_MAX && D <= max_dim;
+    if (max_dim == INT32_MAX) ANNLITE_REQUIRE(ok, search ? "bad shape (1 <= k <= 64)" : wide ? "bad shape (65 <= k <= 1024)" : "bad shape");
+    else
+        ANNLITE_REQUIRE(ok, search ? "bad shape (1 <= k <= 64, D <= %lld)" : wide ? "bad shape (65 <= k <= 1024, D <= %lld)" : "bad shape (D <= %lld)",
+                        (long long)max_dim);
     return ANNLITE_OK;
 }
 
@@ -1825,6 +2001,50 @@ static int flat_workspace_bytes(int filter, bool typed, int64_t N, int64_t D, in
     });
 }
 
+// ---- 64 < k <= 1024 ("limit above 64"): one bound, ONE filter stage, flat_exact_wide_kernel over the lists ----------
+// The plan: a table of at most 2 cap rows is answered over all its rows.  Otherwise the bound of a query is the k-th smallest exact
+// distance among every (cap / 2k)-th valid row -- about cap / 2 rows then pass the filter --, F::launch fills the lists against it, the
+// wide kernel selects from each list, and the queries whose list overflowed are answered over all rows.
+template <class F>
+static int flat_search_wide(const FlatCall &c, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
+                            size_t workspace_bytes) {
+    using T = typename F::Row;
+    if (int rc = flat_check<F>(kFlatSearchWide, c, k)) return rc;
+    if (c.B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(c.q && out_dist_dev && out_id_dev && workspace_dev && (c.N == 0 || (c.x && c.norms)), "null device pointer");
+    const typename F::Ws fw = F::carve(workspace_dev, c.B, c.D);
+    if (int rc = flat_check_workspace(workspace_bytes, fw.bytes)) return rc;
+    const FlatWs &w = F::base(fw);
+    const int64_t B = c.B, N = c.N;
+    hipStream_t st = c.st;
+    const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
+    ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
+    // Every flat_exact_wide_kernel launch: over the lists (list != NULL), or over every stride-th of S rows.
+    auto wide = [&](const int32_t *list, int64_t S, int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
+        const WideTable src{list, w.cnt, kFlatCap, S, stride, only_overflowed, w.ovf, w.ovf_total, 0};
+        hipLaunchKernelGGL((flat_exact_wide_kernel<T, WideTable>), dim3((unsigned)B), dim3(256), 0, st, c.metric, c.q, (int)c.D, (const T *)c.x, N,
+                           src, c.valid, (int)k, sqrt_out, thr_out, out_dist_dev, out_id_dev, F::kScale ? c.row_scale : 1.f);
+        return launch_status("flat_exact_wide_kernel");
+    };
+    if (N <= 2 * kFlatCap) return wide(nullptr, N, 1, do_sqrt, 0, nullptr);
+    static_assert(kFlatCap / (2 * kWideMaxK) >= 2, "the largest k leaves a sample stride of 2");
+    const int64_t stride = kFlatCap / (2 * k);
+    int rc = F::prepare(c, fw);
+    if (rc != ANNLITE_OK) return rc;
+    if ((rc = wide(nullptr, (N + stride - 1) / stride, stride, 0, 0, w.thr)) != ANNLITE_OK) return rc;
+    ANNLITE_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)B * 4, st));
+    if ((rc = F::launch(c, fw, N, 1, w.thr, w.cand, w.cnt, nullptr)) != ANNLITE_OK) return rc;
+    if ((rc = wide(w.cand, 0, 1, do_sqrt, 0, nullptr)) != ANNLITE_OK) return rc;
+    return wide(nullptr, N, 1, do_sqrt, 1, nullptr);
+}
+
+// The run-time filter code of the wide entries: every row kind's own filter; bf16x3 is refused (k > 64 keeps the f32 filter over f32 rows).
+template <class Fn>
+static int flat_with_wide_filter(int filter, Fn &&fn) {
+    ANNLITE_REQUIRE(filter != ANNLITE_FLAT_FILTER_BF16X3, "the bf16x3 filter serves k <= 64 only: search f32 rows with the f32 filter");
+    return flat_with_filter(filter, fn);
+}
+
 // ---- cells: workspace, stages, launchers ---------------------------------------------------------------------------------------------
 constexpr int kIvfFlatMaxStages = 16;  // strides annlite_ivf_flat_stages can return (2^31 rows: 19 bits of stride, 5 at a time, + the first)
 
@@ -2208,6 +2428,26 @@ extern "C" int annlite_flat_filter_grouped(int filter, int metric, const float *
     });
 }
 
+// ---- limit above 64: the table search of every row kind for 64 < k <= 1024 ("limit above 64") ---------------------
+extern "C" int annlite_flat_search_wide_workspace_bytes(int filter, int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    return flat_with_wide_filter(filter, [&](auto F) -> int {
+        if (int rc = flat_check_shape(kFlatSearchWide, ANNLITE_METRIC_EUCLIDEAN, B, D, N, k, F.kMaxDim)) return rc;
+        *bytes = (int64_t)F.carve(nullptr, B, D).bytes;
+        return ANNLITE_OK;
+    });
+}
+
+extern "C" int annlite_flat_search_topk_wide(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                                             float row_scale, const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k,
+                                             int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
+                                             void *stream) {
+    const FlatCall c = flat_table_call(metric, queries_dev, B, D, vectors_dev, row_scale, norms_dev, nullptr, N, valid_bits_dev, stream);
+    return flat_with_wide_filter(filter, [&](auto F) {
+        return flat_search_wide<decltype(F)>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
+    });
+}
+
 extern "C" int annlite_flat_overflow_count(const void *workspace_dev, void *stream, int64_t *count) {
     ANNLITE_REQUIRE(workspace_dev && count, "null pointer");
     uint32_t v = 0;
@@ -2267,6 +2507,24 @@ extern "C" int annlite_ivf_flat_search_topk(int metric, const float *queries_dev
 }
 
 // ---- the split filter over cell tiles ---------------------------------------------------------------------------------------------------
+// 64 < k <= 1024 over the probed cells: one launch of the wide kernel over each query's P ranges -- no plan, no filter, no workspace.
+extern "C" int annlite_ivf_flat_search_topk_wide(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
+                                                 const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C,
+                                                 const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k, int flags,
+                                                 float *out_dist_dev, int64_t *out_id_dev, void *stream) {
+    if (int rc = flat_check_shape(kFlatSearchWide, metric, B, D, N, k, INT32_MAX)) return rc;
+    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && P <= INT32_MAX && n_perm >= 0 && n_perm <= N, "bad cells P=%lld C=%lld n_perm=%lld",
+                    (long long)P, (long long)C, (long long)n_perm);
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && cells_dev && cell_rows_dev && (n_perm == 0 || (vectors_dev && perm_dev)),
+                    "null device pointer");
+    const WideCells src{cells_dev, (int)P, (int)C, cell_rows_dev, perm_dev, n_perm, 0};
+    hipLaunchKernelGGL((flat_exact_wide_kernel<float, WideCells>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, metric, queries_dev, (int)D,
+                       vectors_dev, N, src, valid_bits_dev, (int)k, (flags & ANNLITE_FLAG_SQRT) ? 1 : 0, (float *)nullptr, out_dist_dev, out_id_dev,
+                       1.f);
+    return launch_status("flat_exact_wide_kernel");
+}
+
 extern "C" int annlite_ivf_flat_centred_norms(const float *vectors_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n,
                                               int64_t id_base, const float *centres_dev, int64_t C, const int32_t *cell_of_dev,
                                               float *norms_dev, void *stream) {

@@ -1380,3 +1380,38 @@ def flat_filter_grouped(flat_filter: str, metric: int, queries: torch.Tensor, ve
     (not ``'f32'``), the filter's score of every (query, stage row) pair, f32 [B, ceil(N / stride)]."""
     return _flat_row_set_call('grouped', flat_filter, metric, queries, vectors, norms, n_rows, _grouped_rows(valid_bits, masks, group), centre,
                               scale, workspace, bounds=bounds, stride=stride, scores=scores)
+
+
+# ---------------------------------------------------------------------------------------------- limit above 64 (DESIGN.md section 3.6)
+def flat_search_topk_wide(flat_filter: str, metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, k: int,
+                          valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, scale: float = 1.0, sqrt: bool = False,
+                          workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_flat_search_topk_wide``: exact k nearest rows for ``64 < k <= 1024`` over f32 (``flat_filter`` ``'f32'``), f16
+    (``'f16x2'``) or int8 (``'i8x3'``, ``scale``) rows: ``(dist f32 [B, k], ids i64 [B, k])`` ascending by (distance, id), (+inf, -1)
+    padded.  One bound, one filter stage, a workgroup per query selecting in LDS; ``flat_overflow_count(workspace)`` reads the call's
+    overflow counter afterwards."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    code = _capi.FLAT_FILTER[flat_filter]
+    ws = _flat_workspace('flat_search_wide_workspace_bytes', (code, N, D, B, int(k)), dev, workspace)
+    od, oi = _flat_topk_outputs(B, k, dev)
+    check(lib().annlite_flat_search_topk_wide(code, int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), float(scale), norms.data_ptr(), N,
+                                              _ptr(valid_bits), int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              stream_ptr()), 'flat_search_topk_wide')
+    return od, oi
+
+
+def ivf_flat_search_topk_wide(metric: int, queries: torch.Tensor, vectors: torch.Tensor, cells: torch.Tensor, n_cells: int, perm: torch.Tensor,
+                              cell_rows: torch.Tensor, k: int, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+                              sqrt: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_ivf_flat_search_topk_wide``: exact k nearest (``64 < k <= 1024``) among the rows of each query's probed ``cells`` i32
+    [B, P] (``perm`` / ``cell_rows`` as ``ivf_flat_search_topk``), one launch: ``(dist f32 [B, k], ids i64 [B, k])`` ascending by
+    (distance, id), (+inf, -1) padded."""
+    B, D = queries.shape
+    N = vectors.shape[0] if n_rows is None else n_rows
+    od, oi = _flat_topk_outputs(B, k, queries.device)
+    check(lib().annlite_ivf_flat_search_topk_wide(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, _ptr(valid_bits), cells.data_ptr(),
+                                                  cells.shape[1], int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(), int(k),
+                                                  1 if sqrt else 0, od.data_ptr(), oi.data_ptr(), stream_ptr()), 'ivf_flat_search_topk_wide')
+    return od, oi

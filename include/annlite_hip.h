@@ -782,6 +782,30 @@ ANNLITE_API int annlite_ivf_flat_search_topk_split(int metric, const float *quer
                                        int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * limit above 64 ("limit above 64"): the exact searches above for 64 < k <= 1024.  A workgroup per query scores
+ * its candidates in the arithmetic of every exact stage (the distances of annlite_flat_search_topk / annlite_exact_gather_dist, bit
+ * for bit) and selects through a buffer of 4096 keys in LDS.  Outputs, order, padding and flags as annlite_flat_search_topk.
+ * replaces: HnswIndex.search / FlatIndex.search with limit > 64 (the reference has no limit on k); here it replaces the gather /
+ * torch.topk route of FlatGpuIndex._search_large_k and IvfFlatGpuIndex._search_large_k_cells, whose answer it reproduces bit for bit.
+ * ---------------------------------------------------------------------------------------------- */
+/* filter: ANNLITE_FLAT_FILTER_F32, _F16X2 or _I8X3 (the row kind, as in annlite_flat_search_topk_rows; BF16X3 is refused: k > 64 keeps
+ * the f32 filter over f32 rows).  No reference counterpart. */
+ANNLITE_API int annlite_flat_search_wide_workspace_bytes(int filter, int64_t N, int64_t D, int64_t B, int64_t k, int64_t *bytes);
+/* N <= 8192: exact sums over all rows.  Otherwise: the bound of a query is the k-th smallest exact distance among every (4096 / 2k)-th
+ * valid row, ONE stage of the row kind's filter against it fills the lists, the lists are selected from, and a query whose list
+ * overflowed is answered over all rows (annlite_flat_overflow_count and annlite_flat_list_counts read this workspace too).  All launches
+ * on `stream`, no host round trip.  65 <= k <= 1024, N < 2^31. */
+ANNLITE_API int annlite_flat_search_topk_wide(int filter, int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_dev,
+                                  float row_scale, const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, int64_t k, int flags,
+                                  float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* The same over the rows of each query's P probed cells (operands as annlite_ivf_flat_search_topk): one launch over the ranges, no
+ * filter and no workspace.  replaces: annlite_ivf_flat_search_topk's consumers with limit > 64. */
+ANNLITE_API int annlite_ivf_flat_search_topk_wide(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
+                                      int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C,
+                                      const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k, int flags,
+                                      float *out_dist_dev, int64_t *out_id_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pruned (IVF) search over cells (follow-on of rank 4).
  * Reference structure: AnnLite(n_cells > 1): VQCodec coarse quantiser (annlite/core/codec/vq.py),
  * AnnLite._cell_selection (annlite/index.py:458-466: cdist(query, vq codebook) -> top_k(n_probe)),
