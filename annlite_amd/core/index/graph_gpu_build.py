@@ -24,9 +24,11 @@ Two distance backends share the batching, the seeds, the pair sort and the persi
   * ``GpuLevel0GraphF32`` -- the float backend (``graph_f32.hip``): every distance is
     ``annlite_exact_gather_dist``'s for the metric, between rows of the index's OWN vector column -- it holds no codes, no packed
     records and no second copy of the vectors; below ``BRUTE`` nodes the candidate lists come from one torch product in the metric's
-    order (the select kernel recomputes every distance it compares: only the visiting order is torch's).
+    order (the select kernel recomputes every distance it compares: only the visiting order is torch's).  ``rows='f16'``: the column
+    is the half-precision row store -- the ``annlite_graph_f16_*`` entry points (``graph_f16.hip``), the torch product and the build
+    walk's queries over the widened rows: the f32 graph of the rounded rows, link for link.
 """
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -203,20 +205,37 @@ class GpuLevel0Graph(Level0GraphBase):
         ops.graph_pack_nodes(self.links, self.codes, torch.arange(n, device=self.device, dtype=torch.int64), self.packed, n)
 
 
+class _RowWalk(NamedTuple):
+    """The four entry points of one row format of the float graph"""
+    dtype: torch.dtype
+    search: Callable
+    search_admit: Callable
+    build_select: Callable
+    build_reverse: Callable
+
+
+ROW_WALKS = {'f32': _RowWalk(torch.float32, ops.graph_f32_search, ops.graph_f32_search_admit, ops.graph_f32_build_select,
+                             ops.graph_f32_build_reverse),
+             'f16': _RowWalk(torch.float16, ops.graph_f16_search, ops.graph_f16_search_admit, ops.graph_f16_build_select,
+                             ops.graph_f16_build_reverse)}
+
+
 class GpuLevel0GraphF32(Level0GraphBase):
     """The float backend: ``annlite_graph_f32_search`` / ``_build_select`` / ``_build_reverse`` over the rows of a vector column the
     CALLER owns (``add(vectors, n_new)``: rows ``self.n .. self.n + n_new`` of ``vectors`` are stored already).  ``metric``: the C
-    ABI's number; COSINE rows arrive normalised."""
+    ABI's number; COSINE rows arrive normalised.  ``rows``: ``'f32'`` or ``'f16'``, the column's format -- ``'f16'`` goes to the
+    ``annlite_graph_f16_*`` entry points (``walk``), with f32 queries: the widened rows."""
 
-    def __init__(self, device, metric: int, max_connection: int = 16, ef_construction: int = 200):
+    def __init__(self, device, metric: int, max_connection: int = 16, ef_construction: int = 200, rows: str = 'f32'):
         super().__init__(device, max_connection, ef_construction)
         self.metric = int(metric)
+        self.walk = ROW_WALKS[rows]
         self._v = None
 
     def add(self, vectors: torch.Tensor, n_new: int):
         if n_new == 0:
             return
-        assert vectors.dtype == torch.float32 and vectors.is_contiguous() and vectors.shape[0] >= self.n + n_new
+        assert vectors.dtype == self.walk.dtype and vectors.is_contiguous() and vectors.shape[0] >= self.n + n_new
         self.reserve(self.n + n_new)
         self._v = vectors
         try:
@@ -228,7 +247,8 @@ class GpuLevel0GraphF32(Level0GraphBase):
         """The ``ef_construction`` nearest of the n + b stored rows (batch mates included, the point itself not), ascending in the
         metric's order: squared L2 (COSINE rows are normalised: the same order), or minus the inner product."""
         total = n + b
-        rows, x = self._v[:total], self._v[n: total]
+        rows = self._v[:total].float()  # (f16 rows: the same product over the widened rows)
+        x = rows[n:]
         if self.metric == int(Metric.INNER_PRODUCT):  # 1 - <q, x> ascends as <q, x> descends
             d = -(x @ rows.T)
         else:
@@ -241,14 +261,14 @@ class GpuLevel0GraphF32(Level0GraphBase):
         return cand
 
     def _walk_candidates(self, pos: int, n: int, b: int) -> torch.Tensor:
-        cand, _ = ops.graph_f32_search(self.metric, self._v[n: n + b], self._v, self.links, self.seeds(), self.efc, n_rows=n)
+        cand, _ = self.walk.search(self.metric, self._v[n: n + b].float(), self._v, self.links, self.seeds(), self.efc, n_rows=n)
         return cand
 
     def _select(self, cand: torch.Tensor, n: int, b: int) -> torch.Tensor:
-        return ops.graph_f32_build_select(self.metric, cand, n, self._v, self.Mc, self.links, n_rows=n + b)
+        return self.walk.build_select(self.metric, cand, n, self._v, self.Mc, self.links, n_rows=n + b)
 
     def _reverse(self, keys: torch.Tensor, seg: torch.Tensor, n_after: int):
-        ops.graph_f32_build_reverse(self.metric, keys, seg, self._v, self.links, n_rows=n_after)
+        self.walk.build_reverse(self.metric, keys, seg, self._v, self.links, n_rows=n_after)
 
     def load_state(self, st):
         self._load_links(st)

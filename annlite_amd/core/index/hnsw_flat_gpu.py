@@ -20,6 +20,12 @@ best admitted rows among everything it evaluates ("filter
 clears the validity bit only -- the row keeps routing the walk.  ``flat_filter`` / ``centre`` / ``filter_route`` are the parent's keywords
 and reach it unchanged: they choose the filter of those exact searches (``search_exhaustive`` included) and whether a filtered one scans
 the table or the selected rows, never the walk.
+
+``graph_rows='f16'`` (opt-in; default ``'f32'``) keeps the graph over HALF-PRECISION rows: the index is then the f16 ``FlatGpuIndex`` --
+rows rounded once to nearest even when added, half the HBM, norms, validity and exact search from the f16 store -- with the link lists
+beside it, built and walked by the ``annlite_graph_f16_*`` entry points (``graph_f16.hip``: a quarter wave per row; DESIGN.md section
+3.8, "f16 rows").  Every distance carries ``annlite_exact_gather_dist_f16``'s bits: links, ids and distances are those of an f32 graph
+index fed the rounded rows, bit for bit.  (``dtype=np.float16`` without the keyword stays refused: the keyword is the opt-in.)
 """
 from pathlib import Path
 from typing import List, Optional, Tuple, Union
@@ -39,6 +45,7 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
     ALSO_LOADS = (FlatGpuIndex.FORMAT,)  # (rows without links: the graph is rebuilt from them)
     MAX_EF = 256                         # the walk's list: four registers per lane
     MAX_DIM = 2048
+    GRAPH_ROWS = ('f32', 'f16')
     # (a filter per query: one search_batch per group -- the graph search stays the search it is under every selection)
     search_batch_grouped = RowStoreIndex.search_batch_grouped
     # DESIGN.md section 3.8, table "filtered walk" (1M x 128): the smallest measured share of admitted rows at which the filtered walk
@@ -48,7 +55,7 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
 
     def __init__(self, dim: int, dtype: np.dtype = np.float32, metric: Metric = Metric.COSINE, ef_construction: int = 200,
                  ef_search: int = 50, max_connection: int = 16, seed: int = 100, build: Optional[str] = 'gpu',
-                 index_file: Optional[Union[str, Path]] = None, filter_search: str = 'exact', **kwargs):
+                 index_file: Optional[Union[str, Path]] = None, filter_search: str = 'exact', graph_rows: str = 'f32', **kwargs):
         # (named here: RowStoreIndex drops the HNSW kwargs the reference forwards to every index)
         if build not in (None, 'gpu'):
             raise NotImplementedError(f"build={build!r}: only the GPU-built level-0 graph exists over float vectors (build='gpu')")
@@ -57,13 +64,17 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
         if not 1 <= int(dim) <= self.MAX_DIM:
             raise ValueError(f'dim={dim}: the float graph takes 1 <= dim <= {self.MAX_DIM}')
         self._check_filter_search(filter_search, "the parent's exact filtered search")
-        if is_f16(dtype):
-            raise NotImplementedError('dtype=np.float16: the float graph walks and builds over f32 rows only (half-precision rows exist '
-                                      'in the exhaustive FlatGpuIndex: no graph, n_cells=1)')
+        if graph_rows not in self.GRAPH_ROWS:
+            raise ValueError(f"graph_rows={graph_rows!r}: 'f32' (default) or 'f16' (the graph over half-precision rows)")
+        if is_f16(dtype) and graph_rows != 'f16':
+            raise NotImplementedError("dtype=np.float16: the float graph walks and builds over f32 rows unless graph_rows='f16' opts into "
+                                      'the graph over half-precision rows (they also exist in the exhaustive FlatGpuIndex: no graph, '
+                                      'n_cells=1)')
         if is_i8(dtype):
             raise NotImplementedError('dtype=np.int8: the float graph walks and builds over f32 rows only (int8 rows exist '
                                       'in the exhaustive FlatGpuIndex: no graph, n_cells=1)')
-        super().__init__(dim, dtype=dtype, metric=metric, **kwargs)
+        self.graph_rows = graph_rows
+        super().__init__(dim, dtype=np.float16 if graph_rows == 'f16' else dtype, metric=metric, **kwargs)
         self.ef_construction = int(ef_construction)  # hnsw/index.py:66-69
         self.ef_search = int(ef_search)
         self.max_connection = int(max_connection)
@@ -79,7 +90,7 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
         if self._gg is None:
             from .graph_gpu_build import GpuLevel0GraphF32
 
-            self._gg = GpuLevel0GraphF32(self._device(), int(self.metric), self.max_connection, self.ef_construction)
+            self._gg = GpuLevel0GraphF32(self._device(), int(self.metric), self.max_connection, self.ef_construction, rows=self.graph_rows)
         return self._gg
 
     def _rebuild_graph(self, N: int):
@@ -125,8 +136,7 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
             raise RuntimeError('no graph to walk (the index is empty)')
         if ef > self.MAX_EF:
             raise RuntimeError(f'the GPU walk keeps ef <= {self.MAX_EF} candidates (ef = {ef})')
-        return ops.graph_f32_search(int(self.metric), q_dev.contiguous(), self._vectors, gg.links, gg.seeds(), ef,
-                                    valid_bits=self._valid, n_rows=gg.n)
+        return gg.walk.search(int(self.metric), q_dev.contiguous(), self._vectors, gg.links, gg.seeds(), ef, valid_bits=self._valid, n_rows=gg.n)
 
     def search_exhaustive(self, x, limit: int = 10, **kw):
         return super().search_batch(x, limit=limit, **kw)
@@ -134,8 +144,8 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
     # the filtered walk's two hooks (filter_walk.FilterWalkMixin)
     def _filter_walk(self, q, ef_route: int, ef: int, admit, reach):
         gg = self._gg
-        return ops.graph_f32_search_admit(int(self.metric), q.contiguous(), self._vectors, gg.links, gg.seeds(), ef_route, ef, admit,
-                                          n_rows=gg.n, route_worst=reach)
+        return gg.walk.search_admit(int(self.metric), q.contiguous(), self._vectors, gg.links, gg.seeds(), ef_route, ef, admit, n_rows=gg.n,
+                                    route_worst=reach)
 
     def _filter_rank(self, x, q, cand, cand_d, k: int, ef: int, admit):
         # (the list is ascending with its missing places at the tail: the first k columns are the answer, by position)
@@ -196,6 +206,8 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
         super()._load_state(state, N)
         self._gg = None
         links = state.get('links')
+        if N and np.asarray(state['vectors']).dtype != np.dtype(np.float16 if self.graph_rows == 'f16' else np.float32):
+            links = None  # (rows of the other kind were converted: links built over other bits are not this index's graph)
         if N and links is not None and links.shape == (N, 2 * self.max_connection + 1):
             self._ensure_graph().load_state({'n': N, 'links': links})
         elif N:

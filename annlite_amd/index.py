@@ -124,6 +124,10 @@ class AnnLite:
         channel; default 1.0, ``2**-7`` for cosine) rides the same way: ``FlatGpuIndex`` then stores int8 codes -- a quarter of the HBM,
         the answer of the f32 index over the rows ``int8_scale * code`` bit for bit, its own filter ``'i8x3'``; the float graph and
         the cells over floats raise ``NotImplementedError``, the indexes over PQ codes drop both keywords
+    :param graph_rows: ``'f32'`` (default) or ``'f16'`` (kwarg, same channel; ``graph=True, build='gpu'`` without ``n_subvectors``,
+        dropped for every other index): ``'f16'`` keeps the float graph over half-precision rows -- ``HnswFlatGpuIndex`` is then the
+        f16 ``FlatGpuIndex`` with link lists, built and walked a quarter wave per row (``graph_f16.hip``); links, ids and distances
+        are the f32 graph's over the rounded rows, bit for bit.  Any other value is a ``ValueError``
     :param columns: ``[(name, type), ...]`` (or ``filterable_attrs={name: type}``): the tags a filter may name and have evaluated on
         the device -- ``int`` / ``bool``, ``float`` and ``str`` columns (``ColumnStore``); tags that are not declared stay filterable
         on the host, as before
@@ -286,6 +290,7 @@ class AnnLite:
                 return HnswFlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
             kw.pop('build', None)
             kw.pop('filter_search', None)  # (the float graph's option: these indexes answer a filter exactly)
+            kw.pop('graph_rows', None)     # (the float graph's option)
             if self._vq_codec is not None:  # (ivf_prune=True: the constructor refuses cells over floats without it)
                 from .core.index.ivf_flat_gpu import IvfFlatGpuIndex
 
@@ -294,7 +299,7 @@ class AnnLite:
             return FlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
         if not (self._vq_codec is None and kw.get('graph')):
             kw.pop('filter_search', None)  # (the graph indexes' option: the other indexes over PQ codes answer a filter exactly)
-        for name in ('flat_filter', 'centre', 'cell_filter', 'int8_scale', 'filter_route', 'large_k'):  # (the float indexes' options: nothing over PQ codes runs that filter)
+        for name in ('flat_filter', 'centre', 'cell_filter', 'int8_scale', 'filter_route', 'large_k', 'graph_rows'):  # (the float indexes' options: nothing over PQ codes runs that filter)
             kw.pop(name, None)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')

@@ -233,13 +233,9 @@ def graph_pack_nodes(links: torch.Tensor, codes: torch.Tensor, nodes: torch.Tens
                                          nodes.data_ptr(), nodes.numel(), packed.data_ptr(), stream_ptr()), 'graph_pack_nodes')
 
 
-# ---------------------------------------------------------------------------------------------- float graph (graph_f32.hip)
-def graph_f32_search(metric: int, queries: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor, seeds: torch.Tensor, ef: int,
-                     valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``annlite_graph_f32_search``: the beam walk over the level-0 lists ``links`` i32 [N, L+1] (count, ids) with exact distances on
-    the float rows ``vectors`` f32 [N, D] (``exact_gather_dist``'s bits).  Returns (ids i64 [B, ef] ascending by (distance, id), rows
-    cleared in ``valid_bits`` blanked in place to -1; dist f32 [B, ef], +inf there)."""
-    assert queries.dtype == torch.float32 and vectors.dtype == torch.float32 and queries.is_contiguous() and vectors.is_contiguous()
+# ---------------------------------------------------------------------------------------------- float graph (graph_f32.hip, graph_f16.hip)
+def _graph_rows_search(kind: str, rows: torch.dtype, metric, queries, vectors, links, seeds, ef, valid_bits, n_rows):
+    assert queries.dtype == torch.float32 and vectors.dtype == rows and queries.is_contiguous() and vectors.is_contiguous()
     assert links.is_contiguous() and seeds.is_contiguous() and links.element_size() == 4 and seeds.element_size() == 4
     B, D = queries.shape
     assert vectors.shape[1] == D
@@ -247,10 +243,56 @@ def graph_f32_search(metric: int, queries: torch.Tensor, vectors: torch.Tensor, 
     assert N <= vectors.shape[0] and N <= links.shape[0]
     out_i = torch.empty((B, ef), dtype=torch.int64, device=vectors.device)
     out_d = torch.empty((B, ef), dtype=torch.float32, device=vectors.device)
-    check(lib().annlite_graph_f32_search(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, links.data_ptr(), links.shape[1] - 1,
-                                         seeds.data_ptr(), seeds.numel(), _ptr(valid_bits), int(ef), out_i.data_ptr(), out_d.data_ptr(),
-                                         stream_ptr()), 'graph_f32_search')
+    fn = getattr(lib(), f'annlite_graph_{kind}_search')
+    check(fn(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, links.data_ptr(), links.shape[1] - 1, seeds.data_ptr(),
+             seeds.numel(), _ptr(valid_bits), int(ef), out_i.data_ptr(), out_d.data_ptr(), stream_ptr()), f'graph_{kind}_search')
     return out_i, out_d
+
+
+def _graph_rows_search_admit(kind: str, rows: torch.dtype, metric, queries, vectors, links, seeds, ef_route, ef, admit_bits, n_rows,
+                             route_worst):
+    assert queries.dtype == torch.float32 and vectors.dtype == rows and queries.is_contiguous() and vectors.is_contiguous()
+    assert links.is_contiguous() and seeds.is_contiguous() and links.element_size() == 4 and seeds.element_size() == 4
+    B, D = queries.shape
+    assert vectors.shape[1] == D
+    N = vectors.shape[0] if n_rows is None else int(n_rows)
+    assert N <= vectors.shape[0] and N <= links.shape[0]
+    out_i, out_d = _admit_walk_outputs(B, ef, N, admit_bits, route_worst, vectors.device)
+    fn = getattr(lib(), f'annlite_graph_{kind}_search_admit')
+    check(fn(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, links.data_ptr(), links.shape[1] - 1, seeds.data_ptr(),
+             seeds.numel(), _ptr(admit_bits), int(ef_route), int(ef), out_i.data_ptr(), out_d.data_ptr(), _ptr(route_worst), stream_ptr()),
+          f'graph_{kind}_search_admit')
+    return out_i, out_d
+
+
+def _graph_rows_build_select(kind: str, rows: torch.dtype, metric, cand, base0, vectors, max_keep, links, n_rows):
+    assert cand.dtype == torch.int64 and cand.is_contiguous() and vectors.dtype == rows and vectors.is_contiguous()
+    b, ef = cand.shape
+    N = vectors.shape[0] if n_rows is None else int(n_rows)
+    assert N <= vectors.shape[0] and N <= links.shape[0] and links.is_contiguous() and links.element_size() == 4
+    pairs = torch.empty((b, int(max_keep)), dtype=torch.int64, device=vectors.device)
+    fn = getattr(lib(), f'annlite_graph_{kind}_build_select')
+    check(fn(int(metric), cand.data_ptr(), int(ef), b, int(base0), vectors.data_ptr(), N, vectors.shape[1], int(max_keep), links.data_ptr(),
+             links.shape[1] - 1, pairs.data_ptr(), stream_ptr()), f'graph_{kind}_build_select')
+    return pairs
+
+
+def _graph_rows_build_reverse(kind: str, rows: torch.dtype, metric, keys_sorted, seg, vectors, links, n_rows):
+    assert keys_sorted.dtype == torch.int64 and seg.dtype == torch.int64 and keys_sorted.is_contiguous() and seg.is_contiguous()
+    assert vectors.dtype == rows and vectors.is_contiguous() and links.is_contiguous() and links.element_size() == 4
+    N = vectors.shape[0] if n_rows is None else int(n_rows)
+    assert N <= vectors.shape[0] and N <= links.shape[0]
+    fn = getattr(lib(), f'annlite_graph_{kind}_build_reverse')
+    check(fn(int(metric), keys_sorted.data_ptr(), seg.data_ptr(), seg.numel() - 1, vectors.data_ptr(), N, vectors.shape[1], links.data_ptr(),
+             links.shape[1] - 1, stream_ptr()), f'graph_{kind}_build_reverse')
+
+
+def graph_f32_search(metric: int, queries: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor, seeds: torch.Tensor, ef: int,
+                     valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_graph_f32_search``: the beam walk over the level-0 lists ``links`` i32 [N, L+1] (count, ids) with exact distances on
+    the float rows ``vectors`` f32 [N, D] (``exact_gather_dist``'s bits).  Returns (ids i64 [B, ef] ascending by (distance, id), rows
+    cleared in ``valid_bits`` blanked in place to -1; dist f32 [B, ef], +inf there)."""
+    return _graph_rows_search('f32', torch.float32, metric, queries, vectors, links, seeds, ef, valid_bits, n_rows)
 
 
 def graph_f32_search_admit(metric: int, queries: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor, seeds: torch.Tensor,
@@ -261,22 +303,13 @@ def graph_f32_search_admit(metric: int, queries: torch.Tensor, vectors: torch.Te
     among everything it evaluates.  Returns (ids i64 [B, ef] ascending by (distance, id), admitted rows only, -1 at the tail; dist f32
     [B, ef], +inf there).  ``route_worst`` f32 [B], when given, receives the distance of the routing list's last place (+inf while that
     list is not full): how far the walk reached."""
-    assert queries.dtype == torch.float32 and vectors.dtype == torch.float32 and queries.is_contiguous() and vectors.is_contiguous()
-    assert links.is_contiguous() and seeds.is_contiguous() and links.element_size() == 4 and seeds.element_size() == 4
-    B, D = queries.shape
-    assert vectors.shape[1] == D
-    N = vectors.shape[0] if n_rows is None else int(n_rows)
-    assert N <= vectors.shape[0] and N <= links.shape[0]
-    out_i, out_d = _admit_walk_outputs(B, ef, N, admit_bits, route_worst, vectors.device)
-    check(lib().annlite_graph_f32_search_admit(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, links.data_ptr(),
-                                               links.shape[1] - 1, seeds.data_ptr(), seeds.numel(), _ptr(admit_bits), int(ef_route),
-                                               int(ef), out_i.data_ptr(), out_d.data_ptr(), _ptr(route_worst), stream_ptr()),
-          'graph_f32_search_admit')
-    return out_i, out_d
+    return _graph_rows_search_admit('f32', torch.float32, metric, queries, vectors, links, seeds, ef_route, ef, admit_bits, n_rows,
+                                    route_worst)
 
 
 def graph_f32_search_stats() -> Tuple[int, int]:
-    """(expansions, rows evaluated) of the last float graph walk, with or without an admit list (ANNLITE_DEBUG_COUNTERS=1)."""
+    """(expansions, rows evaluated) of the last float graph walk -- f32 or f16 rows, with or without an admit list
+    (ANNLITE_DEBUG_COUNTERS=1)."""
     out = (ctypes.c_uint64 * 2)()
     check(lib().annlite_graph_f32_search_stats(out), 'graph_f32_search_stats')
     return int(out[0]), int(out[1])
@@ -285,27 +318,40 @@ def graph_f32_search_stats() -> Tuple[int, int]:
 def graph_f32_build_select(metric: int, cand: torch.Tensor, base0: int, vectors: torch.Tensor, max_keep: int, links: torch.Tensor,
                            n_rows: Optional[int] = None) -> torch.Tensor:
     """``annlite_graph_f32_build_select``: ``graph_build_select`` with the float distance between the rows of ``vectors``."""
-    assert cand.dtype == torch.int64 and cand.is_contiguous() and vectors.dtype == torch.float32 and vectors.is_contiguous()
-    b, ef = cand.shape
-    N = vectors.shape[0] if n_rows is None else int(n_rows)
-    assert N <= vectors.shape[0] and N <= links.shape[0] and links.is_contiguous() and links.element_size() == 4
-    pairs = torch.empty((b, int(max_keep)), dtype=torch.int64, device=vectors.device)
-    check(lib().annlite_graph_f32_build_select(int(metric), cand.data_ptr(), int(ef), b, int(base0), vectors.data_ptr(), N, vectors.shape[1],
-                                               int(max_keep), links.data_ptr(), links.shape[1] - 1, pairs.data_ptr(), stream_ptr()),
-          'graph_f32_build_select')
-    return pairs
+    return _graph_rows_build_select('f32', torch.float32, metric, cand, base0, vectors, max_keep, links, n_rows)
 
 
 def graph_f32_build_reverse(metric: int, keys_sorted: torch.Tensor, seg: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor,
                             n_rows: Optional[int] = None):
     """``annlite_graph_f32_build_reverse``: ``graph_build_reverse`` with the float distance between the rows of ``vectors``."""
-    assert keys_sorted.dtype == torch.int64 and seg.dtype == torch.int64 and keys_sorted.is_contiguous() and seg.is_contiguous()
-    assert vectors.dtype == torch.float32 and vectors.is_contiguous() and links.is_contiguous() and links.element_size() == 4
-    N = vectors.shape[0] if n_rows is None else int(n_rows)
-    assert N <= vectors.shape[0] and N <= links.shape[0]
-    check(lib().annlite_graph_f32_build_reverse(int(metric), keys_sorted.data_ptr(), seg.data_ptr(), seg.numel() - 1, vectors.data_ptr(), N,
-                                                vectors.shape[1], links.data_ptr(), links.shape[1] - 1, stream_ptr()),
-          'graph_f32_build_reverse')
+    _graph_rows_build_reverse('f32', torch.float32, metric, keys_sorted, seg, vectors, links, n_rows)
+
+
+def graph_f16_search(metric: int, queries: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor, seeds: torch.Tensor, ef: int,
+                     valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_graph_f16_search``: ``graph_f32_search`` over the half-precision rows ``vectors`` f16 [N, D] (queries stay f32);
+    ``exact_gather_dist_f16``'s bits -- ``graph_f32_search``'s answer over ``vectors.float()``."""
+    return _graph_rows_search('f16', torch.float16, metric, queries, vectors, links, seeds, ef, valid_bits, n_rows)
+
+
+def graph_f16_search_admit(metric: int, queries: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor, seeds: torch.Tensor,
+                           ef_route: int, ef: int, admit_bits: torch.Tensor, n_rows: Optional[int] = None,
+                           route_worst: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_graph_f16_search_admit``: ``graph_f32_search_admit`` over ``vectors`` f16 [N, D]."""
+    return _graph_rows_search_admit('f16', torch.float16, metric, queries, vectors, links, seeds, ef_route, ef, admit_bits, n_rows,
+                                    route_worst)
+
+
+def graph_f16_build_select(metric: int, cand: torch.Tensor, base0: int, vectors: torch.Tensor, max_keep: int, links: torch.Tensor,
+                           n_rows: Optional[int] = None) -> torch.Tensor:
+    """``annlite_graph_f16_build_select``: ``graph_f32_build_select`` between the rows of ``vectors`` f16 [N, D]."""
+    return _graph_rows_build_select('f16', torch.float16, metric, cand, base0, vectors, max_keep, links, n_rows)
+
+
+def graph_f16_build_reverse(metric: int, keys_sorted: torch.Tensor, seg: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor,
+                            n_rows: Optional[int] = None):
+    """``annlite_graph_f16_build_reverse``: ``graph_f32_build_reverse`` between the rows of ``vectors`` f16 [N, D]."""
+    _graph_rows_build_reverse('f16', torch.float16, metric, keys_sorted, seg, vectors, links, n_rows)
 
 
 class ScanWorkspace:

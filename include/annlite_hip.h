@@ -262,6 +262,24 @@ ANNLITE_API int annlite_graph_f32_build_select(int metric, const int64_t *cand_d
 ANNLITE_API int annlite_graph_f32_build_reverse(int metric, const int64_t *keys_dev, const int64_t *seg_dev, int64_t n_segments,
                          const float *vectors_dev, int64_t N, int64_t D, uint32_t *links_dev, int links_per_node, void *stream);
 ANNLITE_API int annlite_graph_f32_search_stats(uint64_t *out2);
+/* ---- the same graph over f16 rows (graph_f16.hip): vectors_f16_dev f16 [N][D], FlatGpuIndex's half-precision row store ------------
+ * The four entry points above with the same arguments, limits and formats; queries stay f32, and in the build the "query" is itself
+ * an f16 row, widened as it is read.  Every distance carries annlite_exact_gather_dist_f16's bits -- the f32 entry points' answer over
+ * the widened rows, bit for bit.  Where D % 4 == 0 (and the table is 8-byte aligned) a QUARTER wave evaluates a row: 16 lanes, four
+ * of the 64 chains per lane (two 4-byte loads per block of 64 elements), four rows per wave-wide pass, up to 16 rows in flight; every other D
+ * takes the lane-strided loop of the f32 form with 2-byte loads.  annlite_graph_f32_search_stats reports these walks as well. */
+ANNLITE_API int annlite_graph_f16_search(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev, int64_t N,
+                         const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
+                         const uint32_t *valid_bits_dev, int ef, int64_t *out_ids_dev, float *out_dist_dev, void *stream);
+ANNLITE_API int annlite_graph_f16_search_admit(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                         int64_t N, const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
+                         const uint32_t *admit_bits_dev, int ef_route, int ef, int64_t *out_ids_dev, float *out_dist_dev,
+                         float *out_route_worst_dev, void *stream);
+ANNLITE_API int annlite_graph_f16_build_select(int metric, const int64_t *cand_dev, int ef, int64_t b, int64_t base0,
+                         const void *vectors_f16_dev, int64_t N, int64_t D, int max_keep, uint32_t *links_dev, int links_per_node,
+                         int64_t *pairs_dev, void *stream);
+ANNLITE_API int annlite_graph_f16_build_reverse(int metric, const int64_t *keys_dev, const int64_t *seg_dev, int64_t n_segments,
+                         const void *vectors_f16_dev, int64_t N, int64_t D, uint32_t *links_dev, int links_per_node, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Batched flat ADC scan + top-k: the hot path.

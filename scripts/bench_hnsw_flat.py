@@ -3,6 +3,11 @@
 ef_search 64 / 128 / 192 on one and two caller streams, FlatGpuIndex on the same table, and the walk's row-gather rate.
 
     python scripts/bench_hnsw_flat.py --rows 1000000        # one JSON line on stdout
+    python scripts/bench_hnsw_flat.py --rows 1000000 --graph-rows both
+
+``--graph-rows f16``: the graph over half-precision rows (``graph_rows='f16'``).  ``both``: an f32 and an f16 index over the SAME data
+rounded to f16 -- the f32 index stores the rounded values, so both graphs, all answers and all counters are identical (checked); the two
+indexes alternate inside every measurement, in one process, and each one's figures are reported side by side under ``f32`` / ``f16``.
 
 Data: scripts/bench_hnsw.py's generator (a 16-d latent mixed into D dimensions + noise, the same seeds), EUCLIDEAN.
 """
@@ -28,6 +33,7 @@ p.add_argument('--ef-search', type=int, nargs='+', default=[64, 128, 192])
 p.add_argument('--ef-construction', type=int, default=200)
 p.add_argument('--max-connection', type=int, default=16)
 p.add_argument('--steps', type=int, default=5)
+p.add_argument('--graph-rows', choices=['f32', 'f16', 'both'], default='f32')
 a = p.parse_args()
 dev = torch.device('cuda', 0)
 torch.cuda.set_device(0)
@@ -44,7 +50,8 @@ def gen(chunk, rows):
     gg.manual_seed(1234 + chunk)
     z = torch.randn((rows, r_lat), generator=gg, device=dev)
     e = torch.randn((rows, D), generator=gg, device=dev)
-    return (z @ A + 0.05 * e).contiguous()
+    x = (z @ A + 0.05 * e).contiguous()
+    return x.half().float() if a.graph_rows == 'both' else x
 
 
 def queries(seed):
@@ -53,15 +60,21 @@ def queries(seed):
     return (torch.randn((B, r_lat), generator=gq, device=dev) @ A + 0.05 * torch.randn((B, D), generator=gq, device=dev)).contiguous()
 
 
-index = HnswFlatGpuIndex(D, metric=Metric.EUCLIDEAN, initial_size=N, ef_search=a.ef_search[0], ef_construction=a.ef_construction,
-                         max_connection=a.max_connection)
-torch.cuda.synchronize()
-t0 = time.time()
-for c in range((N + CH - 1) // CH):
-    rows = min(CH, N - c * CH)
-    index.add_with_ids(gen(c, rows), torch.arange(c * CH, c * CH + rows, device=dev, dtype=torch.int64))
-torch.cuda.synchronize()
-build_s = time.time() - t0
+kinds = ['f32', 'f16'] if a.graph_rows == 'both' else [a.graph_rows]
+indexes, build_s = {}, {}
+for kind in kinds:
+    index = HnswFlatGpuIndex(D, metric=Metric.EUCLIDEAN, initial_size=N, ef_search=a.ef_search[0], ef_construction=a.ef_construction,
+                             max_connection=a.max_connection, graph_rows=kind)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    for c in range((N + CH - 1) // CH):
+        rows = min(CH, N - c * CH)
+        index.add_with_ids(gen(c, rows), torch.arange(c * CH, c * CH + rows, device=dev, dtype=torch.int64))
+    torch.cuda.synchronize()
+    indexes[kind], build_s[kind] = index, time.time() - t0
+index = indexes[kinds[0]]
+if len(kinds) == 2:
+    assert torch.equal(indexes['f32']._gg.links[:N], indexes['f16']._gg.links[:N]), 'the two graphs differ'
 
 q, q_alt = queries(4321), queries(4321 + 7919)
 q_rot = [q, q_alt]  # the timed steps rotate through two query batches (recall is the first batch's)
@@ -98,51 +111,70 @@ def timed(fn, streams=1):
 
 
 def walk_ms(qd, ef):
+    """{kind: mean ms of the walk kernel by HIP events}; the indexes alternate launch by launch"""
     for _ in range(2):
-        index.candidates(qd, ef)
+        for kind in kinds:
+            indexes[kind].candidates(qd, ef)
     torch.cuda.synchronize()
-    out = []
+    out = {kind: [] for kind in kinds}
     for _ in range(max(3, a.steps)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        index.candidates(qd, ef)
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1))
-    return float(np.mean(out))
+        for kind in kinds:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            indexes[kind].candidates(qd, ef)
+            e1.record()
+            e1.synchronize()
+            out[kind].append(e0.elapsed_time(e1))
+    return {kind: float(np.mean(v)) for kind, v in out.items()}
+
+
+def counters(idx, qd, ef):
+    os.environ['ANNLITE_DEBUG_COUNTERS'] = '1'
+    _capi.knobs_reload()  # (the library parses its switches at load)
+    idx.candidates(qd, ef)
+    out = ops.graph_f32_search_stats()
+    del os.environ['ANNLITE_DEBUG_COUNTERS']
+    _capi.knobs_reload()
+    return out
 
 
 qd = index._pre(q)
 lpn = 2 * a.max_connection
 n_seeds = int(index._gg.seeds().numel())
-res = {}
+res = {kind: {} for kind in kinds}
 for ef in a.ef_search:
-    (d, i), qps1 = timed(lambda qq: index.search_batch(qq, limit=k, ef_search=ef), 1)
-    _, qps2 = timed(lambda qq: index.search_batch(qq, limit=k, ef_search=ef), 2)
-    os.environ['ANNLITE_DEBUG_COUNTERS'] = '1'
-    _capi.knobs_reload()  # (the library parses its switches at load)
-    index.candidates(qd, ef)
-    n_expand, n_eval = ops.graph_f32_search_stats()
-    del os.environ['ANNLITE_DEBUG_COUNTERS']
-    _capi.knobs_reload()
+    qps, ans, cnt = {kind: [None, None] for kind in kinds}, {}, {}
+    for rep_ in range(2):  # (the indexes alternate: one stream, then two, each index in turn)
+        for kind in kinds:
+            search = lambda qq, idx=indexes[kind]: idx.search_batch(qq, limit=k, ef_search=ef)
+            ans[kind], qps[kind][rep_] = timed(search, 1 + rep_)
+    for kind in kinds:
+        cnt[kind] = counters(indexes[kind], qd, ef)
     ms = walk_ms(qd, ef)
-    row_bytes = n_eval * D * 4.0                # the gathered rows (seed rows included)
-    list_bytes = n_expand * 4.0 * (lpn + 1)     # one link list per expansion
-    res[f'ef_search_{ef}'] = {'queries_per_s_one_stream': qps1, 'queries_per_s_two_streams': qps2, 'recall_at_10': recall(i),
-                              'walk_kernel_ms': ms, 'expansions_per_query': n_expand / B, 'rows_evaluated_per_query': n_eval / B,
-                              'row_gather_GBps': row_bytes / (ms * 1e-3) / 1e9,
-                              'row_and_list_GBps': (row_bytes + list_bytes) / (ms * 1e-3) / 1e9}
+    if len(kinds) == 2:
+        assert cnt['f32'] == cnt['f16'], ('the two walks counted differently', cnt)
+        assert all(torch.equal(u, v) for u, v in zip(ans['f32'], ans['f16'])), 'the two indexes answer differently'
+    for kind in kinds:
+        n_expand, n_eval = cnt[kind]
+        row_bytes = n_eval * D * float(indexes[kind]._vectors.element_size())  # the gathered rows (seed rows included)
+        list_bytes = n_expand * 4.0 * (lpn + 1)                                # one link list per expansion
+        res[kind][f'ef_search_{ef}'] = {'queries_per_s_one_stream': qps[kind][0], 'queries_per_s_two_streams': qps[kind][1],
+                                        'recall_at_10': recall(ans[kind][1]), 'walk_kernel_ms': ms[kind],
+                                        'expansions_per_query': n_expand / B, 'rows_evaluated_per_query': n_eval / B,
+                                        'row_gather_GBps': row_bytes / (ms[kind] * 1e-3) / 1e9,
+                                        'row_and_list_GBps': (row_bytes + list_bytes) / (ms[kind] * 1e-3) / 1e9}
 
 # FlatGpuIndex on the same table: the index's own exhaustive search (its parent's search_batch over the same rows)
 (fd, fi), flat_qps1 = timed(lambda qq: index.search_exhaustive(qq, limit=k), 1)
 _, flat_qps2 = timed(lambda qq: index.search_exhaustive(qq, limit=k), 2)
 
 links = index._gg.links[:N, 0].float()
-print(json.dumps({'config': f'float HNSW (level 0, GPU-built): {N} x {D}-dim f32, L2, max_connection={a.max_connection}, '
-                            f'ef_construction={a.ef_construction}, batch {B}, k={k}, {n_seeds} seeds',
-                  'metric': 'queries/sec', 'unit': 'queries/s',
-                  'value': res[f'ef_search_{a.ef_search[0]}']['queries_per_s_two_streams'],
-                  'recall_at_10': res[f'ef_search_{a.ef_search[0]}']['recall_at_10'],
-                  'build_s': build_s, 'build_rows_per_s': N / build_s, 'mean_links_per_node': float(links.mean().item()),
+first = res[kinds[0]][f'ef_search_{a.ef_search[0]}']
+per_kind = {kind: {'build_s': build_s[kind], 'build_rows_per_s': N / build_s[kind],
+                   'row_column_bytes': N * D * indexes[kind]._vectors.element_size(), **res[kind]} for kind in kinds}
+print(json.dumps({'config': f'float HNSW (level 0, GPU-built): {N} x {D}-dim, graph rows {a.graph_rows}, L2, '
+                            f'max_connection={a.max_connection}, ef_construction={a.ef_construction}, batch {B}, k={k}, {n_seeds} seeds',
+                  'metric': 'queries/sec', 'unit': 'queries/s', 'value': first['queries_per_s_two_streams'],
+                  'recall_at_10': first['recall_at_10'], 'mean_links_per_node': float(links.mean().item()),
                   'flat_exact_queries_per_s_one_stream': flat_qps1, 'flat_exact_queries_per_s_two_streams': flat_qps2,
-                  'steps': max(a.steps, 2), 'query_batches': 2, **res}))
+                  'steps': max(a.steps, 2), 'query_batches': 2, **(per_kind if len(kinds) == 2 else per_kind[kinds[0]])}))
