@@ -35,8 +35,13 @@ class CellColumnMixin:
         # the reference assigns cells on the vectors as given (index.py:291-292, vq.py:81-90)
         raw = ops.to_dev(x, torch.float32)
         raw = raw.reshape(1, -1) if raw.ndim == 1 else raw
-        self._cell_of[ids_t] = self.vq_codec.encode(raw).to(torch.int32)
+        self._cell_of[ids_t] = self.vq_codec.encode(self._cell_vectors(raw)).to(torch.int32)
         self._sealed = False
+
+    def _cell_vectors(self, raw: torch.Tensor) -> torch.Tensor:
+        """What the cells are assigned from, f32 ``[n, dim]``: the vectors as given.  An index that stores its rows in another
+        precision overrides this with the vectors as it stores them."""
+        return raw
 
     def delete(self, ids):
         super().delete(ids)

@@ -43,25 +43,45 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         to that centroid and does not grow with a common offset of the data; INNER_PRODUCT and COSINE run it uncentred.  The centroids
         are the ``vq_codec``'s codebook as it is at the first ``add_with_ids``, frozen until ``reset()`` (``cell_centres_``).  The
         every-cell search, ``limit > 64`` and searches over at most 4096 probed rows are the same under either value.
+    :param ivf_rows: ``'f32'`` (default) or ``'f16'`` (opt-in): the cells over HALF-PRECISION rows.  The index is then the f16
+        ``FlatGpuIndex`` with the cell column beside it -- rows rounded once to nearest even, half the HBM, norms, validity and the
+        every-cell search from the f16 store -- and a pruned search runs the f16 MFMA filter over the cell tiles
+        (``last_cell_filter == 'f16x2'``; DESIGN.md section 3.7, "f16 rows over cell tiles").  The answer is, bit for bit, the f32
+        index's over the rounded rows: the cells are assigned from the given vectors ROUNDED to f16 as the store rounds them (COSINE
+        stores the normalised vector rounded; no f32 COSINE index holds such rows, the INNER_PRODUCT one does).  ``dim <= 32768``; neither
+        ``cell_filter='bf16x3'`` nor a ``centre`` (a common offset destroys f16 data before any filter sees it).  ``dtype=np.float16``
+        without the keyword stays refused.
     :param flat_filter, centre: the every-cell search's options in ``FlatGpuIndex``; accepted and ignored here (it stays ``'f32'``).
     """
     FORMAT = 'annlite_amd.IvfFlatGpuIndex/1'
     CELL_FILTERS = ('f32', 'bf16x3')
+    IVF_ROWS = ('f32', 'f16')
     # (a filter per query: one search_batch per group -- the pruned search stays the search it is under every selection)
     search_batch_grouped = RowStoreIndex.search_batch_grouped
 
     def __init__(self, dim: int, vq_codec: Optional[VQCodec] = None, n_probe: Optional[int] = None, metric: Metric = Metric.COSINE,
-                 cell_filter: str = 'f32', **kwargs):
+                 cell_filter: str = 'f32', ivf_rows: str = 'f32', **kwargs):
         assert vq_codec is not None, 'IvfFlatGpuIndex needs a VQCodec'
         if cell_filter not in self.CELL_FILTERS:
             raise ValueError(f"cell_filter={cell_filter!r}: 'f32' (the f32 MFMA filter over the cell tiles) or 'bf16x3' (the split-bf16 "
                              "filter, every tile centred on its cell's centroid)")
         if cell_filter == 'bf16x3' and dim > self.SPLIT_MAX_DIM:
             raise ValueError(f"cell_filter='bf16x3' takes dim <= {self.SPLIT_MAX_DIM}")
+        if ivf_rows not in self.IVF_ROWS:
+            raise ValueError(f"ivf_rows={ivf_rows!r}: 'f32' (default) or 'f16' (the cells over half-precision rows)")
+        centre = kwargs.get('centre', 'mean')
+        if ivf_rows == 'f16':
+            if cell_filter == 'bf16x3':
+                raise ValueError("cell_filter='bf16x3' splits f32 rows: ivf_rows='f16' runs the f16 filter over the cell tiles")
+            if not (isinstance(centre, str) and centre == 'mean'):
+                raise ValueError(f"centre={centre!r} with ivf_rows='f16': f16 rows have no centre (centre the data before adding it)")
+            if dim > self.SPLIT_MAX_DIM:
+                raise ValueError(f"ivf_rows='f16' takes dim <= {self.SPLIT_MAX_DIM}")
+        self.ivf_rows = ivf_rows
         self.vq_codec = vq_codec
         self.n_probe = n_probe  # None: every cell (the reference's behaviour)
         self.cell_filter = cell_filter
-        self.last_cell_filter = None  # 'f32' / 'bf16x3': the cell-tile filter of the last search_batch; None: it ran none
+        self.last_cell_filter = None  # 'f32' / 'bf16x3' / 'f16x2': the cell-tile filter of the last search_batch; None: it ran none
         self._cell_centred = cell_filter == 'bf16x3' and Metric(metric) == Metric.EUCLIDEAN
         self._cell_centres_dev = None
         self._stored_cell_centres = None  # (between `_load_state` and the end of `load`: the centres an index file carried)
@@ -70,12 +90,14 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         # (accepted and ignored: this index's every-cell search is the f32 one -- DESIGN.md section 10)
         kwargs.pop('flat_filter', None)
         kwargs.pop('centre', None)
-        if is_f16(kwargs.get('dtype', 'float32')):
-            raise NotImplementedError('dtype=np.float16: the cell-tile kernels read f32 rows only (half-precision rows exist in the '
-                                      'exhaustive FlatGpuIndex: no graph, n_cells=1)')
         if is_i8(kwargs.get('dtype', 'float32')):
-            raise NotImplementedError('dtype=np.int8: the cell-tile kernels read f32 rows only (int8 rows exist in the '
+            raise NotImplementedError('dtype=np.int8: the cell-tile kernels read f32 or f16 rows only (int8 rows exist in the '
                                       'exhaustive FlatGpuIndex: no graph, n_cells=1)')
+        if ivf_rows == 'f16':
+            kwargs['dtype'] = np.float16
+        elif is_f16(kwargs.get('dtype', 'float32')):
+            raise NotImplementedError("dtype=np.float16: the cell-tile kernels read f32 rows unless ivf_rows='f16' opts into the cells over "
+                                      'half-precision rows (they also exist in the exhaustive FlatGpuIndex: no graph, n_cells=1)')
         super().__init__(dim, metric=metric, **kwargs)
 
     # ------------------------------------------------------------------ the split filter's centres and its norms column
@@ -110,6 +132,11 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         if self._cell_centred:  # (after `_cell_of`: a row an update moved gets the norm against its new centroid)
             self._fix_cell_centres()
             ops.ivf_flat_centred_norms(self._vectors, self._cell_centres_dev, self._cell_of, ids=ids_t, out=self._cell_cnorms)
+
+    def _cell_vectors(self, raw):
+        """f16 rows: the cells come from the vectors rounded as the store rounds them, so that the index over f16 rows and the f32
+        index that is given the rounded vectors lay out the same cells"""
+        return raw.to(torch.float16).to(torch.float32) if self._f16 else raw
 
     def reset(self, capacity: Optional[int] = None):
         super().reset(capacity=capacity)
@@ -156,7 +183,8 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
                      large_k: Optional[str] = None):
         """``FlatGpuIndex.search_batch`` over the rows of each query's ``n_probe`` nearest cells (every cell: that search itself, with
         its ``filter_route``; the pruned search scans cell tiles under the bitmap whatever the route, and reports ``'mask'``).  ``large_k``:
-        as there; ``'wide'`` answers a pruned search with ``64 < limit <= 1024`` by ``annlite_ivf_flat_search_topk_wide``."""
+        as there; ``'wide'`` answers a pruned search with ``64 < limit <= 1024`` by ``annlite_ivf_flat_search_topk_wide`` (``_f16`` over f16
+        rows)."""
         large_k = self.large_k if large_k is None else self._check_large_k(large_k)
         P = self.n_probe if n_probe is None else n_probe
         C = self.n_cells
@@ -187,6 +215,12 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
                                                       n_rows=self._n_rows, sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
                 self._overflowed = None
                 self.last_cell_filter = 'bf16x3' if max_probed >= self.FILTER_MIN_ROWS else None
+            elif k <= 64 and self._f16:
+                d, i = ops.ivf_flat_search_topk_f16(int(self.metric), q, self._vectors, self._norms, cells, C, self._perm, self._cell_rows,
+                                                    self._cell_order, max_cell, max_probed, k, valid_bits=valid, n_rows=self._n_rows,
+                                                    sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
+                self._overflowed = None
+                self.last_cell_filter = 'f16x2' if max_probed >= self.FILTER_MIN_ROWS else None
             elif k <= 64:
                 d, i = ops.ivf_flat_search_topk(int(self.metric), q, self._vectors, self._norms, cells, C, self._perm, self._cell_rows,
                                                 self._cell_order, max_cell, max_probed, k, valid_bits=valid, n_rows=self._n_rows,

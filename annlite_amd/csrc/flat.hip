@@ -10,7 +10,7 @@
 // index, container.py:88-144) -- the filter over (cell, queries that probe it) tiles, the cells a permutation
 // of the row offsets.
 //
-// Six MFMA filter kernels (f32, split-bf16, f16 and int8 rows over the table; f32 and split-bf16 over cell tiles) differ in their
+// Seven MFMA filter kernels (f32, split-bf16, f16 and int8 rows over the table; f32, split-bf16 and f16 rows over cell tiles) differ in their
 // contraction and share the rest, each piece written once:
 //   flat_tile_rows / ivf_flat_tile_range + ivf_flat_tile_rows   the row tile's prologue: bounds, bitmap, norms
 //   flat_stage_planes                                            16-byte slots of 2-byte planes from HBM into an LDS stage
@@ -389,12 +389,13 @@ __global__ __launch_bounds__(256) void flat_split_queries_kernel(const float *__
 // One LDS stage of NP planes of 2-byte values (V: eight of them, one 16-byte slot; bf16 or f16): coordinates k0 .. k0 + kSplitDepth of
 // the tile's kFlatTile rows, plane p of row r from src[p] + row_at(r).off -- zeros at or past coordinate `lim` (a multiple of 8) and
 // for a slot that is not ok -- to dst[p] at pitch kSplitLd.  256 threads.
-template <class V, int NP, class E, class RowAt>
+// DEPTH: the coordinates of a stage, pitch DEPTH + 8 (kSplitDepth everywhere but in ivf_flat_f16_filter_kernel, which has a stage of its own).
+template <class V, int NP, int DEPTH = kSplitDepth, class E, class RowAt>
 __device__ __forceinline__ void flat_stage_planes(int tid, int k0, int lim, const E *const (&src)[NP], E *const (&dst)[NP], RowAt &&row_at) {
 #pragma unroll
-    for (int i = 0; i < kSplitDepth / 16; ++i) {
+    for (int i = 0; i < DEPTH / 16; ++i) {
         const int e = tid + i * 256;  // slots of 8 values per plane
-        const int r = e / (kSplitDepth / 8), c = (e % (kSplitDepth / 8)) * 8;
+        const int r = e / (DEPTH / 8), c = (e % (DEPTH / 8)) * 8;
         const FlatSlot s = row_at(r);
         V v[NP];
 #pragma unroll
@@ -407,9 +408,10 @@ __device__ __forceinline__ void flat_stage_planes(int tid, int k0, int lim, cons
             for (int p = 0; p < NP; ++p) v[p] = *(const V *)(src[p] + s.off + k0 + c);
         }
 #pragma unroll
-        for (int p = 0; p < NP; ++p) *(V *)(dst[p] + r * kSplitLd + c) = v[p];
+        for (int p = 0; p < NP; ++p) *(V *)(dst[p] + r * (DEPTH + 8) + c) = v[p];
     }
 }
+static_assert(kSplitLd == kSplitDepth + 8, "flat_stage_planes' pitch");
 
 // The split filter's K loop over one stage: the wave's 64 rows (from wr) x 64 queries (from wq), per K step of 16 the products h.h, h.l
 // and l.h on v_mfma_f32_32x32x16_bf16 -- twelve MFMAs; a K step of padding only ends the loop.  A macro, not a function like
@@ -1114,8 +1116,9 @@ __device__ __forceinline__ void ivf_flat_cell_range(int32_t cell, int C, const i
 }
 
 // flat_exact_kernel's `list == NULL` mode over the probed cells: exact sums of every stride-th entry of each of the query's P cells
-// (the first sample; all probed rows where they are few; the route of an overflowed query).
-__global__ __launch_bounds__(256) void ivf_flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const float *__restrict__ x,
+// (the first sample; all probed rows where they are few; the route of an overflowed query).  T: the row type, float or _Float16.
+template <class T>
+__global__ __launch_bounds__(256) void ivf_flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const T *__restrict__ x,
                                                             int64_t N, const int32_t *__restrict__ cells, int P, int C,
                                                             const int64_t *__restrict__ cell_rows, const int32_t *__restrict__ perm,
                                                             int64_t n_perm, int64_t stride, const uint32_t *__restrict__ valid, int k,
@@ -1527,6 +1530,105 @@ __global__ __launch_bounds__(256) void ivf_flat_split_filter_kernel(int metric, 
 #pragma unroll
             for (int ri = 0; ri < 2; ++ri)
                 flat_tile_epilogue<false, false>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh, [&](int reg) { return acc.tile(ri, qj)[reg]; }, row_of);
+        }
+    }
+}
+
+// ---- f16 rows over cell tiles ("f16 rows over cell tiles") -------------------------------------------------------
+// flat_f16_filter_kernel's contraction -- the rows as stored, the query as the two f16 planes of flat_f16_queries_kernel, two
+// v_mfma_f32_32x32x16_f16 per K step of 16 -- on ivf_flat_filter_kernel's grid, tile walk and rws / qss.  Nothing is centred, so the query
+// operands are BY QUERY (qh / ql f16 [B][Dp], qnorm / qscale / qflush f32 [B]) and written once per call, whatever the plan: a tile
+// gathers the planes of its slots through qss as it gathers its rows through perm.
+//
+// The stage has two depths, measured against each other.  A row gathered through perm is a scattered segment of
+// HBM, where the table kernels read rows back to back: DEPTH = 64 coordinates per stage make that segment one whole 128-byte line (eight
+// lanes, 16 bytes each) where 32 fetch half a line twice, and halve the barriers per row tile.  LDS: three planes (rows, q'_h, q'_l) of
+// 128 x (DEPTH + 8) f16 -- 55 296 bytes at DEPTH = 64, two workgroups per CU at either depth (registers).  Row pitch DEPTH + 8 f16: 144
+// bytes = 9 slots of 16 bytes at 64, 5 slots at 32; a lane reads the 8 coordinates 16 j + 8 (lane >> 5) .. of row lane & 31 as one
+// ds_read_b128; the 16 lanes that instruction serves together hold rows that are distinct mod 16, and 9 r mod 16 is a permutation as
+// 5 r is: every lane group covers the 64 banks once.
+// DEPTH = 32 -- the table kernel's stage -- measured 3 to 5 % FASTER per filter launch where the cells are long and level where they are
+// short: it is what the library launches.  DEPTH = 64 stays behind ANNLITE_IVF_F16_STAGE=64, the A/B switch of that measurement.
+// VEC: D % 8 == 0 and x aligned to 16 bytes; every other D stages single values.  scores != NULL (tests, measurements): as in
+// ivf_flat_split_filter_kernel, by (query, row offset).
+template <bool VEC, int DEPTH>
+__global__ __launch_bounds__(256) void ivf_flat_f16_filter_kernel(int metric, const _Float16 *__restrict__ qh, const _Float16 *__restrict__ ql,
+                                                                 int B, int D, int Dp, const _Float16 *__restrict__ x,
+                                                                 const float *__restrict__ norms, int64_t N,
+                                                                 const int32_t *__restrict__ perm, int64_t n_perm,
+                                                                 const int64_t *__restrict__ tile_rows, const int32_t *__restrict__ vmap,
+                                                                 int n_tiles, int64_t stride, const uint32_t *__restrict__ valid,
+                                                                 const float *__restrict__ qnorm, const float *__restrict__ qscale,
+                                                                 const float *__restrict__ qflush, const float *__restrict__ thr,
+                                                                 float c_rel, float c_abs, int32_t *__restrict__ cand,
+                                                                 int32_t *__restrict__ cnt, int cap, float *__restrict__ scores) {
+    static_assert(DEPTH == 32 || DEPTH == 64, "a stage is two or four K steps of 16");
+    constexpr int LD = DEPTH + 8;  // LDS row pitch in f16
+    __shared__ __attribute__((aligned(16))) _Float16 As[kFlatTile * LD];
+    __shared__ __attribute__((aligned(16))) _Float16 Bh[kFlatTile * LD];
+    __shared__ __attribute__((aligned(16))) _Float16 Bl[kFlatTile * LD];
+    __shared__ float nxs[kFlatTile];
+    __shared__ int rws[kFlatTile];
+    __shared__ int qss[kFlatTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
+    const int wr = (wave >> 1) * 64, wq = (wave & 1) * 64;
+    const int l31 = lane & 31, lh = lane >> 5;
+    const _Float16 *const xp[1] = {x}, *const qp[2] = {qh, ql};
+    _Float16 *const ap[1] = {As}, *const bp[2] = {Bh, Bl};
+    const auto row_of = [&](int rl) { return FlatRow{rws[rl] >= 0, rws[rl], rws[rl] >= 0, (int64_t)rws[rl]}; };
+    for (int t = blockIdx.y; t < n_tiles; t += gridDim.y) {
+        int64_t begin, S;
+        if (!ivf_flat_tile_range(tile_rows, t, n_perm, stride, begin, S) || r0 >= S) continue;  // (the workgroup's: no barrier is left behind)
+        __syncthreads();  // the previous tile's epilogue has read rws / nxs / qss
+        ivf_flat_tile_rows(tid, t, r0, S, begin, stride, perm, N, valid, norms, vmap, B, rws, nxs, qss);
+        FlatAcc acc;
+        acc.zero();
+        for (int k0 = 0; k0 < D; k0 += DEPTH) {
+            __syncthreads();  // the previous stage is consumed (first pass: the tile's rows and queries are written)
+            // rows: f16 gathered from HBM as they are -- DEPTH / 8 neighbouring lanes fetch DEPTH coordinates of one row
+            if constexpr (VEC) {
+                flat_stage_planes<f16x8, 1, DEPTH>(tid, k0, D, xp, ap, [&](int r) { return FlatSlot{rws[r] >= 0, (int64_t)rws[r] * D}; });
+            } else {
+                const int c = tid % DEPTH;  // (256 is a multiple of DEPTH: a thread stages one coordinate of every row it handles)
+#pragma unroll 4
+                for (int i = 0; i < DEPTH / 2; ++i) {
+                    const int r = (tid + i * 256) / DEPTH;  // single values
+                    const int rr = rws[r];
+                    As[r * LD + c] = (rr >= 0 && k0 + c < D) ? x[(int64_t)rr * D + k0 + c] : (_Float16)0.f;
+                }
+            }
+            // queries: the planes of the tile's slots, gathered by query (Dp is a multiple of 8 coordinates)
+            flat_stage_planes<f16x8, 2, DEPTH>(tid, k0, Dp, qp, bp, [&](int r) { return FlatSlot{qss[r] >= 0, (int64_t)qss[r] * Dp}; });
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < DEPTH; kk += 16) {
+                if (k0 + kk >= D) break;  // (K steps of padding only)
+                const int kc = kk + 8 * lh;
+                const f16x8 a0 = *(const f16x8 *)(As + (wr + l31) * LD + kc), a1 = *(const f16x8 *)(As + (wr + 32 + l31) * LD + kc);
+                const f16x8 b0h = *(const f16x8 *)(Bh + (wq + l31) * LD + kc), b0l = *(const f16x8 *)(Bl + (wq + l31) * LD + kc);
+                const f16x8 b1h = *(const f16x8 *)(Bh + (wq + 32 + l31) * LD + kc), b1l = *(const f16x8 *)(Bl + (wq + 32 + l31) * LD + kc);
+                acc.c00 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0h, acc.c00, 0, 0, 0);
+                acc.c01 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1h, acc.c01, 0, 0, 0);
+                acc.c10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0h, acc.c10, 0, 0, 0);
+                acc.c11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1h, acc.c11, 0, 0, 0);
+                acc.c00 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0l, acc.c00, 0, 0, 0);
+                acc.c01 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1l, acc.c01, 0, 0, 0);
+                acc.c10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0l, acc.c10, 0, 0, 0);
+                acc.c11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1l, acc.c11, 0, 0, 0);
+            }
+        }
+        // the accumulator back to the query's scale: that is this kernel's dot product
+#pragma unroll
+        for (int qj = 0; qj < 2; ++qj) {
+            const int qi = qss[wq + qj * 32 + l31];
+            if (qi < 0) continue;
+            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, qflush[qi], cand, cnt, cap, scores, N);
+            const float down = qscale[qi];
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri)
+                flat_tile_epilogue<true, false>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh,
+                                                [&](int reg) { return acc.tile(ri, qj)[reg] * down; }, row_of);
         }
     }
 }
@@ -2149,12 +2251,67 @@ static int ivf_flat_split_launch_filter(int metric, int64_t B, int64_t D, const 
     return launch_status("ivf_flat_split_filter_kernel");
 }
 
+// ---- the f16 filter's share of a cells workspace: the query planes, the scales and the flush terms BY QUERY (w.i.f.qnorm is the third
+// per-query column), behind the IvfFlatWs of the same (B, P, C) ----
+struct IvfFlatF16Ws {
+    IvfFlatWs i;
+    int64_t Dp;  // D rounded up to the MFMA's K step
+    _Float16 *qh, *ql;
+    float *qscale, *qflush;
+    size_t bytes;
+};
+static IvfFlatF16Ws ivf_flat_f16_carve(void *ws, int64_t B, int64_t P, int64_t C, int64_t D) {
+    IvfFlatF16Ws w;
+    w.i = ivf_flat_carve(ws, B, P, C);
+    w.Dp = (D + 15) / 16 * 16;
+    WsBump b{(char *)ws, w.i.bytes};
+    w.qh = b.take<_Float16>((size_t)B * w.Dp * 2);
+    w.ql = b.take<_Float16>((size_t)B * w.Dp * 2);
+    w.qscale = b.take<float>((size_t)B * 4);
+    w.qflush = b.take<float>((size_t)B * 4);
+    w.bytes = b.o;
+    return w;
+}
+
+// Per call: the queries' planes, norms, scales and flush terms -- no plan is needed for them.
+static int ivf_flat_f16_prepare(const float *q, int64_t B, int64_t D, const IvfFlatF16Ws &w, hipStream_t st) {
+    hipLaunchKernelGGL(flat_f16_queries_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, q, (int)B, (int)D, (int)w.Dp, w.qh, w.ql,
+                       w.i.f.qnorm, w.qscale, w.qflush);
+    return launch_status("flat_f16_queries_kernel");
+}
+
+// The stage holds 32 coordinates unless ANNLITE_IVF_F16_STAGE=64 asks for a whole line per gathered row (an A/B switch: common.h, Knobs).
+static int ivf_flat_f16_launch_filter(int metric, int64_t B, int64_t D, const _Float16 *x, const float *norms, int64_t N, const int32_t *perm,
+                                      int64_t n_perm, const IvfFlatF16Ws &w, int64_t max_cell_rows, int64_t stride, const uint32_t *valid,
+                                      const float *thr, int32_t *cand, int32_t *cnt, float *scores, hipStream_t st) {
+    float c_rel, c_abs;
+    flat_f16_slack(metric, D, &c_rel, &c_abs);
+    const dim3 grid = ivf_flat_filter_grid(max_cell_rows, stride, w.i.n_tiles);
+    if (grid.x == 0 || grid.y == 0) return ANNLITE_OK;
+    const bool vec = D % 8 == 0 && ((uintptr_t)x % 16 == 0);
+    const int depth = knobs().ivf_f16_stage == 64 ? 64 : 32;
+#define IVF_FLAT_F16_LAUNCH(VEC, DEPTH)                                                                                                            \
+    hipLaunchKernelGGL((ivf_flat_f16_filter_kernel<VEC, DEPTH>), grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, norms, N, \
+                       perm, n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, valid, w.i.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs,  \
+                       cand, cnt, kFlatCap, scores)
+    if (depth == 64) {
+        if (vec) IVF_FLAT_F16_LAUNCH(true, 64);
+        else IVF_FLAT_F16_LAUNCH(false, 64);
+    } else {
+        if (vec) IVF_FLAT_F16_LAUNCH(true, 32);
+        else IVF_FLAT_F16_LAUNCH(false, 32);
+    }
+#undef IVF_FLAT_F16_LAUNCH
+    return launch_status("ivf_flat_f16_filter_kernel");
+}
+
 // ---- the stages of a search over cells, shared by annlite_ivf_flat_search_topk and
 // annlite_ivf_flat_search_topk_split: the exact-only shortcut, the plan, the first exact sample, the filter stages, the re-rank of the
 // lists and the route of an overflowed list.  prepare(): what the filter needs from the queries, once per call, after the plan;
 // filter(stride): one filter launch into w.f.cand / w.f.cnt against the bounds w.f.thr. ----
-template <class Prepare, class Filter>
-static int ivf_flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
+// T: the row type (float, _Float16) of vectors_dev, which only the exact stages read here.
+template <class T, class Prepare, class Filter>
+static int ivf_flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const T *vectors_dev, int64_t N,
                                   const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C, const int32_t *perm_dev,
                                   int64_t n_perm, const int64_t *cell_rows_dev, const int32_t *cell_order_dev, int64_t max_probed_rows,
                                   int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, const IvfFlatWs &w, hipStream_t st,
@@ -2163,7 +2320,7 @@ static int ivf_flat_search_staged(int metric, const float *queries_dev, int64_t 
     const dim3 qgrid((unsigned)((B + 3) / 4));
     ANNLITE_HIP_TRY(hipMemsetAsync(w.f.ovf_total, 0, 256, st));
     auto exact_cells = [&](int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
-        hipLaunchKernelGGL(ivf_flat_exact_kernel, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, cells_dev, (int)P,
+        hipLaunchKernelGGL(ivf_flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, cells_dev, (int)P,
                            (int)C, cell_rows_dev, perm_dev, n_perm, stride, valid_bits_dev, (int)k, sqrt_out, only_overflowed, thr_out,
                            out_dist_dev, out_id_dev, w.f.ovf);
         return launch_status("ivf_flat_exact_kernel");
@@ -2183,7 +2340,7 @@ static int ivf_flat_search_staged(int metric, const float *queries_dev, int64_t 
         ANNLITE_HIP_TRY(hipMemsetAsync(w.f.cnt, 0, (size_t)B * 4, st));
         if ((rc = filter(strides[s])) != ANNLITE_OK) return rc;
         // the list re-rank of annlite_flat_search_topk, unchanged: the lists hold offsets
-        hipLaunchKernelGGL(flat_exact_kernel<float>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.f.cand, w.f.cnt,
+        hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.f.cand, w.f.cnt,
                            kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0,
                            last ? nullptr : w.f.thr, out_dist_dev, out_id_dev, w.f.ovf, w.f.ovf_total);
         if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
@@ -2602,4 +2759,90 @@ extern "C" int annlite_ivf_flat_search_topk_split(int metric, const float *queri
             return ivf_flat_split_launch_filter(metric, B, D, vectors_dev, centres_dev, C, cell_of_dev, norms_dev, N, perm_dev, n_perm, w,
                                                 max_cell_rows, stride, valid_bits_dev, w.i.f.thr, w.i.f.cand, w.i.f.cnt, nullptr, st);
         });
+}
+
+// ---- f16 rows over cell tiles ("f16 rows over cell tiles") -------------------------------------------------------
+static int ivf_flat_f16_check_cells(int64_t B, int64_t P, int64_t C, int64_t N, int64_t n_perm, int64_t max_cell_rows, int64_t max_probed_rows) {
+    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && B * P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
+                        max_cell_rows <= n_perm && max_probed_rows >= 0,
+                    "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld max_probed_rows=%lld", (long long)P, (long long)C,
+                    (long long)n_perm, (long long)max_cell_rows, (long long)max_probed_rows);
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_ivf_flat_search_f16_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t D, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    ANNLITE_REQUIRE(B >= 0 && P >= 1 && C >= 1 && D >= 1 && D <= kSplitMaxDim && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
+                    (long long)kSplitMaxDim);
+    *bytes = (int64_t)ivf_flat_f16_carve(nullptr, B, P, C, D).bytes;
+    return ANNLITE_OK;
+}
+
+extern "C" int annlite_ivf_flat_filter_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                                           const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev,
+                                           int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                           const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t stride,
+                                           float *query_norms_out_dev, float *query_flush_out_dev, const float *bounds_dev,
+                                           int32_t *cand_dev, int32_t *count_dev, float *scores_dev, void *workspace_dev,
+                                           size_t workspace_bytes, void *stream) {
+    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
+    if (int rc = ivf_flat_f16_check_cells(B, P, C, N, n_perm, max_cell_rows, 0)) return rc;
+    if (B == 0 || n_perm == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && vectors_f16_dev && norms_dev && perm_dev && cells_dev && cell_rows_dev && cell_order_dev && bounds_dev &&
+                        cand_dev && count_dev && workspace_dev,
+                    "null device pointer");
+    const IvfFlatF16Ws w = ivf_flat_f16_carve(workspace_dev, B, P, C, D);
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = annlite_ivf_plan(cells_dev, B, P, C, kFlatTile, cell_rows_dev, cell_order_dev, w.i.n_tiles, w.i.vmap, w.i.slot_of, w.i.tile_rows,
+                              w.i.n_used, stream);
+    if (rc != ANNLITE_OK) return rc;
+    if ((rc = ivf_flat_f16_prepare(queries_dev, B, D, w, st)) != ANNLITE_OK) return rc;
+    rc = ivf_flat_f16_launch_filter(metric, B, D, (const _Float16 *)vectors_f16_dev, norms_dev, N, perm_dev, n_perm, w, max_cell_rows, stride,
+                                    valid_bits_dev, bounds_dev, cand_dev, count_dev, scores_dev, st);
+    if (rc != ANNLITE_OK) return rc;
+    if ((rc = flat_hand_back(query_norms_out_dev, w.i.f.qnorm, B, st)) != ANNLITE_OK) return rc;
+    return flat_hand_back(query_flush_out_dev, w.qflush, B, st);
+}
+
+extern "C" int annlite_ivf_flat_search_topk_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                                                const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev,
+                                                int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                                const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t max_probed_rows, int64_t k,
+                                                int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
+                                                size_t workspace_bytes, void *stream) {
+    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
+    if (int rc = ivf_flat_f16_check_cells(B, P, C, N, n_perm, max_cell_rows, max_probed_rows)) return rc;
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && cells_dev && cell_rows_dev && cell_order_dev &&
+                        (n_perm == 0 || (vectors_f16_dev && norms_dev && perm_dev)),
+                    "null device pointer");
+    const IvfFlatF16Ws w = ivf_flat_f16_carve(workspace_dev, B, P, C, D);
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const _Float16 *x = (const _Float16 *)vectors_f16_dev;
+    return ivf_flat_search_staged(
+        metric, queries_dev, B, D, x, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev, cell_order_dev, max_probed_rows, k,
+        flags, out_dist_dev, out_id_dev, w.i, st, [&]() { return ivf_flat_f16_prepare(queries_dev, B, D, w, st); },
+        [&](int64_t stride) {
+            return ivf_flat_f16_launch_filter(metric, B, D, x, norms_dev, N, perm_dev, n_perm, w, max_cell_rows, stride, valid_bits_dev, w.i.f.thr,
+                                              w.i.f.cand, w.i.f.cnt, nullptr, st);
+        });
+}
+
+extern "C" int annlite_ivf_flat_search_topk_wide_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                                                     int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C,
+                                                     const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k,
+                                                     int flags, float *out_dist_dev, int64_t *out_id_dev, void *stream) {
+    if (int rc = flat_check_shape(kFlatSearchWide, metric, B, D, N, k, kSplitMaxDim)) return rc;
+    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && P <= INT32_MAX && n_perm >= 0 && n_perm <= N, "bad cells P=%lld C=%lld n_perm=%lld",
+                    (long long)P, (long long)C, (long long)n_perm);
+    if (B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && cells_dev && cell_rows_dev && (n_perm == 0 || (vectors_f16_dev && perm_dev)),
+                    "null device pointer");
+    const WideCells src{cells_dev, (int)P, (int)C, cell_rows_dev, perm_dev, n_perm, 0};
+    hipLaunchKernelGGL((flat_exact_wide_kernel<_Float16, WideCells>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, metric, queries_dev,
+                       (int)D, (const _Float16 *)vectors_f16_dev, N, src, valid_bits_dev, (int)k, (flags & ANNLITE_FLAG_SQRT) ? 1 : 0,
+                       (float *)nullptr, out_dist_dev, out_id_dev, 1.f);
+    return launch_status("flat_exact_wide_kernel");
 }

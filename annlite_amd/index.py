@@ -285,7 +285,8 @@ class AnnLite:
             if graph:  # (build='gpu', n_cells == 1: the constructor refuses the rest)
                 from .core.index.hnsw_flat_gpu import HnswFlatGpuIndex
 
-                kw.pop('cell_filter', None)  # (the cells' option)
+                kw.pop('cell_filter', None)  # (the cells' options)
+                kw.pop('ivf_rows', None)
 
                 return HnswFlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
             kw.pop('build', None)
@@ -295,11 +296,12 @@ class AnnLite:
                 from .core.index.ivf_flat_gpu import IvfFlatGpuIndex
 
                 return IvfFlatGpuIndex(dim=self._index_dim, metric=self.metric, vq_codec=self._vq_codec, n_probe=self._n_probe_arg, **kw)
-            kw.pop('cell_filter', None)  # (the cells' option)
+            kw.pop('cell_filter', None)  # (the cells' options)
+            kw.pop('ivf_rows', None)
             return FlatGpuIndex(dim=self._index_dim, metric=self.metric, **kw)
         if not (self._vq_codec is None and kw.get('graph')):
             kw.pop('filter_search', None)  # (the graph indexes' option: the other indexes over PQ codes answer a filter exactly)
-        for name in ('flat_filter', 'centre', 'cell_filter', 'int8_scale', 'filter_route', 'large_k', 'graph_rows'):  # (the float indexes' options: nothing over PQ codes runs that filter)
+        for name in ('flat_filter', 'centre', 'cell_filter', 'int8_scale', 'filter_route', 'large_k', 'graph_rows', 'ivf_rows'):  # (the float indexes' options: nothing over PQ codes runs that filter)
             kw.pop(name, None)
         if self._devices is not None and len(self._devices) > 1 and (self._vq_codec is not None or kw.get('graph')):
             warnings.warn('devices= is ignored for n_cells > 1 and graph=True indexes (they live on the current device)')

@@ -1188,6 +1188,52 @@ def ivf_flat_search_topk_split(metric: int, queries: torch.Tensor, vectors: torc
     return od, oi
 
 
+def ivf_flat_filter_f16(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
+                        cells: torch.Tensor, n_cells: int, perm: torch.Tensor, cell_rows: torch.Tensor, cell_order: torch.Tensor,
+                        max_cell_rows: int, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, stride: int = 1,
+                        scores: bool = False, workspace: Optional[ScanWorkspace] = None):
+    """``annlite_ivf_flat_filter_f16``: the f16 filter stage over the (cell, queries) tiles alone -- ``flat_filter_f16`` of the cells
+    (``vectors`` f16 [N, D], ``norms``: ``flat_row_norms_f16``).  ``(cand i32 [B, cap], count i32 [B], query_norms f32 [B], query_flush
+    f32 [B])`` -- the last two as the filter used them -- and, with ``scores=True``, the filter's score by (query, row offset), f32
+    [B, N]: NaN where the filter evaluated nothing (cell not probed, row not valid, row not at the stride)."""
+    assert vectors.dtype == torch.float16
+    B, D = queries.shape
+    P = cells.shape[1]
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    ws = _flat_workspace('ivf_flat_search_f16_workspace_bytes', (B, P, n_cells, D, 1), dev, workspace)
+    cand, count, sc = _flat_lists(B, dev, N if scores else None)
+    qn, qf = (torch.empty((B,), dtype=torch.float32, device=dev) for _ in range(2))
+    check(lib().annlite_ivf_flat_filter_f16(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
+                                            cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
+                                            cell_order.data_ptr(), int(max_cell_rows), int(stride), qn.data_ptr(), qf.data_ptr(),
+                                            bounds.data_ptr(), cand.data_ptr(), count.data_ptr(), _ptr(sc), ws.data_ptr(), ws.numel(),
+                                            stream_ptr()), 'ivf_flat_filter_f16')
+    return (cand, count, qn, qf, sc) if scores else (cand, count, qn, qf)
+
+
+def ivf_flat_search_topk_f16(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, cells: torch.Tensor,
+                             n_cells: int, perm: torch.Tensor, cell_rows: torch.Tensor, cell_order: torch.Tensor, max_cell_rows: int,
+                             max_probed_rows: int, k: int, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
+                             sqrt: bool = False, workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_ivf_flat_search_topk_f16``: ``ivf_flat_search_topk`` over ``vectors`` f16 [N, D] (``norms``: ``flat_row_norms_f16``) with
+    the f16 filter over the cell tiles: the answer of ``ivf_flat_search_topk`` over the widened rows, bit for bit.
+    ``flat_overflow_count`` / ``flat_list_counts`` read this workspace too."""
+    assert vectors.dtype == torch.float16
+    B, D = queries.shape
+    P = cells.shape[1]
+    N = vectors.shape[0] if n_rows is None else n_rows
+    dev = queries.device
+    ws = _flat_workspace('ivf_flat_search_f16_workspace_bytes', (B, P, n_cells, D, k), dev, workspace)
+    od, oi = _flat_topk_outputs(B, k, dev)
+    check(lib().annlite_ivf_flat_search_topk_f16(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
+                                                 cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
+                                                 cell_order.data_ptr(), int(max_cell_rows), int(max_probed_rows), int(k), 1 if sqrt else 0,
+                                                 od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()),
+          'ivf_flat_search_topk_f16')
+    return od, oi
+
+
 # ---------------------------------------------------------------------------------------------- PCA projector
 def _row_stride(t: torch.Tensor, what: str) -> int:
     assert t.dim() == 2 and t.dtype == torch.float32, f'{what} must be a 2-D float32 tensor'
@@ -1453,11 +1499,13 @@ def ivf_flat_search_topk_wide(metric: int, queries: torch.Tensor, vectors: torch
                               sqrt: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """``annlite_ivf_flat_search_topk_wide``: exact k nearest (``64 < k <= 1024``) among the rows of each query's probed ``cells`` i32
     [B, P] (``perm`` / ``cell_rows`` as ``ivf_flat_search_topk``), one launch: ``(dist f32 [B, k], ids i64 [B, k])`` ascending by
-    (distance, id), (+inf, -1) padded."""
+    (distance, id), (+inf, -1) padded.  ``vectors`` f16: ``annlite_ivf_flat_search_topk_wide_f16``, the same over the widened rows."""
     B, D = queries.shape
     N = vectors.shape[0] if n_rows is None else n_rows
     od, oi = _flat_topk_outputs(B, k, queries.device)
-    check(lib().annlite_ivf_flat_search_topk_wide(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, _ptr(valid_bits), cells.data_ptr(),
-                                                  cells.shape[1], int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(), int(k),
-                                                  1 if sqrt else 0, od.data_ptr(), oi.data_ptr(), stream_ptr()), 'ivf_flat_search_topk_wide')
+    assert vectors.dtype in (torch.float32, torch.float16)
+    entry = 'ivf_flat_search_topk_wide' + ('_f16' if vectors.dtype == torch.float16 else '')
+    check(getattr(lib(), 'annlite_' + entry)(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, _ptr(valid_bits), cells.data_ptr(),
+                                             cells.shape[1], int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(), int(k),
+                                             1 if sqrt else 0, od.data_ptr(), oi.data_ptr(), stream_ptr()), entry)
     return od, oi

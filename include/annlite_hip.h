@@ -799,6 +799,33 @@ ANNLITE_API int annlite_ivf_flat_search_topk_split(int metric, const float *quer
                                        const float *centres_dev, const int32_t *cell_of_dev, int64_t k, int flags, float *out_dist_dev,
                                        int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* The same search over f16 ROWS ("f16 rows over cell tiles"): vectors_f16_dev f16 [N][D] as
+ * annlite_flat_search_topk_f16 reads them, norms_dev = annlite_flat_row_norms_f16.  The filter stage is annlite_flat_search_topk_f16's
+ * contraction -- the rows as stored, the query as two f16 planes, two f16 MFMAs -- over the (cell, queries) tiles, the rows gathered a
+ * 128-byte line at a time; the exact stages read the f16 rows in annlite_exact_gather_dist_f16's arithmetic.  The answer is
+ * annlite_ivf_flat_search_topk's over the rows widened to f32, bit for bit.  1 <= D <= 32768.  No reference counterpart. */
+ANNLITE_API int annlite_ivf_flat_search_f16_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t D, int64_t k, int64_t *bytes);
+/* The f16 filter stage alone (tests and measurements): the annlite_flat_filter_f16 of the cells.  The call plans the tiles, writes the
+ * query planes into the workspace (annlite_ivf_flat_search_f16_workspace_bytes of the same B, P, C, D) and filters every stride-th entry
+ * of each probed cell against bounds_dev f32 [B].  cand_dev i32 [B][capacity] / count_dev i32 [B] (zeroed by the caller) as
+ * annlite_flat_filter; query_norms_out_dev / query_flush_out_dev (may be NULL) f32 [B] receive |q|^2 and the per-query term of the slack
+ * as the filter used them; scores_dev (may be NULL) f32 [B][N] receives the filter's score v by (query, row offset) for every pair it
+ * evaluated -- a row that is not valid or not probed keeps the caller's value. */
+ANNLITE_API int annlite_ivf_flat_filter_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                                const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P,
+                                int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t stride, float *query_norms_out_dev,
+                                float *query_flush_out_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
+                                float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* annlite_ivf_flat_search_topk over f16 rows: the same stages, lists, capacity and overflow route (annlite_flat_overflow_count and
+ * annlite_flat_list_counts read this workspace too). */
+ANNLITE_API int annlite_ivf_flat_search_topk_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                                     const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev,
+                                     int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                     const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t max_probed_rows, int64_t k,
+                                     int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
+                                     void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * limit above 64 ("limit above 64"): the exact searches above for 64 < k <= 1024.  A workgroup per query scores
  * its candidates in the arithmetic of every exact stage (the distances of annlite_flat_search_topk / annlite_exact_gather_dist, bit
@@ -822,6 +849,11 @@ ANNLITE_API int annlite_ivf_flat_search_topk_wide(int metric, const float *queri
                                       int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C,
                                       const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k, int flags,
                                       float *out_dist_dev, int64_t *out_id_dev, void *stream);
+/* ... over f16 rows (vectors_f16_dev f16 [N][D]): annlite_ivf_flat_search_topk_wide's answer over the widened rows, bit for bit. */
+ANNLITE_API int annlite_ivf_flat_search_topk_wide_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
+                                          int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C,
+                                          const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k, int flags,
+                                          float *out_dist_dev, int64_t *out_id_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pruned (IVF) search over cells (follow-on of rank 4).

@@ -7,6 +7,11 @@ profiles/ivf_flat/bench_ivf_flat.jsonl.
     python scripts/bench_ivf_flat.py --rows 10000000 --data lowrank    # the low-rank data of tests/test_ivf.py::_data
     python scripts/bench_ivf_flat.py --filter both                     # cell_filter='f32' against 'bf16x3' 
     python scripts/bench_ivf_flat.py --filter both --offset 1000       # ... on data with a common offset
+    python scripts/bench_ivf_flat.py --ivf-rows both                   # f32 rows against ivf_rows='f16' ("f16 rows")
+
+--ivf-rows both (the row count owns --rows): the f32 index, the index over f16 rows, and that same index with the filter's 64-coordinate
+stage (ANNLITE_IVF_F16_STAGE=64, path 'f16/stage64') alternate round by round.  The f16 paths hold other rows than the f32 path -- the
+rounded ones -- so their answers are compared with each other, and their recall is reported per path.
 
 --filter both: two indexes over the same rows and the same codebook, one per cell filter; the paths alternate round by round in this
 process.  The top-level `pruned_*` / `list_*` / `overflowed_queries` keys describe the first path (`filter`); `paths` holds, per filter
@@ -16,7 +21,8 @@ Recall: against the exhaustive search's answer, which is exact.  Filter time: th
 (ivf_flat_filter_kernel / ivf_flat_split_filter_kernel) in one search, from the profiler's kernel records (null where the profiler
 records no kernels); `pruned_search_kernels` lists every kernel of that search as (launches, ms).
 """
-FILTER_KERNEL = {'f32': 'ivf_flat_filter_kernel', 'bf16x3': 'ivf_flat_split_filter_kernel'}
+FILTER_KERNEL = {'f32': 'ivf_flat_filter_kernel', 'bf16x3': 'ivf_flat_split_filter_kernel', 'f16': 'ivf_flat_f16_filter_kernel',
+                 'f16/stage64': 'ivf_flat_f16_filter_kernel'}
 import argparse
 import json
 import os
@@ -40,6 +46,7 @@ def main():
     ap.add_argument('--probe', type=int, default=16)
     ap.add_argument('--data', default='normal', choices=['normal', 'lowrank'])
     ap.add_argument('--filter', default='f32', choices=['f32', 'bf16x3', 'both'], help='cell_filter of the pruned path(s)')
+    ap.add_argument('--ivf-rows', default='f32', choices=['f32', 'f16', 'both'], help="ivf_rows of the pruned path(s); not with --filter bf16x3 / both")
     ap.add_argument('--offset', type=float, default=0.0, help='added to rows, training rows and queries')
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--steps', type=int, default=5, help='batches per round and path')
@@ -48,7 +55,7 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from annlite_amd import ops
+    from annlite_amd import _capi, ops
     from annlite_amd.core.codec.vq import VQCodec
     from annlite_amd.core.index.flat_gpu import FlatGpuIndex
     from annlite_amd.core.index.ivf_flat_gpu import IvfFlatGpuIndex
@@ -75,10 +82,15 @@ def main():
     vq.fit(first[:args.train_rows].contiguous())
     filters = ['f32', 'bf16x3'] if args.filter == 'both' else [args.filter]
     paths = {f: IvfFlatGpuIndex(D, vq_codec=vq, n_probe=P, metric=metric, initial_size=N, cell_filter=f) for f in filters}
+    if args.ivf_rows != 'f32':
+        assert args.filter == 'f32', "--ivf-rows f16 / both runs the f16 filter: not with --filter bf16x3 / both"
+        half = IvfFlatGpuIndex(D, vq_codec=vq, n_probe=P, metric=metric, initial_size=N, ivf_rows='f16')
+        paths = {**(paths if args.ivf_rows == 'both' else {}), 'f16': half, 'f16/stage64': half}
+        filters = list(paths)
     for r0 in range(0, N, step):
         n = min(step, N - r0)
         chunk = first if r0 == 0 else draw(n)
-        for p in paths.values():
+        for p in {id(p): p for p in paths.values()}.values():
             p.add_with_ids(chunk, torch.arange(r0, r0 + n, device=dev))
     del first, chunk
     idx = paths[filters[0]]
@@ -86,6 +98,12 @@ def main():
 
     def exhaustive():
         return FlatGpuIndex.search_batch(idx, q, limit=k)
+
+    def stage(f):  # the library reads the switch when it is told to: the f16 paths differ in it alone
+        os.environ.pop('ANNLITE_IVF_F16_STAGE', None)
+        if f == 'f16/stage64':
+            os.environ['ANNLITE_IVF_F16_STAGE'] = '64'
+        _capi.knobs_reload()
 
     def timed(fn):
         fn()
@@ -104,10 +122,13 @@ def main():
         ms_e.append(t)
         over_e = idx.last_overflowed
         for f in filters:
+            stage(f)
             t, answers[f] = timed(lambda: paths[f].search_batch(q, limit=k))
             ms_p[f].append(t)
-    for f in filters[1:]:  # (the filters differ in what they list, never in the answer)
-        assert torch.equal(answers[f][1], answers[filters[0]][1]) and torch.equal(answers[f][0], answers[filters[0]][0]), f
+    for f in filters[1:]:  # (the filters differ in what they list, never in the answer; the f16 paths answer over other rows than f32's)
+        same = 'f16' if f == 'f16/stage64' else filters[0]
+        if f != 'f16':
+            assert torch.equal(answers[f][1], answers[same][1]) and torch.equal(answers[f][0], answers[same][0]), f
     dp, ip = answers[filters[0]]
     sizes = (idx._cell_rows[:, 1] - idx._cell_rows[:, 0]).cpu().numpy()
     max_probed = int(idx._sizes_cum[P - 1])
@@ -140,6 +161,7 @@ def main():
     report = {}
     for f in filters:
         p = paths[f]
+        stage(f)
         p.search_batch(q, limit=k)
         count = ops.flat_list_counts(p._ws, B).cpu().numpy()
         filter_ms, kernels = one_search(p, f)
@@ -147,7 +169,10 @@ def main():
         report[f] = {'ms_per_batch': round(med, 4), 'qps': round(B / med * 1e3, 1), 'ms_rounds': [round(v, 4) for v in ms_p[f]],
                      'filter_kernel': FILTER_KERNEL[f], 'filter_kernel_ms': filter_ms, 'kernels': kernels,
                      'list_mean': round(float(count.mean()), 1), 'list_max': int(count.max()), 'overflowed_queries': int(p.last_overflowed),
-                     'last_cell_filter': p.last_cell_filter}
+                     'last_cell_filter': p.last_cell_filter,
+                     'recall_at_k_vs_exhaustive': round(float(np.mean([len(set(a) & set(e)) / k for a, e in
+                                                                        zip(answers[f][1].cpu().numpy(), ie.cpu().numpy())])), 4)}
+    stage(None)
     main_path = report[filters[0]]
     ms_p, filter_ms, kernels = ms_p[filters[0]], main_path['filter_kernel_ms'], main_path['kernels']
 
@@ -155,7 +180,7 @@ def main():
     recall = float(np.mean([len(set(ip_np[b]) & set(ie_np[b])) / k for b in range(B)]))
     med_p, med_e = statistics.median(ms_p), statistics.median(ms_e)
     line = json.dumps({
-        'bench': 'ivf_flat_f32', 'filter': filters[0], 'offset': args.offset, 'rows': N, 'dim': D, 'batch': B, 'k': k, 'metric': 'euclidean', 'data': args.data, 'n_cells': C, 'n_probe': P,
+        'bench': 'ivf_flat_f32', 'filter': filters[0], 'ivf_rows': args.ivf_rows, 'offset': args.offset, 'rows': N, 'dim': D, 'batch': B, 'k': k, 'metric': 'euclidean', 'data': args.data, 'n_cells': C, 'n_probe': P,
         'rounds': args.rounds, 'steps': args.steps,
         'pruned_ms_per_batch': round(med_p, 4), 'pruned_qps': round(B / med_p * 1e3, 1), 'pruned_ms_rounds': [round(v, 4) for v in ms_p],
         'exhaustive_ms_per_batch': round(med_e, 4), 'exhaustive_qps': round(B / med_e * 1e3, 1),
