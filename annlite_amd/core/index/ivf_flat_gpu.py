@@ -206,27 +206,13 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
             valid = self._valid if indices is None else self._filter_bits(indices)
             cells = self.probe_cells(q, P)
             max_cell, max_probed = int(self._sizes_cum[0]), int(self._sizes_cum[P - 1])
-            if k <= 64 and self.cell_filter == 'bf16x3':
-                d, i = ops.ivf_flat_search_topk_split(int(self.metric), q, self._vectors,
-                                                      self._cell_cnorms if self._cell_centred else self._norms, cells, C, self._perm,
-                                                      self._cell_rows, self._cell_order, max_cell, max_probed, k,
-                                                      centres=self._cell_centres_dev if self._cell_centred else None,
-                                                      cell_of=self._cell_of if self._cell_centred else None, valid_bits=valid,
-                                                      n_rows=self._n_rows, sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
-                self._overflowed = None
-                self.last_cell_filter = 'bf16x3' if max_probed >= self.FILTER_MIN_ROWS else None
-            elif k <= 64 and self._f16:
-                d, i = ops.ivf_flat_search_topk_f16(int(self.metric), q, self._vectors, self._norms, cells, C, self._perm, self._cell_rows,
-                                                    self._cell_order, max_cell, max_probed, k, valid_bits=valid, n_rows=self._n_rows,
-                                                    sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)
-                self._overflowed = None
-                self.last_cell_filter = 'f16x2' if max_probed >= self.FILTER_MIN_ROWS else None
-            elif k <= 64:
-                d, i = ops.ivf_flat_search_topk(int(self.metric), q, self._vectors, self._norms, cells, C, self._perm, self._cell_rows,
-                                                self._cell_order, max_cell, max_probed, k, valid_bits=valid, n_rows=self._n_rows,
-                                                sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws)  # hnsw/index.py:164-165
+            if k <= 64:
+                name, search, norms, centres = self._cell_tile_filter()
+                d, i = search(int(self.metric), q, self._vectors, norms, cells, C, self._perm, self._cell_rows, self._cell_order, max_cell,
+                              max_probed, k, valid_bits=valid, n_rows=self._n_rows, sqrt=self.metric == Metric.EUCLIDEAN, workspace=self._ws,
+                              **centres)  # hnsw/index.py:164-165
                 self._overflowed = None  # (read from the workspace when asked for: it costs a synchronisation)
-                self.last_cell_filter = 'f32' if max_probed >= self.FILTER_MIN_ROWS else None
+                self.last_cell_filter = name if max_probed >= self.FILTER_MIN_ROWS else None
             elif large_k == 'wide' and k <= self.WIDE_MAX_K:
                 d, i = ops.ivf_flat_search_topk_wide(int(self.metric), q, self._vectors, cells, C, self._perm, self._cell_rows, k, valid_bits=valid,
                                                      n_rows=self._n_rows, sqrt=self.metric == Metric.EUCLIDEAN)
@@ -235,6 +221,17 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
                 d, i = self._search_large_k_cells(q, k, valid, cells, max_probed)
                 self.last_large_k = 'host'
         return like_input(is_np, d, i)
+
+    def _cell_tile_filter(self):
+        """The cell-tile filter of a pruned search with ``limit <= 64``: its name in ``last_cell_filter``, its ``ops`` search, its norms
+        column and the keywords only it takes (the split filter's centres, where it has them)."""
+        if self.cell_filter == 'bf16x3':
+            if self._cell_centred:
+                return 'bf16x3', ops.ivf_flat_search_topk_split, self._cell_cnorms, dict(centres=self._cell_centres_dev, cell_of=self._cell_of)
+            return 'bf16x3', ops.ivf_flat_search_topk_split, self._norms, {}
+        if self._f16:
+            return 'f16x2', ops.ivf_flat_search_topk_f16, self._norms, {}
+        return 'f32', ops.ivf_flat_search_topk, self._norms, {}
 
     def _probed_rows(self, cells: torch.Tensor, R: int):
         """``(cand i64 [b, R], ok bool [b, R])``: every query's probed rows as one dense block -- the ranges of its cells in

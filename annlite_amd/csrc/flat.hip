@@ -2147,8 +2147,30 @@ static int flat_with_wide_filter(int filter, Fn &&fn) {
     return flat_with_filter(filter, fn);
 }
 
-// ---- cells: workspace, stages, launchers ---------------------------------------------------------------------------------------------
+// ---- cells: one call's operands, the workspaces, one description per cell-tile filter ("the host routine") ----
 constexpr int kIvfFlatMaxStages = 16;  // strides annlite_ivf_flat_stages can return (2^31 rows: 19 bits of stride, 5 at a time, + the first)
+
+struct IvfFlatCall {
+    int metric;
+    const float *q;
+    int64_t B, D;
+    const void *x;  // [N][D] of the filter's row type
+    const float *norms;
+    int64_t N;
+    const uint32_t *valid;
+    const int32_t *cells;  // [B][P] probed cells, below C
+    int64_t P, C;
+    const int32_t *perm;  // n_perm live offsets grouped by cell
+    int64_t n_perm;
+    const int64_t *cell_rows;
+    const int32_t *cell_order;
+    // the largest cell, and the most rows a query probes.  0 from the entries that take none: the wide searches (both), the stages
+    // (max_probed_rows) -- which is how ivf_flat_check leaves them unchecked there.
+    int64_t max_cell_rows, max_probed_rows;
+    const float *centres;  // [C][D], with cell_of [N]: the bf16x3 entries alone have them, NULL from the others
+    const int32_t *cell_of;
+    hipStream_t st;
+};
 
 struct IvfFlatWs {
     FlatWs f;  // (first: annlite_flat_overflow_count reads the same counter)
@@ -2192,19 +2214,6 @@ static int ivf_flat_strides(int64_t M, int64_t *strides) {
     return n;
 }
 
-static int ivf_flat_launch_filter(int metric, const float *q, int64_t B, int64_t D, const float *x, const float *norms, int64_t N,
-                                  const int32_t *perm, int64_t n_perm, const IvfFlatWs &w, int64_t max_cell_rows, int64_t stride,
-                                  const uint32_t *valid, hipStream_t st) {
-    float c_rel, c_abs;
-    flat_slack(metric, D, &c_rel, &c_abs);
-    const dim3 grid = ivf_flat_filter_grid(max_cell_rows, stride, w.n_tiles);
-    if (grid.x == 0 || grid.y == 0) return ANNLITE_OK;
-    const bool vec = D % 4 == 0 && ((uintptr_t)q % 16 == 0) && ((uintptr_t)x % 16 == 0);
-    FLAT_LAUNCH_VEC(vec, ivf_flat_filter_kernel, grid, dim3(256), st, metric, q, (int)B, (int)D, x, norms, N, perm, n_perm, w.tile_rows, w.vmap,
-                    (int)w.n_tiles, stride, valid, w.f.qnorm, w.f.thr, c_rel, c_abs, w.f.cand, w.f.cnt, kFlatCap);
-    return launch_status("ivf_flat_filter_kernel");
-}
-
 // ---- the split filter's share of a cells workspace: the query planes and the pair norms BY PLAN SLOT, behind the IvfFlatWs of the same
 // (B, P, C) (so that the overflow counter and the list counters sit where annlite_flat_overflow_count / annlite_flat_list_counts read
 // them) ----
@@ -2215,44 +2224,8 @@ struct IvfFlatSplitWs {
     float *qnorm;
     size_t bytes;
 };
-static IvfFlatSplitWs ivf_flat_split_carve(void *ws, int64_t B, int64_t P, int64_t C, int64_t D) {
-    IvfFlatSplitWs w;
-    w.i = ivf_flat_carve(ws, B, P, C);
-    w.Dp = (D + 15) / 16 * 16;
-    w.n_slots = w.i.n_tiles * kFlatTile;
-    WsBump b{(char *)ws, w.i.bytes};
-    w.qh = b.take<__bf16>((size_t)w.n_slots * w.Dp * 2);
-    w.ql = b.take<__bf16>((size_t)w.n_slots * w.Dp * 2);
-    w.qnorm = b.take<float>((size_t)w.n_slots * 4);
-    w.bytes = b.o;
-    return w;
-}
-
-// Per call, after the plan: centre and split the queries of every pair into its slot's planes.
-static int ivf_flat_split_prepare(const float *q, int64_t B, int64_t P, int64_t C, int64_t D, const int32_t *cells, const float *centres,
-                                  const IvfFlatSplitWs &w, float *pair_norms, hipStream_t st) {
-    hipLaunchKernelGGL(ivf_flat_split_queries_kernel, dim3((unsigned)((B * P + 3) / 4)), dim3(256), 0, st, q, (int)(B * P), (int)P, (int)D,
-                       (int)w.Dp, cells, (int)C, centres, w.i.slot_of, (int)w.n_slots, w.qh, w.ql, w.qnorm, pair_norms);
-    return launch_status("ivf_flat_split_queries_kernel");
-}
-
-static int ivf_flat_split_launch_filter(int metric, int64_t B, int64_t D, const float *x, const float *centres, int64_t C,
-                                        const int32_t *cell_of, const float *norms, int64_t N, const int32_t *perm, int64_t n_perm,
-                                        const IvfFlatSplitWs &w, int64_t max_cell_rows, int64_t stride, const uint32_t *valid,
-                                        const float *thr, int32_t *cand, int32_t *cnt, float *scores, hipStream_t st) {
-    float c_rel, c_abs;
-    flat_split_slack(metric, D, &c_rel, &c_abs);
-    const dim3 grid = ivf_flat_filter_grid(max_cell_rows, stride, w.i.n_tiles);
-    if (grid.x == 0 || grid.y == 0) return ANNLITE_OK;
-    const bool vec = D % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)centres % 16 == 0);
-    FLAT_LAUNCH_VEC(vec, ivf_flat_split_filter_kernel, grid, dim3(256), st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, centres, (int)C,
-                    cell_of, norms, N, perm, n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, valid, w.qnorm, thr, c_rel, c_abs, cand,
-                    cnt, kFlatCap, scores);
-    return launch_status("ivf_flat_split_filter_kernel");
-}
-
-// ---- the f16 filter's share of a cells workspace: the query planes, the scales and the flush terms BY QUERY (w.i.f.qnorm is the third
-// per-query column), behind the IvfFlatWs of the same (B, P, C) ----
+// ---- the f16 filter's share: the query planes, the scales and the flush terms BY QUERY (the FlatWs's qnorm is the third per-query
+// column), behind the IvfFlatWs of the same (B, P, C) ----
 struct IvfFlatF16Ws {
     IvfFlatWs i;
     int64_t Dp;  // D rounded up to the MFMA's K step
@@ -2260,93 +2233,245 @@ struct IvfFlatF16Ws {
     float *qscale, *qflush;
     size_t bytes;
 };
-static IvfFlatF16Ws ivf_flat_f16_carve(void *ws, int64_t B, int64_t P, int64_t C, int64_t D) {
-    IvfFlatF16Ws w;
-    w.i = ivf_flat_carve(ws, B, P, C);
-    w.Dp = (D + 15) / 16 * 16;
-    WsBump b{(char *)ws, w.i.bytes};
-    w.qh = b.take<_Float16>((size_t)B * w.Dp * 2);
-    w.ql = b.take<_Float16>((size_t)B * w.Dp * 2);
-    w.qscale = b.take<float>((size_t)B * 4);
-    w.qflush = b.take<float>((size_t)B * 4);
-    w.bytes = b.o;
-    return w;
-}
 
-// Per call: the queries' planes, norms, scales and flush terms -- no plan is needed for them.
-static int ivf_flat_f16_prepare(const float *q, int64_t B, int64_t D, const IvfFlatF16Ws &w, hipStream_t st) {
-    hipLaunchKernelGGL(flat_f16_queries_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, q, (int)B, (int)D, (int)w.Dp, w.qh, w.ql,
-                       w.i.f.qnorm, w.qscale, w.qflush);
-    return launch_status("flat_f16_queries_kernel");
-}
-
-// The stage holds 32 coordinates unless ANNLITE_IVF_F16_STAGE=64 asks for a whole line per gathered row (an A/B switch: common.h, Knobs).
-static int ivf_flat_f16_launch_filter(int metric, int64_t B, int64_t D, const _Float16 *x, const float *norms, int64_t N, const int32_t *perm,
-                                      int64_t n_perm, const IvfFlatF16Ws &w, int64_t max_cell_rows, int64_t stride, const uint32_t *valid,
-                                      const float *thr, int32_t *cand, int32_t *cnt, float *scores, hipStream_t st) {
-    float c_rel, c_abs;
-    flat_f16_slack(metric, D, &c_rel, &c_abs);
-    const dim3 grid = ivf_flat_filter_grid(max_cell_rows, stride, w.i.n_tiles);
-    if (grid.x == 0 || grid.y == 0) return ANNLITE_OK;
-    const bool vec = D % 8 == 0 && ((uintptr_t)x % 16 == 0);
-    const int depth = knobs().ivf_f16_stage == 64 ? 64 : 32;
-#define IVF_FLAT_F16_LAUNCH(VEC, DEPTH)                                                                                                            \
-    hipLaunchKernelGGL((ivf_flat_f16_filter_kernel<VEC, DEPTH>), grid, dim3(256), 0, st, metric, w.qh, w.ql, (int)B, (int)D, (int)w.Dp, x, norms, N, \
-                       perm, n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, valid, w.i.f.qnorm, w.qscale, w.qflush, thr, c_rel, c_abs,  \
-                       cand, cnt, kFlatCap, scores)
-    if (depth == 64) {
-        if (vec) IVF_FLAT_F16_LAUNCH(true, 64);
-        else IVF_FLAT_F16_LAUNCH(false, 64);
-    } else {
-        if (vec) IVF_FLAT_F16_LAUNCH(true, 32);
-        else IVF_FLAT_F16_LAUNCH(false, 32);
+// What a cell-tile filter is to the host: its row type, its largest D, whether its entries bound the (query, cell) pairs B P or P alone
+// (kBoundPairs, see ivf_flat_check), its workspace (base(): the IvfFlatWs at its head), prepare() -- what the filter needs from the
+// queries, once per call, AFTER the plan -- and launch(), one filter stage over every stride-th row of the plan's tiles (grid:
+// ivf_flat_filter's) into cand / cnt against the bounds thr.  A new cell-tile filter is one such struct, its entries and its size entry.
+struct IvfF32 {
+    using Row = float;
+    using Ws = IvfFlatWs;
+    static constexpr int64_t kMaxDim = INT32_MAX;
+    static constexpr bool kBoundPairs = false;
+    static Ws carve(void *ws, int64_t B, int64_t P, int64_t C, int64_t) { return ivf_flat_carve(ws, B, P, C); }
+    static const IvfFlatWs &base(const Ws &w) { return w; }
+    static int prepare(const IvfFlatCall &c, const Ws &w, float *) {
+        return annlite_flat_row_norms(c.q, c.B, c.D, nullptr, c.B, 0, w.f.qnorm, (void *)c.st);
     }
+    static int launch(const IvfFlatCall &c, const Ws &w, dim3 grid, int64_t stride, const float *thr, int32_t *cand, int32_t *cnt, float *) {
+        float c_rel, c_abs;
+        flat_slack(c.metric, c.D, &c_rel, &c_abs);
+        const Row *x = (const Row *)c.x;
+        const bool vec = c.D % 4 == 0 && ((uintptr_t)c.q % 16 == 0) && ((uintptr_t)x % 16 == 0);
+        FLAT_LAUNCH_VEC(vec, ivf_flat_filter_kernel, grid, dim3(256), c.st, c.metric, c.q, (int)c.B, (int)c.D, x, c.norms, c.N, c.perm, c.n_perm,
+                        w.tile_rows, w.vmap, (int)w.n_tiles, stride, c.valid, w.f.qnorm, thr, c_rel, c_abs, cand, cnt, kFlatCap);
+        return launch_status("ivf_flat_filter_kernel");
+    }
+};
+struct IvfBf16x3 {
+    using Row = float;
+    using Ws = IvfFlatSplitWs;
+    static constexpr int64_t kMaxDim = kSplitMaxDim;
+    static constexpr bool kBoundPairs = true;
+    static Ws carve(void *ws, int64_t B, int64_t P, int64_t C, int64_t D) {
+        Ws w;
+        w.i = ivf_flat_carve(ws, B, P, C);
+        w.Dp = (D + 15) / 16 * 16;
+        w.n_slots = w.i.n_tiles * kFlatTile;
+        WsBump b{(char *)ws, w.i.bytes};
+        w.qh = b.take<__bf16>((size_t)w.n_slots * w.Dp * 2);
+        w.ql = b.take<__bf16>((size_t)w.n_slots * w.Dp * 2);
+        w.qnorm = b.take<float>((size_t)w.n_slots * 4);
+        w.bytes = b.o;
+        return w;
+    }
+    static const IvfFlatWs &base(const Ws &w) { return w.i; }
+    // Centre and split the queries of every pair into its slot's planes.  pair_norms (may be NULL): |fl(q - mu)|^2 by (query, probe) as
+    // well -- the workspace holds them by plan slot, so the stage entry's hand-back is written here and not copied afterwards.
+    static int prepare(const IvfFlatCall &c, const Ws &w, float *pair_norms) {
+        hipLaunchKernelGGL(ivf_flat_split_queries_kernel, dim3((unsigned)((c.B * c.P + 3) / 4)), dim3(256), 0, c.st, c.q, (int)(c.B * c.P), (int)c.P,
+                           (int)c.D, (int)w.Dp, c.cells, (int)c.C, c.centres, w.i.slot_of, (int)w.n_slots, w.qh, w.ql, w.qnorm, pair_norms);
+        return launch_status("ivf_flat_split_queries_kernel");
+    }
+    static int launch(const IvfFlatCall &c, const Ws &w, dim3 grid, int64_t stride, const float *thr, int32_t *cand, int32_t *cnt, float *scores) {
+        float c_rel, c_abs;
+        flat_split_slack(c.metric, c.D, &c_rel, &c_abs);
+        const Row *x = (const Row *)c.x;
+        const bool vec = c.D % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)c.centres % 16 == 0);
+        FLAT_LAUNCH_VEC(vec, ivf_flat_split_filter_kernel, grid, dim3(256), c.st, c.metric, w.qh, w.ql, (int)c.B, (int)c.D, (int)w.Dp, x, c.centres,
+                        (int)c.C, c.cell_of, c.norms, c.N, c.perm, c.n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, c.valid, w.qnorm, thr,
+                        c_rel, c_abs, cand, cnt, kFlatCap, scores);
+        return launch_status("ivf_flat_split_filter_kernel");
+    }
+};
+struct IvfF16x2 {
+    using Row = _Float16;
+    using Ws = IvfFlatF16Ws;
+    static constexpr int64_t kMaxDim = kSplitMaxDim;
+    static constexpr bool kBoundPairs = true;
+    static Ws carve(void *ws, int64_t B, int64_t P, int64_t C, int64_t D) {
+        Ws w;
+        w.i = ivf_flat_carve(ws, B, P, C);
+        w.Dp = (D + 15) / 16 * 16;
+        WsBump b{(char *)ws, w.i.bytes};
+        w.qh = b.take<_Float16>((size_t)B * w.Dp * 2);
+        w.ql = b.take<_Float16>((size_t)B * w.Dp * 2);
+        w.qscale = b.take<float>((size_t)B * 4);
+        w.qflush = b.take<float>((size_t)B * 4);
+        w.bytes = b.o;
+        return w;
+    }
+    static const IvfFlatWs &base(const Ws &w) { return w.i; }
+    // The queries' planes, norms, scales and flush terms -- no plan is needed for them.
+    static int prepare(const IvfFlatCall &c, const Ws &w, float *) {
+        hipLaunchKernelGGL(flat_f16_queries_kernel, dim3((unsigned)((c.B + 3) / 4)), dim3(256), 0, c.st, c.q, (int)c.B, (int)c.D, (int)w.Dp, w.qh,
+                           w.ql, w.i.f.qnorm, w.qscale, w.qflush);
+        return launch_status("flat_f16_queries_kernel");
+    }
+    // The stage holds 32 coordinates unless ANNLITE_IVF_F16_STAGE=64 asks for a whole line per gathered row (an A/B switch: common.h, Knobs).
+    static int launch(const IvfFlatCall &c, const Ws &w, dim3 grid, int64_t stride, const float *thr, int32_t *cand, int32_t *cnt, float *scores) {
+        float c_rel, c_abs;
+        flat_f16_slack(c.metric, c.D, &c_rel, &c_abs);
+        const Row *x = (const Row *)c.x;
+        const bool vec = c.D % 8 == 0 && ((uintptr_t)x % 16 == 0);
+        const int depth = knobs().ivf_f16_stage == 64 ? 64 : 32;
+#define IVF_FLAT_F16_LAUNCH(VEC, DEPTH)                                                                                                          \
+    hipLaunchKernelGGL((ivf_flat_f16_filter_kernel<VEC, DEPTH>), grid, dim3(256), 0, c.st, c.metric, w.qh, w.ql, (int)c.B, (int)c.D, (int)w.Dp, x, \
+                       c.norms, c.N, c.perm, c.n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, c.valid, w.i.f.qnorm, w.qscale,         \
+                       w.qflush, thr, c_rel, c_abs, cand, cnt, kFlatCap, scores)
+        if (depth == 64) {
+            if (vec) IVF_FLAT_F16_LAUNCH(true, 64);
+            else IVF_FLAT_F16_LAUNCH(false, 64);
+        } else {
+            if (vec) IVF_FLAT_F16_LAUNCH(true, 32);
+            else IVF_FLAT_F16_LAUNCH(false, 32);
+        }
 #undef IVF_FLAT_F16_LAUNCH
-    return launch_status("ivf_flat_f16_filter_kernel");
+        return launch_status("ivf_flat_f16_filter_kernel");
+    }
+};
+
+// What every cells entry asks of the shape (what / arg: as flat_check_shape has them), of the cells and of the centres.  Two things are
+// kept per entry, as each entry has always had them:
+//   the pairs -- the searches and the stages of IvfBf16x3 and IvfF16x2 (F::kBoundPairs) bound the (query, cell) pairs B P; the f32 search
+//   and the two wide searches, of either row type, bound P alone;
+//   max_cell_rows / max_probed_rows -- checked where the entry takes them (IvfFlatCall).
+template <class F>
+static int ivf_flat_check(FlatEntry what, const IvfFlatCall &c, int64_t arg) {
+    if (int rc = flat_check_shape(what, c.metric, c.B, c.D, c.N, arg, F::kMaxDim)) return rc;
+    const bool pairs = F::kBoundPairs && what != kFlatSearchWide;
+    ANNLITE_REQUIRE(c.P >= 1 && c.C >= 1 && c.C <= 16384 && (pairs ? c.B == 0 || c.P <= INT32_MAX / c.B : c.P <= INT32_MAX) && c.n_perm >= 0 &&
+                        c.n_perm <= c.N && c.max_cell_rows >= 0 && c.max_cell_rows <= c.n_perm && c.max_probed_rows >= 0,
+                    "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld max_probed_rows=%lld", (long long)c.P, (long long)c.C,
+                    (long long)c.n_perm, (long long)c.max_cell_rows, (long long)c.max_probed_rows);
+    ANNLITE_REQUIRE(!c.centres || c.metric == ANNLITE_METRIC_EUCLIDEAN, "centres are for EUCLIDEAN only");
+    ANNLITE_REQUIRE(!c.centres || c.cell_of, "centres need cell_of_dev");
+    return ANNLITE_OK;
 }
 
-// ---- the stages of a search over cells, shared by annlite_ivf_flat_search_topk and
-// annlite_ivf_flat_search_topk_split: the exact-only shortcut, the plan, the first exact sample, the filter stages, the re-rank of the
-// lists and the route of an overflowed list.  prepare(): what the filter needs from the queries, once per call, after the plan;
-// filter(stride): one filter launch into w.f.cand / w.f.cnt against the bounds w.f.thr. ----
-// T: the row type (float, _Float16) of vectors_dev, which only the exact stages read here.
-template <class T, class Prepare, class Filter>
-static int ivf_flat_search_staged(int metric, const float *queries_dev, int64_t B, int64_t D, const T *vectors_dev, int64_t N,
-                                  const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C, const int32_t *perm_dev,
-                                  int64_t n_perm, const int64_t *cell_rows_dev, const int32_t *cell_order_dev, int64_t max_probed_rows,
-                                  int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, const IvfFlatWs &w, hipStream_t st,
-                                  Prepare &&prepare, Filter &&filter) {
+// The (cell, queries that probe it) tiles of the filter stages, into the workspace.
+static int ivf_flat_plan(const IvfFlatCall &c, const IvfFlatWs &w) {
+    return annlite_ivf_plan(c.cells, c.B, c.P, c.C, kFlatTile, c.cell_rows, c.cell_order, w.n_tiles, w.vmap, w.slot_of, w.tile_rows, w.n_used,
+                            (void *)c.st);
+}
+// One filter stage of F over the plan's tiles; nothing is launched where the grid is empty.
+template <class F>
+static int ivf_flat_filter(const IvfFlatCall &c, const typename F::Ws &fw, int64_t stride, const float *thr, int32_t *cand, int32_t *cnt,
+                           float *scores) {
+    const dim3 grid = ivf_flat_filter_grid(c.max_cell_rows, stride, F::base(fw).n_tiles);
+    if (grid.x == 0 || grid.y == 0) return ANNLITE_OK;
+    return F::launch(c, fw, grid, stride, thr, cand, cnt, scores);
+}
+
+// ---- the stages of a search over cells, the same for every cell-tile filter F: the exact-only shortcut, the
+// plan, F::prepare, the first exact sample, the filter stages (into w.cand / w.cnt against the bounds w.thr), the re-rank of the lists
+// and the route of an overflowed list.  fw: F's carved workspace.  The exact stages alone read the rows here. ----
+template <class F>
+static int ivf_flat_search_staged(F, const IvfFlatCall &c, const typename F::Ws &fw, int64_t k, int flags, float *out_dist_dev,
+                                  int64_t *out_id_dev) {
+    using T = typename F::Row;
+    const IvfFlatWs &iw = F::base(fw);
+    const FlatWs &w = iw.f;
+    const T *x = (const T *)c.x;
+    hipStream_t st = c.st;
     const int do_sqrt = (flags & ANNLITE_FLAG_SQRT) ? 1 : 0;
-    const dim3 qgrid((unsigned)((B + 3) / 4));
-    ANNLITE_HIP_TRY(hipMemsetAsync(w.f.ovf_total, 0, 256, st));
+    const dim3 qgrid((unsigned)((c.B + 3) / 4));
+    ANNLITE_HIP_TRY(hipMemsetAsync(w.ovf_total, 0, 256, st));
     auto exact_cells = [&](int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
-        hipLaunchKernelGGL(ivf_flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, cells_dev, (int)P,
-                           (int)C, cell_rows_dev, perm_dev, n_perm, stride, valid_bits_dev, (int)k, sqrt_out, only_overflowed, thr_out,
-                           out_dist_dev, out_id_dev, w.f.ovf);
+        hipLaunchKernelGGL(ivf_flat_exact_kernel<T>, qgrid, dim3(256), 0, st, c.metric, c.q, (int)c.B, (int)c.D, x, c.N, c.cells, (int)c.P, (int)c.C,
+                           c.cell_rows, c.perm, c.n_perm, stride, c.valid, (int)k, sqrt_out, only_overflowed, thr_out, out_dist_dev, out_id_dev,
+                           w.ovf);
         return launch_status("ivf_flat_exact_kernel");
     };
     int64_t strides[kIvfFlatMaxStages];
-    const int n_strides = ivf_flat_strides(max_probed_rows, strides);
+    const int n_strides = ivf_flat_strides(c.max_probed_rows, strides);
     if (n_strides == 0) return exact_cells(1, do_sqrt, 0, nullptr);  // few probed rows: exact sums over all of them
-    // the (cell, queries that probe it) tiles of the filter stages
-    int rc = annlite_ivf_plan(cells_dev, B, P, C, kFlatTile, cell_rows_dev, cell_order_dev, w.n_tiles, w.vmap, w.slot_of, w.tile_rows, w.n_used,
-                              (void *)st);
+    int rc = ivf_flat_plan(c, iw);
     if (rc != ANNLITE_OK) return rc;
-    if ((rc = prepare()) != ANNLITE_OK) return rc;
+    if ((rc = F::prepare(c, fw, nullptr)) != ANNLITE_OK) return rc;
     // stage 0: the k-th smallest exact distance among every strides[0]-th entry of the query's cells
-    if ((rc = exact_cells(strides[0], 0, 0, w.f.thr)) != ANNLITE_OK) return rc;
+    if ((rc = exact_cells(strides[0], 0, 0, w.thr)) != ANNLITE_OK) return rc;
     for (int s = 1; s < n_strides; ++s) {
         const bool last = s == n_strides - 1;  // (strides[n_strides - 1] == 1)
-        ANNLITE_HIP_TRY(hipMemsetAsync(w.f.cnt, 0, (size_t)B * 4, st));
-        if ((rc = filter(strides[s])) != ANNLITE_OK) return rc;
+        ANNLITE_HIP_TRY(hipMemsetAsync(w.cnt, 0, (size_t)c.B * 4, st));
+        if ((rc = ivf_flat_filter<F>(c, fw, strides[s], w.thr, w.cand, w.cnt, nullptr)) != ANNLITE_OK) return rc;
         // the list re-rank of annlite_flat_search_topk, unchanged: the lists hold offsets
-        hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, metric, queries_dev, (int)B, (int)D, vectors_dev, N, w.f.cand, w.f.cnt,
-                           kFlatCap, (int64_t)0, (int64_t)1, valid_bits_dev, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0,
-                           last ? nullptr : w.f.thr, out_dist_dev, out_id_dev, w.f.ovf, w.f.ovf_total);
+        hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, c.metric, c.q, (int)c.B, (int)c.D, x, c.N, w.cand, w.cnt, kFlatCap,
+                           (int64_t)0, (int64_t)1, c.valid, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr, out_dist_dev,
+                           out_id_dev, w.ovf, w.ovf_total);
         if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
     }
     // queries whose last list overflowed: exact sums over all their probed rows (the other waves leave at once)
     return exact_cells(1, do_sqrt, 1, nullptr);
+}
+
+// ---- the one body behind the three search entries, the one behind the two stage entries, the one behind the two wide entries and the
+// one behind the three size entries ----
+template <class F>
+static int ivf_flat_search(const IvfFlatCall &c, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
+                           size_t workspace_bytes) {
+    if (int rc = ivf_flat_check<F>(kFlatSearch, c, k)) return rc;
+    if (c.B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(c.q && out_dist_dev && out_id_dev && workspace_dev && c.cells && c.cell_rows && c.cell_order &&
+                        (c.n_perm == 0 || (c.x && c.norms && c.perm)),
+                    "null device pointer");
+    const typename F::Ws w = F::carve(workspace_dev, c.B, c.P, c.C, c.D);
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
+    return ivf_flat_search_staged(F{}, c, w, k, flags, out_dist_dev, out_id_dev);
+}
+
+// One filter stage over the (cell, queries) tiles alone, into the caller's lists: the plan, F::prepare (pair_norms_dev: see
+// IvfBf16x3::prepare) and the stage.  *used (where asked for): the carved workspace, for the entry that hands back what prepare() left per query; it is
+// left alone where the call is refused or has nothing to do.
+template <class F>
+static int ivf_flat_stage(const IvfFlatCall &c, int64_t stride, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
+                          float *pair_norms_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes, typename F::Ws *used = nullptr) {
+    if (int rc = ivf_flat_check<F>(kFlatStage, c, stride)) return rc;
+    if (c.B == 0 || c.n_perm == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(c.q && c.x && c.norms && c.perm && c.cells && c.cell_rows && c.cell_order && bounds_dev && cand_dev && count_dev &&
+                        workspace_dev,
+                    "null device pointer");
+    const typename F::Ws w = F::carve(workspace_dev, c.B, c.P, c.C, c.D);
+    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
+    if (int rc = ivf_flat_plan(c, F::base(w))) return rc;
+    if (int rc = F::prepare(c, w, pair_norms_dev)) return rc;
+    if (used) *used = w;
+    return ivf_flat_filter<F>(c, w, stride, bounds_dev, cand_dev, count_dev, scores_dev);
+}
+
+// 64 < k <= 1024 over the probed cells: one launch of the wide kernel over each query's P ranges -- no plan, no filter, no workspace.
+// Of F, the row type and the largest D alone.
+template <class F>
+static int ivf_flat_search_wide(const IvfFlatCall &c, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev) {
+    using T = typename F::Row;
+    if (int rc = ivf_flat_check<F>(kFlatSearchWide, c, k)) return rc;
+    if (c.B == 0) return ANNLITE_OK;
+    ANNLITE_REQUIRE(c.q && out_dist_dev && out_id_dev && c.cells && c.cell_rows && (c.n_perm == 0 || (c.x && c.perm)), "null device pointer");
+    const WideCells src{c.cells, (int)c.P, (int)c.C, c.cell_rows, c.perm, c.n_perm, 0};
+    hipLaunchKernelGGL((flat_exact_wide_kernel<T, WideCells>), dim3((unsigned)c.B), dim3(256), 0, c.st, c.metric, c.q, (int)c.D, (const T *)c.x, c.N,
+                       src, c.valid, (int)k, (flags & ANNLITE_FLAG_SQRT) ? 1 : 0, (float *)nullptr, out_dist_dev, out_id_dev, 1.f);
+    return launch_status("flat_exact_wide_kernel");
+}
+
+// The workspace of a search or a stage: the filter's own carve.  The size entries have never bounded B, P and C from above as the
+// searches do, and keep accepting what they accepted.  D: 1 from the f32 entry, which takes none.
+template <class F>
+static int ivf_flat_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t D, int64_t k, int64_t *bytes) {
+    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
+    ANNLITE_REQUIRE(B >= 0 && P >= 1 && C >= 1 && D >= 1 && D <= F::kMaxDim && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
+                    (long long)F::kMaxDim);
+    *bytes = (int64_t)F::carve(nullptr, B, P, C, D).bytes;
+    return ANNLITE_OK;
 }
 
 }  // namespace annlite
@@ -2628,11 +2753,9 @@ extern "C" int annlite_ivf_flat_stages(int64_t max_probed_rows, int64_t *strides
     return ANNLITE_OK;
 }
 
+// ---- cells: each entry fills the operands of the call, names its cell-tile filter and forwards -----------------
 extern "C" int annlite_ivf_flat_search_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    ANNLITE_REQUIRE(B >= 0 && P >= 1 && C >= 1 && k >= 1 && k <= 64, "bad shape (1 <= k <= 64)");
-    *bytes = (int64_t)ivf_flat_carve(nullptr, B, P, C).bytes;
-    return ANNLITE_OK;
+    return ivf_flat_workspace_bytes<IvfF32>(B, P, C, 1, k, bytes);
 }
 
 extern "C" int annlite_ivf_flat_search_topk(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
@@ -2641,47 +2764,21 @@ extern "C" int annlite_ivf_flat_search_topk(int metric, const float *queries_dev
                                             const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t max_probed_rows, int64_t k,
                                             int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
                                             size_t workspace_bytes, void *stream) {
-    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, INT32_MAX)) return rc;
-    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
-                        max_cell_rows <= n_perm && max_probed_rows >= 0,
-                    "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld max_probed_rows=%lld", (long long)P, (long long)C,
-                    (long long)n_perm, (long long)max_cell_rows, (long long)max_probed_rows);
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && cells_dev && cell_rows_dev && cell_order_dev &&
-                        (n_perm == 0 || (vectors_dev && norms_dev && perm_dev)),
-                    "null device pointer");
-    const IvfFlatWs w = ivf_flat_carve(workspace_dev, B, P, C);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return ivf_flat_search_staged(
-        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev, cell_order_dev,
-        max_probed_rows, k, flags, out_dist_dev, out_id_dev, w, st,
-        [&]() { return annlite_flat_row_norms(queries_dev, B, D, nullptr, B, 0, w.f.qnorm, stream); },
-        [&](int64_t stride) {
-            return ivf_flat_launch_filter(metric, queries_dev, B, D, vectors_dev, norms_dev, N, perm_dev, n_perm, w, max_cell_rows, stride,
-                                          valid_bits_dev, st);
-        });
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_dev, norms_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        cell_order_dev, max_cell_rows, max_probed_rows, nullptr, nullptr, (hipStream_t)stream};
+    return ivf_flat_search<IvfF32>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
 }
 
-// ---- the split filter over cell tiles ---------------------------------------------------------------------------------------------------
-// 64 < k <= 1024 over the probed cells: one launch of the wide kernel over each query's P ranges -- no plan, no filter, no workspace.
 extern "C" int annlite_ivf_flat_search_topk_wide(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev, int64_t N,
                                                  const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C,
                                                  const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k, int flags,
                                                  float *out_dist_dev, int64_t *out_id_dev, void *stream) {
-    if (int rc = flat_check_shape(kFlatSearchWide, metric, B, D, N, k, INT32_MAX)) return rc;
-    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && P <= INT32_MAX && n_perm >= 0 && n_perm <= N, "bad cells P=%lld C=%lld n_perm=%lld",
-                    (long long)P, (long long)C, (long long)n_perm);
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && cells_dev && cell_rows_dev && (n_perm == 0 || (vectors_dev && perm_dev)),
-                    "null device pointer");
-    const WideCells src{cells_dev, (int)P, (int)C, cell_rows_dev, perm_dev, n_perm, 0};
-    hipLaunchKernelGGL((flat_exact_wide_kernel<float, WideCells>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, metric, queries_dev, (int)D,
-                       vectors_dev, N, src, valid_bits_dev, (int)k, (flags & ANNLITE_FLAG_SQRT) ? 1 : 0, (float *)nullptr, out_dist_dev, out_id_dev,
-                       1.f);
-    return launch_status("flat_exact_wide_kernel");
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_dev, nullptr, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        nullptr, 0, 0, nullptr, nullptr, (hipStream_t)stream};
+    return ivf_flat_search_wide<IvfF32>(c, k, flags, out_dist_dev, out_id_dev);
 }
 
+// ---- the split filter over cell tiles ---------------------------------------------------------------------------------------------------
 extern "C" int annlite_ivf_flat_centred_norms(const float *vectors_dev, int64_t capacity, int64_t D, const int64_t *ids_dev, int64_t n,
                                               int64_t id_base, const float *centres_dev, int64_t C, const int32_t *cell_of_dev,
                                               float *norms_dev, void *stream) {
@@ -2694,11 +2791,7 @@ extern "C" int annlite_ivf_flat_centred_norms(const float *vectors_dev, int64_t 
 }
 
 extern "C" int annlite_ivf_flat_search_split_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t D, int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    ANNLITE_REQUIRE(B >= 0 && P >= 1 && C >= 1 && D >= 1 && D <= kSplitMaxDim && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
-                    (long long)kSplitMaxDim);
-    *bytes = (int64_t)ivf_flat_split_carve(nullptr, B, P, C, D).bytes;
-    return ANNLITE_OK;
+    return ivf_flat_workspace_bytes<IvfBf16x3>(B, P, C, D, k, bytes);
 }
 
 extern "C" int annlite_ivf_flat_filter_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
@@ -2708,26 +2801,9 @@ extern "C" int annlite_ivf_flat_filter_split(int metric, const float *queries_de
                                              const int32_t *cell_of_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
                                              float *pair_norms_out_dev, float *scores_dev, void *workspace_dev, size_t workspace_bytes,
                                              void *stream) {
-    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
-    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && B * P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
-                        max_cell_rows <= n_perm,
-                    "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld", (long long)P, (long long)C, (long long)n_perm,
-                    (long long)max_cell_rows);
-    ANNLITE_REQUIRE(!centres_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "centres are for EUCLIDEAN only");
-    ANNLITE_REQUIRE(!centres_dev || cell_of_dev, "centres need cell_of_dev");
-    if (B == 0 || n_perm == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && vectors_dev && norms_dev && perm_dev && cells_dev && cell_rows_dev && cell_order_dev && bounds_dev &&
-                        cand_dev && count_dev && workspace_dev,
-                    "null device pointer");
-    const IvfFlatSplitWs w = ivf_flat_split_carve(workspace_dev, B, P, C, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = annlite_ivf_plan(cells_dev, B, P, C, kFlatTile, cell_rows_dev, cell_order_dev, w.i.n_tiles, w.i.vmap, w.i.slot_of, w.i.tile_rows,
-                              w.i.n_used, stream);
-    if (rc != ANNLITE_OK) return rc;
-    if ((rc = ivf_flat_split_prepare(queries_dev, B, P, C, D, cells_dev, centres_dev, w, pair_norms_out_dev, st)) != ANNLITE_OK) return rc;
-    return ivf_flat_split_launch_filter(metric, B, D, vectors_dev, centres_dev, C, cell_of_dev, norms_dev, N, perm_dev, n_perm, w, max_cell_rows,
-                                        stride, valid_bits_dev, bounds_dev, cand_dev, count_dev, scores_dev, st);
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_dev, norms_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        cell_order_dev, max_cell_rows, 0, centres_dev, cell_of_dev, (hipStream_t)stream};
+    return ivf_flat_stage<IvfBf16x3>(c, stride, bounds_dev, cand_dev, count_dev, pair_norms_out_dev, scores_dev, workspace_dev, workspace_bytes);
 }
 
 extern "C" int annlite_ivf_flat_search_topk_split(int metric, const float *queries_dev, int64_t B, int64_t D, const float *vectors_dev,
@@ -2737,45 +2813,14 @@ extern "C" int annlite_ivf_flat_search_topk_split(int metric, const float *queri
                                                   int64_t max_probed_rows, const float *centres_dev, const int32_t *cell_of_dev, int64_t k,
                                                   int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
                                                   size_t workspace_bytes, void *stream) {
-    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
-    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && B * P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
-                        max_cell_rows <= n_perm && max_probed_rows >= 0,
-                    "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld max_probed_rows=%lld", (long long)P, (long long)C,
-                    (long long)n_perm, (long long)max_cell_rows, (long long)max_probed_rows);
-    ANNLITE_REQUIRE(!centres_dev || metric == ANNLITE_METRIC_EUCLIDEAN, "centres are for EUCLIDEAN only");
-    ANNLITE_REQUIRE(!centres_dev || cell_of_dev, "centres need cell_of_dev");
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && cells_dev && cell_rows_dev && cell_order_dev &&
-                        (n_perm == 0 || (vectors_dev && norms_dev && perm_dev)),
-                    "null device pointer");
-    const IvfFlatSplitWs w = ivf_flat_split_carve(workspace_dev, B, P, C, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    return ivf_flat_search_staged(
-        metric, queries_dev, B, D, vectors_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev, cell_order_dev,
-        max_probed_rows, k, flags, out_dist_dev, out_id_dev, w.i, st,
-        [&]() { return ivf_flat_split_prepare(queries_dev, B, P, C, D, cells_dev, centres_dev, w, nullptr, st); },
-        [&](int64_t stride) {
-            return ivf_flat_split_launch_filter(metric, B, D, vectors_dev, centres_dev, C, cell_of_dev, norms_dev, N, perm_dev, n_perm, w,
-                                                max_cell_rows, stride, valid_bits_dev, w.i.f.thr, w.i.f.cand, w.i.f.cnt, nullptr, st);
-        });
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_dev, norms_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        cell_order_dev, max_cell_rows, max_probed_rows, centres_dev, cell_of_dev, (hipStream_t)stream};
+    return ivf_flat_search<IvfBf16x3>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
 }
 
 // ---- f16 rows over cell tiles ("f16 rows over cell tiles") -------------------------------------------------------
-static int ivf_flat_f16_check_cells(int64_t B, int64_t P, int64_t C, int64_t N, int64_t n_perm, int64_t max_cell_rows, int64_t max_probed_rows) {
-    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && B * P <= INT32_MAX && n_perm >= 0 && n_perm <= N && max_cell_rows >= 0 &&
-                        max_cell_rows <= n_perm && max_probed_rows >= 0,
-                    "bad cells P=%lld C=%lld n_perm=%lld max_cell_rows=%lld max_probed_rows=%lld", (long long)P, (long long)C,
-                    (long long)n_perm, (long long)max_cell_rows, (long long)max_probed_rows);
-    return ANNLITE_OK;
-}
-
 extern "C" int annlite_ivf_flat_search_f16_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t D, int64_t k, int64_t *bytes) {
-    ANNLITE_REQUIRE(bytes != nullptr, "bytes is NULL");
-    ANNLITE_REQUIRE(B >= 0 && P >= 1 && C >= 1 && D >= 1 && D <= kSplitMaxDim && k >= 1 && k <= 64, "bad shape (1 <= k <= 64, D <= %lld)",
-                    (long long)kSplitMaxDim);
-    *bytes = (int64_t)ivf_flat_f16_carve(nullptr, B, P, C, D).bytes;
-    return ANNLITE_OK;
+    return ivf_flat_workspace_bytes<IvfF16x2>(B, P, C, D, k, bytes);
 }
 
 extern "C" int annlite_ivf_flat_filter_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
@@ -2785,24 +2830,13 @@ extern "C" int annlite_ivf_flat_filter_f16(int metric, const float *queries_dev,
                                            float *query_norms_out_dev, float *query_flush_out_dev, const float *bounds_dev,
                                            int32_t *cand_dev, int32_t *count_dev, float *scores_dev, void *workspace_dev,
                                            size_t workspace_bytes, void *stream) {
-    if (int rc = flat_check_shape(kFlatStage, metric, B, D, N, stride, kSplitMaxDim)) return rc;
-    if (int rc = ivf_flat_f16_check_cells(B, P, C, N, n_perm, max_cell_rows, 0)) return rc;
-    if (B == 0 || n_perm == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && vectors_f16_dev && norms_dev && perm_dev && cells_dev && cell_rows_dev && cell_order_dev && bounds_dev &&
-                        cand_dev && count_dev && workspace_dev,
-                    "null device pointer");
-    const IvfFlatF16Ws w = ivf_flat_f16_carve(workspace_dev, B, P, C, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    int rc = annlite_ivf_plan(cells_dev, B, P, C, kFlatTile, cell_rows_dev, cell_order_dev, w.i.n_tiles, w.i.vmap, w.i.slot_of, w.i.tile_rows,
-                              w.i.n_used, stream);
-    if (rc != ANNLITE_OK) return rc;
-    if ((rc = ivf_flat_f16_prepare(queries_dev, B, D, w, st)) != ANNLITE_OK) return rc;
-    rc = ivf_flat_f16_launch_filter(metric, B, D, (const _Float16 *)vectors_f16_dev, norms_dev, N, perm_dev, n_perm, w, max_cell_rows, stride,
-                                    valid_bits_dev, bounds_dev, cand_dev, count_dev, scores_dev, st);
-    if (rc != ANNLITE_OK) return rc;
-    if ((rc = flat_hand_back(query_norms_out_dev, w.i.f.qnorm, B, st)) != ANNLITE_OK) return rc;
-    return flat_hand_back(query_flush_out_dev, w.qflush, B, st);
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_f16_dev, norms_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        cell_order_dev, max_cell_rows, 0, nullptr, nullptr, (hipStream_t)stream};
+    IvfFlatF16Ws w{};
+    if (int rc = ivf_flat_stage<IvfF16x2>(c, stride, bounds_dev, cand_dev, count_dev, nullptr, scores_dev, workspace_dev, workspace_bytes, &w))
+        return rc;
+    if (int rc = flat_hand_back(query_norms_out_dev, w.i.f.qnorm, B, c.st)) return rc;
+    return flat_hand_back(query_flush_out_dev, w.qflush, B, c.st);
 }
 
 extern "C" int annlite_ivf_flat_search_topk_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
@@ -2811,38 +2845,16 @@ extern "C" int annlite_ivf_flat_search_topk_f16(int metric, const float *queries
                                                 const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t max_probed_rows, int64_t k,
                                                 int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
                                                 size_t workspace_bytes, void *stream) {
-    if (int rc = flat_check_shape(kFlatSearch, metric, B, D, N, k, kSplitMaxDim)) return rc;
-    if (int rc = ivf_flat_f16_check_cells(B, P, C, N, n_perm, max_cell_rows, max_probed_rows)) return rc;
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && workspace_dev && cells_dev && cell_rows_dev && cell_order_dev &&
-                        (n_perm == 0 || (vectors_f16_dev && norms_dev && perm_dev)),
-                    "null device pointer");
-    const IvfFlatF16Ws w = ivf_flat_f16_carve(workspace_dev, B, P, C, D);
-    if (int rc = flat_check_workspace(workspace_bytes, w.bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const _Float16 *x = (const _Float16 *)vectors_f16_dev;
-    return ivf_flat_search_staged(
-        metric, queries_dev, B, D, x, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev, cell_order_dev, max_probed_rows, k,
-        flags, out_dist_dev, out_id_dev, w.i, st, [&]() { return ivf_flat_f16_prepare(queries_dev, B, D, w, st); },
-        [&](int64_t stride) {
-            return ivf_flat_f16_launch_filter(metric, B, D, x, norms_dev, N, perm_dev, n_perm, w, max_cell_rows, stride, valid_bits_dev, w.i.f.thr,
-                                              w.i.f.cand, w.i.f.cnt, nullptr, st);
-        });
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_f16_dev, norms_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        cell_order_dev, max_cell_rows, max_probed_rows, nullptr, nullptr, (hipStream_t)stream};
+    return ivf_flat_search<IvfF16x2>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
 }
 
 extern "C" int annlite_ivf_flat_search_topk_wide_f16(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_f16_dev,
                                                      int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C,
                                                      const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k,
                                                      int flags, float *out_dist_dev, int64_t *out_id_dev, void *stream) {
-    if (int rc = flat_check_shape(kFlatSearchWide, metric, B, D, N, k, kSplitMaxDim)) return rc;
-    ANNLITE_REQUIRE(P >= 1 && C >= 1 && C <= 16384 && P <= INT32_MAX && n_perm >= 0 && n_perm <= N, "bad cells P=%lld C=%lld n_perm=%lld",
-                    (long long)P, (long long)C, (long long)n_perm);
-    if (B == 0) return ANNLITE_OK;
-    ANNLITE_REQUIRE(queries_dev && out_dist_dev && out_id_dev && cells_dev && cell_rows_dev && (n_perm == 0 || (vectors_f16_dev && perm_dev)),
-                    "null device pointer");
-    const WideCells src{cells_dev, (int)P, (int)C, cell_rows_dev, perm_dev, n_perm, 0};
-    hipLaunchKernelGGL((flat_exact_wide_kernel<_Float16, WideCells>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, metric, queries_dev,
-                       (int)D, (const _Float16 *)vectors_f16_dev, N, src, valid_bits_dev, (int)k, (flags & ANNLITE_FLAG_SQRT) ? 1 : 0,
-                       (float *)nullptr, out_dist_dev, out_id_dev, 1.f);
-    return launch_status("flat_exact_wide_kernel");
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_f16_dev, nullptr, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        nullptr, 0, 0, nullptr, nullptr, (hipStream_t)stream};
+    return ivf_flat_search_wide<IvfF16x2>(c, k, flags, out_dist_dev, out_id_dev);
 }

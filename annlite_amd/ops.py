@@ -1104,6 +1104,44 @@ def ivf_flat_stages(max_probed_rows: int) -> List[int]:
     return [int(strides[i]) for i in range(n.value)]
 
 
+def _ivf_flat_operands(suffix: str, k: int, metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows,
+                       valid_bits, n_rows, workspace):
+    """What the searches and the stages over cells share: ``(B, N)``, the workspace by ``annlite_ivf_flat_search<suffix>_workspace_bytes`` (the
+    f32 entry, ``suffix == ''``, takes no D) and the arguments of every entry up to ``max_cell_rows``."""
+    B, D = queries.shape
+    P = cells.shape[1]
+    N = vectors.shape[0] if n_rows is None else n_rows
+    ws = _flat_workspace(f'ivf_flat_search{suffix}_workspace_bytes', (B, P, n_cells) + ((D,) if suffix else ()) + (k,), queries.device, workspace)
+    return (B, N), ws, (int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits), cells.data_ptr(), P,
+                        int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(), cell_order.data_ptr(), int(max_cell_rows))
+
+
+def _ivf_flat_search(suffix: str, metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, max_probed_rows,
+                     k, valid_bits, n_rows, sqrt, workspace, centres=()):
+    """``annlite_ivf_flat_search_topk<suffix>``; ``centres``: what the entry takes behind ``max_probed_rows`` (the bf16x3 filter's centres and
+    ``cell_of``)."""
+    (B, _), ws, head = _ivf_flat_operands(suffix, k, metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows,
+                                          valid_bits, n_rows, workspace)
+    od, oi = _flat_topk_outputs(B, k, queries.device)
+    entry = 'ivf_flat_search_topk' + suffix
+    check(getattr(lib(), 'annlite_' + entry)(*head, int(max_probed_rows), *centres, int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), stream_ptr()), entry)
+    return od, oi
+
+
+def _ivf_flat_stage(suffix: str, metric, queries, vectors, norms, bounds, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, valid_bits,
+                    n_rows, stride, scores, workspace, handed_back, lead, trail=()):
+    """``annlite_ivf_flat_filter<suffix>``: ``(cand, count, *handed_back[, scores])``.  ``handed_back``: the per-filter outputs, which the entry
+    takes among ``lead`` (behind the stride) or ``trail`` (behind the lists)."""
+    (B, N), ws, head = _ivf_flat_operands(suffix, 1, metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows,
+                                          valid_bits, n_rows, workspace)
+    cand, count, sc = _flat_lists(B, queries.device, N if scores else None)
+    entry = 'ivf_flat_filter' + suffix
+    check(getattr(lib(), 'annlite_' + entry)(*head, int(stride), *lead, bounds.data_ptr(), cand.data_ptr(), count.data_ptr(), *trail, _ptr(sc),
+                                             ws.data_ptr(), ws.numel(), stream_ptr()), entry)
+    return (cand, count, *handed_back, sc) if scores else (cand, count, *handed_back)
+
+
 def ivf_flat_search_topk(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, cells: torch.Tensor,
                          n_cells: int, perm: torch.Tensor, cell_rows: torch.Tensor, cell_order: torch.Tensor, max_cell_rows: int,
                          max_probed_rows: int, k: int, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
@@ -1112,17 +1150,8 @@ def ivf_flat_search_topk(metric: int, queries: torch.Tensor, vectors: torch.Tens
     ``perm`` i32 = the live offsets grouped by cell, ``cell_rows`` i64 [C, 2] their ranges, ``cell_order`` i32 [C] cells by
     descending size.  ``(dist f32 [B, k], ids i64 [B, k])`` ascending by (distance, id), (+inf, -1) padded;
     ``flat_overflow_count(workspace)`` reads the call's overflow counter afterwards."""
-    B, D = queries.shape
-    P = cells.shape[1]
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    ws = _flat_workspace('ivf_flat_search_workspace_bytes', (B, P, n_cells, k), dev, workspace)
-    od, oi = _flat_topk_outputs(B, k, dev)
-    check(lib().annlite_ivf_flat_search_topk(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
-                                             cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
-                                             cell_order.data_ptr(), int(max_cell_rows), int(max_probed_rows), int(k), 1 if sqrt else 0,
-                                             od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()), 'ivf_flat_search_topk')
-    return od, oi
+    return _ivf_flat_search('', metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, max_probed_rows, k,
+                            valid_bits, n_rows, sqrt, workspace)
 
 
 def ivf_flat_centred_norms(vectors: torch.Tensor, centres: torch.Tensor, cell_of: torch.Tensor, ids: Optional[torch.Tensor] = None,
@@ -1150,19 +1179,9 @@ def ivf_flat_filter_split(metric: int, queries: torch.Tensor, vectors: torch.Ten
     cells.  ``norms`` are ``ivf_flat_centred_norms`` with the same ``centres`` (``flat_row_norms`` without).  ``(cand i32 [B, cap],
     count i32 [B], pair_norms f32 [B, P])`` -- the last as the filter used them -- and, with ``scores=True``, the filter's score by
     (query, row offset), f32 [B, N]: NaN where the filter evaluated nothing (cell not probed, row not valid)."""
-    B, D = queries.shape
-    P = cells.shape[1]
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    ws = _flat_workspace('ivf_flat_search_split_workspace_bytes', (B, P, n_cells, D, 1), dev, workspace)
-    cand, count, sc = _flat_lists(B, dev, N if scores else None)
-    pn = torch.empty((B, P), dtype=torch.float32, device=dev)
-    check(lib().annlite_ivf_flat_filter_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
-                                              cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
-                                              cell_order.data_ptr(), int(max_cell_rows), int(stride), _ptr(centres), _ptr(cell_of),
-                                              bounds.data_ptr(), cand.data_ptr(), count.data_ptr(), pn.data_ptr(), _ptr(sc),
-                                              ws.data_ptr(), ws.numel(), stream_ptr()), 'ivf_flat_filter_split')
-    return (cand, count, pn, sc) if scores else (cand, count, pn)
+    pn = torch.empty((queries.shape[0], cells.shape[1]), dtype=torch.float32, device=queries.device)
+    return _ivf_flat_stage('_split', metric, queries, vectors, norms, bounds, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, valid_bits,
+                           n_rows, stride, scores, workspace, (pn,), lead=(_ptr(centres), _ptr(cell_of)), trail=(pn.data_ptr(),))
 
 
 def ivf_flat_search_topk_split(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, cells: torch.Tensor,
@@ -1174,18 +1193,8 @@ def ivf_flat_search_topk_split(metric: int, queries: torch.Tensor, vectors: torc
     """``annlite_ivf_flat_search_topk_split``: ``ivf_flat_search_topk`` with the split-bf16 filter over the cell tiles, every tile
     centred on its cell's row of ``centres`` f32 [C, D] (``norms``: see ``ivf_flat_filter_split``); the same answer, bit for bit.
     ``flat_overflow_count`` / ``flat_list_counts`` read this workspace too."""
-    B, D = queries.shape
-    P = cells.shape[1]
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    ws = _flat_workspace('ivf_flat_search_split_workspace_bytes', (B, P, n_cells, D, k), dev, workspace)
-    od, oi = _flat_topk_outputs(B, k, dev)
-    check(lib().annlite_ivf_flat_search_topk_split(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N,
-                                                   _ptr(valid_bits), cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(),
-                                                   cell_rows.data_ptr(), cell_order.data_ptr(), int(max_cell_rows), int(max_probed_rows),
-                                                   _ptr(centres), _ptr(cell_of), int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
-                                                   ws.data_ptr(), ws.numel(), stream_ptr()), 'ivf_flat_search_topk_split')
-    return od, oi
+    return _ivf_flat_search('_split', metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, max_probed_rows,
+                            k, valid_bits, n_rows, sqrt, workspace, centres=(_ptr(centres), _ptr(cell_of)))
 
 
 def ivf_flat_filter_f16(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor,
@@ -1197,19 +1206,9 @@ def ivf_flat_filter_f16(metric: int, queries: torch.Tensor, vectors: torch.Tenso
     f32 [B])`` -- the last two as the filter used them -- and, with ``scores=True``, the filter's score by (query, row offset), f32
     [B, N]: NaN where the filter evaluated nothing (cell not probed, row not valid, row not at the stride)."""
     assert vectors.dtype == torch.float16
-    B, D = queries.shape
-    P = cells.shape[1]
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    ws = _flat_workspace('ivf_flat_search_f16_workspace_bytes', (B, P, n_cells, D, 1), dev, workspace)
-    cand, count, sc = _flat_lists(B, dev, N if scores else None)
-    qn, qf = (torch.empty((B,), dtype=torch.float32, device=dev) for _ in range(2))
-    check(lib().annlite_ivf_flat_filter_f16(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
-                                            cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
-                                            cell_order.data_ptr(), int(max_cell_rows), int(stride), qn.data_ptr(), qf.data_ptr(),
-                                            bounds.data_ptr(), cand.data_ptr(), count.data_ptr(), _ptr(sc), ws.data_ptr(), ws.numel(),
-                                            stream_ptr()), 'ivf_flat_filter_f16')
-    return (cand, count, qn, qf, sc) if scores else (cand, count, qn, qf)
+    qn, qf = (torch.empty((queries.shape[0],), dtype=torch.float32, device=queries.device) for _ in range(2))
+    return _ivf_flat_stage('_f16', metric, queries, vectors, norms, bounds, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, valid_bits,
+                           n_rows, stride, scores, workspace, (qn, qf), lead=(qn.data_ptr(), qf.data_ptr()))
 
 
 def ivf_flat_search_topk_f16(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, cells: torch.Tensor,
@@ -1220,18 +1219,8 @@ def ivf_flat_search_topk_f16(metric: int, queries: torch.Tensor, vectors: torch.
     the f16 filter over the cell tiles: the answer of ``ivf_flat_search_topk`` over the widened rows, bit for bit.
     ``flat_overflow_count`` / ``flat_list_counts`` read this workspace too."""
     assert vectors.dtype == torch.float16
-    B, D = queries.shape
-    P = cells.shape[1]
-    N = vectors.shape[0] if n_rows is None else n_rows
-    dev = queries.device
-    ws = _flat_workspace('ivf_flat_search_f16_workspace_bytes', (B, P, n_cells, D, k), dev, workspace)
-    od, oi = _flat_topk_outputs(B, k, dev)
-    check(lib().annlite_ivf_flat_search_topk_f16(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits),
-                                                 cells.data_ptr(), P, int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(),
-                                                 cell_order.data_ptr(), int(max_cell_rows), int(max_probed_rows), int(k), 1 if sqrt else 0,
-                                                 od.data_ptr(), oi.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()),
-          'ivf_flat_search_topk_f16')
-    return od, oi
+    return _ivf_flat_search('_f16', metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, max_probed_rows, k,
+                            valid_bits, n_rows, sqrt, workspace)
 
 
 # ---------------------------------------------------------------------------------------------- PCA projector
