@@ -153,6 +153,10 @@ SYMBOLS = (
     'annlite_ivf_flat_filter_f16',
     'annlite_ivf_flat_search_topk_f16',
     'annlite_ivf_flat_search_topk_wide_f16',
+    'annlite_ivf_flat_search_i8_workspace_bytes',
+    'annlite_ivf_flat_filter_i8',
+    'annlite_ivf_flat_search_topk_i8',
+    'annlite_ivf_flat_search_topk_wide_i8',
     'annlite_affine_rows',
     'annlite_pca_accumulate_workspace_bytes',
     'annlite_pca_accumulate',
@@ -367,6 +371,13 @@ def lib() -> ctypes.CDLL:
                                               vp, vp, sz, vp]
     L.annlite_ivf_flat_search_topk_f16.argtypes = L.annlite_ivf_flat_search_topk.argtypes
     L.annlite_ivf_flat_search_topk_wide_f16.argtypes = L.annlite_ivf_flat_search_topk_wide.argtypes
+
+    def scaled(argtypes):  # (the int8 entries: the scale behind the vectors)
+        return argtypes[:5] + [ctypes.c_float] + argtypes[5:]
+    L.annlite_ivf_flat_search_i8_workspace_bytes.argtypes = L.annlite_ivf_flat_search_f16_workspace_bytes.argtypes
+    L.annlite_ivf_flat_filter_i8.argtypes = scaled(L.annlite_ivf_flat_filter_f16.argtypes)
+    L.annlite_ivf_flat_search_topk_i8.argtypes = scaled(L.annlite_ivf_flat_search_topk.argtypes)
+    L.annlite_ivf_flat_search_topk_wide_i8.argtypes = scaled(L.annlite_ivf_flat_search_topk_wide.argtypes)
     L.annlite_affine_rows.argtypes = [vp, i64, i64, i64, vp, i64, vp, vp, vp, i64, vp]
     L.annlite_pca_accumulate_workspace_bytes.argtypes = [i64, i64, ctypes.POINTER(ctypes.c_int64)]
     L.annlite_pca_accumulate.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, sz, vp]

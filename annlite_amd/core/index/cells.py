@@ -35,12 +35,12 @@ class CellColumnMixin:
         # the reference assigns cells on the vectors as given (index.py:291-292, vq.py:81-90)
         raw = ops.to_dev(x, torch.float32)
         raw = raw.reshape(1, -1) if raw.ndim == 1 else raw
-        self._cell_of[ids_t] = self.vq_codec.encode(self._cell_vectors(raw)).to(torch.int32)
+        self._cell_of[ids_t] = self.vq_codec.encode(self._cell_vectors(raw, ids_t)).to(torch.int32)
         self._sealed = False
 
-    def _cell_vectors(self, raw: torch.Tensor) -> torch.Tensor:
+    def _cell_vectors(self, raw: torch.Tensor, ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """What the cells are assigned from, f32 ``[n, dim]``: the vectors as given.  An index that stores its rows in another
-        precision overrides this with the vectors as it stores them."""
+        precision overrides this with the vectors as it stores them (``ids``: the rows they were just written to)."""
         return raw
 
     def delete(self, ids):

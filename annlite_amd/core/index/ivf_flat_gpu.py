@@ -50,12 +50,19 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         index's over the rounded rows: the cells are assigned from the given vectors ROUNDED to f16 as the store rounds them (COSINE
         stores the normalised vector rounded; no f32 COSINE index holds such rows, the INNER_PRODUCT one does).  ``dim <= 32768``; neither
         ``cell_filter='bf16x3'`` nor a ``centre`` (a common offset destroys f16 data before any filter sees it).  ``dtype=np.float16``
-        without the keyword stays refused.
+        without the keyword stays refused.  ``'i8'`` (opt-in): the cells over INT8 rows.  The index is the int8 ``FlatGpuIndex`` -- codes
+        ``clamp(rne(x / s), -127, 127)`` standing for ``s * c``, ``s = int8_scale`` (``None``: 1.0, ``2**-7`` for COSINE; ``int8_scale_``), a
+        quarter of the HBM -- with the cell column beside it, and a pruned search runs the int8 MFMA filter over the cell tiles
+        (``last_cell_filter == 'i8x3'``; DESIGN.md section 3.7, "int8 rows over cell tiles").  The answer is, bit for bit, the f32 index's
+        over the decoded rows ``s * c``.  The cells are assigned from the rows AS THE STORE HOLDS THEM, ``s * c``: for COSINE that is the
+        normalised vector, quantised and decoded -- not the given vector rounded, as the f16 rule has it: a COSINE vector as given would
+        saturate at the default scale.  The same refusals as ``'f16'``; ``dtype=np.int8`` without the keyword stays refused.
+    :param int8_scale: with ``ivf_rows='i8'`` only: ``FlatGpuIndex``'s.
     :param flat_filter, centre: the every-cell search's options in ``FlatGpuIndex``; accepted and ignored here (it stays ``'f32'``).
     """
     FORMAT = 'annlite_amd.IvfFlatGpuIndex/1'
     CELL_FILTERS = ('f32', 'bf16x3')
-    IVF_ROWS = ('f32', 'f16')
+    IVF_ROWS = ('f32', 'f16', 'i8')
     # (a filter per query: one search_batch per group -- the pruned search stays the search it is under every selection)
     search_batch_grouped = RowStoreIndex.search_batch_grouped
 
@@ -68,20 +75,20 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         if cell_filter == 'bf16x3' and dim > self.SPLIT_MAX_DIM:
             raise ValueError(f"cell_filter='bf16x3' takes dim <= {self.SPLIT_MAX_DIM}")
         if ivf_rows not in self.IVF_ROWS:
-            raise ValueError(f"ivf_rows={ivf_rows!r}: 'f32' (default) or 'f16' (the cells over half-precision rows)")
+            raise ValueError(f"ivf_rows={ivf_rows!r}: 'f32' (default), 'f16' (the cells over half-precision rows) or 'i8' (over int8 rows)")
         centre = kwargs.get('centre', 'mean')
-        if ivf_rows == 'f16':
+        if ivf_rows != 'f32':
             if cell_filter == 'bf16x3':
-                raise ValueError("cell_filter='bf16x3' splits f32 rows: ivf_rows='f16' runs the f16 filter over the cell tiles")
+                raise ValueError(f"cell_filter='bf16x3' splits f32 rows: ivf_rows={ivf_rows!r} runs its own filter over the cell tiles")
             if not (isinstance(centre, str) and centre == 'mean'):
-                raise ValueError(f"centre={centre!r} with ivf_rows='f16': f16 rows have no centre (centre the data before adding it)")
+                raise ValueError(f"centre={centre!r} with ivf_rows={ivf_rows!r}: such rows have no centre (centre the data before adding it)")
             if dim > self.SPLIT_MAX_DIM:
-                raise ValueError(f"ivf_rows='f16' takes dim <= {self.SPLIT_MAX_DIM}")
+                raise ValueError(f"ivf_rows={ivf_rows!r} takes dim <= {self.SPLIT_MAX_DIM}")
         self.ivf_rows = ivf_rows
         self.vq_codec = vq_codec
         self.n_probe = n_probe  # None: every cell (the reference's behaviour)
         self.cell_filter = cell_filter
-        self.last_cell_filter = None  # 'f32' / 'bf16x3' / 'f16x2': the cell-tile filter of the last search_batch; None: it ran none
+        self.last_cell_filter = None  # 'f32' / 'bf16x3' / 'f16x2' / 'i8x3': the cell-tile filter of the last search_batch; None: it ran none
         self._cell_centred = cell_filter == 'bf16x3' and Metric(metric) == Metric.EUCLIDEAN
         self._cell_centres_dev = None
         self._stored_cell_centres = None  # (between `_load_state` and the end of `load`: the centres an index file carried)
@@ -90,10 +97,12 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
         # (accepted and ignored: this index's every-cell search is the f32 one -- DESIGN.md section 10)
         kwargs.pop('flat_filter', None)
         kwargs.pop('centre', None)
-        if is_i8(kwargs.get('dtype', 'float32')):
-            raise NotImplementedError('dtype=np.int8: the cell-tile kernels read f32 or f16 rows only (int8 rows exist in the '
-                                      'exhaustive FlatGpuIndex: no graph, n_cells=1)')
-        if ivf_rows == 'f16':
+        if ivf_rows != 'i8' and is_i8(kwargs.get('dtype', 'float32')):
+            raise NotImplementedError("dtype=np.int8: the cell-tile kernels read f32 rows unless ivf_rows='i8' opts into the cells over int8 "
+                                      'rows (they also exist in the exhaustive FlatGpuIndex: no graph, n_cells=1)')
+        if ivf_rows == 'i8':
+            kwargs['dtype'] = np.int8  # (int8_scale rides in kwargs: the store checks it)
+        elif ivf_rows == 'f16':
             kwargs['dtype'] = np.float16
         elif is_f16(kwargs.get('dtype', 'float32')):
             raise NotImplementedError("dtype=np.float16: the cell-tile kernels read f32 rows unless ivf_rows='f16' opts into the cells over "
@@ -133,9 +142,13 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
             self._fix_cell_centres()
             ops.ivf_flat_centred_norms(self._vectors, self._cell_centres_dev, self._cell_of, ids=ids_t, out=self._cell_cnorms)
 
-    def _cell_vectors(self, raw):
+    def _cell_vectors(self, raw, ids=None):
         """f16 rows: the cells come from the vectors rounded as the store rounds them, so that the index over f16 rows and the f32
-        index that is given the rounded vectors lay out the same cells"""
+        index that is given the rounded vectors lay out the same cells.  int8 rows: from the rows as the store holds them, ``s * c``
+        (``ids``: where they were just written) -- for COSINE the normalised vector, quantised and decoded; the f16 rule "round the
+        given vector" does not carry over, a COSINE vector as given would saturate at the default scale ``2**-7``."""
+        if self._i8:
+            return self._vectors[ids].to(torch.float32) * self._i8_scale
         return raw.to(torch.float16).to(torch.float32) if self._f16 else raw
 
     def reset(self, capacity: Optional[int] = None):
@@ -183,8 +196,8 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
                      large_k: Optional[str] = None):
         """``FlatGpuIndex.search_batch`` over the rows of each query's ``n_probe`` nearest cells (every cell: that search itself, with
         its ``filter_route``; the pruned search scans cell tiles under the bitmap whatever the route, and reports ``'mask'``).  ``large_k``:
-        as there; ``'wide'`` answers a pruned search with ``64 < limit <= 1024`` by ``annlite_ivf_flat_search_topk_wide`` (``_f16`` over f16
-        rows)."""
+        as there; ``'wide'`` answers a pruned search with ``64 < limit <= 1024`` by ``annlite_ivf_flat_search_topk_wide`` (``_f16`` / ``_i8`` over
+        f16 / int8 rows)."""
         large_k = self.large_k if large_k is None else self._check_large_k(large_k)
         P = self.n_probe if n_probe is None else n_probe
         C = self.n_cells
@@ -215,7 +228,7 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
                 self.last_cell_filter = name if max_probed >= self.FILTER_MIN_ROWS else None
             elif large_k == 'wide' and k <= self.WIDE_MAX_K:
                 d, i = ops.ivf_flat_search_topk_wide(int(self.metric), q, self._vectors, cells, C, self._perm, self._cell_rows, k, valid_bits=valid,
-                                                     n_rows=self._n_rows, sqrt=self.metric == Metric.EUCLIDEAN)
+                                                     n_rows=self._n_rows, sqrt=self.metric == Metric.EUCLIDEAN, scale=self._i8_scale or 1.0)
                 self.last_large_k = 'wide'
             else:
                 d, i = self._search_large_k_cells(q, k, valid, cells, max_probed)
@@ -231,6 +244,8 @@ class IvfFlatGpuIndex(CellColumnMixin, FlatGpuIndex):
             return 'bf16x3', ops.ivf_flat_search_topk_split, self._norms, {}
         if self._f16:
             return 'f16x2', ops.ivf_flat_search_topk_f16, self._norms, {}
+        if self._i8:
+            return 'i8x3', ops.ivf_flat_search_topk_i8, self._norms, dict(scale=self._i8_scale)
         return 'f32', ops.ivf_flat_search_topk, self._norms, {}
 
     def _probed_rows(self, cells: torch.Tensor, R: int):

@@ -100,6 +100,7 @@ static Knobs *parse_knobs() {
     k->graph_seq_insert = getenv("ANNLITE_GRAPH_SEQ_INSERT") != nullptr;
     k->ivf_first = env_int("ANNLITE_IVF_FIRST", -1);
     k->ivf_f16_stage = env_int("ANNLITE_IVF_F16_STAGE", -1);
+    k->ivf_i8_stage = env_int("ANNLITE_IVF_I8_STAGE", -1);
     k->ivf_static_tiles = getenv("ANNLITE_IVF_STATIC_TILES") != nullptr;
     return k;
 }

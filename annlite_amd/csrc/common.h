@@ -89,6 +89,7 @@ struct Knobs {
     bool ivf_static_tiles;      // ANNLITE_IVF_STATIC_TILES (A/B: the cell tiles dealt round-robin instead of drawn from a counter)
     int ivf_first;              // ANNLITE_IVF_FIRST (annlite_ivf_search_topk: probes per query whose tiles come first; -1: the default)
     int ivf_f16_stage;          // ANNLITE_IVF_F16_STAGE=64 (A/B: ivf_flat_f16_filter_kernel with a stage of 64 coordinates, a whole line per gathered row, instead of 32)
+    int ivf_i8_stage;           // ANNLITE_IVF_I8_STAGE=128 (A/B: ivf_flat_i8_filter_kernel with a stage of 128 coordinates, a whole line per gathered row, instead of 64)
 };
 const Knobs &knobs();
 

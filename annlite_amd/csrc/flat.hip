@@ -1116,7 +1116,8 @@ __device__ __forceinline__ void ivf_flat_cell_range(int32_t cell, int C, const i
 }
 
 // flat_exact_kernel's `list == NULL` mode over the probed cells: exact sums of every stride-th entry of each of the query's P cells
-// (the first sample; all probed rows where they are few; the route of an overflowed query).  T: the row type, float or _Float16.
+// (the first sample; all probed rows where they are few; the route of an overflowed query).  T: the row type, float, _Float16 or
+// int8_t; scale: what one code step of an int8 row stands for (1.f from the float row types, which do not read it).
 template <class T>
 __global__ __launch_bounds__(256) void ivf_flat_exact_kernel(int metric, const float *__restrict__ q, int B, int D, const T *__restrict__ x,
                                                             int64_t N, const int32_t *__restrict__ cells, int P, int C,
@@ -1124,7 +1125,7 @@ __global__ __launch_bounds__(256) void ivf_flat_exact_kernel(int metric, const f
                                                             int64_t n_perm, int64_t stride, const uint32_t *__restrict__ valid, int k,
                                                             int do_sqrt, int only_overflowed, float *__restrict__ thr_out,
                                                             float *__restrict__ out_d, int64_t *__restrict__ out_i,
-                                                            const int32_t *__restrict__ ovf) {
+                                                            const int32_t *__restrict__ ovf, float scale) {
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
@@ -1140,7 +1141,7 @@ __global__ __launch_bounds__(256) void ivf_flat_exact_kernel(int metric, const f
         for (int64_t c0 = 0; c0 < n; c0 += 64) {
             const int64_t ci = c0 + lane;
             const int64_t row = ci < n ? (int64_t)perm[begin + ci * stride] : -1;
-            flat_exact_chunk(metric, qr, D, x, N, valid, row, n - c0 < 64 ? (int)(n - c0) : 64, k - 1, lane, L, th, tl);
+            flat_exact_chunk(metric, qr, D, x, N, valid, row, n - c0 < 64 ? (int)(n - c0) : 64, k - 1, lane, L, th, tl, scale);
         }
     }
     flat_exact_finish(L, b, k, lane, do_sqrt, thr_out, out_d, out_i);
@@ -1325,7 +1326,8 @@ __device__ __forceinline__ bool ivf_flat_tile_range(const int64_t *__restrict__ 
 }
 
 // The row tile and the query slots of a cell kernel, by its 2 kFlatTile threads: rws[i] = offset of stage row r0 + i of the tile's range,
-// -1: none (past the cell's end, not valid); nxs[i] = its norm; qss[i] = query of the tile's slot i, -1: padding.
+// -1: none (past the cell's end, not valid); nxs[i] = its norm; qss[i] = query of the tile's slot i, -1: padding.  Written for EXACTLY
+// 2 kFlatTile threads: a kernel with more (ivf_flat_i8_filter_kernel) calls it under tid < 2 kFlatTile.
 __device__ __forceinline__ void ivf_flat_tile_rows(int tid, int t, int64_t r0, int64_t S, int64_t begin, int64_t stride,
                                                    const int32_t *__restrict__ perm, int64_t N, const uint32_t *__restrict__ valid,
                                                    const float *__restrict__ norms, const int32_t *__restrict__ vmap, int B, int *rws, float *nxs,
@@ -1629,6 +1631,141 @@ __global__ __launch_bounds__(256) void ivf_flat_f16_filter_kernel(int metric, co
             for (int ri = 0; ri < 2; ++ri)
                 flat_tile_epilogue<true, false>(metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh,
                                                 [&](int reg) { return acc.tile(ri, qj)[reg] * down; }, row_of);
+        }
+    }
+}
+
+// ---- int8 rows over cell tiles ("int8 rows over cell tiles") -----------------------------------------------------
+// flat_i8_filter_tile's contraction and epilogue -- the codes as stored against the three digit planes of flat_i8_queries_kernel, three
+// v_mfma_i32_32x32x32_i8 per row half and K step of 32 into integer accumulators, T = S2 2^14 + S1 2^7 + S0 recombined in 64 bits, one
+// conversion, the query's 2^-e -- on ivf_flat_filter_kernel's grid, tile walk and rws / nxs / qss.  As in the f16 cell kernel nothing is
+// centred: the planes p0 / p1 / p2 int8 [B][Dp] and qnorm / qscale / qslack f32 [B] are BY QUERY, written once per call whatever the
+// plan, and a tile gathers the planes of its slots through qss as it gathers its rows through perm.
+//
+// Work split: 512 threads, 8 waves, a wave owns 64 rows x 32 query slots of the 128 x 128 tile (wr = (wave >> 2) 64, wq = (wave & 3) 32)
+// in six i32x16 accumulators -- 3 planes x 2 row halves, 96 registers.  The 64 x 64 of the other cell kernels' 4 waves would need 192.
+// ivf_flat_tile_rows is written for 256 threads: the first 256 of the 512 call it.
+//
+// LDS: four planes (rows, d0, d1, d2) of 128 x (DEPTH + 16) bytes.  DEPTH = 64, the table kernel's stage (pitch 80 = 5 slots of 16
+// bytes): 40 960 bytes.  DEPTH = 128 (pitch 144 = 9 slots): 73 728 bytes -- at D >= 128 a gathered int8 row is then ONE whole 128-byte
+// line per stage, fetched by eight neighbouring lanes, and the barriers per row tile halve.  LDS would let two workgroups per CU fit at
+// either depth; the registers do not: 143 VGPRs at 64 and 164 at 128 (the table kernel: 176), ONE workgroup of 8 waves per CU, and a
+// bound of 128 registers spills 60 to 184 bytes per lane, so none is set.
+// A lane reads bytes kk + 16 (lane >> 5) .. + 15 of row lane & 31 as one ds_read_b128; the 16 lanes that instruction serves together
+// hold rows that are distinct mod 16, and 5 r mod 16 and 9 r mod 16 are permutations: every lane group covers the 64 banks once (the
+// argument above ivf_flat_f16_filter_kernel).  Which depth runs is a measurement; the other stays behind
+// ANNLITE_IVF_I8_STAGE, the A/B switch of that measurement.
+// VEC: D % 16 == 0 and x aligned to 16 bytes (a slot of a row is one 16-byte load); every other D stages single bytes.  The planes are
+// always read 16 bytes at a time: Dp is a multiple of 32 and the workspace aligns them.  scores != NULL (tests, measurements): as in the
+// other cell kernels, by (query, row offset).
+template <bool VEC, int DEPTH>
+__global__ __launch_bounds__(kI8Threads) void ivf_flat_i8_filter_kernel(int metric, const int8_t *__restrict__ p0, const int8_t *__restrict__ p1,
+                                                                       const int8_t *__restrict__ p2, int B, int D, int Dp,
+                                                                       const int8_t *__restrict__ x, const float *__restrict__ norms, int64_t N,
+                                                                       const int32_t *__restrict__ perm, int64_t n_perm,
+                                                                       const int64_t *__restrict__ tile_rows, const int32_t *__restrict__ vmap,
+                                                                       int n_tiles, int64_t stride, const uint32_t *__restrict__ valid,
+                                                                       const float *__restrict__ qnorm, const float *__restrict__ qscale,
+                                                                       const float *__restrict__ qslack, const float *__restrict__ thr,
+                                                                       float c_rel, float c_abs, int32_t *__restrict__ cand,
+                                                                       int32_t *__restrict__ cnt, int cap, float *__restrict__ scores) {
+    static_assert(DEPTH == 64 || DEPTH == 128, "a stage is two or four K steps of 32");
+    static_assert(kI8Threads == 4 * kFlatTile, "the staging below deals 16-byte slots to 512 threads");
+    constexpr int LD = DEPTH + 16;      // LDS row pitch in bytes
+    constexpr int SLOTS = DEPTH / 16;   // 16-byte slots of a row per stage
+    constexpr int NI = SLOTS / 4;       // slots per thread and plane: kFlatTile * SLOTS / kI8Threads
+    __shared__ __attribute__((aligned(16))) int8_t As[kFlatTile * LD];
+    __shared__ __attribute__((aligned(16))) int8_t B0[kFlatTile * LD];
+    __shared__ __attribute__((aligned(16))) int8_t B1[kFlatTile * LD];
+    __shared__ __attribute__((aligned(16))) int8_t B2[kFlatTile * LD];
+    __shared__ float nxs[kFlatTile];
+    __shared__ int rws[kFlatTile];
+    __shared__ int qss[kFlatTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * kFlatTile;
+    const int wr = (wave >> 2) * 64, wq = (wave & 3) * 32;
+    const int l31 = lane & 31, lh = lane >> 5;
+    const auto row_of = [&](int rl) { return FlatRow{rws[rl] >= 0, rws[rl], rws[rl] >= 0, (int64_t)rws[rl]}; };
+    for (int t = blockIdx.y; t < n_tiles; t += gridDim.y) {
+        int64_t begin, S;
+        if (!ivf_flat_tile_range(tile_rows, t, n_perm, stride, begin, S) || r0 >= S) continue;  // (the workgroup's: no barrier is left behind)
+        __syncthreads();  // the previous tile's epilogue has read rws / nxs / qss
+        if (tid < 2 * kFlatTile) ivf_flat_tile_rows(tid, t, r0, S, begin, stride, perm, N, valid, norms, vmap, B, rws, nxs, qss);
+        i32x16 s0a, s0b, s1a, s1b, s2a, s2b;  // plane 0 / 1 / 2, rows wr .. wr + 31 (a) and wr + 32 .. wr + 63 (b)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s0a[e] = s0b[e] = s1a[e] = s1b[e] = s2a[e] = s2b[e] = 0;
+        for (int k0 = 0; k0 < D; k0 += DEPTH) {
+            __syncthreads();  // the previous stage is consumed (first pass: the tile's rows and queries are written)
+            // SLOTS neighbouring threads hold the slots of one row and of one query: every load of a stage is issued before its first store
+            i32x4 va[NI], v0[NI], v1[NI], v2[NI];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int e = tid + i * kI8Threads;
+                const int r = e / SLOTS, c = (e % SLOTS) * 16;
+                va[i] = v0[i] = v1[i] = v2[i] = i32x4{0, 0, 0, 0};
+                if constexpr (VEC) {  // rows: the bytes from HBM as they are, gathered through perm
+                    const int rr = rws[r];
+                    if (rr >= 0 && k0 + c < D) va[i] = *(const i32x4 *)(x + (int64_t)rr * D + k0 + c);
+                }
+                // queries: the digit planes of the tile's slots, gathered by query (a padding slot stages zeros)
+                const int qq = qss[r];
+                if (qq >= 0 && k0 + c < Dp) {
+                    v0[i] = *(const i32x4 *)(p0 + (int64_t)qq * Dp + k0 + c);
+                    v1[i] = *(const i32x4 *)(p1 + (int64_t)qq * Dp + k0 + c);
+                    v2[i] = *(const i32x4 *)(p2 + (int64_t)qq * Dp + k0 + c);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const int e = tid + i * kI8Threads;
+                const int o = (e / SLOTS) * LD + (e % SLOTS) * 16;
+                if constexpr (VEC) *(i32x4 *)(As + o) = va[i];
+                *(i32x4 *)(B0 + o) = v0[i];
+                *(i32x4 *)(B1 + o) = v1[i];
+                *(i32x4 *)(B2 + o) = v2[i];
+            }
+            if constexpr (!VEC) {
+                const int c = tid % DEPTH;  // (512 is a multiple of DEPTH: a thread stages one byte of every row it handles)
+#pragma unroll 4
+                for (int i = 0; i < DEPTH / 4; ++i) {
+                    const int r = (tid + i * kI8Threads) / DEPTH;  // single bytes
+                    const int rr = rws[r];
+                    As[r * LD + c] = (rr >= 0 && k0 + c < D) ? x[(int64_t)rr * D + k0 + c] : (int8_t)0;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < DEPTH; kk += 32) {
+                if (k0 + kk >= D) break;  // (a K step of padding only)
+                const int kc = kk + 16 * lh;
+                const i32x4 a0 = *(const i32x4 *)(As + (wr + l31) * LD + kc), a1 = *(const i32x4 *)(As + (wr + 32 + l31) * LD + kc);
+                const i32x4 b0 = *(const i32x4 *)(B0 + (wq + l31) * LD + kc);
+                const i32x4 b1 = *(const i32x4 *)(B1 + (wq + l31) * LD + kc);
+                const i32x4 b2 = *(const i32x4 *)(B2 + (wq + l31) * LD + kc);
+                s0a = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b0, s0a, 0, 0, 0);
+                s0b = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b0, s0b, 0, 0, 0);
+                s1a = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b1, s1a, 0, 0, 0);
+                s1b = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b1, s1b, 0, 0, 0);
+                s2a = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b2, s2a, 0, 0, 0);
+                s2b = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, b2, s2b, 0, 0, 0);
+            }
+        }
+        // the three sums back into ONE integer, one conversion, the query's scale: that is this kernel's dot product.  A lane owns one slot.
+        const int qi = qss[wq + l31];
+        if (qi >= 0) {
+            const FlatQuery Q = flat_query(qi, qnorm[qi], thr, qslack[qi], cand, cnt, cap, scores, N);
+            const float down = qscale[qi];
+#pragma unroll
+            for (int ri = 0; ri < 2; ++ri) {
+                const i32x16 &S0 = ri == 0 ? s0a : s0b, &S1 = ri == 0 ? s1a : s1b, &S2 = ri == 0 ? s2a : s2b;
+                flat_tile_epilogue<true, false>(
+                    metric, c_rel, c_abs, cap, Q, nxs, wr + ri * 32, lh,
+                    [&](int reg) {
+                        const int64_t T = (int64_t)S2[reg] * 16384 + (int64_t)S1[reg] * 128 + (int64_t)S0[reg];  // = sum Q_j c_j, |T| < 2^43
+                        return (float)T * down;
+                    },
+                    row_of);
+            }
         }
     }
 }
@@ -2170,6 +2307,7 @@ struct IvfFlatCall {
     const float *centres;  // [C][D], with cell_of [N]: the bf16x3 entries alone have them, NULL from the others
     const int32_t *cell_of;
     hipStream_t st;
+    float row_scale = 1.f;  // what one code step of an int8 row stands for: the int8 entries set it, the float row types do not read it
 };
 
 struct IvfFlatWs {
@@ -2231,6 +2369,15 @@ struct IvfFlatF16Ws {
     int64_t Dp;  // D rounded up to the MFMA's K step
     _Float16 *qh, *ql;
     float *qscale, *qflush;
+    size_t bytes;
+};
+// ---- the int8 filter's share: the three digit planes, the scales and the per-query slack terms BY QUERY, behind the IvfFlatWs of the same
+// (B, P, C) ----
+struct IvfFlatI8Ws {
+    IvfFlatWs i;
+    int64_t Dp;  // D rounded up to the MFMA's K step
+    int8_t *p0, *p1, *p2;
+    float *qscale, *qslack;
     size_t bytes;
 };
 
@@ -2340,11 +2487,59 @@ struct IvfF16x2 {
         return launch_status("ivf_flat_f16_filter_kernel");
     }
 };
+struct IvfI8x3 {
+    using Row = int8_t;
+    using Ws = IvfFlatI8Ws;
+    static constexpr int64_t kMaxDim = kSplitMaxDim;
+    static constexpr bool kBoundPairs = true;
+    static Ws carve(void *ws, int64_t B, int64_t P, int64_t C, int64_t D) {
+        Ws w;
+        w.i = ivf_flat_carve(ws, B, P, C);
+        w.Dp = (D + 31) / 32 * 32;
+        WsBump b{(char *)ws, w.i.bytes};
+        w.p0 = b.take<int8_t>((size_t)B * w.Dp);
+        w.p1 = b.take<int8_t>((size_t)B * w.Dp);
+        w.p2 = b.take<int8_t>((size_t)B * w.Dp);
+        w.qscale = b.take<float>((size_t)B * 4);
+        w.qslack = b.take<float>((size_t)B * 4);
+        w.bytes = b.o;
+        return w;
+    }
+    static const IvfFlatWs &base(const Ws &w) { return w.i; }
+    // The queries' digit planes, norms, scales and slack terms, with the store's scale folded in as flat_i8_prepare folds it -- no plan is
+    // needed for them.
+    static int prepare(const IvfFlatCall &c, const Ws &w, float *) {
+        hipLaunchKernelGGL(flat_i8_queries_kernel, dim3((unsigned)((c.B + 3) / 4)), dim3(256), 0, c.st, c.q, (int)c.B, (int)c.D, (int)w.Dp,
+                           i8_scale_log2(c.row_scale), w.p0, w.p1, w.p2, w.i.f.qnorm, w.qscale, w.qslack);
+        return launch_status("flat_i8_queries_kernel");
+    }
+    // The stage holds 64 coordinates unless ANNLITE_IVF_I8_STAGE=128 asks for a whole line per gathered row (an A/B switch: common.h, Knobs).
+    static int launch(const IvfFlatCall &c, const Ws &w, dim3 grid, int64_t stride, const float *thr, int32_t *cand, int32_t *cnt, float *scores) {
+        float c_rel, c_abs;
+        flat_i8_slack(c.metric, c.D, &c_rel, &c_abs);
+        const Row *x = (const Row *)c.x;
+        const bool vec = c.D % 16 == 0 && ((uintptr_t)x % 16 == 0);
+        const int depth = knobs().ivf_i8_stage == 128 ? 128 : 64;
+#define IVF_FLAT_I8_LAUNCH(VEC, DEPTH)                                                                                                            \
+    hipLaunchKernelGGL((ivf_flat_i8_filter_kernel<VEC, DEPTH>), grid, dim3(kI8Threads), 0, c.st, c.metric, w.p0, w.p1, w.p2, (int)c.B, (int)c.D,    \
+                       (int)w.Dp, x, c.norms, c.N, c.perm, c.n_perm, w.i.tile_rows, w.i.vmap, (int)w.i.n_tiles, stride, c.valid, w.i.f.qnorm,      \
+                       w.qscale, w.qslack, thr, c_rel, c_abs, cand, cnt, kFlatCap, scores)
+        if (depth == 128) {
+            if (vec) IVF_FLAT_I8_LAUNCH(true, 128);
+            else IVF_FLAT_I8_LAUNCH(false, 128);
+        } else {
+            if (vec) IVF_FLAT_I8_LAUNCH(true, 64);
+            else IVF_FLAT_I8_LAUNCH(false, 64);
+        }
+#undef IVF_FLAT_I8_LAUNCH
+        return launch_status("ivf_flat_i8_filter_kernel");
+    }
+};
 
 // What every cells entry asks of the shape (what / arg: as flat_check_shape has them), of the cells and of the centres.  Two things are
 // kept per entry, as each entry has always had them:
-//   the pairs -- the searches and the stages of IvfBf16x3 and IvfF16x2 (F::kBoundPairs) bound the (query, cell) pairs B P; the f32 search
-//   and the two wide searches, of either row type, bound P alone;
+//   the pairs -- the searches and the stages of IvfBf16x3, IvfF16x2 and IvfI8x3 (F::kBoundPairs) bound the (query, cell) pairs B P; the
+//   f32 search and the wide searches, of every row type, bound P alone;
 //   max_cell_rows / max_probed_rows -- checked where the entry takes them (IvfFlatCall).
 template <class F>
 static int ivf_flat_check(FlatEntry what, const IvfFlatCall &c, int64_t arg) {
@@ -2375,7 +2570,7 @@ static int ivf_flat_filter(const IvfFlatCall &c, const typename F::Ws &fw, int64
 
 // ---- the stages of a search over cells, the same for every cell-tile filter F: the exact-only shortcut, the
 // plan, F::prepare, the first exact sample, the filter stages (into w.cand / w.cnt against the bounds w.thr), the re-rank of the lists
-// and the route of an overflowed list.  fw: F's carved workspace.  The exact stages alone read the rows here. ----
+// and the route of an overflowed list.  fw: F's carved workspace.  The exact stages alone read the rows here (int8: as c.row_scale * code). ----
 template <class F>
 static int ivf_flat_search_staged(F, const IvfFlatCall &c, const typename F::Ws &fw, int64_t k, int flags, float *out_dist_dev,
                                   int64_t *out_id_dev) {
@@ -2390,7 +2585,7 @@ static int ivf_flat_search_staged(F, const IvfFlatCall &c, const typename F::Ws 
     auto exact_cells = [&](int64_t stride, int sqrt_out, int only_overflowed, float *thr_out) {
         hipLaunchKernelGGL(ivf_flat_exact_kernel<T>, qgrid, dim3(256), 0, st, c.metric, c.q, (int)c.B, (int)c.D, x, c.N, c.cells, (int)c.P, (int)c.C,
                            c.cell_rows, c.perm, c.n_perm, stride, c.valid, (int)k, sqrt_out, only_overflowed, thr_out, out_dist_dev, out_id_dev,
-                           w.ovf);
+                           w.ovf, c.row_scale);
         return launch_status("ivf_flat_exact_kernel");
     };
     int64_t strides[kIvfFlatMaxStages];
@@ -2408,15 +2603,15 @@ static int ivf_flat_search_staged(F, const IvfFlatCall &c, const typename F::Ws 
         // the list re-rank of annlite_flat_search_topk, unchanged: the lists hold offsets
         hipLaunchKernelGGL(flat_exact_kernel<T>, qgrid, dim3(256), 0, st, c.metric, c.q, (int)c.B, (int)c.D, x, c.N, w.cand, w.cnt, kFlatCap,
                            (int64_t)0, (int64_t)1, c.valid, (int)k, last ? do_sqrt : 0, last ? 1 : 0, 0, last ? nullptr : w.thr, out_dist_dev,
-                           out_id_dev, w.ovf, w.ovf_total);
+                           out_id_dev, w.ovf, w.ovf_total, c.row_scale);
         if ((rc = launch_status("flat_exact_kernel")) != ANNLITE_OK) return rc;
     }
     // queries whose last list overflowed: exact sums over all their probed rows (the other waves leave at once)
     return exact_cells(1, do_sqrt, 1, nullptr);
 }
 
-// ---- the one body behind the three search entries, the one behind the two stage entries, the one behind the two wide entries and the
-// one behind the three size entries ----
+// ---- the one body behind the four search entries, the one behind the three stage entries, the one behind the three wide entries and
+// the one behind the four size entries ----
 template <class F>
 static int ivf_flat_search(const IvfFlatCall &c, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev,
                            size_t workspace_bytes) {
@@ -2459,7 +2654,7 @@ static int ivf_flat_search_wide(const IvfFlatCall &c, int64_t k, int flags, floa
     ANNLITE_REQUIRE(c.q && out_dist_dev && out_id_dev && c.cells && c.cell_rows && (c.n_perm == 0 || (c.x && c.perm)), "null device pointer");
     const WideCells src{c.cells, (int)c.P, (int)c.C, c.cell_rows, c.perm, c.n_perm, 0};
     hipLaunchKernelGGL((flat_exact_wide_kernel<T, WideCells>), dim3((unsigned)c.B), dim3(256), 0, c.st, c.metric, c.q, (int)c.D, (const T *)c.x, c.N,
-                       src, c.valid, (int)k, (flags & ANNLITE_FLAG_SQRT) ? 1 : 0, (float *)nullptr, out_dist_dev, out_id_dev, 1.f);
+                       src, c.valid, (int)k, (flags & ANNLITE_FLAG_SQRT) ? 1 : 0, (float *)nullptr, out_dist_dev, out_id_dev, c.row_scale);
     return launch_status("flat_exact_wide_kernel");
 }
 
@@ -2857,4 +3052,48 @@ extern "C" int annlite_ivf_flat_search_topk_wide_f16(int metric, const float *qu
     const IvfFlatCall c{metric, queries_dev, B, D, vectors_f16_dev, nullptr, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
                         nullptr, 0, 0, nullptr, nullptr, (hipStream_t)stream};
     return ivf_flat_search_wide<IvfF16x2>(c, k, flags, out_dist_dev, out_id_dev);
+}
+
+// ---- int8 rows over cell tiles ("int8 rows over cell tiles"): the scale behind the vectors, checked first ---------
+extern "C" int annlite_ivf_flat_search_i8_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t D, int64_t k, int64_t *bytes) {
+    return ivf_flat_workspace_bytes<IvfI8x3>(B, P, C, D, k, bytes);
+}
+
+extern "C" int annlite_ivf_flat_filter_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev, float scale,
+                                          const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev,
+                                          int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                                          const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t stride,
+                                          float *query_norms_out_dev, float *query_slack_out_dev, const float *bounds_dev,
+                                          int32_t *cand_dev, int32_t *count_dev, float *scores_dev, void *workspace_dev,
+                                          size_t workspace_bytes, void *stream) {
+    ANNLITE_REQUIRE_I8_SCALE(scale);
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_i8_dev, norms_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        cell_order_dev, max_cell_rows, 0, nullptr, nullptr, (hipStream_t)stream, scale};
+    IvfFlatI8Ws w{};
+    if (int rc = ivf_flat_stage<IvfI8x3>(c, stride, bounds_dev, cand_dev, count_dev, nullptr, scores_dev, workspace_dev, workspace_bytes, &w))
+        return rc;
+    if (int rc = flat_hand_back(query_norms_out_dev, w.i.f.qnorm, B, c.st)) return rc;
+    return flat_hand_back(query_slack_out_dev, w.qslack, B, c.st);
+}
+
+extern "C" int annlite_ivf_flat_search_topk_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev,
+                                               float scale, const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev,
+                                               const int32_t *cells_dev, int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm,
+                                               const int64_t *cell_rows_dev, const int32_t *cell_order_dev, int64_t max_cell_rows,
+                                               int64_t max_probed_rows, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev,
+                                               void *workspace_dev, size_t workspace_bytes, void *stream) {
+    ANNLITE_REQUIRE_I8_SCALE(scale);
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_i8_dev, norms_dev, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        cell_order_dev, max_cell_rows, max_probed_rows, nullptr, nullptr, (hipStream_t)stream, scale};
+    return ivf_flat_search<IvfI8x3>(c, k, flags, out_dist_dev, out_id_dev, workspace_dev, workspace_bytes);
+}
+
+extern "C" int annlite_ivf_flat_search_topk_wide_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev,
+                                                    float scale, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P,
+                                                    int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k,
+                                                    int flags, float *out_dist_dev, int64_t *out_id_dev, void *stream) {
+    ANNLITE_REQUIRE_I8_SCALE(scale);
+    const IvfFlatCall c{metric, queries_dev, B, D, vectors_i8_dev, nullptr, N, valid_bits_dev, cells_dev, P, C, perm_dev, n_perm, cell_rows_dev,
+                        nullptr, 0, 0, nullptr, nullptr, (hipStream_t)stream, scale};
+    return ivf_flat_search_wide<IvfI8x3>(c, k, flags, out_dist_dev, out_id_dev);
 }

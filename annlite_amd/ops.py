@@ -1105,23 +1105,24 @@ def ivf_flat_stages(max_probed_rows: int) -> List[int]:
 
 
 def _ivf_flat_operands(suffix: str, k: int, metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows,
-                       valid_bits, n_rows, workspace):
+                       valid_bits, n_rows, workspace, after_vectors=()):
     """What the searches and the stages over cells share: ``(B, N)``, the workspace by ``annlite_ivf_flat_search<suffix>_workspace_bytes`` (the
-    f32 entry, ``suffix == ''``, takes no D) and the arguments of every entry up to ``max_cell_rows``."""
+    f32 entry, ``suffix == ''``, takes no D) and the arguments of every entry up to ``max_cell_rows``; ``after_vectors``: what the entry
+    takes behind the vectors (int8: the scale)."""
     B, D = queries.shape
     P = cells.shape[1]
     N = vectors.shape[0] if n_rows is None else n_rows
     ws = _flat_workspace(f'ivf_flat_search{suffix}_workspace_bytes', (B, P, n_cells) + ((D,) if suffix else ()) + (k,), queries.device, workspace)
-    return (B, N), ws, (int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), norms.data_ptr(), N, _ptr(valid_bits), cells.data_ptr(), P,
+    return (B, N), ws, (int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), *after_vectors, norms.data_ptr(), N, _ptr(valid_bits), cells.data_ptr(), P,
                         int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(), cell_order.data_ptr(), int(max_cell_rows))
 
 
 def _ivf_flat_search(suffix: str, metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, max_probed_rows,
-                     k, valid_bits, n_rows, sqrt, workspace, centres=()):
+                     k, valid_bits, n_rows, sqrt, workspace, centres=(), after_vectors=()):
     """``annlite_ivf_flat_search_topk<suffix>``; ``centres``: what the entry takes behind ``max_probed_rows`` (the bf16x3 filter's centres and
     ``cell_of``)."""
     (B, _), ws, head = _ivf_flat_operands(suffix, k, metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows,
-                                          valid_bits, n_rows, workspace)
+                                          valid_bits, n_rows, workspace, after_vectors)
     od, oi = _flat_topk_outputs(B, k, queries.device)
     entry = 'ivf_flat_search_topk' + suffix
     check(getattr(lib(), 'annlite_' + entry)(*head, int(max_probed_rows), *centres, int(k), 1 if sqrt else 0, od.data_ptr(), oi.data_ptr(),
@@ -1130,11 +1131,11 @@ def _ivf_flat_search(suffix: str, metric, queries, vectors, norms, cells, n_cell
 
 
 def _ivf_flat_stage(suffix: str, metric, queries, vectors, norms, bounds, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, valid_bits,
-                    n_rows, stride, scores, workspace, handed_back, lead, trail=()):
+                    n_rows, stride, scores, workspace, handed_back, lead, trail=(), after_vectors=()):
     """``annlite_ivf_flat_filter<suffix>``: ``(cand, count, *handed_back[, scores])``.  ``handed_back``: the per-filter outputs, which the entry
     takes among ``lead`` (behind the stride) or ``trail`` (behind the lists)."""
     (B, N), ws, head = _ivf_flat_operands(suffix, 1, metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows,
-                                          valid_bits, n_rows, workspace)
+                                          valid_bits, n_rows, workspace, after_vectors)
     cand, count, sc = _flat_lists(B, queries.device, N if scores else None)
     entry = 'ivf_flat_filter' + suffix
     check(getattr(lib(), 'annlite_' + entry)(*head, int(stride), *lead, bounds.data_ptr(), cand.data_ptr(), count.data_ptr(), *trail, _ptr(sc),
@@ -1221,6 +1222,34 @@ def ivf_flat_search_topk_f16(metric: int, queries: torch.Tensor, vectors: torch.
     assert vectors.dtype == torch.float16
     return _ivf_flat_search('_f16', metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, max_probed_rows, k,
                             valid_bits, n_rows, sqrt, workspace)
+
+
+def ivf_flat_filter_i8(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, bounds: torch.Tensor, scale: float,
+                       cells: torch.Tensor, n_cells: int, perm: torch.Tensor, cell_rows: torch.Tensor, cell_order: torch.Tensor,
+                       max_cell_rows: int, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, stride: int = 1,
+                       scores: bool = False, workspace: Optional[ScanWorkspace] = None):
+    """``annlite_ivf_flat_filter_i8``: the int8 filter stage over the (cell, queries) tiles alone -- ``flat_filter_i8`` of the cells
+    (``vectors`` int8 [N, D] read as ``scale * c``, ``norms``: ``flat_row_norms_i8`` with the same scale).  ``(cand i32 [B, cap], count
+    i32 [B], query_norms f32 [B], query_slack f32 [B])`` -- the last two as the filter used them -- and, with ``scores=True``, the
+    filter's score by (query, row offset), f32 [B, N]: NaN where the filter evaluated nothing (cell not probed, row not valid, row not
+    at the stride)."""
+    assert vectors.dtype == torch.int8
+    qn, qs = (torch.empty((queries.shape[0],), dtype=torch.float32, device=queries.device) for _ in range(2))
+    return _ivf_flat_stage('_i8', metric, queries, vectors, norms, bounds, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, valid_bits,
+                           n_rows, stride, scores, workspace, (qn, qs), lead=(qn.data_ptr(), qs.data_ptr()), after_vectors=(float(scale),))
+
+
+def ivf_flat_search_topk_i8(metric: int, queries: torch.Tensor, vectors: torch.Tensor, norms: torch.Tensor, cells: torch.Tensor,
+                            n_cells: int, perm: torch.Tensor, cell_rows: torch.Tensor, cell_order: torch.Tensor, max_cell_rows: int,
+                            max_probed_rows: int, k: int, scale: float, valid_bits: Optional[torch.Tensor] = None,
+                            n_rows: Optional[int] = None, sqrt: bool = False,
+                            workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_ivf_flat_search_topk_i8``: ``ivf_flat_search_topk`` over ``vectors`` int8 [N, D] read as ``scale * c`` (``norms``:
+    ``flat_row_norms_i8``) with the int8 filter over the cell tiles: the answer of ``ivf_flat_search_topk`` over those f32 rows, bit for
+    bit.  ``flat_overflow_count`` / ``flat_list_counts`` read this workspace too."""
+    assert vectors.dtype == torch.int8
+    return _ivf_flat_search('_i8', metric, queries, vectors, norms, cells, n_cells, perm, cell_rows, cell_order, max_cell_rows, max_probed_rows, k,
+                            valid_bits, n_rows, sqrt, workspace, after_vectors=(float(scale),))
 
 
 # ---------------------------------------------------------------------------------------------- PCA projector
@@ -1485,16 +1514,18 @@ def flat_search_topk_wide(flat_filter: str, metric: int, queries: torch.Tensor, 
 
 def ivf_flat_search_topk_wide(metric: int, queries: torch.Tensor, vectors: torch.Tensor, cells: torch.Tensor, n_cells: int, perm: torch.Tensor,
                               cell_rows: torch.Tensor, k: int, valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None,
-                              sqrt: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                              sqrt: bool = False, scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
     """``annlite_ivf_flat_search_topk_wide``: exact k nearest (``64 < k <= 1024``) among the rows of each query's probed ``cells`` i32
     [B, P] (``perm`` / ``cell_rows`` as ``ivf_flat_search_topk``), one launch: ``(dist f32 [B, k], ids i64 [B, k])`` ascending by
-    (distance, id), (+inf, -1) padded.  ``vectors`` f16: ``annlite_ivf_flat_search_topk_wide_f16``, the same over the widened rows."""
+    (distance, id), (+inf, -1) padded.  ``vectors`` f16: ``annlite_ivf_flat_search_topk_wide_f16``, the same over the widened rows; int8:
+    ``annlite_ivf_flat_search_topk_wide_i8`` over the rows ``scale * c``."""
     B, D = queries.shape
     N = vectors.shape[0] if n_rows is None else n_rows
     od, oi = _flat_topk_outputs(B, k, queries.device)
-    assert vectors.dtype in (torch.float32, torch.float16)
-    entry = 'ivf_flat_search_topk_wide' + ('_f16' if vectors.dtype == torch.float16 else '')
-    check(getattr(lib(), 'annlite_' + entry)(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, _ptr(valid_bits), cells.data_ptr(),
+    suffix = {torch.float32: '', torch.float16: '_f16', torch.int8: '_i8'}[vectors.dtype]
+    entry = 'ivf_flat_search_topk_wide' + suffix
+    after_vectors = (float(scale),) if suffix == '_i8' else ()
+    check(getattr(lib(), 'annlite_' + entry)(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), *after_vectors, N, _ptr(valid_bits), cells.data_ptr(),
                                              cells.shape[1], int(n_cells), perm.data_ptr(), perm.numel(), cell_rows.data_ptr(), int(k),
                                              1 if sqrt else 0, od.data_ptr(), oi.data_ptr(), stream_ptr()), entry)
     return od, oi

@@ -826,6 +826,30 @@ ANNLITE_API int annlite_ivf_flat_search_topk_f16(int metric, const float *querie
                                      int flags, float *out_dist_dev, int64_t *out_id_dev, void *workspace_dev, size_t workspace_bytes,
                                      void *stream);
 
+/* The same search over int8 ROWS ("int8 rows over cell tiles"): vectors_i8_dev int8 [N][D] read as scale * code
+ * as annlite_flat_search_topk_i8 reads them (scale: a power of two in [2^-24, 2^24], checked first), norms_dev =
+ * annlite_flat_row_norms_i8 with that scale.  The filter stage is annlite_flat_search_topk_i8's contraction -- the codes as stored, the
+ * query as three int8 digit planes, integer MFMAs, no rounding -- over the (cell, queries) tiles, the rows gathered through the cell
+ * permutation; the exact stages read scale * code in annlite_exact_gather_dist_i8's arithmetic.  The answer is
+ * annlite_ivf_flat_search_topk's over the rows scale * code, bit for bit.  1 <= D <= 32768.  No reference counterpart. */
+ANNLITE_API int annlite_ivf_flat_search_i8_workspace_bytes(int64_t B, int64_t P, int64_t C, int64_t D, int64_t k, int64_t *bytes);
+/* The int8 filter stage alone (tests and measurements): the annlite_flat_filter_i8 of the cells, arguments as annlite_ivf_flat_filter_f16
+ * with the scale behind the vectors; query_slack_out_dev (may be NULL) f32 [B] receives the per-query term of the slack. */
+ANNLITE_API int annlite_ivf_flat_filter_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev, float scale,
+                               const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P,
+                               int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev,
+                               const int32_t *cell_order_dev, int64_t max_cell_rows, int64_t stride, float *query_norms_out_dev,
+                               float *query_slack_out_dev, const float *bounds_dev, int32_t *cand_dev, int32_t *count_dev,
+                               float *scores_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* annlite_ivf_flat_search_topk over int8 rows: the same stages, lists, capacity and overflow route (annlite_flat_overflow_count and
+ * annlite_flat_list_counts read this workspace too). */
+ANNLITE_API int annlite_ivf_flat_search_topk_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev,
+                                    float scale, const float *norms_dev, int64_t N, const uint32_t *valid_bits_dev,
+                                    const int32_t *cells_dev, int64_t P, int64_t C, const int32_t *perm_dev, int64_t n_perm,
+                                    const int64_t *cell_rows_dev, const int32_t *cell_order_dev, int64_t max_cell_rows,
+                                    int64_t max_probed_rows, int64_t k, int flags, float *out_dist_dev, int64_t *out_id_dev,
+                                    void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * limit above 64 ("limit above 64"): the exact searches above for 64 < k <= 1024.  A workgroup per query scores
  * its candidates in the arithmetic of every exact stage (the distances of annlite_flat_search_topk / annlite_exact_gather_dist, bit
@@ -854,6 +878,12 @@ ANNLITE_API int annlite_ivf_flat_search_topk_wide_f16(int metric, const float *q
                                           int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P, int64_t C,
                                           const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k, int flags,
                                           float *out_dist_dev, int64_t *out_id_dev, void *stream);
+/* ... over int8 rows (vectors_i8_dev int8 [N][D] read as scale * code): annlite_ivf_flat_search_topk_wide's answer over those f32 rows,
+ * bit for bit. */
+ANNLITE_API int annlite_ivf_flat_search_topk_wide_i8(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev,
+                                         float scale, int64_t N, const uint32_t *valid_bits_dev, const int32_t *cells_dev, int64_t P,
+                                         int64_t C, const int32_t *perm_dev, int64_t n_perm, const int64_t *cell_rows_dev, int64_t k,
+                                         int flags, float *out_dist_dev, int64_t *out_id_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pruned (IVF) search over cells (follow-on of rank 4).

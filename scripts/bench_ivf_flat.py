@@ -8,10 +8,13 @@ profiles/ivf_flat/bench_ivf_flat.jsonl.
     python scripts/bench_ivf_flat.py --filter both                     # cell_filter='f32' against 'bf16x3' 
     python scripts/bench_ivf_flat.py --filter both --offset 1000       # ... on data with a common offset
     python scripts/bench_ivf_flat.py --ivf-rows both                   # f32 rows against ivf_rows='f16' ("f16 rows")
+    python scripts/bench_ivf_flat.py --ivf-rows all --data-scale 40    # ... and against ivf_rows='i8' ("int8 rows"), sigma = 40 code steps
 
 --ivf-rows both (the row count owns --rows): the f32 index, the index over f16 rows, and that same index with the filter's 64-coordinate
 stage (ANNLITE_IVF_F16_STAGE=64, path 'f16/stage64') alternate round by round.  The f16 paths hold other rows than the f32 path -- the
-rounded ones -- so their answers are compared with each other, and their recall is reported per path.
+rounded ones -- so their answers are compared with each other, and their recall is reported per path.  --ivf-rows all adds the index over
+int8 rows (int8_scale 1.0: give the data a --data-scale) and that same index with the 128-coordinate stage (ANNLITE_IVF_I8_STAGE=128, path
+'i8/stage128'); the recall of every path is against the exhaustive search over the first path's rows -- with `all`, the unrounded f32 rows.
 
 --filter both: two indexes over the same rows and the same codebook, one per cell filter; the paths alternate round by round in this
 process.  The top-level `pruned_*` / `list_*` / `overflowed_queries` keys describe the first path (`filter`); `paths` holds, per filter
@@ -22,7 +25,8 @@ Recall: against the exhaustive search's answer, which is exact.  Filter time: th
 records no kernels); `pruned_search_kernels` lists every kernel of that search as (launches, ms).
 """
 FILTER_KERNEL = {'f32': 'ivf_flat_filter_kernel', 'bf16x3': 'ivf_flat_split_filter_kernel', 'f16': 'ivf_flat_f16_filter_kernel',
-                 'f16/stage64': 'ivf_flat_f16_filter_kernel'}
+                 'f16/stage64': 'ivf_flat_f16_filter_kernel', 'i8': 'ivf_flat_i8_filter_kernel', 'i8/stage128': 'ivf_flat_i8_filter_kernel'}
+STAGE_SWITCH = {'f16/stage64': ('ANNLITE_IVF_F16_STAGE', '64'), 'i8/stage128': ('ANNLITE_IVF_I8_STAGE', '128')}
 import argparse
 import json
 import os
@@ -46,7 +50,10 @@ def main():
     ap.add_argument('--probe', type=int, default=16)
     ap.add_argument('--data', default='normal', choices=['normal', 'lowrank'])
     ap.add_argument('--filter', default='f32', choices=['f32', 'bf16x3', 'both'], help='cell_filter of the pruned path(s)')
-    ap.add_argument('--ivf-rows', default='f32', choices=['f32', 'f16', 'both'], help="ivf_rows of the pruned path(s); not with --filter bf16x3 / both")
+    ap.add_argument('--ivf-rows', default='f32', choices=['f32', 'f16', 'both', 'i8', 'all'],
+                    help="ivf_rows of the pruned path(s) (both: f32 and f16; all: f32, f16 and i8); not with --filter bf16x3 / both")
+    ap.add_argument('--data-scale', type=float, default=1.0, help='rows, training rows and queries are multiplied by it (int8 rows: the '
+                    'standard deviation in code steps of the default int8_scale 1.0, as in bench_flat.py)')
     ap.add_argument('--offset', type=float, default=0.0, help='added to rows, training rows and queries')
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--steps', type=int, default=5, help='batches per round and path')
@@ -73,6 +80,7 @@ def main():
             x = torch.randn((n, D), generator=gen, device=dev)
         else:
             x = torch.randn((n, 8), generator=gen, device=dev) @ A + 0.1 * torch.randn((n, D), generator=gen, device=dev)
+        x = x * args.data_scale if args.data_scale != 1.0 else x
         return x + args.offset if args.offset else x
 
     step = 1 << 20
@@ -83,9 +91,14 @@ def main():
     filters = ['f32', 'bf16x3'] if args.filter == 'both' else [args.filter]
     paths = {f: IvfFlatGpuIndex(D, vq_codec=vq, n_probe=P, metric=metric, initial_size=N, cell_filter=f) for f in filters}
     if args.ivf_rows != 'f32':
-        assert args.filter == 'f32', "--ivf-rows f16 / both runs the f16 filter: not with --filter bf16x3 / both"
-        half = IvfFlatGpuIndex(D, vq_codec=vq, n_probe=P, metric=metric, initial_size=N, ivf_rows='f16')
-        paths = {**(paths if args.ivf_rows == 'both' else {}), 'f16': half, 'f16/stage64': half}
+        assert args.filter == 'f32', "--ivf-rows f16 / i8 / both / all run the row kind's own filter: not with --filter bf16x3 / both"
+        paths = paths if args.ivf_rows in ('both', 'all') else {}
+        if args.ivf_rows != 'i8':
+            half = IvfFlatGpuIndex(D, vq_codec=vq, n_probe=P, metric=metric, initial_size=N, ivf_rows='f16')
+            paths = {**paths, 'f16': half, 'f16/stage64': half}
+        if args.ivf_rows in ('i8', 'all'):
+            quarter = IvfFlatGpuIndex(D, vq_codec=vq, n_probe=P, metric=metric, initial_size=N, ivf_rows='i8')
+            paths = {**paths, 'i8': quarter, 'i8/stage128': quarter}
         filters = list(paths)
     for r0 in range(0, N, step):
         n = min(step, N - r0)
@@ -99,10 +112,11 @@ def main():
     def exhaustive():
         return FlatGpuIndex.search_batch(idx, q, limit=k)
 
-    def stage(f):  # the library reads the switch when it is told to: the f16 paths differ in it alone
-        os.environ.pop('ANNLITE_IVF_F16_STAGE', None)
-        if f == 'f16/stage64':
-            os.environ['ANNLITE_IVF_F16_STAGE'] = '64'
+    def stage(f):  # the library reads the switches when it is told to: the two paths of a row kind differ in its switch alone
+        for name, _ in STAGE_SWITCH.values():
+            os.environ.pop(name, None)
+        if f in STAGE_SWITCH:
+            os.environ[STAGE_SWITCH[f][0]] = STAGE_SWITCH[f][1]
         _capi.knobs_reload()
 
     def timed(fn):
@@ -125,9 +139,9 @@ def main():
             stage(f)
             t, answers[f] = timed(lambda: paths[f].search_batch(q, limit=k))
             ms_p[f].append(t)
-    for f in filters[1:]:  # (the filters differ in what they list, never in the answer; the f16 paths answer over other rows than f32's)
-        same = 'f16' if f == 'f16/stage64' else filters[0]
-        if f != 'f16':
+    for f in filters[1:]:  # (the filters differ in what they list, never in the answer; the f16 / i8 paths answer over other rows than f32's)
+        same = f.split('/')[0] if f in STAGE_SWITCH else filters[0]
+        if f not in ('f16', 'i8'):
             assert torch.equal(answers[f][1], answers[same][1]) and torch.equal(answers[f][0], answers[same][0]), f
     dp, ip = answers[filters[0]]
     sizes = (idx._cell_rows[:, 1] - idx._cell_rows[:, 0]).cpu().numpy()
