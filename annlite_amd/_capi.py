@@ -64,6 +64,10 @@ SYMBOLS = (
     'annlite_graph_f16_search_admit',
     'annlite_graph_f16_build_select',
     'annlite_graph_f16_build_reverse',
+    'annlite_graph_i8_search',
+    'annlite_graph_i8_search_admit',
+    'annlite_graph_i8_build_select',
+    'annlite_graph_i8_build_reverse',
     'annlite_adc_scan_topk',
     'annlite_adc_scan_topk_packed',
     'annlite_pq_search_workspace_bytes',
@@ -267,6 +271,11 @@ def lib() -> ctypes.CDLL:
     L.annlite_graph_f16_search_admit.argtypes = L.annlite_graph_f32_search_admit.argtypes
     L.annlite_graph_f16_build_select.argtypes = L.annlite_graph_f32_build_select.argtypes
     L.annlite_graph_f16_build_reverse.argtypes = L.annlite_graph_f32_build_reverse.argtypes
+    # (the f32 forms with `float scale` behind the row pointer)
+    L.annlite_graph_i8_search.argtypes = [i32, vp, i64, i64, vp, ctypes.c_float, i64, vp, i32, vp, i64, vp, i32, vp, vp, vp]
+    L.annlite_graph_i8_search_admit.argtypes = [i32, vp, i64, i64, vp, ctypes.c_float, i64, vp, i32, vp, i64, vp, i32, i32, vp, vp, vp, vp]
+    L.annlite_graph_i8_build_select.argtypes = [i32, vp, i32, i64, i64, vp, ctypes.c_float, i64, i64, i32, vp, i32, vp, vp]
+    L.annlite_graph_i8_build_reverse.argtypes = [i32, vp, vp, i64, vp, ctypes.c_float, i64, i64, vp, i32, vp]
     L.annlite_adc_scan_topk.argtypes = [vp, i32, i32, i64, i64, i64, vp, vp, i64, i64, i64, vp, vp, vp, sz, vp]
     L.annlite_adc_scan_candidates.argtypes = L.annlite_adc_scan_topk.argtypes
     L.annlite_pq_search_candidates.argtypes = [i32, vp, i64, i64, vp, vp, i32, i32, i64, i64, i64, vp, i64, i64, vp, vp, vp, sz, vp]

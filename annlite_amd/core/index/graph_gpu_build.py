@@ -26,8 +26,11 @@ Two distance backends share the batching, the seeds, the pair sort and the persi
     records and no second copy of the vectors; below ``BRUTE`` nodes the candidate lists come from one torch product in the metric's
     order (the select kernel recomputes every distance it compares: only the visiting order is torch's).  ``rows='f16'``: the column
     is the half-precision row store -- the ``annlite_graph_f16_*`` entry points (``graph_f16.hip``), the torch product and the build
-    walk's queries over the widened rows: the f32 graph of the rounded rows, link for link.
+    walk's queries over the widened rows: the f32 graph of the rounded rows, link for link.  ``rows='i8'``, ``scale=s``: the int8 row
+    store -- the ``annlite_graph_i8_*`` entry points (``graph_i8.hip``) with the scale bound in, the torch product and the build
+    walk's queries over ``s * codes``: the f32 graph of those rows, link for link.
 """
+from functools import partial
 from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
@@ -217,20 +220,32 @@ class _RowWalk(NamedTuple):
 ROW_WALKS = {'f32': _RowWalk(torch.float32, ops.graph_f32_search, ops.graph_f32_search_admit, ops.graph_f32_build_select,
                              ops.graph_f32_build_reverse),
              'f16': _RowWalk(torch.float16, ops.graph_f16_search, ops.graph_f16_search_admit, ops.graph_f16_build_select,
-                             ops.graph_f16_build_reverse)}
+                             ops.graph_f16_build_reverse),
+             'i8': _RowWalk(torch.int8, ops.graph_i8_search, ops.graph_i8_search_admit, ops.graph_i8_build_select,
+                            ops.graph_i8_build_reverse)}
 
 
 class GpuLevel0GraphF32(Level0GraphBase):
     """The float backend: ``annlite_graph_f32_search`` / ``_build_select`` / ``_build_reverse`` over the rows of a vector column the
     CALLER owns (``add(vectors, n_new)``: rows ``self.n .. self.n + n_new`` of ``vectors`` are stored already).  ``metric``: the C
     ABI's number; COSINE rows arrive normalised.  ``rows``: ``'f32'`` or ``'f16'``, the column's format -- ``'f16'`` goes to the
-    ``annlite_graph_f16_*`` entry points (``walk``), with f32 queries: the widened rows."""
+    ``annlite_graph_f16_*`` entry points (``walk``), with f32 queries: the widened rows.  ``'i8'``: int8 codes of ``scale`` (a power of
+    two, required), to the ``annlite_graph_i8_*`` entry points with that scale bound in; the widened rows are ``scale * codes``."""
 
-    def __init__(self, device, metric: int, max_connection: int = 16, ef_construction: int = 200, rows: str = 'f32'):
+    def __init__(self, device, metric: int, max_connection: int = 16, ef_construction: int = 200, rows: str = 'f32',
+                 scale: Optional[float] = None):
         super().__init__(device, max_connection, ef_construction)
         self.metric = int(metric)
         self.walk = ROW_WALKS[rows]
+        assert (scale is not None) == (rows == 'i8'), 'scale is the scale of int8 rows'
+        if scale is not None:
+            self.walk = _RowWalk(self.walk.dtype, *(partial(fn, scale=float(scale)) for fn in self.walk[1:]))
+        self.scale = scale
         self._v = None
+
+    def _widened(self, rows: torch.Tensor) -> torch.Tensor:
+        """rows of the column as the f32 values the kernels read (exact)"""
+        return rows.float() if self.scale is None else rows.float() * self.scale
 
     def add(self, vectors: torch.Tensor, n_new: int):
         if n_new == 0:
@@ -247,7 +262,7 @@ class GpuLevel0GraphF32(Level0GraphBase):
         """The ``ef_construction`` nearest of the n + b stored rows (batch mates included, the point itself not), ascending in the
         metric's order: squared L2 (COSINE rows are normalised: the same order), or minus the inner product."""
         total = n + b
-        rows = self._v[:total].float()  # (f16 rows: the same product over the widened rows)
+        rows = self._widened(self._v[:total])  # (f16 / int8 rows: the same product over the widened rows)
         x = rows[n:]
         if self.metric == int(Metric.INNER_PRODUCT):  # 1 - <q, x> ascends as <q, x> descends
             d = -(x @ rows.T)
@@ -261,7 +276,7 @@ class GpuLevel0GraphF32(Level0GraphBase):
         return cand
 
     def _walk_candidates(self, pos: int, n: int, b: int) -> torch.Tensor:
-        cand, _ = self.walk.search(self.metric, self._v[n: n + b].float(), self._v, self.links, self.seeds(), self.efc, n_rows=n)
+        cand, _ = self.walk.search(self.metric, self._widened(self._v[n: n + b]), self._v, self.links, self.seeds(), self.efc, n_rows=n)
         return cand
 
     def _select(self, cand: torch.Tensor, n: int, b: int) -> torch.Tensor:

@@ -26,6 +26,12 @@ rows rounded once to nearest even when added, half the HBM, norms, validity and 
 beside it, built and walked by the ``annlite_graph_f16_*`` entry points (``graph_f16.hip``: a quarter wave per row; DESIGN.md section
 3.8, "f16 rows").  Every distance carries ``annlite_exact_gather_dist_f16``'s bits: links, ids and distances are those of an f32 graph
 index fed the rounded rows, bit for bit.  (``dtype=np.float16`` without the keyword stays refused: the keyword is the opt-in.)
+
+``graph_rows='i8'`` (opt-in as well) keeps it over INT8 rows: the index is the int8 ``FlatGpuIndex`` -- codes
+``clamp(rne(x / s), -127, 127)`` of the power-of-two ``int8_scale`` ``s`` (default 1.0, or 2**-7 for COSINE), a quarter of the HBM --
+with the link lists beside it, built and walked by the ``annlite_graph_i8_*`` entry points (``graph_i8.hip``: an eighth wave per row;
+DESIGN.md section 3.8, "int8 rows").  Every distance carries ``annlite_exact_gather_dist_i8``'s bits: links, ids and distances are those
+of an f32 graph index fed the rows ``s * c``, bit for bit.  (``dtype=np.int8`` without the keyword stays refused.)
 """
 from pathlib import Path
 from typing import List, Optional, Tuple, Union
@@ -45,7 +51,7 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
     ALSO_LOADS = (FlatGpuIndex.FORMAT,)  # (rows without links: the graph is rebuilt from them)
     MAX_EF = 256                         # the walk's list: four registers per lane
     MAX_DIM = 2048
-    GRAPH_ROWS = ('f32', 'f16')
+    GRAPH_ROWS = ('f32', 'f16', 'i8')
     # (a filter per query: one search_batch per group -- the graph search stays the search it is under every selection)
     search_batch_grouped = RowStoreIndex.search_batch_grouped
     # DESIGN.md section 3.8, table "filtered walk" (1M x 128): the smallest measured share of admitted rows at which the filtered walk
@@ -65,16 +71,18 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
             raise ValueError(f'dim={dim}: the float graph takes 1 <= dim <= {self.MAX_DIM}')
         self._check_filter_search(filter_search, "the parent's exact filtered search")
         if graph_rows not in self.GRAPH_ROWS:
-            raise ValueError(f"graph_rows={graph_rows!r}: 'f32' (default) or 'f16' (the graph over half-precision rows)")
+            raise ValueError(f"graph_rows={graph_rows!r}: 'f32' (default), 'f16' (the graph over half-precision rows) or 'i8' (over "
+                             'int8 rows)')
         if is_f16(dtype) and graph_rows != 'f16':
             raise NotImplementedError("dtype=np.float16: the float graph walks and builds over f32 rows unless graph_rows='f16' opts into "
                                       'the graph over half-precision rows (they also exist in the exhaustive FlatGpuIndex: no graph, '
                                       'n_cells=1)')
-        if is_i8(dtype):
-            raise NotImplementedError('dtype=np.int8: the float graph walks and builds over f32 rows only (int8 rows exist '
-                                      'in the exhaustive FlatGpuIndex: no graph, n_cells=1)')
+        if is_i8(dtype) and graph_rows != 'i8':
+            raise NotImplementedError("dtype=np.int8: the float graph walks and builds over f32 rows unless graph_rows='i8' opts into "
+                                      'the graph over int8 rows (they also exist in the exhaustive FlatGpuIndex: no graph, n_cells=1)')
         self.graph_rows = graph_rows
-        super().__init__(dim, dtype=np.float16 if graph_rows == 'f16' else dtype, metric=metric, **kwargs)
+        # (int8_scale rides in kwargs: the parent takes it with int8 rows and refuses it with any other)
+        super().__init__(dim, dtype={'f16': np.float16, 'i8': np.int8}.get(graph_rows, dtype), metric=metric, **kwargs)
         self.ef_construction = int(ef_construction)  # hnsw/index.py:66-69
         self.ef_search = int(ef_search)
         self.max_connection = int(max_connection)
@@ -90,7 +98,8 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
         if self._gg is None:
             from .graph_gpu_build import GpuLevel0GraphF32
 
-            self._gg = GpuLevel0GraphF32(self._device(), int(self.metric), self.max_connection, self.ef_construction, rows=self.graph_rows)
+            self._gg = GpuLevel0GraphF32(self._device(), int(self.metric), self.max_connection, self.ef_construction, rows=self.graph_rows,
+                                         scale=self._i8_scale)
         return self._gg
 
     def _rebuild_graph(self, N: int):
@@ -206,7 +215,7 @@ class HnswFlatGpuIndex(FilterWalkMixin, FlatGpuIndex):
         super()._load_state(state, N)
         self._gg = None
         links = state.get('links')
-        if N and np.asarray(state['vectors']).dtype != np.dtype(np.float16 if self.graph_rows == 'f16' else np.float32):
+        if N and np.asarray(state['vectors']).dtype != np.dtype({'f16': np.float16, 'i8': np.int8}.get(self.graph_rows, np.float32)):
             links = None  # (rows of the other kind were converted: links built over other bits are not this index's graph)
         if N and links is not None and links.shape == (N, 2 * self.max_connection + 1):
             self._ensure_graph().load_state({'n': N, 'links': links})

@@ -177,13 +177,8 @@ __global__ __launch_bounds__(256) void kmeans_update_kernel(const float *__restr
 
 // ---- exact distances over candidate lists: one wave per (query, candidate) -------------------------
 // T: the row type, float or _Float16 (FlatGpuIndex's half-precision row store): an f16 value widens exactly, the rest is the f32 form's.
-// int8_t (its int8 row store): a code c stands for scale * c, scale a power of two -- exact as well; `scale` is read by that form only.
-template <class T>
-__device__ __forceinline__ float exact_gather_widen(T v, float scale) {
-    if constexpr (std::is_same<T, int8_t>::value) return scale * (float)v;
-    else return (float)v;
-}
-
+// int8_t (its int8 row store): a code c stands for scale * c, scale a power of two -- exact as well; `scale` is read by that form only
+// (exact_gather_widen, common.h: the float graph's distances widen through it too).
 template <class T>
 __global__ __launch_bounds__(256) void exact_gather_kernel(int metric, const float *__restrict__ q, int B, int D,
                                                           const T *__restrict__ x, int64_t N,

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/annlite_hip.h"
 
 namespace annlite {
@@ -34,6 +36,14 @@ inline int i8_scale_log2(float scale) {
 }
 #define ANNLITE_REQUIRE_I8_SCALE(scale) \
     ANNLITE_REQUIRE(::annlite::i8_scale_log2(scale) != INT32_MIN, "bad int8 scale %g (a power of two in [2^-24, 2^24])", (double)(scale))
+
+// A stored element as the exact distances read it (exact_gather_kernel, codec.hip; rows_dist, graph_rows.h): f32 as it is, f16 widened
+// exactly, an int8 code c as scale * c -- exact as well, scale being such a power of two; `scale` is read by that form only.
+template <class T>
+__device__ __forceinline__ float exact_gather_widen(T v, float scale) {
+    if constexpr (std::is_same<T, int8_t>::value) return scale * (float)v;
+    else return (float)v;
+}
 
 inline int launch_status(const char *kernel) {
     hipError_t e = hipGetLastError();

@@ -32,16 +32,6 @@ constexpr bool kLayoutB = false;
 constexpr bool kLayoutB = true;
 #endif
 
-// v of lane (lane ^ O), O in {8, 4, 2, 1}: inside a group of 16 lanes.  All lanes active.
-template <int O>
-__device__ __forceinline__ float group_xor(float v) {
-    const int i = __float_as_int(v);
-    if constexpr (O == 8) return __int_as_float(__builtin_amdgcn_update_dpp(0, i, 0x128, 0xf, 0xf, false));       // row_ror:8
-    else if constexpr (O == 4) return __int_as_float(__builtin_amdgcn_ds_swizzle(i, 0x101f));                     // and 0x1f, xor 4
-    else if constexpr (O == 2) return __int_as_float(__builtin_amdgcn_update_dpp(0, i, 0x4e, 0xf, 0xf, false));   // quad_perm [2, 3, 0, 1]
-    else return __int_as_float(__builtin_amdgcn_update_dpp(0, i, 0xb1, 0xf, 0xf, false));                         // quad_perm [1, 0, 3, 2]
-}
-
 // four elements of the query at j (j % 4 == 0, j + 3 < D): the walk's f32 image in LDS (16-byte aligned), or an f16 row
 __device__ __forceinline__ void query4(const float *qv, int j, float (&o)[4]) {
     const f32x4 v = *(const f32x4 *)(qv + j);
@@ -179,8 +169,8 @@ __device__ __forceinline__ float rows_dist_quarter(unsigned long long pm, uint32
 struct RowsF16Quarter {
     typedef _Float16 row_t;
     template <bool L2, class Q>
-    static __device__ __forceinline__ float dist(unsigned long long pm, uint32_t node, const _Float16 *__restrict__ x, int D, const Q *qv,
-                                                 int lane) {
+    __device__ __forceinline__ float dist(unsigned long long pm, uint32_t node, const _Float16 *__restrict__ x, int D, const Q *qv,
+                                          int lane) const {
         return rows_dist_quarter<L2>(pm, node, x, D, qv, lane);
     }
 };

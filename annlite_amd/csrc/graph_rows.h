@@ -1,5 +1,5 @@
 // graph_rows.h -- the level-0 graph over FLOAT vectors: the ONE copy of its walk body, of Algorithm 4 and of its four kernels, for
-// every row format the graph is kept over (graph_f32.hip: f32 rows; graph_f16.hip: f16 rows).  The float forms of graph.hip's plain
+// every row format the graph is kept over (graph_f32.hip: f32 rows; graph_f16.hip: f16 rows; graph_i8.hip: int8 rows).  The float forms of graph.hip's plain
 // walk and of graph_build.hip's two kernels: same link lists (u32 [N][L + 1]: count, ids), same seeds, same list / visited table /
 // merge (graph_beam.h), same selection rules, same pairs / keys / seg formats.  What differs is the distance.
 //
@@ -10,8 +10,10 @@
 // (no re-rank launch), a stored vector finds itself at exactly 0.0 and the arithmetic is symmetric in its two arguments
 // (d * d = (-d) * (-d), x * q = q * x; the butterfly's adds commute).
 //
-// A kernel takes its row distance as the class RD: RD::row_t, the stored element, and RD::dist<L2>(pm, node, x, D, qv, lane) with
-// rows_dist's contract; `qv` is the walk's f32 query in LDS or, in the build, another row of `x`.  RowsStrided<T> is rows_dist itself.
+// A kernel takes its row distance as an instance `rd` of the class RD, by value: RD::row_t, the stored element, and
+// rd.dist<L2>(pm, node, x, D, qv, lane) with rows_dist's contract; `qv` is the walk's f32 query in LDS or, in the build, another row
+// of `x`.  RowsStrided<T> is rows_dist itself.  An RD over f32 or f16 rows is empty; one over int8 rows (graph_i8.hip) carries the
+// rows' scale, the power of two a code step stands for (RowScale).
 //
 // Walk: one wave per query.  Per-wave LDS is the query (D * 4 B), the visited table (16 KB up to ef = 208, 32 KB beyond) and the
 // merge scratch (768 E + 1024 B): 19 KB at D = 128, ef <= 128 -- eight waves per CU, two per SIMD, where the PQ walk's 16 KB look-up
@@ -27,8 +29,10 @@ constexpr int kRowsInFlight = 8;  // rerank_topk_kernel's U
 
 // Distance of `qv` [D] (f32 or a row's own type, widened as it is read; LDS or global, wave-uniform pointer) to the rows x[node] of
 // the lanes in `pm` (node: per lane, < N); a lane of `pm` returns its row's distance, every other lane 0.  Wave-uniform control flow.
+// Elements widen as exact_gather_kernel's do (`scale`: read for int8 elements only).
 template <bool L2, class T, class Q>
-__device__ __forceinline__ float rows_dist(unsigned long long pm, uint32_t node, const T *__restrict__ x, int D, const Q *qv, int lane) {
+__device__ __forceinline__ float rows_dist(unsigned long long pm, uint32_t node, const T *__restrict__ x, int D, const Q *qv, int lane,
+                                           float scale) {
     constexpr int U = kRowsInFlight;
     float mine = 0.f;
     while (pm) {
@@ -46,10 +50,10 @@ __device__ __forceinline__ float rows_dist(unsigned long long pm, uint32_t node,
 #pragma unroll
         for (int u = 0; u < U; ++u) s[u] = 0.f;
         for (int j = lane; j < D; j += 64) {
-            const float qj = (float)qv[j];
+            const float qj = exact_gather_widen(qv[j], scale);
             float xv[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) xv[u] = on[u] ? (float)xr[u][j] : 0.f;
+            for (int u = 0; u < U; ++u) xv[u] = on[u] ? exact_gather_widen(xr[u][j], scale) : 0.f;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if constexpr (L2) {
@@ -72,14 +76,35 @@ __device__ __forceinline__ float rows_dist(unsigned long long pm, uint32_t node,
     return mine;
 }
 
+// what a row distance over rows of T carries: nothing, or for int8 rows the scale (a code c stands for scale * c)
 template <class T>
-struct RowsStrided {
+struct RowScale {
+    static constexpr float scale = 1.f;
+};
+template <>
+struct RowScale<int8_t> {
+    float scale;
+};
+
+template <class T>
+struct RowsStrided : RowScale<T> {
     typedef T row_t;
     template <bool L2, class Q>
-    static __device__ __forceinline__ float dist(unsigned long long pm, uint32_t node, const T *__restrict__ x, int D, const Q *qv, int lane) {
-        return rows_dist<L2>(pm, node, x, D, qv, lane);
+    __device__ __forceinline__ float dist(unsigned long long pm, uint32_t node, const T *__restrict__ x, int D, const Q *qv, int lane) const {
+        return rows_dist<L2>(pm, node, x, D, qv, lane, this->scale);
     }
 };
+
+// v of lane (lane ^ O), O in {8, 4, 2, 1}: inside a group of 16 (or 8) lanes, for the row distances that give a row to part of a
+// wave (graph_f16.hip, graph_i8.hip).  All lanes active.
+template <int O>
+__device__ __forceinline__ float group_xor(float v) {
+    const int i = __float_as_int(v);
+    if constexpr (O == 8) return __int_as_float(__builtin_amdgcn_update_dpp(0, i, 0x128, 0xf, 0xf, false));       // row_ror:8
+    else if constexpr (O == 4) return __int_as_float(__builtin_amdgcn_ds_swizzle(i, 0x101f));                     // and 0x1f, xor 4
+    else if constexpr (O == 2) return __int_as_float(__builtin_amdgcn_update_dpp(0, i, 0x4e, 0xf, 0xf, false));   // quad_perm [2, 3, 0, 1]
+    else return __int_as_float(__builtin_amdgcn_update_dpp(0, i, 0xb1, 0xf, 0xf, false));                         // quad_perm [1, 0, 3, 2]
+}
 
 // ---- walk ---------------------------------------------------------------------------------------------------------------------
 // ONE COPY for the two kernels below, in the shape of graph_pq_walk.h's: a kernel sets its wave up with f32_walk_setup, then calls
@@ -116,7 +141,7 @@ __device__ __forceinline__ void f32_walk_setup(unsigned char *smem, int wave, in
 // Seeds, then the walk, until `bm`'s list holds no unexpanded node.  ANNLITE_DEBUG_COUNTERS: `n_expand` link lists read, `n_eval`
 // rows evaluated.
 template <class RD, int E, bool L2, class Offer>
-__device__ __forceinline__ void f32_beam_walk(Beam<E, true> &bm, const float *s_q, int lane, const typename RD::row_t *__restrict__ x, int D,
+__device__ __forceinline__ void f32_beam_walk(const RD rd, Beam<E, true> &bm, const float *s_q, int lane, const typename RD::row_t *__restrict__ x, int D,
                                               int64_t N, const uint32_t *__restrict__ links, int lpn, const uint32_t *__restrict__ seeds,
                                               int n_seeds, Offer &&offer, unsigned int &n_expand, unsigned int &n_eval) {
     // ---- seeds, scanned flat (distinct: no visited check; only the ones that made the list are recorded) ----
@@ -124,7 +149,7 @@ __device__ __forceinline__ void f32_beam_walk(Beam<E, true> &bm, const float *s_
         const uint32_t node = s0 + lane < n_seeds ? seeds[s0 + lane] : kEmpty;
         const bool mine = s0 + lane < n_seeds && (int64_t)node < N;
         const unsigned long long pm = __ballot(mine);
-        const float d = RD::template dist<L2>(pm, node, x, D, s_q, lane);
+        const float d = rd.template dist<L2>(pm, node, x, D, s_q, lane);
         n_eval += (unsigned int)__popcll(pm);
         offer(mine, node, f32_to_key(d));
     }
@@ -155,7 +180,7 @@ __device__ __forceinline__ void f32_beam_walk(Beam<E, true> &bm, const float *s_
         bool mine = lane < lpn && (uint32_t)lane < cnt;
         mine = mine && (int64_t)nb < N && bm.visit(nb);
         const unsigned long long pm = __ballot(mine);
-        const float d = RD::template dist<L2>(pm, nb, x, D, s_q, lane);
+        const float d = rd.template dist<L2>(pm, nb, x, D, s_q, lane);
         n_eval += (unsigned int)__popcll(pm);
         offer(mine, nb, f32_to_key(d));
     }
@@ -177,7 +202,7 @@ __global__ __launch_bounds__(256) void graph_f32_search_kernel(const float *__re
                                                               const uint32_t *__restrict__ seeds, int n_seeds,
                                                               const uint32_t *__restrict__ valid, int ef, int hash_bits,
                                                               int64_t *__restrict__ out_ids, float *__restrict__ out_dist,
-                                                              unsigned long long *__restrict__ stats) {
+                                                              unsigned long long *__restrict__ stats, const RD rd) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -188,7 +213,7 @@ __global__ __launch_bounds__(256) void graph_f32_search_kernel(const float *__re
     const float *s_q;
     f32_walk_setup<E>(smem, wave, lane, q, b, D, ef, hash_bits, bm, s_q);
     auto offer = [&](bool mine, uint32_t node, uint32_t key) __attribute__((always_inline)) { bm.offer(mine, node, key); };
-    f32_beam_walk<RD, E, L2>(bm, s_q, lane, x, D, N, links, lpn, seeds, n_seeds, offer, n_expand, n_eval);
+    f32_beam_walk<RD, E, L2>(rd, bm, s_q, lane, x, D, N, links, lpn, seeds, n_seeds, offer, n_expand, n_eval);
     beam_write(bm, b, ef, valid, out_ids, out_dist);
     f32_walk_add_stats(stats, lane, n_expand, n_eval);
 }
@@ -203,7 +228,7 @@ __global__ __launch_bounds__(256) void graph_f32_admit_kernel(const float *__res
                                                              const uint32_t *__restrict__ admit, int ef_route, int ef, int hash_bits,
                                                              int64_t *__restrict__ out_ids, float *__restrict__ out_dist,
                                                              float *__restrict__ out_route_worst,
-                                                             unsigned long long *__restrict__ stats) {
+                                                             unsigned long long *__restrict__ stats, const RD rd) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -216,7 +241,7 @@ __global__ __launch_bounds__(256) void graph_f32_admit_kernel(const float *__res
     AdmitList<E, ER> rl;
     rl.init(bm, ef, n_seeds, admit);
     auto offer_both = [&](bool mine, uint32_t node, uint32_t key) __attribute__((always_inline)) { rl.offer_both(bm, mine, node, key); };
-    f32_beam_walk<RD, E, L2>(bm, s_q, lane, x, D, N, links, lpn, seeds, n_seeds, offer_both, n_expand, n_eval);
+    f32_beam_walk<RD, E, L2>(rd, bm, s_q, lane, x, D, N, links, lpn, seeds, n_seeds, offer_both, n_expand, n_eval);
     rl.write(b, ef, out_ids, out_dist);
     rl.write_route_worst(bm, b, out_route_worst);
     f32_walk_add_stats(stats, lane, n_expand, n_eval);
@@ -230,7 +255,7 @@ constexpr int kPoolMaxF32 = 256;
 // Lane j < n_kept holds the j-th kept neighbour's id; a candidate's test against all of them is one rows_dist with the candidate's
 // row as the common argument.  Wave-uniform control flow.
 template <class RD, bool L2>
-__device__ __forceinline__ void heuristic_select_f32(const typename RD::row_t *__restrict__ x, int D, const uint32_t *s_id, const float *s_tb,
+__device__ __forceinline__ void heuristic_select_f32(const RD rd, const typename RD::row_t *__restrict__ x, int D, const uint32_t *s_id, const float *s_tb,
                                                      int n_pool, int m_max, int lane, uint32_t &kept_id, int &n_kept) {
     kept_id = 0xffffffffu;
     n_kept = 0;
@@ -241,7 +266,7 @@ __device__ __forceinline__ void heuristic_select_f32(const typename RD::row_t *_
         bool closer_to_kept = false;
         if (n_kept) {
             const unsigned long long pm = n_kept >= 64 ? ~0ull : ((1ull << n_kept) - 1ull);
-            const float dk = RD::template dist<L2>(pm, kept_id, x, D, x + (int64_t)id * D, lane);
+            const float dk = rd.template dist<L2>(pm, kept_id, x, D, x + (int64_t)id * D, lane);
             closer_to_kept = lane < n_kept && dk < tb;
         }
         if (__ballot(closer_to_kept) == 0ull) {
@@ -257,7 +282,8 @@ __device__ __forceinline__ void heuristic_select_f32(const typename RD::row_t *_
 template <class RD, bool L2>
 __global__ __launch_bounds__(256) void graph_f32_select_kernel(const int64_t *__restrict__ cand, int ef, int64_t b, int64_t base0,
                                                               const typename RD::row_t *__restrict__ x, int64_t N, int D, int m_keep,
-                                                              uint32_t *__restrict__ links, int lpn, int64_t *__restrict__ pairs) {
+                                                              uint32_t *__restrict__ links, int lpn, int64_t *__restrict__ pairs,
+                                                              const RD rd) {
     __shared__ uint32_t s_all[4][kPoolMaxF32 * 2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * 4 + wave;
@@ -272,7 +298,7 @@ __global__ __launch_bounds__(256) void graph_f32_select_kernel(const int64_t *__
         const int64_t id = t < ef ? cand[i * ef + t] : -1;
         const bool ok = id >= 0 && id < N && (uint32_t)id != base;
         const unsigned long long pm = __ballot(ok);
-        const float d = RD::template dist<L2>(pm, ok ? (uint32_t)id : 0u, x, D, xb, lane);
+        const float d = rd.template dist<L2>(pm, ok ? (uint32_t)id : 0u, x, D, xb, lane);
         if (t < ef) {
             s_id[t] = ok ? (uint32_t)id : 0xffffffffu;
             s_tb[t] = d;
@@ -296,7 +322,7 @@ __global__ __launch_bounds__(256) void graph_f32_select_kernel(const int64_t *__
         n_kept = n_real;
         if (lane < n_kept) kept_id = __float_as_uint(s_tb[lane]);
     } else {
-        heuristic_select_f32<RD, L2>(x, D, s_id, s_tb, ef, m_keep, lane, kept_id, n_kept);
+        heuristic_select_f32<RD, L2>(rd, x, D, s_id, s_tb, ef, m_keep, lane, kept_id, n_kept);
     }
     uint32_t *ll = links + (int64_t)base * (lpn + 1);
     if (lane == 0) ll[0] = (uint32_t)n_kept;
@@ -310,7 +336,7 @@ __global__ __launch_bounds__(256) void graph_f32_select_kernel(const int64_t *__
 template <class RD, bool L2>
 __global__ __launch_bounds__(256) void graph_f32_reverse_kernel(const int64_t *__restrict__ keys, const int64_t *__restrict__ seg, int64_t S,
                                                                const typename RD::row_t *__restrict__ x, int64_t N, int D,
-                                                               uint32_t *__restrict__ links, int lpn) {
+                                                               uint32_t *__restrict__ links, int lpn, const RD rd) {
     __shared__ uint32_t s_all[4][64 * 2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t s = (int64_t)blockIdx.x * 4 + wave;
@@ -346,7 +372,7 @@ __global__ __launch_bounds__(256) void graph_f32_reverse_kernel(const int64_t *_
     }
     // shrink: the pool ordered by its distance to the target (ties: id), then the heuristic to lpn entries
     const unsigned long long in_table = __ballot(v != 0xffffffffu && (int64_t)v < N);
-    float d = RD::template dist<L2>(in_table, v, x, D, x + (int64_t)o * D, lane);
+    float d = rd.template dist<L2>(in_table, v, x, D, x + (int64_t)o * D, lane);
     if (!((in_table >> lane) & 1ull)) d = __builtin_inff();
     const uint32_t dk = v != 0xffffffffu ? f32_to_key(d) : 0xffffffffu;
     int rank = 0;
@@ -360,12 +386,12 @@ __global__ __launch_bounds__(256) void graph_f32_reverse_kernel(const int64_t *_
     asm volatile("" ::: "memory");
     uint32_t kept_id = 0xffffffffu;
     int n_kept = 0;
-    heuristic_select_f32<RD, L2>(x, D, s_id, s_tb, n_pool, lpn, lane, kept_id, n_kept);
+    heuristic_select_f32<RD, L2>(rd, x, D, s_id, s_tb, n_pool, lpn, lane, kept_id, n_kept);
     if (lane < lpn) ll[1 + lane] = lane < n_kept ? kept_id : 0u;
     if (lane == 0) ll[0] = (uint32_t)n_kept;
 }
 
-// ---- host: the four entry points over rows of RD::row_t (`what`: the C entry point's stem, for messages) -------------------------
+// ---- host: the four entry points over rows of RD::row_t; `rd`: the row distance the kernels receive --------------------------------
 extern unsigned long long *g_graph_f32_stats;  // debug only (ANNLITE_DEBUG_COUNTERS): leaked 16-byte device buffer (graph_f32.hip)
 
 // *stats: the float walk's debug counters, zeroed on `st` (NULL unless ANNLITE_DEBUG_COUNTERS)
@@ -415,7 +441,8 @@ static int launch_f32_walk(void (*fn)(KA...), const char *name, int E, int64_t B
 template <class RD>
 static int graph_rows_search(int metric, const float *queries_dev, int64_t B, int64_t D, const typename RD::row_t *vectors_dev, int64_t N,
                              const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
-                             const uint32_t *valid_bits_dev, int ef, int64_t *out_ids_dev, float *out_dist_dev, void *stream) {
+                             const uint32_t *valid_bits_dev, int ef, int64_t *out_ids_dev, float *out_dist_dev, void *stream,
+                             RD rd = RD()) {
     ANNLITE_REQUIRE(B >= 0 && N >= 0 && ef >= 1 && ef <= 256, "bad B=%lld N=%lld ef=%d (ef <= 256)", (long long)B, (long long)N, ef);
     if (int rc = f32_walk_check(metric, queries_dev, B, D, vectors_dev, N, links_dev, links_per_node, seeds_dev, n_seeds, out_ids_dev,
                                 out_dist_dev))
@@ -427,7 +454,7 @@ static int graph_rows_search(int metric, const float *queries_dev, int64_t B, in
     if (int rc = f32_walk_stats(st, &stats)) return rc;
     const bool l2 = metric == ANNLITE_METRIC_EUCLIDEAN;
 #define ANNLITE_WALK_ARGS B, D, hash_bits, st, queries_dev, (int)B, (int)D, vectors_dev, N, links_dev, links_per_node, seeds_dev, (int)n_seeds, \
-                          valid_bits_dev, ef, hash_bits, out_ids_dev, out_dist_dev, stats
+                          valid_bits_dev, ef, hash_bits, out_ids_dev, out_dist_dev, stats, rd
 #define ANNLITE_WALK(EE)                                                                                       \
     (l2 ? launch_f32_walk(graph_f32_search_kernel<RD, EE, true>, "graph_f32_search_kernel", EE, ANNLITE_WALK_ARGS) \
         : launch_f32_walk(graph_f32_search_kernel<RD, EE, false>, "graph_f32_search_kernel", EE, ANNLITE_WALK_ARGS))
@@ -442,7 +469,7 @@ template <class RD>
 static int graph_rows_search_admit(int metric, const float *queries_dev, int64_t B, int64_t D, const typename RD::row_t *vectors_dev,
                                    int64_t N, const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
                                    const uint32_t *admit_bits_dev, int ef_route, int ef, int64_t *out_ids_dev, float *out_dist_dev,
-                                   float *out_route_worst_dev, void *stream) {
+                                   float *out_route_worst_dev, void *stream, RD rd = RD()) {
     ANNLITE_REQUIRE(B >= 0 && N >= 0 && ef >= 1 && ef <= ef_route && ef_route <= 256, "bad B=%lld N=%lld ef=%d ef_route=%d (ef <= ef_route <= 256)",
                     (long long)B, (long long)N, ef, ef_route);
     ANNLITE_REQUIRE(admit_bits_dev != nullptr, "admit_bits_dev is NULL (a walk without a filter is the plain search)");
@@ -456,7 +483,7 @@ static int graph_rows_search_admit(int metric, const float *queries_dev, int64_t
     if (int rc = f32_walk_stats(st, &stats)) return rc;
     const bool l2 = metric == ANNLITE_METRIC_EUCLIDEAN;
 #define ANNLITE_WALK_ARGS B, D, hash_bits, st, queries_dev, (int)B, (int)D, vectors_dev, N, links_dev, links_per_node, seeds_dev, (int)n_seeds, \
-                          admit_bits_dev, ef_route, ef, hash_bits, out_ids_dev, out_dist_dev, out_route_worst_dev, stats
+                          admit_bits_dev, ef_route, ef, hash_bits, out_ids_dev, out_dist_dev, out_route_worst_dev, stats, rd
 #define ANNLITE_WALK(EE, ER)                                                                                      \
     (l2 ? launch_f32_walk(graph_f32_admit_kernel<RD, EE, ER, true>, "graph_f32_admit_kernel", EE, ANNLITE_WALK_ARGS) \
         : launch_f32_walk(graph_f32_admit_kernel<RD, EE, ER, false>, "graph_f32_admit_kernel", EE, ANNLITE_WALK_ARGS))
@@ -471,7 +498,7 @@ static int graph_rows_search_admit(int metric, const float *queries_dev, int64_t
 template <class RD>
 static int graph_rows_build_select(int metric, const int64_t *cand_dev, int ef, int64_t b, int64_t base0,
                                    const typename RD::row_t *vectors_dev, int64_t N, int64_t D, int max_keep, uint32_t *links_dev,
-                                   int links_per_node, int64_t *pairs_dev, void *stream) {
+                                   int links_per_node, int64_t *pairs_dev, void *stream, RD rd = RD()) {
     ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
     ANNLITE_REQUIRE(b >= 0 && base0 >= 0 && ef >= 1 && ef <= kPoolMaxF32, "bad b=%lld base0=%lld ef=%d (ef <= 256)", (long long)b,
                     (long long)base0, ef);
@@ -485,17 +512,17 @@ static int graph_rows_build_select(int metric, const int64_t *cand_dev, int ef, 
     hipStream_t st = (hipStream_t)stream;
     if (metric == ANNLITE_METRIC_EUCLIDEAN)
         hipLaunchKernelGGL((graph_f32_select_kernel<RD, true>), grid, block, 0, st, cand_dev, ef, b, base0, vectors_dev, N, (int)D, max_keep,
-                           links_dev, links_per_node, pairs_dev);
+                           links_dev, links_per_node, pairs_dev, rd);
     else
         hipLaunchKernelGGL((graph_f32_select_kernel<RD, false>), grid, block, 0, st, cand_dev, ef, b, base0, vectors_dev, N, (int)D, max_keep,
-                           links_dev, links_per_node, pairs_dev);
+                           links_dev, links_per_node, pairs_dev, rd);
     return launch_status("graph_f32_select_kernel");
 }
 
 template <class RD>
 static int graph_rows_build_reverse(int metric, const int64_t *keys_dev, const int64_t *seg_dev, int64_t n_segments,
                                     const typename RD::row_t *vectors_dev, int64_t N, int64_t D, uint32_t *links_dev, int links_per_node,
-                                    void *stream) {
+                                    void *stream, RD rd = RD()) {
     ANNLITE_REQUIRE(metric >= 1 && metric <= 3, "bad metric %d", metric);
     ANNLITE_REQUIRE(n_segments >= 0 && N >= 0 && N < (1ll << 32) - 1, "bad n_segments / N");
     ANNLITE_REQUIRE(D >= 1 && D <= 2048, "the float graph takes 1 <= D <= 2048 (D = %lld)", (long long)D);
@@ -506,10 +533,10 @@ static int graph_rows_build_reverse(int metric, const int64_t *keys_dev, const i
     hipStream_t st = (hipStream_t)stream;
     if (metric == ANNLITE_METRIC_EUCLIDEAN)
         hipLaunchKernelGGL((graph_f32_reverse_kernel<RD, true>), grid, block, 0, st, keys_dev, seg_dev, n_segments, vectors_dev, N, (int)D,
-                           links_dev, links_per_node);
+                           links_dev, links_per_node, rd);
     else
         hipLaunchKernelGGL((graph_f32_reverse_kernel<RD, false>), grid, block, 0, st, keys_dev, seg_dev, n_segments, vectors_dev, N, (int)D,
-                           links_dev, links_per_node);
+                           links_dev, links_per_node, rd);
     return launch_status("graph_f32_reverse_kernel");
 }
 

@@ -123,15 +123,19 @@ class AnnLite:
         ``np.float16``; the indexes over PQ codes ignore ``dtype``, as before.  ``np.int8`` with ``int8_scale`` (a power of two, same
         channel; default 1.0, ``2**-7`` for cosine) rides the same way: ``FlatGpuIndex`` then stores int8 codes -- a quarter of the HBM,
         the answer of the f32 index over the rows ``int8_scale * code`` bit for bit, its own filter ``'i8x3'``; the float graph and
-        the cells over floats raise ``NotImplementedError``, the indexes over PQ codes drop both keywords
+        the cells over floats raise ``NotImplementedError`` (their own keywords ``graph_rows='i8'`` / ``ivf_rows='i8'`` opt in), the
+        indexes over PQ codes drop both keywords
     :param ivf_rows: ``'f32'`` (default), ``'f16'`` or ``'i8'`` (kwarg, same channel; ``n_cells > 1`` with ``ivf_prune=True`` and no
         ``n_subvectors``, dropped for every other index): the row store under the cells of ``IvfFlatGpuIndex`` -- ``'f16'`` half-precision
         rows, ``'i8'`` int8 codes of ``int8_scale`` (same channel), each with its own MFMA filter over the cell tiles; ids and distances
         are the f32 cell index's over the stored rows, bit for bit.  Any other value is a ``ValueError``
-    :param graph_rows: ``'f32'`` (default) or ``'f16'`` (kwarg, same channel; ``graph=True, build='gpu'`` without ``n_subvectors``,
-        dropped for every other index): ``'f16'`` keeps the float graph over half-precision rows -- ``HnswFlatGpuIndex`` is then the
-        f16 ``FlatGpuIndex`` with link lists, built and walked a quarter wave per row (``graph_f16.hip``); links, ids and distances
-        are the f32 graph's over the rounded rows, bit for bit.  Any other value is a ``ValueError``
+    :param graph_rows: ``'f32'`` (default), ``'f16'`` or ``'i8'`` (kwarg, same channel; ``graph=True, build='gpu'`` without
+        ``n_subvectors``, dropped for every other index): ``'f16'`` keeps the float graph over half-precision rows --
+        ``HnswFlatGpuIndex`` is then the f16 ``FlatGpuIndex`` with link lists, built and walked a quarter wave per row
+        (``graph_f16.hip``); links, ids and distances are the f32 graph's over the rounded rows, bit for bit.  ``'i8'`` keeps it over
+        int8 codes of ``int8_scale`` (same channel): the int8 ``FlatGpuIndex`` with link lists, built and walked an eighth wave per
+        row (``graph_i8.hip``); links, ids and distances are the f32 graph's over the rows ``int8_scale * code``, bit for bit.
+        Any other value is a ``ValueError``
     :param columns: ``[(name, type), ...]`` (or ``filterable_attrs={name: type}``): the tags a filter may name and have evaluated on
         the device -- ``int`` / ``bool``, ``float`` and ``str`` columns (``ColumnStore``); tags that are not declared stay filterable
         on the host, as before

@@ -233,8 +233,13 @@ def graph_pack_nodes(links: torch.Tensor, codes: torch.Tensor, nodes: torch.Tens
                                          nodes.data_ptr(), nodes.numel(), packed.data_ptr(), stream_ptr()), 'graph_pack_nodes')
 
 
-# ---------------------------------------------------------------------------------------------- float graph (graph_f32.hip, graph_f16.hip)
-def _graph_rows_search(kind: str, rows: torch.dtype, metric, queries, vectors, links, seeds, ef, valid_bits, n_rows):
+# ---------------------------------------------------------------------------------------------- float graph (graph_f32.hip, graph_f16.hip, graph_i8.hip)
+def _rows_args(vectors: torch.Tensor, scale: Optional[float]) -> tuple:
+    """the row pointer as an entry point takes it: int8 rows (``scale`` given) are followed by their scale"""
+    return (vectors.data_ptr(),) if scale is None else (vectors.data_ptr(), float(scale))
+
+
+def _graph_rows_search(kind: str, rows: torch.dtype, metric, queries, vectors, links, seeds, ef, valid_bits, n_rows, scale=None):
     assert queries.dtype == torch.float32 and vectors.dtype == rows and queries.is_contiguous() and vectors.is_contiguous()
     assert links.is_contiguous() and seeds.is_contiguous() and links.element_size() == 4 and seeds.element_size() == 4
     B, D = queries.shape
@@ -244,13 +249,13 @@ def _graph_rows_search(kind: str, rows: torch.dtype, metric, queries, vectors, l
     out_i = torch.empty((B, ef), dtype=torch.int64, device=vectors.device)
     out_d = torch.empty((B, ef), dtype=torch.float32, device=vectors.device)
     fn = getattr(lib(), f'annlite_graph_{kind}_search')
-    check(fn(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, links.data_ptr(), links.shape[1] - 1, seeds.data_ptr(),
+    check(fn(int(metric), queries.data_ptr(), B, D, *_rows_args(vectors, scale), N, links.data_ptr(), links.shape[1] - 1, seeds.data_ptr(),
              seeds.numel(), _ptr(valid_bits), int(ef), out_i.data_ptr(), out_d.data_ptr(), stream_ptr()), f'graph_{kind}_search')
     return out_i, out_d
 
 
 def _graph_rows_search_admit(kind: str, rows: torch.dtype, metric, queries, vectors, links, seeds, ef_route, ef, admit_bits, n_rows,
-                             route_worst):
+                             route_worst, scale=None):
     assert queries.dtype == torch.float32 and vectors.dtype == rows and queries.is_contiguous() and vectors.is_contiguous()
     assert links.is_contiguous() and seeds.is_contiguous() and links.element_size() == 4 and seeds.element_size() == 4
     B, D = queries.shape
@@ -259,31 +264,31 @@ def _graph_rows_search_admit(kind: str, rows: torch.dtype, metric, queries, vect
     assert N <= vectors.shape[0] and N <= links.shape[0]
     out_i, out_d = _admit_walk_outputs(B, ef, N, admit_bits, route_worst, vectors.device)
     fn = getattr(lib(), f'annlite_graph_{kind}_search_admit')
-    check(fn(int(metric), queries.data_ptr(), B, D, vectors.data_ptr(), N, links.data_ptr(), links.shape[1] - 1, seeds.data_ptr(),
+    check(fn(int(metric), queries.data_ptr(), B, D, *_rows_args(vectors, scale), N, links.data_ptr(), links.shape[1] - 1, seeds.data_ptr(),
              seeds.numel(), _ptr(admit_bits), int(ef_route), int(ef), out_i.data_ptr(), out_d.data_ptr(), _ptr(route_worst), stream_ptr()),
           f'graph_{kind}_search_admit')
     return out_i, out_d
 
 
-def _graph_rows_build_select(kind: str, rows: torch.dtype, metric, cand, base0, vectors, max_keep, links, n_rows):
+def _graph_rows_build_select(kind: str, rows: torch.dtype, metric, cand, base0, vectors, max_keep, links, n_rows, scale=None):
     assert cand.dtype == torch.int64 and cand.is_contiguous() and vectors.dtype == rows and vectors.is_contiguous()
     b, ef = cand.shape
     N = vectors.shape[0] if n_rows is None else int(n_rows)
     assert N <= vectors.shape[0] and N <= links.shape[0] and links.is_contiguous() and links.element_size() == 4
     pairs = torch.empty((b, int(max_keep)), dtype=torch.int64, device=vectors.device)
     fn = getattr(lib(), f'annlite_graph_{kind}_build_select')
-    check(fn(int(metric), cand.data_ptr(), int(ef), b, int(base0), vectors.data_ptr(), N, vectors.shape[1], int(max_keep), links.data_ptr(),
+    check(fn(int(metric), cand.data_ptr(), int(ef), b, int(base0), *_rows_args(vectors, scale), N, vectors.shape[1], int(max_keep), links.data_ptr(),
              links.shape[1] - 1, pairs.data_ptr(), stream_ptr()), f'graph_{kind}_build_select')
     return pairs
 
 
-def _graph_rows_build_reverse(kind: str, rows: torch.dtype, metric, keys_sorted, seg, vectors, links, n_rows):
+def _graph_rows_build_reverse(kind: str, rows: torch.dtype, metric, keys_sorted, seg, vectors, links, n_rows, scale=None):
     assert keys_sorted.dtype == torch.int64 and seg.dtype == torch.int64 and keys_sorted.is_contiguous() and seg.is_contiguous()
     assert vectors.dtype == rows and vectors.is_contiguous() and links.is_contiguous() and links.element_size() == 4
     N = vectors.shape[0] if n_rows is None else int(n_rows)
     assert N <= vectors.shape[0] and N <= links.shape[0]
     fn = getattr(lib(), f'annlite_graph_{kind}_build_reverse')
-    check(fn(int(metric), keys_sorted.data_ptr(), seg.data_ptr(), seg.numel() - 1, vectors.data_ptr(), N, vectors.shape[1], links.data_ptr(),
+    check(fn(int(metric), keys_sorted.data_ptr(), seg.data_ptr(), seg.numel() - 1, *_rows_args(vectors, scale), N, vectors.shape[1], links.data_ptr(),
              links.shape[1] - 1, stream_ptr()), f'graph_{kind}_build_reverse')
 
 
@@ -308,7 +313,7 @@ def graph_f32_search_admit(metric: int, queries: torch.Tensor, vectors: torch.Te
 
 
 def graph_f32_search_stats() -> Tuple[int, int]:
-    """(expansions, rows evaluated) of the last float graph walk -- f32 or f16 rows, with or without an admit list
+    """(expansions, rows evaluated) of the last float graph walk -- f32, f16 or int8 rows, with or without an admit list
     (ANNLITE_DEBUG_COUNTERS=1)."""
     out = (ctypes.c_uint64 * 2)()
     check(lib().annlite_graph_f32_search_stats(out), 'graph_f32_search_stats')
@@ -352,6 +357,33 @@ def graph_f16_build_reverse(metric: int, keys_sorted: torch.Tensor, seg: torch.T
                             n_rows: Optional[int] = None):
     """``annlite_graph_f16_build_reverse``: ``graph_f32_build_reverse`` between the rows of ``vectors`` f16 [N, D]."""
     _graph_rows_build_reverse('f16', torch.float16, metric, keys_sorted, seg, vectors, links, n_rows)
+
+
+def graph_i8_search(metric: int, queries: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor, seeds: torch.Tensor, ef: int,
+                    valid_bits: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, *, scale: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_graph_i8_search``: ``graph_f32_search`` over the int8 rows ``vectors`` i8 [N, D], a code ``c`` standing for
+    ``scale * c`` (queries stay f32); ``exact_gather_dist_i8``'s bits -- ``graph_f32_search``'s answer over ``scale * vectors.float()``."""
+    return _graph_rows_search('i8', torch.int8, metric, queries, vectors, links, seeds, ef, valid_bits, n_rows, scale)
+
+
+def graph_i8_search_admit(metric: int, queries: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor, seeds: torch.Tensor,
+                          ef_route: int, ef: int, admit_bits: torch.Tensor, n_rows: Optional[int] = None,
+                          route_worst: Optional[torch.Tensor] = None, *, scale: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_graph_i8_search_admit``: ``graph_f32_search_admit`` over ``vectors`` i8 [N, D] of ``scale``."""
+    return _graph_rows_search_admit('i8', torch.int8, metric, queries, vectors, links, seeds, ef_route, ef, admit_bits, n_rows,
+                                    route_worst, scale)
+
+
+def graph_i8_build_select(metric: int, cand: torch.Tensor, base0: int, vectors: torch.Tensor, max_keep: int, links: torch.Tensor,
+                          n_rows: Optional[int] = None, *, scale: float) -> torch.Tensor:
+    """``annlite_graph_i8_build_select``: ``graph_f32_build_select`` between the rows of ``vectors`` i8 [N, D] of ``scale``."""
+    return _graph_rows_build_select('i8', torch.int8, metric, cand, base0, vectors, max_keep, links, n_rows, scale)
+
+
+def graph_i8_build_reverse(metric: int, keys_sorted: torch.Tensor, seg: torch.Tensor, vectors: torch.Tensor, links: torch.Tensor,
+                           n_rows: Optional[int] = None, *, scale: float):
+    """``annlite_graph_i8_build_reverse``: ``graph_f32_build_reverse`` between the rows of ``vectors`` i8 [N, D] of ``scale``."""
+    _graph_rows_build_reverse('i8', torch.int8, metric, keys_sorted, seg, vectors, links, n_rows, scale)
 
 
 class ScanWorkspace:

@@ -280,6 +280,27 @@ ANNLITE_API int annlite_graph_f16_build_select(int metric, const int64_t *cand_d
                          int64_t *pairs_dev, void *stream);
 ANNLITE_API int annlite_graph_f16_build_reverse(int metric, const int64_t *keys_dev, const int64_t *seg_dev, int64_t n_segments,
                          const void *vectors_f16_dev, int64_t N, int64_t D, uint32_t *links_dev, int links_per_node, void *stream);
+/* ---- the same graph over int8 rows (graph_i8.hip): vectors_i8_dev i8 [N][D], FlatGpuIndex's int8 row store; a code c stands for
+ * scale * c, scale a power of two in [2^-24, 2^24] (behind the row pointer, as in annlite_exact_gather_dist_i8) ---------------------
+ * The four entry points above with the same limits and formats; queries stay f32, and in the build the "query" is itself an int8 row,
+ * widened as it is read.  Every distance carries annlite_exact_gather_dist_i8's bits -- the f32 entry points' answer over the rows
+ * scale * c, bit for bit; nothing is computed in code units.  Where D % 8 == 0 (and the table is 8-byte aligned) an EIGHTH wave
+ * evaluates a row: 8 lanes, eight of the 64 chains per lane (one 8-byte load per block of 64 elements), eight rows per wave-wide pass,
+ * up to 32 rows in flight; every other D takes the lane-strided loop of the f32 form with one-byte loads.
+ * annlite_graph_f32_search_stats reports these walks as well. */
+ANNLITE_API int annlite_graph_i8_search(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev, float scale,
+                         int64_t N, const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev, int64_t n_seeds,
+                         const uint32_t *valid_bits_dev, int ef, int64_t *out_ids_dev, float *out_dist_dev, void *stream);
+ANNLITE_API int annlite_graph_i8_search_admit(int metric, const float *queries_dev, int64_t B, int64_t D, const void *vectors_i8_dev,
+                         float scale, int64_t N, const uint32_t *links_dev, int links_per_node, const uint32_t *seeds_dev,
+                         int64_t n_seeds, const uint32_t *admit_bits_dev, int ef_route, int ef, int64_t *out_ids_dev,
+                         float *out_dist_dev, float *out_route_worst_dev, void *stream);
+ANNLITE_API int annlite_graph_i8_build_select(int metric, const int64_t *cand_dev, int ef, int64_t b, int64_t base0,
+                         const void *vectors_i8_dev, float scale, int64_t N, int64_t D, int max_keep, uint32_t *links_dev,
+                         int links_per_node, int64_t *pairs_dev, void *stream);
+ANNLITE_API int annlite_graph_i8_build_reverse(int metric, const int64_t *keys_dev, const int64_t *seg_dev, int64_t n_segments,
+                         const void *vectors_i8_dev, float scale, int64_t N, int64_t D, uint32_t *links_dev, int links_per_node,
+                         void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Batched flat ADC scan + top-k: the hot path.

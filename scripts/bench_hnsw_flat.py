@@ -9,6 +9,11 @@ ef_search 64 / 128 / 192 on one and two caller streams, FlatGpuIndex on the same
 rounded to f16 -- the f32 index stores the rounded values, so both graphs, all answers and all counters are identical (checked); the two
 indexes alternate inside every measurement, in one process, and each one's figures are reported side by side under ``f32`` / ``f16``.
 
+``--graph-rows i8``: the graph over int8 rows (``graph_rows='i8'``, int8_scale 1.0: give the data a ``--data-scale``).  ``all``: an f32,
+an f16 and an int8 index over the SAME data rounded to whole code steps in [-127, 127] -- values all three store exactly --, checked and
+measured like ``both``, under ``f32`` / ``f16`` / ``i8``.  ``--data-scale S``: rows and queries are scaled so that a coordinate's
+standard deviation is S code steps.  With ``i8`` / ``all`` recall@10 is against the exact search over the UNROUNDED rows.
+
 Data: scripts/bench_hnsw.py's generator (a 16-d latent mixed into D dimensions + noise, the same seeds), EUCLIDEAN.
 """
 import argparse
@@ -33,7 +38,8 @@ p.add_argument('--ef-search', type=int, nargs='+', default=[64, 128, 192])
 p.add_argument('--ef-construction', type=int, default=200)
 p.add_argument('--max-connection', type=int, default=16)
 p.add_argument('--steps', type=int, default=5)
-p.add_argument('--graph-rows', choices=['f32', 'f16', 'both'], default='f32')
+p.add_argument('--graph-rows', choices=['f32', 'f16', 'i8', 'both', 'all'], default='f32')
+p.add_argument('--data-scale', type=float, default=None, help="a coordinate's standard deviation in int8 code steps (default: unscaled)")
 a = p.parse_args()
 dev = torch.device('cuda', 0)
 torch.cuda.set_device(0)
@@ -43,24 +49,27 @@ g = torch.Generator(device=dev)
 g.manual_seed(99)
 A = torch.randn((r_lat, D), generator=g, device=dev)
 CH = 250_000
+MUL = 1.0 if a.data_scale is None else a.data_scale / (r_lat + 0.0025) ** 0.5  # (a coordinate of z @ A + 0.05 e has variance r_lat + 0.0025)
 
 
-def gen(chunk, rows):
+def gen(chunk, rows, rounded=True):
     gg = torch.Generator(device=dev)
     gg.manual_seed(1234 + chunk)
     z = torch.randn((rows, r_lat), generator=gg, device=dev)
     e = torch.randn((rows, D), generator=gg, device=dev)
-    x = (z @ A + 0.05 * e).contiguous()
-    return x.half().float() if a.graph_rows == 'both' else x
+    x = ((z @ A + 0.05 * e) * MUL).contiguous()
+    if rounded and a.graph_rows == 'all':
+        return torch.round(x).clamp_(-127.0, 127.0)
+    return x.half().float() if rounded and a.graph_rows == 'both' else x
 
 
 def queries(seed):
     gq = torch.Generator(device=dev)
     gq.manual_seed(seed)
-    return (torch.randn((B, r_lat), generator=gq, device=dev) @ A + 0.05 * torch.randn((B, D), generator=gq, device=dev)).contiguous()
+    return ((torch.randn((B, r_lat), generator=gq, device=dev) @ A + 0.05 * torch.randn((B, D), generator=gq, device=dev)) * MUL).contiguous()
 
 
-kinds = ['f32', 'f16'] if a.graph_rows == 'both' else [a.graph_rows]
+kinds = {'both': ['f32', 'f16'], 'all': ['f32', 'f16', 'i8']}.get(a.graph_rows, [a.graph_rows])
 indexes, build_s = {}, {}
 for kind in kinds:
     index = HnswFlatGpuIndex(D, metric=Metric.EUCLIDEAN, initial_size=N, ef_search=a.ef_search[0], ef_construction=a.ef_construction,
@@ -73,14 +82,22 @@ for kind in kinds:
     torch.cuda.synchronize()
     indexes[kind], build_s[kind] = index, time.time() - t0
 index = indexes[kinds[0]]
-if len(kinds) == 2:
-    assert torch.equal(indexes['f32']._gg.links[:N], indexes['f16']._gg.links[:N]), 'the two graphs differ'
+for kind in kinds[1:]:
+    assert torch.equal(index._gg.links[:N], indexes[kind]._gg.links[:N]), f'the {kinds[0]} and the {kind} graph differ'
 
 q, q_alt = queries(4321), queries(4321 + 7919)
 q_rot = [q, q_alt]  # the timed steps rotate through two query batches (recall is the first batch's)
 side = [torch.cuda.Stream(device=dev) for _ in range(2)]
-# exact truth: the index's own exhaustive search (FlatGpuIndex.search_batch on the same rows)
-truth = index.search_exhaustive(q, limit=k)[1].cpu().numpy()
+# exact truth: the index's own exhaustive search (FlatGpuIndex.search_batch on the same rows); with int8 rows: over the UNROUNDED rows
+if 'i8' in kinds:
+    best_d, best_i = torch.full((B, k), float('inf'), device=dev), torch.full((B, k), -1, device=dev, dtype=torch.int64)
+    for c in range((N + CH - 1) // CH):
+        d, i = torch.topk(torch.cdist(q, gen(c, min(CH, N - c * CH), rounded=False)), k, dim=1, largest=False)
+        best_d, pick = torch.topk(torch.cat([best_d, d], 1), k, dim=1, largest=False)
+        best_i = torch.gather(torch.cat([best_i, i + c * CH], 1), 1, pick)
+    truth = best_i.cpu().numpy()
+else:
+    truth = index.search_exhaustive(q, limit=k)[1].cpu().numpy()
 
 
 def recall(ids):
@@ -151,9 +168,9 @@ for ef in a.ef_search:
     for kind in kinds:
         cnt[kind] = counters(indexes[kind], qd, ef)
     ms = walk_ms(qd, ef)
-    if len(kinds) == 2:
-        assert cnt['f32'] == cnt['f16'], ('the two walks counted differently', cnt)
-        assert all(torch.equal(u, v) for u, v in zip(ans['f32'], ans['f16'])), 'the two indexes answer differently'
+    for kind in kinds[1:]:
+        assert cnt[kinds[0]] == cnt[kind], ('the walks counted differently', cnt)
+        assert all(torch.equal(u, v) for u, v in zip(ans[kinds[0]], ans[kind])), f'the {kinds[0]} and the {kind} index answer differently'
     for kind in kinds:
         n_expand, n_eval = cnt[kind]
         row_bytes = n_eval * D * float(indexes[kind]._vectors.element_size())  # the gathered rows (seed rows included)
@@ -177,4 +194,4 @@ print(json.dumps({'config': f'float HNSW (level 0, GPU-built): {N} x {D}-dim, gr
                   'metric': 'queries/sec', 'unit': 'queries/s', 'value': first['queries_per_s_two_streams'],
                   'recall_at_10': first['recall_at_10'], 'mean_links_per_node': float(links.mean().item()),
                   'flat_exact_queries_per_s_one_stream': flat_qps1, 'flat_exact_queries_per_s_two_streams': flat_qps2,
-                  'steps': max(a.steps, 2), 'query_batches': 2, **(per_kind if len(kinds) == 2 else per_kind[kinds[0]])}))
+                  'steps': max(a.steps, 2), 'query_batches': 2, **(per_kind if len(kinds) > 1 else per_kind[kinds[0]])}))
