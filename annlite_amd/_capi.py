@@ -89,6 +89,12 @@ SYMBOLS = (
     'annlite_exact_gather_dist_f16',
     'annlite_exact_gather_dist_i8',
     'annlite_ivf_select_cells',
+    'annlite_vq_assign_workspace_bytes',
+    'annlite_vq_assign',
+    'annlite_vq_assign_undecided',
+    'annlite_vq_assign_slack',
+    'annlite_vq_cell_sums_workspace_bytes',
+    'annlite_vq_cell_sums',
     'annlite_ivf_max_tiles',
     'annlite_ivf_plan',
     'annlite_ivf_max_tiles_first',
@@ -304,6 +310,12 @@ def lib() -> ctypes.CDLL:
     L.annlite_exact_gather_dist_i8.argtypes = [i32, vp, i64, i64, vp, ctypes.c_float, i64, vp, i64, vp, vp]
     L.annlite_codes_skew.argtypes = [vp, i64, i64, vp, i64, vp, i32, vp]
     L.annlite_ivf_select_cells.argtypes = [i32, vp, i64, i64, vp, i64, i64, vp, vp]
+    L.annlite_vq_assign_workspace_bytes.argtypes = [i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_vq_assign.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp]
+    L.annlite_vq_assign_undecided.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_vq_assign_slack.argtypes = [i64, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    L.annlite_vq_cell_sums_workspace_bytes.argtypes = [i64, i64, i64, ctypes.POINTER(ctypes.c_int64)]
+    L.annlite_vq_cell_sums.argtypes = [vp, i64, i64, vp, vp, i64, vp, vp, vp, vp]
     L.annlite_ivf_max_tiles.argtypes = [i64, i64, i64, i64]
     L.annlite_ivf_plan.argtypes = [vp, i64, i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp]
     L.annlite_ivf_max_tiles_first.argtypes = [i64, i64, i64, i64]

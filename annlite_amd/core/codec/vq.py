@@ -7,6 +7,11 @@ Training is statistical parity only (unseeded sklearn in the reference); seedabl
 
 The assignment step runs on the GPU (``annlite_ivf_select_cells`` with one probe); the centroid update is a
 scatter-add (plumbing).  No CPU fallback.
+
+``assign`` (an attribute, used like ``seed``): ``'chain'`` (default) is that path; ``'mfma'`` assigns through ``annlite_vq_assign`` --
+the same cells bit for bit, from f32 MFMA tiles with the chain's arithmetic only for the rows a proven slack leaves undecided
+(``last_assign_undecided`` counts them) -- and takes the sums and counts of ``fit`` / ``partial_fit`` from ``annlite_vq_cell_sums``,
+which has no float atomics: with a ``seed``, ``fit`` then returns the same bits every run.  DESIGN.md section 3.11.
 """
 from typing import Optional
 
@@ -18,8 +23,25 @@ from ...enums import Metric
 from .base import BaseCodec
 
 
+ASSIGN_PATHS = ('chain', 'mfma')
+
+
 def _is_np(x) -> bool:
     return isinstance(x, np.ndarray)
+
+
+def vq_assign_slack_constants(dim: int):
+    """``vq_slack`` of vq.hip restated: ``(c_rel, c_abs)`` as float32."""
+    u = 2.0 ** -24
+    nl = (dim + 63) // 64
+    return np.float32(1.05 * u * (3.0 * dim + nl + 24.0)), np.float32(1e-30)
+
+
+def vq_assign_slack(dim: int, x_norm, c_norm):
+    """eps(row, cell) as ``vq_assign_kernel`` evaluates it, ``fl(fl(c_rel |x|^2) + fl(fl(c_rel |c|^2) + c_abs))`` over float32 norms:
+    a bound of ``|fl(|c|^2 - 2 dot) + |x|^2 - chain|``, chain = the j-ascending ``fmaf`` sum of ``(c_j - x_j)^2``."""
+    c_rel, c_abs = vq_assign_slack_constants(dim)
+    return np.float32(c_rel * np.float32(x_norm)) + np.float32(np.float32(c_rel * np.float32(c_norm)) + c_abs)
 
 
 class VQCodec(BaseCodec):
@@ -30,6 +52,7 @@ class VQCodec(BaseCodec):
         self.iter = int(iter)
         self.n_init = int(n_init)
         self.seed: Optional[int] = None
+        self.assign = 'chain'
         self._codebook: Optional[np.ndarray] = None
         self._cb_dev = {}
         self._sums = None  # partial_fit accumulators (device)
@@ -42,6 +65,8 @@ class VQCodec(BaseCodec):
     def __getstate__(self):
         st = self.__dict__.copy()
         st['_cb_dev'] = {}
+        st.pop('_assign_ws', None)
+        st.pop('_sums_ws', None)
         for key in ('_sums', '_counts', '_pf_cb'):
             if st.get(key) is not None:
                 st[key] = st[key].cpu().numpy()
@@ -51,9 +76,26 @@ class VQCodec(BaseCodec):
         self.__dict__.update(st)
         if not isinstance(self.__dict__.get('_cb_dev'), dict):  # (files written before the per-device cache)
             self._cb_dev = {}
+        self.__dict__.setdefault('_assign_path', 'chain')  # (files written before there was a choice)
         for key in ('_sums', '_counts', '_pf_cb'):
             if isinstance(getattr(self, key, None), np.ndarray):
                 setattr(self, key, None)  # streaming state does not survive a reload (codebook does)
+
+    @property
+    def assign(self) -> str:
+        return self._assign_path
+
+    @assign.setter
+    def assign(self, value):
+        if value not in ASSIGN_PATHS:
+            raise ValueError(f"assign={value!r}: 'chain' (annlite_ivf_select_cells with one probe) or 'mfma' (annlite_vq_assign)")
+        self._assign_path = value
+
+    @property
+    def last_assign_undecided(self) -> int:
+        """rows of the last ``'mfma'`` assignment on the current stream that the chain's arithmetic answered (0 before the first)"""
+        ws = self.__dict__.get('_assign_ws')
+        return 0 if ws is None else ops.vq_assign_undecided(ws)
 
     # ------------------------------------------------------------------ device views
     @property
@@ -76,17 +118,38 @@ class VQCodec(BaseCodec):
         self._is_trained = True
 
     # ------------------------------------------------------------------ training
-    @staticmethod
-    def _assign(x: torch.Tensor, cb: torch.Tensor) -> torch.Tensor:
+    def _workspace(self, name: str) -> 'ops.ScanWorkspace':
+        """A device scratch buffer kept on the codec (not pickled).  It stays as large as its largest call: the assignment's holds
+        4 N + 8 C bytes per stream (40 MB after 10M rows), the sums' 8 C bytes and the chunk totals of long cells."""
+        ws = self.__dict__.get(name)
+        if ws is None:
+            ws = self.__dict__[name] = ops.ScanWorkspace()
+        return ws
+
+    def _assign_cells(self, x: torch.Tensor, cb: torch.Tensor) -> torch.Tensor:
+        """the cell of every row, in the dtype the path produces (i32 under ``'mfma'``: what ``_cell_sums`` sorts)"""
+        if self._assign_path == 'mfma':
+            return ops.vq_assign(x, cb, self._workspace('_assign_ws'))
         return ops.ivf_select_cells(0, x, cb, 1)[:, 0].to(torch.int64)
+
+    def _assign(self, x: torch.Tensor, cb: torch.Tensor) -> torch.Tensor:
+        return self._assign_cells(x, cb).to(torch.int64)
+
+    def _cell_sums(self, x: torch.Tensor, a: torch.Tensor, C: int):
+        """(sums f32 [C, D], counts f32 [C]) of the assignment ``a``"""
+        if self._assign_path == 'mfma':
+            sums, counts = ops.vq_cell_sums(x, a, C, self._workspace('_sums_ws'))
+            return sums, counts.to(torch.float32)
+        sums = torch.zeros((C, x.shape[1]), dtype=torch.float32, device=x.device).index_add_(0, a, x)
+        counts = torch.zeros((C,), dtype=torch.float32, device=x.device).index_add_(
+            0, a, torch.ones_like(a, dtype=torch.float32))
+        return sums, counts
 
     def _lloyd_step(self, x: torch.Tensor, cb: torch.Tensor):
         """one assignment + update; returns (new centres, counts, inertia)"""
-        a = self._assign(x, cb)
+        a = self._assign_cells(x, cb)
         C, D = cb.shape
-        sums = torch.zeros((C, D), dtype=torch.float32, device=x.device).index_add_(0, a, x)
-        counts = torch.zeros((C,), dtype=torch.float32, device=x.device).index_add_(
-            0, a, torch.ones_like(a, dtype=torch.float32))
+        sums, counts = self._cell_sums(x, a, C)
         new = torch.where(counts[:, None] > 0, sums / counts.clamp(min=1.0)[:, None], cb)
         inertia = ((x - cb[a]) ** 2).sum()
         return new, counts, inertia
@@ -167,9 +230,14 @@ class VQCodec(BaseCodec):
             self._pf_cb = x[torch.randperm(x.shape[0], generator=gen, device=x.device)[:C]].clone()
             self._sums = torch.zeros_like(self._pf_cb)
             self._counts = torch.zeros((C,), dtype=torch.float32, device=x.device)
-        a = self._assign(x, self._pf_cb)
-        self._sums.index_add_(0, a, x)
-        self._counts.index_add_(0, a, torch.ones_like(a, dtype=torch.float32))
+        a = self._assign_cells(x, self._pf_cb)
+        if self._assign_path == 'mfma':
+            sums, counts = self._cell_sums(x, a, C)
+            self._sums += sums
+            self._counts += counts
+        else:
+            self._sums.index_add_(0, a, x)
+            self._counts.index_add_(0, a, torch.ones_like(a, dtype=torch.float32))
         self._pf_cb = torch.where(self._counts[:, None] > 0, self._sums / self._counts.clamp(min=1.0)[:, None], self._pf_cb)
 
     def build_codebook(self):

@@ -136,6 +136,9 @@ class AnnLite:
         int8 codes of ``int8_scale`` (same channel): the int8 ``FlatGpuIndex`` with link lists, built and walked an eighth wave per
         row (``graph_i8.hip``); links, ids and distances are the f32 graph's over the rows ``int8_scale * code``, bit for bit.
         Any other value is a ``ValueError``
+    :param vq_assign: ``'chain'`` (default) or ``'mfma'`` (kwarg; ``n_cells > 1``, ignored without a cell codec): how the ``VQCodec`` this
+        index creates or loads assigns rows to cells -- ``annlite_ivf_select_cells`` with one probe, or ``annlite_vq_assign`` on f32 MFMA
+        tiles with per-cell sums free of float atomics in ``train``; the same cells bit for bit.  Any other value is a ``ValueError``
     :param columns: ``[(name, type), ...]`` (or ``filterable_attrs={name: type}``): the tags a filter may name and have evaluated on
         the device -- ``int`` / ``bool``, ``float`` and ``str`` columns (``ColumnStore``); tags that are not declared stay filterable
         on the host, as before
@@ -241,6 +244,9 @@ class AnnLite:
         else:
             self._pq_codec = PQCodec(dim=self._index_dim, n_subvectors=n_subvectors, n_clusters=n_clusters, metric=metric)
 
+        vq_assign = kwargs.pop('vq_assign', 'chain')
+        if vq_assign not in ('chain', 'mfma'):
+            raise ValueError(f"vq_assign={vq_assign!r}: 'chain' or 'mfma'")
         self._vq_codec = None
         if n_cells > 1:  # index.py:125-133
             from .core.codec.vq import VQCodec
@@ -250,6 +256,7 @@ class AnnLite:
                 self._vq_codec = VQCodec.load(self._vq_codec_path)
             else:
                 self._vq_codec = VQCodec(self.n_cells, metric=self.metric)
+            self._vq_codec.assign = vq_assign
 
         if columns is not None:
             filterable_attrs = {n: t for n, t in (columns.items() if isinstance(columns, dict) else columns)}

@@ -545,6 +545,54 @@ def ivf_select_cells(kind: int, queries: torch.Tensor, centroids: torch.Tensor, 
     return cells
 
 
+def vq_assign(rows: torch.Tensor, centroids: torch.Tensor, workspace: Optional[ScanWorkspace] = None) -> torch.Tensor:
+    """``annlite_vq_assign``: i32 [N], the nearest centroid of every row in squared L2 -- ``ivf_select_cells(0, rows, centroids, 1)[:, 0]``
+    bit for bit, on f32 MFMA tiles with the chain's arithmetic for the rows the slack leaves undecided.
+    ``vq_assign_undecided(workspace)`` reads how many those were."""
+    assert rows.dtype == torch.float32 and centroids.dtype == torch.float32 and rows.is_contiguous() and centroids.is_contiguous()
+    N, D = rows.shape
+    C = centroids.shape[0]
+    assert centroids.shape[1] == D
+    ws = _flat_workspace('vq_assign_workspace_bytes', (N, D, C), rows.device, workspace)
+    cells = torch.empty((N,), dtype=torch.int32, device=rows.device)
+    check(lib().annlite_vq_assign(rows.data_ptr(), N, D, centroids.data_ptr(), C, cells.data_ptr(), ws.data_ptr(), stream_ptr()), 'vq_assign')
+    return cells
+
+
+def vq_assign_undecided(workspace: ScanWorkspace) -> int:
+    """Rows of the last ``vq_assign`` on this stream's workspace buffer that the second launch answered."""
+    buf = workspace.bufs.get(stream_ptr())
+    if buf is None:
+        return 0
+    n = ctypes.c_int64(0)
+    check(lib().annlite_vq_assign_undecided(buf.data_ptr(), stream_ptr(), ctypes.byref(n)), 'vq_assign_undecided')
+    return int(n.value)
+
+
+def vq_assign_slack(dim: int) -> Tuple[np.float32, np.float32]:
+    """``annlite_vq_assign_slack``: the ``(c_rel, c_abs)`` the assignment kernel is launched with (host only, needs no GPU)."""
+    c_rel, c_abs = ctypes.c_float(0), ctypes.c_float(0)
+    check(lib().annlite_vq_assign_slack(int(dim), ctypes.byref(c_rel), ctypes.byref(c_abs)), 'vq_assign_slack')
+    return np.float32(c_rel.value), np.float32(c_abs.value)
+
+
+def vq_cell_sums(rows: torch.Tensor, cells: torch.Tensor, n_cells: int,
+                 workspace: Optional[ScanWorkspace] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``annlite_vq_cell_sums``: ``(sums f32 [C, D], counts i32 [C])`` of the rows of every cell of the assignment ``cells`` i32 [N]
+    (ids in [0, C)), every sum taken in float64 in a fixed order and rounded once -- no float atomics, the same bits every call.
+    The stable sort of the assignment is torch's (plumbing)."""
+    assert rows.dtype == torch.float32 and rows.is_contiguous() and cells.dtype == torch.int32 and cells.numel() == rows.shape[0]
+    N, D = rows.shape
+    C = int(n_cells)
+    sorted_cells, perm = torch.sort(cells, stable=True)
+    ws = _flat_workspace('vq_cell_sums_workspace_bytes', (N, D, C), rows.device, workspace)
+    sums = torch.empty((C, D), dtype=torch.float32, device=rows.device)
+    counts = torch.empty((C,), dtype=torch.int32, device=rows.device)
+    check(lib().annlite_vq_cell_sums(rows.data_ptr(), N, D, sorted_cells.data_ptr(), perm.data_ptr(), C, sums.data_ptr(), counts.data_ptr(),
+                                     ws.data_ptr(), stream_ptr()), 'vq_cell_sums')
+    return sums, counts
+
+
 def ivf_max_tiles(B: int, P: int, C: int, qt: int) -> int:
     return int(lib().annlite_ivf_max_tiles(B, P, C, qt))
 

@@ -922,6 +922,33 @@ ANNLITE_API int annlite_ivf_flat_search_topk_wide_i8(int metric, const float *qu
 ANNLITE_API int annlite_ivf_select_cells(int kind, const float *queries_dev, int64_t B, int64_t D,
                              const float *centroids_dev, int64_t C, int64_t P, int32_t *cells_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The coarse quantiser's own kernels (vq.hip): VQCodec(assign='mfma').
+ * ---------------------------------------------------------------------------------------------- */
+/* cells[i] = the nearest centroid of row i in squared L2: annlite_ivf_select_cells(0, rows, ..., P = 1), bit for bit (the first
+ * minimum of the j-ascending fmaf chain of (c_j - x_j)^2), for tables: 128 rows x blocks of 128 centroids per workgroup on f32 MFMA,
+ * the rows whose gap the slack cannot cover (annlite_vq_assign_slack) answered by a second launch in the chain's arithmetic.
+ *   rows_dev f32 [N][D], centroids_dev f32 [C][D]; 1 <= C <= 65536, 1 <= D <= 32768, N < 2^31 (no C + D limit)
+ *   workspace_dev: annlite_vq_assign_workspace_bytes(N, D, C) bytes, 16-byte aligned
+ *   rows_dev / centroids_dev need no alignment beyond a float's: 16-byte loads are taken only where D % 4 == 0 and the pointer allows
+ * Three launches on `stream`, no host round trip.  annlite_vq_assign_undecided(workspace) reads how many rows the second launch
+ * answered (it synchronises the stream). */
+ANNLITE_API int annlite_vq_assign_workspace_bytes(int64_t N, int64_t D, int64_t C, int64_t *bytes);
+ANNLITE_API int annlite_vq_assign(const float *rows_dev, int64_t N, int64_t D, const float *centroids_dev, int64_t C, int32_t *cells_dev,
+                      void *workspace_dev, void *stream);
+ANNLITE_API int annlite_vq_assign_undecided(const void *workspace_dev, void *stream, int64_t *count);
+/* eps(row, cell) = c_rel (|x|^2 + |c|^2) + c_abs bounds |fl(|c|^2 - 2 dot) + |x|^2 - chain| (host only, needs no GPU). */
+ANNLITE_API int annlite_vq_assign_slack(int64_t D, float *c_rel, float *c_abs);
+
+/* The update half of a Lloyd step without float atomics: sums f32 [C][D] and counts i32 [C] of the rows of every cell.
+ *   sorted_cells_dev i32 [N]  the assignment in ASCENDING order (ids in [0, C))
+ *   perm_dev         i64 [N]  the row of every sorted position, from a STABLE sort (the rows of a cell ascend)
+ * Every sum is taken in float64 in an order fixed by (N, the assignment) alone and rounded to f32 once: two calls give the same bits.
+ *   workspace_dev: annlite_vq_cell_sums_workspace_bytes(N, D, C) bytes, 16-byte aligned */
+ANNLITE_API int annlite_vq_cell_sums_workspace_bytes(int64_t N, int64_t D, int64_t C, int64_t *bytes);
+ANNLITE_API int annlite_vq_cell_sums(const float *rows_dev, int64_t N, int64_t D, const int32_t *sorted_cells_dev, const int64_t *perm_dev,
+                         int64_t C, float *sums_dev, int32_t *counts_dev, void *workspace_dev, void *stream);
+
 /* Upper bound of the query tiles annlite_ivf_plan can produce (qt = tile size of the scan plan). */
 ANNLITE_API int64_t annlite_ivf_max_tiles(int64_t B, int64_t P, int64_t C, int64_t qt);
 
